@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: binned-likelihood evaluations per second on the BASELINE.json model.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C4-dense|C5|C5-2anchor]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full] [--config C2|C3|C4|C4-dense|C5|C5-2anchor]
 
 Default workload (BASELINE.json configs[1], "C2"): 4 sources, 3 shape parameters with 5 anchors each (125 anchor
 models), 100x100x100 analysis bins; the anchor tensor (4.0 GB fp64) and the data are resident in HBM before the
@@ -26,10 +26,15 @@ device planner's sort, inside the timed step), 10^4 toy datasets split by range 
 points on a grid cell of configs[4] -- run as STRONG-scaling legs behind the headline on every N and are reported under
 "legs" (fixed total work, gather inside the timed region, cross-rank consistency asserted on a sample).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, the read-back check of
+the timed results).  --dump-outputs DIR also writes what the last timed step computed: DIR/loglikelihood.npy, float64
+[ranks, evaluations per step], the results a caller of the batched call receives (seeded inputs: the same arguments give
+the same inputs on every run).  With --full (--no-legs / --no-extras / --no-cpu-baseline leave parts of it out) the JSON
+line also carries
   roofline      morph+reduce kernel: algorithmic bytes per launch / HIP-event kernel time vs 8 TB/s, the measured
                 stream ceiling of the same access pattern, PMC traffic from profiles/
-  cpu_baseline  the numpy/scipy oracle (the reference's arithmetic) timed on the host, rank 0, N = 1
+  cpu_baseline  the numpy/scipy oracle (the reference's arithmetic) timed on the host, rank 0, N = 1; evaluation 0 of
+                timed step 0 checked against it
   legs          C4 / C4-dense / C3 / C5-BB (every N; C5-BB carries the Beeston-Barlow kernel's own roofline); unbinned (N = 1)
   extras        other call shapes of the same path (N = 1)
 """
@@ -894,6 +899,10 @@ def main():
     ap.add_argument('--warmup', type=int, default=40)
     ap.add_argument('--config', default='C2', help='C2 (headline) | C3 | C4 | C4-dense | C5 | C5-2anchor: the leg that '
                                                     'becomes the JSON line')
+    ap.add_argument('--full', action='store_true', help='C2: after the headline also the roofline, the strong-scaling legs, '
+                                                        'the extras and the CPU baseline with its oracle check')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='C2: write the results of the last timed step as DIR/loglikelihood.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extras', action='store_true')
     ap.add_argument('--no-legs', action='store_true')
@@ -905,6 +914,10 @@ def main():
                                                     '(default rank r -> GPU r; "0,0" rehearses two ranks on one GPU)')
     ap.add_argument('--dry', action='store_true', help='no GPU: launch, rendezvous, dealing and gather only (tests)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs and args.config != 'C2':
+        ap.error('--dump-outputs: the headline (--config C2) only')
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))          # before anything touches the GPU: the ranks are fresh processes
@@ -1056,6 +1069,36 @@ def main():
         # every rank evaluated different points: finite everywhere, and this rank's row is what it computed
         assert gathered.shape == (world, K * PPS) and np.all(np.isfinite(gathered)), 'gathered results are not finite'
         np.testing.assert_array_equal(gathered[rank], timed_out.reshape(-1))
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results of every rank, as the batched call leaves them: [ranks, evaluations per step]
+        last = gathered[:, (K - 1) * PPS:] if gathered is not None else timed_out[K - 1:]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'loglikelihood.npy'), np.ascontiguousarray(last, dtype=np.float64))
+
+    headline = None
+    if rank == 0:
+        headline = {
+            'metric': METRIC,
+            'value': world * K * PPS / elapsed, 'unit': 'evals/s', 'n_gpus': world, 'steps': K, 'warmup': W,
+            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'C2: 4 sources, 3 shape params (5^3 anchors), 100^3 bins; step = one batched call '
+                                   '(one kernel launch) of %d independent dense evaluations, each against its own '
+                                   'dataset, in grid cells that share no anchor (no byte re-used), tensor '
+                                   'replicated per GPU' % PPS,
+                       'sources': model.S, 'anchors': list(model.n_anchor), 'bins': list(model.bins),
+                       'evals_per_step': PPS, 'device': info['arch'], 'gather': ranks.kind,
+                       'host_threads_per_rank': threads},
+        }
+    if not args.full:
+        # a plain run: the headline and the check of its own results; everything below is --full
+        if rank == 0:
+            headline.update(outputs)
+        for p in plans:
+            p.close()
+        emit(headline)
+        leave()
+        return
 
     # kernel time of the same steps, HIP events on the context stream around every launch
     ctx.profile(True)
@@ -1091,18 +1134,7 @@ def main():
 
     result = None
     if rank == 0:
-        result = {
-            'metric': METRIC,
-            'value': world * K * PPS / elapsed, 'unit': 'evals/s', 'n_gpus': world, 'steps': K, 'warmup': W,
-            'ms_per_step': elapsed / K * 1e3, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'C2: 4 sources, 3 shape params (5^3 anchors), 100^3 bins; step = one batched call '
-                                   '(one kernel launch) of %d independent dense evaluations, each against its own '
-                                   'dataset, in grid cells that share no anchor (no byte re-used), tensor '
-                                   'replicated per GPU' % PPS,
-                       'sources': model.S, 'anchors': list(model.n_anchor), 'bins': list(model.bins),
-                       'evals_per_step': PPS, 'device': info['arch'], 'gather': ranks.kind,
-                       'host_threads_per_rank': threads},
+        result = dict(headline, **{
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic, 'traffic_source': traffic_src,
                          'kernel': 'k_morph_reduce<1,false,true> (G=1, no BB, nontemporal loads, in-launch finish)',
@@ -1115,7 +1147,7 @@ def main():
                                          'linear_read_ceiling: one linear 16-byte-load sum over the 4 GB tensor; '
                                          'copy_ceiling: bytes read + written per second of a 2 GiB device-to-device '
                                          'hipMemcpy; all in this process' % (PPS, NS)},
-        }
+        })
 
     # ---- strong-scaling legs: the configurations that really shard (every N) ---------------------------------
     legs = {}

@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -111,12 +112,9 @@ def test_the_line_says_what_rccl_saw(tmp_path):
 
 def test_a_failing_rank_fails_the_command():
     """Without a GPU every rank dies in DeviceContext(): the command must end non-zero and say why -- never print a line."""
-    try:
-        import torch
-        if torch.cuda.is_available():
-            pytest.skip('a GPU is present')
-    except ImportError:
-        pass
+    from hip_devices import visible_gpus
+    if visible_gpus():
+        pytest.skip('a GPU is present')
     res = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--steps', '1', '--warmup', '0', '--no-legs', '--no-extras',
                           '--no-cpu-baseline', '--backend', 'socket'], env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert res.returncode != 0
@@ -129,7 +127,7 @@ def test_two_ranks_on_one_gpu_end_to_end():
     """The real thing on the GPU box: `bench.py --gpus 2` with both ranks on GPU 0 and the host gather (RCCL refuses two
     ranks on one device) -- headline plus every strong-scaling leg, with the scans dealt on the device."""
     res = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--devices', '0,0', '--backend', 'socket', '--steps', '10',
-                          '--warmup', '2'], env=_clean_env(), capture_output=True, text=True, timeout=1500)
+                          '--warmup', '2', '--full'], env=_clean_env(), capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-4000:]
     line = _json_line(res.stdout)
     assert line['n_gpus'] == 2 and line['value'] > 0 and line['scaling'] == 'weak'
@@ -150,3 +148,38 @@ def test_two_ranks_on_one_gpu_end_to_end():
         pc = legs[leg]['predicted_ceiling']
         assert pc['measured_at_n'] == 2 and pc['evals_per_s']['8'] >= pc['evals_per_s']['1'] > 0
     assert legs['C3']['roofline']['bound'] == 'hbm' and legs['C3']['roofline']['launches_per_call'] >= 1
+
+
+def test_bad_step_counts_and_dump_requests_end_before_any_work():
+    """--steps below 1, a negative --warmup and --dump-outputs of a configuration other than the headline are refused by the
+    argument parser."""
+    for extra in (['--steps', '0'], ['--warmup', '-1'], ['--config', 'C4', '--dump-outputs', 'unused']):
+        res = subprocess.run([sys.executable, BENCH, '--gpus', '1'] + extra, env=_clean_env(), capture_output=True, text=True,
+                             timeout=120)
+        assert res.returncode == 2 and 'error:' in res.stderr, (extra, res.stderr[-2000:])
+        assert not [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_the_headline_and_dumps_its_last_step(tmp_path):
+    """A plain run prints the headline alone (no roofline, legs, extras or CPU baseline: those are --full), times exactly
+    --steps steps, and --dump-outputs writes what the last of them computed -- evaluation 0 of it equal to the oracle."""
+    from blueice_amd.synthetic import SyntheticModel
+    from oracle import blueice_oracle as orc
+    K = 5
+    res = subprocess.run([sys.executable, BENCH, '--gpus', '1', '--steps', str(K), '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                         env=_clean_env(), capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-4000:]
+    line = _json_line(res.stdout)
+    assert not set(line) & {'roofline', 'legs', 'extras', 'cpu_baseline', 'north_star'}
+    assert line['steps'] == K and line['warmup'] == 1 and line['dtype'] == 'f64' and line['higher_is_better'] is True
+    pps = line['config']['evals_per_step']
+    assert abs(line['value'] - pps * 1e3 / line['ms_per_step']) <= 1e-9 * line['value']
+    assert line['outputs_checked'] is True and line['results_read_back'] == K * pps
+    ll = np.load(str(tmp_path / 'loglikelihood.npy'))
+    assert ll.dtype == np.float64 and ll.shape == (1, pps) and np.all(np.isfinite(ll))
+    # step K - 1 ran the plan of the point set (K - 1) % 8 (bench.py's POOL); evaluation 0 is against dataset 0
+    m = SyntheticModel.named('C2')
+    z, r = m.disjoint_cell_points(parity=(K - 1) % 8, seed=(K - 1) % 8)
+    want = orc.loglikelihood(m.cell_model(z[0]), m.counts(), z[0], r[0])
+    assert abs(ll[0, 0] - want) <= 1e-10 * max(1.0, abs(want)), (ll[0, 0], want)
