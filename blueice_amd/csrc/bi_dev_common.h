@@ -117,6 +117,23 @@ struct GradMfmaArgs {
     int NS, n_slices;
 };
 
+// k_morph_hess (bi_k_hess.h)
+struct HessArgs {
+    const double* ps;          // [rows][Bp] (or the compacted rows of the non-empty bins)
+    const double* counts;      // [T][Bp] (or the compacted counts); unused when UNB
+    const int64_t* rowoff;     // [items][NS] element offsets of the rows
+    const double* coef;        // [items][NS][G]
+    const int64_t* item_cnt;   // [items] element offset of the item's counts row
+    const int32_t* item_tiles; // [items] 512-bin tiles of the item's rows
+    double* partial;           // [items][nbx][NSL]
+    unsigned* pflags;          // [items][nbx][NSL] (zeroes: k_finish reads them)
+    int64_t B;                 // bins (events) of a row; UNB: later entries are padding
+    double outlier;            // UNB: likelihood of events whose density is not > 0 (0 = none)
+    int NS;                    // rows per item
+    int D;                     // first-order columns (<= DM)
+    int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (as morph_tiles)
+};
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

@@ -327,6 +327,20 @@ class DeviceContext:
                                            ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], status
 
+    def eval_hess(self, z, rate_scale=None, dataset=None):
+        """Value, analytic gradient and Hessian in one pass (bi_eval_hess) -> (ll [P], dll/dz [P, d], dll/drate_scale [P, S],
+        H [P, d + S, d + S] over (z, rate_scale), status).  Raises ValueError (BI_ERR_INVALID) where the kernel has no
+        analytic Hessian: Beeston-Barlow, unbinned pdfs that are not all finite, too many parameters."""
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        F = self.d + self.S
+        ll = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, F), dtype=np.float64)
+        hess = np.empty((P, F, F), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_eval_hess(self._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(hess),
+                                           ptr(status)))
+        return ll, grad[:, :self.d], grad[:, self.d:], hess, status
+
     def fit_batched(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters):
         """bi_fit_batched: the batched profile-fit engine's loop with this context's likelihood as the objective (all
         arguments are C-contiguous numpy arrays of the right dtype or None; results are written into x, f, flags, counters)."""

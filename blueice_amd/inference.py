@@ -2,8 +2,13 @@
 (blueice/inference.py:57-178) plus a batched `best_anchor` (:34-54).
 
 These only need `lf(**kwargs) -> float`, `lf.rate_parameters`, `lf.shape_parameters`,
-`lf.get_bounds`, `lf.pdf_base_config`; scipy.optimize is used as is.  iminuit / emcee drivers and
-plotting are out of scope.
+`lf.get_bounds`, `lf.pdf_base_config`; scipy.optimize is used as is.  The emcee driver and plotting are out of scope
+(SURVEY.md section 2).
+
+Uncertainties: `hesse` turns fitted values into the covariance (-H)^-1 of the floating parameters from the device Hessian
+of the likelihood (`values_gradients_hessians`: bi_eval_hess, one call for a whole ensemble of fits), and
+`bestfit_minuit` -- the reference's iminuit driver (blueice/inference.py:181-244) -- returns the batched engine's fit with
+the parabolic errors sqrt(diag((-H)^-1)) that MIGRAD reports at errordef = 0.5.  iminuit itself is not used.
 
 Profiled quantities -- `likelihood_ratio_scan` with floating nuisances, `one_parameter_interval` -- run on the batched
 profile-fit engine (blueice_amd.profile: all hypotheses advance together, one device call per optimiser iteration)
@@ -13,16 +18,19 @@ loops (blueice/inference.py:332-443).
 from collections import OrderedDict
 from copy import deepcopy
 
+import warnings
+
 import numpy as np
 from scipy import stats
 from scipy.optimize import brentq, minimize
 
 from .exceptions import NoOpimizationNecessary, OptimizationFailed
+from .hessian import to_log10
 from .profile import bestfit_batched, supports_batched_fits
 from .utils import is_numeric
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
-           'one_parameter_interval', 'likelihood_ratio_scan']
+           'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit']
 
 
 def best_anchor(lf):
@@ -224,6 +232,89 @@ def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, f
     finally:
         ctx.set_param('toy_offset', 0)
     return OrderedDict((k, np.concatenate(v)) for k, v in best.items()), np.concatenate(lls)
+
+
+def _covariance(lf, values, livetime_days=None, datasets=None, log_rates=False, **fixed):
+    """-> (names of the floating parameters, covariance [P, F, F], scalar input?) -- see `hesse`."""
+    if not hasattr(lf, 'values_gradients_hessians'):
+        raise NotImplementedError("hesse needs a likelihood with values_gradients_hessians")
+    floating = list(values.keys())
+    cols = {k: np.atleast_1d(np.asarray(v, dtype=float)) for k, v in values.items()}
+    scalar = all(np.ndim(v) == 0 for v in values.values()) and datasets is None
+    P = max([len(c) for c in cols.values()] + [1 if datasets is None else len(np.atleast_1d(datasets))])
+    points = {k: np.broadcast_to(c, (P,)) for k, c in cols.items()}
+    points.update((k, np.broadcast_to(np.asarray(v, dtype=float), (P,))) for k, v in fixed.items())
+    options = {} if datasets is None else dict(dataset=np.broadcast_to(np.asarray(datasets, dtype=np.int64), (P,)))
+    ll, grads, names, H = lf.values_gradients_hessians(points, livetime_days=livetime_days, **options)
+    missing = [k for k in floating if k not in names]
+    if missing:
+        raise ValueError("not parameters of the likelihood: %s" % ', '.join(missing))
+    order = [k for k in names if k in floating]
+    idx = np.array([names.index(k) for k in order], dtype=int)
+    g = np.stack([grads[k] for k in order], axis=1) if order else np.zeros((P, 0))
+    Hf = H[:, idx[:, None], idx[None, :]]
+    if log_rates:
+        g, Hf = to_log10(g, Hf, np.stack([points[k] for k in order], axis=1), [k.endswith('_rate_multiplier') for k in order])
+    F = len(order)
+    cov = np.full((P, F, F), np.nan)
+    ok = np.isfinite(ll) & np.all(np.isfinite(Hf), axis=(1, 2))
+    for p in np.flatnonzero(ok):
+        try:
+            L = np.linalg.cholesky(-Hf[p])
+        except np.linalg.LinAlgError:
+            ok[p] = False
+            continue
+        Li = np.linalg.inv(L)
+        cov[p] = Li.T @ Li
+    if not ok.all():
+        warnings.warn("hesse: -H is not positive definite (or ll = -inf) at %d of %d points: their covariance is nan"
+                      % (int(np.count_nonzero(~ok)), P), RuntimeWarning, stacklevel=3)
+    return order, cov, scalar
+
+
+def hesse(lf, values, livetime_days=None, datasets=None, **fixed):
+    """Covariance of the floating parameters at fitted values: (-H)^-1, H the Hessian of the log likelihood from the device
+    (`lf.values_gradients_hessians`, one call for all points).
+
+    values: the first return of a `bestfit_*` -- dict name -> scalar, or -> array [P] (an ensemble of fits); the parameters
+    named there float, `fixed` holds others at given values.  datasets: the dataset of every point, e.g. np.arange(T) for
+    the T toys fitted by `bestfit_toys`.  -> (names [F], covariance [F, F] for scalar values, [P, F, F] for arrays).  The
+    covariance is nan (with one warning per call) where -H is not positive definite or ll = -inf.  On an anchor the
+    Hessian is that of the cell the point is assigned to."""
+    names, cov, scalar = _covariance(lf, values, livetime_days=livetime_days, datasets=datasets, **fixed)
+    return names, (cov[0] if scalar else cov)
+
+
+_MINUIT_DISPLAY_OPTIONS = ('print_level', 'pedantic', 'errordef')
+
+
+def bestfit_minuit(lf, minimize_kwargs=None, rates_in_log_space=False, **kwargs):
+    """The reference's `bestfit_minuit` (blueice/inference.py:181-244) without iminuit: -> ({name: value, name + '_error':
+    sigma}, max log likelihood).  Values are `bestfit_device`'s (the batched engine); sigma = sqrt(diag((-H)^-1)) from the
+    device Hessian -- MIGRAD's parabolic errors at errordef = 0.5.  With rates_in_log_space=True rate multipliers are
+    reported as log10 values with the errors of those, as the reference's Minuit in log space does.  minimize_kwargs: the
+    Minuit display options print_level, pedantic and errordef are accepted and ignored, any other key is a ValueError.
+    kwargs: parameters held fixed (and `guess`), as `bestfit_scipy`.  Nothing floating: ({}, lf(**kwargs))."""
+    unknown = sorted(set(minimize_kwargs or {}) - set(_MINUIT_DISPLAY_OPTIONS))
+    if unknown:
+        raise ValueError("bestfit_minuit: unsupported minimize_kwargs %s (only %s are accepted, and ignored)"
+                         % (', '.join(unknown), ', '.join(_MINUIT_DISPLAY_OPTIONS)))
+    guess = kwargs.pop('guess', None)
+    fixed = {k: v for k, v in kwargs.items() if k != 'livetime_days'}
+    floating = ['%s_rate_multiplier' % s for s in lf.rate_parameters] + list(lf.shape_parameters)
+    if not [k for k in floating if k not in fixed]:
+        return {}, lf(**kwargs)
+    best, ll = bestfit_device(lf, guess=guess, **kwargs)
+    if not best:
+        return {}, ll
+    names, cov, _ = _covariance(lf, best, livetime_days=kwargs.get('livetime_days'), log_rates=rates_in_log_space, **fixed)
+    err = np.sqrt(np.diag(cov[0]))
+    result = OrderedDict()
+    for k, v in best.items():
+        result[k] = float(np.log10(v)) if rates_in_log_space and k.endswith('_rate_multiplier') else float(v)
+    for k, e in zip(names, err):
+        result[k + '_error'] = float(e)
+    return result, float(ll)
 
 
 def _first_crossing(tfun, a, b, xtol=1e-11, points_per_round=16, max_rounds=12):

@@ -24,6 +24,7 @@ from scipy import stats
 from . import _capi
 from .device import DeviceContext
 from .exceptions import DeviceError, InvalidParameter, InvalidParameterSpecification, NotPreparedException
+from .hessian import chain_rule_hessian, difference_steps, prior_derivatives
 from .histdd import Histdd
 from .model import Model
 from .pdf_morphers import MORPHERS
@@ -672,6 +673,148 @@ class DeviceLogLikelihood(LogLikelihoodBase):
             g[bad] = np.nan
         return out, grads
 
+    # -- second derivatives ----------------------------------------------------------------------
+    @property
+    def supports_hessian(self):
+        """True when bi_eval_hess has an analytic Hessian for this likelihood: binned without Beeston-Barlow, or extended
+        unbinned with finite pdfs, up to 64 coefficient columns and 16 first-order parameters (include/blueice_hip.h).
+        Elsewhere `values_gradients_hessians` takes central differences of the analytic gradient."""
+        ctx = getattr(self, 'ctx', None)
+        if ctx is None or not self.is_data_set or self._bb_source_index() >= 0:
+            return False
+        try:                                   # a call with no points: the library's own checks, no device work
+            ctx.eval_hess(np.zeros((0, ctx.d)), np.zeros((0, ctx.S)))
+        except ValueError:
+            return False
+        return True
+
+    @property
+    def hessian_method(self):
+        """'analytic' (bi_eval_hess) or 'gradient-differences': the route the last `values_gradients_hessians` call took, or
+        the one it will take."""
+        route = self.__dict__.get('_hessian_route')
+        if route is None:
+            route = 'analytic' if self.supports_hessian else 'gradient-differences'
+        return route
+
+    def _parameter_names(self):
+        return ['%s_rate_multiplier' % s for s in self.source_name_list if s in self.rate_parameters] + list(self.shape_parameters)
+
+    @_needs_data
+    def value_gradient_hessian(self, livetime_days=None, **kwargs):
+        """-> (ll, OrderedDict name -> d ll / d parameter, names, H [F, F]) at one point: `values_gradients_hessians` with
+        P = 1."""
+        ll, grads, names, H = self.values_gradients_hessians({k: np.array([v], dtype=float) for k, v in kwargs.items()},
+                                                             livetime_days=livetime_days)
+        return float(ll[0]), OrderedDict((k, float(v[0])) for k, v in grads.items()), names, H[0]
+
+    @_needs_data
+    def values_gradients_hessians(self, points, livetime_days=None, dataset=None):
+        """Value, gradient and Hessian at P points in one device call: points = dict parameter name -> array [P] (as
+        `values_and_gradients`) -> (ll [P], OrderedDict name -> d ll / d parameter [P], names [F], H [P, F, F]) over every
+        registered rate multiplier, then every shape parameter.  The device Hessian over (z, rate_scale) (bi_eval_hess) is
+        carried to the user's parameters by the chain rule (live-time and efficiency factors, shape parameters that double
+        as efficiencies, priors by central second differences).  On an anchor the Hessian is that of the cell the point is
+        assigned to.  Where the device has no analytic Hessian (Beeston-Barlow, unbinned pdfs that are not all finite, too
+        many parameters) central differences of the analytic gradient are taken instead -- all 2 F displaced points of all
+        P points in ONE `values_and_gradients` call, steps kept inside the point's grid cell (one-sided at its edges),
+        the result symmetrised; `hessian_method` says which route was taken.  Points outside the anchor box or with
+        unphysical rates give -inf, nan slopes and a nan Hessian."""
+        if not self.supports_hessian:
+            self._hessian_route = 'gradient-differences'
+            return self._hessian_by_gradient_differences(points, livetime_days, dataset)
+        self._hessian_route = 'analytic'
+        z, scale, prior = self._batch_terms(points, livetime_days)
+        P = len(z)
+        ll, gz, gs, Hth, st = self.ctx.eval_hess(z if z.shape[1] else None, scale, dataset)
+        if np.any(st & _capi.ST_INTERNAL):
+            raise DeviceError("the device gave up waiting for a partial sum (in-launch reduction): GPU fault")
+        bad = (st & (_capi.ST_OUT_OF_BOUNDS | _capi.ST_UNPHYSICAL)) != 0
+        if np.any(st & _capi.ST_UNPHYSICAL) and self.config.get('unphysical_behaviour') == 'error':
+            raise ValueError("Unphysical rates at %d of %d points" % (int(np.count_nonzero(st & _capi.ST_UNPHYSICAL)), P))
+        S = len(self.source_name_list)
+        mult = np.ones((P, S))
+        for s, name in enumerate(self.source_name_list):
+            key = name + '_rate_multiplier'
+            if key in points:
+                mult[:, s] = np.broadcast_to(np.asarray(points[key], dtype=float), (P,))
+        L = 1.0
+        if livetime_days is not None and self.pdf_base_config.get('livetime_days'):
+            L = livetime_days / self.pdf_base_config['livetime_days']
+        eff, eff_axis = np.ones((P, S)), [-1] * S
+        shape_names = list(self.shape_parameters)
+        defaults = self._batch_names[2]
+        for s in np.flatnonzero(self.source_apply_efficiency):
+            en = self.source_efficiency_names[s]
+            v = points[en] if en in points else defaults.get(en)
+            if v is not None:
+                eff[:, s] = np.broadcast_to(np.asarray(v, dtype=float), (P,))
+            if en in shape_names:
+                eff_axis[s] = shape_names.index(en)
+        rate_sources = [s for s, name in enumerate(self.source_name_list) if name in self.rate_parameters]
+        F = len(rate_sources) + len(shape_names)
+        prior_g, prior_h = np.zeros((P, F)), np.zeros((P, F))
+        for j, s in enumerate(rate_sources):
+            lp = self.rate_parameters[self.source_name_list[s]]
+            if lp is not None:
+                prior_g[:, j], prior_h[:, j] = prior_derivatives(lp, mult[:, s])
+        for i, (name, (_, lp, _)) in enumerate(self.shape_parameters.items()):
+            if lp is not None:
+                prior_g[:, len(rate_sources) + i], prior_h[:, len(rate_sources) + i] = prior_derivatives(lp, z[:, i])
+        g, H = chain_rule_hessian(gz, gs, Hth, mult, L, eff, eff_axis, rate_sources, prior_g, prior_h)
+        out = ll + prior
+        out[bad] = -np.inf
+        g[bad] = np.nan
+        H[bad | ~np.isfinite(out)] = np.nan
+        names = self._parameter_names()
+        return out, OrderedDict((n, g[:, j]) for j, n in enumerate(names)), names, H
+
+    def _hessian_by_gradient_differences(self, points, livetime_days, dataset):
+        names = self._parameter_names()
+        F = len(names)
+        P = max([np.size(v) for v in points.values()] + [1])
+        cols = {k: np.broadcast_to(np.asarray(v, dtype=float), (P,)) for k, v in points.items()}
+        self._batch_terms(points, livetime_days)                     # (validates the names, fills the defaults)
+        defaults = self._batch_names[2]
+        X = np.empty((P, F))
+        xp, xm = np.empty((P, F)), np.empty((P, F))
+        for j, n in enumerate(names):
+            if n.endswith('_rate_multiplier'):
+                X[:, j] = cols[n] if n in cols else 1.0
+                h = 1e-5 * np.maximum(1.0, np.abs(X[:, j]))
+                xp[:, j], xm[:, j] = difference_steps(X[:, j], 0.0, np.inf, True, h)
+                continue
+            X[:, j] = cols[n] if n in cols else defaults[n]
+            grid = np.array(sorted(self.shape_parameters[n][0].keys()), dtype=float)
+            if len(grid) < 2:
+                xp[:, j] = xm[:, j] = X[:, j]
+                continue
+            k = np.clip(np.searchsorted(grid, X[:, j], side='right') - 1, 0, len(grid) - 2)
+            lo, hi = grid[k], grid[k + 1]
+            xp[:, j], xm[:, j] = difference_steps(X[:, j], lo, hi, k + 2 == len(grid), 1e-4 * (hi - lo))
+        # one call: the P points themselves, then point p displaced along j to the + and the - side
+        rows = [X]
+        for j in range(F):
+            for side in (xp, xm):
+                Y = X.copy()
+                Y[:, j] = side[:, j]
+                rows.append(Y)
+        Y = np.concatenate(rows)
+        call = {k: np.tile(v, 2 * F + 1) for k, v in cols.items() if k not in names}
+        call.update((n, Y[:, j]) for j, n in enumerate(names))
+        ds = None if dataset is None else np.tile(np.broadcast_to(np.asarray(dataset), (P,)), 2 * F + 1)
+        ll, grads = self.values_and_gradients(call, livetime_days=livetime_days, dataset=ds)
+        G = np.stack([grads[n] for n in names], axis=1).reshape(2 * F + 1, P, F)
+        H = np.zeros((P, F, F))
+        with np.errstate(all='ignore'):
+            for j in range(F):
+                step = xp[:, j] - xm[:, j]
+                H[:, j, :] = np.where((step > 0)[:, None], (G[1 + 2 * j] - G[2 + 2 * j]) / np.where(step > 0, step, 1.0)[:, None], 0.0)
+        H = 0.5 * (H + np.swapaxes(H, 1, 2))
+        out = ll[:P]
+        H[~np.isfinite(out)] = np.nan
+        return out, OrderedDict((n, G[0][:, j]) for j, n in enumerate(names)), names, H
+
     # -- toy-MC ---------------------------------------------------------------------------------
 
 
@@ -1038,6 +1181,39 @@ class LogLikelihoodSum:
             for name, slope in g.items():
                 grads[name] = grads.get(name, 0.) + weight * slope
         return total, grads
+
+    @property
+    def supports_hessian(self):
+        """True when every term has an analytic device Hessian (see DeviceLogLikelihood.supports_hessian)."""
+        return all(getattr(ll, 'supports_hessian', False) for ll in self.likelihood_list)
+
+    @property
+    def hessian_method(self):
+        """'analytic' when every term's Hessian is, else 'gradient-differences'."""
+        methods = {getattr(ll, 'hessian_method', 'gradient-differences') for ll in self.likelihood_list}
+        return 'analytic' if methods == {'analytic'} else 'gradient-differences'
+
+    def values_gradients_hessians(self, points, livetime_days=None, **options):
+        """The weighted sum of the terms' `values_gradients_hessians` (one device call per term), every term's rows and
+        columns placed by parameter name -> (ll [P], OrderedDict name -> slopes [P], names [F], H [P, F, F])."""
+        for ll in self.likelihood_list:
+            if not hasattr(ll, 'values_gradients_hessians'):
+                raise NotImplementedError("a term of this sum has no Hessian (%s)" % type(ll).__name__)
+        parts, names = [], []
+        for i, (ll, pnames, weight) in enumerate(zip(self.likelihood_list, self.likelihood_parameters, self.likelihood_weights)):
+            lt = livetime_days[i] if isinstance(livetime_days, list) else livetime_days
+            v, g, n, H = ll.values_gradients_hessians({k: x for k, x in points.items() if k in pnames}, livetime_days=lt, **options)
+            parts.append((weight, v, g, n, H))
+            names += [k for k in n if k not in names]
+        P = max(len(np.atleast_1d(v)) for _, v, _, _, _ in parts)
+        total, grads, H = np.zeros(P), OrderedDict((k, np.zeros(P)) for k in names), np.zeros((P, len(names), len(names)))
+        for weight, v, g, n, h in parts:
+            total = total + weight * v
+            for k, slope in g.items():
+                grads[k] = grads[k] + weight * slope
+            idx = np.array([names.index(k) for k in n], dtype=int)
+            H[:, idx[:, None], idx[None, :]] += weight * h
+        return total, grads, names, H
 
     def split_results(self, result_dict):
         return [{k: v for k, v in result_dict.items() if k in names} for names in self.likelihood_parameters]

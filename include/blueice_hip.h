@@ -221,6 +221,21 @@ int bi_eval_end(bi_ctx* ctx, double* out, int32_t* status);
 int bi_eval_grad(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
                  double* grad, int32_t* status);
 
+/* Value, gradient and Hessian of ll in one pass over the corner rows of each point.  ll [P], grad [P][d + S] and status [P]
+ * are what bi_eval_grad returns; hess [P][d + S][d + S] holds d2 ll / (d theta_q d theta_r), theta = (z_0 .. z_{d-1},
+ * rate_scale_0 .. rate_scale_{S-1}): full and symmetric (written from one triangle), rows and columns of axes with a single
+ * anchor 0, NaN wherever ll = -inf.  Inside a grid cell the morph is multilinear, so every second derivative of mu_b is
+ * another fixed combination of the cell's corner rows:
+ *   H_qr = sum_b [ (n_b / mu_b - 1) d_qr mu_b - (n_b / mu_b^2) d_q mu_b d_r mu_b ]      (binned; n_b = 0: -d_qr mu_b)
+ *   H_qr = -sum_s d_qr mu_s + sum_e [ d_qr lambda_e / lambda_e - d_q lambda_e d_r lambda_e / lambda_e^2 ]   (unbinned)
+ * an event on the outlier clamp contributes nothing.  On an anchor the Hessian is that of the cell the point is assigned to
+ * (the convention of bi_eval_grad).  Covers binned likelihoods without Beeston-Barlow (dense and non-empty-bin forms,
+ * device-generated toys) and the extended unbinned likelihood with finite pdfs, up to 1 + D + D2 <= 64 coefficient columns
+ * and D <= 16 first-order parameters (D = effective axes + S; D2 = the non-zero second-order columns,
+ * d_eff (d_eff + 1) / 2 + d_eff S).  Anything else returns BI_ERR_INVALID with the reason in bi_last_error. */
+int bi_eval_hess(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                 double* grad, double* hess, int32_t* status);
+
 /* The batched profile-fit engine's inner loop (host code): P minimisations of F variables each advance in lock-step, every
  * optimiser iteration ONE evaluation call over the problems still running -- what replaces the reference's loops of sequential
  * scipy fits (bestfit_scipy, blueice/inference.py:131-178, inside one_parameter_interval / plot_likelihood_ratio, :332-443).

@@ -5,7 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 # (the library is six translation units, blueice_amd/csrc/bi_common.h: each is compiled device-only, side by side, and the
 #  notes of all code objects are read together; UNITS="tu_scan_sorted" limits the run to one of them)
-UNITS=${UNITS:-"blueice_hip tu_morph tu_scan tu_scan_sorted tu_grad tu_prim"}
+UNITS=${UNITS:-"blueice_hip tu_morph tu_scan tu_scan_sorted tu_grad tu_prim tu_hess"}
 OUT=${TMPDIR:-/tmp}/blueice_hip_gfx950
 for u in $UNITS; do
     ( /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -c -ffp-contract=off -mllvm --amdgpu-mfma-vgpr-form \
