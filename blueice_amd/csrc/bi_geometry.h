@@ -101,6 +101,16 @@ bool rates_physical(const bi_ctx* c, const double* mus) {
     return true;
 }
 
+// The reference's early exits for one point, in its order: dataset ds, anchor box, rates.  -> 0 or the status bit; g and
+// the rates r [S] (interpolated, times rs when given) are filled as far as the point got.
+int32_t screen_point(const bi_ctx* c, const double* z, const double* rs, int64_t ds, PointGeom& g, double* r) {
+    if (ds < 0 || ds >= c->T) return BI_ST_BAD_DATASET;
+    if (!point_geometry(c, z, g)) return BI_ST_OUT_OF_BOUNDS;
+    interp_mus(c, g, r);
+    if (rs) for (int s = 0; s < c->S; ++s) r[s] *= rs[s];
+    return rates_physical(c, r) ? 0 : BI_ST_UNPHYSICAL;
+}
+
 int pick_class(int n, int maxg) {
     int g = 1;
     while (g < n && g < maxg) g <<= 1;

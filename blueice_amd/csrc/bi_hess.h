@@ -10,7 +10,8 @@
 //   second order, axis i, t  delta_st (d_i w_c mus_s + w_c d_i mus_s)
 // (rate-rate second derivatives are 0).  The kernel reduces every column with the per-bin weight n / mu - 1 (1 / lambda for
 // events) and the Gram sums of the first-order columns with n / mu^2 (1 / lambda^2); the empty bins of the non-empty-bin
-// form enter through the row totals over them (h_Tz), the unbinned -sum_s mu_s through the slot constants.
+// form enter through the row totals over them (h_Tz), the unbinned -sum_s mu_s through the slot constants.  The steps shared
+// with bi_eval_grad (screen, corner derivatives, first-order columns, chunked launch and finish) are in bi_grad.h.
 #pragma once
 
 namespace {
@@ -70,103 +71,42 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     std::vector<int> full((size_t)D);
     for (int q = 0; q < D; ++q) full[(size_t)q] = q < de ? c->eff_axes[(size_t)q] : d + (q - de);
 
-    // phase 1: which points are evaluated at all (as bi_eval_grad)
-    std::vector<int64_t> corner_off((size_t)nc);
-    for (int k = 0; k < nc; ++k) corner_off[(size_t)k] = corner_offset(c, k);
-    const std::vector<double> ones((size_t)S, 1.0);
-    std::vector<int32_t> st_of((size_t)P, 0);
-    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
-        PointGeom g;
-        std::vector<double> r((size_t)S);
-        for (int64_t p = lo; p < hi; ++p) {
-            ll[p] = ninf;
-            for (int j = 0; j < F; ++j) grad[p * F + j] = qnan;
-            for (int j = 0; j < F * F; ++j) hess[p * F * F + j] = qnan;
-            const int64_t ds = (dataset && !unb) ? dataset[p] : 0;
-            if (!unb && (ds < 0 || ds >= c->T)) { st_of[(size_t)p] = BI_ST_BAD_DATASET; continue; }
-            if (!point_geometry(c, z ? z + p * d : nullptr, g)) { st_of[(size_t)p] = BI_ST_OUT_OF_BOUNDS; continue; }
-            interp_mus(c, g, r.data());
-            const double* rs = rate_scale ? rate_scale + p * S : ones.data();
-            for (int s = 0; s < S; ++s) r[(size_t)s] *= rs[s];
-            if (!rates_physical(c, r.data())) st_of[(size_t)p] = BI_ST_UNPHYSICAL;
-        }
+    // the points that are evaluated at all, then the descriptors of the live ones (as bi_eval_grad)
+    if (unb) dataset = nullptr;        // (one dataset)
+    const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, dataset, status, [&](int64_t p) {
+        ll[p] = ninf;
+        for (int j = 0; j < F; ++j) grad[p * F + j] = qnan;
+        for (int j = 0; j < F * F; ++j) hess[p * F * F + j] = qnan;
     });
-    std::vector<int64_t> live;
-    live.reserve((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        if (status) status[p] = st_of[(size_t)p];
-        if (!st_of[(size_t)p]) live.push_back(p);
-    }
     const int64_t n_items = (int64_t)live.size();
     if (n_items == 0) return BI_OK;
-
-    // phase 2: the descriptors of the live points
+    std::vector<int> axis_col((size_t)de);
+    for (int ii = 0; ii < de; ++ii) axis_col[(size_t)ii] = 1 + ii;
     std::vector<int64_t> rowoff((size_t)n_items * NS), cnt_off((size_t)n_items), perm((size_t)n_items * NSL);
     std::vector<double> coef((size_t)n_items * NS * G, 0.0), slot_lg((size_t)n_items * NSL, 0.0);
     std::vector<int32_t> tiles((size_t)n_items);
     parallel_for(n_items, 512, [&](int64_t lo, int64_t hi) {
-        PointGeom g;
-        const int de1 = std::max(de, 1), npz = std::max(NZZ, 1);
-        std::vector<double> mus((size_t)S), r((size_t)S), dmus((size_t)de1 * S), d2mus((size_t)npz * S);
-        std::vector<double> dw((size_t)nc * de1), d2w((size_t)nc * npz);
+        PointDerivs pd(c, true);
+        const std::vector<double>& mus = pd.mus;
+        const std::vector<double>& dmus = pd.dmus;
+        const std::vector<double>& d2mus = pd.d2mus;
         for (int64_t i = lo; i < hi; ++i) {
             const int64_t p = live[(size_t)i];
-            const int64_t ds = (dataset && !unb) ? dataset[p] : 0;
-            point_geometry(c, z ? z + p * d : nullptr, g);
-            interp_mus(c, g, mus.data());
-            const double* rs = rate_scale ? rate_scale + p * S : ones.data();
-            for (int s = 0; s < S; ++s) r[(size_t)s] = mus[(size_t)s] * rs[s];
-            // d w_c / d z_i = (+-1 / delta_i) prod_{k != i} w^(k);  d2 w_c / d z_i d z_j (i < j): both factors differentiated
-            for (int corner = 0; corner < nc; ++corner) {
-                auto factor = [&](int jj, bool diff) {
-                    const bool up = (corner >> (de - 1 - jj)) & 1;
-                    if (diff) return (up ? 1.0 : -1.0) * g.inv_delta[c->eff_axes[(size_t)jj]];
-                    const double t = g.t[c->eff_axes[(size_t)jj]];
-                    return up ? t : (1 - t);
-                };
-                for (int ii = 0; ii < de; ++ii) {
-                    double v = 1.0;
-                    for (int jj = 0; jj < de; ++jj) v *= factor(jj, jj == ii);
-                    dw[(size_t)corner * de + ii] = v;
-                }
-                for (int ii = 0; ii < de; ++ii)
-                    for (int jj = ii; jj < de; ++jj) {
-                        double v = 0.0;
-                        if (jj != ii) {
-                            v = 1.0;
-                            for (int kk = 0; kk < de; ++kk) v *= factor(kk, kk == ii || kk == jj);
-                        }
-                        d2w[(size_t)corner * npz + (jj * (jj + 1) / 2 + ii)] = v;
-                    }
-            }
-            for (int s = 0; s < S; ++s) {
-                for (int ii = 0; ii < de; ++ii) {
-                    double v = 0.0;
-                    for (int corner = 0; corner < nc; ++corner)
-                        v += dw[(size_t)corner * de + ii] * c->h_mus[(size_t)((g.cell_anchor + corner_off[(size_t)corner]) * S + s)];
-                    dmus[(size_t)ii * S + s] = v;
-                }
-                for (int pz = 0; pz < NZZ; ++pz) {
-                    double v = 0.0;
-                    for (int corner = 0; corner < nc; ++corner)
-                        v += d2w[(size_t)corner * npz + pz] * c->h_mus[(size_t)((g.cell_anchor + corner_off[(size_t)corner]) * S + s)];
-                    d2mus[(size_t)pz * S + s] = v;
-                }
-            }
+            const int64_t ds = dataset ? dataset[p] : 0;
+            pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
+            const double* rs = pd.rs;
             const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
             const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
             const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * NSL;
             int k = 0;
             for (int corner = 0; corner < nc; ++corner)
                 for (int s = 0; s < S; ++s, ++k) {
-                    const int64_t row = (g.cell_anchor + corner_off[(size_t)corner]) * S + s;
+                    const int64_t row = (pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s;
                     rowoff[ro + k] = row_base + row * row_stride;
                     double* col = &coef[co + (size_t)k * G];
-                    const double w = g.w[(size_t)corner];
-                    const double* dwc = &dw[(size_t)corner * de];
-                    col[0] = w * r[(size_t)s];
-                    for (int ii = 0; ii < de; ++ii) col[1 + ii] = dwc[ii] * r[(size_t)s] + w * dmus[(size_t)ii * S + s] * rs[s];
-                    col[1 + de + s] = w * mus[(size_t)s];
+                    const double w = pd.g.w[(size_t)corner];
+                    const double* dwc = &pd.dw[(size_t)corner * de];
+                    pd.first_order(col, corner, s, axis_col.data(), 1 + de + s);
                     int q = 1 + D;
                     for (int ii = 0; ii < de; ++ii)
                         for (int jj = ii; jj < de; ++jj, ++q) {
@@ -174,7 +114,7 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
                             if (ii == jj) col[q] = rs[s] * (2.0 * dwc[ii] * a_i);
                             else {
                                 const int pz = jj * (jj + 1) / 2 + ii;
-                                col[q] = rs[s] * (d2w[(size_t)corner * npz + pz] * mus[(size_t)s] + dwc[ii] * a_j + dwc[jj] * a_i +
+                                col[q] = rs[s] * (pd.d2w[(size_t)corner * NZZ + pz] * mus[(size_t)s] + dwc[ii] * a_j + dwc[jj] * a_i +
                                                   w * d2mus[(size_t)pz * S + s]);
                             }
                         }
@@ -185,15 +125,10 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
                     }
                 }
             if (unb) {
-                // -sum_s mu_s and its derivatives (likelihood.py:690): what the kernel's sums over the events are reduced by
                 double* lg = &slot_lg[po];
-                for (int s = 0; s < S; ++s) {
-                    lg[0] += r[(size_t)s];
-                    lg[1 + de + s] = mus[(size_t)s];
-                }
-                int q = 1 + D;
+                pd.first_order_unbinned(lg, axis_col.data(), 1 + de);
+                int q = 1 + D;                   // the second-order columns' constants
                 for (int ii = 0; ii < de; ++ii) {
-                    for (int s = 0; s < S; ++s) lg[1 + ii] += dmus[(size_t)ii * S + s] * rs[s];
                     for (int jj = ii; jj < de; ++jj, ++q)
                         if (jj != ii)
                             for (int s = 0; s < S; ++s) lg[q] += d2mus[(size_t)(jj * (jj + 1) / 2 + ii) * S + s] * rs[s];
@@ -209,23 +144,12 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     });
     int max_tiles = 1;
     for (int32_t t : tiles) max_tiles = std::max(max_tiles, (int)t);
-    const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
-    const int nbx = (int)std::min<int64_t>(max_tiles, n_items == 1 ? slots : std::max<int64_t>(1, (4 * slots + n_items - 1) / n_items));
-    DevBuf d_part, d_flag;
-    auto cleanup = [&]() { dev_free(d_part); dev_free(d_flag); };
     PackedUpload pu;
-    const size_t out_bytes = (size_t)n_items * NSL * sizeof(double);
-    const int64_t chunk = 65535;
-    const int64_t part_items = std::min<int64_t>(chunk, n_items);      // the chunks run in order on one stream: one partial buffer
     if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
                                 {cnt_off.data(), cnt_off.size() * sizeof(int64_t)}, {tiles.data(), tiles.size() * sizeof(int32_t)},
                                 {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
-                            out_bytes, pu)) ||
-        (rc = dev_alloc(c, d_part, (size_t)part_items * nbx * NSL * sizeof(double))) ||
-        (rc = dev_alloc(c, d_flag, (size_t)part_items * nbx * NSL * sizeof(unsigned)))) {
-        cleanup();
+                            (size_t)n_items * NSL * sizeof(double), pu)))
         return rc;
-    }
     double* h_out = (double*)pu.host_out();
     HessArgs a{};
     a.ps = sparse ? (const double*)c->ps_c.p : (const double*)c->ps.p;
@@ -235,32 +159,20 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     a.NS = NS;
     a.D = D;
     a.chunks = (int)c->tile_chunks;
-    a.partial = (double*)d_part.p;
-    a.pflags = (unsigned*)d_flag.p;
     const bool nt = !sparse && !unb && (c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1));
-    hipError_t e = hipSuccess;
-    for (int64_t i0 = 0; i0 < n_items && e == hipSuccess; i0 += chunk) {
-        const int64_t ni = std::min<int64_t>(chunk, n_items - i0);
-        HessArgs b = a;
-        b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
-        b.coef = pu.dev<double>(1) + i0 * NS * G;
-        b.item_cnt = pu.dev<int64_t>(2) + i0;
-        b.item_tiles = pu.dev<int32_t>(3) + i0;
-        if ((rc = launch_morph_hess(c, G, DM, b, dim3((unsigned)nbx, (unsigned)ni), nt))) {
-            cleanup();
-            return fail(c, rc, "bi_eval_hess: no kernel variant for G = %d, DM = %d", G, DM);
-        }
-        const int64_t n_slots = ni * NSL;
-        const int lanes = nbx > 64 ? kThreads : 64;
-        const int per_block = kThreads / lanes;
-        hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream,
-                           (const double*)b.partial, (const unsigned*)b.pflags, nbx, NSL, lanes, n_slots,
-                           pu.dev<int64_t>(4) + i0 * NSL, pu.dev<double>(5) + i0 * NSL, h_out, (int32_t*)nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_hess: %s", hipGetErrorString(e));
+    rc = run_item_chunks(c, n_items, max_tiles, NSL, pu.dev<int64_t>(4), pu.dev<double>(5), h_out, nullptr, "bi_eval_hess",
+                         [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
+                             HessArgs b = a;
+                             b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
+                             b.coef = pu.dev<double>(1) + i0 * NS * G;
+                             b.item_cnt = pu.dev<int64_t>(2) + i0;
+                             b.item_tiles = pu.dev<int32_t>(3) + i0;
+                             b.partial = partial;
+                             b.pflags = pflags;
+                             const int e = launch_morph_hess(c, G, DM, b, grid, nt);
+                             return e ? fail(c, e, "bi_eval_hess: no kernel variant for G = %d, DM = %d", G, DM) : BI_OK;
+                         });
+    if (rc) return rc;
     parallel_for(n_items, 2048, [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
             const int64_t p = live[(size_t)i];

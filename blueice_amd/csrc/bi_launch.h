@@ -1,5 +1,5 @@
-// bi_launch.h -- mailbox set-up of in-launch finishing and state checks (main translation unit).  The instantiation tables of
-// the heavy kernel families are in tu_*.hip, declared in bi_common.h.
+// bi_launch.h -- mailbox set-up of in-launch finishing, the k_finish launch and state checks (main translation unit).  The
+// instantiation tables of the heavy kernel families are in tu_*.hip, declared in bi_common.h.
 #pragma once
 
 namespace {
@@ -53,5 +53,15 @@ int check_ready(bi_ctx* c, bool need_data) {
 }
 
 int n_tiles_of(const bi_ctx* c) { return (int)(c->Bp / kTile); }
+
+// k_finish over n_slots (item, slot) sums, G slots per item, of nbx per-block partials each: 64 lanes per slot up to 64
+// blocks, else a whole block
+void launch_finish(bi_ctx* c, const double* partial, const unsigned* pflags, int nbx, int G, int64_t n_slots, const int64_t* perm,
+                   const double* slot_lg, double* out, int32_t* status) {
+    const int lanes = nbx > 64 ? kThreads : 64;
+    const int per_block = kThreads / lanes;
+    hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream, partial, pflags,
+                       nbx, G, lanes, n_slots, perm, slot_lg, out, status);
+}
 
 }  // namespace

@@ -108,13 +108,9 @@ int plan_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale,
     parallel_for(P, 4096, [&](int64_t lo, int64_t hi) {
         PointGeom g;
         for (int64_t p = lo; p < hi; ++p) {
-            const int64_t ds = dataset ? dataset[p] : 0;
-            if (ds < 0 || ds >= c->T) { st[(size_t)p] = BI_ST_BAD_DATASET; continue; }
-            if (!point_geometry(c, z ? z + p * d : nullptr, g)) { st[(size_t)p] = BI_ST_OUT_OF_BOUNDS; continue; }
-            double* r = &rates[(size_t)p * S];
-            interp_mus(c, g, r);
-            if (rate_scale) for (int s = 0; s < S; ++s) r[s] *= rate_scale[p * S + s];
-            if (!rates_physical(c, r)) { st[(size_t)p] = BI_ST_UNPHYSICAL; continue; }
+            st[(size_t)p] = screen_point(c, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, dataset ? dataset[p] : 0, g,
+                                         &rates[(size_t)p * S]);
+            if (st[(size_t)p]) continue;
             std::copy(g.w.begin(), g.w.end(), wts.begin() + (size_t)p * nc);
             cell[(size_t)p] = g.cell_anchor;
         }

@@ -836,12 +836,8 @@ int eval_grad_device(bi_ctx* c, int64_t P, const double* z, const double* rate_s
         b.partial = (double*)d_part.p + i0 * nbx * G;
         b.pflags = (unsigned*)d_flag.p + i0 * nbx * G;
         launch_morph_grad(c, G, b, dim3((unsigned)nbx, (unsigned)ni), false);
-        const int64_t n_slots = ni * G;
-        const int lanes = nbx > 64 ? kThreads : 64;
-        const int per_block = kThreads / lanes;
-        hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream,
-                           (const double*)b.partial, (const unsigned*)b.pflags, nbx, G, lanes, n_slots, (const int64_t*)d_perm.p + i0 * G,
-                           (const double*)d_lg.p + i0 * G, (double*)d_out.p, (int32_t*)nullptr);
+        launch_finish(c, b.partial, b.pflags, nbx, G, ni * G, (const int64_t*)d_perm.p + i0 * G, (const double*)d_lg.p + i0 * G,
+                      (double*)d_out.p, nullptr);
     }
     std::vector<double> h_out(nP * W);
     std::vector<int32_t> h_st(nP);

@@ -330,16 +330,12 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
     } park{c, !wait, &parked_ll, &parked_st};
     const int S = c->S;
     const double ninf = -std::numeric_limits<double>::infinity();
-    if (ds < 0 || ds >= c->T) { *out = ninf; if (status) *status = BI_ST_BAD_DATASET; return BI_OK; }
     PointGeom g;
-    if (!point_geometry(c, z, g)) { *out = ninf; if (status) *status = BI_ST_OUT_OF_BOUNDS; return BI_OK; }
     double r[64];
     std::vector<double> rbig;
     double* rates = r;
     if (S > 64) { rbig.resize((size_t)S); rates = rbig.data(); }
-    interp_mus(c, g, rates);
-    if (rate_scale) for (int s = 0; s < S; ++s) rates[s] *= rate_scale[s];
-    if (!rates_physical(c, rates)) { *out = ninf; if (status) *status = BI_ST_UNPHYSICAL; return BI_OK; }
+    if (const int32_t bit = screen_point(c, z, rate_scale, ds, g, rates)) { *out = ninf; if (status) *status = bit; return BI_OK; }
     if (has_infinite_rate(rates, S) && c->bb_source < 0 && !c->unbinned && c->ps_finite && c->dense_counts)
         return inf_rate_value(c, g, rates, ds, out);
 
@@ -441,10 +437,8 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
     a.outlier = c->outlier;
     a.nan_S = (c->unbinned && !c->ps_finite) ? c->S : 0;
     launch_morph_g(c, 1, a, dim3((unsigned)nbx, 1), bb, !sparse && c->nt_loads != 0);
-    const int lanes = nbx > 64 ? kThreads : 64;
-    hipLaunchKernelGGL(k_finish, dim3(1), dim3(kThreads), 0, c->stream, (const double*)a.partial,
-                       (const unsigned*)a.pflags, nbx, 1, lanes, (int64_t)1, (const int64_t*)(dev + (o + 2) * 8),
-                       (const double*)(dev + (o + 3) * 8), (double*)res, (int32_t*)(res + 8));
+    launch_finish(c, a.partial, a.pflags, nbx, 1, 1, (const int64_t*)(dev + (o + 2) * 8), (const double*)(dev + (o + 3) * 8),
+                  (double*)res, (int32_t*)(res + 8));
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *out = *(double*)res;

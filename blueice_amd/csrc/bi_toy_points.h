@@ -480,16 +480,9 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
     std::vector<double> rates((size_t)P * S);
     for (int64_t p = 0; p < P; ++p) {
         PointGeom& g = geom[(size_t)p];
-        if (!point_geometry(c, z ? z + p * d : nullptr, g)) {
-            if (status) status[p] = BI_ST_OUT_OF_BOUNDS;
-            bad_rows.push_back((int32_t)p);
-            continue;
-        }
-        double* r = rates.data() + (size_t)p * S;
-        interp_mus(c, g, r);
-        if (rate_scale) for (int s = 0; s < S; ++s) r[s] *= rate_scale[p * S + s];
-        if (!rates_physical(c, r)) {
-            if (status) status[p] = BI_ST_UNPHYSICAL;
+        if (const int32_t bit = screen_point(c, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, 0, g,
+                                             rates.data() + (size_t)p * S)) {
+            if (status) status[p] = bit;
             bad_rows.push_back((int32_t)p);
             continue;
         }

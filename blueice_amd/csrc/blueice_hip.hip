@@ -29,7 +29,7 @@
 #include "bi_planning.h"
 #include "bi_planning_device.h"
 #include "bi_grad_mfma.h"
-#include "bi_grad_bb.h"
+#include "bi_grad.h"
 #include "bi_params.h"
 
 namespace {
@@ -609,12 +609,8 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
             ++c->n_bb_scan_launches;
             launch_scan_bb(c, plan->bb_kgt, dim3((unsigned)k.nbx, (unsigned)plan->n_groups, (unsigned)quads), ba);
         }
-        const int64_t n_slots = k.n_items * k.G;
-        const int lanes = k.nbx > 64 ? kThreads : 64;
-        const int per_block = kThreads / lanes;
-        hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream,
-                           (const double*)k.partial.p, (const unsigned*)k.pflags.p, k.nbx, k.G, lanes, n_slots, (const int64_t*)k.perm.p,
-                           (const double*)k.slot_lg.p, out, (int32_t*)plan->status.p);
+        launch_finish(c, (const double*)k.partial.p, (const unsigned*)k.pflags.p, k.nbx, k.G, k.n_items * k.G, (const int64_t*)k.perm.p,
+                      (const double*)k.slot_lg.p, out, (int32_t*)plan->status.p);
     }
     for (auto& k : plan->classes) {
         if (plan->use_scan || plan->bb_kgt) break;
@@ -649,13 +645,8 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
             }
             launch_morph_g(c, k.G, b, dim3((unsigned)k.nbx, (unsigned)ni), bb, nt);
             if (fuse) continue;
-            const int64_t n_slots = ni * k.G;
-            const int lanes = k.nbx > 64 ? kThreads : 64;
-            const int per_block = kThreads / lanes;
-            hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0,
-                               c->stream, (const double*)b.partial, (const unsigned*)b.pflags, k.nbx, k.G, lanes, n_slots,
-                               (const int64_t*)k.perm.p + i0 * k.G, (const double*)k.slot_lg.p + i0 * k.G, out,
-                               (int32_t*)plan->status.p);
+            launch_finish(c, b.partial, b.pflags, k.nbx, k.G, ni * k.G, (const int64_t*)k.perm.p + i0 * k.G,
+                          (const double*)k.slot_lg.p + i0 * k.G, out, (int32_t*)plan->status.p);
         }
     }
     if (plan->valid) {
@@ -789,8 +780,7 @@ int bi_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, con
     return rc;
 }
 
-
-// ---- value + analytic gradient in one pass ----------------------------------------------------
+// ---- one evaluation in two halves (value + analytic gradient, bi_eval_grad: bi_grad.h) ----------
 
 // The two halves of bi_eval(P = 1), for callers that evaluate several contexts at once (a sum of likelihoods, one
 // context per term): begin on every context, then end on every context -- the launches overlap.
@@ -819,198 +809,6 @@ int bi_eval_end(bi_ctx* c, double* out, int32_t* status) {
     HIP_TRY(c, hipSetDevice(c->device));
     if (status) *status = 0;
     return single_wait(c, c->pending_seq, out, status);
-}
-
-int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
-                 double* grad, int32_t* status) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (P < 0 || (P > 0 && (!ll || !grad))) return fail(c, BI_ERR_INVALID, "bad P / output pointers");
-    if (c->d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    if (c->bb_source >= 0) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        return eval_grad_bb(c, P, z, rate_scale, dataset, ll, grad, status);
-    }
-    const int S = c->S, d = c->d;
-    const int W = 1 + d + S;
-    if (W > kMaxG) return fail(c, BI_ERR_INVALID, "1 + d + S = %d exceeds %d gradient columns", W, kMaxG);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int G = std::max(2, pick_class(W, kMaxG));
-    const int de = (int)c->eff_axes.size();
-    const int nc = 1 << de, NS = nc * S;
-    bool any_neg = false;
-    for (int q = 0; q < S; ++q) any_neg |= (c->allow_neg[(size_t)q] != 0);
-    const bool unb = c->unbinned;       // extended unbinned likelihood: the rows are pdf values at the events, no counts
-    const bool sparse = !unb && c->sparse && c->compact_ready && c->ps_nonneg && !any_neg;
-    if (!unb && !sparse && !c->dense_counts) return fail(c, BI_ERR_STATE, "dataset counts are not resident in dense form");
-    const int64_t n_rows = c->A * S;
-    const double ninf = -std::numeric_limits<double>::infinity();
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-
-    // large batches: the descriptors are built on the device (k_grad_fill), one work item per point
-    if (!unb && c->device_plan_min > 0 && P >= c->device_plan_min && de <= 6 && P <= ((int64_t)1 << 26)) {
-        // one dataset, up to 32 streams: grouped by grid cell, two matrix products per 16-bin block (k_grad_mfma)
-        if (c->grad_mfma && P >= c->grad_mfma_min && c->scan_mfma && c->ps_finite && NS <= 32 && (!dataset || c->T == 1))
-            return eval_grad_mfma(c, P, z, rate_scale, dataset, sparse, ll, grad, status);
-        return eval_grad_device(c, P, z, rate_scale, dataset, sparse, G, ll, grad, status);
-    }
-
-    // Host half, per point and independent: phase 1 decides which points are evaluated at all (the reference's early
-    // exits), phase 2 fills the descriptor arrays of the live ones.  Both run on a few host threads for large batches --
-    // the batched profile-fit engine calls this once per optimiser iteration over every running problem, and at ~1.7 us
-    // per point single-threaded the host half was six times the kernels' time at 10^5 points.
-    std::vector<int64_t> corner_off((size_t)nc);
-    for (int k = 0; k < nc; ++k) corner_off[(size_t)k] = corner_offset(c, k);
-    const std::vector<double> ones((size_t)S, 1.0);
-    std::vector<int32_t> st_of((size_t)P, 0);
-    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
-        PointGeom g;
-        std::vector<double> r((size_t)S);
-        for (int64_t p = lo; p < hi; ++p) {
-            ll[p] = ninf;
-            for (int j = 0; j < d + S; ++j) grad[p * (d + S) + j] = qnan;
-            const int64_t ds = (dataset && !unb) ? dataset[p] : 0;
-            if (!unb && (ds < 0 || ds >= c->T)) { st_of[(size_t)p] = BI_ST_BAD_DATASET; continue; }
-            if (!point_geometry(c, z ? z + p * d : nullptr, g)) { st_of[(size_t)p] = BI_ST_OUT_OF_BOUNDS; continue; }
-            interp_mus(c, g, r.data());
-            const double* rs = rate_scale ? rate_scale + p * S : ones.data();
-            for (int s = 0; s < S; ++s) r[(size_t)s] *= rs[s];
-            if (!rates_physical(c, r.data())) st_of[(size_t)p] = BI_ST_UNPHYSICAL;
-        }
-    });
-    std::vector<int64_t> live;  // point index of every item
-    live.reserve((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        if (status) status[p] = st_of[(size_t)p];
-        if (!st_of[(size_t)p]) live.push_back(p);
-    }
-    const int64_t n_live = (int64_t)live.size();
-    std::vector<int64_t> rowoff((size_t)n_live * NS), cnt_off((size_t)n_live), perm((size_t)n_live * G, -1);
-    std::vector<double> coef((size_t)n_live * NS * G, 0.0), slot_lg((size_t)n_live * G, 0.0);
-    std::vector<int32_t> tiles((size_t)n_live);
-    parallel_for(n_live, 1024, [&](int64_t lo, int64_t hi) {
-        PointGeom g;
-        std::vector<double> mus((size_t)S), r((size_t)S), dmus((size_t)S * std::max(d, 1)), dw((size_t)nc * std::max(de, 1));
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t p = live[(size_t)i];
-            const int64_t ds = (dataset && !unb) ? dataset[p] : 0;
-            point_geometry(c, z ? z + p * d : nullptr, g);
-            interp_mus(c, g, mus.data());
-            const double* rs = rate_scale ? rate_scale + p * S : ones.data();
-            for (int s = 0; s < S; ++s) r[(size_t)s] = mus[(size_t)s] * rs[s];
-            // d w_c / d z_i for the effective axes: (+-1/delta_i) * prod_{j != i} w^(j)
-            for (int corner = 0; corner < nc; ++corner)
-                for (int ii = 0; ii < de; ++ii) {
-                    const int ax = c->eff_axes[(size_t)ii];
-                    double v = (((corner >> (de - 1 - ii)) & 1) ? 1.0 : -1.0) * g.inv_delta[ax];
-                    for (int j = 0; j < de; ++j) {
-                        if (j == ii) continue;
-                        const double t = g.t[c->eff_axes[(size_t)j]];
-                        v *= ((corner >> (de - 1 - j)) & 1) ? t : (1 - t);
-                    }
-                    dw[(size_t)corner * de + ii] = v;
-                }
-            // d mus_s / d z_i
-            for (int ii = 0; ii < de; ++ii)
-                for (int s = 0; s < S; ++s) {
-                    double v = 0.0;
-                    for (int corner = 0; corner < nc; ++corner)
-                        v += dw[(size_t)corner * de + ii] * c->h_mus[(size_t)((g.cell_anchor + corner_off[(size_t)corner]) * S + s)];
-                    dmus[(size_t)ii * S + s] = v;
-                }
-            const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
-            const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
-            const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * G;
-            int k = 0;
-            for (int corner = 0; corner < nc; ++corner)
-                for (int s = 0; s < S; ++s, ++k) {
-                    const int64_t row = (g.cell_anchor + corner_off[(size_t)corner]) * S + s;
-                    rowoff[ro + k] = row_base + row * row_stride;
-                    double* col = &coef[co + (size_t)k * G];
-                    const double w = g.w[(size_t)corner];
-                    col[0] = w * r[(size_t)s];
-                    for (int ii = 0; ii < de; ++ii)   // total derivative w.r.t. z: through the weights and through mus(z)
-                        col[1 + c->eff_axes[(size_t)ii]] = dw[(size_t)corner * de + ii] * r[(size_t)s] + w * dmus[(size_t)ii * S + s] * rs[s];
-                    col[1 + d + s] = w * mus[(size_t)s];
-                    if (sparse) {
-                        const double tz = c->h_Tz[(size_t)(ds * n_rows + row)];
-                        for (int q = 0; q < W; ++q) slot_lg[po + q] += col[q] * tz;
-                    }
-                }
-            if (unb) {
-                // -sum_s mu_s and its derivatives (likelihood.py:690): what the kernel's sums over the events are reduced by
-                double rsum = 0.0;
-                for (int s = 0; s < S; ++s) rsum += r[(size_t)s];
-                slot_lg[po] = rsum;
-                for (int ii = 0; ii < de; ++ii) {
-                    double v = 0.0;
-                    for (int s = 0; s < S; ++s) v += dmus[(size_t)ii * S + s] * rs[s];
-                    slot_lg[po + 1 + c->eff_axes[(size_t)ii]] = v;
-                }
-                for (int s = 0; s < S; ++s) slot_lg[po + 1 + d + s] = mus[(size_t)s];
-            } else
-                slot_lg[po] += c->h_lgsum[(size_t)ds];
-            for (int q = 0; q < W; ++q) perm[po + q] = i * W + q;
-            cnt_off[(size_t)i] = unb ? 0 : (sparse ? c->h_cnt_off[(size_t)ds] : ds * c->Bp);
-            tiles[(size_t)i] = (int32_t)(row_stride / kTile);
-        }
-    });
-    int max_tiles = 1;
-    for (int32_t t : tiles) max_tiles = std::max(max_tiles, (int)t);
-    const int64_t n_items = (int64_t)live.size();
-    if (n_items == 0) return BI_OK;
-    const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
-    const int nbx = (int)std::min<int64_t>(max_tiles, n_items == 1 ? slots : std::max<int64_t>(1, (4 * slots + n_items - 1) / n_items));
-    // descriptors: one packed copy; results: k_finish writes them straight into pinned host memory
-    DevBuf d_part, d_flag;
-    auto cleanup = [&]() { dev_free(d_part); dev_free(d_flag); };
-    PackedUpload pu;
-    const size_t out_bytes = (size_t)n_items * W * sizeof(double);
-    if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
-                                {cnt_off.data(), cnt_off.size() * sizeof(int64_t)}, {tiles.data(), tiles.size() * sizeof(int32_t)},
-                                {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
-                            out_bytes, pu)) ||
-        (rc = dev_alloc(c, d_part, (size_t)n_items * nbx * G * sizeof(double))) ||
-        (rc = dev_alloc(c, d_flag, (size_t)n_items * nbx * G * sizeof(unsigned)))) {
-        cleanup();
-        return rc;
-    }
-    double* h_out = (double*)pu.host_out();
-    LaunchArgs a{};
-    a.ps = sparse ? (const double*)c->ps_c.p : (const double*)c->ps.p;
-    a.counts = sparse ? (const double*)c->cnt_c.p : (const double*)c->counts.p;
-    a.B = c->B; a.Bp = c->Bp; a.n0 = NS; a.n_tiles = max_tiles; a.chunks = (int)c->tile_chunks;
-    a.outlier = c->outlier;
-    a.nan_S = (unb && !c->ps_finite) ? c->S : 0;
-    if (unb) a.counts = (const double*)c->ps.p;        // (never read in this mode: any valid device address)
-    const bool nt = !sparse && (c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1));
-    for (int64_t i0 = 0; i0 < n_items; i0 += 65535) {
-        const int64_t ni = std::min<int64_t>(65535, n_items - i0);
-        LaunchArgs b = a;
-        b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
-        b.coef = pu.dev<double>(1) + i0 * NS * G;
-        b.item_cnt = pu.dev<int64_t>(2) + i0;
-        b.item_tiles = pu.dev<int32_t>(3) + i0;
-        b.partial = (double*)d_part.p + i0 * nbx * G;
-        b.pflags = (unsigned*)d_flag.p + i0 * nbx * G;
-        launch_morph_grad(c, G, b, dim3((unsigned)nbx, (unsigned)ni), nt);
-        const int64_t n_slots = ni * G;
-        const int lanes = nbx > 64 ? kThreads : 64;
-        const int per_block = kThreads / lanes;
-        hipLaunchKernelGGL(k_finish, dim3((unsigned)((n_slots + per_block - 1) / per_block)), dim3(kThreads), 0, c->stream,
-                           (const double*)b.partial, (const unsigned*)b.pflags, nbx, G, lanes, n_slots,
-                           pu.dev<int64_t>(4) + i0 * G, pu.dev<double>(5) + i0 * G, h_out, (int32_t*)nullptr);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_grad: %s", hipGetErrorString(e));
-    for (int64_t i = 0; i < n_items; ++i) {
-        const int64_t p = live[(size_t)i];
-        ll[p] = h_out[(size_t)i * W];
-        for (int j = 0; j < d + S; ++j) grad[p * (d + S) + j] = (unb && !std::isfinite(ll[p])) ? qnan : h_out[(size_t)i * W + 1 + j];
-    }
-    return BI_OK;
 }
 
 // ---- toy-MC form ---------------------------------------------------------------------------
@@ -1115,11 +913,8 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
         return BI_OK;
     };
     PointGeom g;
-    if (!point_geometry(c, z, g)) return reject(BI_ST_OUT_OF_BOUNDS);
     std::vector<double> r((size_t)c->S);
-    interp_mus(c, g, r.data());
-    if (rate_scale) for (int s = 0; s < c->S; ++s) r[(size_t)s] *= rate_scale[s];
-    if (!rates_physical(c, r.data())) return reject(BI_ST_UNPHYSICAL);
+    if (const int32_t bit = screen_point(c, z, rate_scale, 0, g, r.data())) return reject(bit);
     const int nc = (int)g.w.size();
     const int NS = nc * c->S;
     std::vector<int64_t> rowoff((size_t)NS);
