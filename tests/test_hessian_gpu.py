@@ -7,6 +7,7 @@ from collections import OrderedDict
 import numpy as np
 import pytest
 
+import derivative_oracle as do
 import hessian_oracle as ho
 import model_zoo
 from golden_util import case_names, load_case
@@ -70,6 +71,14 @@ def check_against_oracle(ctx, c, zs, rs, H, ll, grad=None, unbinned_model=None):
             want_ll, want_g, want = ho.hessian_binned(c['model'], c['counts'], zs[p], rs[p])
         tol = 1e-9 * max(1.0, np.abs(want).max())
         np.testing.assert_allclose(H[p], want, rtol=0, atol=tol, err_msg='point %d' % p)
+        # per entry: within C 2^-52 cond of the exact derivative oracle (the small rate-rate entries included)
+        model = unbinned_model if unbinned_model is not None else c['model']
+        exact = do.derivatives(model, zs[p], rs[p], counts=None if unbinned_model is not None else c['counts'],
+                               unbinned=unbinned_model is not None, outlier=c['outlier'])
+        do.check_entries(H[p], exact['hess'], exact['hess_cond'], what='point %d hess' % p)
+        do.check_entries(ll[p], exact['ll'], exact['ll_cond'], what='point %d ll' % p)
+        if grad is not None:
+            do.check_entries(grad[p], exact['grad'], exact['grad_cond'], what='point %d grad' % p)
         assert abs(ll[p] - want_ll) <= 1e-10 * max(1.0, abs(want_ll))
         if grad is not None:
             np.testing.assert_allclose(grad[p], want_g, rtol=0, atol=1e-9 * max(1.0, np.abs(want_g).max()))
