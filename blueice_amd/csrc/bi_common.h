@@ -8,6 +8,7 @@
 //     tu_grad.hip         k_grad_mfma, k_morph_bbgrad                                        bi_k_grad_mfma.h, bi_k_bbgrad.h
 //     tu_scan_bb.hip      k_scan_bb (Beeston-Barlow scans on the matrix cores)               bi_k_scan_bb.h
 //     tu_hess.hip         k_morph_hess (value + gradient + Hessian of one point per item)    bi_k_hess.h
+//     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
@@ -87,3 +88,6 @@ void launch_grad_mfma(bi_ctx* c, int NS, dim3 grid, const GradMfmaArgs& a);
 int scan_bb_variant(int n0, int nc);
 void launch_scan_bb(bi_ctx* c, int kgt, dim3 grid, const BbScanArgs& a);
 int occupancy_scan_bb(int kgt);
+// k_stretch_propose / k_stretch_accept: one half-step of bi_sample_stretch (h = -1: stage the start positions)
+void launch_stretch_propose(bi_ctx* c, const StretchArgs& a);
+void launch_stretch_accept(bi_ctx* c, const StretchArgs& a);

@@ -209,6 +209,8 @@ struct bi_ctx {
     int64_t scan_bb = 1;                         // parameter: device-planned Beeston-Barlow batches on the matrix cores (k_scan_bb)
     int64_t scan_bb_min = 64;                    // ... from this many points on
     int64_t n_bb_scan_launches = 0;              // read-only
+    int64_t plan_refused = 0;                    // read-only last_plan_refused: the last device-planner call refused its batch (1 exact Beeston-Barlow totals, 2 infinite rates)
+    int64_t n_sampler_half_steps = 0;            // read-only: half-steps of bi_sample_stretch run so far
     int64_t device_plan_min = 512;               // batches at least this large are planned on the device
 
     // the events of the last bi_simulate_events into this context: coordinates [k][N], source index [N]

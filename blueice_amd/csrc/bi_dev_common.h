@@ -134,6 +134,35 @@ struct HessArgs {
     int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (as morph_tiles)
 };
 
+// k_stretch_propose / k_stretch_accept (bi_k_sampler.h): one half-step of the ensemble sampler; every pointer is device memory
+struct StretchArgs {
+    int64_t E;                 // ensembles
+    int W, F, d, S;            // walkers per ensemble, variables, shape parameters and sources of the model
+    int h;                     // the half that moves: walkers [h W/2, (h + 1) W/2); -1: stage every walker's own position (the start)
+    int64_t t;                 // step
+    int64_t first_ensemble;    // ensemble e of the call is ensemble first_ensemble + e of the seed's stream
+    uint32_t k0, k1;           // seed, low and high word
+    double a;                  // stretch scale
+    const int32_t* var_kind;   // [F] 0: shape parameter var_index, 1: rate multiplier of source var_index
+    const int32_t* var_index;
+    const double* z0;          // [E][d]  the ensembles' other shape settings
+    const double* scale0;      // [E][S]  ... rate scales of the sources whose multiplier does not float
+    const double* unit;        // [E][S]  rate scale per unit multiplier
+    const int64_t* dataset;    // [E] or NULL
+    const double* lo;          // [F]
+    const double* hi;
+    double* x;                 // [E][W][F] the walkers
+    double* ll;                // [E][W]    their log likelihoods
+    int64_t* n_accepted;       // [E][W]
+    double* z_dev;             // [n][d]   the proposals, in the layouts the resident planner reads
+    double* rs_dev;            // [n][S]
+    int64_t* ds_dev;           // [n]
+    const double* ll_prop;     // [n]   their log likelihoods and status words (accept)
+    const int32_t* st_prop;
+    double* chain;             // [E][W][F] row of step t
+    double* chain_ll;          // [E][W]
+};
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

@@ -3,6 +3,8 @@
 // bi_k_bbgrad.h, bi_k_scan.h, bi_scan_sorted.h and bi_grad_mfma.h, one translation unit each.
 #pragma once
 
+#include "bi_philox.h"
+
 namespace {
 
 // self-test hook: out[i] = bin_log(x[i])
@@ -752,23 +754,6 @@ __global__ __launch_bounds__(kDotThreads) void k_dataset_dot_tiled(const void* _
 // Counter-based Philox4x32-10 keyed by the seed, counter = (bin, dataset, attempt): every (dataset, bin) draw
 // is independent of launch geometry and can be regenerated, which is what lets the two-pass CSR build
 // (count, then scatter) see the same numbers twice.
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ double u53(uint32_t hi, uint32_t lo) {  // uniform on [0, 1) with 53 random bits
-    return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) * (1.0 / 9007199254740992.0);
-}
-
 // lam < 10: inversion by sequential search with one 53-bit uniform; p0 = exp(-lam) comes from a per-bin table (it is
 // the same for every toy)
 __device__ __forceinline__ double poisson_small(double lam, double p0, double u) {

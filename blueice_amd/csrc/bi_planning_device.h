@@ -970,7 +970,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
     if (e != hipSuccess) return abort_plan(fail(c, BI_ERR_HIP, "device planning: %s", hipGetErrorString(e)));
     memcpy(h_scal, c->plan_host, sizeof(h_scal));
     h_inf = h_scal[5];
-    if (h_inf > 0)
+    if (h_inf > 0 && (c->plan_refused = 2))
         return abort_plan(fail(c, BI_ERR_INVALID, "%lld points carry an infinite rate of a source that may go negative: those are answered on "
                                                   "the host (bi_plan_points / bi_eval with host arrays)", (long long)h_inf));
     const int64_t n_valid_all = h_scal[0];           // (table route: the share's window [7], [8] is the same arithmetic as below)

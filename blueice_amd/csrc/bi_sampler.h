@@ -1,0 +1,189 @@
+// bi_sampler.h -- the host loop of the ensemble sampler (bi_sample_stretch): E independent ensembles of W walkers, the context's
+// likelihood as the target density.  The points never leave the device: k_stretch_propose writes the proposals of the moving
+// half into the layouts the resident planner reads, the planner and the evaluation kernels of bi_plan_points_resident /
+// bi_run_plan take them where they lie, k_stretch_accept moves the walkers and appends to the chain in HBM, and chain, log
+// likelihoods and counters are copied to the host once, at the end.  What a half-step still costs on the host is the
+// planner's: it reads its counts back to size its launches (plan_report), the plan's status OR is a second read
+// (bi_plan_status), the plan is made and destroyed (buffers from the context's recycle cache, one stream synchronisation)
+// every half-step.  A plan reused across half-steps would remove most of that; it is not part of this file.  (The
+// reference's counterpart is emcee's loop of n_walkers x n_steps scalar likelihood calls, blueice/inference.py:254-321.)
+#pragma once
+
+namespace {
+
+struct SamplerBuffers {
+    DevBuf kind, index, z0, scale0, unit, dataset, lo, hi, x, ll, nacc, zp, rsp, dsp, llp, chain, chain_ll;
+    ~SamplerBuffers() {
+        for (DevBuf* b : {&kind, &index, &z0, &scale0, &unit, &dataset, &lo, &hi, &x, &ll, &nacc, &zp, &rsp, &dsp, &llp, &chain, &chain_ll})
+            dev_free(*b);
+    }
+};
+
+template <class T>
+std::vector<T> host_copy(const T* p, size_t n, T fill) {
+    return p ? std::vector<T>(p, p + n) : std::vector<T>(n, fill);
+}
+
+// plan and evaluate the n points staged in the proposal buffers into b.llp; the plan is handed back for its status words
+int sampler_evaluate(bi_ctx* c, SamplerBuffers& b, int64_t n, bi_plan** plan, int64_t* counters) {
+    int rc = plan_points_resident_impl(c, n, c->d > 0 ? (const double*)b.zp.p : nullptr, (const double*)b.rsp.p, (const int64_t*)b.dsp.p, 0, 1,
+                                       plan, false);
+    if (rc) return rc;
+    int32_t any = 0;
+    if ((rc = bi_run_plan(c, *plan, (double*)b.llp.p)) || (rc = bi_plan_status(c, *plan, &any))) {
+        bi_plan_destroy(c, *plan);
+        *plan = nullptr;
+        return rc;
+    }
+    if (counters) { counters[1] += n; counters[3] += bi_plan_launches(*plan); }
+    if (any & BI_ST_INTERNAL) {
+        bi_plan_destroy(c, *plan);
+        *plan = nullptr;
+        return fail(c, BI_ERR_HIP, "bi_sample_stretch: the device gave up waiting for a partial sum (in-launch reduction): GPU fault");
+    }
+    return BI_OK;
+}
+
+int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                   const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
+                   int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll, int64_t* n_accepted,
+                   int64_t* counters) {
+    const int d = c->d, S = c->S;
+    const size_t nE = (size_t)E, nW = (size_t)E * W;
+    SamplerBuffers b;
+    int rc;
+    // the chain stays in HBM until the end: it has to fit there
+    {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+        const double need = (double)n_steps * (double)nW * (F + 1) * sizeof(double);
+        if (need > (double)free_b + (double)c->cache_bytes)
+            return fail(c, BI_ERR_NOMEM, "bi_sample_stretch: the chain (%lld steps x %lld walkers x %d variables: %.3g bytes) is larger than the free "
+                                         "device memory (%zu bytes): run fewer steps per call", (long long)n_steps, (long long)nW, F, need, free_b);
+    }
+    // (host copies that live until the uploads have been waited for; absent optional arrays take their defaults)
+    const std::vector<int32_t> h_kind = host_copy(var_kind, (size_t)F, 0), h_index = host_copy(var_index, (size_t)F, 0);
+    const std::vector<double> h_z0 = host_copy(z0, nE * d, 0.0), h_scale0 = host_copy(scale0, nE * S, 1.0), h_unit = host_copy(unit, nE * S, 1.0),
+                              h_lo = host_copy(lo, (size_t)F, 0.0), h_hi = host_copy(hi, (size_t)F, 0.0), h_x = host_copy(x0, nW * F, 0.0);
+    const std::vector<int64_t> h_ds = host_copy(dataset, nE, (int64_t)0);
+    if ((rc = dev_upload(c, b.kind, h_kind)) || (rc = dev_upload(c, b.index, h_index)) || (rc = dev_upload(c, b.z0, h_z0)) ||
+        (rc = dev_upload(c, b.scale0, h_scale0)) || (rc = dev_upload(c, b.unit, h_unit)) || (rc = dev_upload(c, b.dataset, h_ds)) ||
+        (rc = dev_upload(c, b.lo, h_lo)) || (rc = dev_upload(c, b.hi, h_hi)) || (rc = dev_upload(c, b.x, h_x)))
+        return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t steps = (size_t)n_steps;
+    if ((rc = dev_alloc(c, b.ll, nW * sizeof(double))) || (rc = dev_alloc(c, b.nacc, nW * sizeof(int64_t))) ||
+        (rc = dev_alloc(c, b.zp, nW * std::max(d, 1) * sizeof(double))) || (rc = dev_alloc(c, b.rsp, nW * S * sizeof(double))) ||
+        (rc = dev_alloc(c, b.dsp, nW * sizeof(int64_t))) || (rc = dev_alloc(c, b.llp, nW * sizeof(double))) ||
+        (rc = dev_alloc(c, b.chain, std::max<size_t>(steps, 1) * nW * F * sizeof(double))) ||
+        (rc = dev_alloc(c, b.chain_ll, std::max<size_t>(steps, 1) * nW * sizeof(double))))
+        return rc;
+    HIP_TRY(c, hipMemsetAsync(b.nacc.p, 0, nW * sizeof(int64_t), c->stream));
+    StretchArgs s{};
+    s.E = E; s.W = W; s.F = F; s.d = d; s.S = S;
+    s.first_ensemble = first_ensemble;
+    s.k0 = (uint32_t)seed; s.k1 = (uint32_t)(seed >> 32);
+    s.a = a;
+    s.var_kind = (const int32_t*)b.kind.p; s.var_index = (const int32_t*)b.index.p;
+    s.z0 = (const double*)b.z0.p; s.scale0 = (const double*)b.scale0.p; s.unit = (const double*)b.unit.p;
+    s.dataset = dataset ? (const int64_t*)b.dataset.p : nullptr;
+    s.lo = (const double*)b.lo.p; s.hi = (const double*)b.hi.p;
+    s.x = (double*)b.x.p; s.ll = (double*)b.ll.p; s.n_accepted = (int64_t*)b.nacc.p;
+    s.z_dev = (double*)b.zp.p; s.rs_dev = (double*)b.rsp.p; s.ds_dev = (int64_t*)b.dsp.p;
+    s.ll_prop = (const double*)b.llp.p;
+    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
+
+    // the start: every walker's own log likelihood, which must be finite
+    bi_plan* plan = nullptr;
+    s.h = -1;
+    launch_stretch_propose(c, s);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = sampler_evaluate(c, b, (int64_t)nW, &plan, counters))) return rc;
+    {
+        std::vector<double> h_ll(nW);
+        std::vector<int32_t> h_st(nW);
+        hipError_t e = hipMemcpyAsync(h_ll.data(), b.llp.p, nW * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_st.data(), plan->status.p, nW * sizeof(int32_t), hipMemcpyDefault, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(b.ll.p, b.llp.p, nW * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        bi_plan_destroy(c, plan);
+        plan = nullptr;
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_sample_stretch (start): %s", hipGetErrorString(e));
+        for (size_t w = 0; w < nW; ++w)
+            for (int v = 0; v < F; ++v)
+                if (!(h_x[w * F + v] >= h_lo[(size_t)v] && h_x[w * F + v] <= h_hi[(size_t)v]))
+                    return fail(c, BI_ERR_INVALID, "bi_sample_stretch: start walker %lld of ensemble %lld lies outside [lo, hi] in variable %d (%g)",
+                                (long long)(w % (size_t)W), (long long)(w / (size_t)W), v, h_x[w * F + v]);
+        for (size_t w = 0; w < nW; ++w)
+            if (!std::isfinite(h_ll[w]) || h_st[w] != 0)
+                return fail(c, BI_ERR_INVALID, "bi_sample_stretch: the log likelihood of start walker %lld of ensemble %lld is not finite "
+                                               "(%g, status %d): every walker must start at a point of non-zero likelihood",
+                            (long long)(w % (size_t)W), (long long)(w / (size_t)W), h_ll[w], (int)h_st[w]);
+    }
+
+    const int64_t n = E * (W / 2);
+    for (int64_t t = 0; t < n_steps; ++t)
+        for (int h = 0; h < 2; ++h) {
+            s.t = t; s.h = h;
+            s.chain = (double*)b.chain.p + (size_t)t * nW * F;
+            s.chain_ll = (double*)b.chain_ll.p + (size_t)t * nW;
+            launch_stretch_propose(c, s);
+            HIP_TRY(c, hipGetLastError());                      // (nothing is launched after a failed launch)
+            if ((rc = sampler_evaluate(c, b, n, &plan, counters))) return rc;
+            s.st_prop = (const int32_t*)plan->status.p;
+            launch_stretch_accept(c, s);
+            const hipError_t e = hipGetLastError();
+            bi_plan_destroy(c, plan);                           // (waits for the stream: the accept kernel reads the plan's status words)
+            plan = nullptr;
+            if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_sample_stretch (accept): %s", hipGetErrorString(e));
+            ++c->n_sampler_half_steps;
+            if (counters) ++counters[0];
+        }
+    // one copy of chain, log likelihoods and acceptance counters at the end of the call
+    if (n_steps > 0) {
+        HIP_TRY(c, hipMemcpyAsync(chain, b.chain.p, steps * nW * F * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ll, b.chain_ll.p, steps * nW * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(n_accepted, b.nacc.p, nW * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (counters)
+        for (size_t w = 0; w < nW; ++w) counters[2] += n_accepted[w];
+    return BI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                      const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                      const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll,
+                      int64_t* n_accepted, int64_t* counters) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    c->plan_refused = 0;
+    if (W < 2 || (W & 1)) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: the stretch move needs an even number of walkers >= 2 (got %d): the ensemble moves in two halves", W);
+    if (F < 1) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: need F >= 1 variables (got %d)", F);
+    if (!(a > 1.0) || !std::isfinite(a)) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: the stretch scale a must be > 1 (got %g)", a);
+    if (E < 1 || n_steps < 0 || n_steps > (int64_t)1 << 31 || first_ensemble < 0 || first_ensemble + E > (int64_t)1 << 32 ||
+        E * (int64_t)W > (int64_t)1 << 30)
+        return fail(c, BI_ERR_INVALID, "bi_sample_stretch: need E >= 1, E * W <= 2^30, 0 <= n_steps <= 2^31 and ensembles within [0, 2^32)");
+    if (!var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !n_accepted || (n_steps > 0 && (!chain || !ll)))
+        return fail(c, BI_ERR_INVALID, "bi_sample_stretch: NULL argument");
+    for (int j = 0; j < F; ++j)
+        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
+            (var_kind[j] != 0 && var_kind[j] != 1))
+            return fail(c, BI_ERR_INVALID, "bi_sample_stretch: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
+    if (dataset)
+        for (int64_t e = 0; e < E; ++e)
+            if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: dataset %lld of ensemble %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);
+    HIP_TRY(c, hipSetDevice(c->device));
+    try {
+        return sample_stretch(c, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble, chain, ll,
+                              n_accepted, counters);
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "bi_sample_stretch: out of host memory");
+    }
+}
+
+}  // extern "C"

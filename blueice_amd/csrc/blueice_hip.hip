@@ -480,8 +480,13 @@ int bi_plan_points_share(bi_ctx* c, int64_t P, const double* z, const double* ra
     return plan_points(c, P, z, rate_scale, dataset, out, /*transient=*/false, share_rank, share_world);
 }
 
-int bi_plan_points_resident(bi_ctx* c, int64_t P, const double* z_dev, const double* rate_scale_dev, const int64_t* dataset_dev,
-                            int share_rank, int share_world, bi_plan** out) {
+}  // extern "C"
+
+namespace {
+
+// bi_plan_points_resident; check_pointers = false: the caller made the buffers itself (bi_sample_stretch: its proposal buffers)
+int plan_points_resident_impl(bi_ctx* c, int64_t P, const double* z_dev, const double* rate_scale_dev, const int64_t* dataset_dev,
+                              int share_rank, int share_world, bi_plan** out, bool check_pointers) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (!out) return fail(c, BI_ERR_INVALID, "out is NULL");
@@ -496,7 +501,7 @@ int bi_plan_points_resident(bi_ctx* c, int64_t P, const double* z_dev, const dou
     if (P == 0) return plan_points(c, 0, nullptr, nullptr, nullptr, out);
     const void* ptrs[3] = {c->d > 0 ? (const void*)z_dev : nullptr, rate_scale_dev, dataset_dev};
     const char* names[3] = {"z_dev", "rate_scale_dev", "dataset_dev"};
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < 3 && check_pointers; ++i) {
         if (!ptrs[i]) continue;
         hipPointerAttribute_t at;
         const hipError_t e = hipPointerGetAttributes(&at, ptrs[i]);
@@ -511,11 +516,21 @@ int bi_plan_points_resident(bi_ctx* c, int64_t P, const double* z_dev, const dou
                                      "evaluations need the compacted templates (sparse mode, budget) or bi_eval_datasets");
     // (sources that may go negative: an infinite rate among the points is found by the planner itself and refused;
     //  Beeston-Barlow: refused when some point needs the host planner's exact totals)
+    c->plan_refused = 0;
     rc = plan_points_device(c, P, z_dev, rate_scale_dev, dataset_dev, sparse, out, share_rank, share_world, true, false);
-    if (rc == kPlanNeedsHost)
+    if (rc == kPlanNeedsHost && (c->plan_refused = 1))
         return fail(c, BI_ERR_INVALID, "resident points are planned on the device: this Beeston-Barlow batch has points at which some bin can "
                                        "have U_b == 0 (or bb_exact = 1) and needs the host planner's exact totals (bi_plan_points)");
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_plan_points_resident(bi_ctx* c, int64_t P, const double* z_dev, const double* rate_scale_dev, const int64_t* dataset_dev,
+                            int share_rank, int share_world, bi_plan** out) {
+    return plan_points_resident_impl(c, P, z_dev, rate_scale_dev, dataset_dev, share_rank, share_world, out, true);
 }
 
 int bi_plan_share_info(const bi_plan* p, int64_t* n_valid, int64_t* lo, int64_t* hi) {
@@ -2002,3 +2017,4 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 
 #include "bi_fit.h"
 #include "bi_hess.h"
+#include "bi_sampler.h"

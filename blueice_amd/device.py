@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import as_f64, ptr
-from .exceptions import DeviceError, NotPreparedException
+from .exceptions import DeviceError, NotPreparedException, PlannerRefused
 
 __all__ = ['DeviceContext', 'DeviceBuffer', 'EvalPlan', 'default_device']
 
@@ -348,6 +348,38 @@ class DeviceContext:
                                              ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks), ptr(kinks), float(gtol), int(max_iter),
                                              ptr(x), ptr(f), ptr(flags), ptr(counters)))
         return 0
+
+    def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0):
+        """bi_sample_stretch: n_steps stretch-move steps of E ensembles of W walkers with this context's likelihood as the
+        target.  x0 [E, W, F]; z0 [E, d], scale0 / unit [E, S], dataset [E] or None as `fit_batched`.
+        -> (chain [n_steps, E, W, F], ll [n_steps, E, W], n_accepted [E, W], counters [4])."""
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        E, W2, F = x0.shape
+        if W2 != W:
+            raise ValueError("x0 must be [E, W, F]")
+        kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
+        z0 = np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64).reshape(-1, self.d), (E, self.d))) if self.d else np.zeros((E, 0))
+        scale0 = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        unit = np.ascontiguousarray(np.broadcast_to(np.asarray(unit, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        if dataset is not None:
+            dataset = np.ascontiguousarray(np.broadcast_to(np.asarray(dataset, dtype=np.int64), (E,)))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        if len(kind) != F or len(index) != F or len(lo) != F or len(hi) != F:
+            raise ValueError("kind, index, lo and hi must have one entry per variable")
+        n_steps = int(n_steps)
+        chain = np.empty((max(n_steps, 0), E, W, F))
+        ll = np.empty((max(n_steps, 0), E, W))
+        n_acc = np.zeros((E, W), dtype=np.int64)
+        counters = np.zeros(4, dtype=np.int64)
+        rc = self._lib.bi_sample_stretch(self._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0), ptr(unit),
+                                         ptr(dataset), ptr(x0), ptr(lo), ptr(hi), n_steps, float(a), int(seed) & (2 ** 64 - 1),
+                                         int(first_ensemble), ptr(chain), ptr(ll), ptr(n_acc), ptr(counters))
+        if rc == _capi.ERR_INVALID:
+            msg = self._lib.bi_last_error(self._h).decode()
+            if self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:             # the resident planner's two refusals
+                raise PlannerRefused(msg)
+        self._check(rc)
+        return chain, ll, n_acc, counters
 
     def eval_datasets(self, z, rate_scale=None, t0=0, t1=None):
         """One parameter point against datasets [t0, t1) -> (ll [t1-t0], status)."""

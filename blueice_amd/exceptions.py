@@ -4,7 +4,7 @@ including its historical spelling `NoOpimizationNecessary`, so user `except` cla
 
 __all__ = ['BlueIceException', 'NoOpimizationNecessary', 'OptimizationFailed', 'NotPreparedException',
            'NoShapeParameters', 'InvalidParameter', 'InvalidParameterSpecification', 'PDFNotComputedException',
-           'DeviceError']
+           'DeviceError', 'PlannerRefused']
 
 
 class BlueIceException(Exception):
@@ -41,3 +41,8 @@ class PDFNotComputedException(BlueIceException):
 
 class DeviceError(BlueIceException):
     """libblueice_hip reported a failure (missing library, no GPU, HIP error)."""
+
+
+class PlannerRefused(DeviceError, ValueError):
+    """The device planner refuses a batch it cannot plan exactly (Beeston-Barlow points that need exact totals, infinite
+    rates of sources that may go negative): the caller answers it on the host.  A ValueError like every BI_ERR_INVALID."""

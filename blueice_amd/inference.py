@@ -2,8 +2,12 @@
 (blueice/inference.py:57-178) plus a batched `best_anchor` (:34-54).
 
 These only need `lf(**kwargs) -> float`, `lf.rate_parameters`, `lf.shape_parameters`,
-`lf.get_bounds`, `lf.pdf_base_config`; scipy.optimize is used as is.  The emcee driver and plotting are out of scope
-(SURVEY.md section 2).
+`lf.get_bounds`, `lf.pdf_base_config`; scipy.optimize is used as is.
+
+Posteriors: `sample_posterior` (blueice_amd.sampler) runs an affine-invariant ensemble sampler over the floating parameters
+-- on the device from proposal to chain where the likelihood is one device context -- and `bestfit_emcee` is the
+reference's emcee driver (blueice/inference.py:254-321) on top of it; emcee itself is not used.  `plot_likelihood_ratio`
+(:392-443) draws what `likelihood_ratio_scan` computes.
 
 Uncertainties: `hesse` turns fitted values into the covariance (-H)^-1 of the floating parameters from the device Hessian
 of the likelihood (`values_gradients_hessians`: bi_eval_hess, one call for a whole ensemble of fits), and
@@ -27,10 +31,12 @@ from scipy.optimize import brentq, minimize
 from .exceptions import NoOpimizationNecessary, OptimizationFailed
 from .hessian import to_log10
 from .profile import bestfit_batched, supports_batched_fits
+from .sampler import sample_posterior
 from .utils import is_numeric
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
-           'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit']
+           'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
+           'plot_likelihood_ratio']
 
 
 def best_anchor(lf):
@@ -317,6 +323,48 @@ def bestfit_minuit(lf, minimize_kwargs=None, rates_in_log_space=False, **kwargs)
     return result, float(ll)
 
 
+def bestfit_emcee(ll, quiet=False, return_errors=False, return_samples=False, n_walkers=40, n_steps=200, n_burn_in=100,
+                  n_threads=1, seed=0, **kwargs):
+    """The reference's `bestfit_emcee` (blueice/inference.py:254-321) without emcee: `sample_posterior` runs the ensemble
+    (the stretch move emcee defaults to; the reference's start, guess * U(0.95, 1.05) per walker) and the point estimate is
+    read off the chain the way the reference's code does -- `n_steps` steps are run, the first `n_burn_in` of them dropped.
+    -> ({name: posterior median}, ll at the medians)
+       [, {name: half the width of the central 68.27 % interval} with return_errors]
+       [, samples [-1, F], walker by walker, with return_samples].
+    quiet=False prints the mean acceptance fraction and, when `corner` can be imported, draws its corner plot of the whole
+    chain.  n_threads is accepted and ignored (the walkers of a half-step are one device batch); seed: the random stream
+    (extension).  kwargs: `guess` and parameters held fixed, as `make_objective`; `engine`, `p0`, `a` go to
+    `sample_posterior`; `livetime_days` goes to the sampler and to the final likelihood call.  One dataset only:
+    `datasets` / `first_ensemble` belong to `sample_posterior`."""
+    for key in ('datasets', 'first_ensemble'):
+        if key in kwargs:
+            raise ValueError("bestfit_emcee fits one dataset: %s is an option of sample_posterior" % key)
+    sampler_only = {k: kwargs.pop(k) for k in ('engine', 'p0', 'a') if k in kwargs}
+    run = sample_posterior(ll, n_walkers=n_walkers, n_steps=n_steps, seed=seed, **sampler_only, **kwargs)
+    kept = run.flat(discard=n_burn_in)                                 # [W * (n_steps - n_burn_in), F]
+    if not quiet:
+        print("Mean acceptance fraction: %.3f" % float(run.acceptance_fraction.mean()))
+        try:
+            import corner
+        except ImportError:
+            corner = None
+        if corner is not None:
+            from matplotlib import pyplot
+            corner.corner(run.flat(), labels=run.names, show_titles=True, range=[0.99 for _ in run.names])
+            pyplot.show()
+    # central 68.27 % interval and median per parameter, in one pass over the kept samples
+    one_sigma = float(stats.norm.cdf(1.0) - stats.norm.cdf(-1.0))
+    q_lo, q_mid, q_hi = np.quantile(kept, [0.5 - one_sigma / 2, 0.5, 0.5 + one_sigma / 2], axis=0)
+    medians = OrderedDict(zip(run.names, q_mid))
+    held = {k: v for k, v in kwargs.items() if k != 'guess'}
+    at_median = ll(**held, **medians)
+    if return_errors:
+        return medians, at_median, OrderedDict(zip(run.names, 0.5 * (q_hi - q_lo)))
+    if return_samples:
+        return medians, at_median, kept
+    return medians, at_median
+
+
 def _first_crossing(tfun, a, b, xtol=1e-11, points_per_round=16, max_rounds=12):
     """The root of t between a and b that lies nearest to a, by rounds of batched evaluations: every round evaluates a
     fan of hypotheses inside the current bracket in ONE call of tfun(h [n]) -> t [n] -- uniformly spaced at first, then
@@ -467,3 +515,35 @@ def likelihood_ratio_scan(lf, *space, bestfit_routine=None, fit_options=None, **
         for idx in np.ndindex(*grids[0].shape):
             ll[idx] = fit(lf, **dict(kwargs, **{n: float(g[idx]) for n, g in zip(names, grids)}))[1]
     return np.nanmax(ll) - ll
+
+
+_BESTFIT_ROUTINES = dict(scipy=bestfit_scipy, minuit=bestfit_minuit, emcee=bestfit_emcee, device=bestfit_device)
+
+
+def plot_likelihood_ratio(lf, *space, vmax=15, bestfit_routine=None, plot_kwargs=None, **kwargs):
+    """Draw the -log likelihood ratio over a 1-d or 2-d grid of parameter values with matplotlib (the reference's
+    `plot_likelihood_ratio`, blueice/inference.py:392-443, into the current axes): a curve for one (name, values) tuple, a
+    colour mesh with its colour bar for two.  vmax: the top of the y axis / colour scale; plot_kwargs go to the curve / mesh;
+    parameters in kwargs are fixed, all others are fitted at every grid point -- the numbers are `likelihood_ratio_scan`'s
+    (one batched device call, or the batched profile-fit engine), unless a `bestfit_routine` (a callable, or 'scipy' /
+    'minuit' / 'emcee' / 'device') asks for the point-by-point loop.  Returns the values drawn (the reference returns
+    nothing)."""
+    from matplotlib import pyplot
+    if isinstance(bestfit_routine, str):
+        if bestfit_routine not in _BESTFIT_ROUTINES:
+            raise ValueError("unknown bestfit_routine %r" % bestfit_routine)
+        bestfit_routine = _BESTFIT_ROUTINES[bestfit_routine]
+    ratio = likelihood_ratio_scan(lf, *space, bestfit_routine=bestfit_routine, **kwargs)
+    style = dict(plot_kwargs or {})
+    axes = pyplot.gca()
+    title = "-Log likelihood ratio"
+    axis_values = [np.asarray(values, dtype=float) for _, values in space]
+    if len(space) == 1:
+        axes.plot(axis_values[0], ratio, **style)
+        axes.set(xlabel=space[0][0], ylabel=title, xlim=(axis_values[0].min(), axis_values[0].max()), ylim=(0, vmax))
+    else:
+        # (a mesh over the two axes' values: rows of `ratio` run along the first parameter, which is drawn horizontally)
+        mesh = axes.pcolormesh(axis_values[0], axis_values[1], ratio.T, vmax=vmax, shading='nearest', **style)
+        axes.figure.colorbar(mesh, ax=axes, label=title)
+        axes.set(xlabel=space[0][0], ylabel=space[1][0])
+    return ratio

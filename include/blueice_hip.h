@@ -262,6 +262,45 @@ int bi_fit_batched(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const
                    const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, double* x_out,
                    double* f_out, int32_t* flags_out, int64_t* counters);
 
+/* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
+ * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
+ * n_walkers x n_steps scalar likelihood calls (bestfit_emcee, blueice/inference.py:254-321).  The variables are described as
+ * for bi_fit_batched (var_kind / var_index, z0 [E][d], scale0 [E][S], unit [E][S], dataset [E] or NULL: ensemble e samples
+ * the likelihood of dataset[e] with its other settings z0[e], scale0[e]).  x0 [E][W][F]: the start; lo / hi [F]: the box
+ * (+-inf = none).  Between the likelihood evaluations nothing leaves the device: a half-step is k_stretch_propose, the device
+ * planner and evaluation kernels of bi_plan_points_resident / bi_run_plan on the proposal buffers, k_stretch_accept; the host
+ * reads the plan's status OR once per half-step, and chain [n_steps][E][W][F], ll [n_steps][E][W] (state of every walker after
+ * step t and its log likelihood) and n_accepted [E][W] once at the end.  counters [4] or NULL: half-steps, likelihood
+ * evaluations, accepted moves, evaluation launches.
+ *
+ * The random stream and the arithmetic, exactly (binary64, every operation rounded on its own, no fused multiply-add):
+ *   step t = 0 .. n_steps-1, half h = 0, 1: walkers k in [h W/2, (h+1) W/2) of every ensemble move, the others are the
+ *   complementary set; the state they see is the one the previous half-step left.  For ensemble e and moving walker k
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter = (k, first_ensemble + e, t, 0x53545200 | h), key = (seed mod 2^32, seed >> 32))
+ *     (round constants 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85: per round, from counter (c0, c1, c2, c3)
+ *      and key (k0, k1):  c0' = hi(0xCD9E8D57 c2) ^ c1 ^ k0, c1' = lo(0xCD9E8D57 c2), c2' = hi(0xD2511F53 c0) ^ c3 ^ k1,
+ *      c3' = lo(0xD2511F53 c0), then the key is incremented; ten rounds)
+ *     u_z = ((r0 >> 5) 2^26 + (r1 >> 6)) 2^-53              uniform in [0, 1)
+ *     j   = (1 - h) W/2 + ((r2 (W/2)) >> 32)                the partner, in the other half (64-bit product)
+ *     u_a = (r3 + 0.5) 2^-32
+ *     g = (a - 1) u_z + 1;  z = (g g) / a                    (IEEE division)
+ *     y_i = x_j,i + z (x_k,i - x_j,i)                        i.e. s = x_k,i - x_j,i; p = z s; y_i = x_j,i + p
+ *   the point evaluated is z_i = y_v for a shape variable, rate_scale_s = y_v unit[e][s] for a rate multiplier.  The move is
+ *   accepted iff lo <= y <= hi in every variable, ll(y) is finite with status word 0, and
+ *     log(u_a) < (((F - 1) log z) + ll(y)) - ll(x_k)
+ *   (proposals outside the anchor box or with unphysical rates are -inf as in bi_eval and never accepted; so is a point at
+ *   which a Beeston-Barlow assertion would fire).  Ensemble e of a call is ensemble first_ensemble + e of the seed's stream:
+ *   a joint run over E ensembles and E runs of one ensemble each draw the same numbers.
+ * Errors (BI_ERR_INVALID unless noted, reason in bi_last_error): W odd or < 2, F < 1, a <= 1, a start walker outside [lo, hi]
+ * or whose log likelihood is not finite (so no stored position ever lies outside the box), a chain larger than the free
+ * device memory (BI_ERR_NOMEM), and whatever bi_plan_points_resident
+ * refuses (Beeston-Barlow points that need exact totals, infinite rates of sources that may go negative).  Read-only parameter
+ * n_sampler_half_steps counts the half-steps run on the context. */
+int bi_sample_stretch(bi_ctx* ctx, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                      const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                      const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll,
+                      int64_t* n_accepted, int64_t* counters);
+
 /* One parameter point against datasets [t0, t1): the toy-MC form.  mu_b / log mu_b are computed
  * once and every dataset reduces sum_b xlogy(n, mu) against them.  Not available with
  * Beeston-Barlow (mu then depends on the data).  out [t1 - t0]. */
@@ -480,7 +519,9 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     fails does the same before it gives up
  *   debug_skip_post, debug_late_post   (write; fault injection for tests) block k of the NEXT launch that finishes through the
  *                     mailbox never posts its partial sum / posts it after the collector has given up; consumed by that launch
- * read-only: tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total;
+ * read-only: n_sampler_half_steps (half-steps of bi_sample_stretch so far), last_plan_refused (the last bi_plan_points_resident /
+ *            bi_sample_stretch planning refused its batch: 1 Beeston-Barlow points that need exact totals, 2 infinite rates of sources that may
+ *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total;
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
  *            the last plan, and the resident blocks per CU it sized them by), last_toy_method (1 = event by event);
  *   single_calls, single_ns_host, single_ns_launch, single_ns_wait   wall time (ns, summed over single_calls calls) of
