@@ -52,8 +52,12 @@ SIGNATURES = {
     'bi_eval_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     'bi_minimize_batched': (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
+    'bi_fit_batched_gauss': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
+                                       _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
                                     _p, _p, _p, _p]),
+    'bi_sample_stretch_gauss': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
+                                          _p, _p, _p, _p, _p, _p, _p]),
     'bi_eval_datasets': (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points_device': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),

@@ -91,3 +91,5 @@ int occupancy_scan_bb(int kgt);
 // k_stretch_propose / k_stretch_accept: one half-step of bi_sample_stretch (h = -1: stage the start positions)
 void launch_stretch_propose(bi_ctx* c, const StretchArgs& a);
 void launch_stretch_accept(bi_ctx* c, const StretchArgs& a);
+// k_stretch_start_density: the start walkers' log likelihoods (ll_prop) -> their log densities ll + p (ll)
+void launch_stretch_start_density(bi_ctx* c, const StretchArgs& a);

@@ -161,6 +161,11 @@ struct StretchArgs {
     const int32_t* st_prop;
     double* chain;             // [E][W][F] row of step t
     double* chain_ll;          // [E][W]
+    // Gaussian constraint terms on the variables (bi_sample_stretch_gauss): `ll` above then holds the log density ll + p.
+    // prior_sigma NULL: no term on any variable; prior_const NULL: 0; both NULL: the kernels do what they did without terms
+    const double* prior_mean;  // [F]
+    const double* prior_sigma; // [F]  +inf: no term on that variable
+    const double* prior_const; // [E]
 };
 
 namespace {

@@ -11,6 +11,7 @@
 //   bi_minimize_batched   the optimiser over an objective callback  fun(x [n][F], rows [n]) -> f [n], g [n][F]
 //   bi_fit_batched        ... with the device likelihood as the objective, no Python between the iterations: optimiser
 //                         variable j is a shape parameter (z_i = x_j) or a rate multiplier (rate_scale_s = x_j * unit_s)
+//   bi_fit_batched_gauss  ... plus Gaussian constraint terms on the optimiser variables: f = -(ll + p)
 #pragma once
 
 #include <new>
@@ -369,7 +370,7 @@ int minimize_batched(bi_objective_fn fun, void* user, int64_t P, int F, const do
     return BI_OK;
 }
 
-// the device likelihood as the objective: f = -ll, g = -d ll / d x
+// the device likelihood as the objective: f = -(ll + p), g = -d (ll + p) / d x, p the Gaussian constraint terms (none: p = 0)
 struct DeviceObjective {
     bi_ctx* c;
     int F;
@@ -379,6 +380,9 @@ struct DeviceObjective {
     const double* scale0;       // [P][S]   the problems' rate scales for FIXED multipliers
     const double* unit;         // [P][S]   d rate_scale / d multiplier (live time, efficiency)
     const int64_t* dataset;     // [P] or NULL
+    const double* prior_mean;   // [F]      Gaussian constraint on variable j (all three NULL: no terms) ...
+    const double* prior_sigma;  // [F]      ... +inf: none on that variable
+    const double* prior_const;  // [P] or NULL: what of p does not depend on x
     std::vector<double> z, sc, ll, grad;
     std::vector<int64_t> ds;
     std::vector<int32_t> st;
@@ -417,11 +421,24 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
         double ll = o->ll[(size_t)i];
         if (st & (BI_ST_BB_ROOT1 | BI_ST_BB_NEG)) ll = qnan;          // a point to avoid, not an exception (bb_assert = 'nan')
         const bool bad = (st & (BI_ST_OUT_OF_BOUNDS | BI_ST_UNPHYSICAL)) != 0;
+        if (o->prior_sigma) {
+            // the terms as include/blueice_hip.h states them: every operation rounded on its own (-ffp-contract=off)
+            double pr = o->prior_const ? o->prior_const[p] : 0.0;
+            for (int j = 0; j < F; ++j)
+                if (std::isfinite(o->prior_sigma[j])) {
+                    const double t = (x[i * F + j] - o->prior_mean[j]) / o->prior_sigma[j];
+                    pr = pr - 0.5 * (t * t);
+                }
+            ll = ll + pr;
+        }
         f[i] = bad ? std::numeric_limits<double>::infinity() : -ll;
         for (int j = 0; j < F; ++j) {
             double v = o->var_kind[j] == 0 ? o->grad[(size_t)i * (d + S) + o->var_index[j]]
                                            : o->grad[(size_t)i * (d + S) + d + o->var_index[j]] * o->unit[p * S + o->var_index[j]];
-            g[i * F + j] = bad ? qnan : -v;
+            v = -v;
+            if (o->prior_sigma && std::isfinite(o->prior_sigma[j]))
+                v = v + ((x[i * F + j] - o->prior_mean[j]) / o->prior_sigma[j]) / o->prior_sigma[j];
+            g[i * F + j] = bad ? qnan : v;
         }
     }
     return BI_OK;
@@ -440,6 +457,58 @@ bool kinks_are_valid(int F, const int32_t* n_kinks, const double* kinks) {
         off += n_kinks[j];
     }
     return true;
+}
+
+// the constraint arrays of the *_gauss entry points: nullptr = fine, else what is wrong with them
+const char* gauss_terms_invalid(int F, int64_t P, const double* mean, const double* sigma, const double* konst) {
+    if (!mean || !sigma) return "prior_mean and prior_sigma must not be NULL (prior_sigma = +inf: no term)";
+    for (int j = 0; j < F; ++j) {
+        if (mean[j] != mean[j] || sigma[j] != sigma[j]) return "NaN in prior_mean / prior_sigma";
+        if (!(sigma[j] > 0)) return "prior_sigma must be > 0 (+inf: no term on that variable)";
+        if (std::isfinite(sigma[j]) && !std::isfinite(mean[j])) return "prior_mean of a constrained variable must be finite";
+    }
+    if (konst)
+        for (int64_t p = 0; p < P; ++p)
+            if (konst[p] != konst[p]) return "NaN in prior_const";
+    return nullptr;
+}
+
+// no finite sigma and no constants: the call has no terms at all
+bool gauss_terms_empty(int F, const double* sigma, const double* konst) {
+    if (konst) return false;
+    for (int j = 0; j < F; ++j)
+        if (std::isfinite(sigma[j])) return false;
+    return true;
+}
+
+// bi_fit_batched (no terms: the three prior arrays NULL) and bi_fit_batched_gauss
+int fit_batched(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0, const double* scale0,
+                const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi, const int32_t* n_kinks,
+                const double* kinks, double gtol, int max_iter, const double* prior_mean, const double* prior_sigma,
+                const double* prior_const, double* x_out, double* f_out, int32_t* flags_out, int64_t* counters) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !x_out ||
+        !f_out || !flags_out)
+        return fail(c, BI_ERR_INVALID, "bi_fit_batched: bad arguments");
+    for (int j = 0; j < F; ++j)
+        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
+            (var_kind[j] != 0 && var_kind[j] != 1))
+            return fail(c, BI_ERR_INVALID, "bi_fit_batched: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
+    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "bi_fit_batched: n_kinks must be >= 0 and the kinks of a variable ascending");
+    if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
+    DeviceObjective o{};
+    o.c = c; o.F = F; o.var_kind = var_kind; o.var_index = var_index; o.z0 = z0; o.scale0 = scale0; o.unit = unit; o.dataset = dataset;
+    o.prior_mean = prior_mean; o.prior_sigma = prior_sigma; o.prior_const = prior_const;
+    try {
+        rc = minimize_batched(device_objective, &o, P, F, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x_out, f_out, flags_out, counters);
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "bi_fit_batched: out of host memory for %lld problems of %d variables", (long long)P, F);
+    } catch (const std::exception& e) {
+        return fail(c, BI_ERR_INVALID, "bi_fit_batched: %s", e.what());
+    }
+    if (counters) counters[3] = o.evaluations;
+    return rc;
 }
 
 }  // namespace
@@ -466,28 +535,22 @@ int bi_fit_batched(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const i
                    const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                    const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, double* x_out,
                    double* f_out, int32_t* flags_out, int64_t* counters) {
+    return fit_batched(c, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, nullptr, nullptr,
+                       nullptr, x_out, f_out, flags_out, counters);
+}
+
+int bi_fit_batched_gauss(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                         const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                         const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
+                         const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
+                         double* f_out, int32_t* flags_out, int64_t* counters) {
     int rc = check_ready(c, true);
     if (rc) return rc;
-    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !x_out ||
-        !f_out || !flags_out)
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched: bad arguments");
-    for (int j = 0; j < F; ++j)
-        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
-            (var_kind[j] != 0 && var_kind[j] != 1))
-            return fail(c, BI_ERR_INVALID, "bi_fit_batched: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
-    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "bi_fit_batched: n_kinks must be >= 0 and the kinks of a variable ascending");
-    if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
-    DeviceObjective o{};
-    o.c = c; o.F = F; o.var_kind = var_kind; o.var_index = var_index; o.z0 = z0; o.scale0 = scale0; o.unit = unit; o.dataset = dataset;
-    try {
-        rc = minimize_batched(device_objective, &o, P, F, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x_out, f_out, flags_out, counters);
-    } catch (const std::bad_alloc&) {
-        return fail(c, BI_ERR_NOMEM, "bi_fit_batched: out of host memory for %lld problems of %d variables", (long long)P, F);
-    } catch (const std::exception& e) {
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched: %s", e.what());
-    }
-    if (counters) counters[3] = o.evaluations;
-    return rc;
+    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: bad arguments");
+    if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: %s", why);
+    if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
+    return fit_batched(c, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, prior_mean,
+                       prior_sigma, prior_const, x_out, f_out, flags_out, counters);
 }
 
 }  // extern "C"

@@ -40,6 +40,31 @@ __device__ __forceinline__ double stretch_coord(const StretchArgs& a, const Stre
     return __dadd_rn(xj, __dmul_rn(m.z, __dsub_rn(xk, xj)));
 }
 
+// The Gaussian constraint terms of ensemble e at a point whose coordinate v is coord(v), in the order include/blueice_hip.h
+// states: p = prior_const[e]; per variable with a finite sigma t = (x - mean) / sigma, p = p - 0.5 (t t); every operation
+// rounded on its own.  (F loads of mean and sigma per thread, from two arrays of F doubles that every thread reads alike.)
+template <class Coord>
+__device__ __forceinline__ double gauss_terms(const StretchArgs& a, int64_t e, Coord coord) {
+    double p = a.prior_const ? a.prior_const[e] : 0.0;
+    if (a.prior_sigma)
+        for (int v = 0; v < a.F; ++v) {
+            const double sg = a.prior_sigma[v];
+            if (sg - sg == 0.0) {                                    // finite
+                const double t = __ddiv_rn(__dsub_rn(coord(v), a.prior_mean[v]), sg);
+                p = __dsub_rn(p, __dmul_rn(0.5, __dmul_rn(t, t)));
+            }
+        }
+    return p;
+}
+
+// the start: every walker's log likelihood (ll_prop, row e W + k) becomes its log density.  Only launched with terms.
+__global__ __launch_bounds__(kThreads) void k_stretch_start_density(const StretchArgs a) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= a.E * a.W) return;
+    const double p = gauss_terms(a, w / a.W, [&](int v) { return a.x[w * a.F + v]; });
+    a.ll[w] = __dadd_rn(a.ll_prop[w], p);
+}
+
 // h = 0 / 1: the proposals of the moving half; h = -1: every walker's own position (the log likelihoods of the start).
 // Row i of z_dev / rs_dev / ds_dev is what bi_plan_points_resident reads as point i.
 __global__ __launch_bounds__(kThreads) void k_stretch_propose(const StretchArgs a) {
@@ -69,8 +94,11 @@ __global__ __launch_bounds__(kThreads) void k_stretch_accept(const StretchArgs a
     StretchMove m;
     if (!stretch_move(a, i, m)) return;
     const int64_t w = m.e * a.W + m.k;
-    const double ll_y = a.ll_prop[i], ll_x = a.ll[w];
-    bool ok = a.st_prop[i] == 0 && ll_y - ll_y == 0.0;              // status word clean, log likelihood finite
+    double ll_y = a.ll_prop[i];
+    const double ll_x = a.ll[w];
+    // with constraint terms the density of the proposal is ll + p, p from the proposal's own coordinates
+    if (a.prior_sigma || a.prior_const) ll_y = __dadd_rn(ll_y, gauss_terms(a, m.e, [&](int v) { return stretch_coord(a, m, v); }));
+    bool ok = a.st_prop[i] == 0 && ll_y - ll_y == 0.0;              // status word clean, log density finite
     for (int v = 0; v < a.F && ok; ++v) {
         const double y = stretch_coord(a, m, v);
         ok = y >= a.lo[v] && y <= a.hi[v];

@@ -12,9 +12,10 @@
 namespace {
 
 struct SamplerBuffers {
-    DevBuf kind, index, z0, scale0, unit, dataset, lo, hi, x, ll, nacc, zp, rsp, dsp, llp, chain, chain_ll;
+    DevBuf kind, index, z0, scale0, unit, dataset, lo, hi, x, ll, nacc, zp, rsp, dsp, llp, chain, chain_ll, pmean, psigma, pconst;
     ~SamplerBuffers() {
-        for (DevBuf* b : {&kind, &index, &z0, &scale0, &unit, &dataset, &lo, &hi, &x, &ll, &nacc, &zp, &rsp, &dsp, &llp, &chain, &chain_ll})
+        for (DevBuf* b : {&kind, &index, &z0, &scale0, &unit, &dataset, &lo, &hi, &x, &ll, &nacc, &zp, &rsp, &dsp, &llp, &chain, &chain_ll, &pmean,
+                          &psigma, &pconst})
             dev_free(*b);
     }
 };
@@ -46,8 +47,8 @@ int sampler_evaluate(bi_ctx* c, SamplerBuffers& b, int64_t n, bi_plan** plan, in
 
 int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                    const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
-                   int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll, int64_t* n_accepted,
-                   int64_t* counters) {
+                   int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, const double* prior_mean, const double* prior_sigma,
+                   const double* prior_const, double* chain, double* ll, int64_t* n_accepted, int64_t* counters) {
     const int d = c->d, S = c->S;
     const size_t nE = (size_t)E, nW = (size_t)E * W;
     SamplerBuffers b;
@@ -70,6 +71,13 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
         (rc = dev_upload(c, b.scale0, h_scale0)) || (rc = dev_upload(c, b.unit, h_unit)) || (rc = dev_upload(c, b.dataset, h_ds)) ||
         (rc = dev_upload(c, b.lo, h_lo)) || (rc = dev_upload(c, b.hi, h_hi)) || (rc = dev_upload(c, b.x, h_x)))
         return rc;
+    // Gaussian constraint terms (prior_sigma NULL here: none on any variable)
+    const std::vector<double> h_pmean = host_copy(prior_sigma ? prior_mean : nullptr, (size_t)F, 0.0),
+                              h_psigma = host_copy(prior_sigma, (size_t)F, std::numeric_limits<double>::infinity()),
+                              h_pconst = host_copy(prior_const, nE, 0.0);
+    const bool terms = prior_sigma || prior_const;
+    if (prior_sigma && ((rc = dev_upload(c, b.pmean, h_pmean)) || (rc = dev_upload(c, b.psigma, h_psigma)))) return rc;
+    if (prior_const && (rc = dev_upload(c, b.pconst, h_pconst))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const size_t steps = (size_t)n_steps;
     if ((rc = dev_alloc(c, b.ll, nW * sizeof(double))) || (rc = dev_alloc(c, b.nacc, nW * sizeof(int64_t))) ||
@@ -91,9 +99,12 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
     s.x = (double*)b.x.p; s.ll = (double*)b.ll.p; s.n_accepted = (int64_t*)b.nacc.p;
     s.z_dev = (double*)b.zp.p; s.rs_dev = (double*)b.rsp.p; s.ds_dev = (int64_t*)b.dsp.p;
     s.ll_prop = (const double*)b.llp.p;
+    s.prior_mean = prior_sigma ? (const double*)b.pmean.p : nullptr;
+    s.prior_sigma = prior_sigma ? (const double*)b.psigma.p : nullptr;
+    s.prior_const = prior_const ? (const double*)b.pconst.p : nullptr;
     if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
 
-    // the start: every walker's own log likelihood, which must be finite
+    // the start: every walker's own log density (the log likelihood, plus the constraint terms if there are any), which must be finite
     bi_plan* plan = nullptr;
     s.h = -1;
     launch_stretch_propose(c, s);
@@ -102,9 +113,14 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
     {
         std::vector<double> h_ll(nW);
         std::vector<int32_t> h_st(nW);
-        hipError_t e = hipMemcpyAsync(h_ll.data(), b.llp.p, nW * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        hipError_t e = hipSuccess;
+        if (terms) {
+            launch_stretch_start_density(c, s);                 // b.ll = b.llp + p
+            e = hipGetLastError();
+        } else
+            e = hipMemcpyAsync(b.ll.p, b.llp.p, nW * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_ll.data(), b.ll.p, nW * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(h_st.data(), plan->status.p, nW * sizeof(int32_t), hipMemcpyDefault, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(b.ll.p, b.llp.p, nW * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         bi_plan_destroy(c, plan);
         plan = nullptr;
@@ -117,8 +133,9 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
         for (size_t w = 0; w < nW; ++w)
             if (!std::isfinite(h_ll[w]) || h_st[w] != 0)
                 return fail(c, BI_ERR_INVALID, "bi_sample_stretch: the log likelihood of start walker %lld of ensemble %lld is not finite "
-                                               "(%g, status %d): every walker must start at a point of non-zero likelihood",
-                            (long long)(w % (size_t)W), (long long)(w / (size_t)W), h_ll[w], (int)h_st[w]);
+                                               "(%g, status %d): every walker must start at a point of non-zero likelihood%s",
+                            (long long)(w % (size_t)W), (long long)(w / (size_t)W), h_ll[w], (int)h_st[w],
+                            terms ? " (constraint terms included)" : "");
     }
 
     const int64_t n = E * (W / 2);
@@ -155,10 +172,11 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
 
 extern "C" {
 
-int bi_sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
-                      const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
-                      const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll,
-                      int64_t* n_accepted, int64_t* counters) {
+int bi_sample_stretch_gauss(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index,
+                            const double* z0, const double* scale0, const double* unit, const int64_t* dataset, const double* x0,
+                            const double* lo, const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble,
+                            const double* prior_mean, const double* prior_sigma, const double* prior_const, double* chain,
+                            double* ll, int64_t* n_accepted, int64_t* counters) {
     int rc = check_ready(c, true);
     if (rc) return rc;
     c->plan_refused = 0;
@@ -177,13 +195,29 @@ int bi_sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kin
     if (dataset)
         for (int64_t e = 0; e < E; ++e)
             if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: dataset %lld of ensemble %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);
+    // the constraint terms: all three arrays NULL is bi_sample_stretch; otherwise mean and sigma are required
+    if (prior_mean || prior_sigma || prior_const) {
+        if (const char* why = gauss_terms_invalid(F, E, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_sample_stretch_gauss: %s", why);
+        // no finite sigma: no term on any variable, and the kernels are not handed the two arrays
+        bool any = false;
+        for (int j = 0; j < F; ++j) any |= std::isfinite(prior_sigma[j]);
+        if (!any) prior_mean = prior_sigma = nullptr;
+    }
     HIP_TRY(c, hipSetDevice(c->device));
     try {
-        return sample_stretch(c, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble, chain, ll,
-                              n_accepted, counters);
+        return sample_stretch(c, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble, prior_mean,
+                              prior_sigma, prior_const, chain, ll, n_accepted, counters);
     } catch (const std::bad_alloc&) {
         return fail(c, BI_ERR_NOMEM, "bi_sample_stretch: out of host memory");
     }
+}
+
+int bi_sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                      const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                      const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll,
+                      int64_t* n_accepted, int64_t* counters) {
+    return bi_sample_stretch_gauss(c, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble, nullptr,
+                                   nullptr, nullptr, chain, ll, n_accepted, counters);
 }
 
 }  // extern "C"

@@ -341,17 +341,37 @@ class DeviceContext:
                                            ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], hess, status
 
-    def fit_batched(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters):
+    @staticmethod
+    def _gauss_terms(priors, F, n):
+        """priors = (prior_mean [F], prior_sigma [F], prior_const [n] or None) -> the three as C-contiguous float64 arrays"""
+        mean, sigma, const = priors
+        mean, sigma = as_f64(mean, (F,)), as_f64(sigma, (F,))
+        if const is not None:
+            const = np.ascontiguousarray(np.broadcast_to(np.asarray(const, dtype=np.float64), (n,)))
+        return mean, sigma, const
+
+    def fit_batched(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters,
+                    priors=None):
         """bi_fit_batched: the batched profile-fit engine's loop with this context's likelihood as the objective (all
-        arguments are C-contiguous numpy arrays of the right dtype or None; results are written into x, f, flags, counters)."""
+        arguments are C-contiguous numpy arrays of the right dtype or None; results are written into x, f, flags, counters).
+        priors = (prior_mean [F], prior_sigma [F], prior_const [P] or None): Gaussian constraint terms on the variables
+        (bi_fit_batched_gauss)."""
+        if priors is not None:
+            mean, sigma, const = self._gauss_terms(priors, int(F), int(P))
+            self._check(self._lib.bi_fit_batched_gauss(self._h, int(P), int(F), ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
+                                                       ptr(unit), ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks), ptr(kinks), float(gtol),
+                                                       int(max_iter), ptr(mean), ptr(sigma), ptr(const), ptr(x), ptr(f), ptr(flags), ptr(counters)))
+            return 0
         self._check(self._lib.bi_fit_batched(self._h, int(P), int(F), ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0), ptr(unit),
                                              ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks), ptr(kinks), float(gtol), int(max_iter),
                                              ptr(x), ptr(f), ptr(flags), ptr(counters)))
         return 0
 
-    def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0):
+    def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0, priors=None):
         """bi_sample_stretch: n_steps stretch-move steps of E ensembles of W walkers with this context's likelihood as the
         target.  x0 [E, W, F]; z0 [E, d], scale0 / unit [E, S], dataset [E] or None as `fit_batched`.
+        priors = (prior_mean [F], prior_sigma [F], prior_const [E] or None): Gaussian constraint terms on the variables
+        (bi_sample_stretch_gauss); the target and the returned ll are then the log density ll + p.
         -> (chain [n_steps, E, W, F], ll [n_steps, E, W], n_accepted [E, W], counters [4])."""
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         E, W2, F = x0.shape
@@ -371,9 +391,14 @@ class DeviceContext:
         ll = np.empty((max(n_steps, 0), E, W))
         n_acc = np.zeros((E, W), dtype=np.int64)
         counters = np.zeros(4, dtype=np.int64)
-        rc = self._lib.bi_sample_stretch(self._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0), ptr(unit),
-                                         ptr(dataset), ptr(x0), ptr(lo), ptr(hi), n_steps, float(a), int(seed) & (2 ** 64 - 1),
-                                         int(first_ensemble), ptr(chain), ptr(ll), ptr(n_acc), ptr(counters))
+        head = (self._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0), ptr(unit), ptr(dataset), ptr(x0), ptr(lo),
+                ptr(hi), n_steps, float(a), int(seed) & (2 ** 64 - 1), int(first_ensemble))
+        tail = (ptr(chain), ptr(ll), ptr(n_acc), ptr(counters))
+        if priors is not None:
+            mean, sigma, const = self._gauss_terms(priors, F, E)
+            rc = self._lib.bi_sample_stretch_gauss(*head, ptr(mean), ptr(sigma), ptr(const), *tail)
+        else:
+            rc = self._lib.bi_sample_stretch(*head, *tail)
         if rc == _capi.ERR_INVALID:
             msg = self._lib.bi_last_error(self._h).decode()
             if self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:             # the resident planner's two refusals

@@ -65,9 +65,13 @@ def to_log10(g, H, values, which):
 
 def prior_derivatives(log_prior, x):
     """Central differences of a (vectorised or scalar) log prior at x [P]: -> (slope [P], curvature [P]).  The slope takes
-    the step of `values_and_gradients` (1e-6 relative), the second difference a wider one (1e-4)."""
+    the step of `values_and_gradients` (1e-6 relative), the second difference a wider one (1e-4).  A GaussianPrior gives both in
+    closed form."""
     from .likelihood import _prior_of
+    from .priors import GaussianPrior
     x = np.asarray(x, float)
+    if isinstance(log_prior, GaussianPrior):
+        return log_prior.slope(x), np.full(x.shape, log_prior.curvature)
     h1 = 1e-6 * np.maximum(1.0, np.abs(x))
     h2 = 1e-4 * np.maximum(1.0, np.abs(x))
     slope = (_prior_of(log_prior, x + h1) - _prior_of(log_prior, x - h1)) / (2 * h1)

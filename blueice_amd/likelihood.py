@@ -28,6 +28,7 @@ from .hessian import chain_rule_hessian, difference_steps, prior_derivatives
 from .histdd import Histdd
 from .model import Model
 from .pdf_morphers import MORPHERS
+from .priors import GaussianPrior
 from .utils import combine_dicts, is_numeric
 
 __all__ = ['LogLikelihoodBase', 'BinnedLogLikelihood', 'UnbinnedLogLikelihood', 'LogLikelihoodSum',
@@ -107,12 +108,19 @@ class LogLikelihoodBase:
         self.shape_parameters[setting_name] = (anchors, log_prior, base_value)
 
     def add_rate_uncertainty(self, source_name, fractional_uncertainty):
+        # likelihood_config['gaussian_priors_on_device']: register the closed form (priors.GaussianPrior), which the native
+        # fit and sampler loops take; the default is the reference's scipy bound method, a Python callable like any other
+        if self.config.get('gaussian_priors_on_device', False):
+            return self.add_rate_parameter(source_name, log_prior=GaussianPrior(1, fractional_uncertainty))
         self.add_rate_parameter(source_name, log_prior=stats.norm(1, fractional_uncertainty).logpdf)
 
     def add_shape_uncertainty(self, setting_name, fractional_uncertainty, anchor_zs=(-2, -1, 0, 1, 2), base_value=None):
         self.add_shape_parameter(setting_name, anchor_zs, base_value=base_value)
         anchors, _, base_value = self.shape_parameters[setting_name]
-        prior = stats.norm(base_value, base_value * fractional_uncertainty).logpdf
+        if self.config.get('gaussian_priors_on_device', False):
+            prior = GaussianPrior(base_value, base_value * fractional_uncertainty)
+        else:
+            prior = stats.norm(base_value, base_value * fractional_uncertainty).logpdf
         self.shape_parameters[setting_name] = (anchors, prior, base_value)
 
     def get_bounds(self, parameter_name=None):
@@ -338,7 +346,9 @@ class _SourceWiseModel:
 
 def _prior_of(log_prior, values):
     """log_prior over an array of parameter values: one vectorised call when the callable takes arrays (scipy's
-    frozen distributions do), the reference's one call per value otherwise."""
+    frozen distributions do), the reference's one call per value otherwise; a GaussianPrior is its closed form."""
+    if isinstance(log_prior, GaussianPrior):
+        return np.asarray(log_prior(values), dtype=float)
     try:
         out = np.asarray(log_prior(values), dtype=float)
         if out.shape == values.shape:
@@ -577,6 +587,8 @@ class DeviceLogLikelihood(LogLikelihoodBase):
     def _prior_slope(log_prior, x):
         if log_prior is None:
             return 0.0
+        if isinstance(log_prior, GaussianPrior):
+            return log_prior.slope(x)
         h = 1e-6 * max(1.0, abs(x))
         return (log_prior(x + h) - log_prior(x - h)) / (2 * h)
 
@@ -596,7 +608,8 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         """-> (ll, OrderedDict parameter name -> d ll / d parameter) for every registered rate and shape
         parameter, from ONE pass over the templates (`bi_eval_grad`).  Inside a grid cell ll is smooth in
         the shape parameters; exactly on an anchor the slope of the cell the point is assigned to is
-        returned.  Prior terms are differentiated numerically on the host (they are Python callables)."""
+        returned.  Prior terms are differentiated numerically on the host (they are Python callables), except a
+        GaussianPrior, whose slope is known."""
         prior, zs, scale = self._host_terms(livetime_days, kwargs)
         grads = OrderedDict()
         names = ['%s_rate_multiplier' % s for s in self.rate_parameters] + list(self.shape_parameters)
@@ -653,6 +666,8 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         def slope(log_prior, x):               # priors are Python callables: central differences, vectorised
             if log_prior is None:
                 return 0.0
+            if isinstance(log_prior, GaussianPrior):
+                return log_prior.slope(x)
             h = 1e-6 * np.maximum(1.0, np.abs(x))
             return (_prior_of(log_prior, x + h) - _prior_of(log_prior, x - h)) / (2 * h)
 
@@ -700,6 +715,11 @@ class DeviceLogLikelihood(LogLikelihoodBase):
     def _parameter_names(self):
         return ['%s_rate_multiplier' % s for s in self.source_name_list if s in self.rate_parameters] + list(self.shape_parameters)
 
+    def _parameter_priors(self):
+        """the log priors (or None) of `_parameter_names()`, in that order"""
+        return [self.rate_parameters[s] for s in self.source_name_list if s in self.rate_parameters] + \
+            [sp[1] for sp in self.shape_parameters.values()]
+
     @_needs_data
     def value_gradient_hessian(self, livetime_days=None, **kwargs):
         """-> (ll, OrderedDict name -> d ll / d parameter, names, H [F, F]) at one point: `values_gradients_hessians` with
@@ -714,7 +734,7 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         `values_and_gradients`) -> (ll [P], OrderedDict name -> d ll / d parameter [P], names [F], H [P, F, F]) over every
         registered rate multiplier, then every shape parameter.  The device Hessian over (z, rate_scale) (bi_eval_hess) is
         carried to the user's parameters by the chain rule (live-time and efficiency factors, shape parameters that double
-        as efficiencies, priors by central second differences).  On an anchor the Hessian is that of the cell the point is
+        as efficiencies, priors by central second differences, a GaussianPrior in closed form).  On an anchor the Hessian is that of the cell the point is
         assigned to.  Where the device has no analytic Hessian (Beeston-Barlow, unbinned pdfs that are not all finite, too
         many parameters) central differences of the analytic gradient are taken instead -- all 2 F displaced points of all
         P points in ONE `values_and_gradients` call, steps kept inside the point's grid cell (one-sided at its edges),
@@ -805,12 +825,21 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         ds = None if dataset is None else np.tile(np.broadcast_to(np.asarray(dataset), (P,)), 2 * F + 1)
         ll, grads = self.values_and_gradients(call, livetime_days=livetime_days, dataset=ds)
         G = np.stack([grads[n] for n in names], axis=1).reshape(2 * F + 1, P, F)
+        # Gaussian constraints: their slope leaves the differenced gradient, their curvature is added in closed form
+        gauss = [(j, lp) for j, lp in enumerate(self._parameter_priors()) if isinstance(lp, GaussianPrior)]
+        Gd = G
+        if gauss:
+            Gd = G.copy()
+            for j, lp in gauss:
+                Gd[:, :, j] -= lp.slope(Y[:, j]).reshape(2 * F + 1, P)
         H = np.zeros((P, F, F))
         with np.errstate(all='ignore'):
             for j in range(F):
                 step = xp[:, j] - xm[:, j]
-                H[:, j, :] = np.where((step > 0)[:, None], (G[1 + 2 * j] - G[2 + 2 * j]) / np.where(step > 0, step, 1.0)[:, None], 0.0)
+                H[:, j, :] = np.where((step > 0)[:, None], (Gd[1 + 2 * j] - Gd[2 + 2 * j]) / np.where(step > 0, step, 1.0)[:, None], 0.0)
         H = 0.5 * (H + np.swapaxes(H, 1, 2))
+        for j, lp in gauss:
+            H[:, j, j] += lp.curvature
         out = ll[:P]
         H[~np.isfinite(out)] = np.nan
         return out, OrderedDict((n, G[0][:, j]) for j, n in enumerate(names)), names, H

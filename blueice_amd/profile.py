@@ -22,6 +22,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .exceptions import DeviceError, NoOpimizationNecessary
+from .priors import GaussianPrior, gaussian_terms
 from .utils import is_numeric
 
 # The optimiser's inner loop: 'native' = the C++ port inside libblueice_hip.so (bi_minimize_batched / bi_fit_batched,
@@ -63,9 +64,10 @@ class BatchObjective:
 
     def native(self):
         """What bi_fit_batched needs to evaluate this objective without Python: the problems' settings as arrays, and which
-        optimiser variable is which parameter -- or None where a Python callable sits between x and the device call (priors,
-        a shape parameter that doubles as an efficiency, 'unphysical_behaviour': 'error', likelihoods that are not one
-        device context)."""
+        optimiser variable is which parameter -- or None where a Python callable sits between x and the device call (priors
+        other than a GaussianPrior, a shape parameter that doubles as an efficiency, 'unphysical_behaviour': 'error',
+        likelihoods that are not one device context).  Gaussian constraints come as prior_mean / prior_sigma [F] (sigma +inf:
+        none on that variable) and prior_const [P] (bi_fit_batched_gauss, bi_sample_stretch_gauss)."""
         if hasattr(self, '_native'):
             return self._native
         self._native = None
@@ -73,7 +75,8 @@ class BatchObjective:
         ok = self.analytic and hasattr(lf, '_batch_terms') and getattr(lf, 'ctx', None) is not None and \
             hasattr(lf.ctx, 'fit_batched') and not any(getattr(lf, 'source_apply_efficiency', [])) and \
             lf.config.get('unphysical_behaviour') != 'error' and \
-            all(v[1] is None for v in lf.shape_parameters.values()) and all(v is None for v in lf.rate_parameters.values())
+            all(v[1] is None or isinstance(v[1], GaussianPrior) for v in lf.shape_parameters.values()) and \
+            all(v is None or isinstance(v, GaussianPrior) for v in lf.rate_parameters.values())
         if not ok:
             return None
         P = max([len(v) for v in self.points.values()] + ([len(self.datasets)] if self.datasets is not None else []) + [1])
@@ -92,7 +95,15 @@ class BatchObjective:
                 index.append(lf.source_name_list.index(n[:-16]))
             else:
                 return None
-        self._native = dict(P=P, z0=z0, scale0=scale0, unit=unit, kind=np.array(kind, dtype=np.int32), index=np.array(index, dtype=np.int32))
+        # the constraint terms: the fixed parameters' priors at the problems' values (the multipliers as given: not scale0,
+        # which carries live time), the floating ones' as mean / sigma on their variable
+        mult = np.ones_like(scale0)
+        for s, n in enumerate(lf.source_name_list):
+            if n + '_rate_multiplier' in pts:
+                mult[:, s] = pts[n + '_rate_multiplier']
+        mean, sigma, const = gaussian_terms(lf, self.names, z0, mult)
+        self._native = dict(P=P, z0=z0, scale0=scale0, unit=unit, kind=np.array(kind, dtype=np.int32), index=np.array(index, dtype=np.int32),
+                            prior_mean=mean, prior_sigma=sigma, prior_const=const)
         return self._native
 
     def stacked(self, period):
@@ -182,7 +193,11 @@ def _native_minimize(fun, x0, lo, hi, gtol, max_iter, kinks):
         tile = (lambda a: np.ascontiguousarray(np.tile(a, (reps,) + (1,) * (a.ndim - 1)))) if reps > 1 else (lambda a: a)
         ds = None if base.datasets is None else np.ascontiguousarray(tile(np.broadcast_to(base.datasets, (nat['P'],))), dtype=np.int64)
         z0, s0, un = tile(nat['z0']), tile(nat['scale0']), tile(nat['unit'])
-        rc = base.lf.ctx.fit_batched(P, F, nat['kind'], nat['index'], z0, s0, un, ds, x0, lo, hi, n_k, k_flat, gtol, max_iter, x, f, flags, counters)
+        priors = None
+        if np.any(np.isfinite(nat['prior_sigma'])) or np.any(nat['prior_const'] != 0):
+            priors = (nat['prior_mean'], nat['prior_sigma'], tile(nat['prior_const']))
+        rc = base.lf.ctx.fit_batched(P, F, nat['kind'], nat['index'], z0, s0, un, ds, x0, lo, hi, n_k, k_flat, gtol, max_iter, x, f, flags, counters,
+                                     priors=priors)
         base.calls += int(counters[1])
         base.evaluations += int(counters[3])
     else:

@@ -7,10 +7,11 @@ which is what the device evaluates best.  Two engines run the SAME algorithm on 
 documented with `bi_sample_stretch` in include/blueice_hip.h):
 
     'native'   bi_sample_stretch: propose, evaluate, accept and the chain stay on the device; taken whenever nothing but
-               the device call sits between the parameters and the likelihood (`BatchObjective.native()`)
-    'host'     the restatement below in NumPy, one `lf.eval_points` call per half-step -- for likelihoods with Python
-               priors, sums, re-parametrisations, efficiencies, unphysical_behaviour='error', and models whose batches
-               the device planner refuses
+               the device call sits between the parameters and the likelihood (`BatchObjective.native()`); Gaussian
+               constraints (`priors.GaussianPrior`) are added on the device (bi_sample_stretch_gauss)
+    'host'     the restatement below in NumPy, one `lf.eval_points` call per half-step -- for likelihoods with other
+               Python callables as priors, sums, re-parametrisations, efficiencies, unphysical_behaviour='error', and
+               models whose batches the device planner refuses
 
 Proposals are bitwise the same in both; accept decisions differ only where the two evaluations of the likelihood do.
 """
@@ -155,13 +156,16 @@ def sample_posterior(lf, n_walkers=40, n_steps=200, a=2.0, seed=0, guess=None, p
     if engine != 'host':
         native = BatchObjective(lf, names, {}, fixed, livetime_days, datasets).native()
         if native is None and engine == 'native':
-            raise ValueError("sample_posterior: this likelihood has Python between its parameters and the device call (priors, "
-                             "efficiencies, a sum or re-parametrisation): engine='host'")
+            raise ValueError("sample_posterior: this likelihood has Python between its parameters and the device call (priors "
+                             "that are not a GaussianPrior, efficiencies, a sum or re-parametrisation): engine='host'")
     result = None
     if native is not None:
         try:
+            priors = None
+            if np.any(np.isfinite(native['prior_sigma'])) or np.any(native['prior_const'] != 0):
+                priors = (native['prior_mean'], native['prior_sigma'], native['prior_const'])
             result = lf.ctx.sample_stretch(W, native['kind'], native['index'], native['z0'], native['scale0'], native['unit'], datasets, x, lo, hi,
-                                           n_steps, a=a, seed=seed, first_ensemble=first_ensemble)
+                                           n_steps, a=a, seed=seed, first_ensemble=first_ensemble, priors=priors)
             used = 'native'
         except PlannerRefused:
             if engine == 'native':

@@ -262,6 +262,29 @@ int bi_fit_batched(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const
                    const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, double* x_out,
                    double* f_out, int32_t* flags_out, int64_t* counters);
 
+/* Gaussian constraint terms inside the two native loops (bi_fit_batched_gauss below, bi_sample_stretch_gauss after
+ * bi_sample_stretch): the log density is ll + p, with p a sum of normal log densities on the OPTIMISER VARIABLES x_v -- the
+ * multiplier itself for var_kind 1, not rate_scale -- which is what the reference adds for add_rate_uncertainty /
+ * add_shape_uncertainty and any Gaussian log_prior (blueice/likelihood.py:280-296,341-372).  Three more arrays:
+ *   prior_mean [F], prior_sigma [F]   the term on variable v; prior_sigma[v] = +inf: no term on that variable
+ *   prior_const [P] ([E] for the sampler) or NULL for 0: filled in by the caller with everything of p that does not depend on
+ *                                     x -- the normalisation constants -log(sigma) - log(2 pi)/2 of the floating terms plus
+ *                                     the complete priors of the problem's fixed parameters
+ * The arithmetic, exactly (binary64, every operation rounded on its own, no fused multiply-add), for problem / ensemble e:
+ *     p = prior_const[e]
+ *     for v = 0 .. F-1 with finite prior_sigma[v]:  t = (x_v - prior_mean[v]) / prior_sigma[v]   (IEEE division)
+ *                                                   p = p - 0.5 (t t)
+ * A finite prior_sigma <= 0, or a NaN in any of the three arrays, returns BI_ERR_INVALID with the reason in bi_last_error
+ * before anything is launched.  bi_fit_batched and bi_sample_stretch are these entry points without terms.
+ *
+ * bi_fit_batched_gauss: f = -(ll + p) and g_v gains + t_v / prior_sigma[v]; rejected points stay +inf with nan slopes, points
+ * at which a Beeston-Barlow assertion would fire stay nan. */
+int bi_fit_batched_gauss(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                         const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                         const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
+                         const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
+                         double* f_out, int32_t* flags_out, int64_t* counters);
+
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
  * n_walkers x n_steps scalar likelihood calls (bestfit_emcee, blueice/inference.py:254-321).  The variables are described as
@@ -300,6 +323,17 @@ int bi_sample_stretch(bi_ctx* ctx, int64_t E, int W, int F, const int32_t* var_k
                       const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                       const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, double* chain, double* ll,
                       int64_t* n_accepted, int64_t* counters);
+/* ... with Gaussian constraint terms (prior_mean / prior_sigma [F], prior_const [E] or NULL: see bi_fit_batched_gauss): the
+ * quantity held per walker, compared in the accept step -- log(u_a) < (((F - 1) log z) + (ll(y) + p(y))) - (ll(x_k) + p(x_k)) --
+ * and written to `ll` is the log density ll + p (one addition, after p has been summed as above); the start walkers' values
+ * include it, and it is the density that must be finite at the start and at an accepted proposal.  p of a proposal is
+ * computed on the device from the proposal's coordinates: nothing more crosses to the host inside a half-step.  With every
+ * prior_sigma +inf and prior_const NULL the chain is bit for bit that of bi_sample_stretch. */
+int bi_sample_stretch_gauss(bi_ctx* ctx, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index,
+                            const double* z0, const double* scale0, const double* unit, const int64_t* dataset, const double* x0,
+                            const double* lo, const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble,
+                            const double* prior_mean, const double* prior_sigma, const double* prior_const, double* chain,
+                            double* ll, int64_t* n_accepted, int64_t* counters);
 
 /* One parameter point against datasets [t0, t1): the toy-MC form.  mu_b / log mu_b are computed
  * once and every dataset reduces sum_b xlogy(n, mu) against them.  Not available with
