@@ -59,6 +59,7 @@ struct bi_plan {
     bool device_planned = false;  // built by plan_points_device: rejected points are found through the status array
     bool no_reuse = false;     // no anchor model is touched by two items of the plan
     bool sparse = false;       // rows / counts refer to the compacted (non-empty-bin) copies
+    bool narrow = false;       // every dataset the plan's items refer to has an exact narrow copy of its counts (decided when the plan is built)
     bool sorted = false;       // rows / counts refer to the count-sorted copy of all bins (dense-data scans, ensure_sorted_rows)
     bool by_count = false;     // the rows the scan kernel reads are ordered by count (sorted, or a count-sorted compacted copy)
     int64_t bytes = 0;         // algorithmic HBM bytes per run
@@ -100,6 +101,15 @@ struct bi_ctx {
     int64_t T = 0;
     DevBuf counts, lgsum;
     std::vector<double> h_lgsum;
+    // the narrow copy of the dense counts: [T][Bp] bytes beside the doubles, rebuilt by every writer of `counts`
+    // (build_narrow_counts); the dense morph kernels stream it instead of the doubles for datasets it represents exactly
+    DevBuf cnt8, cnt8_bad;                       // ... and [T] words, non-zero: the dataset has a value with no one-byte form
+    std::vector<uint32_t> h_cnt8_bad;            // host copy of the flags (arrives with the upload's own synchronisation)
+    bool cnt8_valid = false;                     // the copy matches `counts` (false: never read)
+    int cnt8_all = -1;                           // every dataset has a narrow form: 1 / 0, -1 = not looked at yet
+    int64_t narrow_counts = 1;                   // parameter: 0 = never read the narrow copy
+    int64_t last_streamed_bytes = 0;             // read-only: bytes the last bi_run_plan streamed (plan bytes less 7 per bin of every item read narrow)
+    int64_t n_narrow_launches = 0;               // read-only: morph launches that read the narrow copy
 
     // model statistics (for the sparse forms)
     std::vector<double> h_rowsum;  // [A*S] sum over bins of every ps row

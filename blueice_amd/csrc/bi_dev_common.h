@@ -37,6 +37,8 @@ struct LaunchArgs {
     long long mail_timeout = 2000 * kMailTicksPerMs; // in-launch finish: ticks of the 100 MHz wall clock a collector waits (context: mail_timeout_ms;
                             // default 2 s, far beyond any delay a busy, shared GPU causes)
     int skip_post = -1, late_post = -1;   // fault injection (tests): this block never posts / posts after the collector gave up; -1 = off
+    // (last, so that no other member moves in the kernel-argument block: the existing instantiations compile as before)
+    const uint8_t* cnt8 = nullptr;   // [T][Bp] the counts as one byte per bin, or NULL: the launch reads the doubles (build_narrow_counts)
 };
 
 constexpr int kMaxSingleStreams = 128;

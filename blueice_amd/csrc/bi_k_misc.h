@@ -186,6 +186,32 @@ __global__ __launch_bounds__(kThreads) void k_counts_lgamma(const double* __rest
     }
 }
 
+// The narrow copy of the counts (build_narrow_counts): one byte per bin beside the doubles, same [dataset][padded bin] layout,
+// eight bins per thread.  A value has a narrow form when converting it to a byte and back gives the SAME BITS (0 ... 255, whole;
+// -0.0, nan, +-inf, negative, fractional and larger values have none); a dataset with one value that has none is flagged in
+// bad[t] and keeps the double path (its narrow row is never read).  Padding bins are written as 0.
+constexpr int kNarrowPerThread = 8;
+__global__ __launch_bounds__(kThreads) void k_counts_narrow(const double* __restrict__ counts, int64_t B, int64_t Bp,
+                                                            uint8_t* __restrict__ narrow, unsigned* __restrict__ bad) {
+    const int t = blockIdx.y;
+    const int64_t b0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * kNarrowPerThread;
+    bool lossy = false;
+    if (b0 < Bp) {                                               // (Bp is a multiple of 512: a thread's eight bins are all inside or all outside)
+        const double* __restrict__ src = counts + (int64_t)t * Bp + b0;
+        unsigned long long packed = 0ull;
+#pragma unroll
+        for (int j = 0; j < kNarrowPerThread; ++j) {
+            const double v = b0 + j < B ? src[j] : 0.0;
+            const bool in_range = v >= 0.0 && v <= 255.0;       // (false for nan)
+            const unsigned q = in_range ? (unsigned)(int)v : 0u;
+            lossy |= __double_as_longlong((double)q) != __double_as_longlong(v);
+            packed |= (unsigned long long)q << (8 * j);
+        }
+        *reinterpret_cast<unsigned long long*>(narrow + (int64_t)t * Bp + b0) = packed;
+    }
+    if (__ballot(lossy) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad + t, 1u);
+}
+
 __global__ void k_rows_sum(const double* __restrict__ partial, int nblk, double* __restrict__ out, int64_t T) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;

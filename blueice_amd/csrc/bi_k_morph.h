@@ -1,6 +1,10 @@
 // bi_k_morph.h -- the morph + reduce kernels (k_morph_reduce, k_morph_single): translation unit tu_morph.hip.
 #pragma once
 
+#ifndef BI_CNT8_NT
+#define BI_CNT8_NT 0
+#endif
+
 namespace {
 
 // The morph + reduce kernel.  blockIdx.y = item (a cell pass with up to G points),
@@ -8,11 +12,13 @@ namespace {
 
 // The accumulate + per-bin term loop shared by the batched kernel and the single-point kernel: tiles
 // tile0, tile0 + tile_step, ... of one work item.
-template <int G, bool BB, bool NT, int MODE>
+// CNT8: the counts row is read from the narrow copy (one byte per bin, build_narrow_counts) instead of the doubles; the
+// conversion back is exact, everything after the load is the same instruction stream.
+template <int G, bool BB, bool NT, int MODE, bool CNT8 = false>
 __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* __restrict__ rowoff,
                                             const double* __restrict__ coef, const double* __restrict__ aux_base,
-                                            const double* __restrict__ cnt, int n_tiles, int tile0, int tile_step,
-                                            double (&sum)[G], unsigned (&flg)[G]) {
+                                            const double* __restrict__ cnt, const uint8_t* __restrict__ cnt8, int n_tiles, int tile0,
+                                            int tile_step, double (&sum)[G], unsigned (&flg)[G]) {
     // the log table travels global -> registers -> LDS; the request goes out first and lands under the first tile's
     // row loads, so a block that lives for only a few tiles does not wait for it separately
     double4 tab = {0.0, 0.0, 0.0, 0.0};
@@ -33,7 +39,17 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
         // the tile's counts go out FIRST: behind the stream loop their load was the one latency of a tile that nothing covered
         // (a block of the single-point call lives for two tiles: ~1 us of its 40)
         double2 nv;
-        if constexpr (MODE == 2 || MODE == 3) { nv.x = nv.y = 0.0; } else { nv = *reinterpret_cast<const double2*>(cnt + bin0); }
+        if constexpr (MODE == 2 || MODE == 3) { nv.x = nv.y = 0.0; }
+        else if constexpr (CNT8) {
+            // two bins = one aligned 2-byte load (bin0 is even); u8 -> double is exact
+#if BI_CNT8_NT      // (kernel experiment, BLUEICE_AMD_EXTRA_FLAGS=-DBI_CNT8_NT=1: the hint the template rows carry; DESIGN.md on the counts format)
+            const unsigned pair = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(cnt8 + bin0));
+#else
+            const unsigned pair = *reinterpret_cast<const uint16_t*>(cnt8 + bin0);
+#endif
+            nv.x = (double)(pair & 0xffu);
+            nv.y = (double)(pair >> 8);
+        } else { nv = *reinterpret_cast<const double2*>(cnt + bin0); }
 
         int k0 = 0;
         if constexpr (NT && G == 1 && MODE != 2 && MODE != 3) {
@@ -224,13 +240,15 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
 // MODE 0: G parameter points of one cell.  MODE 1 (gradient): ONE point; column 0 of the coefficient matrix
 // gives mu, columns 1.. give d mu / d theta_j (theta = shape parameters, then rate scales), and the per-bin
 // chain rule d ll / d theta_j = (n / mu - 1) * d mu / d theta_j is reduced alongside the likelihood.
-template <int G, bool BB, bool NT, int MODE = 0>
+template <int G, bool BB, bool NT, int MODE = 0, bool CNT8 = false>
 __global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
     const int item = blockIdx.y;
     const int NS = a.n0 + a.n1 + a.n2;
     const int64_t* __restrict__ rowoff = a.rowoff + (int64_t)item * NS;
     const double* __restrict__ coef = a.coef + (int64_t)item * NS * G;
-    const double* __restrict__ cnt = a.counts + a.item_cnt[item];
+    const int64_t cnt_off = a.item_cnt[item];                  // (one element offset addresses the doubles and the narrow copy alike)
+    const double* __restrict__ cnt = a.counts + cnt_off;
+    const uint8_t* __restrict__ cnt8 = CNT8 ? a.cnt8 + cnt_off : nullptr;
     const int n_tiles = a.item_tiles ? a.item_tiles[item] : a.n_tiles;
 
     double sum[G];
@@ -238,7 +256,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
 #pragma unroll
     for (int g = 0; g < G; ++g) { sum[g] = 0.0; flg[g] = 0u; }
 
-    morph_tiles<G, BB, NT, MODE>(a, rowoff, coef, a.aux + (int64_t)item * G * 2, cnt, n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
+    morph_tiles<G, BB, NT, MODE, CNT8>(a, rowoff, coef, a.aux + (int64_t)item * G * 2, cnt, cnt8, n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
 
     __shared__ double s_sum[kThreads / 64][G];
     __shared__ unsigned s_flg[kThreads / 64][G];
@@ -335,11 +353,11 @@ __global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
 // launch: every block posts its partial into a mailbox slot and leaves, the last block in dispatch order collects
 // them in block order (fixed order => bitwise reproducible; see mail_post) and writes {ll, status} straight into
 // pinned host memory.
-template <bool BB, bool NT, int MODE, bool FUSE>
+template <bool BB, bool NT, int MODE, bool FUSE, bool CNT8 = false>
 __global__ __launch_bounds__(kThreads) void k_morph_single(LaunchArgs a, SingleDesc d) {
     double sum[1] = {0.0};
     unsigned flg[1] = {0u};
-    morph_tiles<1, BB, NT, MODE>(a, d.rowoff, d.coef, d.aux, a.counts, a.n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
+    morph_tiles<1, BB, NT, MODE, CNT8>(a, d.rowoff, d.coef, d.aux, a.counts, a.cnt8, a.n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
 
     __shared__ double s_sum[kThreads / 64];
     __shared__ unsigned s_flg[kThreads / 64];

@@ -54,6 +54,48 @@ int check_ready(bi_ctx* c, bool need_data) {
 
 int n_tiles_of(const bi_ctx* c) { return (int)(c->Bp / kTile); }
 
+// ---- the narrow copy of the dense counts ----
+// Called by every writer of c->counts [T][Bp] after its last write is queued and BEFORE its own stream synchronisation, which
+// also brings the per-dataset flags to the host: no synchronisation of its own.  Failing to allocate the extra byte per
+// bin is not an error: the context then simply has no narrow copy.
+void build_narrow_counts(bi_ctx* c, int64_t T) {
+    c->cnt8_valid = false;
+    c->cnt8_all = -1;
+    if (c->unbinned || T < 1 || !c->counts.p) return;
+    const std::string keep = c->err;
+    if (dev_alloc(c, c->cnt8, (size_t)T * c->Bp) || dev_alloc(c, c->cnt8_bad, (size_t)T * sizeof(unsigned))) {
+        (void)hipGetLastError();
+        c->err = keep;
+        return;
+    }
+    if (hipMemsetAsync(c->cnt8_bad.p, 0, (size_t)T * sizeof(unsigned), c->stream) != hipSuccess) { (void)hipGetLastError(); return; }
+    const unsigned nbx = (unsigned)((c->Bp + (int64_t)kThreads * kNarrowPerThread - 1) / ((int64_t)kThreads * kNarrowPerThread));
+    const int64_t chunk = 32768;  // datasets per launch (gridDim.y limit)
+    for (int64_t t0 = 0; t0 < T; t0 += chunk)
+        hipLaunchKernelGGL(k_counts_narrow, dim3(nbx, (unsigned)std::min(chunk, T - t0)), dim3(kThreads), 0, c->stream,
+                           (const double*)c->counts.p + t0 * c->Bp, c->B, c->Bp, (uint8_t*)c->cnt8.p + t0 * c->Bp, (unsigned*)c->cnt8_bad.p + t0);
+    c->h_cnt8_bad.assign((size_t)T, 1u);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpyAsync(c->h_cnt8_bad.data(), c->cnt8_bad.p, (size_t)T * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return;
+    }
+    c->cnt8_valid = true;
+}
+
+// is there a narrow copy that dense launches may read at all ...
+bool narrow_on(const bi_ctx* c) { return c->narrow_counts && c->cnt8_valid && !c->unbinned && c->dense_counts; }
+// ... does it represent dataset ds exactly ...
+bool narrow_has(const bi_ctx* c, int64_t ds) {
+    return c->cnt8_valid && ds >= 0 && ds < (int64_t)c->h_cnt8_bad.size() && c->h_cnt8_bad[(size_t)ds] == 0u;
+}
+// ... and every one of the T datasets (batches planned on the device: their dataset list exists only there)
+bool narrow_has_all(bi_ctx* c) {
+    if (!c->cnt8_valid) return false;
+    if (c->cnt8_all < 0) c->cnt8_all = std::all_of(c->h_cnt8_bad.begin(), c->h_cnt8_bad.end(), [](uint32_t f) { return f == 0u; }) ? 1 : 0;
+    return c->cnt8_all == 1;
+}
+
 // k_finish over n_slots (item, slot) sums, G slots per item, of nbx per-block partials each: 64 lanes per slot up to 64
 // blocks, else a whole block
 void launch_finish(bi_ctx* c, const double* partial, const unsigned* pflags, int nbx, int G, int64_t n_slots, const int64_t* perm,

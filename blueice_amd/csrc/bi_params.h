@@ -89,6 +89,7 @@ const ParamDef kParams[] = {
     {"dot_lanes", kParamRW, BI_P_GET(c->dot_lanes), BI_P_SET(c->dot_lanes = (v == 16 || v == 8 || v == 4) ? v : 0)},
     {"compact_budget", kParamRW, BI_P_GET(c->compact_budget), BI_P_SET(c->compact_budget = v)},
     {"toy_offset", kParamRW, BI_P_GET(c->toy_offset), BI_P_RANGE(0, INT64_MAX, toy_offset, "toy_offset >= 0")},
+    {"narrow_counts", kParamRW, BI_P_GET(c->narrow_counts), BI_P_FLAG(narrow_counts)},
     {"mail_timeout_ms", kParamRW, BI_P_GET(c->mail_timeout_ms),
      BI_P_RANGE(1, 60000, mail_timeout_ms, "mail_timeout_ms in [1, 60000]")},
     // ---- triggers (write-only) ---------------------------------------------------------------------------------
@@ -117,6 +118,9 @@ const ParamDef kParams[] = {
     BI_P_RO("n_sorted_scans", c->n_sorted_scans),
     BI_P_RO("n_bb_exact", c->n_bb_exact),
     BI_P_RO("n_mail_resets", c->n_mail_resets),
+    BI_P_RO("last_streamed_bytes", c->last_streamed_bytes),
+    BI_P_RO("n_narrow_launches", c->n_narrow_launches),
+    BI_P_RO("narrow_ready", c->cnt8_valid ? 1 : 0),
     // "ready" = prepared AND in use as an evaluation path (with sparse = 0 at upload they serve split scans only)
     BI_P_RO("csr_ready", (c->csr_ready && (c->sparse_at_upload != 0 || !c->dense_counts)) ? 1 : 0),
     BI_P_RO("compact_ready", (c->compact_ready && c->ps_nonneg && (c->sparse_at_upload != 0 || !c->dense_counts)) ? 1 : 0),

@@ -272,6 +272,8 @@ int plan_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale,
     plan->sparse = sparse;
     plan->epoch = c->epoch;
     plan->no_reuse = !reuse;
+    plan->narrow = !sparse && !c->unbinned && c->cnt8_valid;      // ... and every dataset an item refers to has a narrow form
+    for (size_t it = 0; it < items.size() && plan->narrow; ++it) plan->narrow = narrow_has(c, pts[(size_t)items[it].first].key % c->T);
     plan->h_status = st;
     auto abort_plan = [&](int code) { free_plan_buffers(plan); delete plan; return code; };
     const int n_tiles = n_tiles_of(c);

@@ -882,6 +882,9 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
 
     bi_plan* plan = new bi_plan();
     plan->P = P; plan->sparse = sparse; plan->epoch = c->epoch; plan->device_planned = true; plan->no_reuse = false;
+    // (the points' datasets are known on the device only: the narrow copy of the counts is read if it is exact for ALL datasets --
+    //  for the one dataset there is when the batch names none)
+    plan->narrow = !sparse && !c->unbinned && (dataset ? narrow_has_all(c) : narrow_has(c, 0));
     DevBuf d_z, d_rs, d_ds, d_keys, d_keys2, d_idx, d_idx2, d_a, d_b, d_tmp, d_scal;
     auto cleanup = [&]() { dev_free(d_z); dev_free(d_rs); dev_free(d_ds); dev_free(d_keys);
                            dev_free(d_keys2); dev_free(d_idx); dev_free(d_idx2); dev_free(d_a); dev_free(d_b); dev_free(d_tmp); dev_free(d_scal); };

@@ -278,6 +278,10 @@ int eval_single_fused(bi_ctx* c, const PointGeom& g, const double* rates, int64_
     a.outlier = c->outlier;
     a.nan_S = (c->unbinned && !c->ps_finite) ? c->S : 0;
     if (fuse) arm_mail(c, a);
+    if (!sparse && narrow_on(c) && narrow_has(c, ds)) {
+        a.cnt8 = (const uint8_t*)c->cnt8.p + ds * c->Bp;
+        ++c->n_narrow_launches;
+    }
     const bool nt = !sparse && c->nt_loads != 0;
     // Repeated evaluations in one grid cell (a minimizer's access pattern): let most of the cell's rows keep the default
     // cache policy so that they stay in the 256 MiB Infinity Cache between calls (the rest, and every call into a new
@@ -436,6 +440,10 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
     a.B = c->B; a.Bp = c->Bp; a.n0 = n0; a.n1 = n1; a.n2 = n2; a.n_tiles = tiles; a.chunks = (int)c->tile_chunks;
     a.outlier = c->outlier;
     a.nan_S = (c->unbinned && !c->ps_finite) ? c->S : 0;
+    if (!sparse && narrow_on(c) && narrow_has(c, ds)) {
+        a.cnt8 = (const uint8_t*)c->cnt8.p;
+        ++c->n_narrow_launches;
+    }
     launch_morph_g(c, 1, a, dim3((unsigned)nbx, 1), bb, !sparse && c->nt_loads != 0);
     launch_finish(c, a.partial, a.pflags, nbx, 1, 1, (const int64_t*)(dev + (o + 2) * 8), (const double*)(dev + (o + 3) * 8),
                   (double*)res, (int32_t*)(res + 8));

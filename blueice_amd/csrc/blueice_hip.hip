@@ -50,6 +50,7 @@ int finish_counts(bi_ctx* c, int64_t T) {
                            (const double*)c->scratch.p, nblk, (double*)c->lgsum.p + t0, n);
     }
     HIP_TRY(c, hipGetLastError());
+    build_narrow_counts(c, T);      // (its flags reach the host with the synchronisation below)
     c->h_lgsum.assign((size_t)T, 0.0);
     HIP_TRY(c, hipMemcpyAsync(c->h_lgsum.data(), c->lgsum.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -93,7 +94,7 @@ void bi_destroy(bi_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    dev_free(c->ps); dev_free(c->nm); dev_free(c->nm_tot); dev_free(c->counts); dev_free(c->lgsum);
+    dev_free(c->ps); dev_free(c->nm); dev_free(c->nm_tot); dev_free(c->counts); dev_free(c->lgsum); dev_free(c->cnt8); dev_free(c->cnt8_bad);
     dev_free(c->scratch); dev_free(c->scratch2); dev_free(c->logmu); dev_free(c->toy_blocks_done); dev_free(c->ev_perm);
     dev_free(c->slot_dev); dev_free(c->slot_partial); dev_free(c->slot_pflags); dev_free(c->slot_counter); dev_free(c->space_edges);
     dev_free(c->mail); dev_free(c->mail_flags);
@@ -180,6 +181,7 @@ int bi_model_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anch
     if (d > 0 && (!n_anchor || !anchor_z)) return fail(c, BI_ERR_INVALID, "anchor arrays are NULL");
     c->model_ready = false;
     c->data_ready = false;  // a new model invalidates the data (likelihood.py:253)
+    c->cnt8_valid = false;
     ++c->epoch;
     c->d = d; c->S = S; c->B = B; c->bb_source = bb_source;
     c->Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
@@ -575,6 +577,9 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
     a.n_tiles = n_tiles_of(c);
     a.chunks = (int)c->tile_chunks;
     const int NS = a.n0 + a.n1 + a.n2;
+    c->last_streamed_bytes = plan->bytes;
+    // the morph launches below read the one-byte copy of the counts when every dataset of the plan has an exact one
+    const bool narrow = plan->narrow && !plan->sparse && narrow_on(c);
     if (plan->use_scan) {
         bi_plan::Class& k = plan->classes[0];
         ScanArgs sa{};
@@ -657,6 +662,11 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
                 b.fin_out = out;
                 b.fin_status = (int32_t*)plan->status.p;
                 arm_mail(c, b);
+            }
+            if (narrow) {
+                b.cnt8 = (const uint8_t*)c->cnt8.p;
+                c->last_streamed_bytes -= 7 * c->Bp * ni;
+                ++c->n_narrow_launches;
             }
             launch_morph_g(c, k.G, b, dim3((unsigned)k.nbx, (unsigned)ni), bb, nt);
             if (fuse) continue;
@@ -1150,6 +1160,7 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     c->csr_ready = c->compact_ready = false;
     ++c->epoch;
     dev_free(c->counts);  // the toys exist as non-empty-bin lists only
+    c->cnt8_valid = false;  // ... and the narrow copy of the dense counts goes with them (bi_counts_to_dense rebuilds it)
     const int nc = (int)g.w.size(), NS = nc * c->S;
     std::vector<int64_t> rowoff((size_t)NS);
     std::vector<double> coef((size_t)NS);
@@ -1359,6 +1370,7 @@ int bi_counts_to_dense(bi_ctx* c) {
                                (const int32_t*)c->nz_idx.p + lo, (const double*)c->nz_n.p + lo, nnz, (double*)c->counts.p + t * c->Bp);
     }
     HIP_TRY(c, hipGetLastError());
+    build_narrow_counts(c, c->T);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->dense_counts = true;
     ++c->epoch;                                  // plans made over the lists alone are stale
@@ -1375,6 +1387,7 @@ int bi_set_unbinned(bi_ctx* c, double outlier_likelihood) {
     HIP_TRY(c, hipSetDevice(c->device));
     ++c->epoch;
     c->unbinned = true;
+    c->cnt8_valid = false;
     c->outlier = outlier_likelihood;
     c->csr_ready = c->compact_ready = false;
     // one pseudo dataset with zero lgamma sum; the counts row is never read in this mode

@@ -13,6 +13,13 @@ void launch_morph(bi_ctx* c, const LaunchArgs& a, dim3 grid, bool bb, bool nt) {
         else hipLaunchKernelGGL((k_morph_reduce<G, false, false, 2>), grid, dim3(kThreads), 0, c->stream, a);
         return;
     }
+    if (a.cnt8) {      // every dataset of the launch has an exact one-byte copy of its counts: the same kernels, narrow counts load
+        if (bb && nt) hipLaunchKernelGGL((k_morph_reduce<G, true, true, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else if (bb) hipLaunchKernelGGL((k_morph_reduce<G, true, false, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else if (nt) hipLaunchKernelGGL((k_morph_reduce<G, false, true, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_morph_reduce<G, false, false, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
+        return;
+    }
     if (bb && nt) hipLaunchKernelGGL((k_morph_reduce<G, true, true>), grid, dim3(kThreads), 0, c->stream, a);
     else if (bb) hipLaunchKernelGGL((k_morph_reduce<G, true, false>), grid, dim3(kThreads), 0, c->stream, a);
     else if (nt) hipLaunchKernelGGL((k_morph_reduce<G, false, true>), grid, dim3(kThreads), 0, c->stream, a);
@@ -57,15 +64,17 @@ void launch_morph_g(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid, bool bb, b
 
 void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, const LaunchArgs& a, const SingleDesc& d) {
     const dim3 block(kThreads);
-#define BI_SINGLE(BBv, MODEv)                                                                                          \
+#define BI_SINGLE(BBv, MODEv, C8v)                                                                                          \
     do {                                                                                                               \
-        if (nt && fuse) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, true>), grid, block, 0, c->stream, a, d);    \
-        else if (nt) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, false>), grid, block, 0, c->stream, a, d);      \
-        else if (fuse) hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, true>), grid, block, 0, c->stream, a, d);    \
-        else hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, false>), grid, block, 0, c->stream, a, d);             \
+        if (nt && fuse) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, true, C8v>), grid, block, 0, c->stream, a, d);    \
+        else if (nt) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, false, C8v>), grid, block, 0, c->stream, a, d);      \
+        else if (fuse) hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, true, C8v>), grid, block, 0, c->stream, a, d);    \
+        else hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, false, C8v>), grid, block, 0, c->stream, a, d);             \
     } while (0)
-    if (c->unbinned) BI_SINGLE(false, 2);
-    else if (bb) BI_SINGLE(true, 0);
-    else BI_SINGLE(false, 0);
+    if (c->unbinned) BI_SINGLE(false, 2, false);
+    else if (a.cnt8 && bb) BI_SINGLE(true, 0, true);          // (the binned forms with an exact one-byte copy of the counts)
+    else if (a.cnt8) BI_SINGLE(false, 0, true);
+    else if (bb) BI_SINGLE(true, 0, false);
+    else BI_SINGLE(false, 0, false);
 #undef BI_SINGLE
 }

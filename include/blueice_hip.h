@@ -545,6 +545,15 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     Read-only n_sorted_scans counts the scans that ran on the copy
  *   mail_timeout_ms   in-launch finish: how long an item's collecting block waits for a sibling's partial sum before it gives
  *                     up with BI_ST_INTERNAL (2000)
+ *   narrow_counts     dense evaluations (sparse = 0, Beeston-Barlow, sources that may go negative) stream the counts of a dataset
+ *                     as ONE byte per bin instead of eight where that is exact: every upload of dense counts also builds a
+ *                     [T][padded bins] byte copy on the device (one more byte per bin and dataset; skipped, not an error, if it
+ *                     cannot be allocated), and a dataset all of whose values are whole numbers 0 ... 255 (not -0.0, nan, inf)
+ *                     is read from it by the morph kernels -- a launch only if EVERY dataset its work items refer to is
+ *                     such a dataset; every result bit is the same (1, default; 0 = always the doubles).  Read-only:
+ *                     narrow_ready (the copy exists for the resident data), n_narrow_launches (launches that read it),
+ *                     last_streamed_bytes (bytes the last bi_run_plan streamed: bi_plan_bytes -- the algorithmic bytes of the
+ *                     all-double formulation -- less 7 x padded bins for every work item read narrow)
  *   single_timing_reset   (write) zero the single-call wall-time accumulators below
  *   bb_max_group      points per work item of a Beeston-Barlow batch (the points of a grid cell share a pass over the streams):
  *                     1, 2, 4, 8 (default) or 16 -- sixteen keep their accumulators partly in AGPRs, one wave per SIMD
