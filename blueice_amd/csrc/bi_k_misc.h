@@ -1234,6 +1234,7 @@ struct SimArgs {
     int64_t stride[kMaxDim];     // bins (C order) per step along the axis
 };
 constexpr uint32_t kSimTag = 0x53494D45u;
+constexpr double kSimMaxRate = 1073741824.0;   // 2^30 expected events per source: toy_event_count returns an int, bi_simulate_events refuses more
 
 // dens [S][B] (morphed densities) -> pmf [S][B] = density x bin volume (negative / nan densities count as 0)
 __global__ __launch_bounds__(kThreads) void k_sim_pmf(const double* __restrict__ dens, SimArgs a, const double* __restrict__ edges,
@@ -1257,7 +1258,7 @@ __global__ void k_sim_counts(const double* __restrict__ rates, int S, uint64_t s
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= S) return;
     const double M = rates[s];
-    n_out[s] = (M > 0.0 && M < 1e15) ? (int64_t)toy_event_count(M, seed ^ 0x9E3779B97F4A7C15ull, (int64_t)s) : 0;
+    n_out[s] = (M > 0.0 && M < kSimMaxRate) ? (int64_t)toy_event_count(M, seed ^ 0x9E3779B97F4A7C15ull, (int64_t)s) : 0;
 }
 
 __global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restrict__ cdf /*[S][B]*/, int64_t B, SimArgs a,

@@ -1549,6 +1549,9 @@ int bi_simulate_events(bi_ctx* tp, bi_ctx* c, const double* z, const double* rat
     for (int s = 0; s < S; ++s)
         if (!(r[(size_t)s] >= 0.0 && r[(size_t)s] < std::numeric_limits<double>::infinity()))
             return fail(c, BI_ERR_INVALID, "event simulation needs rates in [0, inf)");
+    for (int s = 0; s < S; ++s)               // (N_s travels as a 32-bit int through the samplers: keep it far inside)
+        if (r[(size_t)s] >= kSimMaxRate)
+            return fail(c, BI_ERR_INVALID, "event simulation draws at most 2^30 expected events per source: source %d has %g", s, r[(size_t)s]);
     const int nc = (int)g.w.size();
     const int64_t B = tp->B;
     std::vector<int64_t> rowoff((size_t)S * nc);

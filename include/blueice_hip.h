@@ -154,7 +154,24 @@ int bi_score_events(bi_ctx* templates, bi_ctx* target, int method, int k, const 
  *   n_edges [k], edges concatenated: the BIN EDGES of the analysis space
  *   n_per_source [S] or NULL: receives the number of events drawn per source
  * bi_download_events copies the simulated coordinates [k][N] (and the source index of every event) to the host,
- * N = bi_simulated_event_count. */
+ * N = bi_simulated_event_count.
+ *
+ * The random stream, exactly (Philox, u53, poisson_small and poisson_ptrs as defined at bi_generate_toys below; binary64):
+ *   rates   r_s = mus_s(z) rate_scale_s.  N_s = 0 where r_s = 0; otherwise N_s is the event count of bi_generate_toys' stream B
+ *           with M = r_s, dataset number t = s and the key taken from  seed ^ 0x9E3779B97F4A7C15  (everything below is keyed
+ *           by the seed itself).  The count travels as a 32-bit int: rates of 2^30 and above are refused (BI_ERR_INVALID,
+ *           "... at most 2^30 expected events per source"), so that no count can pass 2^31.
+ *   pmf     bins are numbered in C order over the axes (axis 0 slowest; stride_i = prod_{i' > i} (n_edges_i' - 1)); the decode
+ *           of bin b is, axis by axis from 0:  i_ax = rem / stride_ax, rem -= i_ax stride_ax.  vol_b = prod_ax (e_ax[i_ax + 1] -
+ *           e_ax[i_ax]) (multiplied in axis order from 1), pmf_s,b = max(density_s,b(z) vol_b, 0) (nan counts as 0), F_s = the
+ *           running sums of pmf_s over b (a device prefix sum: a fixed tree order, not left to right).
+ *   events  are stored -- and downloaded -- in drawn order: source by source, event j = 0 .. N_s - 1 of source s at position
+ *           first_s + j, first_s = sum_{s' < s} N_s'.  score_sorted orders a private index of the events by histogram cell for
+ *           the scoring gathers only; the stored coordinates, their order and the per-event values handed back are untouched.
+ *           bin:       (r0, r1, ., .) = Philox(counter = (j mod 2^32, j >> 32, s, 0x53494D45), key);  target = u53(r0, r1) F_s[B-1];
+ *                      the bin is the first b with F_s[b] > target, clamped to B - 1 (so never a bin of zero pmf below the last).
+ *           position:  per axis ax, (r0, r1, ., .) = Philox(counter = (j mod 2^32, j >> 32, s | ax << 24, 0x53494D46), key),
+ *                      u = u53(r0, r1),  x_ax = e_ax[i_ax] + u (e_ax[i_ax + 1] - e_ax[i_ax])  (the multiply-add may be fused). */
 int bi_simulate_events(bi_ctx* templates, bi_ctx* target, const double* z, const double* rate_scale, int method, int k,
                        const int32_t* n_edges, const double* edges, uint64_t seed, double outlier_likelihood,
                        int64_t* n_per_source);
@@ -166,7 +183,37 @@ int64_t bi_simulated_event_count(const bi_ctx* target);
  * the source's pdf) followed by set_data's binning (blueice/likelihood.py:603-609).  Philox4x32-10 keyed by
  * (seed; dataset, bin): reproducible and independent of launch geometry.  The T datasets REPLACE the
  * context's data and are stored as non-empty-bin lists only (no [T][B] array, no host transfer);
- * bi_eval_datasets works on them directly, point evaluations when the compacted templates fit the budget. */
+ * bi_eval_datasets works on them directly, point evaluations when the compacted templates fit the budget.
+ *
+ * The random streams, exactly (binary64; tests/toy_oracle.py is written from this text).  Toy t of a call is dataset
+ * D = toy_offset + t of the seed's stream, whatever the launch geometry; key = (seed mod 2^32, seed >> 32); Dlo = D mod 2^32,
+ * Dhi = (D >> 32) & 0xFFFF (dataset numbers are told apart up to 2^48).  Philox = Philox4x32-10 as written out at
+ * bi_sample_stretch.  u53(a, b) = ((a >> 5) 2^26 + (b >> 6)) 2^-53, uniform on [0, 1).
+ *   poisson_small(lam, u), lam < 10: inversion by sequential search.  p = F = exp(-lam), n = 0; while u > F and n < 1000:
+ *       n += 1, p *= lam / n, F += p; the draw is n -- in exact arithmetic the smallest n with u <= CDF(n; lam).  The cap:
+ *       where the rounded F stalls below a u within a few ulp of 1 the loop runs out and the draw is 1000 (probability
+ *       ~2^-50 per draw; it is returned as drawn, not clamped).
+ *   poisson_ptrs(lam, D, b), lam >= 10: PTRS (Hoermann 1993).  slam = sqrt(lam), loglam = log(lam), bb = 0.931 + 2.53 slam,
+ *       aa = -0.059 + 0.02483 bb, invalpha = 1.1239 + 1.1328 / (bb - 3.4), vr = 0.9277 - 3.6224 / (bb - 2).  Attempt a = 0, 1, ...:
+ *         (r0, r1, r2, r3) = Philox(counter = (b mod 2^32, b >> 32, Dlo, Dhi | (a + 1) << 16), key)
+ *         U = u53(r0, r1) - 0.5, V = u53(r2, r3), us = 0.5 - |U|, k = floor((2 aa / us + bb) U + lam + 0.43)
+ *         if us >= 0.07 and V <= vr: the draw is k
+ *         if k < 0 or (us < 0.013 and V > us): next attempt
+ *         if log(V) + log(invalpha) - log(aa / (us us) + bb) <= -lam + k loglam - lgamma(k + 1): the draw is k
+ *       (after 4096 rejected attempts the draw is floor(lam); the acceptance is above 0.9 per attempt).
+ *   A, one draw per bin (toy_events = 0, B < 4096, templates that may be negative, or expectations not sparse -- see
+ *   toy_events): bins 2q and 2q + 1 share the block (r0, r1, r2, r3) = Philox(counter = (q mod 2^32, q >> 32, Dlo, Dhi), key):
+ *       the even bin draws poisson_small(mu, u53(r0, r1)), the odd one poisson_small(mu, u53(r2, r3)), each where 0 < mu < 10;
+ *       a bin with mu >= 10 draws poisson_ptrs(mu, D, b) with its own bin number b; mu = 0 (or nan, or below 0) gives 0.
+ *   B, event by event (last_toy_method = 1): M = sum_b mu_b and the running sums F of mu come from a device prefix sum (a
+ *   fixed tree order).  The call goes this way iff 0 < M < B / 8 and M + 12 sqrt(max(M, 1)) + 32 <= 32768, and no toy of
+ *   the call draws more events than the smallest power of two >= that bound (at least 1024); else all of it goes by A.
+ *       events of the toy:  N = poisson_ptrs(M, D, 2^40 + 7) for M >= 10 (a bin no model has); for M < 10
+ *                           N = poisson_small(M, u53(r0, r1)), (r0, r1, ., .) = Philox(counter = (0xFFFFFFFF, 0x45564E54, Dlo, Dhi), key)
+ *       bin of event e < N: (r0, r1, ., .) = Philox(counter = (e, 0x45564E54, Dlo, Dhi), key), target = u53(r0, r1) M; the bin
+ *                           is the first b with F[b] > target, clamped to B - 1: bins of mu = 0 below the last never get one.
+ *       The toy's counts are the histogram of its events' bins (sorted per toy in LDS -- a 4-bit LSD radix sort up to 16384
+ *       keys, a bitonic network for 32768 -- and run-length encoded); the lists come out in ascending bin order by A and B. */
 int bi_generate_toys(bi_ctx* ctx, const double* z, const double* rate_scale, int64_t T, uint64_t seed);
 /* Expands device-generated toys (non-empty-bin lists) into the dense [T][B] counts array as well, on the device: what
  * the paths that visit every bin need -- Beeston-Barlow point evaluations and gradients (likelihood.py:618-660 read n in
