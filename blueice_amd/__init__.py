@@ -7,6 +7,6 @@ from .model import Model  # noqa: F401
 from .priors import GaussianPrior  # noqa: F401
 from .source import Source, HistogramPdfSource, DensityEstimatingSource, MonteCarloSource  # noqa: F401
 from .likelihood import (LogLikelihoodBase, BinnedLogLikelihood, UnbinnedLogLikelihood,  # noqa: F401
-                         LogLikelihoodSum, LogLikelihoodReParam, LogAncillaryLikelihood)
+                         LogLikelihoodSum, LogLikelihoodReParam, LogAncillaryLikelihood, toy_seed)
 
 __version__ = '0.1.0'

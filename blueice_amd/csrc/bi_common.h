@@ -3,6 +3,7 @@
 // small kernels) reaches the heavy template families, each of which is compiled in its own translation unit so that a
 // clean build runs on several cores (blueice_amd/build.py):
 //     tu_morph.hip        k_morph_reduce (values, gradients, unbinned), k_morph_single        bi_k_morph.h
+//                         k_morph_sets (unbinned work items with an event set each)          bi_k_sets.h
 //     tu_scan.hip         k_scan_mfma, k_scan_valid                                          bi_k_scan.h
 //     tu_scan_sorted.hip  k_scan_sorted                                                      bi_scan_sorted.h
 //     tu_grad.hip         k_grad_mfma, k_morph_bbgrad                                        bi_k_grad_mfma.h, bi_k_bbgrad.h
@@ -66,6 +67,8 @@ struct EventScope {
 void launch_morph_g(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid, bool bb, bool nt);
 // ... MODE 1 / 3: value + gradient columns of one point (G = 2, 4, 8, 16 columns)
 void launch_morph_grad(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid, bool nt);
+// k_morph_sets<G, MODE>: unbinned work items that each have their own event set (item_cnt = the set's events); G = 1 values
+void launch_morph_sets(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid);
 // k_morph_single<BB, NT, MODE, FUSE>: the single-point call
 void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, const LaunchArgs& a, const SingleDesc& d);
 // k_morph_bbgrad<G, DZ, NT>: value + gradient with Beeston-Barlow; BI_ERR_INVALID for a column count without a variant

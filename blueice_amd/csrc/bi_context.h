@@ -99,6 +99,12 @@ struct bi_ctx {
     bool data_ready = false;
     bool dense_counts = false;  // counts [T][Bp] resident (false for device-generated toys: CSR lists only)
     int64_t T = 0;
+    // unbinned: the event sets held side by side on the event axis (bi_score_event_sets / bi_simulate_event_toys); set t is
+    // columns [set_first[t], set_first[t] + set_n[t]), every first even.  With several sets T = n_sets and B = set_n[0]: what
+    // knows nothing of sets evaluates set 0 (its columns start at 0; the tiles behind them are masked by B)
+    int64_t n_sets = 1;
+    std::vector<int64_t> set_first, set_n;
+    int64_t n_set_launches = 0;                  // read-only: launches of k_morph_sets
     DevBuf counts, lgsum;
     std::vector<double> h_lgsum;
     // the narrow copy of the dense counts: [T][Bp] bytes beside the doubles, rebuilt by every writer of `counts`
@@ -227,6 +233,8 @@ struct bi_ctx {
     DevBuf sim_coords, sim_source;
     int sim_k = 0;
     int64_t sim_n = -1;
+    int64_t sim_epoch = -1;     // ... and the data epoch they belong to
+    int64_t sim_cols = -1;      // bi_simulate_event_toys: the buffers hold this many columns in the padded layout of the sets (-1: one toy)
 
     // scratch
     DevBuf scratch, scratch2, logmu;
@@ -261,6 +269,8 @@ struct bi_ctx {
 
 namespace {
 
+inline bool multi_set(const bi_ctx* c) { return c->unbinned && c->n_sets > 1; }
+
 int fail(bi_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -269,6 +279,10 @@ int fail(bi_ctx* c, int code, const char* fmt, ...) {
     va_end(ap);
     if (c) c->err = buf; else g_create_error = buf;
     return code;
+}
+
+int refuse_sets(bi_ctx* c, const char* what) {
+    return fail(c, BI_ERR_INVALID, "%s is not available on an unbinned context that holds several event sets (%lld)", what, (long long)c->n_sets);
 }
 
 #define HIP_TRY(c, expr)                                                                          \

@@ -14,7 +14,7 @@ struct LaunchArgs {
     const int64_t* rowoff;  // [items][NS]  element offsets of the stream rows
     const double* coef;     // [items][NS][G]
     const double* aux;      // [items][G][2]  (p_cal, N) for BB
-    const int64_t* item_cnt; // [items] element offset of the item's counts row
+    const int64_t* item_cnt; // [items] element offset of the item's counts row (k_morph_sets: the events of the item's set)
     const int32_t* item_tiles; // [items] 512-bin tiles of the item's rows (NULL: n_tiles)
     double* partial;        // [items][nbx][G]
     unsigned* pflags;       // [items][nbx][G]

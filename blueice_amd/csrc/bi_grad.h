@@ -290,6 +290,9 @@ int eval_grad_bb(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
 
 }  // namespace
 
+static int eval_grad_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                            double* grad, int32_t* status, bool values_only);
+
 extern "C" {
 
 int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
@@ -302,11 +305,21 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
         HIP_TRY(c, hipSetDevice(c->device));
         return eval_grad_bb(c, P, z, rate_scale, dataset, ll, grad, status);
     }
+    return eval_grad_points(c, P, z, rate_scale, dataset, ll, grad, status, false);
+}
+
+}  // extern "C"
+
+// bi_eval_grad without Beeston-Barlow.  values_only (unbinned contexts with several event sets, bi_eval): the same
+// descriptors with the value column alone, grad is not touched.
+static int eval_grad_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                            double* grad, int32_t* status, bool values_only) {
+    int rc;
     const int S = c->S, d = c->d;
-    const int W = 1 + d + S;
+    const int W = values_only ? 1 : 1 + d + S;
     if (W > kMaxG) return fail(c, BI_ERR_INVALID, "1 + d + S = %d exceeds %d gradient columns", W, kMaxG);
     HIP_TRY(c, hipSetDevice(c->device));
-    const int G = std::max(2, pick_class(W, kMaxG));
+    const int G = values_only ? 1 : std::max(2, pick_class(W, kMaxG));
     const int de = (int)c->eff_axes.size();
     const int nc = 1 << de, NS = nc * S;
     bool any_neg = false;
@@ -330,10 +343,12 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     // exits), then the descriptor arrays of the live ones are filled.  Both run on a few host threads for large batches --
     // the batched profile-fit engine calls this once per optimiser iteration over every running problem, and at ~1.7 us
     // per point single-threaded the host half was six times the kernels' time at 10^5 points.
-    if (unb) dataset = nullptr;        // (one dataset)
+    // (one dataset -- or several event sets side by side on the event axis: set t is columns [first_t, first_t + N_t))
+    const bool sets = multi_set(c);
+    if (unb && !sets) dataset = nullptr;
     const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, dataset, status, [&](int64_t p) {
         ll[p] = ninf;
-        for (int j = 0; j < d + S; ++j) grad[p * (d + S) + j] = qnan;
+        for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
     });
     const int64_t n_items = (int64_t)live.size();
     if (n_items == 0) return BI_OK;
@@ -349,7 +364,7 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
             const int64_t ds = dataset ? dataset[p] : 0;
             pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
             const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
-            const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
+            const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : (sets ? c->set_first[(size_t)ds] : 0);
             const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * G;
             int k = 0;
             for (int corner = 0; corner < nc; ++corner)
@@ -357,23 +372,40 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
                     const int64_t row = (pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s;
                     rowoff[ro + k] = row_base + row * row_stride;
                     double* col = &coef[co + (size_t)k * G];
-                    pd.first_order(col, corner, s, axis_col.data(), 1 + d + s);
+                    if (values_only) col[0] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];      // (first_order's column 0)
+                    else pd.first_order(col, corner, s, axis_col.data(), 1 + d + s);
                     if (sparse) {
                         const double tz = c->h_Tz[(size_t)(ds * n_rows + row)];
                         for (int q = 0; q < W; ++q) slot_lg[po + q] += col[q] * tz;
                     }
                 }
-            if (unb)
+            if (unb && values_only) {
+                double rsum = 0.0;
+                for (int s = 0; s < S; ++s) rsum += pd.r[(size_t)s];
+                slot_lg[po] = rsum;
+            } else if (unb)
                 pd.first_order_unbinned(&slot_lg[po], axis_col.data(), 1 + d);
             else
                 slot_lg[po] += c->h_lgsum[(size_t)ds];
             for (int q = 0; q < W; ++q) perm[po + q] = i * W + q;
-            cnt_off[(size_t)i] = unb ? 0 : (sparse ? c->h_cnt_off[(size_t)ds] : ds * c->Bp);
-            tiles[(size_t)i] = (int32_t)(row_stride / kTile);
+            // (several event sets: the item's tiles cover its own segment, and k_morph_sets takes the segment's length here)
+            cnt_off[(size_t)i] = sets ? c->set_n[(size_t)ds] : unb ? 0 : (sparse ? c->h_cnt_off[(size_t)ds] : ds * c->Bp);
+            tiles[(size_t)i] = sets ? (int32_t)std::max<int64_t>(1, (c->set_n[(size_t)ds] + kTile - 1) / kTile) : (int32_t)(row_stride / kTile);
         }
     });
     int max_tiles = 1;
     for (int32_t t : tiles) max_tiles = std::max(max_tiles, (int)t);
+    // several event sets: a launch whose items all name ONE set runs the ordinary kernels over that set's columns (the row
+    // offsets start at first_t, B = N_t; their counts offset is 0 as for every unbinned launch); items with different sets
+    // take k_morph_sets, every item over its own segment, whose length travels in the counts-offset array
+    bool mixed = false;
+    int64_t ds0 = 0;
+    if (sets) {
+        ds0 = dataset ? dataset[live[0]] : 0;
+        for (int64_t i = 1; dataset && i < n_items && !mixed; ++i) mixed = dataset[live[(size_t)i]] != ds0;
+        if (mixed) ++c->n_set_launches;
+        else std::fill(cnt_off.begin(), cnt_off.end(), (int64_t)0);
+    }
     // descriptors: one packed copy; results: k_finish writes them straight into pinned host memory
     PackedUpload pu;
     if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
@@ -389,6 +421,7 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     a.outlier = c->outlier;
     a.nan_S = (unb && !c->ps_finite) ? c->S : 0;
     if (unb) a.counts = (const double*)c->ps.p;        // (never read in this mode: any valid device address)
+    if (sets) a.B = c->set_n[(size_t)ds0];             // (one set: its events; several: k_morph_sets takes every item's own)
     const bool nt = !sparse && (c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1));
     rc = run_item_chunks(c, n_items, max_tiles, G, pu.dev<int64_t>(4), pu.dev<double>(5), h_out, nullptr, "bi_eval_grad",
                          [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
@@ -399,16 +432,17 @@ int bi_eval_grad(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
                              b.item_tiles = pu.dev<int32_t>(3) + i0;
                              b.partial = partial;
                              b.pflags = pflags;
-                             launch_morph_grad(c, G, b, grid, nt);
+                             if (mixed) launch_morph_sets(c, G, b, grid);
+                             else if (values_only) launch_morph_g(c, 1, b, grid, false, nt);
+                             else launch_morph_grad(c, G, b, grid, nt);
                              return BI_OK;
                          });
     if (rc) return rc;
     for (int64_t i = 0; i < n_items; ++i) {
         const int64_t p = live[(size_t)i];
         ll[p] = h_out[(size_t)i * W];
-        for (int j = 0; j < d + S; ++j) grad[p * (d + S) + j] = (unb && !std::isfinite(ll[p])) ? qnan : h_out[(size_t)i * W + 1 + j];
+        for (int j = 0; !values_only && j < d + S; ++j)
+            grad[p * (d + S) + j] = (unb && !std::isfinite(ll[p])) ? qnan : h_out[(size_t)i * W + 1 + j];
     }
     return BI_OK;
 }
-
-}  // extern "C"

@@ -72,7 +72,8 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     for (int q = 0; q < D; ++q) full[(size_t)q] = q < de ? c->eff_axes[(size_t)q] : d + (q - de);
 
     // the points that are evaluated at all, then the descriptors of the live ones (as bi_eval_grad)
-    if (unb) dataset = nullptr;        // (one dataset)
+    if (dataset && multi_set(c)) return refuse_sets(c, "bi_eval_hess with a dataset column");
+    if (unb) dataset = nullptr;        // (one dataset; several event sets: set 0, whose columns B counts)
     const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, dataset, status, [&](int64_t p) {
         ll[p] = ninf;
         for (int j = 0; j < F; ++j) grad[p * F + j] = qnan;

@@ -1261,15 +1261,10 @@ __global__ void k_sim_counts(const double* __restrict__ rates, int S, uint64_t s
     n_out[s] = (M > 0.0 && M < kSimMaxRate) ? (int64_t)toy_event_count(M, seed ^ 0x9E3779B97F4A7C15ull, (int64_t)s) : 0;
 }
 
-__global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restrict__ cdf /*[S][B]*/, int64_t B, SimArgs a,
-                                                         const double* __restrict__ edges, const int64_t* __restrict__ first /*[S+1]*/,
-                                                         uint64_t seed, int64_t N, double* __restrict__ coords /*[k][N]*/,
-                                                         int32_t* __restrict__ source /*[N]*/) {
-    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (e >= N) return;
-    int s = 0;
-    while (s + 1 < a.S && e >= first[s + 1]) ++s;
-    const int64_t j = e - first[s];                                      // event j of source s
+// event j of source s of the toy keyed by `seed`, stored at column e of coords [k][N]
+__device__ __forceinline__ void sim_one_event(const double* __restrict__ cdf /*[S][B]*/, int64_t B, const SimArgs& a,
+                                              const double* __restrict__ edges, uint64_t seed, int s, int64_t j, int64_t N, int64_t e,
+                                              double* __restrict__ coords /*[k][N]*/, int32_t* __restrict__ source /*[N]*/) {
     const double* __restrict__ F = cdf + (int64_t)s * B;
     const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
     uint32_t r[4];
@@ -1293,6 +1288,92 @@ __global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restric
         coords[(int64_t)ax * N + e] = ed[i] + u * (ed[i + 1] - ed[i]);
     }
     source[e] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restrict__ cdf /*[S][B]*/, int64_t B, SimArgs a,
+                                                         const double* __restrict__ edges, const int64_t* __restrict__ first /*[S+1]*/,
+                                                         uint64_t seed, int64_t N, double* __restrict__ coords /*[k][N]*/,
+                                                         int32_t* __restrict__ source /*[N]*/) {
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= N) return;
+    int s = 0;
+    while (s + 1 < a.S && e >= first[s + 1]) ++s;
+    sim_one_event(cdf, B, a, edges, seed, s, e - first[s], N, e, coords, source);          // event j = e - first_s of source s
+}
+
+// ---- an ensemble of T event-level toys (bi_simulate_event_toys) ------------------------------------------------
+// Toy D of the seed's ensemble is bi_simulate_events' toy with the seed toy_seed(seed, D) (include/blueice_hip.h): D ->
+// seed + (D + 1) c is one-to-one modulo 2^64 (c odd), the rest is the bijective finaliser of splitmix64.
+__host__ __device__ inline uint64_t toy_seed(uint64_t seed, uint64_t D) {
+    uint64_t x = seed + (D + 1ull) * 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// one launch for the T x S counts: N_{t,s} ~ Poisson(rate_s) of toy toy0 + t (k_sim_counts with that toy's seed)
+__global__ void k_sim_toy_counts(const double* __restrict__ rates, int S, int64_t T, uint64_t seed, int64_t toy0, int64_t* __restrict__ n_out /*[T][S]*/) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * S) return;
+    const int64_t t = i / S;
+    const int s = (int)(i - t * S);
+    const double M = rates[s];
+    const uint64_t ts = toy_seed(seed, (uint64_t)(toy0 + t));
+    n_out[i] = (M > 0.0 && M < kSimMaxRate) ? (int64_t)toy_event_count(M, ts ^ 0x9E3779B97F4A7C15ull, (int64_t)s) : 0;
+}
+
+// the columns a toy takes: its events rounded up to even, so that the next set starts 16-byte aligned; room [T + 1] (last 0)
+// goes through an exclusive prefix sum -> set_first [T + 1]
+__global__ void k_sim_toy_room(const int64_t* __restrict__ n /*[T][S]*/, int S, int64_t T, int64_t* __restrict__ room /*[T+1]*/) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > T) return;
+    int64_t tot = 0;
+    if (t < T) for (int s = 0; s < S; ++s) tot += n[t * S + s];
+    room[t] = (tot + 1) & ~(int64_t)1;
+}
+
+// first_{t,s} = set_first_t + sum_{s' < s} N_{t,s'}: [T][S + 1], the last entry the end of the toy's events
+__global__ void k_sim_toy_first(const int64_t* __restrict__ n /*[T][S]*/, const int64_t* __restrict__ set_first /*[T+1]*/, int S, int64_t T,
+                                int64_t* __restrict__ first /*[T][S+1]*/) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    int64_t at = set_first[t];
+    for (int s = 0; s < S; ++s) { first[t * (S + 1) + s] = at; at += n[t * S + s]; }
+    first[t * (S + 1) + S] = at;
+}
+
+// one launch for the bin search and the positions of all (t, s, j): column e of the padded layout belongs to the toy whose
+// [set_first_t, set_first_{t+1}) holds it (bisection), then to a source as in k_sim_events.  A padding column (at most one
+// behind a toy) gets the coordinate 0 and source -1.
+__global__ __launch_bounds__(kThreads) void k_sim_toy_events(const double* __restrict__ cdf /*[S][B]*/, int64_t B, SimArgs a,
+                                                             const double* __restrict__ edges, const int64_t* __restrict__ set_first /*[T+1]*/,
+                                                             const int64_t* __restrict__ first /*[T][S+1]*/, int64_t T, uint64_t seed,
+                                                             int64_t toy0, int64_t N /*columns*/, double* __restrict__ coords /*[k][N]*/,
+                                                             int32_t* __restrict__ source /*[N]*/) {
+    const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (e >= N) return;
+    int64_t lo = 0, hi = T;                          // the last t with set_first[t] <= e (empty toys share their start with the next)
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (set_first[mid] <= e) lo = mid; else hi = mid;
+    }
+    const int64_t t = lo;
+    const int64_t* __restrict__ f = first + t * (a.S + 1);
+    if (e >= f[a.S]) {                               // padding
+        for (int ax = 0; ax < a.k; ++ax) coords[(int64_t)ax * N + e] = 0.0;
+        source[e] = -1;
+        return;
+    }
+    int s = 0;
+    while (s + 1 < a.S && e >= f[s + 1]) ++s;
+    sim_one_event(cdf, B, a, edges, toy_seed(seed, (uint64_t)(toy0 + t)), s, e - f[s], N, e, coords, source);
+}
+
+// value -> the given columns of every row (the padding columns between event sets)
+__global__ void k_fill_columns(double* __restrict__ rows, int64_t row_stride, int64_t n_rows, const int64_t* __restrict__ cols, int64_t n_cols, double value) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows * n_cols) return;
+    rows[(i / n_cols) * row_stride + cols[i % n_cols]] = value;
 }
 
 // small device -> pinned-host copies as a kernel (bi_memcpy_to_host): a copy-engine transfer of 80 KB costs 15 ... 110 us on

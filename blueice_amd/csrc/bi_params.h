@@ -109,6 +109,7 @@ const ParamDef kParams[] = {
     BI_P_RO("n_toy_points_passes", c->n_toy_points_passes),
     BI_P_RO("n_bb_scan_launches", c->n_bb_scan_launches),
     BI_P_RO("n_sampler_half_steps", c->n_sampler_half_steps),
+    BI_P_RO("n_set_launches", c->n_set_launches),
     BI_P_RO("last_plan_refused", c->plan_refused),
     BI_P_RO("tmm_entry_bytes", c->tmm_ok ? c->tmm_width : 0),
     BI_P_RO("tm_entry_bytes", c->tm_width),

@@ -192,6 +192,8 @@ int bi_sample_stretch_gauss(bi_ctx* c, int64_t E, int W, int F, const int32_t* v
         if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
             (var_kind[j] != 0 && var_kind[j] != 1))
             return fail(c, BI_ERR_INVALID, "bi_sample_stretch: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
+    if (multi_set(c) && (E > 1 || (dataset && dataset[0] != 0)))
+        return refuse_sets(c, "bi_sample_stretch with more than one ensemble, or with another set than 0,");
     if (dataset)
         for (int64_t e = 0; e < E; ++e)
             if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: dataset %lld of ensemble %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);

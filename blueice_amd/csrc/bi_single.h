@@ -201,7 +201,7 @@ int eval_single_fused(bi_ctx* c, const PointGeom& g, const double* rates, int64_
     const int n0 = bb ? nc * (S - 1) : nc * S, n1 = bb ? nc : 0, n2 = bb ? nc : 0;
     const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
     const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
-    const int tiles = (int)(row_stride / kTile);
+    const int tiles = multi_set(c) ? (int)std::max<int64_t>(1, (c->set_n[(size_t)ds] + kTile - 1) / kTile) : (int)(row_stride / kTile);
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     // launch shape of ONE pass over the rows: every block gets the same number of tiles and all blocks are resident at
     // once (a second, thin round of blocks is a tail the size of a block's lifetime).  Measured on C2 (1954 tiles):
@@ -275,6 +275,10 @@ int eval_single_fused(bi_ctx* c, const PointGeom& g, const double* rates, int64_
     a.partial = fuse ? (double*)c->mail.p : (double*)c->slot_partial.p;
     a.pflags = (unsigned*)c->slot_pflags.p;
     a.B = c->B; a.Bp = c->Bp; a.n0 = n0; a.n1 = n1; a.n2 = n2; a.n_tiles = tiles; a.chunks = (int)c->tile_chunks;
+    if (multi_set(c)) {        // one of several event sets: the same kernel over that set's columns
+        a.ps += c->set_first[(size_t)ds];
+        a.B = c->set_n[(size_t)ds];
+    }
     a.outlier = c->outlier;
     a.nan_S = (c->unbinned && !c->ps_finite) ? c->S : 0;
     if (fuse) arm_mail(c, a);
@@ -352,7 +356,7 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
     if (!sparse && !c->dense_counts) return fail(c, BI_ERR_STATE, "dataset counts are not resident in dense form");
     const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
     const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
-    const int tiles = (int)(row_stride / kTile);
+    const int tiles = multi_set(c) ? (int)std::max<int64_t>(1, (c->set_n[(size_t)ds] + kTile - 1) / kTile) : (int)(row_stride / kTile);
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     const int nbx = (int)std::min<int64_t>(tiles, slots);
 
@@ -438,6 +442,10 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
     a.partial = (double*)c->slot_partial.p;
     a.pflags = (unsigned*)c->slot_pflags.p;
     a.B = c->B; a.Bp = c->Bp; a.n0 = n0; a.n1 = n1; a.n2 = n2; a.n_tiles = tiles; a.chunks = (int)c->tile_chunks;
+    if (multi_set(c)) {        // one of several event sets: the same kernel over that set's columns
+        a.ps += c->set_first[(size_t)ds];
+        a.B = c->set_n[(size_t)ds];
+    }
     a.outlier = c->outlier;
     a.nan_S = (c->unbinned && !c->ps_finite) ? c->S : 0;
     if (!sparse && narrow_on(c) && narrow_has(c, ds)) {

@@ -437,6 +437,7 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (c->bb_source >= 0) return fail(c, BI_ERR_INVALID, "bi_eval_datasets_points is not available with Beeston-Barlow");
+    if (multi_set(c)) return refuse_sets(c, "bi_eval_datasets_points");
     if (c->unbinned) return fail(c, BI_ERR_INVALID, "bi_eval_datasets_points needs a binned likelihood");
     if (P < 0 || P > 65535) return fail(c, BI_ERR_INVALID, "P = %lld outside [0, 65535]", (long long)P);
     if (t0 < 0 || t1 > c->T || t0 > t1) return fail(c, BI_ERR_INVALID, "dataset range [%lld,%lld) outside [0,%lld)", (long long)t0, (long long)t1, (long long)c->T);

@@ -187,6 +187,9 @@ int bi_model_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anch
     c->Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
     c->unbinned = false;
     c->ev_sorted = false;
+    c->n_sets = 1;
+    c->set_first.clear();
+    c->set_n.clear();
     c->n_anchor.assign(d, 0);
     c->grid.assign(d, {});
     c->A = 1;
@@ -210,7 +213,8 @@ int bi_model_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anch
     c->h_mus.assign((size_t)c->A * S, 0.0);
     c->h_nm_tot.assign((size_t)c->A, 0.0);
     c->anchor_set.assign((size_t)c->A, 0);
-    const size_t ps_bytes = (size_t)c->A * S * c->Bp * sizeof(double);
+    // (one tile of slack behind the last row: an event set that starts inside a tile is read in whole tiles from its first column)
+    const size_t ps_bytes = ((size_t)c->A * S * c->Bp + kTile) * sizeof(double);
     int rc = dev_alloc(c, c->ps, ps_bytes);
     if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(c->ps.p, 0, ps_bytes, c->stream));
@@ -473,11 +477,13 @@ int64_t bi_plan_launches(const bi_plan* p) { return p ? p->launches : 0; }
 
 int bi_plan_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
                    bi_plan** out) {
+    if (c && multi_set(c)) return refuse_sets(c, "bi_plan_points");
     return plan_points(c, P, z, rate_scale, dataset, out);
 }
 
 int bi_plan_points_share(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, int share_rank,
                          int share_world, bi_plan** out) {
+    if (c && multi_set(c)) return refuse_sets(c, "bi_plan_points_share");
     if (share_world < 1) return fail(c, BI_ERR_INVALID, "share_world must be >= 1");
     return plan_points(c, P, z, rate_scale, dataset, out, /*transient=*/false, share_rank, share_world);
 }
@@ -532,6 +538,7 @@ extern "C" {
 
 int bi_plan_points_resident(bi_ctx* c, int64_t P, const double* z_dev, const double* rate_scale_dev, const int64_t* dataset_dev,
                             int share_rank, int share_world, bi_plan** out) {
+    if (c && multi_set(c)) return refuse_sets(c, "bi_plan_points_resident");
     return plan_points_resident_impl(c, P, z_dev, rate_scale_dev, dataset_dev, share_rank, share_world, out, true);
 }
 
@@ -784,6 +791,13 @@ int bi_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, con
         if (status) *status = 0;
         return eval_single(c, z, rate_scale, dataset ? dataset[0] : 0, out, status);
     }
+    if (multi_set(c)) {                // several event sets: one work item per point over its own set (bi_grad.h)
+        int rc1 = check_ready(c, true);
+        if (rc1) return rc1;
+        if (P < 0) return fail(c, BI_ERR_INVALID, "bad P");
+        if (c->d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+        return eval_grad_points(c, P, z, rate_scale, dataset, out, nullptr, status, true);
+    }
     bi_plan* plan = nullptr;
     int rc = plan_points(c, P, z, rate_scale, dataset, &plan, /*transient=*/true);
     if (rc) return rc;
@@ -914,6 +928,7 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
     int rc = check_ready(c, true);
     if (rc) return rc;
     if (c->bb_source >= 0) return fail(c, BI_ERR_INVALID, "bi_eval_datasets is not available with Beeston-Barlow");
+    if (multi_set(c)) return refuse_sets(c, "bi_eval_datasets");
     if (c->unbinned) return fail(c, BI_ERR_INVALID, "bi_eval_datasets needs a binned likelihood");
     if (t0 < 0 || t1 > c->T || t0 > t1) return fail(c, BI_ERR_INVALID, "dataset range [%lld,%lld) outside [0,%lld)", (long long)t0, (long long)t1, (long long)c->T);
     if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
@@ -1396,6 +1411,9 @@ int bi_set_unbinned(bi_ctx* c, double outlier_likelihood) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->T = 1;
     c->h_lgsum.assign(1, 0.0);
+    c->n_sets = 1;
+    c->set_first.assign(1, 0);
+    c->set_n.assign(1, c->B);
     c->dense_counts = true;
     c->data_ready = true;
     return BI_OK;
@@ -1406,8 +1424,10 @@ int bi_set_unbinned(bi_ctx* c, double outlier_likelihood) {
 namespace {
 
 // coords: host [k][N], or coords_dev: the same block already in HBM (bi_simulate_events)
+// pad_cols (several event sets: the padding columns between them, which get 1.0 in every row): the events keep their order
 int score_events_impl(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t N,
-                      const double* coords, const double* coords_dev, double outlier_likelihood) {
+                      const double* coords, const double* coords_dev, double outlier_likelihood,
+                      const std::vector<int64_t>* pad_cols = nullptr) {
     if (!c) return BI_ERR_INVALID;
     if (!tp || tp == c) return fail(c, BI_ERR_INVALID, "need a templates context different from the target");
     if (c->pending || tp->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding: call bi_eval_end first");
@@ -1442,10 +1462,12 @@ int score_events_impl(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n
     int rc = bi_model_begin(c, tp->d, na.data(), az.data(), tp->S, N, -1);
     if (rc) return rc;
     if (N > 0) {
-        DevBuf d_ev, d_grid, d_base, d_t, d_keys, d_iota, d_tmp;
-        auto drop = [&]() { dev_free(d_ev); dev_free(d_grid); dev_free(d_base); dev_free(d_t); dev_free(d_keys); dev_free(d_iota); dev_free(d_tmp); };
+        DevBuf d_ev, d_grid, d_base, d_t, d_keys, d_iota, d_tmp, d_pad;
+        auto drop = [&]() { dev_free(d_ev); dev_free(d_grid); dev_free(d_base); dev_free(d_t); dev_free(d_keys); dev_free(d_iota); dev_free(d_tmp); dev_free(d_pad); };
         // events ordered by cell (see k_score_rows): from a few thousand events on, and while 32-bit positions do
-        const bool sorted = c->score_sorted && N >= 4096 && N < ((int64_t)1 << 31);
+        // (not with several event sets: a set is a range of columns)
+        const bool sorted = !pad_cols && c->score_sorted && N >= 4096 && N < ((int64_t)1 << 31);
+        if (pad_cols && !pad_cols->empty() && (rc = dev_upload(c, d_pad, *pad_cols))) { drop(); return rc; }
         size_t sort_bytes = 0;
         if (sorted) (void)prim_sort_pairs(nullptr, sort_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (const int32_t*)nullptr,
                                                     (int32_t*)nullptr, (size_t)N, 0u, 64u, c->stream);
@@ -1488,6 +1510,11 @@ int score_events_impl(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n
                 default: BI_ROWS(8); break;
             }
 #undef BI_ROWS
+            if (e == hipSuccess && pad_cols && !pad_cols->empty()) {
+                const int64_t n_fill = (int64_t)n_rows * (int64_t)pad_cols->size();
+                hipLaunchKernelGGL(k_fill_columns, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, c->stream, (double*)c->ps.p, c->Bp,
+                                   (int64_t)n_rows, (const int64_t*)d_pad.p, (int64_t)pad_cols->size(), 1.0);
+            }
             if (e == hipSuccess) e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);              // coords are borrowed for the call only
@@ -1598,6 +1625,7 @@ int bi_simulate_events(bi_ctx* tp, bi_ctx* c, const double* z, const double* rat
         (rc = dev_alloc(c, c->sim_source, (size_t)std::max<int64_t>(N, 1) * sizeof(int32_t))) || (rc = dev_upload(c, d_first, first))) { cleanup(); return rc; }
     c->sim_k = k;
     c->sim_n = N;
+    c->sim_cols = -1;
     if (N > 0) {
         hipLaunchKernelGGL(k_sim_events, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, (const double*)d_cdf.p, B, a,
                            (const double*)d_edges.p, (const int64_t*)d_first.p, seed, N, (double*)c->sim_coords.p, (int32_t*)c->sim_source.p);
@@ -1628,6 +1656,23 @@ int bi_download_events(bi_ctx* c, double* coords, int32_t* source) {
     if (!c) return BI_ERR_INVALID;
     if (c->sim_n < 0) return fail(c, BI_ERR_STATE, "no simulated events are resident (bi_simulate_events first)");
     HIP_TRY(c, hipSetDevice(c->device));
+    if (c->sim_cols >= 0) {            // an ensemble (bi_simulate_event_toys): the columns without the padding between the sets
+        if (!multi_set(c) || c->sim_epoch != c->epoch || c->sim_n == 0) return c->sim_n == 0 ? BI_OK : fail(c, BI_ERR_STATE, "the simulated ensemble is no longer the context's data");
+        std::vector<double> hc(coords ? (size_t)c->sim_cols * c->sim_k : 0);
+        std::vector<int32_t> hs(source ? (size_t)c->sim_cols : 0);
+        if (coords) HIP_TRY(c, hipMemcpyAsync(hc.data(), c->sim_coords.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (source) HIP_TRY(c, hipMemcpyAsync(hs.data(), c->sim_source.p, hs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        int64_t at = 0;
+        for (int64_t t = 0; t < c->n_sets; ++t) {
+            const int64_t f = c->set_first[(size_t)t], n = c->set_n[(size_t)t];
+            for (int ax = 0; coords && ax < c->sim_k; ++ax)
+                std::copy(hc.begin() + (size_t)ax * c->sim_cols + f, hc.begin() + (size_t)ax * c->sim_cols + f + n, coords + (size_t)ax * c->sim_n + at);
+            if (source) std::copy(hs.begin() + f, hs.begin() + f + n, source + at);
+            at += n;
+        }
+        return BI_OK;
+    }
     if (c->sim_n > 0 && coords)
         HIP_TRY(c, hipMemcpyAsync(coords, c->sim_coords.p, (size_t)c->sim_n * c->sim_k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (c->sim_n > 0 && source)
@@ -1638,9 +1683,268 @@ int bi_download_events(bi_ctx* c, double* coords, int32_t* source) {
 
 int64_t bi_simulated_event_count(const bi_ctx* c) { return c ? c->sim_n : -1; }
 
+}  // extern "C"
+
+namespace {
+
+// the target of a scoring call over `cols` columns becomes a context of T event sets: set t at [first[t], first[t] + n[t])
+void adopt_event_sets(bi_ctx* c, const std::vector<int64_t>& first, const std::vector<int64_t>& n) {
+    const int64_t T = (int64_t)n.size();
+    c->n_sets = T;
+    c->set_first.assign(first.begin(), first.begin() + T);
+    c->set_n = n;
+    c->T = T;
+    c->h_lgsum.assign((size_t)T, 0.0);
+    c->B = n[0];              // (see bi_context.h: whatever knows nothing of sets evaluates set 0)
+    ++c->epoch;
+}
+
+// set_first [T + 1] of sets with n[t] events each (even starts), and the padding columns
+void layout_event_sets(const std::vector<int64_t>& n, std::vector<int64_t>& first, std::vector<int64_t>& pads) {
+    first.assign(n.size() + 1, 0);
+    pads.clear();
+    for (size_t t = 0; t < n.size(); ++t) {
+        first[t + 1] = (first[t] + n[t] + 1) & ~(int64_t)1;
+        if (n[t] & 1) pads.push_back(first[t] + n[t]);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_score_event_sets(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t T,
+                        const int64_t* offsets, const double* coords, double outlier_likelihood) {
+    if (!c) return BI_ERR_INVALID;
+    if (T < 1 || !offsets) return fail(c, BI_ERR_INVALID, "need T >= 1 event sets and their offsets");
+    if (offsets[0] != 0) return fail(c, BI_ERR_INVALID, "offsets[0] must be 0");
+    for (int64_t t = 0; t < T; ++t)
+        if (offsets[t + 1] < offsets[t]) return fail(c, BI_ERR_INVALID, "offsets are not ascending at set %lld", (long long)t);
+    const int64_t N = offsets[T];
+    if (T == 1) return score_events_impl(tp, c, method, k, n_grid, grid, N, coords, nullptr, outlier_likelihood);
+    if (k < 1 || k > kMaxDim || !n_grid || !grid) return fail(c, BI_ERR_INVALID, "need 1..%d axes with grid values", kMaxDim);
+    if (N > 0 && !coords) return fail(c, BI_ERR_INVALID, "bad N / coords");
+    std::vector<int64_t> n((size_t)T), first, pads;
+    for (int64_t t = 0; t < T; ++t) n[(size_t)t] = offsets[t + 1] - offsets[t];
+    layout_event_sets(n, first, pads);
+    const int64_t cols = first[(size_t)T];
+    // the caller's events at their columns; a padding column scores at the first grid value of every axis (and is then set to 1)
+    std::vector<double> padded((size_t)cols * k);
+    int go = 0;
+    for (int ax = 0; ax < k; ++ax) {
+        if (n_grid[ax] < 1) return fail(c, BI_ERR_INVALID, "axis %d needs at least two grid values", ax);
+        double* row = padded.data() + (size_t)ax * cols;
+        std::fill(row, row + cols, grid[go]);
+        for (int64_t t = 0; t < T; ++t)
+            std::copy(coords + (size_t)ax * N + offsets[t], coords + (size_t)ax * N + offsets[t + 1], row + first[(size_t)t]);
+        go += n_grid[ax];
+    }
+    const int rc = score_events_impl(tp, c, method, k, n_grid, grid, cols, padded.data(), nullptr, outlier_likelihood, &pads);
+    if (rc) return rc;
+    adopt_event_sets(c, first, n);
+    return BI_OK;
+}
+
+int bi_simulate_event_toys(bi_ctx* tp, bi_ctx* c, const double* z, const double* rate_scale, int method, int k, const int32_t* n_edges,
+                           const double* edges, int64_t T, uint64_t seed, double outlier_likelihood, int64_t* n_per_toy_source) {
+    if (!c) return BI_ERR_INVALID;
+    if (T < 1 || T > ((int64_t)1 << 40)) return fail(c, BI_ERR_INVALID, "need T >= 1 toys");
+    if (!tp || tp == c) return fail(c, BI_ERR_INVALID, "need a templates context different from the target");
+    if (c->pending || tp->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding: call bi_eval_end first");
+    if (!tp->model_ready) return fail(c, BI_ERR_STATE, "the templates context holds no model");
+    if (tp->device != c->device) return fail(c, BI_ERR_INVALID, "templates and target live on different devices");
+    if (method != 0 && method != 1) return fail(c, BI_ERR_INVALID, "method must be 0 (piecewise) or 1 (linear)");
+    if (k < 1 || k > kMaxDim || !n_edges || !edges) return fail(c, BI_ERR_INVALID, "need 1..%d axes with bin edges", kMaxDim);
+    if (tp->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+    const int64_t toy0 = c->toy_offset;
+    if (toy0 + T > ((int64_t)1 << 48)) return fail(c, BI_ERR_INVALID, "toy numbers are told apart up to 2^48");
+    if (T == 1) {             // (one set: today's layout, through today's call)
+        const int rc1 = bi_simulate_events(tp, c, z, rate_scale, method, k, n_edges, edges, toy_seed(seed, (uint64_t)toy0), outlier_likelihood, n_per_toy_source);
+        return rc1;
+    }
+    SimArgs a{};
+    a.k = k; a.S = tp->S;
+    int64_t bins = 1;
+    int off = 0;
+    for (int i = 0; i < k; ++i) {
+        if (n_edges[i] < (method == 1 ? 3 : 2)) return fail(c, BI_ERR_INVALID, "axis %d has too few bin edges", i);
+        for (int j = 1; j < n_edges[i]; ++j)
+            if (!(edges[off + j] > edges[off + j - 1])) return fail(c, BI_ERR_INVALID, "bin edges of axis %d are not strictly ascending", i);
+        a.n_edges[i] = n_edges[i];
+        a.edge_off[i] = off;
+        off += n_edges[i];
+        bins *= n_edges[i] - 1;
+    }
+    if (bins != tp->B) return fail(c, BI_ERR_INVALID, "the edges describe %lld bins, the templates have %lld", (long long)bins, (long long)tp->B);
+    int64_t step = 1;
+    for (int i = k - 1; i >= 0; --i) { a.stride[i] = step; step *= n_edges[i] - 1; }
+    HIP_TRY(c, hipSetDevice(c->device));
+    PointGeom g;
+    if (!point_geometry(tp, z, g)) return fail(c, BI_ERR_INVALID, "simulation point is outside the anchor box");
+    const int S = tp->S;
+    std::vector<double> r((size_t)S);
+    interp_mus(tp, g, r.data());
+    if (rate_scale) for (int s = 0; s < S; ++s) r[(size_t)s] *= rate_scale[s];
+    for (int s = 0; s < S; ++s)
+        if (!(r[(size_t)s] >= 0.0 && r[(size_t)s] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "event simulation needs rates in [0, inf)");
+    for (int s = 0; s < S; ++s)
+        if (r[(size_t)s] >= kSimMaxRate)
+            return fail(c, BI_ERR_INVALID, "event simulation draws at most 2^30 expected events per source: source %d has %g", s, r[(size_t)s]);
+    const int nc = (int)g.w.size();
+    const int64_t B = tp->B;
+    std::vector<int64_t> rowoff((size_t)S * nc);
+    for (int s = 0; s < S; ++s)
+        for (int corner = 0; corner < nc; ++corner)
+            rowoff[(size_t)s * nc + corner] = ((g.cell_anchor + corner_offset(tp, corner)) * S + s) * tp->Bp;
+    DevBuf d_row, d_w, d_dens, d_cdf, d_edges, d_rates, d_n, d_room, d_setfirst, d_first, d_tmp;
+    auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_dens); dev_free(d_cdf); dev_free(d_edges); dev_free(d_rates);
+                           dev_free(d_n); dev_free(d_room); dev_free(d_setfirst); dev_free(d_first); dev_free(d_tmp); };
+    int rc;
+    size_t scan_bytes = 0, scan2 = 0;
+    (void)prim_inclusive_scan_sum(nullptr, scan_bytes, (const double*)nullptr, (double*)nullptr, (size_t)B, c->stream);
+    (void)prim_exclusive_scan_sum(nullptr, scan2, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(T + 1), c->stream);
+    std::vector<double> h_edges(edges, edges + off);
+    if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) || (rc = dev_upload(c, d_edges, h_edges)) ||
+        (rc = dev_upload(c, d_rates, r)) || (rc = dev_alloc(c, d_dens, (size_t)S * B * sizeof(double))) ||
+        (rc = dev_alloc(c, d_cdf, (size_t)S * B * sizeof(double))) || (rc = dev_alloc(c, d_n, (size_t)T * S * sizeof(int64_t))) ||
+        (rc = dev_alloc(c, d_room, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, d_setfirst, (size_t)(T + 1) * sizeof(int64_t))) ||
+        (rc = dev_alloc(c, d_first, (size_t)T * (S + 1) * sizeof(int64_t))) ||
+        (rc = dev_alloc(c, d_tmp, std::max<size_t>(std::max(scan_bytes, scan2), 256)))) { cleanup(); return rc; }
+    hipError_t e = hipStreamSynchronize(tp->stream);                      // whatever filled the templates is complete
+    if (e == hipSuccess) {                                                // the pmf rows and their running sums: once for the ensemble
+        hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
+                           (const double*)tp->ps.p, (const int64_t*)d_row.p, (const double*)d_w.p, nc, B, (double*)d_dens.p);
+        hipLaunchKernelGGL(k_sim_pmf, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
+                           (const double*)d_dens.p, a, (const double*)d_edges.p, B, (double*)d_dens.p);
+        e = hipGetLastError();
+    }
+    for (int s = 0; e == hipSuccess && s < S; ++s) {
+        size_t tb = d_tmp.bytes;
+        e = prim_inclusive_scan_sum(d_tmp.p, tb, (const double*)d_dens.p + (size_t)s * B, (double*)d_cdf.p + (size_t)s * B, (size_t)B, c->stream);
+    }
+    // counts of all (t, s), the columns every toy takes, their prefix sum, the start of every (t, s): four small launches
+    std::vector<int64_t> n_ts((size_t)T * S, 0), set_first((size_t)T + 1, 0);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_sim_toy_counts, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, c->stream, (const double*)d_rates.p, S, T, seed,
+                           toy0, (int64_t*)d_n.p);
+        hipLaunchKernelGGL(k_sim_toy_room, dim3((unsigned)((T + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int64_t*)d_n.p, S, T, (int64_t*)d_room.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        size_t tb = d_tmp.bytes;
+        e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_room.p, (int64_t*)d_setfirst.p, (int64_t)0, (size_t)(T + 1), c->stream);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_sim_toy_first, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, (const int64_t*)d_n.p,
+                           (const int64_t*)d_setfirst.p, S, T, (int64_t*)d_first.p);
+        e = hipGetLastError();
+    }
+    // the one read-back: the counts (they size the tensor and are what the caller asked for) and the set boundaries
+    if (e == hipSuccess) e = hipMemcpyAsync(n_ts.data(), d_n.p, n_ts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(set_first.data(), d_setfirst.p, set_first.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: %s", hipGetErrorString(e)); }
+    if (n_per_toy_source) std::copy(n_ts.begin(), n_ts.end(), n_per_toy_source);
+    std::vector<int64_t> n_t((size_t)T, 0), first_chk, pads;
+    int64_t n_events = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        for (int s = 0; s < S; ++s) n_t[(size_t)t] += n_ts[(size_t)(t * S + s)];
+        n_events += n_t[(size_t)t];
+    }
+    layout_event_sets(n_t, first_chk, pads);
+    if (first_chk != set_first) { cleanup(); return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: the device's set boundaries are not the counts' prefix sums"); }
+    const int64_t cols = set_first[(size_t)T];
+    if ((rc = dev_alloc(c, c->sim_coords, (size_t)std::max<int64_t>(cols, 1) * k * sizeof(double))) ||
+        (rc = dev_alloc(c, c->sim_source, (size_t)std::max<int64_t>(cols, 1) * sizeof(int32_t)))) { cleanup(); return rc; }
+    c->sim_k = k;
+    c->sim_n = n_events;
+    c->sim_cols = cols;
+    if (cols > 0) {
+        hipLaunchKernelGGL(k_sim_toy_events, dim3((unsigned)((cols + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, (const double*)d_cdf.p, B,
+                           a, (const double*)d_edges.p, (const int64_t*)d_setfirst.p, (const int64_t*)d_first.p, T, seed, toy0, cols,
+                           (double*)c->sim_coords.p, (int32_t*)c->sim_source.p);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    cleanup();
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: %s", hipGetErrorString(e));
+    std::vector<int32_t> n_grid((size_t)k);
+    std::vector<double> grid;
+    int eo = 0;
+    for (int i = 0; i < k; ++i) {
+        if (method == 0) {
+            n_grid[(size_t)i] = n_edges[i];
+            grid.insert(grid.end(), edges + eo, edges + eo + n_edges[i]);
+        } else {
+            n_grid[(size_t)i] = n_edges[i] - 1;
+            for (int j = 0; j + 1 < n_edges[i]; ++j) grid.push_back(0.5 * (edges[eo + j] + edges[eo + j + 1]));
+        }
+        eo += n_edges[i];
+    }
+    rc = score_events_impl(tp, c, method, k, n_grid.data(), grid.data(), cols, nullptr, (const double*)c->sim_coords.p, outlier_likelihood, &pads);
+    if (rc) return rc;
+    adopt_event_sets(c, set_first, n_t);
+    c->sim_epoch = c->epoch;
+    return BI_OK;
+}
+
+int bi_event_set_offsets(bi_ctx* c, int64_t* offsets) {
+    if (!c || !offsets) return BI_ERR_INVALID;
+    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
+    for (int64_t t = 0; t < c->n_sets; ++t) offsets[t] = c->set_first[(size_t)t];
+    const int64_t end = c->set_first[(size_t)c->n_sets - 1] + c->set_n[(size_t)c->n_sets - 1];
+    offsets[c->n_sets] = c->n_sets > 1 ? ((end + 1) & ~(int64_t)1) : end;
+    return BI_OK;
+}
+
+int bi_event_set_counts(bi_ctx* c, int64_t* counts) {
+    if (!c || !counts) return BI_ERR_INVALID;
+    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
+    std::copy(c->set_n.begin(), c->set_n.end(), counts);
+    return BI_OK;
+}
+
+int64_t bi_event_set_count(const bi_ctx* c) { return (c && c->unbinned && c->data_ready) ? c->n_sets : 0; }
+
+int bi_set_event_sets(bi_ctx* c, int64_t T, const int64_t* counts) {
+    if (!c) return BI_ERR_INVALID;
+    if (!c->unbinned || !c->data_ready || c->n_sets != 1) return fail(c, BI_ERR_STATE, "bi_set_event_sets follows bi_set_unbinned");
+    if (T < 1 || !counts) return fail(c, BI_ERR_INVALID, "need T >= 1 event sets and their counts");
+    if (c->ev_sorted) return fail(c, BI_ERR_STATE, "the columns are ordered by histogram cell (score_sorted)");
+    std::vector<int64_t> n(counts, counts + T), first, pads;
+    for (int64_t t = 0; t < T; ++t)
+        if (n[(size_t)t] < 0) return fail(c, BI_ERR_INVALID, "event set %lld has a negative count", (long long)t);
+    if (T == 1) return n[0] == c->B ? BI_OK : fail(c, BI_ERR_INVALID, "one set of %lld events, the model has %lld columns", (long long)n[0], (long long)c->B);
+    layout_event_sets(n, first, pads);
+    if (first[(size_t)T] != c->B)
+        return fail(c, BI_ERR_INVALID, "the sets take %lld columns (even starts), the model has %lld", (long long)first[(size_t)T], (long long)c->B);
+    adopt_event_sets(c, first, n);
+    return BI_OK;
+}
+
+int bi_download_event_set(bi_ctx* c, int64_t t, double* out) {
+    if (!c) return BI_ERR_INVALID;
+    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
+    if (t < 0 || t >= c->n_sets) return fail(c, BI_ERR_INVALID, "event set %lld outside [0, %lld)", (long long)t, (long long)c->n_sets);
+    if (c->ev_sorted) return fail(c, BI_ERR_STATE, "the columns are ordered by histogram cell (score_sorted): bi_interpolate hands them back in event order");
+    const int64_t n = c->set_n[(size_t)t];
+    if (n == 0) return BI_OK;
+    if (!out) return fail(c, BI_ERR_INVALID, "out is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)n * sizeof(double), (const double*)c->ps.p + c->set_first[(size_t)t], (size_t)c->Bp * sizeof(double),
+                                (size_t)n * sizeof(double), (size_t)(c->A * c->S), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BI_OK;
+}
+
 // ---- compatibility mode --------------------------------------------------------------------
 
-int bi_interpolate(bi_ctx* c, int which, const double* z, double* out) {
+}  // extern "C"
+
+// bi_interpolate; set: the event set whose columns `which` = 0 hands back (an unbinned context with several sets: N_set columns
+// from first_set; otherwise 0)
+static int interpolate_set(bi_ctx* c, int which, const double* z, double* out, int64_t set) {
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!out) return fail(c, BI_ERR_INVALID, "out is NULL");
@@ -1654,28 +1958,35 @@ int bi_interpolate(bi_ctx* c, int which, const double* z, double* out) {
     HIP_TRY(c, hipSetDevice(c->device));
     const int nc = (int)g.w.size();
     const int R = which == 0 ? c->S : 1;
+    const bool of_set = which == 0 && multi_set(c);
+    const int64_t col0 = of_set ? c->set_first[(size_t)set] : 0, nB = of_set ? c->set_n[(size_t)set] : c->B;
+    if (of_set && nB == 0) return BI_OK;              // an empty set: nothing to hand back
     std::vector<int64_t> rowoff((size_t)R * nc);
     for (int r = 0; r < R; ++r)
         for (int corner = 0; corner < nc; ++corner) {
             const int64_t a = g.cell_anchor + corner_offset(c, corner);
-            rowoff[(size_t)r * nc + corner] = which == 0 ? (a * c->S + r) * c->Bp : a * c->Bp;
+            rowoff[(size_t)r * nc + corner] = which == 0 ? (a * c->S + r) * c->Bp + col0 : a * c->Bp;
         }
     DevBuf d_row, d_w, d_out;
     auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_out); };
     if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) ||
-        (rc = dev_alloc(c, d_out, (size_t)R * c->B * sizeof(double)))) { cleanup(); return rc; }
-    hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((c->B + kThreads - 1) / kThreads), (unsigned)R), dim3(kThreads), 0,
+        (rc = dev_alloc(c, d_out, (size_t)R * nB * sizeof(double)))) { cleanup(); return rc; }
+    hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((nB + kThreads - 1) / kThreads), (unsigned)R), dim3(kThreads), 0,
                        c->stream, which == 0 ? (const double*)c->ps.p : (const double*)c->nm.p,
-                       (const int64_t*)d_row.p, (const double*)d_w.p, nc, c->B, (double*)d_out.p,
+                       (const int64_t*)d_row.p, (const double*)d_w.p, nc, nB, (double*)d_out.p,
                        // (an unbinned tensor scored on the device holds its events ordered by cell: back to the caller's order)
                        which == 0 && c->ev_sorted ? (const int32_t*)c->ev_perm.p : (const int32_t*)nullptr);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t)R * c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t)R * nB * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_interpolate: %s", hipGetErrorString(e));
     return BI_OK;
 }
+
+extern "C" {
+
+int bi_interpolate(bi_ctx* c, int which, const double* z, double* out) { return interpolate_set(c, which, z, out, 0); }
 
 int bi_eval_full(bi_ctx* c, const double* z, const double* rate_scale, int64_t dataset, double* ll, double* mus_out,
                  double* ps_out, int32_t* status) {
@@ -1692,7 +2003,7 @@ int bi_eval_full(bi_ctx* c, const double* z, const double* rate_scale, int64_t d
     point_geometry(c, z, g);
     interp_mus(c, g, mus_out);
     if (rate_scale) for (int s = 0; s < c->S; ++s) mus_out[s] *= rate_scale[s];
-    if ((rc = bi_interpolate(c, 0, z, ps_out))) return rc;
+    if ((rc = interpolate_set(c, 0, z, ps_out, dataset))) return rc;      // (several event sets: the N_dataset columns of that set)
     if (c->bb_source < 0) return BI_OK;
     // Beeston-Barlow adjusted (mus, pmfs) for full_output (likelihood.py:656-658), on the device.
     HIP_TRY(c, hipSetDevice(c->device));

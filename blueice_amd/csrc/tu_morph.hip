@@ -1,8 +1,9 @@
 // tu_morph.hip -- translation unit of the morph + reduce kernels: k_morph_reduce<G, BB, NT, MODE> (bi_k_morph.h: batched
-// values, gradients, the unbinned likelihood) and k_morph_single (the synchronous single-point call), with their
-// instantiation tables.  See bi_common.h for how the library is split.
+// values, gradients, the unbinned likelihood), k_morph_single (the synchronous single-point call) and k_morph_sets
+// (bi_k_sets.h: unbinned work items with an event set each), with their instantiation tables.  See bi_common.h for how the library is split.
 #include "bi_common.h"
 #include "bi_k_morph.h"
+#include "bi_k_sets.h"
 
 namespace {
 
@@ -77,4 +78,16 @@ void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, cons
     else if (bb) BI_SINGLE(true, 0, false);
     else BI_SINGLE(false, 0, false);
 #undef BI_SINGLE
+}
+
+// k_morph_sets<G, MODE>: G = 1 the value (MODE 2), else value + gradient columns (MODE 3)
+void launch_morph_sets(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid) {
+    EventScope ev(c);
+    switch (G) {
+        case 1: hipLaunchKernelGGL((k_morph_sets<1, 2>), grid, dim3(kThreads), 0, c->stream, a); break;
+        case 2: hipLaunchKernelGGL((k_morph_sets<2, 3>), grid, dim3(kThreads), 0, c->stream, a); break;
+        case 4: hipLaunchKernelGGL((k_morph_sets<4, 3>), grid, dim3(kThreads), 0, c->stream, a); break;
+        case 8: hipLaunchKernelGGL((k_morph_sets<8, 3>), grid, dim3(kThreads), 0, c->stream, a); break;
+        default: hipLaunchKernelGGL((k_morph_sets<16, 3>), grid, dim3(kThreads), 0, c->stream, a); break;
+    }
 }

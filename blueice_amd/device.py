@@ -230,6 +230,73 @@ class DeviceContext:
         target._sim_dims = len(edges)
         return per_source
 
+    def score_event_sets(self, target, method, grid, coord_sets, outlier_likelihood=1e-12):
+        """`score_events` for a stack of T datasets: coord_sets = T lists of coordinate arrays (one per analysis dimension).
+        `target` then holds the T event sets side by side (bi_score_event_sets); its dataset t is set t."""
+        code = {'piecewise': 0, 'linear': 1}[method]
+        grid = [np.ascontiguousarray(g, dtype=np.float64) for g in grid]
+        sets = [np.stack([np.asarray(c, dtype=np.float64).ravel() for c in cs]).reshape(len(grid), -1) for cs in coord_sets]
+        offsets = np.concatenate([[0], np.cumsum([x.shape[1] for x in sets])]).astype(np.int64)
+        cols = np.ascontiguousarray(np.concatenate(sets, axis=1))
+        n_grid = np.array([len(g) for g in grid], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(grid))
+        target._check(self._lib.bi_score_event_sets(self._h, target._h, code, len(grid), ptr(n_grid), ptr(flat), len(sets), ptr(offsets),
+                                                    ptr(cols), float(outlier_likelihood)))
+        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(sets[0].shape[1]), -1, len(sets)
+        target.anchor_z = self.anchor_z
+
+    def simulate_event_toys(self, target, method, edges, z, rate_scale=None, n_toys=1, seed=0, outlier_likelihood=1e-12):
+        """`simulate_events` for an ensemble: n_toys toys at (z, rate_scale), toy t of the call being toy toy_offset + t (the
+        TARGET's parameter) of the seed's ensemble = `simulate_events` with the seed `toy_seed(seed, toy_offset + t)`.
+        -> events per toy and source [T, S]."""
+        code = {'piecewise': 0, 'linear': 1}[method]
+        edges = [np.ascontiguousarray(e, dtype=np.float64) for e in edges]
+        n_edges = np.array([len(e) for e in edges], dtype=np.int32)
+        flat = np.ascontiguousarray(np.concatenate(edges))
+        z = as_f64(z).reshape(self.d) if self.d else None
+        if rate_scale is not None:
+            rate_scale = as_f64(rate_scale, (self.S,))
+        counts = np.zeros((int(n_toys), self.S), dtype=np.int64)
+        target._check(self._lib.bi_simulate_event_toys(self._h, target._h, ptr(z), ptr(rate_scale), code, len(edges), ptr(n_edges),
+                                                       ptr(flat), int(n_toys), int(seed) & (2**64 - 1), float(outlier_likelihood),
+                                                       ptr(counts)))
+        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(counts[0].sum()), -1, int(n_toys)
+        target.anchor_z = self.anchor_z
+        target._sim_dims = len(edges)
+        return counts
+
+    def adopt_event_sets(self, counts):
+        """After `set_unbinned` on a model whose columns hold T event sets side by side (even starts): declare them."""
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        self._check(self._lib.bi_set_event_sets(self._h, len(counts), ptr(counts)))
+        self.T, self.B = len(counts), int(counts[0])
+
+    def event_set_offsets(self):
+        """-> first column of every event set of this (unbinned) context and, last, the columns in use: [T + 1]."""
+        T = int(self._lib.bi_event_set_count(self._h))
+        if T < 1:
+            raise NotPreparedException("the context holds no unbinned data")
+        out = np.zeros(T + 1, dtype=np.int64)
+        self._check(self._lib.bi_event_set_offsets(self._h, ptr(out)))
+        return out
+
+    def event_set_counts(self):
+        """-> events of every event set of this (unbinned) context: [T]."""
+        T = int(self._lib.bi_event_set_count(self._h))
+        if T < 1:
+            raise NotPreparedException("the context holds no unbinned data")
+        out = np.zeros(T, dtype=np.int64)
+        self._check(self._lib.bi_event_set_counts(self._h, ptr(out)))
+        return out
+
+    def download_event_set(self, t=0):
+        """-> the resident pdf values of event set t, [anchors, S, N_t]."""
+        n = int(self.event_set_counts()[t])
+        A = int(np.prod([len(a) for a in self.anchor_z], dtype=np.int64)) if self.d else 1
+        out = np.empty((A, self.S, n), dtype=np.float64)
+        self._check(self._lib.bi_download_event_set(self._h, int(t), ptr(out)))
+        return out
+
     def download_events(self):
         """The events of the last simulate_events into this context -> (coords [k, N], source index [N])."""
         n = int(self._lib.bi_simulated_event_count(self._h))
@@ -469,7 +536,10 @@ class DeviceContext:
             rate_scale = as_f64(rate_scale, (self.S,))
         ll = np.zeros(1)
         mus = np.zeros(self.S)
-        ps = np.zeros((self.S, self.B))
+        n = self.B
+        if int(dataset) and 0 <= int(dataset) < self.T and int(self._lib.bi_event_set_count(self._h)) > 1:
+            n = int(self.event_set_counts()[int(dataset)])          # several event sets: the events of that set
+        ps = np.zeros((self.S, n))
         st = np.zeros(1, dtype=np.int32)
         self._check(self._lib.bi_eval_full(self._h, ptr(z), ptr(rate_scale), int(dataset), ptr(ll), ptr(mus), ptr(ps),
                                            ptr(st)))

@@ -209,7 +209,8 @@ def bestfit_toys(lf, t0=0, t1=None, **kwargs):
 
 
 def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, first_toy=0, **fit_kwargs):
-    """A toy-MC ensemble with a fit per toy, start to finish on the device: `n_toys` binned toys drawn at the parameter
+    """A toy-MC ensemble with a fit per toy, start to finish on the device: `n_toys` toys (binned, or event-level for an
+    unbinned likelihood) drawn at the parameter
     values `truth` (dict; defaults elsewhere) and fitted, `chunk` toys at a time (`simulate_toys` + `bestfit_toys`) -- the
     reference's `for _ in range(n_toys): d = lf.base_model.simulate(); lf.set_data(d); bestfit_scipy(lf)`
     (blueice/model.py:69-91, inference.py:131-178).  The toys are numbered globally (the generator's counters are
@@ -220,8 +221,10 @@ def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, f
     -> (OrderedDict name -> fitted values [n_toys], max log likelihood [n_toys]).  Afterwards the likelihood's data are
     the toys of the last chunk."""
     ctx = getattr(lf, 'ctx', None)
+    if ctx is None and hasattr(lf, '_device_context'):
+        ctx = lf._device_context()             # (an unbinned likelihood makes its context with its first data)
     if ctx is None or not hasattr(lf, 'simulate_toys'):
-        raise NotImplementedError("toy_mc_fits needs a binned likelihood on one device context")
+        raise NotImplementedError("toy_mc_fits needs a binned or an unbinned likelihood with simulate_toys on one device context")
     best, lls = None, []
     try:
         for t0 in range(0, int(n_toys), int(chunk)):

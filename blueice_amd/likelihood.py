@@ -1095,16 +1095,129 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
         self.is_data_set = True
         return per_source
 
-    def simulated_events(self):
+    @_needs_preparation
+    def simulate_toys(self, n_toys, seed=0, livetime_days=None, **truth):
+        """Draw an ensemble of `n_toys` event-level toys ON THE DEVICE at the given parameter values and make them the
+        likelihood's datasets (dataset 0 is what plain `lf(**params)` sees; `eval_toys`, `bestfit_toys` and `hesse(...,
+        datasets=)` take them all): the unbinned counterpart of `BinnedLogLikelihood.simulate_toys`, `simulate_toy` for T
+        toys in one call (`bi_simulate_event_toys`).  Toy t of the call is toy `toy_offset + t` (the context parameter) of
+        the seed's ensemble -- event for event what `simulate_toy(seed=toy_seed(seed, toy_offset + t))` draws.  Needs
+        sources whose pdf is a histogram; raises as `simulate_toy` does.  -> events per toy and source [T, S]."""
+        if int(n_toys) < 1:
+            raise ValueError("n_toys must be at least 1")
+        tpl = self._histogram_templates()
+        if not tpl:
+            raise NotImplementedError("device-side event simulation needs sources whose pdf is a histogram over the analysis space")
+        prior, zs, scale = self._host_terms(livetime_days, truth)
+        if prior is None:
+            raise ValueError("cannot simulate outside the anchor box")
+        tp, method, _ = tpl
+        edges = [np.asarray(e, dtype=float) for _, e in self.base_model.config['analysis_space']]
+        counts = tp.simulate_event_toys(self._device_context(), method, edges, zs, scale, int(n_toys), seed, self.outlier_likelihood)
+        self._data = None
+        self.bin_shape = (int(counts[0].sum()),)
+        self.is_data_set = True
+        return counts
+
+    def _device_context(self):
+        if self.ctx is None:
+            self.ctx = DeviceContext(self.config.get('device'))
+        return self.ctx
+
+    @_needs_preparation
+    def set_datasets(self, datasets):
+        """Make a list of T event record arrays the likelihood's datasets: the unbinned counterpart of
+        `set_binned_data([T, ...])`.  Histogram-pdf sources are scored on the device in one launch
+        (`bi_score_event_sets`); otherwise every set is scored on the host, anchor by anchor as `set_data` does, and the
+        sets are streamed up side by side (every set starts at an even column; a padding column holds 1)."""
+        datasets = list(datasets)
+        if not datasets:
+            raise ValueError("need at least one dataset")
+        names = [n for n, _ in self.base_model.config['analysis_space']]
+        for t, d in enumerate(datasets):
+            fields = getattr(getattr(d, 'dtype', None), 'names', None) or ()
+            missing = [n for n in names if n not in fields]
+            if missing:
+                raise ValueError("dataset %d lacks the analysis dimensions %s" % (t, ', '.join(missing)))
+        if len(datasets) == 1:
+            return self.set_data(datasets[0])
+        self._data = None
+        self.is_data_set = True
+        self.bin_shape = (len(datasets[0]),)
+        coords = [[np.asarray(c, dtype=float) for c in self.base_model.to_analysis_dimensions(d)] for d in datasets]
+        tpl = self._histogram_templates() if all(np.all(np.isfinite(c)) for cs in coords for c in cs) else None
+        if tpl:
+            tp, method, grid = tpl
+            if method == 'linear':
+                coords = [[np.clip(c, g[0], g[-1]) for c, g in zip(cs, grid)] for cs in coords]
+            tp.score_event_sets(self._device_context(), method, grid, coords, self.outlier_likelihood)
+            return
+        n = np.array([len(d) for d in datasets], dtype=np.int64)
+        first = np.concatenate([[0], np.cumsum((n + 1) // 2 * 2)])
+
+        def rows_of(model):
+            out = np.ones((len(model.sources), int(first[-1])))
+            for t, d in enumerate(datasets):
+                out[:, first[t]:first[t] + n[t]] = model.score_events(d)
+            return out, None
+        self._stream_models(rows_of, int(first[-1]))
+        self.ctx.set_unbinned(self.outlier_likelihood)
+        self.ctx.adopt_event_sets(n)
+
+    @property
+    def n_events_per_dataset(self):
+        """events of every dataset the likelihood holds: [T]"""
+        return self.ctx.event_set_counts()
+
+    @property
+    def supports_hessian(self):
+        """As the base class; with several datasets the device has no analytic Hessian per dataset, and
+        `values_gradients_hessians` takes differences of the analytic gradient."""
+        if self.ctx is not None and self.is_data_set and self.ctx.T > 1:
+            return False
+        return DeviceLogLikelihood.supports_hessian.fget(self)
+
+    @_needs_data
+    def eval_toys(self, livetime_days=None, **params):
+        """One parameter point against every dataset the likelihood holds (`simulate_toys`, `set_datasets`): ll [T]."""
+        T = self.ctx.T
+        prior, zs, scale = self._host_terms(livetime_days, params)
+        if prior is None:
+            return np.full(T, -np.inf)
+        ll, st = self.ctx.eval(np.tile(zs, (T, 1)) if len(zs) else None, np.tile(scale, (T, 1)), np.arange(T))
+        return np.array([prior + self._interpret(a, int(b)) for a, b in zip(ll, st)])
+
+    def simulated_events(self, t=None):
         """The events of the last `simulate_toy` as a record array with the analysis dimensions and a 'source' field, as
-        `Model.simulate` returns them."""
+        `Model.simulate` returns them.  After `simulate_toys`: the events of toy t, or (t = None) of all toys, set by set in
+        drawn order, with a 'toy' field."""
         coords, source = self.ctx.download_events()
         names = [n for n, _ in self.base_model.config['analysis_space']]
-        d = np.zeros(coords.shape[1], dtype=[(n, float) for n in names] + [('source', int)])
+        many = self.ctx.T > 1
+        d = np.zeros(coords.shape[1], dtype=[(n, float) for n in names] + [('source', int)] + ([('toy', int)] if many else []))
         for n, c in zip(names, coords):
             d[n] = c
         d['source'] = source
-        return d
+        if many:
+            d['toy'] = np.repeat(np.arange(self.ctx.T), self.ctx.event_set_counts())
+        if t is None:
+            return d
+        if not many:
+            if t != 0:
+                raise ValueError("the likelihood holds one toy")
+            return d
+        keep = d[d['toy'] == int(t)]
+        return keep[[n for n in keep.dtype.names if n != 'toy']].copy()
+
+
+def toy_seed(seed, toy):
+    """The seed of toy number `toy` of the ensemble `simulate_toys(seed=seed)` draws: `simulate_toy(seed=toy_seed(seed, D))`
+    is toy D, event for event (include/blueice_hip.h, bi_simulate_event_toys).  One-to-one in `toy` for a fixed seed."""
+    m = (1 << 64) - 1
+    x = (int(seed) + (int(toy) + 1) * 0x9E3779B97F4A7C15) & m
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
+    return x ^ (x >> 31)
 
 
 class LogLikelihoodSum:

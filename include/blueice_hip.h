@@ -178,6 +178,48 @@ int bi_simulate_events(bi_ctx* templates, bi_ctx* target, const double* z, const
 int bi_download_events(bi_ctx* target, double* coords /*[k][N] or NULL*/, int32_t* source /*[N] or NULL*/);
 int64_t bi_simulated_event_count(const bi_ctx* target);
 
+/* Several event sets in one unbinned context: an ensemble of T event-level datasets (toys) side by side on the event axis
+ * of the [A..][S][columns] tensor.  Set t occupies columns [first_t, first_t + N_t); every first_t is even (first_0 = 0,
+ * first_{t+1} = first_t + N_t rounded up to even), so a set starts 16-byte aligned; the at most one padding column behind a
+ * set holds 1.0 in every row and enters no sum; N_t = 0 is allowed.  Point evaluations take the set from their `dataset`
+ * column (bi_eval, bi_eval_grad, bi_fit_batched*, the `dataset` of bi_eval_begin and bi_eval_full; no column: set 0); the expected-event
+ * term -sum_s mu_s is per point as before.  With T = 1 the two calls below ARE bi_score_events / bi_simulate_events.
+ * Not available on a context with T > 1 sets (BI_ERR_INVALID, "... several event sets ..."): bi_plan_points*, bi_eval_hess
+ * with a dataset column, bi_sample_stretch* with more than one ensemble or another set than 0, and bi_eval_datasets*.
+ * bi_eval_full(dataset = t) hands back ps_out [S][N_t], the pdf values at the events of set t; bi_interpolate(0) those of
+ * set 0.  Beeston-Barlow and binned contexts have no event sets.
+ *
+ * bi_score_event_sets: bi_score_events for a stack of T datasets; coords [k][N] holds the events of set t at
+ * [offsets[t], offsets[t + 1]), offsets[0] = 0, offsets[T] = N, ascending.  One scoring launch fills the tensor.
+ *
+ * bi_simulate_event_toys: T toys at one truth point, drawn, placed and scored without a host round trip per toy (one
+ * read-back: the counts, which size the tensor).  Toy t of the call is toy D = toy_offset + t (the context parameter, as
+ * for bi_generate_toys) of the seed's ensemble, and toy D is -- event for event, bit for bit -- what bi_simulate_events
+ * draws with the seed toy_seed(seed, D):
+ *     toy_seed(seed, D):  x = seed + (D + 1) 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) 0xBF58476D1CE4E5B9;
+ *                         x = (x ^ x >> 27) 0x94D049BB133111EB;  toy_seed = x ^ x >> 31        (all modulo 2^64)
+ * D -> seed + (D + 1) c is one-to-one modulo 2^64 (c is odd) and the three mixing steps are bijections, so two toys of one
+ * ensemble never share a stream; an ensemble depends on neither T, nor the chunking, nor the launch geometry.  The
+ * per-source limits of bi_simulate_events hold per toy; the total event count is 64-bit.
+ *   n_per_toy_source [T][S] or NULL: receives the events drawn per toy and source
+ * bi_event_set_offsets: offsets [T + 1] receives first_0 .. first_{T-1} and, last, the number of columns in use;
+ * bi_event_set_counts: counts [T] receives N_t.  bi_event_set_count: T (1 for every other unbinned context, 0 otherwise).
+ * bi_download_events after bi_simulate_event_toys hands back all events set by set, in drawn order, without the padding:
+ * coords [k][N], N = bi_simulated_event_count = sum_t N_t, set t at [sum_{t' < t} N_t', ...). */
+int bi_score_event_sets(bi_ctx* templates, bi_ctx* target, int method, int k, const int32_t* n_grid, const double* grid,
+                        int64_t T, const int64_t* offsets /*[T+1]*/, const double* coords /*[k][N]*/, double outlier_likelihood);
+int bi_simulate_event_toys(bi_ctx* templates, bi_ctx* target, const double* z, const double* rate_scale, int method, int k,
+                           const int32_t* n_edges, const double* edges, int64_t T, uint64_t seed, double outlier_likelihood,
+                           int64_t* n_per_toy_source /*[T][S] or NULL*/);
+int bi_event_set_offsets(bi_ctx* target, int64_t* offsets /*[T+1]*/);
+int bi_event_set_counts(bi_ctx* target, int64_t* counts /*[T]*/);
+int64_t bi_event_set_count(const bi_ctx* target);
+/* after bi_set_unbinned on a model whose columns the caller filled in that layout (pdf values scored on the host; padding
+ * columns finite): declare the T sets, counts [T]; the padded sets must take exactly the model's B columns */
+int bi_set_event_sets(bi_ctx* ctx, int64_t T, const int64_t* counts);
+/* the pdf values of set t as they are resident: out [A..][S][N_t] (BI_ERR_STATE while the columns are ordered by cell, score_sorted) */
+int bi_download_event_set(bi_ctx* target, int64_t t, double* out);
+
 /* Toy-MC datasets generated on the device: n_{t,b} ~ Poisson(mu_b), mu_b = sum_s r_s p_{s,b}(z) -- the binned
  * equivalent of Model.simulate (blueice/model.py:69-91: Poisson number of events per source, each drawn from
  * the source's pdf) followed by set_data's binning (blueice/likelihood.py:603-609).  Philox4x32-10 keyed by
@@ -609,7 +651,8 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     fails does the same before it gives up
  *   debug_skip_post, debug_late_post   (write; fault injection for tests) block k of the NEXT launch that finishes through the
  *                     mailbox never posts its partial sum / posts it after the collector has given up; consumed by that launch
- * read-only: n_sampler_half_steps (half-steps of bi_sample_stretch so far), last_plan_refused (the last bi_plan_points_resident /
+ * read-only: n_set_launches (evaluation launches of k_morph_sets: work items with different event sets, see bi_score_event_sets),
+ *            n_sampler_half_steps (half-steps of bi_sample_stretch so far), last_plan_refused (the last bi_plan_points_resident /
  *            bi_sample_stretch planning refused its batch: 1 Beeston-Barlow points that need exact totals, 2 infinite rates of sources that may
  *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total;
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
