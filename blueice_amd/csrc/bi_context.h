@@ -116,6 +116,9 @@ struct bi_ctx {
     int64_t narrow_counts = 1;                   // parameter: 0 = never read the narrow copy
     int64_t last_streamed_bytes = 0;             // read-only: bytes the last bi_run_plan streamed (plan bytes less 7 per bin of every item read narrow)
     int64_t n_narrow_launches = 0;               // read-only: morph launches that read the narrow copy
+    // read-only: the grid of the most recent k_morph_reduce / k_morph_single launch (gridDim.x blocks per item, gridDim.y items)
+    // and whether it finished through the mailbox (0: k_finish, k_finish_single or the two-kernel fallback ran behind it)
+    int64_t last_morph_nbx = 0, last_morph_items = 0, last_morph_fused = 0;
 
     // model statistics (for the sparse forms)
     std::vector<double> h_rowsum;  // [A*S] sum over bins of every ps row

@@ -435,6 +435,7 @@ static int eval_grad_points(bi_ctx* c, int64_t P, const double* z, const double*
                              if (mixed) launch_morph_sets(c, G, b, grid);
                              else if (values_only) launch_morph_g(c, 1, b, grid, false, nt);
                              else launch_morph_grad(c, G, b, grid, nt);
+                             if (!mixed) { c->last_morph_nbx = grid.x; c->last_morph_items = grid.y; c->last_morph_fused = 0; }
                              return BI_OK;
                          });
     if (rc) return rc;

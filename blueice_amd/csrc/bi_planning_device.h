@@ -1140,7 +1140,9 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
             plan->max_group_items = h_max;
             plan->max_item_tiles = (int)max_tiles;
         }
-        if (bb_scan) {
+        // (k_scan_bb's gridDim.z counts a group's quads of items: a group of more than 4 x 65 535 items keeps bb_kgt = 0, and its
+        //  16-point items -- whose descriptors are the same -- run through k_morph_reduce<16, true> in launches of 65 535)
+        if (bb_scan && h_max <= 4 * (int64_t)65535) {
             plan->bb_kgt = bb_kgt;
             plan->n_groups = n_groups;
             plan->max_group_items = h_max;

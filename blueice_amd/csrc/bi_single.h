@@ -304,6 +304,7 @@ int eval_single_fused(bi_ctx* c, const PointGeom& g, const double* rates, int64_
         EventScope ev(c);
         launch_morph_single(c, bb, nt, fuse, grid, a, d);
     }
+    c->last_morph_nbx = nbx; c->last_morph_items = 1; c->last_morph_fused = fuse ? 1 : 0;
     if (!fuse)
         hipLaunchKernelGGL(k_finish_single, dim3(1), block, 0, c->stream, (const double*)a.partial, (const unsigned*)a.pflags,
                            nbx, d.slot_lg, d.out, d.status, d.done, d.seq);
@@ -453,6 +454,7 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
         ++c->n_narrow_launches;
     }
     launch_morph_g(c, 1, a, dim3((unsigned)nbx, 1), bb, !sparse && c->nt_loads != 0);
+    c->last_morph_nbx = nbx; c->last_morph_items = 1; c->last_morph_fused = 0;
     launch_finish(c, a.partial, a.pflags, nbx, 1, 1, (const int64_t*)(dev + (o + 2) * 8), (const double*)(dev + (o + 3) * 8),
                   (double*)res, (int32_t*)(res + 8));
     HIP_TRY(c, hipGetLastError());

@@ -676,6 +676,7 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
                 ++c->n_narrow_launches;
             }
             launch_morph_g(c, k.G, b, dim3((unsigned)k.nbx, (unsigned)ni), bb, nt);
+            c->last_morph_nbx = k.nbx; c->last_morph_items = ni; c->last_morph_fused = fuse ? 1 : 0;
             if (fuse) continue;
             launch_finish(c, b.partial, b.pflags, k.nbx, k.G, ni * k.G, (const int64_t*)k.perm.p + i0 * k.G,
                           (const double*)k.slot_lg.p + i0 * k.G, out, (int32_t*)plan->status.p);

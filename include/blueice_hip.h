@@ -655,6 +655,8 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *            n_sampler_half_steps (half-steps of bi_sample_stretch so far), last_plan_refused (the last bi_plan_points_resident /
  *            bi_sample_stretch planning refused its batch: 1 Beeston-Barlow points that need exact totals, 2 infinite rates of sources that may
  *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total;
+ *            last_morph_nbx / last_morph_items / last_morph_fused (the most recent k_morph_reduce or k_morph_single launch: blocks per
+ *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it);
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
  *            the last plan, and the resident blocks per CU it sized them by), last_toy_method (1 = event by event);
  *   single_calls, single_ns_host, single_ns_launch, single_ns_wait   wall time (ns, summed over single_calls calls) of
