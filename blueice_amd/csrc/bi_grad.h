@@ -135,27 +135,19 @@ int run_item_chunks(bi_ctx* c, int64_t n_items, int max_tiles, int nsl, const in
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     const int nbx = (int)std::min<int64_t>(max_tiles, n_items == 1 ? slots : std::max<int64_t>(1, (4 * slots + n_items - 1) / n_items));
     const int64_t chunk = 65535, part_items = std::min(chunk, n_items);
-    DevBuf d_part, d_flag;
-    auto cleanup = [&]() { dev_free(d_part); dev_free(d_flag); };
+    ScratchBuf d_part, d_flag;
     int rc;
     if ((rc = dev_alloc(c, d_part, (size_t)part_items * nbx * nsl * sizeof(double))) ||
-        (rc = dev_alloc(c, d_flag, (size_t)part_items * nbx * nsl * sizeof(unsigned)))) {
-        cleanup();
-        return rc;
-    }
+        (rc = dev_alloc(c, d_flag, (size_t)part_items * nbx * nsl * sizeof(unsigned)))) return rc;
     hipError_t e = hipSuccess;
     for (int64_t i0 = 0; i0 < n_items && e == hipSuccess; i0 += chunk) {
         const int64_t ni = std::min(chunk, n_items - i0);
-        if ((rc = launch(i0, dim3((unsigned)nbx, (unsigned)ni), (double*)d_part.p, (unsigned*)d_flag.p))) {
-            cleanup();
-            return rc;
-        }
+        if ((rc = launch(i0, dim3((unsigned)nbx, (unsigned)ni), (double*)d_part.p, (unsigned*)d_flag.p))) return rc;
         launch_finish(c, (const double*)d_part.p, (const unsigned*)d_flag.p, nbx, nsl, ni * nsl, perm + i0 * nsl, slot_lg + i0 * nsl,
                       out, status);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
     return BI_OK;
 }

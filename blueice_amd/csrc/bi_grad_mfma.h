@@ -184,8 +184,7 @@ int eval_grad_mfma(bi_ctx* c, int64_t P, const double* z, const double* rate_sca
     if (rc) return rc;
     const double ninf = -std::numeric_limits<double>::infinity(), qnan = std::numeric_limits<double>::quiet_NaN();
     std::vector<int32_t> h_st((size_t)P, 0);
-    DevBuf d_pll, d_pg, d_ll, d_grad, d_rll, d_rg;
-    auto cleanup = [&]() { dev_free(d_pll); dev_free(d_pg); dev_free(d_ll); dev_free(d_grad); dev_free(d_rll); dev_free(d_rg); bi_plan_destroy(c, plan); };
+    ScratchBuf d_pll, d_pg, d_ll, d_grad, d_rll, d_rg;
     hipError_t e = hipSuccess;
     bool have_results = false;                       // (results go straight into the caller's arrays: one pass over 8 P (1 + d + S) bytes less)
     if (!plan->classes.empty() && plan->classes[0].n_items > 0) {
@@ -205,7 +204,7 @@ int eval_grad_mfma(bi_ctx* c, int64_t P, const double* z, const double* rate_sca
         if (c->grad_slices > 0) n_slices = (int)std::min<int64_t>(c->grad_slices, std::max<int64_t>(1, n_blocks));
         const size_t ni = (size_t)k.n_items;
         if ((rc = dev_alloc(c, d_pll, ni * n_slices * 16 * 8)) || (rc = dev_alloc(c, d_pg, ni * n_slices * NSP * 16 * 8)) ||
-            (rc = dev_alloc(c, d_ll, (size_t)P * 8)) || (rc = dev_alloc(c, d_grad, (size_t)P * (d + S) * 8))) { cleanup(); return rc; }
+            (rc = dev_alloc(c, d_ll, (size_t)P * 8)) || (rc = dev_alloc(c, d_grad, (size_t)P * (d + S) * 8))) { bi_plan_destroy(c, plan); return rc; }
         GradMfmaArgs ga{};
         ga.ps = sparse ? (const double*)c->ps_c.p : (const double*)c->ps.p;
         ga.counts = sparse ? (const double*)c->cnt_c.p : (const double*)c->counts.p;
@@ -225,7 +224,7 @@ int eval_grad_mfma(bi_ctx* c, int64_t P, const double* z, const double* rate_sca
         const double* fin_g = (const double*)d_pg.p;
         int fin_slices = n_slices;
         if (n_slices > 1) {
-            if ((rc = dev_alloc(c, d_rll, ni * 16 * 8)) || (rc = dev_alloc(c, d_rg, ni * NSP * 16 * 8))) { (void)hipStreamSynchronize(c->stream); cleanup(); return rc; }
+            if ((rc = dev_alloc(c, d_rll, ni * 16 * 8)) || (rc = dev_alloc(c, d_rg, ni * NSP * 16 * 8))) { (void)hipStreamSynchronize(c->stream); bi_plan_destroy(c, plan); return rc; }
             const int64_t n_ll = (int64_t)ni * 16, n_g = (int64_t)ni * NSP * 16;
             hipLaunchKernelGGL(k_grad_reduce_slices, dim3((unsigned)((n_ll + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
                                (const double*)d_pll.p, n_ll, (int64_t)16, n_slices, (double*)d_rll.p);
@@ -249,11 +248,11 @@ int eval_grad_mfma(bi_ctx* c, int64_t P, const double* z, const double* rate_sca
         have_results = e == hipSuccess;
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_st.data(), plan->status.p, (size_t)P * 4, hipMemcpyDeviceToHost, c->stream);
-    // (on an error part way the kernels already queued still write into the buffers cleanup() hands back to the recycle
-    //  cache: drain the stream first, whatever it reports)
+    // (on an error part way the kernels already queued still write into the scratch buffers that go back to the recycle
+    //  cache when the function returns: drain the stream first, whatever it reports)
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
-    cleanup();
+    bi_plan_destroy(c, plan);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_grad (matrix-core path): %s", hipGetErrorString(e));
     for (int64_t p = 0; p < P; ++p) {
         if (status) status[p] = h_st[(size_t)p];

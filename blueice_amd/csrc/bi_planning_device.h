@@ -51,15 +51,13 @@ bool ensure_sorted_rows(bi_ctx* c) {
     const int64_t B = c->B, Bp = c->Bp, rows = c->A * c->S;
     if (!c->scan_pow || c->T != 1 || !c->dense_counts || c->unbinned || c->bb_source >= 0 || B < 64 || B > INT32_MAX || rows > 65535) return false;
     if ((rows + 1) * Bp * (int64_t)sizeof(double) > c->compact_budget) return false;
-    DevBuf d_iota, d_perm, d_tmp;
-    auto drop = [&]() { dev_free(d_iota); dev_free(d_perm); dev_free(d_tmp); };
+    ScratchBuf d_iota, d_perm, d_tmp;
     size_t tmp_bytes = 0;
     (void)prim_sort_pairs(nullptr, tmp_bytes, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr,
                                     (size_t)B, 0u, 64u, c->stream);
     if (dev_alloc(c, c->ps_sorted, (size_t)rows * Bp * sizeof(double)) || dev_alloc(c, c->cnt_sorted, (size_t)Bp * sizeof(double)) ||
         dev_alloc(c, d_iota, (size_t)B * sizeof(int32_t)) || dev_alloc(c, d_perm, (size_t)B * sizeof(int32_t)) ||
         dev_alloc(c, d_tmp, std::max<size_t>(tmp_bytes, 256))) {
-        drop();
         dev_free(c->ps_sorted); dev_free(c->cnt_sorted);
         return false;
     }
@@ -75,7 +73,6 @@ bool ensure_sorted_rows(bi_ctx* c) {
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) { dev_free(c->ps_sorted); dev_free(c->cnt_sorted); return false; }
     c->sorted_ok = true;
     return true;
@@ -795,9 +792,7 @@ int eval_grad_device(bi_ctx* c, int64_t P, const double* z, const double* rate_s
     if (rc) return rc;
     const int S = c->S, d = c->d, W = 1 + d + S, NS = (1 << (int)c->eff_axes.size()) * S;
     PlanMeta m = plan_meta_of(c, sparse);
-    DevBuf d_z, d_rs, d_ds, d_row, d_coef, d_cnt, d_tiles, d_perm, d_lg, d_st, d_part, d_flag, d_out;
-    auto cleanup = [&]() { dev_free(d_z); dev_free(d_rs); dev_free(d_ds); dev_free(d_row); dev_free(d_coef); dev_free(d_cnt); dev_free(d_tiles);
-                           dev_free(d_perm); dev_free(d_lg); dev_free(d_st); dev_free(d_part); dev_free(d_flag); dev_free(d_out); };
+    ScratchBuf d_z, d_rs, d_ds, d_row, d_coef, d_cnt, d_tiles, d_perm, d_lg, d_st, d_part, d_flag, d_out;
     const size_t nP = (size_t)P;
     int max_tiles = n_tiles_of(c);
     if (sparse) max_tiles = (int)(*std::max_element(c->h_c_np.begin(), c->h_c_np.end()) / kTile);
@@ -807,7 +802,7 @@ int eval_grad_device(bi_ctx* c, int64_t P, const double* z, const double* rate_s
         (dataset && (rc = dev_alloc(c, d_ds, nP * 8))) || (rc = dev_alloc(c, d_row, nP * NS * 8)) || (rc = dev_alloc(c, d_coef, nP * NS * G * 8)) ||
         (rc = dev_alloc(c, d_cnt, nP * 8)) || (rc = dev_alloc(c, d_tiles, nP * 4)) || (rc = dev_alloc(c, d_perm, nP * G * 8)) ||
         (rc = dev_alloc(c, d_lg, nP * G * 8)) || (rc = dev_alloc(c, d_st, nP * 4)) || (rc = dev_alloc(c, d_part, nP * nbx * G * 8)) ||
-        (rc = dev_alloc(c, d_flag, nP * nbx * G * 4)) || (rc = dev_alloc(c, d_out, nP * W * 8))) { cleanup(); return rc; }
+        (rc = dev_alloc(c, d_flag, nP * nbx * G * 4)) || (rc = dev_alloc(c, d_out, nP * W * 8))) return rc;
     hipError_t e = hipSuccess;
     if (d) e = hipMemcpyAsync(d_z.p, z, nP * d * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && rate_scale) e = hipMemcpyAsync(d_rs.p, rate_scale, nP * S * 8, hipMemcpyHostToDevice, c->stream);
@@ -821,7 +816,7 @@ int eval_grad_device(bi_ctx* c, int64_t P, const double* z, const double* rate_s
                            (double*)d_coef.p, (int64_t*)d_cnt.p, (int32_t*)d_tiles.p, (int64_t*)d_perm.p, (double*)d_lg.p, (int32_t*)d_st.p);
         e = hipGetLastError();
     }
-    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "bi_eval_grad (device planning): %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_grad (device planning): %s", hipGetErrorString(e));
     LaunchArgs a{};
     a.ps = sparse ? (const double*)c->ps_c.p : (const double*)c->ps.p;
     a.counts = sparse ? (const double*)c->cnt_c.p : (const double*)c->counts.p;
@@ -845,7 +840,6 @@ int eval_grad_device(bi_ctx* c, int64_t P, const double* z, const double* rate_s
     if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out.p, h_out.size() * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(h_st.data(), d_st.p, nP * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_grad (device planning): %s", hipGetErrorString(e));
     const double ninf = -std::numeric_limits<double>::infinity(), qnan = std::numeric_limits<double>::quiet_NaN();
     for (int64_t p = 0; p < P; ++p) {
@@ -885,10 +879,8 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
     // (the points' datasets are known on the device only: the narrow copy of the counts is read if it is exact for ALL datasets --
     //  for the one dataset there is when the batch names none)
     plan->narrow = !sparse && !c->unbinned && (dataset ? narrow_has_all(c) : narrow_has(c, 0));
-    DevBuf d_z, d_rs, d_ds, d_keys, d_keys2, d_idx, d_idx2, d_a, d_b, d_tmp, d_scal;
-    auto cleanup = [&]() { dev_free(d_z); dev_free(d_rs); dev_free(d_ds); dev_free(d_keys);
-                           dev_free(d_keys2); dev_free(d_idx); dev_free(d_idx2); dev_free(d_a); dev_free(d_b); dev_free(d_tmp); dev_free(d_scal); };
-    auto abort_plan = [&](int code) { cleanup(); free_plan_buffers(plan); delete plan; return code; };
+    ScratchBuf d_z, d_rs, d_ds, d_keys, d_keys2, d_idx, d_idx2, d_a, d_b, d_tmp, d_scal;
+    auto abort_plan = [&](int code) { free_plan_buffers(plan); delete plan; return code; };
     const size_t nP = (size_t)P;
     // resident: z / rate_scale / dataset ARE device arrays (bi_plan_points_resident) and are read where they lie
     if ((!resident && (rc = dev_alloc(c, d_z, nP * std::max(d, 1) * sizeof(double)))) ||
@@ -952,14 +944,11 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
     // few distinct keys (A * T + 1 <= 65 536: every named configuration): the group structure from per-key tables, one round trip
     const int64_t K = (int64_t)m.bad_key;
     const bool by_tables = K <= 65536 && c->plan_tables;
-    DevBuf d_kstart, d_tab_start, d_tab_item;
+    ScratchBuf d_kstart, d_tab_start, d_tab_item;
     int64_t h_scal[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, h_inf = 0;
     if (by_tables) {
         if ((rc = dev_alloc(c, d_kstart, (size_t)(K + 1) * 8)) || (rc = dev_alloc(c, d_tab_start, (size_t)K * 8)) || (rc = dev_alloc(c, d_tab_item, (size_t)K * 8)) ||
-            (rc = dev_alloc(c, plan->grp_first, (size_t)K * 8)) || (rc = dev_alloc(c, plan->grp_items, (size_t)K * 4))) {
-            dev_free(d_kstart); dev_free(d_tab_start); dev_free(d_tab_item);
-            return abort_plan(rc);
-        }
+            (rc = dev_alloc(c, plan->grp_first, (size_t)K * 8)) || (rc = dev_alloc(c, plan->grp_items, (size_t)K * 4))) return abort_plan(rc);
         e = hipMemsetAsync(d_kstart.p, 0xFF, (size_t)(K + 1) * 8, c->stream);
         hipLaunchKernelGGL(k_plan_key_bounds, dim3(nblk), dim3(kThreads), 0, c->stream, (const uint64_t*)d_keys2.p, P, (int64_t*)d_kstart.p);
         hipLaunchKernelGGL(k_plan_key_tables, dim3(1), dim3(kThreads), 0, c->stream, (const int64_t*)d_kstart.p, K, P, share_rank, share_world, G,
@@ -968,7 +957,6 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
         hipLaunchKernelGGL(k_plan_count_valid, dim3(1), dim3(64), 0, c->stream, (const uint64_t*)d_keys2.p, P, m.bad_key, scal);
     }
     // (the tables live until the fill kernel has run: freed with the other planning scratch -- stream order keeps them valid)
-    struct TabGuard { DevBuf &a, &b, &c3; ~TabGuard() { dev_free(a); dev_free(b); dev_free(c3); } } tab_guard{d_kstart, d_tab_start, d_tab_item};
     if (e == hipSuccess) e = plan_report(c, ReportPiece{(const uint32_t*)scal, 32, 0});
     if (e != hipSuccess) return abort_plan(fail(c, BI_ERR_HIP, "device planning: %s", hipGetErrorString(e)));
     memcpy(h_scal, c->plan_host, sizeof(h_scal));
@@ -1295,13 +1283,12 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
     }
     if (shared) {                 // the sorted -> original index map outlives the planning: unsort_share reads it
         plan->sorted_idx = d_idx2;
-        d_idx2 = DevBuf{};
+        (DevBuf&)d_idx2 = DevBuf{};
     }
     if (grad_mode && !resident) {
-        plan->keep_z = d_z; d_z = DevBuf{};
-        plan->keep_rs = d_rs; d_rs = DevBuf{};
+        plan->keep_z = d_z; (DevBuf&)d_z = DevBuf{};
+        plan->keep_rs = d_rs; (DevBuf&)d_rs = DevBuf{};
     }
-    cleanup();
     *out = plan;
     return BI_OK;
 }

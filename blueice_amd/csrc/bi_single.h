@@ -93,12 +93,9 @@ int bb_exact_totals(bi_ctx* c, int64_t n, const int64_t* cell_anchor, const doub
     for (int64_t q = 0; q < n; ++q)
         for (int corner = 0; corner < nc; ++corner) rowoff[(size_t)(q * nc + corner)] = (cell_anchor[q] + corner_offset(c, corner)) * c->Bp;
     const size_t per_point = (size_t)(n_full + tail_n);
-    DevBuf d_in, d_out;
+    ScratchBuf d_in, d_out;
     int rc;
-    if ((rc = dev_alloc(c, d_in, (size_t)n * nc * 16)) || (rc = dev_alloc(c, d_out, (size_t)n * per_point * sizeof(double)))) {
-        dev_free(d_in); dev_free(d_out);
-        return rc;
-    }
+    if ((rc = dev_alloc(c, d_in, (size_t)n * nc * 16)) || (rc = dev_alloc(c, d_out, (size_t)n * per_point * sizeof(double)))) return rc;
     std::vector<double> h_out((size_t)n * per_point);
     hipError_t e = hipMemcpyAsync(d_in.p, rowoff.data(), (size_t)n * nc * 8, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync((char*)d_in.p + (size_t)n * nc * 8, w, (size_t)n * nc * 8, hipMemcpyHostToDevice, c->stream);
@@ -113,7 +110,6 @@ int bb_exact_totals(bi_ctx* c, int64_t n, const int64_t* cell_anchor, const doub
     }
     if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out.p, h_out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_in); dev_free(d_out);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "Beeston-Barlow total: %s", hipGetErrorString(e));
     for (int64_t q = 0; q < n; ++q) {
         const double* cs = h_out.data() + (size_t)q * n_full;
@@ -152,11 +148,10 @@ int inf_rate_value(bi_ctx* c, const PointGeom& g, const double* rates, int64_t d
     for (int r = 0; r < R; ++r)
         for (int corner = 0; corner < nc; ++corner)
             rowoff[(size_t)r * nc + corner] = ((g.cell_anchor + corner_offset(c, corner)) * c->S + srcs[(size_t)r]) * c->Bp;
-    DevBuf d_row, d_w, d_out;
-    auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_out); };
+    ScratchBuf d_row, d_w, d_out;
     int rc;
     if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) ||
-        (rc = dev_alloc(c, d_out, (size_t)R * std::max<int64_t>(B, 1) * sizeof(double)))) { cleanup(); return rc; }
+        (rc = dev_alloc(c, d_out, (size_t)R * std::max<int64_t>(B, 1) * sizeof(double)))) return rc;
     std::vector<double> rows((size_t)R * B), n((size_t)B);
     hipError_t e = hipSuccess;
     if (B > 0) {
@@ -167,7 +162,6 @@ int inf_rate_value(bi_ctx* c, const PointGeom& g, const double* rates, int64_t d
         if (e == hipSuccess) e = hipMemcpyAsync(n.data(), (const double*)c->counts.p + ds * c->Bp, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "infinite-rate evaluation: %s", hipGetErrorString(e));
     bool any_nan = false;
     for (int64_t b = 0; b < B && !any_nan; ++b) {

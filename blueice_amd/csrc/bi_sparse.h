@@ -42,8 +42,7 @@ int build_compact_templates(bi_ctx* c) {
     // counts into one logarithm per lane and strip (k_scan_mfma PROD = 2).  The CSR lists themselves stay in bin order.
     c->compact_sorted = false;
     const bool sort_by_count = c->scan_pow && T <= 64;
-    DevBuf d_sidx, d_sn, d_tmp;
-    auto drop = [&]() { dev_free(d_sidx); dev_free(d_sn); dev_free(d_tmp); };
+    ScratchBuf d_sidx, d_sn, d_tmp;
     for (int64_t t = 0; t < T; ++t) {
         const int64_t lo = c->h_nz_off[(size_t)t], nnz = c->h_nz_off[(size_t)t + 1] - lo, np = c->h_c_np[(size_t)t];
         double* dst = (double*)c->ps_c.p + c->h_c_off[(size_t)t];
@@ -54,10 +53,10 @@ int build_compact_templates(bi_ctx* c) {
             (void)prim_sort_pairs(nullptr, tmp_bytes, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr,
                                             (int32_t*)nullptr, (size_t)nnz, 0u, 64u, c->stream);
             if ((rc = dev_alloc(c, d_sidx, (size_t)nnz * sizeof(int32_t))) || (rc = dev_alloc(c, d_sn, (size_t)nnz * sizeof(double))) ||
-                (rc = dev_alloc(c, d_tmp, std::max<size_t>(tmp_bytes, 256)))) { drop(); return rc; }
+                (rc = dev_alloc(c, d_tmp, std::max<size_t>(tmp_bytes, 256)))) return rc;
             size_t tb = d_tmp.bytes;
             e = prim_sort_pairs(d_tmp.p, tb, cnt, (double*)d_sn.p, idx, (int32_t*)d_sidx.p, (size_t)nnz, 0u, 64u, c->stream);
-            if (e != hipSuccess) { drop(); return fail(c, BI_ERR_HIP, "template compaction (sort by count): %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(c, BI_ERR_HIP, "template compaction (sort by count): %s", hipGetErrorString(e));
             idx = (const int32_t*)d_sidx.p;
             cnt = (const double*)d_sn.p;
         }
@@ -68,12 +67,11 @@ int build_compact_templates(bi_ctx* c) {
         hipLaunchKernelGGL(k_row_total, dim3((unsigned)rows), dim3(kThreads), 0, c->stream, (const double*)dst, np, np,
                            (double*)c->scratch.p + t * rows);
         e = hipGetLastError();
-        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); drop(); return fail(c, BI_ERR_HIP, "template compaction: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); return fail(c, BI_ERR_HIP, "template compaction: %s", hipGetErrorString(e)); }
     }
     e = hipMemcpyAsync(tnz.data(), c->scratch.p, tnz.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "template compaction: %s", hipGetErrorString(e));
     for (int64_t t = 0; t < T; ++t)
         for (int64_t r = 0; r < rows; ++r) c->h_Tz[(size_t)(t * rows + r)] = c->h_rowsum[(size_t)r] - tnz[(size_t)(t * rows + r)];
@@ -93,8 +91,7 @@ int build_sparse_forms(bi_ctx* c) {
     const int64_t T = c->T, B = c->B, Bp = c->Bp;
     const int nchunks = (int)((B + kNzChunk - 1) / kNzChunk);
     int rc;
-    DevBuf d_cnt, d_off;
-    auto cleanup = [&]() { dev_free(d_cnt); dev_free(d_off); };
+    ScratchBuf d_cnt, d_off;
     if ((rc = dev_alloc(c, d_cnt, (size_t)T * nchunks * sizeof(int32_t)))) return rc;
     const int64_t tchunk = 32768;
     for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
@@ -106,7 +103,7 @@ int build_sparse_forms(bi_ctx* c) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "non-empty-bin count: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "non-empty-bin count: %s", hipGetErrorString(e));
     std::vector<int64_t> h_off(h_cnt.size());
     c->h_nz_off.assign((size_t)T + 1, 0);
     int64_t run = 0;
@@ -119,12 +116,9 @@ int build_sparse_forms(bi_ctx* c) {
     // dense data (more than a quarter of the bins hold events): dense forms only, unless the caller forces the lists.
     // Mostly empty data get the lists and the compacted templates whatever `sparse` says: with sparse = 0 they are
     // used by split scans only (k_scan_valid), every other path then visits every bin
-    if (run > T * B / 4 && c->sparse != 2) { cleanup(); return BI_OK; }
+    if (run > T * B / 4 && c->sparse != 2) return BI_OK;
     if ((rc = dev_upload(c, d_off, h_off)) || (rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
-        (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double))) || (rc = dev_upload(c, c->nz_off, c->h_nz_off))) {
-        cleanup();
-        return rc;
-    }
+        (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double))) || (rc = dev_upload(c, c->nz_off, c->h_nz_off))) return rc;
     for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
         const int64_t n = std::min(tchunk, T - t0);
         hipLaunchKernelGGL(k_nz_scatter, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream,
@@ -133,7 +127,7 @@ int build_sparse_forms(bi_ctx* c) {
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
+    dev_free(d_cnt); dev_free(d_off);       // (before the compacted templates are allocated)
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "non-empty-bin scatter: %s", hipGetErrorString(e));
     c->csr_ready = true;
 

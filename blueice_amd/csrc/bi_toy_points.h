@@ -552,8 +552,7 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
     for (int gr = 0; gr < n_groups; ++gr) max_group_items = std::max(max_group_items, item_begin[(size_t)gr + 1] - item_begin[(size_t)gr]);
     const double ninf = -std::numeric_limits<double>::infinity();
     const bool host_out = !out_dev && (size_t)P * n * sizeof(double) <= ((size_t)4 << 20);
-    DevBuf d_out, d_lm, d_part, d_mu;
-    auto cleanup = [&]() { dev_free(d_out); dev_free(d_lm); dev_free(d_part); dev_free(d_mu); };
+    ScratchBuf d_out, d_lm, d_part, d_mu;
     const int n_tiles = n_tiles_of(c);
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     const int nmu = (int)std::max<int64_t>(1, std::min<int64_t>(n_tiles, (slots + max_group_items - 1) / max_group_items));   // blocks per item of a log mu launch
@@ -577,10 +576,7 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
         (n_pass > 0 && (rc = dev_alloc(c, d_lm, (size_t)n_buf * lm_group * sizeof(double)))) ||
         (n_pass > 0 && (rc = dev_alloc(c, d_part, (size_t)n_buf * part_group * sizeof(double)))) ||
         (rc = dev_alloc(c, d_mu, 2 * ((mu_bytes + 63) / 64 * 64) + (size_t)std::max(n_groups, 1) * GC * 16)) ||
-        (!host_out && !out_dev && (rc = dev_alloc(c, d_out, (size_t)P * n * sizeof(double))))) {
-        cleanup();
-        return rc;
-    }
+        (!host_out && !out_dev && (rc = dev_alloc(c, d_out, (size_t)P * n * sizeof(double))))) return rc;
     double* res = out_dev ? out_dev : (host_out ? (double*)pu.host_out() : (double*)d_out.p);
     hipError_t e = hipSuccess;
     unsigned long long* done_word = nullptr;
@@ -606,7 +602,7 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
         // the completion word in the pinned block (behind the results, if they go there): polled instead of a stream synchronisation,
         // whether the results land in pinned host memory or stay in HBM (out_dev)
         if ((host_out || out_dev) && c->poll_result && !c->profiling && (c->toy_fast_call & 4)) {
-            if ((rc = dev_alloc(c, c->toy_blocks_done, 64))) { cleanup(); return rc; }
+            if ((rc = dev_alloc(c, c->toy_blocks_done, 64))) return rc;
             if (!c->toy_blocks_done_zeroed) {
                 e = hipMemsetAsync(c->toy_blocks_done.p, 0, 64, c->stream);
                 c->toy_blocks_done_zeroed = true;
@@ -745,7 +741,6 @@ int eval_datasets_points_impl(bi_ctx* c, int64_t P, const double* z, const doubl
     else if (e != hipSuccess) { (void)hipStreamSynchronize(c->stream); if (c->stream2) (void)hipStreamSynchronize(c->stream2); }
     if (done_word && !arrived) c->toy_blocks_done_zeroed = false;
     if (e == hipSuccess && host_out) memcpy(out, res, (size_t)P * n * sizeof(double));
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets_points: %s", hipGetErrorString(e));
     return BI_OK;
 }

@@ -31,6 +31,7 @@
 #include "bi_grad_mfma.h"
 #include "bi_grad.h"
 #include "bi_params.h"
+#include "bi_events.h"
 
 namespace {
 
@@ -362,25 +363,13 @@ int bi_upload_counts(bi_ctx* c, int64_t T, const double* counts) {
 int bi_set_analysis_space(bi_ctx* c, int k, const int32_t* n_edges, const double* edges) {
     int rc = check_ready(c, false);
     if (rc) return rc;
-    if (k < 1 || k > kMaxDim || !n_edges || !edges) return fail(c, BI_ERR_INVALID, "need 1..%d axes with edges", kMaxDim);
-    int64_t bins = 1;
-    std::vector<double> flat;
-    std::vector<int32_t> ne(n_edges, n_edges + k);
-    for (int i = 0; i < k; ++i) {
-        if (ne[(size_t)i] < 2) return fail(c, BI_ERR_INVALID, "axis %d needs at least two edges", i);
-        bins *= ne[(size_t)i] - 1;
-    }
-    const double* e = edges;
-    for (int i = 0; i < k; ++i) {
-        for (int j = 1; j < ne[(size_t)i]; ++j)
-            if (!(e[j] > e[j - 1])) return fail(c, BI_ERR_INVALID, "bin edges of axis %d are not strictly ascending", i);
-        flat.insert(flat.end(), e, e + ne[(size_t)i]);
-        e += ne[(size_t)i];
-    }
-    if (bins != c->B) return fail(c, BI_ERR_INVALID, "analysis space has %lld bins, the model %lld", (long long)bins, (long long)c->B);
+    AxisWalk ax;
+    if ((rc = walk_axes(c, k, n_edges, edges, 2, false, kSpaceWords, ax))) return rc;
+    if (ax.bins != c->B) return fail(c, BI_ERR_INVALID, "analysis space has %lld bins, the model %lld", (long long)ax.bins, (long long)c->B);
     HIP_TRY(c, hipSetDevice(c->device));
     c->space_k = k;
-    c->space_n_edges = ne;
+    c->space_n_edges.assign(n_edges, n_edges + k);
+    const std::vector<double> flat(edges, edges + ax.flat);      // (alive until the copy below is complete)
     if ((rc = dev_upload(c, c->space_edges, flat))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BI_OK;
@@ -399,7 +388,7 @@ int bi_upload_events(bi_ctx* c, int64_t N, const double* coords) {
     if ((rc = dev_alloc(c, c->counts, bytes))) return rc;
     HIP_TRY(c, hipMemsetAsync(c->counts.p, 0, bytes, c->stream));
     if (N > 0) {
-        DevBuf d_ev;
+        ScratchBuf d_ev;
         if ((rc = dev_alloc(c, d_ev, (size_t)N * c->space_k * sizeof(double)))) return rc;
         hipError_t e = hipMemcpyAsync(d_ev.p, coords, (size_t)N * c->space_k * sizeof(double), hipMemcpyHostToDevice, c->stream);
         HistArgs h{};
@@ -412,7 +401,6 @@ int bi_upload_events(bi_ctx* c, int64_t N, const double* coords) {
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // coords are borrowed for the call only
-        dev_free(d_ev);
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_upload_events: %s", hipGetErrorString(e));
     }
     return finish_counts(c, 1);
@@ -422,29 +410,19 @@ int bi_histogram_events(bi_ctx* c, int k, const int32_t* n_edges, const double* 
                         double* counts) {
     if (!c) return BI_ERR_INVALID;
     if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
-    if (k < 1 || k > kMaxDim || !n_edges || !edges || !counts) return fail(c, BI_ERR_INVALID, "need 1..%d axes with edges, and a counts buffer", kMaxDim);
+    AxisWalk ax;              // (a missing counts buffer is reported with the axes)
+    int rc = walk_axes(c, k, n_edges, counts ? edges : nullptr, 2, false, kHistWords, ax);
+    if (rc) return rc;
     if (N < 0 || (N > 0 && !coords)) return fail(c, BI_ERR_INVALID, "bad N / coords");
     HistArgs h{};
     h.k = k;
-    int64_t bins = 1;
-    int off = 0;
-    for (int i = 0; i < k; ++i) {
-        if (n_edges[i] < 2) return fail(c, BI_ERR_INVALID, "axis %d needs at least two edges", i);
-        for (int j = 1; j < n_edges[i]; ++j)
-            if (!(edges[off + j] > edges[off + j - 1])) return fail(c, BI_ERR_INVALID, "bin edges of axis %d are not strictly ascending", i);
-        h.n_edges[i] = n_edges[i];
-        h.edge_off[i] = off;
-        off += n_edges[i];
-        bins *= n_edges[i] - 1;
-    }
+    ax.put(h.n_edges, h.edge_off);
+    const int64_t bins = ax.bins;
+    const int off = ax.flat;
     HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf d_ev, d_edges, d_counts;
-    int rc;
+    ScratchBuf d_ev, d_edges, d_counts;
     if ((rc = dev_alloc(c, d_counts, (size_t)bins * sizeof(double))) || (rc = dev_alloc(c, d_edges, (size_t)off * sizeof(double))) ||
-        (N > 0 && (rc = dev_alloc(c, d_ev, (size_t)N * k * sizeof(double))))) {
-        dev_free(d_counts); dev_free(d_edges); dev_free(d_ev);
-        return rc;
-    }
+        (N > 0 && (rc = dev_alloc(c, d_ev, (size_t)N * k * sizeof(double))))) return rc;
     hipError_t e = hipMemsetAsync(d_counts.p, 0, (size_t)bins * sizeof(double), c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_edges.p, edges, (size_t)off * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && N > 0) {
@@ -458,7 +436,6 @@ int bi_histogram_events(bi_ctx* c, int k, const int32_t* n_edges, const double* 
     if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts.p, (size_t)bins * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
-    dev_free(d_counts); dev_free(d_edges); dev_free(d_ev);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_histogram_events: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -759,7 +736,7 @@ int bi_plan_status(bi_ctx* c, bi_plan* plan, int32_t* status_or) {
             const int32_t* st = (const int32_t*)plan->status.p;
             for (int64_t p = 0; p < plan->P; ++p) any |= st[p];
         } else {
-            DevBuf d_or;
+            ScratchBuf d_or;
             int rc = dev_alloc(c, d_or, 64);
             if (rc) return rc;
             hipError_t e = hipMemsetAsync(d_or.p, 0, 4, c->stream);
@@ -771,7 +748,6 @@ int bi_plan_status(bi_ctx* c, bi_plan* plan, int32_t* status_or) {
             // (the word comes back through the planner's pinned report block: no copy into pageable memory, no stream synchronisation)
             if (e == hipSuccess) e = plan_report(c, ReportPiece{(const uint32_t*)d_or.p, 1, 0});
             if (e == hipSuccess) any = *(const int32_t*)c->plan_host;
-            dev_free(d_or);
             if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_plan_status: %s", hipGetErrorString(e));
         }
     }
@@ -867,16 +843,12 @@ int build_tile_major(bi_ctx* c, int tile_bins, DevBuf& entries, DevBuf& off, boo
     const int64_t nnz = c->h_nz_off.back(), cells = (int64_t)n_tl * c->T;
     const uint32_t pad_entry = (uint32_t)tile_bins << 3;          // four-byte lists: the offset of the extra LDS slot behind the tile (0.0), count 0
     int rc;
-    DevBuf d_tile, d_cnt, d_tmp, d_bad;
-    auto drop = [&]() { dev_free(d_tile); dev_free(d_cnt); dev_free(d_tmp); dev_free(d_bad); };
+    ScratchBuf d_tile, d_cnt, d_tmp, d_bad;
     size_t scan_bytes = 0;
     (void)prim_exclusive_scan_sum(nullptr, scan_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(cells + 1), c->stream);
     if ((rc = dev_alloc(c, d_tile, (size_t)c->T * (n_tl + 1) * sizeof(int32_t))) || (rc = dev_alloc(c, d_cnt, (size_t)(cells + 1) * sizeof(int64_t))) ||
         (rc = dev_alloc(c, d_tmp, std::max<size_t>(scan_bytes, 256))) || (rc = dev_alloc(c, d_bad, 64)) ||
-        (rc = dev_alloc(c, off, (size_t)(cells + 1) * sizeof(int64_t)))) {
-        drop();
-        return rc;
-    }
+        (rc = dev_alloc(c, off, (size_t)(cells + 1) * sizeof(int64_t)))) return rc;
     hipLaunchKernelGGL(k_csr_tile_offsets, dim3((unsigned)c->T), dim3(kThreads), 0, c->stream, (const int32_t*)c->nz_idx.p,
                        (const int64_t*)c->nz_off.p, n_tl, (int32_t*)d_tile.p, tile_shift);
     hipError_t e = hipGetLastError();
@@ -886,7 +858,7 @@ int build_tile_major(bi_ctx* c, int tile_bins, DevBuf& entries, DevBuf& off, boo
     for (int width = c->dot_entry16 ? 2 : 4; e == hipSuccess && !ok; width = 4) {
         const int group = 16 / width;
         const size_t n_entries = (size_t)(nnz + (group - 1) * cells + kDotPad);     // (every run padded to whole 16-byte groups; + the kernel's read-ahead)
-        if ((rc = dev_alloc(c, entries, n_entries * width))) { drop(); return rc; }
+        if ((rc = dev_alloc(c, entries, n_entries * width))) return rc;
         e = hipMemsetAsync(d_bad.p, 0, 64, c->stream);
         // (two-byte entries: 13 bits of offset -- tiles of 8192 bins use them all, their padding is entry 0, dropped by a select on
         //  the count; tiles of up to 4096 bins leave the bit for the offset of the extra zero slot behind the tile, as four-byte
@@ -916,7 +888,6 @@ int build_tile_major(bi_ctx* c, int tile_bins, DevBuf& entries, DevBuf& off, boo
         if (width == 4) break;
     }
     if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets (tile-major lists): %s", hipGetErrorString(e));
     if (!ok) { dev_free(entries); dev_free(off); }
     return BI_OK;
@@ -969,8 +940,7 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
     const int n_tiles = n_tiles_of(c);
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     const int nmu = (int)std::min<int64_t>(n_tiles, slots);
-    DevBuf d_out;
-    auto cleanup = [&]() { dev_free(d_out); };
+    ScratchBuf d_out;
     const bool csr = (c->sparse && c->csr_ready) || !c->dense_counts;
     if (csr && !c->csr_ready) return fail(c, BI_ERR_STATE, "no counts resident");
     // Non-empty-bin lists with enough entries per (dataset, bin tile): the tiled kernel (log mu staged through LDS, the
@@ -996,10 +966,7 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
         (rc = dev_alloc(c, c->logmu, (size_t)c->Bp * sizeof(double))) ||
         (rc = dev_alloc(c, c->scratch, (size_t)nmu * sizeof(double) + (size_t)nmu * sizeof(unsigned) + 64)) ||
         (rc = dev_alloc(c, c->scratch2, (size_t)std::min(n, chunk) * nbx * sizeof(double))) ||
-        (!host_out && !out_dev && (rc = dev_alloc(c, d_out, (size_t)std::max<int64_t>(n, 1) * sizeof(double))))) {
-        cleanup();
-        return rc;
-    }
+        (!host_out && !out_dev && (rc = dev_alloc(c, d_out, (size_t)std::max<int64_t>(n, 1) * sizeof(double))))) return rc;
     double* res = out_dev ? out_dev : (host_out ? (double*)pu.host_out() : (double*)d_out.p);
     LaunchArgs a{};
     a.ps = (const double*)c->ps.p;
@@ -1013,7 +980,7 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
     unsigned long long* done_word = nullptr;
     unsigned long long seq = 0;
     if (tiled && host_out && n <= chunk && c->poll_result && !c->profiling && (c->toy_fast_call & 6) == 6) {
-        if ((rc = dev_alloc(c, c->toy_blocks_done, 64))) { cleanup(); return rc; }
+        if ((rc = dev_alloc(c, c->toy_blocks_done, 64))) return rc;
         if (!c->toy_blocks_done_zeroed) {
             HIP_TRY(c, hipMemsetAsync(c->toy_blocks_done.p, 0, 64, c->stream));
             c->toy_blocks_done_zeroed = true;
@@ -1118,7 +1085,6 @@ int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int
     //  unknown state: it is zeroed again before the next call, which would otherwise wait out its 50 ms every time)
     if (done_word && !arrived) c->toy_blocks_done_zeroed = false;
     if (e == hipSuccess && n && host_out) memcpy(out, res, (size_t)n * sizeof(double));
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -1156,27 +1122,10 @@ int bi_eval_datasets_device(bi_ctx* c, const double* z, const double* rate_scale
 
 // ---- toy-MC generation -------------------------------------------------------------------------
 
-int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64_t T, uint64_t seed) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (T < 1) return fail(c, BI_ERR_INVALID, "need T >= 1 toys");
-    if (c->B < 1) return fail(c, BI_ERR_INVALID, "a binned likelihood needs at least one bin");
-    if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    HIP_TRY(c, hipSetDevice(c->device));
-    PointGeom g;
-    if (!point_geometry(c, z, g)) return fail(c, BI_ERR_INVALID, "toy generation point is outside the anchor box");
-    std::vector<double> r((size_t)c->S);
-    interp_mus(c, g, r.data());
-    if (rate_scale) for (int s = 0; s < c->S; ++s) r[(size_t)s] *= rate_scale[s];
-    for (int s = 0; s < c->S; ++s)
-        if (!(r[(size_t)s] >= 0.0 && r[(size_t)s] < std::numeric_limits<double>::infinity()))
-            return fail(c, BI_ERR_INVALID, "toy generation needs rates in [0, inf)");
-    c->data_ready = false;
-    c->dense_counts = false;
-    c->csr_ready = c->compact_ready = false;
-    ++c->epoch;
-    dev_free(c->counts);  // the toys exist as non-empty-bin lists only
-    c->cnt8_valid = false;  // ... and the narrow copy of the dense counts goes with them (bi_counts_to_dense rebuilds it)
+// bi_generate_toys: the non-empty-bin lists (nz_*, lgsum) of T toys at the point with geometry g and rates r; its scratch is
+// back in the recycle cache when it returns
+static int draw_toy_lists(bi_ctx* c, const PointGeom& g, const std::vector<double>& r, int64_t T, uint64_t seed) {
+    int rc;
     const int nc = (int)g.w.size(), NS = nc * c->S;
     std::vector<int64_t> rowoff((size_t)NS);
     std::vector<double> coef((size_t)NS);
@@ -1191,16 +1140,12 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     const int nmu = (int)std::min<int64_t>(n_tiles, slots);
     const int64_t B = c->B;
     const int nchunks = (int)((B + kNzChunk - 1) / kNzChunk);
-    DevBuf d_row, d_coef, d_cnt, d_off, d_lgp, d_p0;
-    auto cleanup = [&]() { dev_free(d_row); dev_free(d_coef); dev_free(d_cnt); dev_free(d_off); dev_free(d_lgp); dev_free(d_p0); };
+    ScratchBuf d_row, d_coef, d_cnt, d_off, d_lgp, d_p0;
     if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_coef, coef)) ||
         (rc = dev_alloc(c, c->logmu, (size_t)c->Bp * sizeof(double))) || (rc = dev_alloc(c, d_p0, (size_t)c->Bp * sizeof(double))) ||
         (rc = dev_alloc(c, c->scratch, (size_t)nmu * sizeof(double) + (size_t)nmu * sizeof(unsigned) + 64)) ||
         (rc = dev_alloc(c, d_cnt, (size_t)T * nchunks * sizeof(int32_t))) ||
-        (rc = dev_alloc(c, d_lgp, (size_t)T * nchunks * sizeof(double))) || (rc = dev_alloc(c, c->lgsum, (size_t)T * sizeof(double)))) {
-        cleanup();
-        return rc;
-    }
+        (rc = dev_alloc(c, d_lgp, (size_t)T * nchunks * sizeof(double))) || (rc = dev_alloc(c, c->lgsum, (size_t)T * sizeof(double)))) return rc;
     LaunchArgs a{};
     a.ps = (const double*)c->ps.p;
     a.rowoff = (const int64_t*)d_row.p;
@@ -1216,34 +1161,28 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     // in the cumulative sums, sorted and run-length encoded per toy (k_toy_events); else one draw per bin.
     c->last_toy_method = 0;
     if (c->toy_events && c->ps_nonneg && B >= 4096) {
-        DevBuf d_cdf, d_tmp, d_nev, d_room, d_nnz, d_ovf, d_tidx, d_tn;
-        auto drop = [&]() { dev_free(d_cdf); dev_free(d_tmp); dev_free(d_nev); dev_free(d_room); dev_free(d_nnz); dev_free(d_ovf); dev_free(d_tidx); dev_free(d_tn); };
+        ScratchBuf d_cdf, d_tmp, d_nev, d_room, d_nnz, d_ovf, d_tidx, d_tn;
         size_t sb1 = 0, sb2 = 0;
         (void)prim_inclusive_scan_sum(nullptr, sb1, (const double*)nullptr, (double*)nullptr, (size_t)B, c->stream);
         (void)prim_exclusive_scan_sum(nullptr, sb2, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(T + 1), c->stream);
         if ((rc = dev_alloc(c, d_cdf, (size_t)B * sizeof(double))) || (rc = dev_alloc(c, d_tmp, std::max<size_t>({sb1, sb2, 256}))) ||
-            (rc = dev_alloc(c, d_ovf, 64))) { drop(); cleanup(); return rc; }
+            (rc = dev_alloc(c, d_ovf, 64))) return rc;
         size_t tb = d_tmp.bytes;
         hipError_t e = prim_inclusive_scan_sum(d_tmp.p, tb, mu, (double*)d_cdf.p, (size_t)B, c->stream);
         double M = 0.0;
         if (e == hipSuccess) e = hipMemcpyAsync(&M, (const double*)d_cdf.p + (B - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_ovf.p, 0, 64, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { drop(); cleanup(); return fail(c, BI_ERR_HIP, "toy generation (cumulative sums): %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (cumulative sums): %s", hipGetErrorString(e));
         const double bound = M + 12.0 * std::sqrt(std::max(M, 1.0)) + 32.0;
         int npow2 = 1024;
         while (npow2 < bound && npow2 < 65536) npow2 <<= 1;
         if (M > 0.0 && M == M && M < (double)B / 8.0 && npow2 <= 32768) {
             const size_t lds = (npow2 <= 16384 ? (size_t)2 * npow2 * sizeof(uint32_t) + 16 * kEvThreads * sizeof(uint16_t)
                                                : (size_t)npow2 * sizeof(uint32_t)) + kEvThreads * (sizeof(int) + sizeof(double)) + 64;
-            if ((e = hipFuncSetAttribute((const void*)k_toy_events, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) {
-                drop(); cleanup();
-                return fail(c, BI_ERR_HIP, "toy generation (LDS size of the event kernel): %s", hipGetErrorString(e));
-            }
+            if ((e = hipFuncSetAttribute((const void*)k_toy_events, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (LDS size of the event kernel): %s", hipGetErrorString(e));
             if ((rc = dev_alloc(c, d_nev, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, d_room, (size_t)(T + 1) * sizeof(int64_t))) ||
-                (rc = dev_alloc(c, d_nnz, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, c->nz_off, (size_t)(T + 1) * sizeof(int64_t)))) {
-                drop(); cleanup(); return rc;
-            }
+                (rc = dev_alloc(c, d_nnz, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, c->nz_off, (size_t)(T + 1) * sizeof(int64_t)))) return rc;
             // (1) events per toy -> room in the provisional lists
             hipLaunchKernelGGL(k_toy_event_counts, dim3((unsigned)((T + 1 + 255) / 256)), dim3(256), 0, c->stream, M, seed, c->toy_offset, T,
                                npow2, (int64_t*)d_nev.p, (int*)d_ovf.p);
@@ -1254,10 +1193,10 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
             if (e == hipSuccess) e = hipMemcpyAsync(&n_events, (const int64_t*)d_room.p + T, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(&ovf, d_ovf.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) { drop(); cleanup(); return fail(c, BI_ERR_HIP, "toy generation (events per toy): %s", hipGetErrorString(e)); }
+            if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events per toy): %s", hipGetErrorString(e));
             if (!ovf) {
                 if ((rc = dev_alloc(c, d_tidx, (size_t)std::max<int64_t>(n_events, 1) * sizeof(int32_t))) ||
-                    (rc = dev_alloc(c, d_tn, (size_t)std::max<int64_t>(n_events, 1) * sizeof(double)))) { drop(); cleanup(); return rc; }
+                    (rc = dev_alloc(c, d_tn, (size_t)std::max<int64_t>(n_events, 1) * sizeof(double)))) return rc;
                 // (2) one block per toy: events -> sorted bins -> (bin, count) runs, written into the toy's room
                 const int64_t tchunk_ev = 65535;
                 for (int64_t t0 = 0; t0 < T; t0 += tchunk_ev) {
@@ -1274,10 +1213,10 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
                 if (e == hipSuccess) e = hipGetLastError();
                 if (e == hipSuccess) e = hipMemcpyAsync(c->h_nz_off.data(), c->nz_off.p, (size_t)(T + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) { drop(); cleanup(); return fail(c, BI_ERR_HIP, "toy generation (events): %s", hipGetErrorString(e)); }
+                if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events): %s", hipGetErrorString(e));
                 const int64_t run = c->h_nz_off[(size_t)T];
                 if ((rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
-                    (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double)))) { drop(); cleanup(); return rc; }
+                    (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double)))) return rc;
                 for (int64_t t0 = 0; t0 < T; t0 += tchunk_ev) {
                     const int64_t n = std::min(tchunk_ev, T - t0);
                     hipLaunchKernelGGL(k_toy_pack, dim3((unsigned)n), dim3(kThreads), 0, c->stream, (const int64_t*)d_room.p + t0,
@@ -1288,19 +1227,12 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
                 e = hipGetLastError();
                 if (e == hipSuccess) e = hipMemcpyAsync(c->h_lgsum.data(), c->lgsum.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                drop();
-                cleanup();
                 if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events, pack): %s", hipGetErrorString(e));
                 c->last_toy_method = 1;
-                c->T = T;
-                c->csr_ready = true;
-                if ((rc = build_compact_templates(c))) return rc;
-                c->data_ready = true;
                 return BI_OK;
             }
         }
-        drop();            // not sparse enough, or a toy beyond the sort buffer (12 sigma): one draw per bin below
-    }
+    }                      // not sparse enough, or a toy beyond the sort buffer (12 sigma): one draw per bin below, without that scratch
     const int64_t tchunk = 32768;
     for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
         const int64_t n = std::min(tchunk, T - t0);
@@ -1311,7 +1243,7 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "toy count: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy count: %s", hipGetErrorString(e));
     std::vector<int64_t> h_off(h_cnt.size());
     c->h_nz_off.assign((size_t)T + 1, 0);
     int64_t run = 0;
@@ -1321,10 +1253,7 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     }
     c->h_nz_off[(size_t)T] = run;
     if ((rc = dev_upload(c, d_off, h_off)) || (rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
-        (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double))) || (rc = dev_upload(c, c->nz_off, c->h_nz_off))) {
-        cleanup();
-        return rc;
-    }
+        (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double))) || (rc = dev_upload(c, c->nz_off, c->h_nz_off))) return rc;
     for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
         const int64_t n = std::min(tchunk, T - t0);
         hipLaunchKernelGGL(k_toy_scatter, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream, mu, p0, B, seed,
@@ -1337,8 +1266,27 @@ int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_lgsum.data(), c->lgsum.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy scatter: %s", hipGetErrorString(e));
+    return BI_OK;
+}
+
+int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64_t T, uint64_t seed) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (T < 1) return fail(c, BI_ERR_INVALID, "need T >= 1 toys");
+    if (c->B < 1) return fail(c, BI_ERR_INVALID, "a binned likelihood needs at least one bin");
+    if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    PointGeom g;
+    std::vector<double> r;
+    if ((rc = rates_at(c, c, z, rate_scale, "toy generation", "toy generation", g, r))) return rc;
+    c->data_ready = false;
+    c->dense_counts = false;
+    c->csr_ready = c->compact_ready = false;
+    ++c->epoch;
+    dev_free(c->counts);  // the toys exist as non-empty-bin lists only
+    c->cnt8_valid = false;  // ... and the narrow copy of the dense counts goes with them (bi_counts_to_dense rebuilds it)
+    if ((rc = draw_toy_lists(c, g, r, T, seed))) return rc;
     c->T = T;
     c->csr_ready = true;
     if ((rc = build_compact_templates(c))) return rc;   // per-toy point evaluations, when the budget allows
@@ -1422,526 +1370,7 @@ int bi_set_unbinned(bi_ctx* c, double outlier_likelihood) {
 
 }  // extern "C"
 
-namespace {
-
-// coords: host [k][N], or coords_dev: the same block already in HBM (bi_simulate_events)
-// pad_cols (several event sets: the padding columns between them, which get 1.0 in every row): the events keep their order
-int score_events_impl(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t N,
-                      const double* coords, const double* coords_dev, double outlier_likelihood,
-                      const std::vector<int64_t>* pad_cols = nullptr) {
-    if (!c) return BI_ERR_INVALID;
-    if (!tp || tp == c) return fail(c, BI_ERR_INVALID, "need a templates context different from the target");
-    if (c->pending || tp->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding: call bi_eval_end first");
-    if (!tp->model_ready) return fail(c, BI_ERR_STATE, "the templates context holds no model");
-    if (tp->device != c->device) return fail(c, BI_ERR_INVALID, "templates and target live on different devices");
-    if (tp->bb_source >= 0) return fail(c, BI_ERR_INVALID, "Beeston-Barlow applies to binned likelihoods only");
-    if (method != 0 && method != 1) return fail(c, BI_ERR_INVALID, "method must be 0 (piecewise) or 1 (linear)");
-    if (k < 1 || k > kMaxDim || !n_grid || !grid) return fail(c, BI_ERR_INVALID, "need 1..%d axes with grid values", kMaxDim);
-    if (N < 0 || (N > 0 && !coords && !coords_dev)) return fail(c, BI_ERR_INVALID, "bad N / coords");
-    ScoreArgs a{};
-    a.k = k;
-    a.method = method;
-    a.clip = coords_dev ? 1 : 0;          // events simulated on the device arrive unclipped; a caller's events are clipped already
-    int64_t bins = 1;
-    int off = 0;
-    for (int i = 0; i < k; ++i) {
-        if (n_grid[i] < 2) return fail(c, BI_ERR_INVALID, "axis %d needs at least two grid values", i);
-        for (int j = 1; j < n_grid[i]; ++j)
-            if (!(grid[off + j] > grid[off + j - 1])) return fail(c, BI_ERR_INVALID, "grid values of axis %d are not strictly ascending", i);
-        a.n_grid[i] = n_grid[i];
-        a.grid_off[i] = off;
-        off += n_grid[i];
-        bins *= method == 0 ? n_grid[i] - 1 : n_grid[i];
-    }
-    if (bins != tp->B) return fail(c, BI_ERR_INVALID, "the grid describes %lld bins, the templates have %lld", (long long)bins, (long long)tp->B);
-    int64_t step = 1;
-    for (int i = k - 1; i >= 0; --i) { a.stride[i] = step; step *= method == 0 ? n_grid[i] - 1 : n_grid[i]; }
-    // the target becomes a model on the same anchor grid with one "bin" per event
-    std::vector<int32_t> na(tp->n_anchor.begin(), tp->n_anchor.end());
-    std::vector<double> az;
-    for (int i = 0; i < tp->d; ++i) az.insert(az.end(), tp->grid[(size_t)i].begin(), tp->grid[(size_t)i].end());
-    int rc = bi_model_begin(c, tp->d, na.data(), az.data(), tp->S, N, -1);
-    if (rc) return rc;
-    if (N > 0) {
-        DevBuf d_ev, d_grid, d_base, d_t, d_keys, d_iota, d_tmp, d_pad;
-        auto drop = [&]() { dev_free(d_ev); dev_free(d_grid); dev_free(d_base); dev_free(d_t); dev_free(d_keys); dev_free(d_iota); dev_free(d_tmp); dev_free(d_pad); };
-        // events ordered by cell (see k_score_rows): from a few thousand events on, and while 32-bit positions do
-        // (not with several event sets: a set is a range of columns)
-        const bool sorted = !pad_cols && c->score_sorted && N >= 4096 && N < ((int64_t)1 << 31);
-        if (pad_cols && !pad_cols->empty() && (rc = dev_upload(c, d_pad, *pad_cols))) { drop(); return rc; }
-        size_t sort_bytes = 0;
-        if (sorted) (void)prim_sort_pairs(nullptr, sort_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (const int32_t*)nullptr,
-                                                    (int32_t*)nullptr, (size_t)N, 0u, 64u, c->stream);
-        if ((!coords_dev && (rc = dev_alloc(c, d_ev, (size_t)N * k * sizeof(double)))) || (rc = dev_alloc(c, d_grid, (size_t)off * sizeof(double))) ||
-            (rc = dev_alloc(c, d_base, (size_t)N * sizeof(int64_t))) || (method == 1 && (rc = dev_alloc(c, d_t, (size_t)N * k * sizeof(double)))) ||
-            (sorted && ((rc = dev_alloc(c, d_keys, (size_t)N * sizeof(int64_t))) || (rc = dev_alloc(c, d_iota, (size_t)N * sizeof(int32_t))) ||
-                        (rc = dev_alloc(c, d_tmp, std::max<size_t>(sort_bytes, 256))) || (rc = dev_alloc(c, c->ev_perm, (size_t)N * sizeof(int32_t)))))) {
-            drop();
-            return rc;
-        }
-        hipError_t e = coords_dev ? hipSuccess : hipMemcpyAsync(d_ev.p, coords, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_grid.p, grid, (size_t)off * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(tp->stream);            // whatever filled the templates is complete
-        if (e == hipSuccess) {
-            // every event's cell and weights once, then the gathers row by row: the row is the slow dimension of the grid, so
-            // the chip works on one or two 8 MB histograms at a time (see k_score_rows)
-            const int n_rows = (int)(tp->A * tp->S);
-            hipLaunchKernelGGL(k_score_locate, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
-                               coords_dev ? coords_dev : (const double*)d_ev.p, N, a, (const double*)d_grid.p, (int64_t*)d_base.p, (double*)d_t.p);
-            const int64_t* base_used = (const int64_t*)d_base.p;
-            if (sorted) {
-                hipLaunchKernelGGL(k_iota32, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, (int32_t*)d_iota.p, N);
-                size_t tb = d_tmp.bytes;
-                // (the cell index needs ceil(log2 B) bits: fewer radix passes than 64)
-                unsigned bits = 1;
-                while (bits < 63 && ((int64_t)1 << bits) < tp->B) ++bits;
-                e = prim_sort_pairs(d_tmp.p, tb, (const int64_t*)d_base.p, (int64_t*)d_keys.p, (const int32_t*)d_iota.p,
-                                              (int32_t*)c->ev_perm.p, (size_t)N, 0u, bits, c->stream);
-                base_used = (const int64_t*)d_keys.p;
-            }
-            const int per_block = kThreads * score_events_per_thread(method == 0 ? 0 : k);
-            const unsigned bx = (unsigned)((N + per_block - 1) / per_block);
-#define BI_ROWS(K)                                                                                                 \
-    hipLaunchKernelGGL((k_score_rows<K>), dim3(bx, (unsigned)std::min(n_rows, 65535)), dim3(kThreads), 0, c->stream, \
-                       base_used, (const double*)d_t.p, N, a, (const double*)tp->ps.p, tp->Bp, n_rows, (double*)c->ps.p, c->Bp,        \
-                       sorted ? (const int32_t*)c->ev_perm.p : (const int32_t*)nullptr)
-            if (e == hipSuccess) switch (method == 0 ? 0 : k) {
-                case 0: BI_ROWS(0); break; case 1: BI_ROWS(1); break; case 2: BI_ROWS(2); break; case 3: BI_ROWS(3); break;
-                case 4: BI_ROWS(4); break; case 5: BI_ROWS(5); break; case 6: BI_ROWS(6); break; case 7: BI_ROWS(7); break;
-                default: BI_ROWS(8); break;
-            }
-#undef BI_ROWS
-            if (e == hipSuccess && pad_cols && !pad_cols->empty()) {
-                const int64_t n_fill = (int64_t)n_rows * (int64_t)pad_cols->size();
-                hipLaunchKernelGGL(k_fill_columns, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, c->stream, (double*)c->ps.p, c->Bp,
-                                   (int64_t)n_rows, (const int64_t*)d_pad.p, (int64_t)pad_cols->size(), 1.0);
-            }
-            if (e == hipSuccess) e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);              // coords are borrowed for the call only
-        else (void)hipStreamSynchronize(c->stream);
-        drop();
-        c->ev_sorted = e == hipSuccess && sorted;
-        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_score_events: %s", hipGetErrorString(e));
-    }
-    c->h_mus = tp->h_mus;
-    std::fill(c->anchor_set.begin(), c->anchor_set.end(), 1);
-    if ((rc = bi_model_end(c))) return rc;
-    c->allow_neg = tp->allow_neg;
-    return bi_set_unbinned(c, outlier_likelihood);
-}
-
-}  // namespace
-
-extern "C" {
-
-int bi_score_events(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t N,
-                    const double* coords, double outlier_likelihood) {
-    return score_events_impl(tp, c, method, k, n_grid, grid, N, coords, nullptr, outlier_likelihood);
-}
-
-int bi_simulate_events(bi_ctx* tp, bi_ctx* c, const double* z, const double* rate_scale, int method, int k, const int32_t* n_edges,
-                       const double* edges, uint64_t seed, double outlier_likelihood, int64_t* n_per_source) {
-    if (!c) return BI_ERR_INVALID;
-    if (!tp || tp == c) return fail(c, BI_ERR_INVALID, "need a templates context different from the target");
-    if (c->pending || tp->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding: call bi_eval_end first");
-    if (!tp->model_ready) return fail(c, BI_ERR_STATE, "the templates context holds no model");
-    if (tp->device != c->device) return fail(c, BI_ERR_INVALID, "templates and target live on different devices");
-    if (method != 0 && method != 1) return fail(c, BI_ERR_INVALID, "method must be 0 (piecewise) or 1 (linear)");
-    if (k < 1 || k > kMaxDim || !n_edges || !edges) return fail(c, BI_ERR_INVALID, "need 1..%d axes with bin edges", kMaxDim);
-    if (tp->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    SimArgs a{};
-    a.k = k; a.S = tp->S;
-    int64_t bins = 1;
-    int off = 0;
-    for (int i = 0; i < k; ++i) {
-        if (n_edges[i] < (method == 1 ? 3 : 2)) return fail(c, BI_ERR_INVALID, "axis %d has too few bin edges", i);
-        for (int j = 1; j < n_edges[i]; ++j)
-            if (!(edges[off + j] > edges[off + j - 1])) return fail(c, BI_ERR_INVALID, "bin edges of axis %d are not strictly ascending", i);
-        a.n_edges[i] = n_edges[i];
-        a.edge_off[i] = off;
-        off += n_edges[i];
-        bins *= n_edges[i] - 1;
-    }
-    if (bins != tp->B) return fail(c, BI_ERR_INVALID, "the edges describe %lld bins, the templates have %lld", (long long)bins, (long long)tp->B);
-    int64_t step = 1;
-    for (int i = k - 1; i >= 0; --i) { a.stride[i] = step; step *= n_edges[i] - 1; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    // expected events per source at z (the scalar half of likelihood.py:355-393), then N_s ~ Poisson
-    PointGeom g;
-    if (!point_geometry(tp, z, g)) return fail(c, BI_ERR_INVALID, "simulation point is outside the anchor box");
-    const int S = tp->S;
-    std::vector<double> r((size_t)S);
-    interp_mus(tp, g, r.data());
-    if (rate_scale) for (int s = 0; s < S; ++s) r[(size_t)s] *= rate_scale[s];
-    for (int s = 0; s < S; ++s)
-        if (!(r[(size_t)s] >= 0.0 && r[(size_t)s] < std::numeric_limits<double>::infinity()))
-            return fail(c, BI_ERR_INVALID, "event simulation needs rates in [0, inf)");
-    for (int s = 0; s < S; ++s)               // (N_s travels as a 32-bit int through the samplers: keep it far inside)
-        if (r[(size_t)s] >= kSimMaxRate)
-            return fail(c, BI_ERR_INVALID, "event simulation draws at most 2^30 expected events per source: source %d has %g", s, r[(size_t)s]);
-    const int nc = (int)g.w.size();
-    const int64_t B = tp->B;
-    std::vector<int64_t> rowoff((size_t)S * nc);
-    for (int s = 0; s < S; ++s)
-        for (int corner = 0; corner < nc; ++corner)
-            rowoff[(size_t)s * nc + corner] = ((g.cell_anchor + corner_offset(tp, corner)) * S + s) * tp->Bp;
-    DevBuf d_row, d_w, d_dens, d_cdf, d_edges, d_rates, d_n, d_first, d_tmp;
-    auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_dens); dev_free(d_cdf); dev_free(d_edges); dev_free(d_rates);
-                           dev_free(d_n); dev_free(d_first); dev_free(d_tmp); };
-    int rc;
-    size_t scan_bytes = 0;
-    (void)prim_inclusive_scan_sum(nullptr, scan_bytes, (const double*)nullptr, (double*)nullptr, (size_t)B, c->stream);
-    std::vector<double> h_edges(edges, edges + off);
-    if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) || (rc = dev_upload(c, d_edges, h_edges)) ||
-        (rc = dev_upload(c, d_rates, r)) || (rc = dev_alloc(c, d_dens, (size_t)S * B * sizeof(double))) ||
-        (rc = dev_alloc(c, d_cdf, (size_t)S * B * sizeof(double))) || (rc = dev_alloc(c, d_n, (size_t)S * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, d_tmp, std::max<size_t>(scan_bytes, 256)))) { cleanup(); return rc; }
-    hipError_t e = hipStreamSynchronize(tp->stream);                      // whatever filled the templates is complete
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
-                           (const double*)tp->ps.p, (const int64_t*)d_row.p, (const double*)d_w.p, nc, B, (double*)d_dens.p);
-        hipLaunchKernelGGL(k_sim_pmf, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
-                           (const double*)d_dens.p, a, (const double*)d_edges.p, B, (double*)d_dens.p);
-        e = hipGetLastError();
-    }
-    for (int s = 0; e == hipSuccess && s < S; ++s) {
-        size_t tb = d_tmp.bytes;
-        e = prim_inclusive_scan_sum(d_tmp.p, tb, (const double*)d_dens.p + (size_t)s * B, (double*)d_cdf.p + (size_t)s * B, (size_t)B, c->stream);
-    }
-    std::vector<int64_t> n_s((size_t)S, 0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sim_counts, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, c->stream, (const double*)d_rates.p, S, seed, (int64_t*)d_n.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(n_s.data(), d_n.p, (size_t)S * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "bi_simulate_events: %s", hipGetErrorString(e)); }
-    std::vector<int64_t> first((size_t)S + 1, 0);
-    for (int s = 0; s < S; ++s) first[(size_t)s + 1] = first[(size_t)s] + n_s[(size_t)s];
-    const int64_t N = first[(size_t)S];
-    if (n_per_source) std::copy(n_s.begin(), n_s.end(), n_per_source);
-    // the events themselves: coordinates [k][N] and the source of every event, kept with the target for bi_download_events
-    if ((rc = dev_alloc(c, c->sim_coords, (size_t)std::max<int64_t>(N, 1) * k * sizeof(double))) ||
-        (rc = dev_alloc(c, c->sim_source, (size_t)std::max<int64_t>(N, 1) * sizeof(int32_t))) || (rc = dev_upload(c, d_first, first))) { cleanup(); return rc; }
-    c->sim_k = k;
-    c->sim_n = N;
-    c->sim_cols = -1;
-    if (N > 0) {
-        hipLaunchKernelGGL(k_sim_events, dim3((unsigned)((N + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, (const double*)d_cdf.p, B, a,
-                           (const double*)d_edges.p, (const int64_t*)d_first.p, seed, N, (double*)c->sim_coords.p, (int32_t*)c->sim_source.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    cleanup();
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_simulate_events: %s", hipGetErrorString(e));
-    // score them at every anchor model: the grid of the lookup is the edges ('piecewise') or the bin centres ('linear')
-    std::vector<int32_t> n_grid((size_t)k);
-    std::vector<double> grid;
-    int eo = 0;
-    for (int i = 0; i < k; ++i) {
-        if (method == 0) {
-            n_grid[(size_t)i] = n_edges[i];
-            grid.insert(grid.end(), edges + eo, edges + eo + n_edges[i]);
-        } else {
-            n_grid[(size_t)i] = n_edges[i] - 1;
-            for (int j = 0; j + 1 < n_edges[i]; ++j) grid.push_back(0.5 * (edges[eo + j] + edges[eo + j + 1]));
-        }
-        eo += n_edges[i];
-    }
-    // (bi_model_begin inside re-allocates the target's model, not the sim_* buffers)
-    return score_events_impl(tp, c, method, k, n_grid.data(), grid.data(), N, nullptr, (const double*)c->sim_coords.p, outlier_likelihood);
-}
-
-int bi_download_events(bi_ctx* c, double* coords, int32_t* source) {
-    if (!c) return BI_ERR_INVALID;
-    if (c->sim_n < 0) return fail(c, BI_ERR_STATE, "no simulated events are resident (bi_simulate_events first)");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->sim_cols >= 0) {            // an ensemble (bi_simulate_event_toys): the columns without the padding between the sets
-        if (!multi_set(c) || c->sim_epoch != c->epoch || c->sim_n == 0) return c->sim_n == 0 ? BI_OK : fail(c, BI_ERR_STATE, "the simulated ensemble is no longer the context's data");
-        std::vector<double> hc(coords ? (size_t)c->sim_cols * c->sim_k : 0);
-        std::vector<int32_t> hs(source ? (size_t)c->sim_cols : 0);
-        if (coords) HIP_TRY(c, hipMemcpyAsync(hc.data(), c->sim_coords.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (source) HIP_TRY(c, hipMemcpyAsync(hs.data(), c->sim_source.p, hs.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        int64_t at = 0;
-        for (int64_t t = 0; t < c->n_sets; ++t) {
-            const int64_t f = c->set_first[(size_t)t], n = c->set_n[(size_t)t];
-            for (int ax = 0; coords && ax < c->sim_k; ++ax)
-                std::copy(hc.begin() + (size_t)ax * c->sim_cols + f, hc.begin() + (size_t)ax * c->sim_cols + f + n, coords + (size_t)ax * c->sim_n + at);
-            if (source) std::copy(hs.begin() + f, hs.begin() + f + n, source + at);
-            at += n;
-        }
-        return BI_OK;
-    }
-    if (c->sim_n > 0 && coords)
-        HIP_TRY(c, hipMemcpyAsync(coords, c->sim_coords.p, (size_t)c->sim_n * c->sim_k * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    if (c->sim_n > 0 && source)
-        HIP_TRY(c, hipMemcpyAsync(source, c->sim_source.p, (size_t)c->sim_n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return BI_OK;
-}
-
-int64_t bi_simulated_event_count(const bi_ctx* c) { return c ? c->sim_n : -1; }
-
-}  // extern "C"
-
-namespace {
-
-// the target of a scoring call over `cols` columns becomes a context of T event sets: set t at [first[t], first[t] + n[t])
-void adopt_event_sets(bi_ctx* c, const std::vector<int64_t>& first, const std::vector<int64_t>& n) {
-    const int64_t T = (int64_t)n.size();
-    c->n_sets = T;
-    c->set_first.assign(first.begin(), first.begin() + T);
-    c->set_n = n;
-    c->T = T;
-    c->h_lgsum.assign((size_t)T, 0.0);
-    c->B = n[0];              // (see bi_context.h: whatever knows nothing of sets evaluates set 0)
-    ++c->epoch;
-}
-
-// set_first [T + 1] of sets with n[t] events each (even starts), and the padding columns
-void layout_event_sets(const std::vector<int64_t>& n, std::vector<int64_t>& first, std::vector<int64_t>& pads) {
-    first.assign(n.size() + 1, 0);
-    pads.clear();
-    for (size_t t = 0; t < n.size(); ++t) {
-        first[t + 1] = (first[t] + n[t] + 1) & ~(int64_t)1;
-        if (n[t] & 1) pads.push_back(first[t] + n[t]);
-    }
-}
-
-}  // namespace
-
-extern "C" {
-
-int bi_score_event_sets(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t T,
-                        const int64_t* offsets, const double* coords, double outlier_likelihood) {
-    if (!c) return BI_ERR_INVALID;
-    if (T < 1 || !offsets) return fail(c, BI_ERR_INVALID, "need T >= 1 event sets and their offsets");
-    if (offsets[0] != 0) return fail(c, BI_ERR_INVALID, "offsets[0] must be 0");
-    for (int64_t t = 0; t < T; ++t)
-        if (offsets[t + 1] < offsets[t]) return fail(c, BI_ERR_INVALID, "offsets are not ascending at set %lld", (long long)t);
-    const int64_t N = offsets[T];
-    if (T == 1) return score_events_impl(tp, c, method, k, n_grid, grid, N, coords, nullptr, outlier_likelihood);
-    if (k < 1 || k > kMaxDim || !n_grid || !grid) return fail(c, BI_ERR_INVALID, "need 1..%d axes with grid values", kMaxDim);
-    if (N > 0 && !coords) return fail(c, BI_ERR_INVALID, "bad N / coords");
-    std::vector<int64_t> n((size_t)T), first, pads;
-    for (int64_t t = 0; t < T; ++t) n[(size_t)t] = offsets[t + 1] - offsets[t];
-    layout_event_sets(n, first, pads);
-    const int64_t cols = first[(size_t)T];
-    // the caller's events at their columns; a padding column scores at the first grid value of every axis (and is then set to 1)
-    std::vector<double> padded((size_t)cols * k);
-    int go = 0;
-    for (int ax = 0; ax < k; ++ax) {
-        if (n_grid[ax] < 1) return fail(c, BI_ERR_INVALID, "axis %d needs at least two grid values", ax);
-        double* row = padded.data() + (size_t)ax * cols;
-        std::fill(row, row + cols, grid[go]);
-        for (int64_t t = 0; t < T; ++t)
-            std::copy(coords + (size_t)ax * N + offsets[t], coords + (size_t)ax * N + offsets[t + 1], row + first[(size_t)t]);
-        go += n_grid[ax];
-    }
-    const int rc = score_events_impl(tp, c, method, k, n_grid, grid, cols, padded.data(), nullptr, outlier_likelihood, &pads);
-    if (rc) return rc;
-    adopt_event_sets(c, first, n);
-    return BI_OK;
-}
-
-int bi_simulate_event_toys(bi_ctx* tp, bi_ctx* c, const double* z, const double* rate_scale, int method, int k, const int32_t* n_edges,
-                           const double* edges, int64_t T, uint64_t seed, double outlier_likelihood, int64_t* n_per_toy_source) {
-    if (!c) return BI_ERR_INVALID;
-    if (T < 1 || T > ((int64_t)1 << 40)) return fail(c, BI_ERR_INVALID, "need T >= 1 toys");
-    if (!tp || tp == c) return fail(c, BI_ERR_INVALID, "need a templates context different from the target");
-    if (c->pending || tp->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding: call bi_eval_end first");
-    if (!tp->model_ready) return fail(c, BI_ERR_STATE, "the templates context holds no model");
-    if (tp->device != c->device) return fail(c, BI_ERR_INVALID, "templates and target live on different devices");
-    if (method != 0 && method != 1) return fail(c, BI_ERR_INVALID, "method must be 0 (piecewise) or 1 (linear)");
-    if (k < 1 || k > kMaxDim || !n_edges || !edges) return fail(c, BI_ERR_INVALID, "need 1..%d axes with bin edges", kMaxDim);
-    if (tp->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    const int64_t toy0 = c->toy_offset;
-    if (toy0 + T > ((int64_t)1 << 48)) return fail(c, BI_ERR_INVALID, "toy numbers are told apart up to 2^48");
-    if (T == 1) {             // (one set: today's layout, through today's call)
-        const int rc1 = bi_simulate_events(tp, c, z, rate_scale, method, k, n_edges, edges, toy_seed(seed, (uint64_t)toy0), outlier_likelihood, n_per_toy_source);
-        return rc1;
-    }
-    SimArgs a{};
-    a.k = k; a.S = tp->S;
-    int64_t bins = 1;
-    int off = 0;
-    for (int i = 0; i < k; ++i) {
-        if (n_edges[i] < (method == 1 ? 3 : 2)) return fail(c, BI_ERR_INVALID, "axis %d has too few bin edges", i);
-        for (int j = 1; j < n_edges[i]; ++j)
-            if (!(edges[off + j] > edges[off + j - 1])) return fail(c, BI_ERR_INVALID, "bin edges of axis %d are not strictly ascending", i);
-        a.n_edges[i] = n_edges[i];
-        a.edge_off[i] = off;
-        off += n_edges[i];
-        bins *= n_edges[i] - 1;
-    }
-    if (bins != tp->B) return fail(c, BI_ERR_INVALID, "the edges describe %lld bins, the templates have %lld", (long long)bins, (long long)tp->B);
-    int64_t step = 1;
-    for (int i = k - 1; i >= 0; --i) { a.stride[i] = step; step *= n_edges[i] - 1; }
-    HIP_TRY(c, hipSetDevice(c->device));
-    PointGeom g;
-    if (!point_geometry(tp, z, g)) return fail(c, BI_ERR_INVALID, "simulation point is outside the anchor box");
-    const int S = tp->S;
-    std::vector<double> r((size_t)S);
-    interp_mus(tp, g, r.data());
-    if (rate_scale) for (int s = 0; s < S; ++s) r[(size_t)s] *= rate_scale[s];
-    for (int s = 0; s < S; ++s)
-        if (!(r[(size_t)s] >= 0.0 && r[(size_t)s] < std::numeric_limits<double>::infinity()))
-            return fail(c, BI_ERR_INVALID, "event simulation needs rates in [0, inf)");
-    for (int s = 0; s < S; ++s)
-        if (r[(size_t)s] >= kSimMaxRate)
-            return fail(c, BI_ERR_INVALID, "event simulation draws at most 2^30 expected events per source: source %d has %g", s, r[(size_t)s]);
-    const int nc = (int)g.w.size();
-    const int64_t B = tp->B;
-    std::vector<int64_t> rowoff((size_t)S * nc);
-    for (int s = 0; s < S; ++s)
-        for (int corner = 0; corner < nc; ++corner)
-            rowoff[(size_t)s * nc + corner] = ((g.cell_anchor + corner_offset(tp, corner)) * S + s) * tp->Bp;
-    DevBuf d_row, d_w, d_dens, d_cdf, d_edges, d_rates, d_n, d_room, d_setfirst, d_first, d_tmp;
-    auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_dens); dev_free(d_cdf); dev_free(d_edges); dev_free(d_rates);
-                           dev_free(d_n); dev_free(d_room); dev_free(d_setfirst); dev_free(d_first); dev_free(d_tmp); };
-    int rc;
-    size_t scan_bytes = 0, scan2 = 0;
-    (void)prim_inclusive_scan_sum(nullptr, scan_bytes, (const double*)nullptr, (double*)nullptr, (size_t)B, c->stream);
-    (void)prim_exclusive_scan_sum(nullptr, scan2, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(T + 1), c->stream);
-    std::vector<double> h_edges(edges, edges + off);
-    if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) || (rc = dev_upload(c, d_edges, h_edges)) ||
-        (rc = dev_upload(c, d_rates, r)) || (rc = dev_alloc(c, d_dens, (size_t)S * B * sizeof(double))) ||
-        (rc = dev_alloc(c, d_cdf, (size_t)S * B * sizeof(double))) || (rc = dev_alloc(c, d_n, (size_t)T * S * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, d_room, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, d_setfirst, (size_t)(T + 1) * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, d_first, (size_t)T * (S + 1) * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, d_tmp, std::max<size_t>(std::max(scan_bytes, scan2), 256)))) { cleanup(); return rc; }
-    hipError_t e = hipStreamSynchronize(tp->stream);                      // whatever filled the templates is complete
-    if (e == hipSuccess) {                                                // the pmf rows and their running sums: once for the ensemble
-        hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
-                           (const double*)tp->ps.p, (const int64_t*)d_row.p, (const double*)d_w.p, nc, B, (double*)d_dens.p);
-        hipLaunchKernelGGL(k_sim_pmf, dim3((unsigned)((B + kThreads - 1) / kThreads), (unsigned)S), dim3(kThreads), 0, c->stream,
-                           (const double*)d_dens.p, a, (const double*)d_edges.p, B, (double*)d_dens.p);
-        e = hipGetLastError();
-    }
-    for (int s = 0; e == hipSuccess && s < S; ++s) {
-        size_t tb = d_tmp.bytes;
-        e = prim_inclusive_scan_sum(d_tmp.p, tb, (const double*)d_dens.p + (size_t)s * B, (double*)d_cdf.p + (size_t)s * B, (size_t)B, c->stream);
-    }
-    // counts of all (t, s), the columns every toy takes, their prefix sum, the start of every (t, s): four small launches
-    std::vector<int64_t> n_ts((size_t)T * S, 0), set_first((size_t)T + 1, 0);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sim_toy_counts, dim3((unsigned)((T * S + 255) / 256)), dim3(256), 0, c->stream, (const double*)d_rates.p, S, T, seed,
-                           toy0, (int64_t*)d_n.p);
-        hipLaunchKernelGGL(k_sim_toy_room, dim3((unsigned)((T + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int64_t*)d_n.p, S, T, (int64_t*)d_room.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        size_t tb = d_tmp.bytes;
-        e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_room.p, (int64_t*)d_setfirst.p, (int64_t)0, (size_t)(T + 1), c->stream);
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_sim_toy_first, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, c->stream, (const int64_t*)d_n.p,
-                           (const int64_t*)d_setfirst.p, S, T, (int64_t*)d_first.p);
-        e = hipGetLastError();
-    }
-    // the one read-back: the counts (they size the tensor and are what the caller asked for) and the set boundaries
-    if (e == hipSuccess) e = hipMemcpyAsync(n_ts.data(), d_n.p, n_ts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(set_first.data(), d_setfirst.p, set_first.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { cleanup(); return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: %s", hipGetErrorString(e)); }
-    if (n_per_toy_source) std::copy(n_ts.begin(), n_ts.end(), n_per_toy_source);
-    std::vector<int64_t> n_t((size_t)T, 0), first_chk, pads;
-    int64_t n_events = 0;
-    for (int64_t t = 0; t < T; ++t) {
-        for (int s = 0; s < S; ++s) n_t[(size_t)t] += n_ts[(size_t)(t * S + s)];
-        n_events += n_t[(size_t)t];
-    }
-    layout_event_sets(n_t, first_chk, pads);
-    if (first_chk != set_first) { cleanup(); return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: the device's set boundaries are not the counts' prefix sums"); }
-    const int64_t cols = set_first[(size_t)T];
-    if ((rc = dev_alloc(c, c->sim_coords, (size_t)std::max<int64_t>(cols, 1) * k * sizeof(double))) ||
-        (rc = dev_alloc(c, c->sim_source, (size_t)std::max<int64_t>(cols, 1) * sizeof(int32_t)))) { cleanup(); return rc; }
-    c->sim_k = k;
-    c->sim_n = n_events;
-    c->sim_cols = cols;
-    if (cols > 0) {
-        hipLaunchKernelGGL(k_sim_toy_events, dim3((unsigned)((cols + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, (const double*)d_cdf.p, B,
-                           a, (const double*)d_edges.p, (const int64_t*)d_setfirst.p, (const int64_t*)d_first.p, T, seed, toy0, cols,
-                           (double*)c->sim_coords.p, (int32_t*)c->sim_source.p);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    cleanup();
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_simulate_event_toys: %s", hipGetErrorString(e));
-    std::vector<int32_t> n_grid((size_t)k);
-    std::vector<double> grid;
-    int eo = 0;
-    for (int i = 0; i < k; ++i) {
-        if (method == 0) {
-            n_grid[(size_t)i] = n_edges[i];
-            grid.insert(grid.end(), edges + eo, edges + eo + n_edges[i]);
-        } else {
-            n_grid[(size_t)i] = n_edges[i] - 1;
-            for (int j = 0; j + 1 < n_edges[i]; ++j) grid.push_back(0.5 * (edges[eo + j] + edges[eo + j + 1]));
-        }
-        eo += n_edges[i];
-    }
-    rc = score_events_impl(tp, c, method, k, n_grid.data(), grid.data(), cols, nullptr, (const double*)c->sim_coords.p, outlier_likelihood, &pads);
-    if (rc) return rc;
-    adopt_event_sets(c, set_first, n_t);
-    c->sim_epoch = c->epoch;
-    return BI_OK;
-}
-
-int bi_event_set_offsets(bi_ctx* c, int64_t* offsets) {
-    if (!c || !offsets) return BI_ERR_INVALID;
-    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
-    for (int64_t t = 0; t < c->n_sets; ++t) offsets[t] = c->set_first[(size_t)t];
-    const int64_t end = c->set_first[(size_t)c->n_sets - 1] + c->set_n[(size_t)c->n_sets - 1];
-    offsets[c->n_sets] = c->n_sets > 1 ? ((end + 1) & ~(int64_t)1) : end;
-    return BI_OK;
-}
-
-int bi_event_set_counts(bi_ctx* c, int64_t* counts) {
-    if (!c || !counts) return BI_ERR_INVALID;
-    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
-    std::copy(c->set_n.begin(), c->set_n.end(), counts);
-    return BI_OK;
-}
-
-int64_t bi_event_set_count(const bi_ctx* c) { return (c && c->unbinned && c->data_ready) ? c->n_sets : 0; }
-
-int bi_set_event_sets(bi_ctx* c, int64_t T, const int64_t* counts) {
-    if (!c) return BI_ERR_INVALID;
-    if (!c->unbinned || !c->data_ready || c->n_sets != 1) return fail(c, BI_ERR_STATE, "bi_set_event_sets follows bi_set_unbinned");
-    if (T < 1 || !counts) return fail(c, BI_ERR_INVALID, "need T >= 1 event sets and their counts");
-    if (c->ev_sorted) return fail(c, BI_ERR_STATE, "the columns are ordered by histogram cell (score_sorted)");
-    std::vector<int64_t> n(counts, counts + T), first, pads;
-    for (int64_t t = 0; t < T; ++t)
-        if (n[(size_t)t] < 0) return fail(c, BI_ERR_INVALID, "event set %lld has a negative count", (long long)t);
-    if (T == 1) return n[0] == c->B ? BI_OK : fail(c, BI_ERR_INVALID, "one set of %lld events, the model has %lld columns", (long long)n[0], (long long)c->B);
-    layout_event_sets(n, first, pads);
-    if (first[(size_t)T] != c->B)
-        return fail(c, BI_ERR_INVALID, "the sets take %lld columns (even starts), the model has %lld", (long long)first[(size_t)T], (long long)c->B);
-    adopt_event_sets(c, first, n);
-    return BI_OK;
-}
-
-int bi_download_event_set(bi_ctx* c, int64_t t, double* out) {
-    if (!c) return BI_ERR_INVALID;
-    if (!c->unbinned || !c->data_ready) return fail(c, BI_ERR_STATE, "the context holds no unbinned data");
-    if (t < 0 || t >= c->n_sets) return fail(c, BI_ERR_INVALID, "event set %lld outside [0, %lld)", (long long)t, (long long)c->n_sets);
-    if (c->ev_sorted) return fail(c, BI_ERR_STATE, "the columns are ordered by histogram cell (score_sorted): bi_interpolate hands them back in event order");
-    const int64_t n = c->set_n[(size_t)t];
-    if (n == 0) return BI_OK;
-    if (!out) return fail(c, BI_ERR_INVALID, "out is NULL");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)n * sizeof(double), (const double*)c->ps.p + c->set_first[(size_t)t], (size_t)c->Bp * sizeof(double),
-                                (size_t)n * sizeof(double), (size_t)(c->A * c->S), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return BI_OK;
-}
-
 // ---- compatibility mode --------------------------------------------------------------------
-
-}  // extern "C"
 
 // bi_interpolate; set: the event set whose columns `which` = 0 hands back (an unbinned context with several sets: N_set columns
 // from first_set; otherwise 0)
@@ -1968,10 +1397,9 @@ static int interpolate_set(bi_ctx* c, int which, const double* z, double* out, i
             const int64_t a = g.cell_anchor + corner_offset(c, corner);
             rowoff[(size_t)r * nc + corner] = which == 0 ? (a * c->S + r) * c->Bp + col0 : a * c->Bp;
         }
-    DevBuf d_row, d_w, d_out;
-    auto cleanup = [&]() { dev_free(d_row); dev_free(d_w); dev_free(d_out); };
+    ScratchBuf d_row, d_w, d_out;
     if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_w, g.w)) ||
-        (rc = dev_alloc(c, d_out, (size_t)R * nB * sizeof(double)))) { cleanup(); return rc; }
+        (rc = dev_alloc(c, d_out, (size_t)R * nB * sizeof(double)))) return rc;
     hipLaunchKernelGGL(k_morph_store, dim3((unsigned)((nB + kThreads - 1) / kThreads), (unsigned)R), dim3(kThreads), 0,
                        c->stream, which == 0 ? (const double*)c->ps.p : (const double*)c->nm.p,
                        (const int64_t*)d_row.p, (const double*)d_w.p, nc, nB, (double*)d_out.p,
@@ -1980,7 +1408,6 @@ static int interpolate_set(bi_ctx* c, int which, const double* z, double* out, i
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out.p, (size_t)R * nB * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_interpolate: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -2022,15 +1449,11 @@ int bi_eval_full(bi_ctx* c, const double* z, const double* rate_scale, int64_t d
     std::vector<double> a_row((size_t)B);
     if ((rc = bi_interpolate(c, 2, z, a_row.data()))) return rc;
     const int nblk = (int)std::min<int64_t>(1024, (B + kThreads - 1) / kThreads);
-    DevBuf d_ps, d_a, d_mus, d_aw, d_part, d_tot;
-    auto cleanup = [&]() { dev_free(d_ps); dev_free(d_a); dev_free(d_mus); dev_free(d_aw); dev_free(d_part); dev_free(d_tot); };
+    ScratchBuf d_ps, d_a, d_mus, d_aw, d_part, d_tot;
     std::vector<double> mus_v(mus_out, mus_out + c->S);
     if ((rc = dev_alloc(c, d_ps, (size_t)c->S * B * sizeof(double))) || (rc = dev_upload(c, d_a, a_row)) ||
         (rc = dev_upload(c, d_mus, mus_v)) || (rc = dev_alloc(c, d_aw, (size_t)B * sizeof(double))) ||
-        (rc = dev_alloc(c, d_part, (size_t)nblk * sizeof(double))) || (rc = dev_alloc(c, d_tot, sizeof(double)))) {
-        cleanup();
-        return rc;
-    }
+        (rc = dev_alloc(c, d_part, (size_t)nblk * sizeof(double))) || (rc = dev_alloc(c, d_tot, sizeof(double)))) return rc;
     hipError_t e = hipMemcpyAsync(d_ps.p, ps_out, (size_t)c->S * B * sizeof(double), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(k_bb_full, dim3((unsigned)nblk), dim3(kThreads), 0, c->stream, (const double*)d_ps.p,
@@ -2046,7 +1469,6 @@ int bi_eval_full(bi_ctx* c, const double* z, const double* rate_scale, int64_t d
     if (e == hipSuccess) e = hipMemcpyAsync(ps_out + (size_t)i * B, (double*)d_ps.p + (size_t)i * B, (size_t)B * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&tot, d_tot.p, sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_full: %s", hipGetErrorString(e));
     mus_out[i] = tot * p_cal;  // likelihood.py:658
     return BI_OK;
@@ -2135,10 +1557,10 @@ int bi_memcpy_to_device(bi_ctx* c, void* dst, const void* src, int64_t bytes) {
 int bi_selftest_log(bi_ctx* c, int64_t n, const double* x, double* out) {
     if (!c || n < 0 || (n > 0 && (!x || !out))) return BI_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf dx, dy;
+    ScratchBuf dx, dy;
     int rc;
     if ((rc = dev_alloc(c, dx, (size_t)std::max<int64_t>(n, 1) * sizeof(double))) ||
-        (rc = dev_alloc(c, dy, (size_t)std::max<int64_t>(n, 1) * sizeof(double)))) { dev_free(dx); dev_free(dy); return rc; }
+        (rc = dev_alloc(c, dy, (size_t)std::max<int64_t>(n, 1) * sizeof(double)))) return rc;
     hipError_t e = n ? hipMemcpyAsync(dx.p, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream) : hipSuccess;
     if (e == hipSuccess && n) {
         hipLaunchKernelGGL(k_selftest_log, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double*)dx.p, n, (double*)dy.p);
@@ -2146,7 +1568,6 @@ int bi_selftest_log(bi_ctx* c, int64_t n, const double* x, double* out) {
     }
     if (e == hipSuccess && n) e = hipMemcpyAsync(out, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(dx); dev_free(dy);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_selftest_log: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -2159,8 +1580,7 @@ int bi_selftest_sort(bi_ctx* c, int kind, int64_t n, const void* keys, const voi
         return BI_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t vb = (kind == 0 || kind == 3) ? 8 : 4, nn = (size_t)std::max<int64_t>(n, 1);
-    DevBuf dk, dv, dk2, dv2, dt;
-    auto drop = [&]() { dev_free(dk); dev_free(dv); dev_free(dk2); dev_free(dv2); dev_free(dt); };
+    ScratchBuf dk, dv, dk2, dv2, dt;
     size_t tb = 0;
     if (kind == 0) (void)prim_sort_pairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const int64_t*)nullptr, (int64_t*)nullptr, (size_t)n, 0u, 64u, c->stream);
     else if (kind == 3) (void)prim_count_sort_pairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const int64_t*)nullptr, (int64_t*)nullptr, (size_t)n, (uint64_t)end_bit, c->stream);
@@ -2168,7 +1588,7 @@ int bi_selftest_sort(bi_ctx* c, int kind, int64_t n, const void* keys, const voi
     else (void)prim_sort_pairs(nullptr, tb, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)n, 0u, 64u, c->stream);
     int rc;
     if ((rc = dev_alloc(c, dk, nn * 8)) || (rc = dev_alloc(c, dv, nn * vb)) || (rc = dev_alloc(c, dk2, nn * 8)) || (rc = dev_alloc(c, dv2, nn * vb)) ||
-        (rc = dev_alloc(c, dt, std::max<size_t>(tb, 256)))) { drop(); return rc; }
+        (rc = dev_alloc(c, dt, std::max<size_t>(tb, 256)))) return rc;
     hipError_t e = n ? hipMemcpyAsync(dk.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, c->stream) : hipSuccess;
     if (e == hipSuccess && n) e = hipMemcpyAsync(dv.p, vals, (size_t)n * vb, hipMemcpyHostToDevice, c->stream);
     size_t t2 = dt.bytes;
@@ -2181,7 +1601,6 @@ int bi_selftest_sort(bi_ctx* c, int kind, int64_t n, const void* keys, const voi
     if (e == hipSuccess && n) e = hipMemcpyAsync(keys_out, dk2.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && n) e = hipMemcpyAsync(vals_out, dv2.p, (size_t)n * vb, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); else (void)hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_selftest_sort: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -2190,12 +1609,11 @@ int bi_selftest_scan(bi_ctx* c, int kind, int64_t n, const void* in, int64_t ini
     if (!c || n < 0 || kind < 0 || kind > 3 || (n > 0 && (!in || !out))) return BI_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    DevBuf di, dout, dt;
-    auto drop = [&]() { dev_free(di); dev_free(dout); dev_free(dt); };
+    ScratchBuf di, dout, dt;
     size_t tb = 0;
     (void)prim_exclusive_scan_sum(nullptr, tb, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)n, c->stream);   // (all kinds: 8-byte elements, the same size)
     int rc;
-    if ((rc = dev_alloc(c, di, nn * 8)) || (rc = dev_alloc(c, dout, nn * 8)) || (rc = dev_alloc(c, dt, std::max<size_t>(tb, 256)))) { drop(); return rc; }
+    if ((rc = dev_alloc(c, di, nn * 8)) || (rc = dev_alloc(c, dout, nn * 8)) || (rc = dev_alloc(c, dt, std::max<size_t>(tb, 256)))) return rc;
     hipError_t e = n ? hipMemcpyAsync(di.p, in, (size_t)n * 8, hipMemcpyHostToDevice, c->stream) : hipSuccess;
     size_t t2 = dt.bytes;
     if (e == hipSuccess) {
@@ -2206,7 +1624,6 @@ int bi_selftest_scan(bi_ctx* c, int kind, int64_t n, const void* in, int64_t ini
     }
     if (e == hipSuccess && n) e = hipMemcpyAsync(out, dout.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); else (void)hipStreamSynchronize(c->stream);
-    drop();
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_selftest_scan: %s", hipGetErrorString(e));
     return BI_OK;
 }
@@ -2217,7 +1634,7 @@ int bi_measure_read_bandwidth(bi_ctx* c, int nontemporal, int blocks_per_cu, int
     if (!c || !gb_per_s || reps < 1 || blocks_per_cu < 1) return BI_ERR_INVALID;
     if (!c->model_ready || !c->ps.p) return fail(c, BI_ERR_STATE, "bi_measure_read_bandwidth: no model resident");
     HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf sink;
+    ScratchBuf sink;
     int rc = dev_alloc(c, sink, 8);
     if (rc) return rc;
     const int64_t n2 = c->A * c->S * c->Bp / 2;       // the whole template tensor, in 16-byte elements
@@ -2238,7 +1655,6 @@ int bi_measure_read_bandwidth(bi_ctx* c, int nontemporal, int blocks_per_cu, int
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    dev_free(sink);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_measure_read_bandwidth: %s", hipGetErrorString(e));
     *gb_per_s = best;
     return BI_OK;
@@ -2248,7 +1664,7 @@ int bi_measure_stream_bandwidth(bi_ctx* c, int items, int rows, int nontemporal,
     if (!c || !gb_per_s || reps < 1 || blocks_per_cu < 1 || items < 1 || rows < 1) return BI_ERR_INVALID;
     if (!c->model_ready || !c->ps.p) return fail(c, BI_ERR_STATE, "bi_measure_stream_bandwidth: no model resident");
     HIP_TRY(c, hipSetDevice(c->device));
-    DevBuf sink;
+    ScratchBuf sink;
     int rc = dev_alloc(c, sink, 8);
     if (rc) return rc;
     const int64_t total_rows = c->A * c->S;
@@ -2281,7 +1697,6 @@ int bi_measure_stream_bandwidth(bi_ctx* c, int items, int rows, int nontemporal,
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    dev_free(sink);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_measure_stream_bandwidth: %s", hipGetErrorString(e));
     *gb_per_s = best;
     return BI_OK;

@@ -193,76 +193,73 @@ class DeviceContext:
                                                   ptr(counts)))
         return counts
 
+    @staticmethod
+    def _axes_args(method, axes):
+        """-> (method code, number of axes k, values per axis [k], the values of all axes back to back)"""
+        code = {'piecewise': 0, 'linear': 1}[method]
+        axes = [np.ascontiguousarray(a, dtype=np.float64) for a in axes]
+        n = np.array([len(a) for a in axes], dtype=np.int32)
+        return code, len(axes), n, np.ascontiguousarray(np.concatenate(axes))
+
+    def _made_unbinned(self, target, B, T):
+        """`target` now holds this context's model as an unbinned one: B columns (those of its first event set), T event sets"""
+        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(B), -1, int(T)
+        target.anchor_z = self.anchor_z
+
     def score_events(self, target, method, grid, coords, outlier_likelihood=1e-12):
         """This context holds density histograms as its model rows: evaluate all of them at the events and make the
         result the (unbinned) model of `target` -- `Model.score_events` for every anchor, on the device.
         method 'piecewise' (grid = bin edges per axis) or 'linear' (grid = bin centres per axis; coords clipped to
         them and finite)."""
-        code = {'piecewise': 0, 'linear': 1}[method]
-        grid = [np.ascontiguousarray(g, dtype=np.float64) for g in grid]
+        code, k, n_grid, flat = self._axes_args(method, grid)
         cols = np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64).ravel() for c in coords]))
-        if cols.shape[0] != len(grid):
-            raise ValueError("need %d coordinate arrays" % len(grid))
-        n_grid = np.array([len(g) for g in grid], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(grid))
-        target._check(self._lib.bi_score_events(self._h, target._h, code, len(grid), ptr(n_grid), ptr(flat), cols.shape[1],
+        if cols.shape[0] != k:
+            raise ValueError("need %d coordinate arrays" % k)
+        target._check(self._lib.bi_score_events(self._h, target._h, code, k, ptr(n_grid), ptr(flat), cols.shape[1],
                                                 ptr(cols), float(outlier_likelihood)))
-        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(cols.shape[1]), -1, 1
-        target.anchor_z = self.anchor_z
+        self._made_unbinned(target, cols.shape[1], 1)
 
     def simulate_events(self, target, method, edges, z, rate_scale=None, seed=0, outlier_likelihood=1e-12):
         """This context holds density histograms as its model rows: draw an event-level toy dataset from them at (z,
         rate_scale) on the device -- `Model.simulate` for histogram-pdf sources -- and make it the (unbinned) data of
         `target`, scored at every anchor model, without a host hop.  edges: the bin edges of every analysis dimension.
         -> events per source [S]."""
-        code = {'piecewise': 0, 'linear': 1}[method]
-        edges = [np.ascontiguousarray(e, dtype=np.float64) for e in edges]
-        n_edges = np.array([len(e) for e in edges], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(edges))
+        code, k, n_edges, flat = self._axes_args(method, edges)
         z = as_f64(z).reshape(self.d) if self.d else None
         if rate_scale is not None:
             rate_scale = as_f64(rate_scale, (self.S,))
         per_source = np.zeros(self.S, dtype=np.int64)
-        target._check(self._lib.bi_simulate_events(self._h, target._h, ptr(z), ptr(rate_scale), code, len(edges), ptr(n_edges),
+        target._check(self._lib.bi_simulate_events(self._h, target._h, ptr(z), ptr(rate_scale), code, k, ptr(n_edges),
                                                    ptr(flat), int(seed) & (2**64 - 1), float(outlier_likelihood), ptr(per_source)))
-        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(per_source.sum()), -1, 1
-        target.anchor_z = self.anchor_z
-        target._sim_dims = len(edges)
+        self._made_unbinned(target, per_source.sum(), 1)
+        target._sim_dims = k
         return per_source
 
     def score_event_sets(self, target, method, grid, coord_sets, outlier_likelihood=1e-12):
         """`score_events` for a stack of T datasets: coord_sets = T lists of coordinate arrays (one per analysis dimension).
         `target` then holds the T event sets side by side (bi_score_event_sets); its dataset t is set t."""
-        code = {'piecewise': 0, 'linear': 1}[method]
-        grid = [np.ascontiguousarray(g, dtype=np.float64) for g in grid]
-        sets = [np.stack([np.asarray(c, dtype=np.float64).ravel() for c in cs]).reshape(len(grid), -1) for cs in coord_sets]
+        code, k, n_grid, flat = self._axes_args(method, grid)
+        sets = [np.stack([np.asarray(c, dtype=np.float64).ravel() for c in cs]).reshape(k, -1) for cs in coord_sets]
         offsets = np.concatenate([[0], np.cumsum([x.shape[1] for x in sets])]).astype(np.int64)
         cols = np.ascontiguousarray(np.concatenate(sets, axis=1))
-        n_grid = np.array([len(g) for g in grid], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(grid))
-        target._check(self._lib.bi_score_event_sets(self._h, target._h, code, len(grid), ptr(n_grid), ptr(flat), len(sets), ptr(offsets),
+        target._check(self._lib.bi_score_event_sets(self._h, target._h, code, k, ptr(n_grid), ptr(flat), len(sets), ptr(offsets),
                                                     ptr(cols), float(outlier_likelihood)))
-        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(sets[0].shape[1]), -1, len(sets)
-        target.anchor_z = self.anchor_z
+        self._made_unbinned(target, sets[0].shape[1], len(sets))
 
     def simulate_event_toys(self, target, method, edges, z, rate_scale=None, n_toys=1, seed=0, outlier_likelihood=1e-12):
         """`simulate_events` for an ensemble: n_toys toys at (z, rate_scale), toy t of the call being toy toy_offset + t (the
         TARGET's parameter) of the seed's ensemble = `simulate_events` with the seed `toy_seed(seed, toy_offset + t)`.
         -> events per toy and source [T, S]."""
-        code = {'piecewise': 0, 'linear': 1}[method]
-        edges = [np.ascontiguousarray(e, dtype=np.float64) for e in edges]
-        n_edges = np.array([len(e) for e in edges], dtype=np.int32)
-        flat = np.ascontiguousarray(np.concatenate(edges))
+        code, k, n_edges, flat = self._axes_args(method, edges)
         z = as_f64(z).reshape(self.d) if self.d else None
         if rate_scale is not None:
             rate_scale = as_f64(rate_scale, (self.S,))
         counts = np.zeros((int(n_toys), self.S), dtype=np.int64)
-        target._check(self._lib.bi_simulate_event_toys(self._h, target._h, ptr(z), ptr(rate_scale), code, len(edges), ptr(n_edges),
+        target._check(self._lib.bi_simulate_event_toys(self._h, target._h, ptr(z), ptr(rate_scale), code, k, ptr(n_edges),
                                                        ptr(flat), int(n_toys), int(seed) & (2**64 - 1), float(outlier_likelihood),
                                                        ptr(counts)))
-        target.d, target.S, target.B, target.bb_source, target.T = self.d, self.S, int(counts[0].sum()), -1, int(n_toys)
-        target.anchor_z = self.anchor_z
-        target._sim_dims = len(edges)
+        self._made_unbinned(target, counts[0].sum(), n_toys)
+        target._sim_dims = k
         return counts
 
     def adopt_event_sets(self, counts):

@@ -1070,6 +1070,16 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
         self._stream_models(self._rows_of, len(d))
         self.ctx.set_unbinned(self.outlier_likelihood)
 
+    def _simulation_inputs(self, livetime_days, truth):
+        """-> (templates context, method, bin edges, z, rate scale) of a device-side simulation at `truth`"""
+        tpl = self._histogram_templates()
+        if not tpl:
+            raise NotImplementedError("device-side event simulation needs sources whose pdf is a histogram over the analysis space")
+        prior, zs, scale = self._host_terms(livetime_days, truth)
+        if prior is None:
+            raise ValueError("cannot simulate outside the anchor box")
+        edges = [np.asarray(e, dtype=float) for _, e in self.base_model.config['analysis_space']]
+        return tpl[0], tpl[1], edges, zs, scale
 
     @_needs_preparation
     def simulate_toy(self, seed=0, livetime_days=None, **kwargs):
@@ -1079,17 +1089,8 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
         volume of the (morphed) histogram pdf and a uniform position inside it, then scored at every anchor model --
         with nothing but the call crossing PCIe.  Needs sources whose pdf is a histogram (see `set_data`); raises
         NotImplementedError otherwise.  -> events per source; `simulated_events()` fetches the events themselves."""
-        tpl = self._histogram_templates()
-        if not tpl:
-            raise NotImplementedError("device-side event simulation needs sources whose pdf is a histogram over the analysis space")
-        prior, zs, scale = self._host_terms(livetime_days, kwargs)
-        if prior is None:
-            raise ValueError("cannot simulate outside the anchor box")
-        tp, method, _ = tpl
-        if self.ctx is None:
-            self.ctx = DeviceContext(self.config.get('device'))
-        edges = [np.asarray(e, dtype=float) for _, e in self.base_model.config['analysis_space']]
-        per_source = tp.simulate_events(self.ctx, method, edges, zs, scale, seed, self.outlier_likelihood)
+        tp, method, edges, zs, scale = self._simulation_inputs(livetime_days, kwargs)
+        per_source = tp.simulate_events(self._device_context(), method, edges, zs, scale, seed, self.outlier_likelihood)
         self._data = None
         self.bin_shape = (int(per_source.sum()),)
         self.is_data_set = True
@@ -1105,14 +1106,7 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
         sources whose pdf is a histogram; raises as `simulate_toy` does.  -> events per toy and source [T, S]."""
         if int(n_toys) < 1:
             raise ValueError("n_toys must be at least 1")
-        tpl = self._histogram_templates()
-        if not tpl:
-            raise NotImplementedError("device-side event simulation needs sources whose pdf is a histogram over the analysis space")
-        prior, zs, scale = self._host_terms(livetime_days, truth)
-        if prior is None:
-            raise ValueError("cannot simulate outside the anchor box")
-        tp, method, _ = tpl
-        edges = [np.asarray(e, dtype=float) for _, e in self.base_model.config['analysis_space']]
+        tp, method, edges, zs, scale = self._simulation_inputs(livetime_days, truth)
         counts = tp.simulate_event_toys(self._device_context(), method, edges, zs, scale, int(n_toys), seed, self.outlier_likelihood)
         self._data = None
         self.bin_shape = (int(counts[0].sum()),)
