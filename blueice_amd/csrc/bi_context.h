@@ -54,7 +54,7 @@ struct bi_plan {
     int64_t share_lo = 0, share_hi = 0, n_valid = 0;   // back to the caller's point indices
     DevBuf sorted_idx;
     DevBuf keep_z, keep_rs;       // gradient batches on the matrix cores: the points' z / rate_scale stay on the device for the finish kernel
-    int64_t max_group_items = 0;  // ... the largest number of work items a (cell, dataset) group holds
+    int64_t max_group_items = 0;  // ... the largest number of work items a (cell, dataset) group holds (scan plans: after chunk_groups)
     int max_item_tiles = 0;       // ... and the tiles of the longest rows
     bool device_planned = false;  // built by plan_points_device: rejected points are found through the status array
     bool no_reuse = false;     // no anchor model is touched by two items of the plan
@@ -190,6 +190,10 @@ struct bi_ctx {
     int64_t n_valid_launches = 0;                // how often the validity pass of a split scan ran
     int64_t n_scan_launches = 0;                 // how often the matrix-core scan kernel ran (observability)
     int64_t last_scan_nslots = 0, last_scan_resident = 0, last_valid_nslots = 0;   // what the planner chose last (read-only parameters)
+    // the most recent scan launch (read-only parameters, all set in bi_run_plan beside the launch): the plan's groups and its longest
+    // group's items after chunk_groups (a split scan: those of its validity pass, which sets these two only), the strip width in
+    // 16-bin blocks, 1 = k_scan_sorted took it, 1 = k_scan_mfma's PROD = 1 instantiation did (set where it is chosen)
+    int64_t last_scan_groups = 0, last_scan_max_items = 0, last_scan_cb = 0, last_scan_by_count = 0, last_scan_prod = 0;
     int64_t grad_mfma = 1;                       // bi_eval_grad: large single-dataset batches of plain binned likelihoods on the matrix cores (k_grad_mfma)
     int64_t grad_mfma_min = 2048;                // ... from this many points on (below, the planning of the batch costs more than the kernel saves)
     int64_t grad_slices = 0;                     // ... slices a cell's 16-bin blocks are split into (0 = by the batch)

@@ -135,6 +135,11 @@ const ParamDef kParams[] = {
     BI_P_RO("last_scan_nslots", c->last_scan_nslots),
     BI_P_RO("last_valid_nslots", c->last_valid_nslots),
     BI_P_RO("last_scan_resident", c->last_scan_resident),
+    BI_P_RO("last_scan_groups", c->last_scan_groups),
+    BI_P_RO("last_scan_max_items", c->last_scan_max_items),
+    BI_P_RO("last_scan_cb", c->last_scan_cb),
+    BI_P_RO("last_scan_by_count", c->last_scan_by_count),
+    BI_P_RO("last_scan_prod", c->last_scan_prod),
     BI_P_RO("last_toy_method", c->last_toy_method),
     BI_P_RO("single_calls", c->single_calls),
     BI_P_RO("single_ns_host", c->single_ns[0]),

@@ -1087,7 +1087,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
                                (const int64_t*)d_keys.p, n_valid, (int64_t*)plan->grp_first.p);
             hipLaunchKernelGGL(k_plan_group_items, dim3((unsigned)((n_groups + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
                                (const int64_t*)plan->grp_first.p, n_groups, n_items, (int32_t*)plan->grp_items.p,
-                               (grad_mode || bb_kgt) ? (unsigned long long*)(scal + 3) : (unsigned long long*)nullptr);
+                               (grad_mode || bb_kgt || split || scan_ok) ? (unsigned long long*)(scal + 3) : (unsigned long long*)nullptr);
             return BI_OK;
         };
         // (the group tables go out before the read-back, so that a gradient batch's largest group and -- for the scan kernels --
@@ -1098,6 +1098,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
         std::vector<int64_t> h_grp_first;
         std::vector<int32_t> h_grp_items;
         int64_t h_zero_u = 0, h_max = 0;
+        int64_t scan_max_items = 0;           // scan plans: the longest group's items (chunk_groups below may cut it)
         {
             // one report: the counters and -- where the item lists may be cut into chunks below -- the group tables
             const bool want_tables = (split || scan_ok) && c->scan_chunk && n_groups <= 4096;
@@ -1110,6 +1111,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
                 h_scal[2] = hs[2];
                 if (bb) h_zero_u = hs[4];
                 if (grad_mode || bb_scan) h_max = hs[3];
+                if (split || scan_ok) scan_max_items = hs[3];
                 if (want_tables) {
                     h_grp_first.assign((const int64_t*)((const uint32_t*)c->plan_host + 32), (const int64_t*)((const uint32_t*)c->plan_host + 32) + ng);
                     h_grp_items.assign((const int32_t*)c->plan_host + 32 + 2 * 4096, (const int32_t*)c->plan_host + 32 + 2 * 4096 + ng);
@@ -1238,6 +1240,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
             int rc2;
             if ((rc2 = dev_upload(c, plan->grp_first, first2)) || (rc2 = dev_upload(c, plan->grp_items, items2))) return rc2;
             n_groups = (int64_t)first2.size();
+            scan_max_items = *std::max_element(items2.begin(), items2.end());
             return BI_OK;
         };
         if (split) {
@@ -1250,6 +1253,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
             plan->valid_nslots = (int)waves_per_group((int64_t)n_tiles * (kTile / 64), scan_resident_blocks(true, 4, NS),
                                                       (int64_t)1 << 40);       // (the pass keeps no per-wave partial sums)
             c->last_valid_nslots = plan->valid_nslots;
+            plan->max_group_items = scan_max_items;
             plan->launches += 1;
             if ((e = hipGetLastError()) != hipSuccess) return abort_plan(fail(c, BI_ERR_HIP, "device planning groups: %s", hipGetErrorString(e)));
         }
@@ -1274,6 +1278,7 @@ int plan_points_device(bi_ctx* c, int64_t P, const double* z, const double* rate
             k.nbx = (int)waves_per_group(max_tiles * (kTile / (16 * strip_cb)), resident, slot_cap, plan->by_count);
             c->last_scan_nslots = k.nbx;
             c->last_scan_resident = resident;
+            plan->max_group_items = scan_max_items;
             dev_free(k.partial);
             dev_free(k.pflags);                     // the scan kernel raises no per-block flags (k_finish_scan reads none)
             if ((rc = dev_alloc(c, k.partial, ni * k.nbx * kDevG * sizeof(double)))) return abort_plan(rc);

@@ -582,6 +582,10 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
             EventScope ev(c);
             ++c->n_scan_launches;
             const dim3 sgrid((unsigned)(k.nbx / 4), (unsigned)plan->n_groups);
+            c->last_scan_groups = plan->n_groups; c->last_scan_max_items = plan->max_group_items;
+            c->last_scan_cb = plan->by_count ? 4 : (plan->scan_cb == 2 ? 2 : 4);
+            c->last_scan_by_count = plan->by_count ? 1 : 0;
+            c->last_scan_prod = 0;                  // (launch_scan_mfma sets it where it takes the PROD = 1 instantiation)
             if (plan->by_count) {
                 // rows ordered by count (all bins of dense data, or the compacted non-empty bins): 64-bin strips, four items at a time
                 sa.n_groups = (int)plan->n_groups;
@@ -672,6 +676,7 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
         {
             EventScope ev(c);
             ++c->n_valid_launches;
+            c->last_scan_groups = plan->n_groups; c->last_scan_max_items = plan->max_group_items;
             const dim3 vgrid((unsigned)(plan->valid_nslots / 4), (unsigned)plan->n_groups);
             launch_scan_valid(c, NS, vgrid, va);
         }

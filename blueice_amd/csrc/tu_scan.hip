@@ -8,6 +8,7 @@ void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 sgrid, const Sc
 #define BI_SCAN(CB, KG)                                                                                           \
     do {                                                                                                          \
         if (CB == 2 && prod) { /* compacted rows in bin order: blocks of counts 1 and 2 take the logarithm of the product mu^n */ \
+            c->last_scan_prod = 1;                                                                                \
             if (NS == 4 * KG) hipLaunchKernelGGL((k_scan_mfma<2, KG, false, 1>), sgrid, dim3(kThreads), 0, c->stream, sa); \
             else hipLaunchKernelGGL((k_scan_mfma<2, KG, true, 1>), sgrid, dim3(kThreads), 0, c->stream, sa);     \
         } else if (NS == 4 * KG) hipLaunchKernelGGL((k_scan_mfma<CB, KG, false>), sgrid, dim3(kThreads), 0, c->stream, sa); \

@@ -659,6 +659,12 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it);
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
  *            the last plan, and the resident blocks per CU it sized them by), last_toy_method (1 = event by event);
+ *            last_scan_groups / last_scan_max_items (groups of work items of the last scan LAUNCH and the items of the longest
+ *            one, after long item lists were cut into groups of their own: scan_chunk; the validity pass of a split scan sets
+ *            these two as well), last_scan_cb (strip width of the last matrix-core scan launch in 16-bin blocks: 2 or 4),
+ *            last_scan_by_count (1: the kernel for rows in count order took it), last_scan_prod (1: the product form for compacted
+ *            rows in bin order did) -- all five are set when a plan runs, so a plan run again describes itself, whereas
+ *            last_scan_nslots / last_valid_nslots / last_scan_resident are set when a plan is made;
  *   single_calls, single_ns_host, single_ns_launch, single_ns_wait   wall time (ns, summed over single_calls calls) of
  *                     bi_eval(P = 1): host half (geometry, rates, descriptors), launch calls, wait for the result */
 int bi_set_param(bi_ctx* ctx, const char* name, int64_t value);   /* unknown or read-only name: BI_ERR_INVALID */
