@@ -53,6 +53,7 @@ SIGNATURES = {
     'bi_download_events': (C.c_int, [_p, _p, _p]),
     'bi_simulated_event_count': (_i64, [_p]),
     'bi_generate_toys': (C.c_int, [_p, _p, _p, _i64, C.c_uint64]),
+    'bi_generate_toys_points': (C.c_int, [_p, _i64, _p, _p, _p, C.c_uint64, _p]),
     'bi_download_counts': (C.c_int, [_p, _i64, _p]),
     'bi_eval': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p]),
     'bi_eval_grad': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),

@@ -838,9 +838,22 @@ __global__ void k_exp_neg(const double* __restrict__ mu, int64_t n, double* __re
     if (i < n) p0[i] = exp(-mu[i]);
 }
 
-__global__ __launch_bounds__(kThreads) void k_toy_count(const double* __restrict__ mu, const double* __restrict__ p0, int64_t B,
-                                                        uint64_t seed, int64_t t0, int32_t* __restrict__ cnt, int nchunks) {
-    const int64_t t = t0 + blockIdx.y;
+// A toy of a generator call: its number in the call (toy_offset + t is its number in the seed's ensemble) and the truth point
+// it is drawn at.  The kernels below run over one method group of a call (the toys whose truth is drawn bin by bin, or event by
+// event), blockIdx / thread i of a launch taking ref[i]; the entry is uniform over a block, so the loads stay scalar.  mu, p0
+// (rows of stride Bp) and cdf (rows of stride B), M and npow2 are tables over the truths of the call.
+struct ToyRef {
+    int32_t t;
+    int32_t h;
+};
+
+__global__ __launch_bounds__(kThreads) void k_toy_count(const double* __restrict__ mu, const double* __restrict__ p0, int64_t Bp,
+                                                        int64_t B, uint64_t seed, int64_t toy0, const ToyRef* __restrict__ ref,
+                                                        int32_t* __restrict__ cnt, int nchunks) {
+    const ToyRef r = ref[blockIdx.y];
+    const int64_t t = toy0 + r.t;
+    mu += (int64_t)r.h * Bp;
+    p0 += (int64_t)r.h * Bp;
     const int64_t b0 = (int64_t)blockIdx.x * kNzChunk + threadIdx.x * kNzPerThread;
     int k = 0;
 #pragma unroll 1
@@ -857,12 +870,15 @@ __global__ __launch_bounds__(kThreads) void k_toy_count(const double* __restrict
     if (threadIdx.x == 0) cnt[(int64_t)blockIdx.y * nchunks + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
-__global__ __launch_bounds__(kThreads) void k_toy_scatter(const double* __restrict__ mu, const double* __restrict__ p0, int64_t B,
-                                                          uint64_t seed, int64_t t0,
+__global__ __launch_bounds__(kThreads) void k_toy_scatter(const double* __restrict__ mu, const double* __restrict__ p0, int64_t Bp,
+                                                          int64_t B, uint64_t seed, int64_t toy0, const ToyRef* __restrict__ ref,
                                                           const int64_t* __restrict__ chunk_off, int nchunks,
                                                           int32_t* __restrict__ nz_idx, double* __restrict__ nz_n,
                                                           double* __restrict__ lg_partial) {
-    const int64_t t = t0 + blockIdx.y;
+    const ToyRef r = ref[blockIdx.y];
+    const int64_t t = toy0 + r.t;
+    mu += (int64_t)r.h * Bp;
+    p0 += (int64_t)r.h * Bp;
     const int64_t b0 = (int64_t)blockIdx.x * kNzChunk + threadIdx.x * kNzPerThread;
     double v[kNzPerThread];
     int k = 0;
@@ -900,6 +916,16 @@ __global__ __launch_bounds__(kThreads) void k_toy_scatter(const double* __restri
     if (threadIdx.x == 0) lg_partial[(int64_t)blockIdx.y * nchunks + blockIdx.x] = shl[0] + shl[1] + shl[2] + shl[3];
 }
 
+// lgsum of the toys of the bin-by-bin group: k_rows_sum's left-to-right sum over a toy's chunks, stored at the toy's number
+__global__ void k_toy_lgsum(const double* __restrict__ lg_partial, int nchunks, const ToyRef* __restrict__ ref, int64_t n,
+                            double* __restrict__ lgsum) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double s = 0.0;
+    for (int q = 0; q < nchunks; ++q) s += lg_partial[i * nchunks + q];
+    lgsum[ref[i].t] = s;
+}
+
 // ---- toy-MC generation, event by event (sparse expectations) ----------------------------------------------------
 // Independent n_b ~ Poisson(mu_b) is the same law as N ~ Poisson(M = sum_b mu_b) events thrown onto the bins with
 // probabilities mu_b / M.  Where M << B (10^4 expected events in 10^6 bins at C2) that is 100 times fewer random numbers
@@ -919,21 +945,31 @@ __device__ __forceinline__ int toy_event_count(double M, uint64_t seed, int64_t 
 }
 
 // events per toy (an upper bound of its non-empty bins: the room it gets in the provisional lists)
-__global__ void k_toy_event_counts(double M, uint64_t seed, int64_t t0, int64_t T, int npow2, int64_t* __restrict__ n_ev,
-                                   int* __restrict__ overflow) {
+// (overflow: one word per truth -- a toy beyond its truth's sort buffer sends that truth to the bin-by-bin group)
+__global__ void k_toy_event_counts(const double* __restrict__ Mtab, const int* __restrict__ npow2tab, uint64_t seed, int64_t toy0,
+                                   const ToyRef* __restrict__ ref, int64_t T, int64_t* __restrict__ n_ev, int* __restrict__ overflow) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > T) return;
     if (i == T) { n_ev[i] = 0; return; }
-    const int n = toy_event_count(M, seed, t0 + i);
-    if (n > npow2) atomicOr(overflow, 1);
+    const ToyRef r = ref[i];
+    const int npow2 = npow2tab[r.h];
+    const int n = toy_event_count(Mtab[r.h], seed, toy0 + r.t);
+    if (n > npow2) atomicOr(overflow + r.h, 1);
     n_ev[i] = min(n, npow2);
 }
 
-__global__ __launch_bounds__(kEvThreads) void k_toy_events(const double* __restrict__ cdf, int64_t B, double M, uint64_t seed,
-                                                           int64_t t0, int npow2, const int64_t* __restrict__ room_off,
+// (nnz_out runs over the group like room_off; lgsum over the toys of the call)
+__global__ __launch_bounds__(kEvThreads) void k_toy_events(const double* __restrict__ cdf, int64_t B, const double* __restrict__ Mtab,
+                                                           const int* __restrict__ npow2tab, uint64_t seed, int64_t toy0,
+                                                           const ToyRef* __restrict__ ref, const int64_t* __restrict__ room_off,
                                                            int32_t* __restrict__ idx_out, double* __restrict__ n_out,
                                                            int64_t* __restrict__ nnz_out, double* __restrict__ lgsum) {
-    // LDS: radix sort (npow2 <= 16384): two key buffers of npow2 and 16 x 512 counters; bitonic sort: one key buffer;
+    const ToyRef tr = ref[blockIdx.x];
+    const double M = Mtab[tr.h];
+    const int npow2 = npow2tab[tr.h];
+    cdf += (int64_t)tr.h * B;
+    // LDS (sized for the truth of the call that needs most, laid out by this toy's own npow2):
+    // radix sort (npow2 <= 16384): two key buffers of npow2 and 16 x 512 counters; bitonic sort: one key buffer;
     // then kEvThreads ints and doubles of scratch
     extern __shared__ uint32_t s_keys[];
     const bool radix = npow2 <= 16384;
@@ -943,7 +979,7 @@ __global__ __launch_bounds__(kEvThreads) void k_toy_events(const double* __restr
     int* s_scan = reinterpret_cast<int*>(s_keys + (radix ? 2 * n_alloc + 16 * kEvThreads / 2 : n_alloc));
     double* s_lg = reinterpret_cast<double*>(s_scan + kEvThreads);
     __shared__ int s_N;
-    const int64_t t = t0 + blockIdx.x;
+    const int64_t t = toy0 + tr.t;
     const int tid = threadIdx.x;
     if (tid == 0) s_N = min(toy_event_count(M, seed, t), npow2);
     __syncthreads();
@@ -1050,7 +1086,7 @@ __global__ __launch_bounds__(kEvThreads) void k_toy_events(const double* __restr
     if (tid == 0) {
         double tot = 0.0;
         for (int q = 0; q < kEvThreads; ++q) tot += s_lg[q];
-        lgsum[blockIdx.x] = tot;
+        lgsum[tr.t] = tot;
         int nn = 0;
         for (int q = 0; q < kEvThreads; ++q) nn += s_scan[q];
         nnz_out[blockIdx.x] = nn;
@@ -1058,11 +1094,12 @@ __global__ __launch_bounds__(kEvThreads) void k_toy_events(const double* __restr
 }
 
 // the provisional lists (room for one entry per EVENT) packed into the final ones (one entry per non-empty bin)
-__global__ __launch_bounds__(kThreads) void k_toy_pack(const int64_t* __restrict__ room_off, const int64_t* __restrict__ nz_off,
+__global__ __launch_bounds__(kThreads) void k_toy_pack(const ToyRef* __restrict__ ref, const int64_t* __restrict__ room_off,
+                                                       const int64_t* __restrict__ nz_off,
                                                        const int32_t* __restrict__ idx_in, const double* __restrict__ n_in,
                                                        int32_t* __restrict__ nz_idx, double* __restrict__ nz_n) {
-    const int64_t t = blockIdx.x;
-    const int64_t src = room_off[t], dst = nz_off[t], n = nz_off[t + 1] - dst;
+    const int64_t t = ref[blockIdx.x].t;
+    const int64_t src = room_off[blockIdx.x], dst = nz_off[t], n = nz_off[t + 1] - dst;
     for (int64_t j = threadIdx.x; j < n; j += kThreads) { nz_idx[dst + j] = idx_in[src + j]; nz_n[dst + j] = n_in[src + j]; }
 }
 

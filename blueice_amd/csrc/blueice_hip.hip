@@ -1127,176 +1127,251 @@ int bi_eval_datasets_device(bi_ctx* c, const double* z, const double* rate_scale
 
 // ---- toy-MC generation -------------------------------------------------------------------------
 
-// bi_generate_toys: the non-empty-bin lists (nz_*, lgsum) of T toys at the point with geometry g and rates r; its scratch is
-// back in the recycle cache when it returns
-static int draw_toy_lists(bi_ctx* c, const PointGeom& g, const std::vector<double>& r, int64_t T, uint64_t seed) {
+// a truth point of a generator call: its place on the anchor grid and its rates
+struct ToyTruth {
+    PointGeom g;
+    std::vector<double> r;
+};
+
+// The generator: the non-empty-bin lists (nz_*, lgsum) of T = sum n_toys toys, n_toys[h] of them at truth h, truth-major; toy t
+// of the call is toy toy_offset + t of the seed's ensemble.  Every truth picks its own method (meth: 1 = event by event, 0 = bin
+// by bin, -1 = no toys), which splits the toys into at most two groups; from the draws onward each group is one set of launches
+// and the scans and read-backs run once, whatever the number of truths.  The scratch is back in the recycle cache on return.
+static int draw_toy_lists(bi_ctx* c, const std::vector<ToyTruth>& truths, const int64_t* n_toys, int64_t T, uint64_t seed,
+                          std::vector<int32_t>& meth) {
     int rc;
-    const int nc = (int)g.w.size(), NS = nc * c->S;
-    std::vector<int64_t> rowoff((size_t)NS);
-    std::vector<double> coef((size_t)NS);
-    int k = 0;
-    for (int corner = 0; corner < nc; ++corner)
-        for (int s = 0; s < c->S; ++s) {
-            rowoff[(size_t)k] = ((g.cell_anchor + corner_offset(c, corner)) * c->S + s) * c->Bp;
-            coef[(size_t)k++] = g.w[(size_t)corner] * r[(size_t)s];
-        }
+    const int64_t H = (int64_t)truths.size(), B = c->B, Bp = c->Bp;
+    std::vector<int64_t> rowoff, first_row((size_t)H + 1, 0), first_toy((size_t)H + 1, 0);
+    std::vector<double> coef;
+    for (int64_t h = 0; h < H; ++h) {
+        const PointGeom& g = truths[(size_t)h].g;
+        for (int corner = 0; corner < (int)g.w.size(); ++corner)
+            for (int s = 0; s < c->S; ++s) {
+                rowoff.push_back(((g.cell_anchor + corner_offset(c, corner)) * c->S + s) * Bp);
+                coef.push_back(g.w[(size_t)corner] * truths[(size_t)h].r[(size_t)s]);
+            }
+        first_row[(size_t)h + 1] = (int64_t)rowoff.size();
+        first_toy[(size_t)h + 1] = first_toy[(size_t)h] + n_toys[h];
+    }
     const int n_tiles = n_tiles_of(c);
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
     const int nmu = (int)std::min<int64_t>(n_tiles, slots);
-    const int64_t B = c->B;
     const int nchunks = (int)((B + kNzChunk - 1) / kNzChunk);
-    ScratchBuf d_row, d_coef, d_cnt, d_off, d_lgp, d_p0;
+    ScratchBuf d_row, d_coef, d_mu, d_p0;
     if ((rc = dev_upload(c, d_row, rowoff)) || (rc = dev_upload(c, d_coef, coef)) ||
-        (rc = dev_alloc(c, c->logmu, (size_t)c->Bp * sizeof(double))) || (rc = dev_alloc(c, d_p0, (size_t)c->Bp * sizeof(double))) ||
+        (rc = dev_alloc(c, d_mu, (size_t)H * Bp * sizeof(double))) ||
+        (rc = dev_alloc(c, d_p0, (size_t)H * Bp * sizeof(double))) ||
         (rc = dev_alloc(c, c->scratch, (size_t)nmu * sizeof(double) + (size_t)nmu * sizeof(unsigned) + 64)) ||
-        (rc = dev_alloc(c, d_cnt, (size_t)T * nchunks * sizeof(int32_t))) ||
-        (rc = dev_alloc(c, d_lgp, (size_t)T * nchunks * sizeof(double))) || (rc = dev_alloc(c, c->lgsum, (size_t)T * sizeof(double)))) return rc;
+        (rc = dev_alloc(c, c->lgsum, (size_t)T * sizeof(double)))) return rc;
     LaunchArgs a{};
     a.ps = (const double*)c->ps.p;
-    a.rowoff = (const int64_t*)d_row.p;
-    a.coef = (const double*)d_coef.p;
     a.partial = (double*)c->scratch.p;
     a.pflags = (unsigned*)((char*)c->scratch.p + (((size_t)nmu * sizeof(double) + 63) / 64) * 64);
-    a.B = c->B; a.Bp = c->Bp; a.n0 = NS; a.n_tiles = n_tiles;
-    hipLaunchKernelGGL(k_morph_logmu, dim3((unsigned)nmu), dim3(kThreads), 0, c->stream, a, (double*)c->logmu.p, 1);
-    const double* mu = (const double*)c->logmu.p;
+    a.B = B; a.Bp = Bp; a.n_tiles = n_tiles;
+    const double* mu = (const double*)d_mu.p;
     const double* p0 = (const double*)d_p0.p;
-    hipLaunchKernelGGL(k_exp_neg, dim3((unsigned)((c->Bp + 255) / 256)), dim3(256), 0, c->stream, mu, c->Bp, (double*)d_p0.p);
+    for (int64_t h = 0; h < H; ++h) {
+        a.rowoff = (const int64_t*)d_row.p + first_row[(size_t)h];
+        a.coef = (const double*)d_coef.p + first_row[(size_t)h];
+        a.n0 = (int)(first_row[(size_t)h + 1] - first_row[(size_t)h]);
+        hipLaunchKernelGGL(k_morph_logmu, dim3((unsigned)nmu), dim3(kThreads), 0, c->stream, a, (double*)d_mu.p + h * Bp, 1);
+    }
+    hipLaunchKernelGGL(k_exp_neg, dim3((unsigned)((H * Bp + 255) / 256)), dim3(256), 0, c->stream, mu, H * Bp, (double*)d_p0.p);
     // Sparse expectations (M = sum mu << B, templates and rates >= 0): event by event -- N ~ Poisson(M), the bins by bisection
-    // in the cumulative sums, sorted and run-length encoded per toy (k_toy_events); else one draw per bin.
-    c->last_toy_method = 0;
+    // in the cumulative sums, sorted and run-length encoded per toy (k_toy_events); else one draw per bin.  M, the sort
+    // buffer npow2 and with them the choice are each truth's own.
+    meth.assign((size_t)H, 0);
+    for (int64_t h = 0; h < H; ++h) if (n_toys[h] == 0) meth[(size_t)h] = -1;
+    std::vector<double> Mh((size_t)H, 0.0);
+    std::vector<int> np2((size_t)H, 1024), ovf((size_t)H, 0);
+    std::vector<ToyRef> refA, refB;
+    int64_t n_events = 0;
+    ScratchBuf d_cdf, d_tmp, d_M, d_np2, d_ovf, d_refA, d_refB, d_nev, d_room, d_nnz, d_tidx, d_tn, d_cnt, d_off, d_lgp;
+    hipError_t e;
     if (c->toy_events && c->ps_nonneg && B >= 4096) {
-        ScratchBuf d_cdf, d_tmp, d_nev, d_room, d_nnz, d_ovf, d_tidx, d_tn;
         size_t sb1 = 0, sb2 = 0;
         (void)prim_inclusive_scan_sum(nullptr, sb1, (const double*)nullptr, (double*)nullptr, (size_t)B, c->stream);
         (void)prim_exclusive_scan_sum(nullptr, sb2, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(T + 1), c->stream);
-        if ((rc = dev_alloc(c, d_cdf, (size_t)B * sizeof(double))) || (rc = dev_alloc(c, d_tmp, std::max<size_t>({sb1, sb2, 256}))) ||
-            (rc = dev_alloc(c, d_ovf, 64))) return rc;
-        size_t tb = d_tmp.bytes;
-        hipError_t e = prim_inclusive_scan_sum(d_tmp.p, tb, mu, (double*)d_cdf.p, (size_t)B, c->stream);
-        double M = 0.0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&M, (const double*)d_cdf.p + (B - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_ovf.p, 0, 64, c->stream);
+        if ((rc = dev_alloc(c, d_cdf, (size_t)H * B * sizeof(double))) || (rc = dev_alloc(c, d_tmp, std::max<size_t>({sb1, sb2, 256})))) return rc;
+        e = hipSuccess;
+        for (int64_t h = 0; h < H && e == hipSuccess; ++h) {       // (one scan per row: its tree order is part of the stream)
+            size_t tb = d_tmp.bytes;
+            e = prim_inclusive_scan_sum(d_tmp.p, tb, mu + h * Bp, (double*)d_cdf.p + h * B, (size_t)B, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(&Mh[(size_t)h], (const double*)d_cdf.p + h * B + (B - 1), sizeof(double), hipMemcpyDeviceToHost, c->stream);
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (cumulative sums): %s", hipGetErrorString(e));
-        const double bound = M + 12.0 * std::sqrt(std::max(M, 1.0)) + 32.0;
-        int npow2 = 1024;
-        while (npow2 < bound && npow2 < 65536) npow2 <<= 1;
-        if (M > 0.0 && M == M && M < (double)B / 8.0 && npow2 <= 32768) {
-            const size_t lds = (npow2 <= 16384 ? (size_t)2 * npow2 * sizeof(uint32_t) + 16 * kEvThreads * sizeof(uint16_t)
-                                               : (size_t)npow2 * sizeof(uint32_t)) + kEvThreads * (sizeof(int) + sizeof(double)) + 64;
-            if ((e = hipFuncSetAttribute((const void*)k_toy_events, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (LDS size of the event kernel): %s", hipGetErrorString(e));
-            if ((rc = dev_alloc(c, d_nev, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, d_room, (size_t)(T + 1) * sizeof(int64_t))) ||
-                (rc = dev_alloc(c, d_nnz, (size_t)(T + 1) * sizeof(int64_t))) || (rc = dev_alloc(c, c->nz_off, (size_t)(T + 1) * sizeof(int64_t)))) return rc;
-            // (1) events per toy -> room in the provisional lists
-            hipLaunchKernelGGL(k_toy_event_counts, dim3((unsigned)((T + 1 + 255) / 256)), dim3(256), 0, c->stream, M, seed, c->toy_offset, T,
-                               npow2, (int64_t*)d_nev.p, (int*)d_ovf.p);
-            tb = d_tmp.bytes;
-            e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_nev.p, (int64_t*)d_room.p, (int64_t)0, (size_t)(T + 1), c->stream);
-            int64_t n_events = 0;
-            int ovf = 0;
-            if (e == hipSuccess) e = hipMemcpyAsync(&n_events, (const int64_t*)d_room.p + T, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(&ovf, d_ovf.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-            if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events per toy): %s", hipGetErrorString(e));
-            if (!ovf) {
-                if ((rc = dev_alloc(c, d_tidx, (size_t)std::max<int64_t>(n_events, 1) * sizeof(int32_t))) ||
-                    (rc = dev_alloc(c, d_tn, (size_t)std::max<int64_t>(n_events, 1) * sizeof(double)))) return rc;
-                // (2) one block per toy: events -> sorted bins -> (bin, count) runs, written into the toy's room
-                const int64_t tchunk_ev = 65535;
-                for (int64_t t0 = 0; t0 < T; t0 += tchunk_ev) {
-                    const int64_t n = std::min(tchunk_ev, T - t0);
-                    hipLaunchKernelGGL(k_toy_events, dim3((unsigned)n), dim3(kEvThreads), lds, c->stream, (const double*)d_cdf.p, B, M, seed,
-                                       t0 + c->toy_offset, npow2, (const int64_t*)d_room.p + t0, (int32_t*)d_tidx.p, (double*)d_tn.p,
-                                       (int64_t*)d_nnz.p + t0, (double*)c->lgsum.p + t0);
-                }
-                // (3) non-empty bins per toy -> final offsets; pack
-                e = hipMemsetAsync((int64_t*)d_nnz.p + T, 0, sizeof(int64_t), c->stream);
-                tb = d_tmp.bytes;
-                if (e == hipSuccess) e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_nnz.p, (int64_t*)c->nz_off.p, (int64_t)0, (size_t)(T + 1), c->stream);
-                c->h_nz_off.assign((size_t)T + 1, 0);
-                if (e == hipSuccess) e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(c->h_nz_off.data(), c->nz_off.p, (size_t)(T + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events): %s", hipGetErrorString(e));
-                const int64_t run = c->h_nz_off[(size_t)T];
-                if ((rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
-                    (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double)))) return rc;
-                for (int64_t t0 = 0; t0 < T; t0 += tchunk_ev) {
-                    const int64_t n = std::min(tchunk_ev, T - t0);
-                    hipLaunchKernelGGL(k_toy_pack, dim3((unsigned)n), dim3(kThreads), 0, c->stream, (const int64_t*)d_room.p + t0,
-                                       (const int64_t*)c->nz_off.p + t0, (const int32_t*)d_tidx.p, (const double*)d_tn.p,
-                                       (int32_t*)c->nz_idx.p, (double*)c->nz_n.p);
-                }
-                c->h_lgsum.assign((size_t)T, 0.0);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(c->h_lgsum.data(), c->lgsum.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events, pack): %s", hipGetErrorString(e));
-                c->last_toy_method = 1;
-                return BI_OK;
-            }
+        for (int64_t h = 0; h < H; ++h) {
+            const double M = Mh[(size_t)h];
+            const double bound = M + 12.0 * std::sqrt(std::max(M, 1.0)) + 32.0;
+            int npow2 = 1024;
+            while (npow2 < bound && npow2 < 65536) npow2 <<= 1;
+            np2[(size_t)h] = npow2;
+            if (n_toys[h] > 0 && M > 0.0 && M == M && M < (double)B / 8.0 && npow2 <= 32768) meth[(size_t)h] = 1;
         }
-    }                      // not sparse enough, or a toy beyond the sort buffer (12 sigma): one draw per bin below, without that scratch
-    const int64_t tchunk = 32768;
-    for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
-        const int64_t n = std::min(tchunk, T - t0);
-        hipLaunchKernelGGL(k_toy_count, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream, mu, p0, B, seed,
-                           t0 + c->toy_offset, (int32_t*)d_cnt.p + t0 * nchunks, nchunks);
     }
-    std::vector<int32_t> h_cnt((size_t)T * nchunks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    // (1) the two groups; events per toy of the event group -> room in the provisional lists.  A toy beyond its truth's sort
+    // buffer (12 sigma) sends that truth to the bin-by-bin group and the round is made again without it (once at the most:
+    // the truths that stay had no such toy).
+    for (;;) {
+        refA.clear();
+        refB.clear();
+        for (int64_t h = 0; h < H; ++h)
+            for (int64_t j = 0; j < n_toys[h]; ++j)
+                (meth[(size_t)h] == 1 ? refB : refA).push_back(ToyRef{(int32_t)(first_toy[(size_t)h] + j), (int32_t)h});
+        if (refB.empty()) break;
+        const int64_t nB = (int64_t)refB.size();
+        if ((rc = dev_upload(c, d_refB, refB)) || (rc = dev_upload(c, d_M, Mh)) || (rc = dev_upload(c, d_np2, np2)) ||
+            (rc = dev_alloc(c, d_ovf, (size_t)H * sizeof(int))) || (rc = dev_alloc(c, d_nev, (size_t)(nB + 1) * sizeof(int64_t))) ||
+            (rc = dev_alloc(c, d_room, (size_t)(nB + 1) * sizeof(int64_t)))) return rc;
+        e = hipMemsetAsync(d_ovf.p, 0, (size_t)H * sizeof(int), c->stream);
+        hipLaunchKernelGGL(k_toy_event_counts, dim3((unsigned)((nB + 1 + 255) / 256)), dim3(256), 0, c->stream, (const double*)d_M.p,
+                           (const int*)d_np2.p, seed, c->toy_offset, (const ToyRef*)d_refB.p, nB, (int64_t*)d_nev.p, (int*)d_ovf.p);
+        size_t tb = d_tmp.bytes;
+        if (e == hipSuccess) e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_nev.p, (int64_t*)d_room.p, (int64_t)0, (size_t)(nB + 1), c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(&n_events, (const int64_t*)d_room.p + nB, sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ovf.data(), d_ovf.p, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (events per toy): %s", hipGetErrorString(e));
+        bool again = false;
+        for (int64_t h = 0; h < H; ++h)
+            if (ovf[(size_t)h]) { meth[(size_t)h] = 0; again = true; }
+        if (!again) break;
+    }
+    const int64_t nA = (int64_t)refA.size(), nB = (int64_t)refB.size();
+    // (2) event group: one block per toy: events -> sorted bins -> (bin, count) runs, written into the toy's room;
+    //     bin-by-bin group: the non-empty bins per chunk of every toy
+    const int64_t tchunk_ev = 65535, tchunk = 32768;
+    std::vector<int64_t> h_nnz((size_t)nB, 0);
+    std::vector<int32_t> h_cnt((size_t)nA * nchunks);
+    e = hipSuccess;
+    if (nB) {
+        size_t lds = 0;
+        for (int64_t h = 0; h < H; ++h) {
+            if (meth[(size_t)h] != 1) continue;
+            const int npow2 = np2[(size_t)h];
+            lds = std::max(lds, (npow2 <= 16384 ? (size_t)2 * npow2 * sizeof(uint32_t) + 16 * kEvThreads * sizeof(uint16_t)
+                                                : (size_t)npow2 * sizeof(uint32_t)) + kEvThreads * (sizeof(int) + sizeof(double)) + 64);
+        }
+        if ((e = hipFuncSetAttribute((const void*)k_toy_events, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (LDS size of the event kernel): %s", hipGetErrorString(e));
+        if ((rc = dev_alloc(c, d_tidx, (size_t)std::max<int64_t>(n_events, 1) * sizeof(int32_t))) ||
+            (rc = dev_alloc(c, d_tn, (size_t)std::max<int64_t>(n_events, 1) * sizeof(double))) ||
+            (rc = dev_alloc(c, d_nnz, (size_t)nB * sizeof(int64_t)))) return rc;
+        for (int64_t g0 = 0; g0 < nB; g0 += tchunk_ev) {
+            const int64_t n = std::min(tchunk_ev, nB - g0);
+            hipLaunchKernelGGL(k_toy_events, dim3((unsigned)n), dim3(kEvThreads), lds, c->stream, (const double*)d_cdf.p, B,
+                               (const double*)d_M.p, (const int*)d_np2.p, seed, c->toy_offset, (const ToyRef*)d_refB.p + g0,
+                               (const int64_t*)d_room.p + g0, (int32_t*)d_tidx.p, (double*)d_tn.p, (int64_t*)d_nnz.p + g0,
+                               (double*)c->lgsum.p);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_nnz.data(), d_nnz.p, (size_t)nB * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    }
+    if (nA && e == hipSuccess) {
+        if ((rc = dev_upload(c, d_refA, refA)) || (rc = dev_alloc(c, d_cnt, (size_t)nA * nchunks * sizeof(int32_t))) ||
+            (rc = dev_alloc(c, d_lgp, (size_t)nA * nchunks * sizeof(double)))) return rc;
+        for (int64_t g0 = 0; g0 < nA; g0 += tchunk) {
+            const int64_t n = std::min(tchunk, nA - g0);
+            hipLaunchKernelGGL(k_toy_count, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream, mu, p0, Bp, B, seed,
+                               c->toy_offset, (const ToyRef*)d_refA.p + g0, (int32_t*)d_cnt.p + g0 * nchunks, nchunks);
+        }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt.data(), d_cnt.p, h_cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy count: %s", hipGetErrorString(e));
-    std::vector<int64_t> h_off(h_cnt.size());
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (non-empty bins per toy): %s", hipGetErrorString(e));
+    // (3) non-empty bins per toy -> the offsets of all T lists, in toy order; scatter and pack
     c->h_nz_off.assign((size_t)T + 1, 0);
-    int64_t run = 0;
-    for (int64_t t = 0; t < T; ++t) {
-        c->h_nz_off[(size_t)t] = run;
-        for (int q = 0; q < nchunks; ++q) { h_off[(size_t)t * nchunks + q] = run; run += h_cnt[(size_t)t * nchunks + q]; }
+    for (int64_t i = 0; i < nB; ++i) c->h_nz_off[(size_t)refB[(size_t)i].t + 1] = h_nnz[(size_t)i];
+    for (int64_t i = 0; i < nA; ++i) {
+        int64_t len = 0;
+        for (int q = 0; q < nchunks; ++q) len += h_cnt[(size_t)i * nchunks + q];
+        c->h_nz_off[(size_t)refA[(size_t)i].t + 1] = len;
     }
-    c->h_nz_off[(size_t)T] = run;
-    if ((rc = dev_upload(c, d_off, h_off)) || (rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
+    for (int64_t t = 0; t < T; ++t) c->h_nz_off[(size_t)t + 1] += c->h_nz_off[(size_t)t];
+    const int64_t run = c->h_nz_off[(size_t)T];
+    std::vector<int64_t> h_off(h_cnt.size());
+    for (int64_t i = 0; i < nA; ++i) {
+        int64_t at = c->h_nz_off[(size_t)refA[(size_t)i].t];
+        for (int q = 0; q < nchunks; ++q) { h_off[(size_t)i * nchunks + q] = at; at += h_cnt[(size_t)i * nchunks + q]; }
+    }
+    if ((rc = dev_alloc(c, c->nz_idx, (size_t)std::max<int64_t>(run, 1) * sizeof(int32_t))) ||
         (rc = dev_alloc(c, c->nz_n, (size_t)std::max<int64_t>(run, 1) * sizeof(double))) || (rc = dev_upload(c, c->nz_off, c->h_nz_off))) return rc;
-    for (int64_t t0 = 0; t0 < T; t0 += tchunk) {
-        const int64_t n = std::min(tchunk, T - t0);
-        hipLaunchKernelGGL(k_toy_scatter, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream, mu, p0, B, seed,
-                           t0 + c->toy_offset, (const int64_t*)d_off.p + t0 * nchunks, nchunks, (int32_t*)c->nz_idx.p, (double*)c->nz_n.p,
-                           (double*)d_lgp.p + t0 * nchunks);
-        hipLaunchKernelGGL(k_rows_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                           (const double*)d_lgp.p + t0 * nchunks, nchunks, (double*)c->lgsum.p + t0, n);
+    if (nA) {
+        if ((rc = dev_upload(c, d_off, h_off))) return rc;
+        for (int64_t g0 = 0; g0 < nA; g0 += tchunk) {
+            const int64_t n = std::min(tchunk, nA - g0);
+            hipLaunchKernelGGL(k_toy_scatter, dim3((unsigned)nchunks, (unsigned)n), dim3(kThreads), 0, c->stream, mu, p0, Bp, B, seed,
+                               c->toy_offset, (const ToyRef*)d_refA.p + g0, (const int64_t*)d_off.p + g0 * nchunks, nchunks,
+                               (int32_t*)c->nz_idx.p, (double*)c->nz_n.p, (double*)d_lgp.p + g0 * nchunks);
+        }
+        hipLaunchKernelGGL(k_toy_lgsum, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, c->stream, (const double*)d_lgp.p, nchunks,
+                           (const ToyRef*)d_refA.p, nA, (double*)c->lgsum.p);
+    }
+    for (int64_t g0 = 0; g0 < nB; g0 += tchunk_ev) {
+        const int64_t n = std::min(tchunk_ev, nB - g0);
+        hipLaunchKernelGGL(k_toy_pack, dim3((unsigned)n), dim3(kThreads), 0, c->stream, (const ToyRef*)d_refB.p + g0,
+                           (const int64_t*)d_room.p + g0, (const int64_t*)c->nz_off.p, (const int32_t*)d_tidx.p, (const double*)d_tn.p,
+                           (int32_t*)c->nz_idx.p, (double*)c->nz_n.p);
     }
     c->h_lgsum.assign((size_t)T, 0.0);
     e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c->h_lgsum.data(), c->lgsum.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy scatter: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "toy generation (lists): %s", hipGetErrorString(e));
+    c->last_toy_method = nB > 0 && nA == 0;
     return BI_OK;
 }
 
-int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64_t T, uint64_t seed) {
+// the generator's entry: every truth is validated before the context changes; `one`: bi_generate_toys' messages
+static int generate_toys_impl(bi_ctx* c, int64_t H, const double* z, const double* rate_scale, const int64_t* n_toys, uint64_t seed,
+                              int32_t* method_out, bool one) {
     int rc = check_ready(c, false);
     if (rc) return rc;
+    if (H < 1 || !n_toys) return fail(c, BI_ERR_INVALID, "need H >= 1 truth points and their numbers of toys");
+    int64_t T = 0;
+    for (int64_t h = 0; h < H; ++h) {
+        if (n_toys[h] < 0 && one) break;
+        if (n_toys[h] < 0) return fail(c, BI_ERR_INVALID, "n_toys[%lld] = %lld is negative", (long long)h, (long long)n_toys[h]);
+        if (n_toys[h] > INT32_MAX - T) return fail(c, BI_ERR_INVALID, "a call draws fewer than 2^31 toys");
+        T += n_toys[h];
+    }
     if (T < 1) return fail(c, BI_ERR_INVALID, "need T >= 1 toys");
     if (c->B < 1) return fail(c, BI_ERR_INVALID, "a binned likelihood needs at least one bin");
     if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
     HIP_TRY(c, hipSetDevice(c->device));
-    PointGeom g;
-    std::vector<double> r;
-    if ((rc = rates_at(c, c, z, rate_scale, "toy generation", "toy generation", g, r))) return rc;
+    std::vector<ToyTruth> truths((size_t)H);
+    for (int64_t h = 0; h < H; ++h) {
+        char where[64] = "toy generation";
+        if (!one) snprintf(where, sizeof where, "toy generation (truth %lld)", (long long)h);
+        if ((rc = rates_at(c, c, z ? z + h * c->d : nullptr, rate_scale ? rate_scale + h * c->S : nullptr, where, where,
+                           truths[(size_t)h].g, truths[(size_t)h].r))) return rc;
+    }
     c->data_ready = false;
     c->dense_counts = false;
     c->csr_ready = c->compact_ready = false;
     ++c->epoch;
     dev_free(c->counts);  // the toys exist as non-empty-bin lists only
     c->cnt8_valid = false;  // ... and the narrow copy of the dense counts goes with them (bi_counts_to_dense rebuilds it)
-    if ((rc = draw_toy_lists(c, g, r, T, seed))) return rc;
+    std::vector<int32_t> meth;
+    if ((rc = draw_toy_lists(c, truths, n_toys, T, seed, meth))) return rc;
+    if (method_out) std::copy(meth.begin(), meth.end(), method_out);
     c->T = T;
     c->csr_ready = true;
     if ((rc = build_compact_templates(c))) return rc;   // per-toy point evaluations, when the budget allows
     c->data_ready = true;
     return BI_OK;
+}
+
+int bi_generate_toys(bi_ctx* c, const double* z, const double* rate_scale, int64_t T, uint64_t seed) {
+    if (!c) return BI_ERR_INVALID;
+    return generate_toys_impl(c, 1, z, rate_scale, &T, seed, nullptr, true);
+}
+
+int bi_generate_toys_points(bi_ctx* c, int64_t H, const double* z, const double* rate_scale, const int64_t* n_toys, uint64_t seed,
+                            int32_t* method_out) {
+    if (!c) return BI_ERR_INVALID;
+    return generate_toys_impl(c, H, z, rate_scale, n_toys, seed, method_out, false);
 }
 
 int bi_download_counts(bi_ctx* c, int64_t t, double* out) {

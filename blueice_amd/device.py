@@ -322,6 +322,21 @@ class DeviceContext:
         self._check(self._lib.bi_generate_toys(self._h, ptr(z), ptr(rate_scale), int(T), int(seed) & (2**64 - 1)))
         self.T = int(T)
 
+    def generate_toys_points(self, z, rate_scale=None, n_toys=1, seed=0):
+        """Replace the data by sum(n_toys) toy datasets, n_toys[h] of them drawn at truth point (z[h], rate_scale[h]),
+        truth-major, in one call: the same toys as one `generate_toys` per truth with `toy_offset` advanced.
+        -> methods [H]: 1 = drawn event by event, 0 = bin by bin, -1 = a truth without toys."""
+        n_toys = np.ascontiguousarray(np.atleast_1d(n_toys), dtype=np.int64)
+        H = len(n_toys)
+        z = np.ascontiguousarray(as_f64(z).reshape(H, self.d)) if self.d else None
+        if rate_scale is not None:
+            rate_scale = np.ascontiguousarray(np.broadcast_to(as_f64(np.atleast_2d(rate_scale)), (H, self.S)))
+        methods = np.empty(H, dtype=np.int32)
+        self._check(self._lib.bi_generate_toys_points(self._h, H, ptr(z), ptr(rate_scale), ptr(n_toys), int(seed) & (2**64 - 1),
+                                                      ptr(methods)))
+        self.T = int(n_toys.sum())
+        return methods
+
     def download_counts(self, t=0):
         out = np.empty(self.B, dtype=np.float64)
         self._check(self._lib.bi_download_counts(self._h, int(t), ptr(out)))

@@ -35,7 +35,7 @@ from .sampler import sample_posterior
 from .utils import is_numeric
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
-           'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
+           'toy_test_statistics', 'neyman_thresholds', 'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
            'plot_likelihood_ratio']
 
 
@@ -243,6 +243,196 @@ def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, f
     return OrderedDict((k, np.concatenate(v)) for k, v in best.items()), np.concatenate(lls)
 
 
+class ToyStatistics:
+    """What `toy_test_statistics` returns: t [H, n] -- 2 (ll_free - ll_cond), raw (rounding can leave it a hair below 0), and
+    0 where the one-sided rule says so --, ll_free, ll_cond, best (OrderedDict name -> the free fit's values [H, n]) and
+    target_hat [H, n] (its entry of the target), hypotheses [H], kind, and the flags of the fits: converged / failed [H, n] (both fits of the toy converged or stalled on a
+    flat stretch; either of them failed), n_converged, n_failed, and engine_calls (fit-engine and evaluation calls made)."""
+
+    def __init__(self, hypotheses, kind, t, ll_free, ll_cond, target_hat, converged, failed, engine_calls=0, best=None):
+        self.hypotheses, self.kind = np.asarray(hypotheses, dtype=float), kind
+        self.t, self.ll_free, self.ll_cond, self.target_hat, self.best = t, ll_free, ll_cond, target_hat, best
+        self.converged, self.failed = converged, failed
+        self.n_converged, self.n_failed = int(np.count_nonzero(converged)), int(np.count_nonzero(failed))
+        self.engine_calls = int(engine_calls)
+
+
+def _resident_data(lf, ctx):
+    """-> a callable that gives `lf` the data back that it holds now, or None where that is not possible"""
+    if not getattr(lf, 'is_data_set', False):
+        return None
+    if hasattr(lf, 'set_binned_data') and ctx is not None and hasattr(ctx, 'download_counts'):
+        counts = np.stack([ctx.download_counts(t) for t in range(int(ctx.T))])
+        counts = counts.reshape(((len(counts),) if len(counts) > 1 else ()) + tuple(lf.bin_shape))
+        events = getattr(lf, '_data', None)
+
+        def restore():
+            lf.set_binned_data(counts)
+            if events is not None:
+                lf._data = events
+        return restore
+    if getattr(lf, '_data', None) is not None and hasattr(lf, 'set_data'):
+        events = lf._data
+        return lambda: lf.set_data(events)
+    return None
+
+
+def toy_test_statistics(lf, target, hypotheses, n_toys, seed=0, kind='central', truth=None, chunk=256, first_toy=0, toy_range=None,
+                        livetime_days=None, fit_options=None, **fixed):
+    """The profile-likelihood-ratio test statistic of `n_toys` toys at each of H hypotheses of `target`: the distribution
+    that a toy-calibrated (Neyman) interval takes its critical values from, where `one_parameter_interval` by default
+    takes Wilks' chi-square.
+
+    Toy j of hypothesis i is drawn at {target: hypotheses[i], **truth_i} (truth: dict of nuisance values, scalars or
+    arrays [H]; other parameters at their defaults) and is toy D = first_toy + i n_toys + j of the seed's ensemble: the
+    result does not depend on `chunk`, and ranks can each take toy_range = (j0, j1), the toys j0 <= j < j1 of every
+    hypothesis.  Toys are drawn and fitted `chunk` at a time.  A likelihood with `simulate_toys_points` (binned) gets chunks
+    that run across hypothesis boundaries -- toys of several hypotheses from one generator call, fitted in one engine
+    call per fit; any other likelihood with `simulate_toys` (unbinned; a duck-typed one) gets chunks of one hypothesis, with
+    its context's toy_offset set as `toy_mc_fits` does -- as does a toy_range that leaves toys out (the numbers of a
+    generator call are consecutive).
+
+    The fit recipe, per chunk of m toys with h_of_toy [m] the hypothesis of every toy:
+      conditional:  bestfit_batched(lf, points={target: h_of_toy}, datasets=arange(m), **fit_options, **fixed)
+                    (`eval_points` where nothing is left to profile);
+      free:         bestfit_batched(lf, datasets=arange(m), also_from=[the conditional solution with target = h_of_toy], ...):
+                    the free maximum is never started below the conditional one.
+    t = 2 (ll_free - ll_cond), not clipped; for kind 'upper' t = 0 where target_hat >= hypothesis, for 'lower' where
+    target_hat <= hypothesis (the rule `one_parameter_interval` applies to the data); 'central' keeps every t.
+    fixed (kwargs): parameters held fixed in both fits.  -> ToyStatistics.
+
+    Afterwards the likelihood has its own data back where that is possible: a binned likelihood's resident datasets are read
+    (`download_counts`) before and handed to `set_binned_data` after -- the same counts, as a dense stack; an unbinned
+    one gets `set_data` of the events it still holds.  It is not possible for datasets that exist on the device only
+    (`set_datasets`, simulated events): then the toys of the last chunk stay, as after `toy_mc_fits`."""
+    if kind not in ('upper', 'lower', 'central'):
+        raise ValueError("kind must be 'upper', 'lower' or 'central'")
+    hyp = np.atleast_1d(np.asarray(hypotheses, dtype=float))
+    H, n = len(hyp), int(n_toys)
+    j0, j1 = (0, n) if toy_range is None else (int(toy_range[0]), int(toy_range[1]))
+    if not 0 <= j0 < j1 <= n:
+        raise ValueError("toy_range (%d, %d) of %d toys per hypothesis" % (j0, j1, n))
+    nj, chunk = j1 - j0, max(int(chunk), 1)
+    truth = {k: np.broadcast_to(np.asarray(v, dtype=float), (H,)) for k, v in (truth or {}).items()}
+    fit_options = dict(fit_options or {})
+    more_starts = list(fit_options.pop('also_from', ()))
+    ctx = getattr(lf, 'ctx', None)
+    if ctx is None and hasattr(lf, '_device_context'):
+        ctx = lf._device_context()             # (an unbinned likelihood makes its context with its first data)
+    if not hasattr(lf, 'simulate_toys') or not supports_batched_fits(lf):
+        raise NotImplementedError("toy_test_statistics needs a likelihood with simulate_toys and batched evaluation")
+    mixed = hasattr(lf, 'simulate_toys_points') and nj == n
+    restore = _resident_data(lf, ctx)
+    out = {k: np.empty(H * nj) for k in ('ll_free', 'll_cond', 'target_hat')}
+    flags = {k: np.zeros(H * nj, dtype=bool) for k in ('converged', 'failed')}
+    calls, fitted = 0, None
+    try:
+        f0 = 0
+        while f0 < H * nj:                     # toys in hypothesis-major order: toy f is (i, j) = (f // nj, j0 + f % nj)
+            f1 = min(f0 + chunk, H * nj if mixed else (f0 // nj + 1) * nj)
+            i_of = np.arange(f0, f1) // nj
+            i_a, i_b = int(i_of[0]), int(i_of[-1]) + 1
+            if ctx is not None:
+                ctx.set_param('toy_offset', int(first_toy) + i_a * n + j0 + f0 % nj)
+            if mixed:
+                pts = {k: v[i_a:i_b] for k, v in truth.items()}
+                pts[target] = hyp[i_a:i_b]
+                lf.simulate_toys_points(pts, np.bincount(i_of - i_a, minlength=i_b - i_a), seed=seed, livetime_days=livetime_days)
+            else:
+                lf.simulate_toys(f1 - f0, seed=seed, livetime_days=livetime_days,
+                                 **dict({k: float(v[i_a]) for k, v in truth.items()}, **{target: float(hyp[i_a])}))
+            ds, h_of_toy = np.arange(f1 - f0), hyp[i_of]
+            try:
+                start, ll_cond, info_c = bestfit_batched(lf, points={target: h_of_toy}, datasets=ds, livetime_days=livetime_days,
+                                                         return_info=True, also_from=more_starts, **fit_options, **fixed)
+                calls += info_c['calls']
+            except NoOpimizationNecessary:
+                start, info_c = {}, None
+                ll_cond = np.asarray(lf.eval_points(dict(fixed, **{target: h_of_toy}), livetime_days=livetime_days, dataset=ds))
+                calls += 1
+            start = dict(start, **{target: h_of_toy})
+            best, ll_free, info_f = bestfit_batched(lf, datasets=ds, livetime_days=livetime_days, return_info=True,
+                                                    also_from=more_starts + [start], **fit_options, **fixed)
+            calls += info_f['calls']
+            out['ll_free'][f0:f1], out['ll_cond'][f0:f1], out['target_hat'][f0:f1] = ll_free, ll_cond, best[target]
+            if fitted is None:
+                fitted = OrderedDict((k, np.empty(H * nj)) for k in best)
+            for k, v in best.items():
+                fitted[k][f0:f1] = v
+            done, bad = info_f['converged'] | info_f['stalled'], np.array(info_f['failed'], dtype=bool)
+            if info_c is not None:
+                done, bad = done & (info_c['converged'] | info_c['stalled']), bad | info_c['failed']
+            flags['converged'][f0:f1], flags['failed'][f0:f1] = done, bad
+            f0 = f1
+    finally:
+        if ctx is not None:
+            ctx.set_param('toy_offset', 0)
+        if restore is not None:
+            restore()
+    out = {k: v.reshape(H, nj) for k, v in out.items()}
+    t = 2 * (out['ll_free'] - out['ll_cond'])
+    if kind == 'upper':
+        t = np.where(out['target_hat'] >= hyp[:, None], 0.0, t)
+    elif kind == 'lower':
+        t = np.where(out['target_hat'] <= hyp[:, None], 0.0, t)
+    return ToyStatistics(hyp, kind, t, out['ll_free'], out['ll_cond'], out['target_hat'], flags['converged'].reshape(H, nj),
+                         flags['failed'].reshape(H, nj), calls, OrderedDict((k, v.reshape(H, nj)) for k, v in fitted.items()))
+
+
+class ToyThresholds:
+    """Critical values of the test statistic from toys: a `t_ppf(hypothesis, quantile)` for `one_parameter_interval`.
+
+    At each tabulated hypothesis the value is the empirical quantile of t over its toys on the conservative side
+    (numpy.quantile(..., method='higher'): an order statistic, never an interpolation below one); between hypotheses it is
+    interpolated linearly, beyond the first and last it is held constant.  The level of that quantile is chosen so that the
+    table's large-sample (Wilks) limit is what `one_parameter_interval` compares with by default, norm.ppf(quantile)**2:
+      kind 'upper' / 'lower': t is half chi-square, P(t <= c) = Phi(sqrt(c)) -> level = quantile (for a quantile below 1/2
+                              -- kind 'lower' searches with 1 - confidence_level -- its mirror image 1 - quantile, which has
+                              the same norm.ppf(quantile)**2);
+      kind 'central':         t is chi-square with one degree of freedom, P(t <= c) = 2 Phi(sqrt(c)) - 1 -> level = |2 quantile - 1|.
+    A level above 1 - 1/n needs more than the n toys per hypothesis of the table, and is refused."""
+
+    def __init__(self, hypotheses, t, kind):
+        if kind not in ('upper', 'lower', 'central'):
+            raise ValueError("kind must be 'upper', 'lower' or 'central'")
+        hyp, t = np.atleast_1d(np.asarray(hypotheses, dtype=float)), np.atleast_2d(np.asarray(t, dtype=float))
+        if t.shape[0] != len(hyp) or t.shape[1] < 1 or not np.all(np.isfinite(t)):
+            raise ValueError("need a finite table t [H, n] with a row per hypothesis")
+        order = np.argsort(hyp, kind='stable')
+        self.hypotheses, self.t, self.kind = hyp[order], t[order], kind
+        self._critical = {}
+
+    @classmethod
+    def from_statistics(cls, stats_):
+        return cls(stats_.hypotheses, stats_.t, stats_.kind)
+
+    def level(self, quantile):
+        quantile = float(quantile)
+        return abs(2 * quantile - 1) if self.kind == 'central' else max(quantile, 1 - quantile)
+
+    def critical_values(self, quantile):
+        """-> the critical value at every tabulated hypothesis [H]"""
+        level, n = self.level(quantile), self.t.shape[1]
+        if level > 1 - 1.0 / n:
+            raise ValueError("quantile %g asks for the level %g of the test statistic: %d toys per hypothesis resolve levels up to "
+                             "1 - 1/n = %g only -- more toys are needed" % (quantile, level, n, 1 - 1.0 / n))
+        if level not in self._critical:
+            self._critical[level] = np.quantile(self.t, level, axis=1, method='higher')
+        return self._critical[level]
+
+    def __call__(self, hypothesis, quantile):
+        return float(np.interp(float(hypothesis), self.hypotheses, self.critical_values(quantile)))
+
+
+def neyman_thresholds(lf, target, hypotheses, n_toys, **options):
+    """Toy-calibrated critical values for `one_parameter_interval`: `toy_test_statistics` (same arguments and options; its
+    `kind` must be the interval's) tabulated as a `ToyThresholds`, e.g.
+        table = lf.neyman_thresholds('s0_rate_multiplier', np.linspace(0.5, 4, 16), 1000, kind='upper')
+        limit = lf.one_parameter_interval('s0_rate_multiplier', bound=4., kind='upper', t_ppf=table)
+    A ToyStatistics at hand (ranks' parts put together, say) becomes a table with ToyThresholds.from_statistics(stats)."""
+    return ToyThresholds.from_statistics(toy_test_statistics(lf, target, hypotheses, n_toys, **options))
+
+
 def _covariance(lf, values, livetime_days=None, datasets=None, log_rates=False, **fixed):
     """-> (names of the floating parameters, covariance [P, F, F], scalar input?) -- see `hesse`."""
     if not hasattr(lf, 'values_gradients_hessians'):
@@ -427,7 +617,7 @@ def one_parameter_interval(lf, target, bound, confidence_level=0.9, kind='upper'
     the batched profile-fit engine: every round profiles a fan of hypotheses in lock-step on the device (a handful of
     rounds of ~16 fits, each a few dozen device calls) instead of brentq's chain of nested sequential fits (3 387 scalar
     likelihood calls per limit in SURVEY.md's probe); otherwise the reference's loop.  fit_options: dict of options of the
-    batched engine (`bestfit_batched`: multi_start='cells', gtol, ...)."""
+    batched engine (`bestfit_batched`: multi_start='cells', gtol, ...).  `neyman_thresholds` makes a t_ppf from toys."""
     fit_options = dict(fit_options or {})
     if target is None:
         target = lf.source_list[-1] + '_rate_multiplier'

@@ -940,6 +940,33 @@ class BinnedLogLikelihood(DeviceLogLikelihood):
         self._binned = None
         self.is_data_set = True
 
+    @_needs_preparation
+    def simulate_toys_points(self, points, n_toys, seed=0, livetime_days=None):
+        """`simulate_toys` at H truth points in ONE generator call (`bi_generate_toys_points`): n_toys[h] toys (an int: the
+        same number everywhere) at truth h, truth-major.  points: dict parameter name -> array [H] (scalars broadcast; absent
+        parameters take their defaults), as `eval_points`.  Toy t of the call is toy `toy_offset + t` (the context parameter)
+        of the seed's ensemble, and the toys of truth h are those `simulate_toys(n_toys[h], seed, **point h)` draws with
+        toy_offset advanced by the toys of the truths before it: an ensemble over many hypotheses does not depend on how they
+        are grouped into calls.  Afterwards `toy_truth` [T] holds the truth index of every dataset.
+        -> methods [H]: 1 = drawn event by event, 0 = bin by bin, -1 = no toys."""
+        z, scale, _ = self._batch_terms(points, livetime_days)
+        H = max(len(z), np.size(n_toys))
+        n_toys = np.ascontiguousarray(np.broadcast_to(np.asarray(n_toys, dtype=np.int64), (H,)))
+        z, scale = np.broadcast_to(z, (H, z.shape[1])), np.broadcast_to(scale, (H, scale.shape[1]))
+        for i, name in enumerate(self.shape_parameters):
+            lo, hi = self.get_bounds(name)
+            outside = np.flatnonzero(~((z[:, i] >= lo) & (z[:, i] <= hi)))
+            if len(outside):
+                raise ValueError("cannot simulate outside the anchor box (truth %d: %s = %r)" % (outside[0], name, z[outside[0], i]))
+        methods = self.ctx.generate_toys_points(z if z.shape[1] else None, scale, n_toys, seed)
+        if self.model_statistical_uncertainty_handling is not None:
+            self.ctx.counts_to_dense()             # Beeston-Barlow reads n in every bin: the toys as a dense array too
+        self._data = None
+        self._binned = None
+        self.is_data_set = True
+        self.toy_truth = np.repeat(np.arange(H), n_toys)
+        return methods
+
     # -- analytic gradient (one device pass; the reference differentiates numerically) ----------
     @_needs_data
     def eval_toys(self, livetime_days=None, t0=0, t1=None, **kwargs):

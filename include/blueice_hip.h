@@ -257,6 +257,23 @@ int bi_download_event_set(bi_ctx* target, int64_t t, double* out);
  *       The toy's counts are the histogram of its events' bins (sorted per toy in LDS -- a 4-bit LSD radix sort up to 16384
  *       keys, a bitonic network for 32768 -- and run-length encoded); the lists come out in ascending bin order by A and B. */
 int bi_generate_toys(bi_ctx* ctx, const double* z, const double* rate_scale, int64_t T, uint64_t seed);
+/* T = sum_h n_toys[h] toys at H truth points in one call: n_toys[h] >= 0 toys at (z[h], rate_scale[h]), truth-major.  The
+ * stream, exactly: with first_h = sum_{h' < h} n_toys[h'], toy t of the call is toy D = toy_offset + t of the seed's ensemble,
+ * and the toys first_h .. first_h + n_toys[h] - 1 of the call -- their non-empty-bin lists, lgsum entries and numbers of
+ * non-empty bins -- are bit for bit what bi_generate_toys(z[h], rate_scale[h], n_toys[h], seed) leaves with the context
+ * parameter toy_offset at toy_offset + first_h.  The ensemble therefore does not depend on how truths are grouped into calls.
+ * Every truth chooses between A and B by the rules above as a call of its own would: with its own M_h, its own bound and
+ * power of two (which enters both the test "no toy draws more events" and the size of the sort), and its own fall-back to A
+ * when one of ITS toys draws more events than that; the toys of the other truths are not affected.  method_out (when given)
+ * [H]: 1 = B, 0 = A, -1 = a truth with n_toys[h] = 0; last_toy_method = 1 iff every truth that has toys went by B.
+ * bi_generate_toys is the H = 1 case of this call.
+ * All truths are validated before the context changes: one outside the anchor box, or with rates outside [0, inf), refuses
+ * the whole call with bi_generate_toys' error, which names the truth ("toy generation (truth 1) point is outside the anchor
+ * box"), and the data held so far stay usable.  z: [H][d] (NULL when d = 0), rate_scale: [H][S] or NULL; n_toys [H] with
+ * 1 <= T < 2^31.  Afterwards the context is as bi_generate_toys leaves it, with T datasets.  Scratch: H * Bp doubles each for
+ * mu and exp(-mu), H * B for the running sums where B applies: callers bound H per call. */
+int bi_generate_toys_points(bi_ctx* ctx, int64_t H, const double* z, const double* rate_scale, const int64_t* n_toys, uint64_t seed,
+                            int32_t* method_out);
 /* Expands device-generated toys (non-empty-bin lists) into the dense [T][B] counts array as well, on the device: what
  * the paths that visit every bin need -- Beeston-Barlow point evaluations and gradients (likelihood.py:618-660 read n in
  * every bin), sparse = 0.  T * B * 8 bytes of HBM; a no-op when the counts are dense already. */
