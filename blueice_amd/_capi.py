@@ -58,6 +58,8 @@ SIGNATURES = {
     'bi_eval': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p]),
     'bi_eval_grad': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_eval_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'bi_eval_gof': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_expected_counts': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p]),
     'bi_minimize_batched': (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched_gauss': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,

@@ -9,6 +9,7 @@
 //     tu_grad.hip         k_grad_mfma, k_morph_bbgrad                                        bi_k_grad_mfma.h, bi_k_bbgrad.h
 //     tu_scan_bb.hip      k_scan_bb (Beeston-Barlow scans on the matrix cores)               bi_k_scan_bb.h
 //     tu_hess.hip         k_morph_hess (value + gradient + Hessian of one point per item)    bi_k_hess.h
+//     tu_gof.hip          k_morph_gof (deviance + Pearson chi2 of one point per item), k_morph_expect   bi_k_gof.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
@@ -75,6 +76,10 @@ void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, cons
 int launch_morph_bbgrad(bi_ctx* c, int G, int DZ, const LaunchArgs& a, dim3 grid, bool nt);
 // k_morph_hess<G, DM, UNB, NT>: value, gradient and Hessian of one point per item; BI_ERR_INVALID for a (G, DM) without a variant
 int launch_morph_hess(bi_ctx* c, int G, int DM, const HessArgs& a, dim3 grid, bool nt);
+// k_morph_gof<NT>: half-deviance and Pearson chi2 of one (point, dataset) per item, HessArgs with ONE coefficient column
+void launch_morph_gof(bi_ctx* c, const HessArgs& a, dim3 grid, bool nt);
+// k_morph_expect: the per-bin expectation of n_items (<= 65 535) points, a.R groups of rows each
+void launch_morph_expect(bi_ctx* c, const ExpectArgs& a, int64_t n_items);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -136,6 +136,18 @@ struct HessArgs {
     int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (as morph_tiles)
 };
 
+// k_morph_expect (bi_k_gof.h)
+struct ExpectArgs {
+    const double* ps;          // [rows][Bp] the dense template tensor
+    const int64_t* rowoff;     // [items][NS] element offsets of the rows, row k = (corner, source): k = corner * S + source
+    const double* coef;        // [items][NS] a_k
+    double* out;               // [items][R][B]
+    int64_t B;
+    int NS;
+    int S;                     // sources: group r of a per-source call holds the rows k = r, r + S, ...
+    int R;                     // groups per item: 1 (every row) or S
+};
+
 // k_stretch_propose / k_stretch_accept (bi_k_sampler.h): one half-step of the ensemble sampler; every pointer is device memory
 struct StretchArgs {
     int64_t E;                 // ensembles

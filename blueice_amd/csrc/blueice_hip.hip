@@ -1840,4 +1840,5 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 
 #include "bi_fit.h"
 #include "bi_hess.h"
+#include "bi_gof.h"
 #include "bi_sampler.h"

@@ -420,6 +420,26 @@ class DeviceContext:
                                            ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], hess, status
 
+    def eval_gof(self, z, rate_scale=None, dataset=None):
+        """Goodness of fit of the data term (bi_eval_gof) -> (half-deviance [P], Pearson chi2 [P], status [P]) of point p
+        against dataset[p]; +inf / nan where the likelihood is -inf / nan.  Raises ValueError (BI_ERR_INVALID) for
+        Beeston-Barlow and unbinned contexts."""
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        half_deviance = np.empty(P, dtype=np.float64)
+        pearson = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_eval_gof(self._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(half_deviance), ptr(pearson),
+                                          ptr(status)))
+        return half_deviance, pearson, status
+
+    def expected_counts(self, z, rate_scale=None, per_source=False):
+        """The expectation per bin (bi_expected_counts) -> mu [P, B], or mu [P, S, B] per source; nan rows for points outside
+        the anchor box or with unphysical rates.  Raises ValueError (BI_ERR_INVALID) for Beeston-Barlow and unbinned contexts."""
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        out = np.empty((P, self.S, self.B) if per_source else (P, self.B), dtype=np.float64)
+        self._check(self._lib.bi_expected_counts(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
+        return out
+
     @staticmethod
     def _gauss_terms(priors, F, n):
         """priors = (prior_mean [F], prior_sigma [F], prior_const [n] or None) -> the three as C-contiguous float64 arrays"""

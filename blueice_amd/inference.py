@@ -14,6 +14,10 @@ of the likelihood (`values_gradients_hessians`: bi_eval_hess, one call for a who
 `bestfit_minuit` -- the reference's iminuit driver (blueice/inference.py:181-244) -- returns the batched engine's fit with
 the parabolic errors sqrt(diag((-H)^-1)) that MIGRAD reports at errordef = 0.5.  iminuit itself is not used.
 
+Goodness of fit: `gof_statistics` evaluates the deviance and Pearson's chi2 of the data term on the device (bi_eval_gof),
+`goodness_of_fit` calibrates either with toys fitted like the data, and `expected_counts` hands back the per-bin expectation
+the statistics are made of (bi_expected_counts).  Plain binned likelihoods only.
+
 Profiled quantities -- `likelihood_ratio_scan` with floating nuisances, `one_parameter_interval` -- run on the batched
 profile-fit engine (blueice_amd.profile: all hypotheses advance together, one device call per optimiser iteration)
 whenever the likelihood offers batched evaluation; a user-supplied `bestfit_routine` keeps the reference's sequential
@@ -28,14 +32,15 @@ import numpy as np
 from scipy import stats
 from scipy.optimize import brentq, minimize
 
-from .exceptions import NoOpimizationNecessary, OptimizationFailed
+from .exceptions import NoOpimizationNecessary, NotPreparedException, OptimizationFailed
 from .hessian import to_log10
 from .profile import bestfit_batched, supports_batched_fits
 from .sampler import sample_posterior
 from .utils import is_numeric
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
-           'toy_test_statistics', 'neyman_thresholds', 'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
+           'toy_test_statistics', 'neyman_thresholds', 'expected_counts', 'expected_counts_points', 'gof_statistics', 'goodness_of_fit',
+           'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
            'plot_likelihood_ratio']
 
 
@@ -431,6 +436,160 @@ def neyman_thresholds(lf, target, hypotheses, n_toys, **options):
         limit = lf.one_parameter_interval('s0_rate_multiplier', bound=4., kind='upper', t_ppf=table)
     A ToyStatistics at hand (ranks' parts put together, say) becomes a table with ToyThresholds.from_statistics(stats)."""
     return ToyThresholds.from_statistics(toy_test_statistics(lf, target, hypotheses, n_toys, **options))
+
+
+# ---- goodness of fit ------------------------------------------------------------------------------------------------
+
+def _binned_for_gof(lf, what):
+    """-> lf if it is a binned likelihood without Beeston-Barlow; NotImplementedError otherwise (before any device work)"""
+    from .likelihood import BinnedLogLikelihood
+    if not isinstance(lf, BinnedLogLikelihood):
+        raise NotImplementedError("%s needs a BinnedLogLikelihood: a %s has no bins of its own" % (what, type(lf).__name__))
+    if lf.model_statistical_uncertainty_handling is not None:
+        raise NotImplementedError("%s is not defined with Beeston-Barlow (model_statistical_uncertainty_handling = %r): the "
+                                  "expectation depends on the data" % (what, lf.model_statistical_uncertainty_handling))
+    if not lf.is_prepared:
+        if len(lf.shape_parameters):
+            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+        lf.prepare()            # nothing to morph: preparation is trivial
+    return lf
+
+
+def expected_counts_points(lf, points, per_source=False, livetime_days=None):
+    """The expected events per bin at P parameter points: points = dict parameter name -> array [P] (scalars broadcast;
+    absent parameters take their defaults), as `eval_points` -> mu [P, *bin_shape], or [P, S, *bin_shape] with per_source
+    (source order: `source_name_list`; the sum over sources is the total).  Live time, rate multipliers and efficiencies
+    enter exactly as in `lf(**params)` (the same host terms); the morph runs on the device (bi_expected_counts), where the
+    dense templates lie -- no data are needed.  A point outside the anchor box or with unphysical rates gets nan."""
+    _binned_for_gof(lf, 'expected_counts_points')
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    mu = lf.ctx.expected_counts(z if z.shape[1] else None, scale, per_source=per_source)
+    return mu.reshape(mu.shape[:-1] + tuple(lf.bin_shape))
+
+
+def expected_counts(lf, per_source=False, livetime_days=None, **params):
+    """The expected events per bin at one parameter point -> array of `lf.bin_shape`, or [S, *bin_shape] with per_source:
+    the best-fit histogram, the denominator of a pull.  As `expected_counts_points`, with the host terms of the scalar
+    call `lf(**params)`; nan outside the anchor box or where the rates are unphysical."""
+    _binned_for_gof(lf, 'expected_counts')
+    _, zs, scale = lf._host_terms(livetime_days, params)
+    S = len(lf.source_name_list)
+    shape = ((S,) if per_source else ()) + tuple(lf.bin_shape)
+    if zs is None:
+        return np.full(shape, np.nan)
+    return lf.ctx.expected_counts(zs if len(zs) else None, scale[None, :], per_source=per_source)[0].reshape(shape)
+
+
+def gof_statistics(lf, points=None, datasets=None, livetime_days=None, **fixed):
+    """Goodness-of-fit statistics of the binned data at P parameter points, summed bin by bin on the device (bi_eval_gof):
+        deviance = 2 sum_b [mu_b - n_b - n_b log(mu_b / n_b)]     (the likelihood ratio against the saturated model, Baker-Cousins)
+        pearson  =   sum_b (n_b - mu_b)^2 / mu_b
+    with an empty bin contributing 2 mu_b and mu_b.  points: dict parameter name -> array [P] (as `eval_points`); fixed
+    (kwargs): parameters at one value everywhere; datasets: the dataset of every point [P], e.g. np.arange(T) with the fitted
+    values of `bestfit_toys` (None: dataset 0).
+    -> dict(deviance [P], pearson [P], n_bins, n_events [P] (the events of every point's dataset), status [P]).
+    PRIORS ARE NOT PART OF EITHER STATISTIC: both are statements about the data term only, whatever constraint terms the
+    likelihood carries.  A point outside the anchor box or with unphysical rates gives +inf in both; so does a point where
+    the likelihood is -inf (an event in a bin where nothing is expected), and both are nan where it is nan."""
+    _binned_for_gof(lf, 'gof_statistics')
+    if not lf.is_data_set:
+        raise NotPreparedException("gof_statistics requires you to first set the data using set_data()")
+    pts = dict(fixed)
+    pts.update(points or {})
+    z, scale, _ = lf._batch_terms(pts, livetime_days)
+    if datasets is not None:
+        datasets = np.atleast_1d(np.asarray(datasets, dtype=np.int64))
+        P = max(len(z), len(datasets))
+        z, scale = np.broadcast_to(z, (P, z.shape[1])), np.broadcast_to(scale, (P, scale.shape[1]))
+        datasets = np.broadcast_to(datasets, (P,))
+    half, pearson, st = lf.ctx.eval_gof(z if z.shape[1] else None, scale, datasets)
+    ds = np.zeros(len(half), dtype=np.int64) if datasets is None else datasets
+    totals = {int(t): float(lf.ctx.download_counts(int(t)).sum()) for t in np.unique(ds) if 0 <= t < lf.ctx.T}
+    return dict(deviance=2.0 * half, pearson=pearson, n_bins=int(np.prod(lf.bin_shape, dtype=np.int64)),
+                n_events=np.array([totals.get(int(t), np.nan) for t in ds]), status=st)
+
+
+def toy_p_value(observed, toys, failed=None):
+    """The p-value of `observed` among the toys' statistics: (1 + #{toys >= observed}) / (n + 1) -- ties count as >=, and so
+    do toys whose fit failed (`failed` [n], bool) and toys whose statistic is nan: the conservative side, never dropped."""
+    toys = np.atleast_1d(np.asarray(toys, dtype=float))
+    if toys.ndim != 1 or len(toys) == 0:
+        raise ValueError("toy_p_value needs the statistics of at least one toy")
+    above = ~(toys < float(observed))
+    if failed is not None:
+        failed = np.asarray(failed, dtype=bool)
+        if failed.shape != toys.shape:
+            raise ValueError("failed must have one flag per toy")
+        above = above | failed
+    return (1.0 + np.count_nonzero(above)) / (len(toys) + 1.0)
+
+
+class GofResult:
+    """What `goodness_of_fit` returns: statistic ('deviance' or 'pearson'), observed (its value for the data at their best
+    fit), toys [n] (its value for every toy at that toy's own fit), p_value = (1 + #{toys >= observed}) / (n + 1),
+    p_value_chi2 = chi2.sf(observed, ndof) with ndof = n_bins - n_floating -- ASYMPTOTIC: unreliable with sparse bins (few
+    expected events per bin), where the toys are the answer --, best (OrderedDict name -> fitted value of the data),
+    toy_best (OrderedDict name -> fitted values [n]), failed [n] and n_failed: the toys whose fit failed; they count as >=
+    observed in p_value and are reported, never dropped."""
+
+    def __init__(self, statistic, observed, toys, failed, ndof, best, toy_best):
+        self.statistic, self.observed, self.toys = statistic, float(observed), np.asarray(toys, dtype=float)
+        self.failed = np.asarray(failed, dtype=bool)
+        self.n_failed = int(np.count_nonzero(self.failed))
+        self.ndof, self.best, self.toy_best = int(ndof), best, toy_best
+        self.p_value = toy_p_value(self.observed, self.toys, self.failed)
+        self.p_value_chi2 = float(stats.chi2.sf(self.observed, self.ndof)) if self.ndof > 0 else float('nan')
+
+
+def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, first_toy=0, fit_options=None, livetime_days=None,
+                    **fixed):
+    """Does the fitted model describe the data?  The goodness-of-fit statistic ('deviance' or 'pearson', see
+    `gof_statistics`) of the data at their best fit, and its p-value from toys that are treated like the data:
+      1. the data are fitted (`bestfit_batched`; `fixed` parameters stay fixed, fit_options go to the engine);
+      2. the observed statistic is evaluated at that fit;
+      3. `n_toys` toys are drawn at the fitted values (`simulate_toys`), `chunk` at a time; toy j is toy first_toy + j of the
+         seed's ensemble, so the result does not depend on `chunk` (as `toy_mc_fits`);
+      4. every toy is fitted (`bestfit_toys`, the same options);
+      5. every toy's statistic is evaluated at its own fit.
+    -> GofResult.  Priors shape the fits but are no part of the statistic.  p_value_chi2 is the asymptotic reading
+    chi2.sf(observed, n_bins - n_floating); with sparse bins it is unreliable and p_value is the number to quote.
+    Afterwards the likelihood has its own data back (as after `toy_test_statistics`)."""
+    _binned_for_gof(lf, 'goodness_of_fit')
+    if statistic not in ('deviance', 'pearson'):
+        raise ValueError("statistic must be 'deviance' or 'pearson'")
+    n, chunk = int(n_toys), max(int(chunk), 1)
+    if n < 1:
+        raise ValueError("goodness_of_fit needs at least one toy")
+    fit_options = dict(fit_options or {})
+    ctx = lf.ctx
+    try:
+        b, _ = bestfit_batched(lf, livetime_days=livetime_days, **fit_options, **fixed)
+        best = OrderedDict((k, float(v[0])) for k, v in b.items())
+    except NoOpimizationNecessary:
+        best = OrderedDict()
+    truth = dict(fixed, **best)
+    observed = float(gof_statistics(lf, livetime_days=livetime_days, **truth)[statistic][0])
+    n_bins = int(np.prod(lf.bin_shape, dtype=np.int64))
+    restore = _resident_data(lf, ctx)
+    toys, failed = np.empty(n), np.zeros(n, dtype=bool)
+    toy_best = OrderedDict((k, np.empty(n)) for k in best)
+    try:
+        for t0 in range(0, n, chunk):
+            m = min(chunk, n - t0)
+            ctx.set_param('toy_offset', int(first_toy) + t0)
+            lf.simulate_toys(m, seed=seed, livetime_days=livetime_days, **truth)
+            fitted = {}
+            if best:
+                fitted, _, info = bestfit_toys(lf, livetime_days=livetime_days, return_info=True, **fit_options, **fixed)
+                failed[t0:t0 + m] = info['failed']
+                for k, v in fitted.items():
+                    toy_best[k][t0:t0 + m] = v
+            toys[t0:t0 + m] = gof_statistics(lf, points=fitted, datasets=np.arange(m), livetime_days=livetime_days, **fixed)[statistic]
+    finally:
+        ctx.set_param('toy_offset', 0)
+        if restore is not None:
+            restore()
+    return GofResult(statistic, observed, toys, failed, n_bins - len(best), best, toy_best)
 
 
 def _covariance(lf, values, livetime_days=None, datasets=None, log_rates=False, **fixed):

@@ -342,6 +342,25 @@ int bi_eval_grad(bi_ctx* ctx, int64_t P, const double* z, const double* rate_sca
 int bi_eval_hess(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
                  double* grad, double* hess, int32_t* status);
 
+/* Goodness of fit of the data term: per point p, against dataset dataset[p] (NULL: dataset 0), with mu_b the expectation of
+ * bin b at (z, rate_scale) and n_b the dataset's count,
+ *   half_deviance [P]   sum_b  mu_b - n_b - n_b log(mu_b / n_b)      (n_b = 0: mu_b)    -- the deviance is twice this
+ *   pearson       [P]   sum_b  (n_b - mu_b)^2 / mu_b                   (n_b = 0: mu_b)
+ * each summed bin by bin in this form, never as a difference of two log-likelihoods.  A bin with n_b = 0 and mu_b = 0
+ * contributes 0 to both.  Points are screened as by bi_eval_grad (same status bits); a point outside the anchor box or with
+ * unphysical rates gets +inf in both.  For a live point both are +inf where bi_eval returns ll = -inf (an event in a bin
+ * where nothing is expected) and nan where it returns nan (a negative expectation).  Priors are no part of either.
+ * Dense and non-empty-bin forms of the data (device-generated toys included), chosen as bi_eval_hess chooses.  Binned
+ * likelihoods without Beeston-Barlow only: BI_ERR_INVALID with the reason in bi_last_error otherwise. */
+int bi_eval_gof(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                double* half_deviance, double* pearson, int32_t* status);
+
+/* The expectation itself: out [P][B] holds mu_b at every point (per_source = 0), or out [P][S][B] the expectation
+ * mu_{s,b} of every source (per_source != 0; their sum over s is mu_b).  Read from the dense template tensor: no data
+ * are needed.  The row(s) of a point outside the anchor box or with unphysical rates are nan.  Binned likelihoods without
+ * Beeston-Barlow only (there the expectation depends on the data): BI_ERR_INVALID otherwise. */
+int bi_expected_counts(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out);
+
 /* The batched profile-fit engine's inner loop (host code): P minimisations of F variables each advance in lock-step, every
  * optimiser iteration ONE evaluation call over the problems still running -- what replaces the reference's loops of sequential
  * scipy fits (bestfit_scipy, blueice/inference.py:131-178, inside one_parameter_interval / plot_likelihood_ratio, :332-443).
