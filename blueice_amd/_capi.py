@@ -60,10 +60,17 @@ SIGNATURES = {
     'bi_eval_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     'bi_eval_gof': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_expected_counts': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p]),
+    'bi_set_real_counts': (C.c_int, [_p, _i64, _p]),
+    'bi_set_asimov_counts': (C.c_int, [_p, _i64, _p, _p]),
+    'bi_real_count_sets': (_i64, [_p]),
+    'bi_download_real_counts': (C.c_int, [_p, _i64, _p]),
+    'bi_eval_real': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_minimize_batched': (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched_gauss': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                        _p, _p, _p, _p]),
+    'bi_fit_batched_real': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
+                                      _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
                                     _p, _p, _p, _p]),
     'bi_sample_stretch_gauss': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,

@@ -10,6 +10,7 @@
 //     tu_scan_bb.hip      k_scan_bb (Beeston-Barlow scans on the matrix cores)               bi_k_scan_bb.h
 //     tu_hess.hip         k_morph_hess (value + gradient + Hessian of one point per item)    bi_k_hess.h
 //     tu_gof.hip          k_morph_gof (deviance + Pearson chi2 of one point per item), k_morph_expect   bi_k_gof.h
+//     tu_real.hip         k_morph_real (half-deviance + gradient against real-valued counts), k_real_expect   bi_k_real.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
@@ -80,6 +81,11 @@ int launch_morph_hess(bi_ctx* c, int G, int DM, const HessArgs& a, dim3 grid, bo
 void launch_morph_gof(bi_ctx* c, const HessArgs& a, dim3 grid, bool nt);
 // k_morph_expect: the per-bin expectation of n_items (<= 65 535) points, a.R groups of rows each
 void launch_morph_expect(bi_ctx* c, const ExpectArgs& a, int64_t n_items);
+// k_morph_real<G, NT>: half-deviance and its first derivatives of one (point, real-valued dataset) per item, G = 1 (value
+// only), 4, 8 or 16 coefficient columns; BI_ERR_INVALID for another G
+int launch_morph_real(bi_ctx* c, int G, const HessArgs& a, dim3 grid, bool nt);
+// k_real_expect: the expectation of n_items (<= 65 535) truths into rows of the real-valued store
+void launch_real_expect(bi_ctx* c, const RealExpectArgs& a, int64_t n_items);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -120,6 +120,11 @@ struct bi_ctx {
     // and whether it finished through the mailbox (0: k_finish, k_finish_single or the two-kernel fallback ran behind it)
     int64_t last_morph_nbx = 0, last_morph_items = 0, last_morph_fused = 0;
 
+    // real-valued datasets [real_T][Bp] (bi_set_real_counts / bi_set_asimov_counts; bi_real.h): a store of its own beside
+    // `counts`, read by bi_eval_real / bi_fit_batched_real only and released by a new model
+    DevBuf real_counts;
+    int64_t real_T = 0;
+
     // model statistics (for the sparse forms)
     std::vector<double> h_rowsum;  // [A*S] sum over bins of every ps row
     std::vector<double> h_rowmin;  // [A*S] smallest entry of every ps row

@@ -148,6 +148,17 @@ struct ExpectArgs {
     int R;                     // groups per item: 1 (every row) or S
 };
 
+// k_real_expect (bi_k_real.h)
+struct RealExpectArgs {
+    const double* ps;          // [rows][Bp] the dense template tensor
+    const int64_t* rowoff;     // [items][NS] element offsets of the rows, row k = (corner, source)
+    const double* coef;        // [items][NS] a_k
+    double* out;               // [items][Bp] rows of the real-valued store (the padding bins are zeroed by the caller)
+    int64_t* bad;              // [items] 0, or 1 + a bin whose expectation is negative or nan
+    int64_t B, Bp;
+    int NS;
+};
+
 // k_stretch_propose / k_stretch_accept (bi_k_sampler.h): one half-step of the ensemble sampler; every pointer is device memory
 struct StretchArgs {
     int64_t E;                 // ensembles

@@ -12,6 +12,7 @@
 //   bi_fit_batched        ... with the device likelihood as the objective, no Python between the iterations: optimiser
 //                         variable j is a shape parameter (z_i = x_j) or a rate multiplier (rate_scale_s = x_j * unit_s)
 //   bi_fit_batched_gauss  ... plus Gaussian constraint terms on the optimiser variables: f = -(ll + p)
+//   bi_fit_batched_real   (bi_real.h) ... against a real-valued dataset: f = half_deviance - p
 #pragma once
 
 #include <new>
@@ -383,6 +384,7 @@ struct DeviceObjective {
     const double* prior_mean;   // [F]      Gaussian constraint on variable j (all three NULL: no terms) ...
     const double* prior_sigma;  // [F]      ... +inf: none on that variable
     const double* prior_const;  // [P] or NULL: what of p does not depend on x
+    bool real = false;          // the data are the real-valued store's (bi_fit_batched_real, bi_real.h): ll stands for -half_deviance (bi_eval_real)
     std::vector<double> z, sc, ll, grad;
     std::vector<int64_t> ds;
     std::vector<int32_t> st;
@@ -410,9 +412,13 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
         if (o->dataset) o->ds[(size_t)i] = o->dataset[p];
     }
     o->evaluations += n;
-    const int rc = bi_eval_grad(c, n, d ? o->z.data() : nullptr, o->sc.data(), o->dataset ? o->ds.data() : nullptr, o->ll.data(),
-                                o->grad.data(), o->st.data());
+    const int rc = (o->real ? bi_eval_real : bi_eval_grad)(c, n, d ? o->z.data() : nullptr, o->sc.data(), o->dataset ? o->ds.data() : nullptr,
+                                                           o->ll.data(), o->grad.data(), o->st.data());
     if (rc) return rc;
+    if (o->real) {
+        for (double& v : o->ll) v = -v;
+        for (double& v : o->grad) v = -v;
+    }
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     for (int64_t i = 0; i < n; ++i) {
         const int64_t p = rows[i];

@@ -1,0 +1,301 @@
+// bi_real.h -- real-valued datasets: the store (bi_set_real_counts, bi_set_asimov_counts, bi_real_count_sets,
+// bi_download_real_counts), bi_eval_real and bi_fit_batched_real (host half; the kernels are k_morph_real and k_real_expect,
+// bi_k_real.h).
+//
+// The store c->real_counts [real_T][Bp] lies beside the context's ordinary data and is read by nothing else: every existing
+// data path keeps scipy's poisson.logpmf semantics (a count that is no integer is -inf).  bi_eval_real is bi_eval_grad's
+// host half over the dense rows -- one work item per live point, the coefficient columns of PointDerivs::first_order, the
+// chunked launch and k_finish of run_item_chunks -- with the half-deviance in slot 0 instead of the log-likelihood.  The
+// points are screened by screen_point's box and rate tests; its dataset test is against the integer store (c->T, which may
+// be empty here: expected results need no observed data) and is replaced by a check of the whole dataset column.
+#pragma once
+
+namespace {
+
+// the early exits of screen_point (bi_geometry.h) less its dataset test -> 0 or the status bit
+int32_t real_screen_point(const bi_ctx* c, const double* z, const double* rs, PointGeom& g, double* r) {
+    if (!point_geometry(c, z, g)) return BI_ST_OUT_OF_BOUNDS;
+    interp_mus(c, g, r);
+    if (rs) for (int s = 0; s < c->S; ++s) r[s] *= rs[s];
+    return rates_physical(c, r) ? 0 : BI_ST_UNPHYSICAL;
+}
+
+// a new store takes the place of the old one only when it is complete: on any refusal the previous one stays usable
+void real_store_swap(bi_ctx* c, DevBuf& fresh, int64_t T) {
+    dev_free(c->real_counts);
+    c->real_counts = fresh;
+    c->real_T = T;
+    fresh = DevBuf{};
+}
+
+int real_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* half_deviance,
+              double* grad, int32_t* status) {
+    const int S = c->S, d = c->d;
+    const bool values_only = grad == nullptr;
+    const int W = values_only ? 1 : 1 + d + S;
+    if (W > kMaxG) return fail(c, BI_ERR_INVALID, "bi_eval_real: 1 + d + S = %d exceeds %d gradient columns (value-only calls have no such limit)", W, kMaxG);
+    for (int64_t p = 0; dataset && p < P; ++p)
+        if (dataset[p] < 0 || dataset[p] >= c->real_T)
+            return fail(c, BI_ERR_INVALID, "bi_eval_real: dataset[%lld] = %lld outside the %lld real-valued sets", (long long)p,
+                        (long long)dataset[p], (long long)c->real_T);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int G = W == 1 ? 1 : W <= 4 ? 4 : W <= 8 ? 8 : 16;
+    const int de = (int)c->eff_axes.size();
+    const int nc = 1 << de, NS = nc * S;
+    const double inf = std::numeric_limits<double>::infinity();
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+
+    std::vector<int32_t> st((size_t)P);
+    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
+        PointGeom g;
+        std::vector<double> r((size_t)S);
+        for (int64_t p = lo; p < hi; ++p) {
+            half_deviance[p] = inf;
+            for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
+            st[(size_t)p] = real_screen_point(c, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, g, r.data());
+        }
+    });
+    std::vector<int64_t> live;
+    live.reserve((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        if (status) status[p] = st[(size_t)p];
+        if (!st[(size_t)p]) live.push_back(p);
+    }
+    const int64_t n_items = (int64_t)live.size();
+    if (n_items == 0) return BI_OK;
+
+    std::vector<int> axis_col((size_t)de);
+    for (int i = 0; i < de; ++i) axis_col[(size_t)i] = 1 + c->eff_axes[(size_t)i];
+    std::vector<int64_t> rowoff((size_t)n_items * NS), cnt_off((size_t)n_items), perm((size_t)n_items * G, -1);
+    std::vector<double> coef((size_t)n_items * NS * G, 0.0), slot_lg((size_t)n_items * G, 0.0);
+    std::vector<int32_t> tiles((size_t)n_items, (int32_t)(c->Bp / kTile));
+    parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
+        PointDerivs pd(c, false);
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t p = live[(size_t)i];
+            pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
+            const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * G;
+            int k = 0;
+            for (int corner = 0; corner < nc; ++corner)
+                for (int s = 0; s < S; ++s, ++k) {
+                    rowoff[ro + k] = ((pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s) * c->Bp;
+                    double* col = &coef[co + (size_t)k * G];
+                    if (values_only) col[0] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];      // (first_order's column 0: k_real_expect's a_k)
+                    else pd.first_order(col, corner, s, axis_col.data(), 1 + d + s);
+                }
+            for (int q = 0; q < W; ++q) perm[po + q] = i * W + q;
+            cnt_off[(size_t)i] = (dataset ? dataset[p] : 0) * c->Bp;
+        }
+    });
+    const int max_tiles = (int)(c->Bp / kTile);
+    int rc;
+    PackedUpload pu;
+    if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
+                                {cnt_off.data(), cnt_off.size() * sizeof(int64_t)}, {tiles.data(), tiles.size() * sizeof(int32_t)},
+                                {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
+                            (size_t)n_items * W * sizeof(double), pu)))
+        return rc;
+    double* h_out = (double*)pu.host_out();
+    HessArgs a{};
+    a.ps = (const double*)c->ps.p;
+    a.counts = (const double*)c->real_counts.p;
+    a.B = c->B;
+    a.NS = NS;
+    a.D = W - 1;
+    a.chunks = (int)c->tile_chunks;
+    const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
+    rc = run_item_chunks(c, n_items, max_tiles, G, pu.dev<int64_t>(4), pu.dev<double>(5), h_out, nullptr, "bi_eval_real",
+                         [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
+                             HessArgs b = a;
+                             b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
+                             b.coef = pu.dev<double>(1) + i0 * NS * G;
+                             b.item_cnt = pu.dev<int64_t>(2) + i0;
+                             b.item_tiles = pu.dev<int32_t>(3) + i0;
+                             b.partial = partial;
+                             b.pflags = pflags;
+                             const int e = launch_morph_real(c, G, b, grid, nt);
+                             return e ? fail(c, e, "bi_eval_real: no kernel variant for %d columns", G) : BI_OK;
+                         });
+    if (rc) return rc;
+    for (int64_t i = 0; i < n_items; ++i) {
+        const int64_t p = live[(size_t)i];
+        const double hd = h_out[(size_t)i * W];
+        half_deviance[p] = hd;
+        for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = std::isfinite(hd) ? h_out[(size_t)i * W + 1 + j] : qnan;
+    }
+    return BI_OK;
+}
+
+// what every entry point of the real-valued store refuses, and `need_store`: the evaluations
+int real_check(bi_ctx* c, const char* what, bool need_store) {
+    int rc = gof_check(c, what, false);
+    if (rc) return rc;
+    if (need_store && (c->real_T < 1 || !c->real_counts.p))
+        return fail(c, BI_ERR_STATE, "%s: no real-valued dataset is resident (bi_set_real_counts / bi_set_asimov_counts first)", what);
+    return BI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_set_real_counts(bi_ctx* c, int64_t T, const double* counts) {
+    int rc = real_check(c, "bi_set_real_counts", false);
+    if (rc) return rc;
+    if (T < 0) return fail(c, BI_ERR_INVALID, "bi_set_real_counts: T = %lld", (long long)T);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (T == 0 || !counts) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        dev_free(c->real_counts);
+        c->real_T = 0;
+        return BI_OK;
+    }
+    const int64_t B = c->B, Bp = c->Bp;
+    for (int64_t t = 0; t < T; ++t)
+        for (int64_t b = 0; b < B; ++b) {
+            const double n = counts[t * B + b];
+            if (!(n >= 0.0 && n < std::numeric_limits<double>::infinity()))
+                return fail(c, BI_ERR_INVALID, "bi_set_real_counts: dataset %lld, bin %lld holds %g: every count must be finite and >= 0",
+                            (long long)t, (long long)b, n);
+        }
+    std::vector<double> padded((size_t)(T * Bp), 0.0);
+    for (int64_t t = 0; t < T; ++t) std::copy(counts + t * B, counts + (t + 1) * B, padded.begin() + (size_t)(t * Bp));
+    DevBuf fresh;
+    if ((rc = dev_alloc(c, fresh, padded.size() * sizeof(double)))) return rc;
+    hipError_t e = hipMemcpyAsync(fresh.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        dev_free(fresh);
+        return fail(c, BI_ERR_HIP, "bi_set_real_counts: %s", hipGetErrorString(e));
+    }
+    real_store_swap(c, fresh, T);
+    return BI_OK;
+}
+
+int bi_set_asimov_counts(bi_ctx* c, int64_t H, const double* z, const double* rate_scale) {
+    int rc = real_check(c, "bi_set_asimov_counts", false);
+    if (rc) return rc;
+    if (H < 1) return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: H = %lld (at least one truth)", (long long)H);
+    if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+    const int S = c->S, d = c->d;
+    const int de = (int)c->eff_axes.size();
+    const int nc = 1 << de, NS = nc * S;
+    const int64_t Bp = c->Bp;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // every truth is screened before anything changes
+    {
+        PointGeom g;
+        std::vector<double> r((size_t)S);
+        for (int64_t h = 0; h < H; ++h) {
+            const int32_t bit = real_screen_point(c, z ? z + h * d : nullptr, rate_scale ? rate_scale + h * S : nullptr, g, r.data());
+            if (bit)
+                return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: truth %lld %s", (long long)h,
+                            bit == BI_ST_OUT_OF_BOUNDS ? "lies outside the anchor box" : "has unphysical rates");
+        }
+    }
+    std::vector<int64_t> rowoff((size_t)H * NS);
+    std::vector<double> coef((size_t)H * NS);
+    PointDerivs pd(c, false);
+    for (int64_t h = 0; h < H; ++h) {
+        pd.at(z ? z + h * d : nullptr, rate_scale ? rate_scale + h * S : nullptr);
+        int k = 0;
+        for (int corner = 0; corner < nc; ++corner)
+            for (int s = 0; s < S; ++s, ++k) {
+                rowoff[(size_t)(h * NS + k)] = ((pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s) * Bp;
+                coef[(size_t)(h * NS + k)] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];
+            }
+    }
+    ScratchBuf fresh, d_rowoff, d_coef, d_bad;
+    std::vector<int64_t> bad((size_t)H, 0);
+    if ((rc = dev_alloc(c, fresh, (size_t)(H * Bp) * sizeof(double))) || (rc = dev_upload(c, d_rowoff, rowoff)) ||
+        (rc = dev_upload(c, d_coef, coef)) || (rc = dev_upload(c, d_bad, bad)))
+        return rc;
+    hipError_t e = hipMemsetAsync(fresh.p, 0, (size_t)(H * Bp) * sizeof(double), c->stream);
+    for (int64_t h0 = 0; h0 < H && e == hipSuccess; h0 += 65535) {
+        const int64_t nh = std::min<int64_t>(65535, H - h0);
+        RealExpectArgs a{};
+        a.ps = (const double*)c->ps.p;
+        a.rowoff = (const int64_t*)d_rowoff.p + h0 * NS;
+        a.coef = (const double*)d_coef.p + h0 * NS;
+        a.out = (double*)fresh.p + h0 * Bp;
+        a.bad = (int64_t*)d_bad.p + h0;
+        a.B = c->B; a.Bp = Bp; a.NS = NS;
+        launch_real_expect(c, a, nh);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad.p, (size_t)H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_set_asimov_counts: %s", hipGetErrorString(e));
+    for (int64_t h = 0; h < H; ++h)
+        if (bad[(size_t)h])
+            return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: the expectation of truth %lld is negative or nan in bin %lld: no dataset",
+                        (long long)h, (long long)(bad[(size_t)h] - 1));
+    DevBuf keep = fresh;                 // (out of the scope's hands: the store owns it from here)
+    static_cast<DevBuf&>(fresh) = DevBuf{};
+    real_store_swap(c, keep, H);
+    return BI_OK;
+}
+
+int64_t bi_real_count_sets(bi_ctx* c) { return c ? c->real_T : 0; }
+
+int bi_download_real_counts(bi_ctx* c, int64_t t, double* out) {
+    int rc = real_check(c, "bi_download_real_counts", true);
+    if (rc) return rc;
+    if (t < 0 || t >= c->real_T || !out)
+        return fail(c, BI_ERR_INVALID, "bi_download_real_counts: dataset %lld outside [0,%lld) or out is NULL", (long long)t, (long long)c->real_T);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(out, (const double*)c->real_counts.p + t * c->Bp, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BI_OK;
+}
+
+int bi_eval_real(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* half_deviance,
+                 double* grad, int32_t* status) {
+    int rc = real_check(c, "bi_eval_real", true);
+    if (rc) return rc;
+    if (P < 0 || (P > 0 && !half_deviance)) return fail(c, BI_ERR_INVALID, "bad P / output pointer");
+    if (c->d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+    return real_eval(c, P, z, rate_scale, dataset, half_deviance, grad, status);
+}
+
+int bi_fit_batched_real(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                        const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                        const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
+                        const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
+                        double* f_out, int32_t* flags_out, int64_t* counters) {
+    int rc = real_check(c, "bi_fit_batched_real", true);
+    if (rc) return rc;
+    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi ||
+        !x_out || !f_out || !flags_out)
+        return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: bad arguments");
+    for (int j = 0; j < F; ++j)
+        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
+            (var_kind[j] != 0 && var_kind[j] != 1))
+            return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
+    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: n_kinks must be >= 0 and the kinks of a variable ascending");
+    if (prior_mean || prior_sigma || prior_const) {
+        if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: %s", why);
+        if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
+    }
+    for (int64_t p = 0; dataset && p < P; ++p)
+        if (dataset[p] < 0 || dataset[p] >= c->real_T)
+            return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: dataset[%lld] = %lld outside the %lld real-valued sets", (long long)p,
+                        (long long)dataset[p], (long long)c->real_T);
+    if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
+    DeviceObjective o{};
+    o.c = c; o.F = F; o.var_kind = var_kind; o.var_index = var_index; o.z0 = z0; o.scale0 = scale0; o.unit = unit; o.dataset = dataset;
+    o.prior_mean = prior_mean; o.prior_sigma = prior_sigma; o.prior_const = prior_const;
+    o.real = true;
+    try {
+        rc = minimize_batched(device_objective, &o, P, F, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x_out, f_out, flags_out, counters);
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "bi_fit_batched_real: out of host memory for %lld problems of %d variables", (long long)P, F);
+    } catch (const std::exception& e) {
+        return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: %s", e.what());
+    }
+    if (counters) counters[3] = o.evaluations;
+    return rc;
+}
+
+}  // extern "C"

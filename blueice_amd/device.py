@@ -440,6 +440,59 @@ class DeviceContext:
         self._check(self._lib.bi_expected_counts(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
         return out
 
+    # -- real-valued datasets: a store of its own beside the ordinary data (bi_set_real_counts ... bi_fit_batched_real) --
+    def set_real_counts(self, counts):
+        """counts: [*bins] (one set) or [T, *bins], every count finite and >= 0 (ValueError otherwise); None drops the store."""
+        if counts is None:
+            self._check(self._lib.bi_set_real_counts(self._h, 0, None))
+            return
+        c = as_f64(counts)
+        if c.size == 0 or c.size % self.B:
+            raise ValueError("counts size %d is not a positive multiple of B=%d" % (c.size, self.B))
+        T = c.size // self.B
+        self._check(self._lib.bi_set_real_counts(self._h, T, ptr(c.reshape(T, self.B))))
+
+    def set_asimov_counts(self, z, rate_scale=None):
+        """H Asimov datasets made on the device (bi_set_asimov_counts): set h holds the expectation at truth (z[h],
+        rate_scale[h]), bit for bit the row of `expected_counts`.  ValueError names a truth outside the anchor box, with
+        unphysical rates or with a negative / nan expectation; the previous store then stays.  -> H"""
+        H, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        self._check(self._lib.bi_set_asimov_counts(self._h, H, ptr(z), ptr(rate_scale)))
+        return H
+
+    @property
+    def real_count_sets(self):
+        return int(self._lib.bi_real_count_sets(self._h))
+
+    def download_real_counts(self, t=0):
+        out = np.empty(self.B, dtype=np.float64)
+        self._check(self._lib.bi_download_real_counts(self._h, int(t), ptr(out)))
+        return out
+
+    def eval_real(self, z, rate_scale=None, dataset=None, gradient=True):
+        """Half-deviance against the real-valued store (bi_eval_real) -> (half_deviance [P], d/dz [P, d], d/drate_scale
+        [P, S], status [P]); gradient=False: the two slope arrays are None (no limit on 1 + d + S then).  +inf outside the
+        box / for unphysical rates / where a filled bin expects nothing, nan where an expectation is negative."""
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        half = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, self.d + self.S), dtype=np.float64) if gradient else None
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_eval_real(self._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(half), ptr(grad), ptr(status)))
+        if not gradient:
+            return half, None, None, status
+        return half, grad[:, :self.d], grad[:, self.d:], status
+
+    def fit_batched_real(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters,
+                         priors=None):
+        """bi_fit_batched_real: `fit_batched` with f = half_deviance - p against the real-valued store."""
+        mean = sigma = const = None
+        if priors is not None:
+            mean, sigma, const = self._gauss_terms(priors, int(F), int(P))
+        self._check(self._lib.bi_fit_batched_real(self._h, int(P), int(F), ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
+                                                  ptr(unit), ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks), ptr(kinks), float(gtol),
+                                                  int(max_iter), ptr(mean), ptr(sigma), ptr(const), ptr(x), ptr(f), ptr(flags), ptr(counters)))
+        return 0
+
     @staticmethod
     def _gauss_terms(priors, F, n):
         """priors = (prior_mean [F], prior_sigma [F], prior_const [n] or None) -> the three as C-contiguous float64 arrays"""

@@ -18,6 +18,10 @@ Goodness of fit: `gof_statistics` evaluates the deviance and Pearson's chi2 of t
 `goodness_of_fit` calibrates either with toys fitted like the data, and `expected_counts` hands back the per-bin expectation
 the statistics are made of (bi_expected_counts).  Plain binned likelihoods only.
 
+Expected results without toys: `asimov_test_statistic`, `expected_upper_limit` and `expected_discovery_significance` profile
+the Asimov dataset of a truth (blueice_amd.asimov: n_b = mu_b(truth), real-valued counts in a device store of their own) and
+apply the asymptotic formulae of Cowan, Cranmer, Gross and Vitells.
+
 Profiled quantities -- `likelihood_ratio_scan` with floating nuisances, `one_parameter_interval` -- run on the batched
 profile-fit engine (blueice_amd.profile: all hypotheses advance together, one device call per optimiser iteration)
 whenever the likelihood offers batched evaluation; a user-supplied `bestfit_routine` keeps the reference's sequential
@@ -40,6 +44,7 @@ from .utils import is_numeric
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
            'toy_test_statistics', 'neyman_thresholds', 'expected_counts', 'expected_counts_points', 'gof_statistics', 'goodness_of_fit',
+           'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
            'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
            'plot_likelihood_ratio']
 
@@ -867,6 +872,80 @@ def likelihood_ratio_scan(lf, *space, bestfit_routine=None, fit_options=None, **
         for idx in np.ndindex(*grids[0].shape):
             ll[idx] = fit(lf, **dict(kwargs, **{n: float(g[idx]) for n, g in zip(names, grids)}))[1]
     return np.nanmax(ll) - ll
+
+
+# ---- expected results from the Asimov dataset ------------------------------------------------------------------------
+
+def _asimov_truth(lf, target, truth):
+    """-> (truth dict with the target in it, the target's value there); default: target = 0, everything else at its default"""
+    truth = {target: 0.0} if truth is None else dict(truth)
+    if target not in truth:
+        if target.endswith('_rate_multiplier'):
+            truth[target] = 1.0
+        else:
+            truth[target] = lf._kwargs_to_settings()[1][target]
+    return truth, float(truth[target])
+
+
+def _asimov_fits(view, target, hypotheses, truth, fit_options, livetime_days, fixed):
+    """-> (max over everything [scalar], max at every hypothesis of the target [H]) of the view's value -D + prior"""
+    options = dict(fit_options or {})
+    if livetime_days is not None:
+        options['livetime_days'] = livetime_days
+    start = {k: v for k, v in truth.items() if k not in fixed}
+    free = bestfit_batched(view, also_from=[start], **options, **fixed)[1][0]
+    nuisance_start = {k: v for k, v in start.items() if k != target}
+    try:
+        cond = bestfit_batched(view, points={target: hypotheses}, also_from=[nuisance_start], **options, **fixed)[1]
+    except NoOpimizationNecessary:            # nothing left to profile: plain evaluations
+        cond = np.asarray(view.eval_points(dict(fixed, **{target: hypotheses}), livetime_days=livetime_days))
+    return float(free), np.asarray(cond, dtype=float)
+
+
+def asimov_test_statistic(lf, target, hypotheses, truth=None, fit_options=None, livetime_days=None, **fixed):
+    """The profile-likelihood test statistic of every hypothesis of `target` on the Asimov dataset of `truth`:
+        q_A [H] = 2 (min_nu D(h, nu) - min D),     D = half-deviance + (-prior)
+    (Cowan, Cranmer, Gross, Vitells: sqrt(q_A) is the median significance with which h is excluded when `truth` holds; for
+    truth = the signal hypothesis and h = 0, the median discovery significance).  truth: dict of parameter values (default:
+    target = 0, everything else at its default) at which the data are made (`lf.asimov`); fixed (kwargs): parameters held
+    fixed in every fit; fit_options: options of `bestfit_batched`.  All hypotheses are profiled in ONE `bestfit_batched` call
+    on the view, on the native loop (bi_fit_batched_real); D is summed bin by bin without cancellation, so q_A is good to
+    ~1e-10 max(1, D), not to 1e-10 of a log-likelihood.  `lf`'s own data are not touched."""
+    hypotheses = np.atleast_1d(np.asarray(hypotheses, dtype=float))
+    truth, _ = _asimov_truth(lf, target, truth)
+    view = lf.asimov(livetime_days=livetime_days, **truth)
+    free, cond = _asimov_fits(view, target, hypotheses, truth, fit_options, livetime_days, fixed)
+    return 2.0 * (free - cond)
+
+
+def expected_upper_limit(lf, target, bound, confidence_level=0.9, n_sigma=(-2, -1, 0, 1, 2), truth=None, fit_options=None,
+                         livetime_days=None, **fixed):
+    """The expected upper limit on `target` and its band from the Asimov dataset of `truth` (default: background only,
+    target = 0) -> {N: limit} for every N of n_sigma: the N-sigma expected limit is where sqrt(q_A(mu)) crosses
+    Phi^-1(confidence_level) + N, i.e. `one_parameter_interval(view, target, bound, kind='upper', t_ppf=lambda h, q:
+    (norm.ppf(q) + N) ** 2)` on the Asimov view; N = 0 is the median.  An N with Phi^-1(confidence_level) + N <= 0 has no
+    crossing above the truth and returns the truth's value of the target.  bound: the far end of the search, as
+    `one_parameter_interval`."""
+    truth, at_truth = _asimov_truth(lf, target, truth)
+    view = lf.asimov(livetime_days=livetime_days, **truth)
+    more = dict(fixed)
+    if livetime_days is not None:
+        more['livetime_days'] = livetime_days
+    out = OrderedDict()
+    for n in n_sigma:
+        if stats.norm.ppf(confidence_level) + n <= 0:
+            out[n] = at_truth
+            continue
+        out[n] = one_parameter_interval(view, target, bound, confidence_level=confidence_level, kind='upper', fit_options=fit_options,
+                                        t_ppf=lambda h, q, n=n: (stats.norm.ppf(q) + n) ** 2, **more)
+    return out
+
+
+def expected_discovery_significance(lf, target, truth, fit_options=None, livetime_days=None, **fixed):
+    """The median significance with which target = 0 is rejected when `truth` (dict of parameter values: the signal
+    hypothesis) holds: sqrt(q_A(0)) on the Asimov dataset of `truth`."""
+    q = asimov_test_statistic(lf, target, [0.0], truth=truth, fit_options=fit_options, livetime_days=livetime_days, **fixed)[0]
+    return float(np.sqrt(max(q, 0.0)))
 
 
 _BESTFIT_ROUTINES = dict(scipy=bestfit_scipy, minuit=bestfit_minuit, emcee=bestfit_emcee, device=bestfit_device)

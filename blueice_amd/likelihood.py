@@ -1525,3 +1525,6 @@ from . import inference  # noqa: E402
 for _name in inference.__all__:
     for _cls in (LogLikelihoodBase, LogLikelihoodSum, LogAncillaryLikelihood, LogLikelihoodReParam):
         setattr(_cls, _name, getattr(inference, _name))
+
+# ... and the views on real-valued data (asimov.py: lf.asimov, lf.asimov_points, lf.real_data)
+from . import asimov as _asimov  # noqa: E402,F401

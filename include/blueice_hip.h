@@ -361,6 +361,37 @@ int bi_eval_gof(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scal
  * Beeston-Barlow only (there the expectation depends on the data): BI_ERR_INVALID otherwise. */
 int bi_expected_counts(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out);
 
+/* Real-valued datasets: Asimov data (n_b = mu_b(truth), Cowan, Cranmer, Gross, Vitells, Eur. Phys. J. C 71 (2011) 1554) and
+ * weighted histograms used as pseudo-data.  They live in a store of their own, per context and independent of its ordinary
+ * data, which stay resident and keep their semantics (a count that is no integer is -inf in every other entry point):
+ *   bi_set_real_counts       counts [T][B]: every count finite and >= 0, otherwise BI_ERR_INVALID naming dataset and bin;
+ *                            T = 0 or counts = NULL drops the store
+ *   bi_set_asimov_counts     H datasets made on the device: set h holds mu_b at truth (z[h], rate_scale[h]; rate_scale NULL:
+ *                            ones), bit for bit the row bi_expected_counts(per_source = 0) returns there.  Every truth is
+ *                            screened first (outside the anchor box, unphysical rates: BI_ERR_INVALID naming the truth), and
+ *                            a truth whose expectation is negative or nan in some bin (sources that may go negative) is
+ *                            refused as well
+ *   bi_real_count_sets       the number of sets in the store (0: none)
+ *   bi_download_real_counts  out [B] = set t
+ * A new store replaces the previous one; on any refusal the previous one stays as it was.  bi_destroy and a new model
+ * release it.  Binned likelihoods without Beeston-Barlow only: BI_ERR_INVALID with the reason otherwise.
+ *
+ * bi_eval_real: per point p, against set dataset[p] of the store (NULL: set 0; an index outside it: BI_ERR_INVALID),
+ *   half_deviance [P]        sum_b  (mu_b - n_b) - n_b log(mu_b / n_b)        (n_b = 0: mu_b)
+ *   grad [P][d + S] or NULL  sum_b  d_q mu_b (1 - n_b / mu_b)                 (n_b = 0: d_q mu_b)
+ * q over z_0 .. z_{d-1}, then the rate scales; on an anchor the slope of the cell the point is assigned to (bi_eval_grad's
+ * convention).  The log-likelihood ratio to the saturated model is -half_deviance: a constant below ll, summed bin by bin
+ * without the cancellation of two log-likelihoods.  n_b > 0 with mu_b = 0 gives +inf, a negative or nan mu_b nan; points
+ * outside the box or with unphysical rates get +inf and bi_eval_grad's status bits; grad is nan wherever the value is not
+ * finite.  With grad, 1 + d + S <= 16 (BI_ERR_INVALID otherwise); value-only calls have no such limit.  At the truth of an
+ * Asimov set the value and every slope are 0.0 exactly (the same fused multiply-add chain makes mu_b on both sides). */
+int bi_set_real_counts(bi_ctx* ctx, int64_t T, const double* counts);
+int bi_set_asimov_counts(bi_ctx* ctx, int64_t H, const double* z, const double* rate_scale);
+int64_t bi_real_count_sets(bi_ctx* ctx);
+int bi_download_real_counts(bi_ctx* ctx, int64_t t, double* out);
+int bi_eval_real(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                 double* half_deviance, double* grad, int32_t* status);
+
 /* The batched profile-fit engine's inner loop (host code): P minimisations of F variables each advance in lock-step, every
  * optimiser iteration ONE evaluation call over the problems still running -- what replaces the reference's loops of sequential
  * scipy fits (bestfit_scipy, blueice/inference.py:131-178, inside one_parameter_interval / plot_likelihood_ratio, :332-443).
@@ -409,6 +440,14 @@ int bi_fit_batched_gauss(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind,
                          const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
                          const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
                          double* f_out, int32_t* flags_out, int64_t* counters);
+
+/* ... against the real-valued store (bi_eval_real): f = half_deviance - p, `dataset` indexes the store; the three prior
+ * arrays may all be NULL (no terms).  Needs no ordinary data. */
+int bi_fit_batched_real(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                        const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                        const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
+                        const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
+                        double* f_out, int32_t* flags_out, int64_t* counters);
 
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
