@@ -8,5 +8,6 @@ from .priors import GaussianPrior  # noqa: F401
 from .source import Source, HistogramPdfSource, DensityEstimatingSource, MonteCarloSource  # noqa: F401
 from .likelihood import (LogLikelihoodBase, BinnedLogLikelihood, UnbinnedLogLikelihood,  # noqa: F401
                          LogLikelihoodSum, LogLikelihoodReParam, LogAncillaryLikelihood, toy_seed)
+from .grid import grid_scan, GridResult  # noqa: F401
 
 __version__ = '0.1.0'

@@ -75,6 +75,7 @@ SIGNATURES = {
                                     _p, _p, _p, _p]),
     'bi_sample_stretch_gauss': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
                                           _p, _p, _p, _p, _p, _p, _p]),
+    'bi_grid_reduce': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     'bi_eval_datasets': (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points_device': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),
@@ -104,6 +105,7 @@ SIGNATURES = {
     'bi_selftest_log': (C.c_int, [_p, _i64, _p, _p]),
     'bi_selftest_sort': (C.c_int, [_p, C.c_int, _i64, _p, _p, C.c_int, C.c_int, _p, _p]),
     'bi_selftest_scan': (C.c_int, [_p, C.c_int, _i64, _p, _i64, _p]),
+    'bi_selftest_grid_reduce': (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),
     'bi_measure_read_bandwidth': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, _p]),
     'bi_measure_stream_bandwidth': (C.c_int, [_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     'bi_measure_copy_bandwidth': (C.c_int, [_p, _i64, C.c_int, _p]),

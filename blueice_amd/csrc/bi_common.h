@@ -12,6 +12,7 @@
 //     tu_gof.hip          k_morph_gof (deviance + Pearson chi2 of one point per item), k_morph_expect   bi_k_gof.h
 //     tu_real.hip         k_morph_real (half-deviance + gradient against real-valued counts), k_real_expect   bi_k_real.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
+//     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
@@ -107,3 +108,9 @@ void launch_stretch_propose(bi_ctx* c, const StretchArgs& a);
 void launch_stretch_accept(bi_ctx* c, const StretchArgs& a);
 // k_stretch_start_density: the start walkers' log likelihoods (ll_prop) -> their log densities ll + p (ll)
 void launch_stretch_start_density(bi_ctx* c, const StretchArgs& a);
+// k_grid_points: the points [g0, g0 + n) of a tensor-product grid into the resident planner's layouts, with their additive terms
+void launch_grid_points(bi_ctx* c, const GridArgs& a);
+// k_grid_reduce: the chunk's results folded into the per-cell state; k_grid_init / k_grid_finish: the state's start and the outputs
+void launch_grid_reduce(bi_ctx* c, const GridArgs& a);
+void launch_grid_init(bi_ctx* c, const GridArgs& a);
+void launch_grid_finish(bi_ctx* c, const GridArgs& a);

@@ -193,6 +193,48 @@ struct StretchArgs {
     const double* prior_const; // [E]
 };
 
+// k_grid_points / k_grid_reduce / k_grid_finish (bi_k_grid.h): one chunk of a tensor-product grid; every pointer is device memory
+constexpr int kGridMaxVars = 16;
+
+struct GridArgs {
+    int64_t g0, n;             // the chunk: grid points [g0, g0 + n)
+    int64_t R, GK;             // points of a cell (product of the reduced node counts), points of a dataset entry (K R)
+    int F, d, S, n_keep;       // variables, shape parameters and sources of the model, kept variables (the first n_keep)
+    int32_t n_nodes[kGridMaxVars];   // nodes of variable j
+    int64_t node_off[kGridMaxVars];  // where they start in nodes / term / logw
+    int64_t stride[kGridMaxVars];    // grid points per step of variable j: i_j = (g / stride_j) mod n_j
+    int32_t var_kind[kGridMaxVars];  // 0: shape parameter var_index, 1: rate multiplier of source var_index
+    int32_t var_index[kGridMaxVars];
+    const double* z0;          // [E][d]  the entries' other shape settings
+    const double* scale0;      // [E][S]  ... rate scales of the sources whose multiplier is no variable
+    const double* unit;        // [E][S]  rate scale per unit multiplier
+    const int64_t* dataset;    // [E] or NULL
+    const double* nodes;       // concatenated
+    const double* term;        // concatenated or NULL
+    const double* logw;        // concatenated or NULL
+    double* z_dev;             // [n][d]   the chunk's points, in the layouts the resident planner reads
+    double* rs_dev;            // [n][S]
+    int64_t* ds_dev;           // [n]
+    double* p;                 // [n] or NULL (no term): the additive terms of the points
+    double* q;                 // [n] or NULL (no logw)
+    // the reduction
+    const double* ll;          // [n]  the chunk's result vector
+    const int32_t* st;         // [n]  its status words, or NULL (self-test)
+    int64_t cell0, n_cells;    // the cells the chunk touches: [cell0, cell0 + n_cells)
+    int cpb;                   // cells per block: 1 (four waves per cell) or 4 (one wave per cell)
+    double* m;                 // [cells] per-cell state: running maximum of u
+    double* s;                 // [cells] ... sum of exp(u - m)
+    double* best;              // [cells] ... maximum of t
+    int64_t* arg;              // [cells] ... smallest r that attains it, -1: none
+    int64_t* n_excl;           // [cells] ... excluded points
+    int32_t* nan_flag;         // [cells] ... a nan with status 0 was seen
+    // k_grid_finish
+    int64_t cells;
+    double* out_lm;            // [cells]
+    double* out_prof;          // [cells]
+    int64_t* out_arg;          // [cells]
+};
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

@@ -1,0 +1,231 @@
+// bi_grid.h -- the host loop of the gridded likelihood (bi_grid_reduce): the context's likelihood on a tensor-product grid of
+// F variables, reduced over the last F - n_keep of them on the device.  The grid is never held anywhere: k_grid_points writes
+// one chunk of it into the layouts the resident planner reads, the planner and the evaluation kernels of
+// bi_plan_points_resident / bi_run_plan take the points where they lie, k_grid_reduce folds the chunk's result vector and
+// status words into the per-cell state in HBM, and the three output arrays are copied to the host once, at the end.  What a
+// chunk costs on the host is the planner's (see bi_sampler.h): its counts, the status OR, making and destroying the plan.
+// (The reference's counterpart is the Python double loop of blueice/inference.py:424-432, one scalar call per grid point.)
+#pragma once
+
+namespace {
+
+constexpr int64_t kGridDefaultChunk = (int64_t)1 << 20, kGridMaxChunk = (int64_t)1 << 26, kGridMaxCells = (int64_t)1 << 24,
+                  kGridMaxPoints = (int64_t)1 << 48;
+constexpr int64_t kGridWaveCell = 256;      // cells of up to this many points are reduced by one wave each, larger ones by a block
+
+struct GridState {
+    ScratchBuf m, s, best, arg, n_excl, nan_flag, out_lm, out_prof, out_arg;
+};
+
+int grid_state_begin(bi_ctx* c, GridState& st, GridArgs& a, int64_t cells) {
+    const size_t n = (size_t)cells;
+    int rc;
+    if ((rc = dev_alloc(c, st.m, n * 8)) || (rc = dev_alloc(c, st.s, n * 8)) || (rc = dev_alloc(c, st.best, n * 8)) ||
+        (rc = dev_alloc(c, st.arg, n * 8)) || (rc = dev_alloc(c, st.n_excl, n * 8)) || (rc = dev_alloc(c, st.nan_flag, n * 4)) ||
+        (rc = dev_alloc(c, st.out_lm, n * 8)) || (rc = dev_alloc(c, st.out_prof, n * 8)) || (rc = dev_alloc(c, st.out_arg, n * 8)))
+        return rc;
+    a.cells = cells;
+    a.m = (double*)st.m.p; a.s = (double*)st.s.p; a.best = (double*)st.best.p;
+    a.arg = (int64_t*)st.arg.p; a.n_excl = (int64_t*)st.n_excl.p; a.nan_flag = (int32_t*)st.nan_flag.p;
+    a.out_lm = (double*)st.out_lm.p; a.out_prof = (double*)st.out_prof.p; a.out_arg = (int64_t*)st.out_arg.p;
+    launch_grid_init(c, a);
+    HIP_TRY(c, hipGetLastError());
+    return BI_OK;
+}
+
+// the cells that the chunk [g0, g0 + n) touches, and how they are dealt to the blocks
+void grid_chunk_cells(GridArgs& a) {
+    a.cell0 = a.g0 / a.R;
+    a.n_cells = (a.g0 + a.n - 1) / a.R - a.cell0 + 1;
+    a.cpb = a.R <= kGridWaveCell ? 4 : 1;
+}
+
+// the outputs from the state, one copy each; excluded: the sum of the cells' counts (or NULL)
+int grid_state_end(bi_ctx* c, GridArgs& a, double* log_marginal, double* profile, int64_t* argmax, int64_t* excluded) {
+    const size_t n = (size_t)a.cells;
+    launch_grid_finish(c, a);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<int64_t> h_excl(excluded ? n : 0);
+    HIP_TRY(c, hipMemcpyAsync(log_marginal, a.out_lm, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(profile, a.out_prof, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(argmax, a.out_arg, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (excluded) HIP_TRY(c, hipMemcpyAsync(h_excl.data(), a.n_excl, n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (excluded) *excluded = std::accumulate(h_excl.begin(), h_excl.end(), (int64_t)0);
+    return BI_OK;
+}
+
+int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_t n_total, const double* z0, const double* scale0,
+                const double* unit, const double* nodes, const double* term, const double* logw, int64_t chunk, double* log_marginal,
+                double* profile, int64_t* argmax, int64_t* counters) {
+    const int d = c->d, S = c->S;
+    const size_t nE = (size_t)E, nn = (size_t)n_total;
+    const int64_t G = E * a.GK;
+    if (chunk == 0) chunk = kGridDefaultChunk;
+    chunk = std::min(chunk, G);
+    ScratchBuf b_z0, b_scale0, b_unit, b_ds, b_nodes, b_term, b_logw, b_zp, b_rsp, b_dsp, b_llp, b_p, b_q;
+    int rc;
+    // (host copies that live until the uploads have been waited for)
+    const std::vector<double> h_z0 = host_copy(z0, nE * d, 0.0), h_scale0(scale0, scale0 + nE * S), h_unit(unit, unit + nE * S),
+                              h_nodes(nodes, nodes + nn), h_term = host_copy(term, term ? nn : 0, 0.0),
+                              h_logw = host_copy(logw, logw ? nn : 0, 0.0);
+    const std::vector<int64_t> h_ds = host_copy(dataset, nE, (int64_t)0);
+    if ((rc = dev_upload(c, b_z0, h_z0)) || (rc = dev_upload(c, b_scale0, h_scale0)) || (rc = dev_upload(c, b_unit, h_unit)) ||
+        (rc = dev_upload(c, b_ds, h_ds)) || (rc = dev_upload(c, b_nodes, h_nodes)) || (term && (rc = dev_upload(c, b_term, h_term))) ||
+        (logw && (rc = dev_upload(c, b_logw, h_logw))))
+        return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const size_t nc = (size_t)chunk;
+    if ((rc = dev_alloc(c, b_zp, nc * std::max(d, 1) * sizeof(double))) || (rc = dev_alloc(c, b_rsp, nc * S * sizeof(double))) ||
+        (rc = dev_alloc(c, b_dsp, nc * sizeof(int64_t))) || (rc = dev_alloc(c, b_llp, nc * sizeof(double))) ||
+        (term && (rc = dev_alloc(c, b_p, nc * sizeof(double)))) || (logw && (rc = dev_alloc(c, b_q, nc * sizeof(double)))))
+        return rc;
+    a.d = d; a.S = S;
+    a.z0 = (const double*)b_z0.p; a.scale0 = (const double*)b_scale0.p; a.unit = (const double*)b_unit.p;
+    a.dataset = dataset ? (const int64_t*)b_ds.p : nullptr;
+    a.nodes = (const double*)b_nodes.p;
+    a.term = term ? (const double*)b_term.p : nullptr;
+    a.logw = logw ? (const double*)b_logw.p : nullptr;
+    a.z_dev = (double*)b_zp.p; a.rs_dev = (double*)b_rsp.p; a.ds_dev = (int64_t*)b_dsp.p;
+    a.p = term ? (double*)b_p.p : nullptr;
+    a.q = logw ? (double*)b_q.p : nullptr;
+    a.ll = (const double*)b_llp.p;
+    GridState st;
+    if ((rc = grid_state_begin(c, st, a, G / a.R))) return rc;
+    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
+
+    for (a.g0 = 0; a.g0 < G; a.g0 += chunk) {
+        a.n = std::min(chunk, G - a.g0);
+        grid_chunk_cells(a);
+        launch_grid_points(c, a);
+        HIP_TRY(c, hipGetLastError());                          // (nothing is launched after a failed launch)
+        bi_plan* plan = nullptr;
+        if ((rc = plan_points_resident_impl(c, a.n, d > 0 ? (const double*)a.z_dev : nullptr, (const double*)a.rs_dev,
+                                            (const int64_t*)a.ds_dev, 0, 1, &plan, false)))
+            return rc;
+        int32_t any = 0;
+        if ((rc = bi_run_plan(c, plan, (double*)b_llp.p)) || (rc = bi_plan_status(c, plan, &any))) {
+            bi_plan_destroy(c, plan);
+            return rc;
+        }
+        if (counters) { ++counters[0]; counters[1] += a.n; counters[3] += bi_plan_launches(plan); }
+        if (any & BI_ST_INTERNAL) {
+            bi_plan_destroy(c, plan);
+            return fail(c, BI_ERR_HIP, "bi_grid_reduce: the device gave up waiting for a partial sum (in-launch reduction): GPU fault");
+        }
+        a.st = (const int32_t*)plan->status.p;
+        launch_grid_reduce(c, a);
+        const hipError_t e = hipGetLastError();
+        bi_plan_destroy(c, plan);                               // (waits for the stream: the reduction reads the plan's status words)
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_grid_reduce (reduce): %s", hipGetErrorString(e));
+    }
+    return grid_state_end(c, a, log_marginal, profile, argmax, counters ? &counters[2] : nullptr);
+}
+
+// true: a * b fits below `limit` (a, b >= 1), and *out = a * b
+bool grid_mul(int64_t a, int64_t b, int64_t limit, int64_t* out) {
+    if (a > limit / b) return false;
+    *out = a * b;
+    return *out <= limit;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_keep, const int32_t* var_kind, const int32_t* var_index,
+                   const double* z0, const double* scale0, const double* unit, const int32_t* n_nodes, const double* nodes,
+                   const double* term, const double* logw, int64_t chunk, double* log_marginal, double* profile, int64_t* argmax,
+                   int64_t* counters) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    c->plan_refused = 0;
+    if (F < 1 || F > kGridMaxVars) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: need 1 <= F <= %d variables (got %d)", kGridMaxVars, F);
+    if (n_keep < 0 || n_keep > F) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: n_keep must lie in [0, F = %d] (got %d)", F, n_keep);
+    if (E < 1) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: need E >= 1 (got %lld)", (long long)E);
+    if (chunk < 0 || chunk > kGridMaxChunk) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: chunk must lie in [0, 2^26] (got %lld)", (long long)chunk);
+    if (!var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !n_nodes || !nodes || !log_marginal || !profile || !argmax)
+        return fail(c, BI_ERR_INVALID, "bi_grid_reduce: NULL argument");
+    GridArgs a{};
+    a.F = F; a.n_keep = n_keep;
+    for (int j = 0; j < F; ++j) {
+        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
+            (var_kind[j] != 0 && var_kind[j] != 1))
+            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
+        for (int i = 0; i < j; ++i)
+            if (var_kind[i] == var_kind[j] && var_index[i] == var_index[j])
+                return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variables %d and %d are the same parameter", i, j);
+        if (n_nodes[j] < 1) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variable %d has %d nodes: need at least 1", j, (int)n_nodes[j]);
+        a.var_kind[j] = var_kind[j]; a.var_index[j] = var_index[j]; a.n_nodes[j] = n_nodes[j];
+    }
+    int64_t n_total = 0, K = 1, R = 1, cells = 0, G = 0;
+    for (int j = 0; j < F; ++j) {
+        a.node_off[j] = n_total;
+        n_total += n_nodes[j];
+        if (!grid_mul(j < n_keep ? K : R, n_nodes[j], kGridMaxPoints, j < n_keep ? &K : &R))
+            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: the grid has more than 2^48 points");
+    }
+    if (!grid_mul(E, K, kGridMaxCells, &cells))
+        return fail(c, BI_ERR_INVALID, "bi_grid_reduce: E * K (%lld dataset entries x %lld kept points) is more than 2^24 cells", (long long)E, (long long)K);
+    if (!grid_mul(cells, R, kGridMaxPoints, &G)) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: the grid has more than 2^48 points");
+    for (int64_t stride = 1, j = F - 1; j >= 0; --j) {
+        a.stride[j] = stride;
+        stride *= n_nodes[j];
+    }
+    a.R = R; a.GK = K * R;
+    for (int64_t i = 0; i < n_total; ++i) {
+        if (!std::isfinite(nodes[i])) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: node %lld is not finite (%g)", (long long)i, nodes[i]);
+        if (term && !(term[i] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: term %lld is %g: a term is finite or -inf", (long long)i, term[i]);
+        if (logw && !(logw[i] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: logw %lld is %g: a log weight is finite or -inf", (long long)i, logw[i]);
+    }
+    if (multi_set(c) && (E > 1 || (dataset && dataset[0] != 0)))
+        return refuse_sets(c, "bi_grid_reduce with more than one dataset entry, or with another set than 0,");
+    if (dataset)
+        for (int64_t e = 0; e < E; ++e)
+            if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: dataset %lld of entry %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);
+    HIP_TRY(c, hipSetDevice(c->device));
+    try {
+        return grid_reduce(c, E, dataset, a, n_total, z0, scale0, unit, nodes, term, logw, chunk, log_marginal, profile, argmax, counters);
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "bi_grid_reduce: out of host memory");
+    }
+}
+
+// the reduction kernels of bi_grid_reduce on caller data: t [cells][R] in the place of ll + p, q [cells][R] or NULL, folded in
+// chunks of `chunk` values (0: all at once)
+int bi_selftest_grid_reduce(bi_ctx* c, int64_t cells, int64_t R, int64_t chunk, const double* t, const double* q, double* log_marginal,
+                            double* profile, int64_t* argmax) {
+    if (!c || cells < 1 || cells > kGridMaxCells || R < 1 || R > ((int64_t)1 << 28) / cells || chunk < 0 || !t || !log_marginal || !profile || !argmax)
+        return BI_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t G = cells * R;
+    if (chunk == 0 || chunk > G) chunk = G;
+    ScratchBuf dt, dq;
+    int rc;
+    if ((rc = dev_alloc(c, dt, (size_t)G * 8)) || (q && (rc = dev_alloc(c, dq, (size_t)G * 8)))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(dt.p, t, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    if (q) HIP_TRY(c, hipMemcpyAsync(dq.p, q, (size_t)G * 8, hipMemcpyHostToDevice, c->stream));
+    GridArgs a{};
+    a.R = R;
+    GridState st;
+    if ((rc = grid_state_begin(c, st, a, cells))) return rc;
+    for (a.g0 = 0; a.g0 < G; a.g0 += chunk) {
+        a.n = std::min(chunk, G - a.g0);
+        grid_chunk_cells(a);
+        a.ll = (const double*)dt.p + a.g0;
+        a.q = q ? (double*)dq.p + a.g0 : nullptr;
+        launch_grid_reduce(c, a);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
+            return fail(c, BI_ERR_HIP, "bi_selftest_grid_reduce: %s", hipGetErrorString(e));
+        }
+    }
+    rc = grid_state_end(c, a, log_marginal, profile, argmax, nullptr);
+    if (rc) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // extern "C"

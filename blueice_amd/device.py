@@ -558,6 +558,62 @@ class DeviceContext:
         self._check(rc)
         return chain, ll, n_acc, counters
 
+    def grid_reduce(self, kind, index, z0, scale0, unit, dataset, n_keep, nodes, term=None, logw=None, chunk=0):
+        """bi_grid_reduce: this context's likelihood on the tensor-product grid of `nodes` (one 1-d array per variable; kind /
+        index as `fit_batched`), reduced over the variables from n_keep on.  z0 [E, d], scale0 / unit [E, S] (rows broadcast),
+        dataset [E] or None (one entry, dataset 0); term / logw: None or one array per variable, shaped as its nodes.
+        -> (log_marginal [E, K], profile [E, K], argmax [E, K], counters [4]: chunks, evaluations, excluded points, launches)."""
+        kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
+        nodes = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in nodes]
+        F, n_keep = len(nodes), int(n_keep)
+        if len(kind) != F or len(index) != F or any(v.ndim != 1 for v in nodes):
+            raise ValueError("kind, index and nodes must have one entry per variable, every entry of nodes one-dimensional")
+        n_nodes = np.array([len(v) for v in nodes], dtype=np.int32)
+
+        def flat(arrays, what):
+            if arrays is None:
+                return None
+            arrays = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in arrays]
+            if len(arrays) != F or any(v.shape != w.shape for v, w in zip(arrays, nodes)):
+                raise ValueError("%s must hold one array per variable, shaped as its nodes" % what)
+            return np.ascontiguousarray(np.concatenate(arrays)) if F else np.zeros(0)
+        term, logw = flat(term, 'term'), flat(logw, 'logw')
+        nodes_flat = np.ascontiguousarray(np.concatenate(nodes)) if F else np.zeros(0)
+        if dataset is not None:
+            dataset = np.ascontiguousarray(np.atleast_1d(np.asarray(dataset, dtype=np.int64)))
+        E = 1 if dataset is None else len(dataset)
+        z0 = np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64).reshape(-1, self.d), (E, self.d))) if self.d else np.zeros((E, 0))
+        scale0 = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        unit = np.ascontiguousarray(np.broadcast_to(np.asarray(unit, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        K = int(np.prod(n_nodes[:max(0, min(n_keep, F))], dtype=np.int64)) if F and np.all(n_nodes >= 1) else 1
+        if E * K > 2 ** 24:                                   # (refused by the library too; here before the outputs are made)
+            raise ValueError("bi_grid_reduce: E * K (%d dataset entries x %d kept points) is more than 2^24 cells" % (E, K))
+        log_marginal, profile = np.empty((E, K)), np.empty((E, K))
+        argmax = np.empty((E, K), dtype=np.int64)
+        counters = np.zeros(4, dtype=np.int64)
+        rc = self._lib.bi_grid_reduce(self._h, E, ptr(dataset), F, n_keep, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
+                                      ptr(unit), ptr(n_nodes), ptr(nodes_flat), ptr(term), ptr(logw), int(chunk), ptr(log_marginal),
+                                      ptr(profile), ptr(argmax), ptr(counters))
+        if rc == _capi.ERR_INVALID:
+            msg = self._lib.bi_last_error(self._h).decode()
+            if self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:             # the resident planner's two refusals
+                raise PlannerRefused(msg)
+        self._check(rc)
+        return log_marginal, profile, argmax, counters
+
+    def selftest_grid_reduce(self, t, q=None, chunk=0):
+        """bi_selftest_grid_reduce: t [cells, R] (and q, or None) through the reduction kernels of `grid_reduce`, in chunks of
+        `chunk` values -> (log_marginal [cells], profile [cells], argmax [cells])."""
+        t = as_f64(t)
+        if t.ndim != 2:
+            raise ValueError("t must be [cells, R]")
+        q = None if q is None else as_f64(q, t.shape)
+        cells, R = t.shape
+        log_marginal, profile, argmax = np.empty(cells), np.empty(cells), np.empty(cells, dtype=np.int64)
+        self._check(self._lib.bi_selftest_grid_reduce(self._h, cells, R, int(chunk), ptr(t), ptr(q), ptr(log_marginal), ptr(profile),
+                                                      ptr(argmax)))
+        return log_marginal, profile, argmax
+
     def eval_datasets(self, z, rate_scale=None, t0=0, t1=None):
         """One parameter point against datasets [t0, t1) -> (ll [t1-t0], status)."""
         t1 = self.T if t1 is None else int(t1)

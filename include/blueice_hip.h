@@ -499,6 +499,36 @@ int bi_sample_stretch_gauss(bi_ctx* ctx, int64_t E, int W, int F, const int32_t*
                             const double* prior_mean, const double* prior_sigma, const double* prior_const, double* chain,
                             double* ll, int64_t* n_accepted, int64_t* counters);
 
+/* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
+ * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
+ * lists one after the other; any order, finite).  The first n_keep variables are kept, the others reduced:
+ *   K = prod_{j < n_keep} n_j,  R = prod_{j >= n_keep} n_j,  grid point g = (e K + k) R + r  (variable 0 slowest, the entry e
+ *   slowest of all); entry e evaluates dataset[e] (NULL: dataset 0) with its other settings z0[e] [d], scale0[e] [S]; a
+ *   shape variable sets z_i = node, a rate variable rate_scale_s = node unit[e][s].
+ *   p_g = sum_j term_j[i_j]  (j ascending, from 0.0; `term` laid out as `nodes`: e.g. log priors at the nodes; NULL: none)
+ *   q_g = sum_{j >= n_keep} logw_j[i_j]  (log quadrature weights; NULL: none)
+ *   t_g = ll_g + p_g,  u_g = t_g + q_g   (binary64, every addition rounded on its own)
+ *   profile[e][k] = max_r t_g,  argmax[e][k] = the smallest r that attains it
+ *   log_marginal[e][k] = m + log sum_r exp(u_g - m),  m = max_r u_g
+ * A point is EXCLUDED from its cell (and counted) when its status word is not 0 (outside the anchor box, unphysical rates, a
+ * Beeston-Barlow assertion), when its ll is -inf, or when one of its terms is -inf.  A cell with no point left has -inf, -inf
+ * and argmax -1; a ll of nan with status 0 makes both outputs of its cell nan and its argmax -1.  A log weight of -inf takes a
+ * point out of the marginal only.
+ * The grid is produced, evaluated and reduced in chunks of `chunk` points (0: 2^20) that never leave the device:
+ * k_grid_points, the planner and kernels of bi_plan_points_resident / bi_run_plan, k_grid_reduce (an online log-sum-exp
+ * and max / argmax per cell, state in HBM; a cell may lie inside one chunk, straddle two or span many).  The host reads the
+ * plan's status OR once per chunk and the three output arrays [E][K] once at the end.  No atomics: every sum has a fixed
+ * order, so a call is bitwise reproducible for a given chunk; different chunks regroup the sums (agreement to rounding,
+ * profile and argmax identical).  counters [4] or NULL: chunks, evaluations, excluded points, evaluation launches.
+ * Errors (BI_ERR_INVALID, reason in bi_last_error): F < 1 or > 16, n_keep outside [0, F], a node count < 1, a node that is
+ * not finite, +inf or nan in term or logw, E K > 2^24 cells, more than 2^48 points, chunk outside [0, 2^26], a variable that
+ * is no parameter of the model or appears twice, and whatever bi_plan_points_resident refuses (as bi_sample_stretch). */
+int bi_grid_reduce(bi_ctx* ctx, int64_t E, const int64_t* dataset /*[E] or NULL*/, int F, int n_keep, const int32_t* var_kind,
+                   const int32_t* var_index, const double* z0 /*[E][d]*/, const double* scale0 /*[E][S]*/,
+                   const double* unit /*[E][S]*/, const int32_t* n_nodes /*[F]*/, const double* nodes, const double* term,
+                   const double* logw, int64_t chunk, double* log_marginal /*[E][K]*/, double* profile /*[E][K]*/,
+                   int64_t* argmax /*[E][K]*/, int64_t* counters /*[4] or NULL*/);
+
 /* One parameter point against datasets [t0, t1): the toy-MC form.  mu_b / log mu_b are computed
  * once and every dataset reduces sum_b xlogy(n, mu) against them.  Not available with
  * Beeston-Barlow (mu then depends on the data).  out [t1 - t0]. */
@@ -603,6 +633,11 @@ int bi_selftest_log(bi_ctx* ctx, int64_t n, const double* x, double* out);
 int bi_selftest_sort(bi_ctx* ctx, int kind, int64_t n, const void* keys, const void* vals, int begin_bit, int end_bit, void* keys_out,
                      void* vals_out);
 int bi_selftest_scan(bi_ctx* ctx, int kind, int64_t n, const void* in, int64_t init, void* out);
+/* self-test of the reduction kernels of bi_grid_reduce on caller data: t [cells][R] stands for ll + p (-inf: an excluded
+ * point, nan: a nan), q [cells][R] or NULL for the log weights; the values are folded in chunks of `chunk` (0: all at once)
+ * exactly as a grid's result vectors are -> log_marginal, profile, argmax [cells] */
+int bi_selftest_grid_reduce(bi_ctx* ctx, int64_t cells, int64_t R, int64_t chunk, const double* t, const double* q,
+                            double* log_marginal, double* profile, int64_t* argmax);
 
 /* ---- measurement ---------------------------------------------------------------------------
  * While enabled, every morph+reduce launch is bracketed by HIP events on the context stream;
