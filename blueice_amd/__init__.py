@@ -9,5 +9,6 @@ from .source import Source, HistogramPdfSource, DensityEstimatingSource, MonteCa
 from .likelihood import (LogLikelihoodBase, BinnedLogLikelihood, UnbinnedLogLikelihood,  # noqa: F401
                          LogLikelihoodSum, LogLikelihoodReParam, LogAncillaryLikelihood, toy_seed)
 from .grid import grid_scan, GridResult  # noqa: F401
+from .coarse import CoarseBinning  # noqa: F401
 
 __version__ = '0.1.0'

@@ -1,0 +1,200 @@
+"""Coarse views of a binned likelihood: projections on one or two analysis dimensions, a rebinned analysis space, a signal box.
+
+`CoarseBinning` is the host specification: a tensor product of groups of adjacent fine bins, one list of boundaries per
+analysis dimension.  `expected_coarse` / `expected_coarse_points` return the morphed expectation summed over the cells,
+`coarse_counts` the resident data summed the same way -- both reduced on the device (bi_expected_coarse, bi_coarse_counts:
+the corner rows of a point are streamed once and summed as they arrive, the fine bins never cross the bus) --, and
+`coarse_statistics` forms the deviance and Pearson's chi2 over the cells, which `gof_statistics(..., binning=)` and
+`goodness_of_fit(..., binning=)` use (blueice_amd.inference).  Plain binned likelihoods only.
+
+    box = CoarseBinning(lf, keep=['cs1'], rebin={'cs1': 4}, ranges={'cs2': (2.0, 3.5)})
+    mu = lf.expected_coarse(box, per_source=True, **best)            # [S, n_cs1 / 4]
+    band = np.percentile(lf.expected_coarse_points(box, samples), [16, 50, 84], axis=0)
+"""
+import numpy as np
+
+from .exceptions import NotPreparedException
+
+__all__ = ['CoarseBinning', 'expected_coarse', 'expected_coarse_points', 'coarse_counts', 'coarse_statistics']
+
+EDGE_TOLERANCE = 1e-9          # an edge value must lie within this fraction of the bin's width of a fine edge
+
+
+def _binned_for_gof(lf, what, prepared=True):
+    """-> lf if it is a binned likelihood without Beeston-Barlow; NotImplementedError otherwise (before any device work).
+    prepared=False: the type alone is checked (a `CoarseBinning` needs the analysis space only, fixed when the likelihood is made)"""
+    from .likelihood import BinnedLogLikelihood
+    if not isinstance(lf, BinnedLogLikelihood):
+        raise NotImplementedError("%s needs a BinnedLogLikelihood: a %s has no bins of its own" % (what, type(lf).__name__))
+    if lf.model_statistical_uncertainty_handling is not None:
+        raise NotImplementedError("%s is not defined with Beeston-Barlow (model_statistical_uncertainty_handling = %r): the "
+                                  "expectation depends on the data" % (what, lf.model_statistical_uncertainty_handling))
+    if prepared and not lf.is_prepared:
+        if len(lf.shape_parameters):
+            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+        lf.prepare()            # nothing to morph: preparation is trivial
+    return lf
+
+
+def _edge_index(name, fine, value):
+    """-> the index of the fine edge `value` coincides with; ValueError if there is none"""
+    value = float(value)
+    i = int(np.argmin(np.abs(fine - value)))
+    widths = np.diff(fine)
+    width = min(widths[max(i - 1, 0)], widths[min(i, len(widths) - 1)])
+    if not abs(fine[i] - value) <= EDGE_TOLERANCE * width:
+        raise ValueError("%r: %r is not an edge of the fine binning (nearest: %r)" % (name, value, float(fine[i])))
+    return i
+
+
+class CoarseBinning:
+    """A coarse binning of the analysis space of a plain `BinnedLogLikelihood`.
+
+    keep    names of the analysis dimensions that stay as axes of the result, in the order of the analysis space; the others
+            are summed over.  Default: all.
+    rebin   name -> int n: merge n adjacent fine bins, starting at the first bin of the range, the last group possibly
+            shorter; or name -> ascending edge values, each of which must coincide with a fine edge to within 1e-9 of that
+            bin's width (ValueError otherwise).  Kept dimensions only.
+    ranges  name -> (lo, hi) edge values, checked the same way: fine bins outside belong to no cell.  For kept and summed
+            dimensions alike -- a signal box is one cell.
+
+    dims, shape, edges (per kept dimension), n_cells; groups: per ANALYSIS dimension the ascending fine-bin boundaries
+    e_0 < ... < e_m (group g holds the fine bins e_g <= i < e_g+1; a summed dimension has one group); fine_shape.
+    `bin_map()` is the executable specification: fine flat index -> coarse flat index, both in C order."""
+
+    def __init__(self, lf, keep=None, rebin=None, ranges=None):
+        _binned_for_gof(lf, 'CoarseBinning', prepared=False)
+        space = [(str(n), np.asarray(e, dtype=float)) for n, e in lf.base_model.config['analysis_space']]
+        names = [n for n, _ in space]
+        keep = names if keep is None else ([keep] if isinstance(keep, str) else list(keep))
+        rebin, ranges = dict(rebin or {}), dict(ranges or {})
+        for what, given in (('keep', keep), ('rebin', rebin), ('ranges', ranges)):
+            for n in given:
+                if n not in names:
+                    raise ValueError("%s: %r is not a dimension of the analysis space %s" % (what, n, names))
+        if len(set(keep)) != len(keep):
+            raise ValueError("keep names a dimension twice: %s" % (keep,))
+        self.fine_shape = tuple(len(e) - 1 for _, e in space)
+        self.fine_dims, self.fine_edges = names, [e for _, e in space]
+        self.dims, self.edges, self.groups = [], [], []
+        for name, fine in space:
+            n_fine = len(fine) - 1
+            lo, hi = 0, n_fine
+            if name in ranges:
+                a, b = ranges[name]
+                lo, hi = _edge_index(name, fine, a), _edge_index(name, fine, b)
+                if not lo < hi:
+                    raise ValueError("%r: the range (%r, %r) holds no bin" % (name, a, b))
+            if name not in keep:
+                if name in rebin:
+                    raise ValueError("%r is summed over: it cannot be rebinned (keep it, or give its range)" % name)
+                bounds = [lo, hi]
+            elif name not in rebin:
+                bounds = list(range(lo, hi + 1))
+            elif np.ndim(rebin[name]) == 0:
+                n = int(rebin[name])
+                if n < 1 or n != rebin[name]:
+                    raise ValueError("%r: rebin by %r" % (name, rebin[name]))
+                bounds = list(range(lo, hi, n)) + [hi]
+            else:
+                bounds = [_edge_index(name, fine, v) for v in np.asarray(rebin[name], dtype=float).ravel()]
+                if len(bounds) < 2 or np.any(np.diff(bounds) <= 0):
+                    raise ValueError("%r: the rebinned edges must be at least two, ascending" % name)
+                if bounds[0] < lo or bounds[-1] > hi:
+                    raise ValueError("%r: the rebinned edges leave the range" % name)
+            self.groups.append(np.asarray(bounds, dtype=np.int32))
+            if name in keep:
+                self.dims.append(name)
+                self.edges.append(fine[self.groups[-1]])
+        self.shape = tuple(len(e) - 1 for e in self.edges)
+        self.n_cells = int(np.prod(self.shape, dtype=np.int64))
+
+    def bin_map(self):
+        """int32 [B]: the coarse flat index of every fine bin (C order, as `lf.bin_shape` implies), -1 where it is left out"""
+        cell = np.zeros(self.fine_shape, dtype=np.int64)
+        out = np.zeros(self.fine_shape, dtype=bool)
+        for axis, (n, bounds) in enumerate(zip(self.fine_shape, self.groups)):
+            g = np.searchsorted(bounds, np.arange(n), side='right') - 1
+            left_out = (np.arange(n) < bounds[0]) | (np.arange(n) >= bounds[-1])
+            shape = [1] * len(self.fine_shape)
+            shape[axis] = n
+            cell = cell * (len(bounds) - 1) + np.where(left_out, 0, g).reshape(shape)
+            out = out | left_out.reshape(shape)
+        return np.where(out, -1, cell).astype(np.int32).ravel()
+
+    def attach(self, lf, what):
+        """Refuse what has no coarse view, then make this the coarse binning of lf's device context -- a no-op while the context
+        still holds it (a new model releases it).  ValueError for a likelihood with another analysis space."""
+        _binned_for_gof(lf, what)
+        space = lf.base_model.config['analysis_space']
+        if [str(n) for n, _ in space] != self.fine_dims or tuple(lf.bin_shape) != self.fine_shape or \
+                not all(np.array_equal(np.asarray(e, dtype=float), mine) for (_, e), mine in zip(space, self.fine_edges)):
+            raise ValueError("%s: the binning was made for another analysis space (dimensions %s, bins %s)" % (what, self.fine_dims, self.fine_shape))
+        cells = lf.ctx.set_coarse_binning(self.fine_shape, self.groups)
+        assert cells == self.n_cells
+        return lf
+
+
+def _prepared(lf, binning, what):
+    if not isinstance(binning, CoarseBinning):
+        _binned_for_gof(lf, what)                   # (the likelihood's own refusal comes first)
+        raise TypeError("%s needs a CoarseBinning, not a %s" % (what, type(binning).__name__))
+    return binning.attach(lf, what)
+
+
+def expected_coarse_points(lf, binning, points, per_source=False, livetime_days=None):
+    """The expected events per cell of `binning` at P parameter points: points = dict parameter name -> array [P] (scalars
+    broadcast; absent parameters take their defaults), as `expected_counts_points` -> mu [P, *binning.shape], or
+    [P, S, *binning.shape] with per_source.  The host terms (live time, rate multipliers, efficiencies) are those of
+    `expected_counts_points`; the morph and the sum over the fine bins of every cell run on the device in one pass over the
+    corner rows (bi_expected_coarse).  A point outside the anchor box or with unphysical rates gets nan in every cell."""
+    _prepared(lf, binning, 'expected_coarse_points')
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    mu, _ = lf.ctx.expected_coarse(binning.n_cells, z if z.shape[1] else None, scale, per_source=per_source)
+    return mu.reshape(mu.shape[:-1] + binning.shape)
+
+
+def expected_coarse(lf, binning, per_source=False, livetime_days=None, **params):
+    """The expected events per cell of `binning` at one parameter point -> array of `binning.shape`, or [S, *binning.shape]
+    with per_source: a projection of the fitted model with its components.  As `expected_coarse_points`, with the host terms
+    of the scalar call `lf(**params)`; nan outside the anchor box or where the rates are unphysical."""
+    _prepared(lf, binning, 'expected_coarse')
+    _, zs, scale = lf._host_terms(livetime_days, params)
+    shape = ((len(lf.source_name_list),) if per_source else ()) + binning.shape
+    if zs is None:
+        return np.full(shape, np.nan)
+    mu, _ = lf.ctx.expected_coarse(binning.n_cells, zs if len(zs) else None, scale[None, :], per_source=per_source)
+    return mu[0].reshape(shape)
+
+
+def coarse_counts(lf, binning, datasets=None):
+    """The resident datasets' counts per cell of `binning` -> [T, *binning.shape] (datasets: indices, None: all), summed on
+    the device from whichever form the data are held in (dense, or the lists of device-generated toys)."""
+    _prepared(lf, binning, 'coarse_counts')
+    if not lf.is_data_set:
+        raise NotPreparedException("coarse_counts requires you to first set the data using set_data()")
+    n = lf.ctx.coarse_counts(binning.n_cells, datasets)
+    return n.reshape((len(n),) + binning.shape)
+
+
+def coarse_statistics(n, mu):
+    """The goodness-of-fit statistics over coarse cells, from counts n and expectations mu (arrays [..., C], broadcast against
+    each other) -> (deviance [...], pearson [...]), in the cancellation-free per-cell forms of the device's `gof_terms`:
+        half-deviance   n > 0: (mu - n) - n log(mu / n)     n = 0: mu
+        Pearson         n > 0: (n - mu)^2 / mu              n = 0: mu
+    n = mu = 0 gives 0 in both, n > 0 with mu = 0 gives +inf in both; a negative or nan mu (or a nan n) gives nan in both, a
+    negative or non-integer n +inf in both."""
+    n, mu = np.broadcast_arrays(np.asarray(n, dtype=float), np.asarray(mu, dtype=float))
+    hit = n > 0
+    with np.errstate(all='ignore'):
+        safe_n = np.where(hit, n, 1.0)
+        half = np.where(hit, (mu - n) - n * np.log(np.where(hit, mu, 1.0) / safe_n), mu)
+        pearson = np.where(hit, (n - mu) ** 2 / np.where(hit & (mu == 0), 1.0, mu), mu)
+        empty_expectation = hit & (mu == 0)
+        half = np.where(empty_expectation, np.inf, half)
+        pearson = np.where(empty_expectation, np.inf, pearson)
+        no_count = (n < 0) | (n != np.floor(n))
+        half, pearson = np.where(no_count, np.inf, half), np.where(no_count, np.inf, pearson)
+        bad = ~(mu >= 0) | np.isnan(n)
+        half, pearson = np.where(bad, np.nan, half), np.where(bad, np.nan, pearson)
+    return 2.0 * half.sum(axis=-1), pearson.sum(axis=-1)

@@ -13,6 +13,7 @@
 //     tu_real.hip         k_morph_real (half-deviance + gradient against real-valued counts), k_real_expect   bi_k_real.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
+//     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
@@ -114,3 +115,7 @@ void launch_grid_points(bi_ctx* c, const GridArgs& a);
 void launch_grid_reduce(bi_ctx* c, const GridArgs& a);
 void launch_grid_init(bi_ctx* c, const GridArgs& a);
 void launch_grid_finish(bi_ctx* c, const GridArgs& a);
+// k_morph_coarse + k_coarse_finish: the expectation (or a row of counts) of n_items (<= 65 535) items summed over the groups of a coarse binning
+void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items);
+// k_coarse_list + k_coarse_table: the non-empty-bin lists of n (<= 65 535) datasets into the cells, out [n][C] (device memory)
+void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out);

@@ -125,6 +125,20 @@ struct bi_ctx {
     DevBuf real_counts;
     int64_t real_T = 0;
 
+    // the coarse binning of bi_set_coarse_binning (bi_coarse.h): tensor-product groups of fine bins, b = r L + x with L the
+    // fine bins of the last analysis axis.  Released by a new model.
+    struct Coarse {
+        bool set = false;
+        int64_t C = 0, CR = 0, Cx = 0;   // cells = coarse rows (leading axes) x coarse columns (last axis)
+        int64_t L = 0, NR = 0;           // fine bins of the last axis, fine rows
+        int64_t x_lo = 0, Lx = 0;        // the fine columns [x_lo, x_lo + Lx) that belong to a cell
+        int64_t max_rows = 0;            // fine rows of the longest coarse row
+        int64_t max_width = 0;           // fine columns of the widest column group
+        DevBuf row_off, row_list;        // [CR + 1] int64, [rows] int32: the fine rows of every coarse row (left-out rows are absent)
+        DevBuf xb;                       // [Cx + 1] int32: the column groups' boundaries
+        DevBuf row_map, x_map;           // [NR], [L] int32: fine row -> coarse row, fine column -> coarse column, -1 = left out
+    } coarse;
+
     // model statistics (for the sparse forms)
     std::vector<double> h_rowsum;  // [A*S] sum over bins of every ps row
     std::vector<double> h_rowmin;  // [A*S] smallest entry of every ps row
@@ -333,6 +347,12 @@ struct ScratchBuf : DevBuf {
     ScratchBuf& operator=(const ScratchBuf&) = delete;
     ~ScratchBuf() { dev_free(*this); }
 };
+
+void release_coarse(bi_ctx* c) {
+    dev_free(c->coarse.row_off); dev_free(c->coarse.row_list); dev_free(c->coarse.xb); dev_free(c->coarse.row_map); dev_free(c->coarse.x_map);
+    c->coarse.set = false;
+    c->coarse.C = 0;
+}
 
 void drop_recycle_cache(bi_ctx* c) {
     (void)hipGetLastError();

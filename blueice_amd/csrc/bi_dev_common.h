@@ -148,6 +148,39 @@ struct ExpectArgs {
     int R;                     // groups per item: 1 (every row) or S
 };
 
+// k_morph_coarse / k_coarse_finish (bi_k_coarse.h)
+struct CoarseArgs {
+    const double* ps;          // [rows][Bp] the dense template tensor (or the dense counts [T][Bp])
+    const int64_t* rowoff;     // [items][NS] element offsets of the rows, k = corner * S + source
+    const double* coef;        // [items][NS] a_k
+    const int64_t* row_off;    // [CR + 1] the fine rows of coarse row q are row_list[row_off[q] .. row_off[q + 1])
+    const int32_t* row_list;
+    const int32_t* xb;         // [Cx + 1] fine columns [xb[j], xb[j + 1]) make coarse column j; xb[0] = x_lo
+    double* partial;           // [items][R][CR][nsplit][Lx]
+    double* out;               // [items][R][CR][Cx]
+    int64_t L;                 // fine bins of the last axis: fine bin b = r L + x
+    int64_t x_lo, Lx;          // the fine columns that belong to a cell
+    int64_t CR, Cx;
+    int64_t n_out;             // items R CR Cx
+    int NS, S, R;              // R groups of rows per item: 1 (every row) or S (group r holds the rows k = r, r + S, ...)
+    int nsplit;                // shares a coarse row's fine rows are dealt into
+    int n_xt;                  // x-tiles of TX = 1 << tx_shift lanes
+    int tx_shift;              // 6, 7 or 8; TY = 256 >> tx_shift fine rows of a share are in flight at a time
+    int wide;                  // the finish kernel: 0 one thread per cell, 1 one block per cell (k_coarse_finish_wide)
+};
+
+// k_coarse_list (bi_k_coarse.h): the non-empty-bin lists of n datasets into 64-bit integer tables [n][C]
+struct CoarseListArgs {
+    const int32_t* nz_idx;     // fine bin of every entry
+    const double* nz_n;        // ... and its count (an integer by construction)
+    const int64_t* nz_off;     // [T + 1]
+    const int64_t* dataset;    // [n]
+    const int32_t* row_map;    // [NR]
+    const int32_t* x_map;      // [L]
+    unsigned long long* table; // [n][C], zeroed
+    int64_t L, Cx, C;
+};
+
 // k_real_expect (bi_k_real.h)
 struct RealExpectArgs {
     const double* ps;          // [rows][Bp] the dense template tensor

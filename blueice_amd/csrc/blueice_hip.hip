@@ -102,6 +102,7 @@ void bi_destroy(bi_ctx* c) {
     dev_free(c->ps_sorted); dev_free(c->cnt_sorted);
     dev_free(c->sim_coords); dev_free(c->sim_source);
     dev_free(c->real_counts);
+    release_coarse(c);
     if (c->slot_host) (void)hipHostFree(c->slot_host);
     if (c->pack_host) (void)hipHostFree(c->pack_host);
     if (c->bounce_host) (void)hipHostFree(c->bounce_host);
@@ -186,6 +187,7 @@ int bi_model_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anch
     c->cnt8_valid = false;
     dev_free(c->real_counts);   // (rows of the previous model's padded length)
     c->real_T = 0;
+    release_coarse(c);          // (groups of the previous model's bins)
     ++c->epoch;
     c->d = d; c->S = S; c->B = B; c->bb_source = bb_source;
     c->Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
@@ -1847,3 +1849,4 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_real.h"
 #include "bi_sampler.h"
 #include "bi_grid.h"
+#include "bi_coarse.h"

@@ -1,0 +1,19 @@
+// tu_coarse.hip -- translation unit of the coarse-view kernels k_morph_coarse, k_coarse_finish(_wide), k_coarse_list and
+// k_coarse_table (bi_k_coarse.h).  See bi_common.h for how the library is split.
+#include "bi_common.h"
+#include "bi_k_coarse.h"
+
+void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items) {
+    EventScope ev(c);
+    const dim3 grid((unsigned)(a.CR * a.nsplit * a.n_xt), (unsigned)a.R, (unsigned)n_items);
+    hipLaunchKernelGGL(k_morph_coarse, grid, dim3(kThreads), 0, c->stream, a);
+    if (a.wide) hipLaunchKernelGGL(k_coarse_finish_wide, dim3((unsigned)a.n_out), dim3(kThreads), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_coarse_finish, dim3((unsigned)((a.n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+}
+
+void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out) {
+    EventScope ev(c);
+    hipLaunchKernelGGL(k_coarse_list, dim3(64, (unsigned)n), dim3(kThreads), 0, c->stream, a);
+    hipLaunchKernelGGL(k_coarse_table, dim3((unsigned)((n * a.C + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
+                       (const unsigned long long*)a.table, n * a.C, out);
+}

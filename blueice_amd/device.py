@@ -440,6 +440,51 @@ class DeviceContext:
         self._check(self._lib.bi_expected_counts(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
         return out
 
+    # -- coarse views: the expectation and the data summed over groups of fine bins (bi_set_coarse_binning ...) --
+    def set_coarse_binning(self, n_fine=None, groups=None):
+        """The context's coarse binning: n_fine [k] fine bins per analysis axis, groups: per axis the ascending fine-bin
+        boundaries e_0 < ... < e_m (`CoarseBinning.groups`) -> the number of cells.  No arguments: clear it.  A new model
+        releases it.  ValueError (BI_ERR_INVALID) for boundaries that do not fit the model, Beeston-Barlow and unbinned contexts."""
+        cells = C.c_int64(0)
+        if n_fine is None:
+            self._coarse_key = None
+            self._check(self._lib.bi_set_coarse_binning(self._h, 0, None, None, None, C.byref(cells)))
+            return 0
+        n_fine = np.ascontiguousarray(n_fine, dtype=np.int32)
+        groups = [np.ascontiguousarray(g, dtype=np.int32).ravel() for g in groups]
+        if len(groups) != len(n_fine) or not len(n_fine):
+            raise ValueError("need the boundaries of every one of the %d axes" % len(n_fine))
+        n_groups = np.array([len(g) - 1 for g in groups], dtype=np.int32)
+        bounds = np.ascontiguousarray(np.concatenate(groups), dtype=np.int32)
+        # the binning the context holds already (coarse_cells is 0 once a new model has released it): nothing to build or upload
+        key = (n_fine.tobytes(), n_groups.tobytes(), bounds.tobytes())
+        held = getattr(self, '_coarse_key', None)
+        if held is not None and held[0] == key and self.get_param('coarse_cells') == held[1]:
+            return held[1]
+        self._coarse_key = None
+        self._check(self._lib.bi_set_coarse_binning(self._h, len(n_fine), ptr(n_fine), ptr(n_groups), ptr(bounds), C.byref(cells)))
+        self._coarse_key = (key, int(cells.value))
+        return int(cells.value)
+
+    def expected_coarse(self, n_cells, z, rate_scale=None, per_source=False):
+        """The expectation per cell of the coarse binning (bi_expected_coarse) -> (mu [P, C] or [P, S, C], status [P]); nan
+        rows and the status bit for points outside the anchor box or with unphysical rates."""
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        out = np.empty((P, self.S, int(n_cells)) if per_source else (P, int(n_cells)), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_expected_coarse(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out), ptr(status)))
+        return out, status
+
+    def coarse_counts(self, n_cells, datasets=None):
+        """The resident datasets' counts per cell of the coarse binning (bi_coarse_counts) -> [n, C]; datasets: indices [n]
+        (None: all T)."""
+        if datasets is not None:
+            datasets = np.ascontiguousarray(np.atleast_1d(datasets), dtype=np.int64)
+        n = int(self.T) if datasets is None else len(datasets)
+        out = np.empty((n, int(n_cells)), dtype=np.float64)
+        self._check(self._lib.bi_coarse_counts(self._h, n, ptr(datasets), ptr(out)))
+        return out
+
     # -- real-valued datasets: a store of its own beside the ordinary data (bi_set_real_counts ... bi_fit_batched_real) --
     def set_real_counts(self, counts):
         """counts: [*bins] (one set) or [T, *bins], every count finite and >= 0 (ValueError otherwise); None drops the store."""

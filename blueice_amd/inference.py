@@ -16,7 +16,10 @@ the parabolic errors sqrt(diag((-H)^-1)) that MIGRAD reports at errordef = 0.5. 
 
 Goodness of fit: `gof_statistics` evaluates the deviance and Pearson's chi2 of the data term on the device (bi_eval_gof),
 `goodness_of_fit` calibrates either with toys fitted like the data, and `expected_counts` hands back the per-bin expectation
-the statistics are made of (bi_expected_counts).  Plain binned likelihoods only.
+the statistics are made of (bi_expected_counts).  Plain binned likelihoods only.  `expected_coarse`, `expected_coarse_points`
+and `coarse_counts` (blueice_amd.coarse) sum the expectation and the data over the cells of a `CoarseBinning` on the device
+-- projections with their components, a signal box -- and `gof_statistics` / `goodness_of_fit` take such a binning to test
+where the data can tell.
 
 Expected results without toys: `asimov_test_statistic`, `expected_upper_limit` and `expected_discovery_significance` profile
 the Asimov dataset of a truth (blueice_amd.asimov: n_b = mu_b(truth), real-valued counts in a device store of their own) and
@@ -41,9 +44,11 @@ from .hessian import to_log10
 from .profile import bestfit_batched, supports_batched_fits
 from .sampler import sample_posterior
 from .utils import is_numeric
+from .coarse import _binned_for_gof, _prepared, coarse_counts, coarse_statistics, expected_coarse, expected_coarse_points
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
            'toy_test_statistics', 'neyman_thresholds', 'expected_counts', 'expected_counts_points', 'gof_statistics', 'goodness_of_fit',
+           'expected_coarse', 'expected_coarse_points', 'coarse_counts',
            'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
            'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
            'plot_likelihood_ratio']
@@ -445,21 +450,6 @@ def neyman_thresholds(lf, target, hypotheses, n_toys, **options):
 
 # ---- goodness of fit ------------------------------------------------------------------------------------------------
 
-def _binned_for_gof(lf, what):
-    """-> lf if it is a binned likelihood without Beeston-Barlow; NotImplementedError otherwise (before any device work)"""
-    from .likelihood import BinnedLogLikelihood
-    if not isinstance(lf, BinnedLogLikelihood):
-        raise NotImplementedError("%s needs a BinnedLogLikelihood: a %s has no bins of its own" % (what, type(lf).__name__))
-    if lf.model_statistical_uncertainty_handling is not None:
-        raise NotImplementedError("%s is not defined with Beeston-Barlow (model_statistical_uncertainty_handling = %r): the "
-                                  "expectation depends on the data" % (what, lf.model_statistical_uncertainty_handling))
-    if not lf.is_prepared:
-        if len(lf.shape_parameters):
-            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
-        lf.prepare()            # nothing to morph: preparation is trivial
-    return lf
-
-
 def expected_counts_points(lf, points, per_source=False, livetime_days=None):
     """The expected events per bin at P parameter points: points = dict parameter name -> array [P] (scalars broadcast;
     absent parameters take their defaults), as `eval_points` -> mu [P, *bin_shape], or [P, S, *bin_shape] with per_source
@@ -485,7 +475,7 @@ def expected_counts(lf, per_source=False, livetime_days=None, **params):
     return lf.ctx.expected_counts(zs if len(zs) else None, scale[None, :], per_source=per_source)[0].reshape(shape)
 
 
-def gof_statistics(lf, points=None, datasets=None, livetime_days=None, **fixed):
+def gof_statistics(lf, points=None, datasets=None, livetime_days=None, binning=None, **fixed):
     """Goodness-of-fit statistics of the binned data at P parameter points, summed bin by bin on the device (bi_eval_gof):
         deviance = 2 sum_b [mu_b - n_b - n_b log(mu_b / n_b)]     (the likelihood ratio against the saturated model, Baker-Cousins)
         pearson  =   sum_b (n_b - mu_b)^2 / mu_b
@@ -495,7 +485,13 @@ def gof_statistics(lf, points=None, datasets=None, livetime_days=None, **fixed):
     -> dict(deviance [P], pearson [P], n_bins, n_events [P] (the events of every point's dataset), status [P]).
     PRIORS ARE NOT PART OF EITHER STATISTIC: both are statements about the data term only, whatever constraint terms the
     likelihood carries.  A point outside the anchor box or with unphysical rates gives +inf in both; so does a point where
-    the likelihood is -inf (an event in a bin where nothing is expected), and both are nan where it is nan."""
+    the likelihood is -inf (an event in a bin where nothing is expected), and both are nan where it is nan.
+
+    binning: a `CoarseBinning` -- both statistics are then formed over its C cells, from the expectation and the counts summed
+    over the fine bins of every cell on the device (bi_expected_coarse, bi_coarse_counts) and the same per-cell forms
+    (`coarse_statistics`); n_bins is C, and n_events counts the events inside the cells.  THE STATISTIC IS THEN A STATEMENT
+    ABOUT THE COARSE CELLS ONLY: what happens inside a cell, or in fine bins that belong to no cell, is invisible to it -- in
+    particular an event in a fine bin with no expectation no longer forces +inf, unless its whole cell expects nothing."""
     _binned_for_gof(lf, 'gof_statistics')
     if not lf.is_data_set:
         raise NotPreparedException("gof_statistics requires you to first set the data using set_data()")
@@ -507,11 +503,32 @@ def gof_statistics(lf, points=None, datasets=None, livetime_days=None, **fixed):
         P = max(len(z), len(datasets))
         z, scale = np.broadcast_to(z, (P, z.shape[1])), np.broadcast_to(scale, (P, scale.shape[1]))
         datasets = np.broadcast_to(datasets, (P,))
+    if binning is not None:
+        return _gof_statistics_coarse(lf, binning, z, scale, datasets)
     half, pearson, st = lf.ctx.eval_gof(z if z.shape[1] else None, scale, datasets)
     ds = np.zeros(len(half), dtype=np.int64) if datasets is None else datasets
     totals = {int(t): float(lf.ctx.download_counts(int(t)).sum()) for t in np.unique(ds) if 0 <= t < lf.ctx.T}
     return dict(deviance=2.0 * half, pearson=pearson, n_bins=int(np.prod(lf.bin_shape, dtype=np.int64)),
                 n_events=np.array([totals.get(int(t), np.nan) for t in ds]), status=st)
+
+
+def _gof_statistics_coarse(lf, binning, z, scale, datasets):
+    """`gof_statistics` over the cells of `binning`: z [P, d], scale [P, S] and datasets [P] (or None) as it prepared them"""
+    _prepared(lf, binning, 'gof_statistics')
+    mu, st = lf.ctx.expected_coarse(binning.n_cells, z if z.shape[1] else None, scale)
+    ds = np.zeros(len(mu), dtype=np.int64) if datasets is None else np.asarray(datasets, dtype=np.int64)
+    T = int(lf.ctx.T)
+    known = np.unique(ds[(ds >= 0) & (ds < T)])
+    n_of = np.full((len(mu), binning.n_cells), np.nan)
+    if len(known):
+        table = lf.ctx.coarse_counts(binning.n_cells, known)
+        inside = np.isin(ds, known)
+        n_of[inside] = table[np.searchsorted(known, ds[inside])]
+    st = np.where((ds < 0) | (ds >= T), st | 16, st).astype(np.int32)       # (BI_ST_BAD_DATASET, as bi_eval_gof reports it)
+    deviance, pearson = coarse_statistics(n_of, mu)
+    dead = st != 0
+    deviance[dead] = pearson[dead] = np.inf
+    return dict(deviance=deviance, pearson=pearson, n_bins=int(binning.n_cells), n_events=n_of.sum(axis=1), status=st)
 
 
 def toy_p_value(observed, toys, failed=None):
@@ -547,7 +564,7 @@ class GofResult:
 
 
 def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, first_toy=0, fit_options=None, livetime_days=None,
-                    **fixed):
+                    binning=None, **fixed):
     """Does the fitted model describe the data?  The goodness-of-fit statistic ('deviance' or 'pearson', see
     `gof_statistics`) of the data at their best fit, and its p-value from toys that are treated like the data:
       1. the data are fitted (`bestfit_batched`; `fixed` parameters stay fixed, fit_options go to the engine);
@@ -558,7 +575,11 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
       5. every toy's statistic is evaluated at its own fit.
     -> GofResult.  Priors shape the fits but are no part of the statistic.  p_value_chi2 is the asymptotic reading
     chi2.sf(observed, n_bins - n_floating); with sparse bins it is unreliable and p_value is the number to quote.
-    Afterwards the likelihood has its own data back (as after `toy_test_statistics`)."""
+    Afterwards the likelihood has its own data back (as after `toy_test_statistics`).
+
+    binning: a `CoarseBinning` -- the data and every toy are still FITTED on the fine bins, but the statistic of steps 2 and 5
+    is formed over the cells of the binning (`gof_statistics(..., binning=)`: a statement about the coarse cells only), where
+    a test on ~10^4 events has power that it lacks on 10^6 fine bins; ndof = n_cells - n_floating."""
     _binned_for_gof(lf, 'goodness_of_fit')
     if statistic not in ('deviance', 'pearson'):
         raise ValueError("statistic must be 'deviance' or 'pearson'")
@@ -573,8 +594,8 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
     except NoOpimizationNecessary:
         best = OrderedDict()
     truth = dict(fixed, **best)
-    observed = float(gof_statistics(lf, livetime_days=livetime_days, **truth)[statistic][0])
-    n_bins = int(np.prod(lf.bin_shape, dtype=np.int64))
+    observed = float(gof_statistics(lf, livetime_days=livetime_days, binning=binning, **truth)[statistic][0])
+    n_bins = int(np.prod(lf.bin_shape, dtype=np.int64)) if binning is None else int(binning.n_cells)
     restore = _resident_data(lf, ctx)
     toys, failed = np.empty(n), np.zeros(n, dtype=bool)
     toy_best = OrderedDict((k, np.empty(n)) for k in best)
@@ -589,7 +610,8 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
                 failed[t0:t0 + m] = info['failed']
                 for k, v in fitted.items():
                     toy_best[k][t0:t0 + m] = v
-            toys[t0:t0 + m] = gof_statistics(lf, points=fitted, datasets=np.arange(m), livetime_days=livetime_days, **fixed)[statistic]
+            toys[t0:t0 + m] = gof_statistics(lf, points=fitted, datasets=np.arange(m), livetime_days=livetime_days, binning=binning,
+                                             **fixed)[statistic]
     finally:
         ctx.set_param('toy_offset', 0)
         if restore is not None:

@@ -361,6 +361,32 @@ int bi_eval_gof(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scal
  * Beeston-Barlow only (there the expectation depends on the data): BI_ERR_INVALID otherwise. */
 int bi_expected_counts(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out);
 
+/* Coarse views: the expectation, and the data, summed over tensor-product groups of fine bins -- projections on one or two
+ * analysis axes, a rebinned space, a signal box -- without the fine bins ever leaving the device.
+ *   bi_set_coarse_binning   the binning of the context.  k analysis axes with n_fine[j] fine bins each (their product must be
+ *                           the model's B; bins are in C order, the last axis fastest); axis j is cut into n_groups[j] >= 1
+ *                           groups of adjacent fine bins by the n_groups[j] + 1 boundaries e_0 < ... < e_m, 0 <= e_0 and
+ *                           e_m <= n_fine[j] (group g holds the fine bins e_g <= i < e_g+1; bins below e_0 or from e_m on
+ *                           belong to no cell); `bounds` holds the axes' boundaries one after the other.  A cell is one group
+ *                           per axis, C = prod_j n_groups[j] cells in C order; *n_cells (nullable) gets C.  An axis that is
+ *                           summed over has one group.  k = 0 clears the binning, and a new model releases it.
+ *                           BI_ERR_INVALID: prod_j n_fine[j] != B, n_groups[j] < 1, boundaries that are not strictly ascending
+ *                           or leave [0, n_fine[j]]; Beeston-Barlow and unbinned contexts, as bi_expected_counts.
+ *   bi_expected_coarse      out [P][C] (per_source = 0) or [P][S][C]: the expectation of every cell at every point, with the
+ *                           screen of bi_expected_counts: a point outside the anchor box or with unphysical rates gets nan in
+ *                           every cell and its bit in status [P] (nullable; 0 for a live point).  The corner rows are streamed
+ *                           once per point and reduced as they arrive; no floating-point atomics: every sum runs in an order
+ *                           fixed by the binning and the device, a repeated call is bitwise identical, and a point's result
+ *                           does not depend on the other points of the call.
+ *   bi_coarse_counts        out [n][C]: the counts of datasets dataset[0 .. n) (NULL: all of them, n = T) in the cells, from
+ *                           the resident data in whichever form they are held (dense, or the non-empty-bin lists of
+ *                           device-generated toys); a dataset index outside [0, T) is BI_ERR_INVALID.
+ * Without a binning the last two return BI_ERR_STATE. */
+int bi_set_coarse_binning(bi_ctx* ctx, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds, int64_t* n_cells);
+int bi_expected_coarse(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out,
+                       int32_t* status);
+int bi_coarse_counts(bi_ctx* ctx, int64_t n, const int64_t* dataset, double* out);
+
 /* Real-valued datasets: Asimov data (n_b = mu_b(truth), Cowan, Cranmer, Gross, Vitells, Eur. Phys. J. C 71 (2011) 1554) and
  * weighted histograms used as pseudo-data.  They live in a store of their own, per context and independent of its ordinary
  * data, which stay resident and keep their semantics (a count that is no integer is -inf in every other entry point):
@@ -764,7 +790,7 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  * read-only: n_set_launches (evaluation launches of k_morph_sets: work items with different event sets, see bi_score_event_sets),
  *            n_sampler_half_steps (half-steps of bi_sample_stretch so far), last_plan_refused (the last bi_plan_points_resident /
  *            bi_sample_stretch planning refused its batch: 1 Beeston-Barlow points that need exact totals, 2 infinite rates of sources that may
- *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total;
+ *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total, dense_counts (the resident datasets are held as dense rows; 0: as non-empty-bin lists only, device-generated toys), coarse_cells (cells of the coarse binning set by bi_set_coarse_binning, 0: none);
  *            last_morph_nbx / last_morph_items / last_morph_fused (the most recent k_morph_reduce or k_morph_single launch: blocks per
  *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it);
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
