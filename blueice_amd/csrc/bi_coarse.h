@@ -5,8 +5,8 @@
 // axis; fine bins below e_0 or from e_m on belong to no cell.  With b = r L + x (x on the last axis) the binning becomes, once:
 //     the fine rows of every coarse row in CSR form (ascending inside a coarse row, left-out rows absent), row_map [NR],
 //     the boundaries of the column groups xb [Cx + 1] and x_map [L].
-// bi_expected_coarse: per live point the descriptors of bi_expected_counts (row offsets and a_k = w_corner r_source of the
-// 2^d_eff S corner rows), one launch pair per chunk of points; the chunk is sized so that the x-resolved partial sums of
+// bi_expected_coarse: per live point the value rows of bi_items.h, bi_expected_counts's (row offsets and a_k = w_corner r_source
+// of the 2^d_eff S corner rows), one launch pair and one download of the live runs per chunk of points; the chunk is sized so that the x-resolved partial sums of
 // k_morph_coarse and the output stay within ~64 MB each.  bi_coarse_counts: the dense counts rows through the same kernels,
 // or the non-empty-bin lists through k_coarse_list where only those exist.
 #pragma once
@@ -182,24 +182,15 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
     if (rc) return rc;
     if (P < 0 || (P > 0 && !out)) return fail(c, BI_ERR_INVALID, "bad P / output pointer");
     if (c->d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    const int S = c->S, d = c->d;
+    const int S = c->S;
     const int de = (int)c->eff_axes.size();
-    const int nc = 1 << de, NS = nc * S, R = per_source ? S : 1;
+    const int NS = (1 << de) * S, R = per_source ? S : 1;
     const int64_t per_item = (int64_t)R * c->coarse.C;
     HIP_TRY(c, hipSetDevice(c->device));
     const double qnan = std::numeric_limits<double>::quiet_NaN();
-    // the screen of bi_expected_counts (screen_point less its dataset test); here the bit is reported too
-    std::vector<int64_t> live;
-    {
-        PointGeom g;
-        std::vector<double> r((size_t)S);
-        for (int64_t p = 0; p < P; ++p) {
-            const int32_t bit = real_screen_point(c, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, g, r.data());
-            if (status) status[p] = bit;
-            if (bit) std::fill(out + p * per_item, out + (p + 1) * per_item, qnan);
-            else live.push_back(p);
-        }
-    }
+    // the screen of bi_expected_counts (no dataset test); here the bit is reported too
+    const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, nullptr, status,
+                                                    [&](int64_t p) { std::fill(out + p * per_item, out + (p + 1) * per_item, qnan); }, false);
     const int64_t n_items = (int64_t)live.size();
     if (n_items == 0) return BI_OK;
     const int64_t chunk = coarse_chunk(c, n_items, R);
@@ -212,32 +203,13 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
     PointDerivs pd(c, false);
     for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
         const int64_t ni = std::min(chunk, n_items - i0);
-        for (int64_t i = 0; i < ni; ++i) {
-            const int64_t p = live[(size_t)(i0 + i)];
-            pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
-            int k = 0;
-            for (int corner = 0; corner < nc; ++corner)
-                for (int s = 0; s < S; ++s, ++k) {
-                    rowoff[(size_t)(i * NS + k)] = ((pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s) * c->Bp;
-                    coef[(size_t)(i * NS + k)] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];
-                }
-        }
+        fill_value_rows(pd, &live[(size_t)i0], ni, z, rate_scale, rowoff.data(), coef.data());
         PackedUpload pu;
         if ((rc = packed_upload(c, {{rowoff.data(), (size_t)ni * NS * sizeof(int64_t)}, {coef.data(), (size_t)ni * NS * sizeof(double)}}, 0, pu)))
             return rc;
         coarse_launch(c, (const double*)c->ps.p, pu.dev<int64_t>(0), pu.dev<double>(1), NS, S, R, ni, (double*)d_partial.p, (double*)d_out.p);
-        hipError_t e = hipGetLastError();
-        // runs of consecutive live points are consecutive in `out` too: one copy each
-        for (int64_t i = 0; i < ni && e == hipSuccess;) {
-            int64_t j = i + 1;
-            while (j < ni && live[(size_t)(i0 + j)] == live[(size_t)(i0 + j - 1)] + 1) ++j;
-            e = hipMemcpyAsync(out + live[(size_t)(i0 + i)] * per_item, (const double*)d_out.p + i * per_item,
-                               (size_t)((j - i) * per_item) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            i = j;
-        }
-        // (the staging block of packed_upload, d_partial and d_out are reused by the next chunk)
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        else (void)hipStreamSynchronize(c->stream);
+        // (the staging block of packed_upload, d_partial and d_out are reused by the next chunk: the download synchronises)
+        const hipError_t e = download_live_runs(c, &live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse: %s", hipGetErrorString(e));
     }
     return BI_OK;

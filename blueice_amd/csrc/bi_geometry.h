@@ -102,13 +102,17 @@ bool rates_physical(const bi_ctx* c, const double* mus) {
 }
 
 // The reference's early exits for one point, in its order: dataset ds, anchor box, rates.  -> 0 or the status bit; g and
-// the rates r [S] (interpolated, times rs when given) are filled as far as the point got.
-int32_t screen_point(const bi_ctx* c, const double* z, const double* rs, int64_t ds, PointGeom& g, double* r) {
-    if (ds < 0 || ds >= c->T) return BI_ST_BAD_DATASET;
+// the rates r [S] (interpolated, times rs when given) are filled as far as the point got.  screen_point_rates: the exits that
+// do not depend on the context's data (expectations, the real-valued store).
+int32_t screen_point_rates(const bi_ctx* c, const double* z, const double* rs, PointGeom& g, double* r) {
     if (!point_geometry(c, z, g)) return BI_ST_OUT_OF_BOUNDS;
     interp_mus(c, g, r);
     if (rs) for (int s = 0; s < c->S; ++s) r[s] *= rs[s];
     return rates_physical(c, r) ? 0 : BI_ST_UNPHYSICAL;
+}
+int32_t screen_point(const bi_ctx* c, const double* z, const double* rs, int64_t ds, PointGeom& g, double* r) {
+    if (ds < 0 || ds >= c->T) return BI_ST_BAD_DATASET;
+    return screen_point_rates(c, z, rs, g, r);
 }
 
 int pick_class(int n, int maxg) {

@@ -10,8 +10,9 @@
 //   second order, axis i, t  delta_st (d_i w_c mus_s + w_c d_i mus_s)
 // (rate-rate second derivatives are 0).  The kernel reduces every column with the per-bin weight n / mu - 1 (1 / lambda for
 // events) and the Gram sums of the first-order columns with n / mu^2 (1 / lambda^2); the empty bins of the non-empty-bin
-// form enter through the row totals over them (h_Tz), the unbinned -sum_s mu_s through the slot constants.  The steps shared
-// with bi_eval_grad (screen, corner derivatives, first-order columns, chunked launch and finish) are in bi_grad.h.
+// form enter through the row totals over them (h_Tz), the unbinned -sum_s mu_s through the slot constants.  The route, the
+// screen, the corner derivatives and first-order columns, the descriptor batch and its chunked launch and finish are
+// bi_items.h's; the second-order columns and their unbinned constants are written here.
 #pragma once
 
 namespace {
@@ -49,12 +50,9 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     const int NSL = G + DM * (DM + 1) / 2;             // result slots per item: the columns, then the Gram pairs
     const int F = d + S;
     HIP_TRY(c, hipSetDevice(c->device));
-    const int nc = 1 << de, NS = nc * S;
-    bool any_neg = false;
-    for (int q = 0; q < S; ++q) any_neg |= (c->allow_neg[(size_t)q] != 0);
-    const bool sparse = !unb && c->sparse && c->compact_ready && c->ps_nonneg && !any_neg;
-    if (!unb && !sparse && !c->dense_counts) return fail(c, BI_ERR_STATE, "dataset counts are not resident in dense form");
-    const int64_t n_rows = c->A * S;
+    const int NS = (1 << de) * S;
+    const ItemRoute rt(c);
+    if (!rt.has_counts()) return fail(c, BI_ERR_STATE, "dataset counts are not resident in dense form");
     const double ninf = -std::numeric_limits<double>::infinity();
     const double qnan = std::numeric_limits<double>::quiet_NaN();
 
@@ -83,101 +81,60 @@ int bi_eval_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale
     if (n_items == 0) return BI_OK;
     std::vector<int> axis_col((size_t)de);
     for (int ii = 0; ii < de; ++ii) axis_col[(size_t)ii] = 1 + ii;
-    std::vector<int64_t> rowoff((size_t)n_items * NS), cnt_off((size_t)n_items), perm((size_t)n_items * NSL);
-    std::vector<double> coef((size_t)n_items * NS * G, 0.0), slot_lg((size_t)n_items * NSL, 0.0);
-    std::vector<int32_t> tiles((size_t)n_items);
-    parallel_for(n_items, 512, [&](int64_t lo, int64_t hi) {
-        PointDerivs pd(c, true);
-        const std::vector<double>& mus = pd.mus;
-        const std::vector<double>& dmus = pd.dmus;
-        const std::vector<double>& d2mus = pd.d2mus;
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t p = live[(size_t)i];
-            const int64_t ds = dataset ? dataset[p] : 0;
-            pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
-            const double* rs = pd.rs;
-            const int64_t row_stride = sparse ? c->h_c_np[(size_t)ds] : c->Bp;
-            const int64_t row_base = sparse ? c->h_c_off[(size_t)ds] : 0;
-            const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * NSL;
-            int k = 0;
-            for (int corner = 0; corner < nc; ++corner)
-                for (int s = 0; s < S; ++s, ++k) {
-                    const int64_t row = (pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s;
-                    rowoff[ro + k] = row_base + row * row_stride;
-                    double* col = &coef[co + (size_t)k * G];
-                    const double w = pd.g.w[(size_t)corner];
-                    const double* dwc = &pd.dw[(size_t)corner * de];
-                    pd.first_order(col, corner, s, axis_col.data(), 1 + de + s);
-                    int q = 1 + D;
-                    for (int ii = 0; ii < de; ++ii)
-                        for (int jj = ii; jj < de; ++jj, ++q) {
-                            const double a_i = dmus[(size_t)ii * S + s], a_j = dmus[(size_t)jj * S + s];
-                            if (ii == jj) col[q] = rs[s] * (2.0 * dwc[ii] * a_i);
-                            else {
-                                const int pz = jj * (jj + 1) / 2 + ii;
-                                col[q] = rs[s] * (pd.d2w[(size_t)corner * NZZ + pz] * mus[(size_t)s] + dwc[ii] * a_j + dwc[jj] * a_i +
-                                                  w * d2mus[(size_t)pz * S + s]);
-                            }
-                        }
-                    for (int ii = 0; ii < de; ++ii, q += S) col[q + s] = dwc[ii] * mus[(size_t)s] + w * dmus[(size_t)ii * S + s];
-                    if (sparse) {
-                        const double tz = c->h_Tz[(size_t)(ds * n_rows + row)];
-                        for (int j = 0; j < Gc; ++j) slot_lg[po + j] += col[j] * tz;
-                    }
-                }
-            if (unb) {
-                double* lg = &slot_lg[po];
-                pd.first_order_unbinned(lg, axis_col.data(), 1 + de);
-                int q = 1 + D;                   // the second-order columns' constants
-                for (int ii = 0; ii < de; ++ii) {
-                    for (int jj = ii; jj < de; ++jj, ++q)
-                        if (jj != ii)
-                            for (int s = 0; s < S; ++s) lg[q] += d2mus[(size_t)(jj * (jj + 1) / 2 + ii) * S + s] * rs[s];
-                }
-                for (int ii = 0; ii < de; ++ii)
-                    for (int t = 0; t < S; ++t, ++q) lg[q] = dmus[(size_t)ii * S + t];
-            } else
-                slot_lg[po] += c->h_lgsum[(size_t)ds];
-            for (int j = 0; j < NSL; ++j) perm[po + j] = (int64_t)po + j;
-            cnt_off[(size_t)i] = unb ? 0 : (sparse ? c->h_cnt_off[(size_t)ds] : ds * c->Bp);
-            tiles[(size_t)i] = (int32_t)(row_stride / kTile);
-        }
-    });
-    int max_tiles = 1;
-    for (int32_t t : tiles) max_tiles = std::max(max_tiles, (int)t);
-    PackedUpload pu;
-    if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
-                                {cnt_off.data(), cnt_off.size() * sizeof(int64_t)}, {tiles.data(), tiles.size() * sizeof(int32_t)},
-                                {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
-                            (size_t)n_items * NSL * sizeof(double), pu)))
-        return rc;
-    double* h_out = (double*)pu.host_out();
+    ItemBatch batch(c, live, G, NSL, NSL);
+    batch.fill(rt, z, rate_scale, dataset, true, 512, Gc,
+               [&](const PointDerivs& pd, double* col, int corner, int s) {
+                   const double* rs = pd.rs;
+                   const double w = pd.g.w[(size_t)corner];
+                   const double* dwc = &pd.dw[(size_t)corner * de];
+                   pd.first_order(col, corner, s, axis_col.data(), 1 + de + s);
+                   int q = 1 + D;
+                   for (int ii = 0; ii < de; ++ii)
+                       for (int jj = ii; jj < de; ++jj, ++q) {
+                           const double a_i = pd.dmus[(size_t)ii * S + s], a_j = pd.dmus[(size_t)jj * S + s];
+                           if (ii == jj) col[q] = rs[s] * (2.0 * dwc[ii] * a_i);
+                           else {
+                               const int pz = jj * (jj + 1) / 2 + ii;
+                               col[q] = rs[s] * (pd.d2w[(size_t)corner * NZZ + pz] * pd.mus[(size_t)s] + dwc[ii] * a_j + dwc[jj] * a_i +
+                                                 w * pd.d2mus[(size_t)pz * S + s]);
+                           }
+                       }
+                   for (int ii = 0; ii < de; ++ii, q += S) col[q + s] = dwc[ii] * pd.mus[(size_t)s] + w * pd.dmus[(size_t)ii * S + s];
+               },
+               [&](const PointDerivs& pd, double* lg, int64_t ds) {
+                   if (!unb) {
+                       lg[0] += c->h_lgsum[(size_t)ds];
+                       return;
+                   }
+                   pd.first_order_unbinned(lg, axis_col.data(), 1 + de);
+                   int q = 1 + D;                   // the second-order columns' constants
+                   for (int ii = 0; ii < de; ++ii) {
+                       for (int jj = ii; jj < de; ++jj, ++q)
+                           if (jj != ii)
+                               for (int s = 0; s < S; ++s) lg[q] += pd.d2mus[(size_t)(jj * (jj + 1) / 2 + ii) * S + s] * pd.rs[s];
+                   }
+                   for (int ii = 0; ii < de; ++ii)
+                       for (int t = 0; t < S; ++t, ++q) lg[q] = pd.dmus[(size_t)ii * S + t];
+               });
+    if ((rc = batch.upload(c))) return rc;
     HessArgs a{};
-    a.ps = sparse ? (const double*)c->ps_c.p : (const double*)c->ps.p;
-    a.counts = unb ? (const double*)c->ps.p : (sparse ? (const double*)c->cnt_c.p : (const double*)c->counts.p);
+    a.ps = rt.ps;
+    a.counts = rt.counts;
     a.B = c->B;
     a.outlier = c->outlier;
     a.NS = NS;
     a.D = D;
     a.chunks = (int)c->tile_chunks;
-    const bool nt = !sparse && !unb && (c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1));
-    rc = run_item_chunks(c, n_items, max_tiles, NSL, pu.dev<int64_t>(4), pu.dev<double>(5), h_out, nullptr, "bi_eval_hess",
-                         [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
-                             HessArgs b = a;
-                             b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
-                             b.coef = pu.dev<double>(1) + i0 * NS * G;
-                             b.item_cnt = pu.dev<int64_t>(2) + i0;
-                             b.item_tiles = pu.dev<int32_t>(3) + i0;
-                             b.partial = partial;
-                             b.pflags = pflags;
-                             const int e = launch_morph_hess(c, G, DM, b, grid, nt);
-                             return e ? fail(c, e, "bi_eval_hess: no kernel variant for G = %d, DM = %d", G, DM) : BI_OK;
-                         });
+    const bool nt = !unb && rt.nt(n_items);
+    rc = batch.run(c, a, "bi_eval_hess", [&](const HessArgs& b, dim3 grid) {
+        const int e = launch_morph_hess(c, G, DM, b, grid, nt);
+        return e ? fail(c, e, "bi_eval_hess: no kernel variant for G = %d, DM = %d", G, DM) : BI_OK;
+    });
     if (rc) return rc;
     parallel_for(n_items, 2048, [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
             const int64_t p = live[(size_t)i];
-            const double* h = h_out + (size_t)i * NSL;
+            const double* h = batch.out(i);
             ll[p] = h[0];
             double* gp = grad + p * F;
             double* hp = hess + p * F * F;

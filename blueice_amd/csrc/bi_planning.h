@@ -67,9 +67,8 @@ int plan_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale,
     const int n0 = bb ? nc * (S - 1) : nc * S;
     const int n1 = bb ? nc : 0, n2 = bb ? nc : 0;
     const int NS = n0 + n1 + n2;
-    bool any_neg = false;
-    for (int q = 0; q < S; ++q) any_neg |= (c->allow_neg[(size_t)q] != 0);
-    const bool sparse = c->sparse && c->compact_ready && c->ps_nonneg && !bb && !any_neg && !c->unbinned;
+    const bool any_neg = any_negative_source(c);
+    const bool sparse = ItemRoute(c).compact;
     const int64_t n_rows = c->A * S;
     if (!sparse && !c->dense_counts)
         return fail(c, BI_ERR_STATE, "the datasets exist only as non-empty-bin lists (device-generated toys): point "

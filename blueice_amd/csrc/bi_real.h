@@ -3,22 +3,15 @@
 // bi_k_real.h).
 //
 // The store c->real_counts [real_T][Bp] lies beside the context's ordinary data and is read by nothing else: every existing
-// data path keeps scipy's poisson.logpmf semantics (a count that is no integer is -inf).  bi_eval_real is bi_eval_grad's
-// host half over the dense rows -- one work item per live point, the coefficient columns of PointDerivs::first_order, the
-// chunked launch and k_finish of run_item_chunks -- with the half-deviance in slot 0 instead of the log-likelihood.  The
-// points are screened by screen_point's box and rate tests; its dataset test is against the integer store (c->T, which may
-// be empty here: expected results need no observed data) and is replaced by a check of the whole dataset column.
+// data path keeps scipy's poisson.logpmf semantics (a count that is no integer is -inf).  bi_eval_real is the descriptor batch
+// of bi_items.h over the dense rows -- one work item per live point, the coefficient columns of PointDerivs::first_order, the
+// chunked launch and k_finish -- with the half-deviance in slot 0 instead of the log-likelihood and the store's rows for the
+// counts.  The points are screened by the box and rate tests alone; the dataset test of the other evaluations is against the
+// integer store (c->T, which may be empty here: expected results need no observed data) and is replaced by a check of the
+// whole dataset column.  bi_set_asimov_counts writes the value rows of bi_items.h, bi_expected_counts's, through k_real_expect.
 #pragma once
 
 namespace {
-
-// the early exits of screen_point (bi_geometry.h) less its dataset test -> 0 or the status bit
-int32_t real_screen_point(const bi_ctx* c, const double* z, const double* rs, PointGeom& g, double* r) {
-    if (!point_geometry(c, z, g)) return BI_ST_OUT_OF_BOUNDS;
-    interp_mus(c, g, r);
-    if (rs) for (int s = 0; s < c->S; ++s) r[s] *= rs[s];
-    return rates_physical(c, r) ? 0 : BI_ST_UNPHYSICAL;
-}
 
 // a new store takes the place of the old one only when it is complete: on any refusal the previous one stays usable
 void real_store_swap(bi_ctx* c, DevBuf& fresh, int64_t T) {
@@ -41,87 +34,48 @@ int real_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, c
     HIP_TRY(c, hipSetDevice(c->device));
     const int G = W == 1 ? 1 : W <= 4 ? 4 : W <= 8 ? 8 : 16;
     const int de = (int)c->eff_axes.size();
-    const int nc = 1 << de, NS = nc * S;
+    const int NS = (1 << de) * S;
     const double inf = std::numeric_limits<double>::infinity();
     const double qnan = std::numeric_limits<double>::quiet_NaN();
 
-    std::vector<int32_t> st((size_t)P);
-    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
-        PointGeom g;
-        std::vector<double> r((size_t)S);
-        for (int64_t p = lo; p < hi; ++p) {
-            half_deviance[p] = inf;
-            for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
-            st[(size_t)p] = real_screen_point(c, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, g, r.data());
-        }
-    });
-    std::vector<int64_t> live;
-    live.reserve((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        if (status) status[p] = st[(size_t)p];
-        if (!st[(size_t)p]) live.push_back(p);
-    }
+    const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, nullptr, status, [&](int64_t p) {
+        half_deviance[p] = inf;
+        for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
+    }, false);
     const int64_t n_items = (int64_t)live.size();
     if (n_items == 0) return BI_OK;
 
     std::vector<int> axis_col((size_t)de);
     for (int i = 0; i < de; ++i) axis_col[(size_t)i] = 1 + c->eff_axes[(size_t)i];
-    std::vector<int64_t> rowoff((size_t)n_items * NS), cnt_off((size_t)n_items), perm((size_t)n_items * G, -1);
-    std::vector<double> coef((size_t)n_items * NS * G, 0.0), slot_lg((size_t)n_items * G, 0.0);
-    std::vector<int32_t> tiles((size_t)n_items, (int32_t)(c->Bp / kTile));
-    parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
-        PointDerivs pd(c, false);
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t p = live[(size_t)i];
-            pd.at(z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr);
-            const size_t ro = (size_t)i * NS, co = (size_t)i * NS * G, po = (size_t)i * G;
-            int k = 0;
-            for (int corner = 0; corner < nc; ++corner)
-                for (int s = 0; s < S; ++s, ++k) {
-                    rowoff[ro + k] = ((pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s) * c->Bp;
-                    double* col = &coef[co + (size_t)k * G];
-                    if (values_only) col[0] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];      // (first_order's column 0: k_real_expect's a_k)
-                    else pd.first_order(col, corner, s, axis_col.data(), 1 + d + s);
-                }
-            for (int q = 0; q < W; ++q) perm[po + q] = i * W + q;
-            cnt_off[(size_t)i] = (dataset ? dataset[p] : 0) * c->Bp;
-        }
-    });
-    const int max_tiles = (int)(c->Bp / kTile);
+    // the dense route, its counts offsets dataset * Bp into the real-valued store; no slot constants
+    const ItemRoute rt = ItemRoute::dense(c);
+    ItemBatch batch(c, live, G, G, W);
+    batch.fill(rt, z, rate_scale, dataset, false, 1024, 0,
+               [&](const PointDerivs& pd, double* col, int corner, int s) {
+                   if (values_only) col[0] = pd.value(corner, s);      // (k_real_expect's a_k)
+                   else pd.first_order(col, corner, s, axis_col.data(), 1 + d + s);
+               },
+               [](const PointDerivs&, double*, int64_t) {});
     int rc;
-    PackedUpload pu;
-    if ((rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
-                                {cnt_off.data(), cnt_off.size() * sizeof(int64_t)}, {tiles.data(), tiles.size() * sizeof(int32_t)},
-                                {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
-                            (size_t)n_items * W * sizeof(double), pu)))
-        return rc;
-    double* h_out = (double*)pu.host_out();
+    if ((rc = batch.upload(c))) return rc;
     HessArgs a{};
-    a.ps = (const double*)c->ps.p;
+    a.ps = rt.ps;
     a.counts = (const double*)c->real_counts.p;
     a.B = c->B;
     a.NS = NS;
     a.D = W - 1;
     a.chunks = (int)c->tile_chunks;
-    const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
-    rc = run_item_chunks(c, n_items, max_tiles, G, pu.dev<int64_t>(4), pu.dev<double>(5), h_out, nullptr, "bi_eval_real",
-                         [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
-                             HessArgs b = a;
-                             b.rowoff = pu.dev<int64_t>(0) + i0 * NS;
-                             b.coef = pu.dev<double>(1) + i0 * NS * G;
-                             b.item_cnt = pu.dev<int64_t>(2) + i0;
-                             b.item_tiles = pu.dev<int32_t>(3) + i0;
-                             b.partial = partial;
-                             b.pflags = pflags;
-                             const int e = launch_morph_real(c, G, b, grid, nt);
-                             return e ? fail(c, e, "bi_eval_real: no kernel variant for %d columns", G) : BI_OK;
-                         });
+    const bool nt = rt.nt(n_items);
+    rc = batch.run(c, a, "bi_eval_real", [&](const HessArgs& b, dim3 grid) {
+        const int e = launch_morph_real(c, G, b, grid, nt);
+        return e ? fail(c, e, "bi_eval_real: no kernel variant for %d columns", G) : BI_OK;
+    });
     if (rc) return rc;
     for (int64_t i = 0; i < n_items; ++i) {
         const int64_t p = live[(size_t)i];
-        const double hd = h_out[(size_t)i * W];
-        half_deviance[p] = hd;
-        for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = std::isfinite(hd) ? h_out[(size_t)i * W + 1 + j] : qnan;
+        const double* h = batch.out(i);
+        half_deviance[p] = h[0];
+        for (int j = 0; !values_only && j < d + S; ++j) grad[p * (d + S) + j] = std::isfinite(h[0]) ? h[1 + j] : qnan;
     }
     return BI_OK;
 }
@@ -177,34 +131,22 @@ int bi_set_asimov_counts(bi_ctx* c, int64_t H, const double* z, const double* ra
     if (rc) return rc;
     if (H < 1) return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: H = %lld (at least one truth)", (long long)H);
     if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    const int S = c->S, d = c->d;
+    const int S = c->S;
     const int de = (int)c->eff_axes.size();
-    const int nc = 1 << de, NS = nc * S;
+    const int NS = (1 << de) * S;
     const int64_t Bp = c->Bp;
     HIP_TRY(c, hipSetDevice(c->device));
     // every truth is screened before anything changes
-    {
-        PointGeom g;
-        std::vector<double> r((size_t)S);
-        for (int64_t h = 0; h < H; ++h) {
-            const int32_t bit = real_screen_point(c, z ? z + h * d : nullptr, rate_scale ? rate_scale + h * S : nullptr, g, r.data());
-            if (bit)
-                return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: truth %lld %s", (long long)h,
-                            bit == BI_ST_OUT_OF_BOUNDS ? "lies outside the anchor box" : "has unphysical rates");
-        }
-    }
+    std::vector<int32_t> bits((size_t)H);
+    screen_points(c, H, z, rate_scale, nullptr, bits.data(), [](int64_t) {}, false);
+    for (int64_t h = 0; h < H; ++h)
+        if (bits[(size_t)h])
+            return fail(c, BI_ERR_INVALID, "bi_set_asimov_counts: truth %lld %s", (long long)h,
+                        bits[(size_t)h] == BI_ST_OUT_OF_BOUNDS ? "lies outside the anchor box" : "has unphysical rates");
     std::vector<int64_t> rowoff((size_t)H * NS);
     std::vector<double> coef((size_t)H * NS);
     PointDerivs pd(c, false);
-    for (int64_t h = 0; h < H; ++h) {
-        pd.at(z ? z + h * d : nullptr, rate_scale ? rate_scale + h * S : nullptr);
-        int k = 0;
-        for (int corner = 0; corner < nc; ++corner)
-            for (int s = 0; s < S; ++s, ++k) {
-                rowoff[(size_t)(h * NS + k)] = ((pd.g.cell_anchor + pd.corner_off[(size_t)corner]) * S + s) * Bp;
-                coef[(size_t)(h * NS + k)] = pd.g.w[(size_t)corner] * pd.r[(size_t)s];
-            }
-    }
+    fill_value_rows(pd, nullptr, H, z, rate_scale, rowoff.data(), coef.data());
     ScratchBuf fresh, d_rowoff, d_coef, d_bad;
     std::vector<int64_t> bad((size_t)H, 0);
     if ((rc = dev_alloc(c, fresh, (size_t)(H * Bp) * sizeof(double))) || (rc = dev_upload(c, d_rowoff, rowoff)) ||

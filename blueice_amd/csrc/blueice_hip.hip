@@ -24,6 +24,7 @@
 #include "bi_k_misc.h"
 #include "bi_geometry.h"
 #include "bi_launch.h"
+#include "bi_items.h"
 #include "bi_sparse.h"
 #include "bi_single.h"
 #include "bi_planning.h"
@@ -485,8 +486,6 @@ int plan_points_resident_impl(bi_ctx* c, int64_t P, const double* z_dev, const d
     if (share_world < 1 || share_rank < 0 || share_rank >= share_world)
         return fail(c, BI_ERR_INVALID, "share %d outside [0,%d)", share_rank, share_world);
     if (c->d > 0 && P > 0 && !z_dev) return fail(c, BI_ERR_INVALID, "z_dev is NULL");
-    bool any_neg = false;
-    for (int q = 0; q < c->S; ++q) any_neg |= (c->allow_neg[(size_t)q] != 0);
     HIP_TRY(c, hipSetDevice(c->device));
     if (P == 0) return plan_points(c, 0, nullptr, nullptr, nullptr, out);
     const void* ptrs[3] = {c->d > 0 ? (const void*)z_dev : nullptr, rate_scale_dev, dataset_dev};
@@ -500,7 +499,7 @@ int plan_points_resident_impl(bi_ctx* c, int64_t P, const double* z_dev, const d
             return fail(c, BI_ERR_INVALID, "%s is not device memory of GPU %d", names[i], c->device);
         }
     }
-    const bool sparse = c->sparse && c->compact_ready && c->ps_nonneg && !c->unbinned && c->bb_source < 0 && !any_neg;
+    const bool sparse = ItemRoute(c).compact;
     if (!sparse && !c->dense_counts)
         return fail(c, BI_ERR_STATE, "the datasets exist only as non-empty-bin lists (device-generated toys): point "
                                      "evaluations need the compacted templates (sparse mode, budget) or bi_eval_datasets");
