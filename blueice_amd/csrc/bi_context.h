@@ -340,7 +340,7 @@ void dev_free(DevBuf& b) {
 // The scratch of one function call: a DevBuf that goes back to its context's recycle cache when its scope ends, on every
 // exit path.  dev_alloc, dev_upload and dev_free take it as the DevBuf it is; to release it before later work of the same
 // function, close an inner { } scope or call dev_free(b), which leaves b empty.  What outlives a call -- the members of
-// bi_ctx, bi_plan and the sampler's state, the entries of the cache -- stays a plain DevBuf, copied by value.
+// bi_ctx and bi_plan, the entries of the cache -- stays a plain DevBuf, copied by value.
 struct ScratchBuf : DevBuf {
     ScratchBuf() = default;
     ScratchBuf(const ScratchBuf&) = delete;

@@ -192,30 +192,56 @@ struct RealExpectArgs {
     int NS;
 };
 
+// The free-variable map of the native loops (fit, sampler, grid): which variable is which model parameter, the other settings
+// of every entry (problem, ensemble, dataset entry) and the staging rows, in the layouts bi_eval_grad and the resident planner
+// read.  The device loops hold device pointers, the fit's objective host pointers.  Its host side is bi_varmap.h.
+struct VarMap {
+    int F, d, S;               // variables, shape parameters and sources of the model
+    const int32_t* var_kind;   // [F] 0: shape parameter var_index, 1: rate multiplier of source var_index
+    const int32_t* var_index;
+    const double* z0;          // [E][d]  the entries' other shape settings
+    const double* scale0;      // [E][S]  ... rate scales of the sources whose multiplier is no variable
+    const double* unit;        // [E][S]  rate scale per unit multiplier
+    const int64_t* dataset;    // [E] or NULL
+    double* z_dev;             // [n][d]  the points
+    double* rs_dev;            // [n][S]
+    int64_t* ds_dev;           // [n]
+};
+
+// point i = entry e with variable j at coord(j); coord is called once per variable, in order.  The product is one rounded
+// multiply on both sides (the host is compiled without contraction).
+template <class Coord>
+__host__ __device__ __forceinline__ void varmap_write_point(const VarMap& m, int64_t i, int64_t e, Coord coord) {
+    for (int k = 0; k < m.d; ++k) m.z_dev[i * m.d + k] = m.z0[e * m.d + k];
+    for (int s = 0; s < m.S; ++s) m.rs_dev[i * m.S + s] = m.scale0[e * m.S + s];
+    for (int j = 0; j < m.F; ++j) {
+        const double y = coord(j);
+        const int k = m.var_index[j];
+        if (m.var_kind[j] == 0) m.z_dev[i * m.d + k] = y;
+#ifdef __HIP_DEVICE_COMPILE__
+        else m.rs_dev[i * m.S + k] = __dmul_rn(y, m.unit[e * m.S + k]);
+#else
+        else m.rs_dev[i * m.S + k] = y * m.unit[e * m.S + k];
+#endif
+    }
+    m.ds_dev[i] = m.dataset ? m.dataset[e] : 0;
+}
+
 // k_stretch_propose / k_stretch_accept (bi_k_sampler.h): one half-step of the ensemble sampler; every pointer is device memory
-struct StretchArgs {
+struct StretchArgs : VarMap {  // the variables (F), the ensembles' settings, the proposals' rows
     int64_t E;                 // ensembles
-    int W, F, d, S;            // walkers per ensemble, variables, shape parameters and sources of the model
+    int W;                     // walkers per ensemble
     int h;                     // the half that moves: walkers [h W/2, (h + 1) W/2); -1: stage every walker's own position (the start)
     int64_t t;                 // step
     int64_t first_ensemble;    // ensemble e of the call is ensemble first_ensemble + e of the seed's stream
     uint32_t k0, k1;           // seed, low and high word
     double a;                  // stretch scale
-    const int32_t* var_kind;   // [F] 0: shape parameter var_index, 1: rate multiplier of source var_index
-    const int32_t* var_index;
-    const double* z0;          // [E][d]  the ensembles' other shape settings
-    const double* scale0;      // [E][S]  ... rate scales of the sources whose multiplier does not float
-    const double* unit;        // [E][S]  rate scale per unit multiplier
-    const int64_t* dataset;    // [E] or NULL
     const double* lo;          // [F]
     const double* hi;
     double* x;                 // [E][W][F] the walkers
     double* ll;                // [E][W]    their log likelihoods
     int64_t* n_accepted;       // [E][W]
-    double* z_dev;             // [n][d]   the proposals, in the layouts the resident planner reads
-    double* rs_dev;            // [n][S]
-    int64_t* ds_dev;           // [n]
-    const double* ll_prop;     // [n]   their log likelihoods and status words (accept)
+    const double* ll_prop;     // [n]   the proposals' log likelihoods and status words (accept)
     const int32_t* st_prop;
     double* chain;             // [E][W][F] row of step t
     double* chain_ll;          // [E][W]
@@ -229,25 +255,16 @@ struct StretchArgs {
 // k_grid_points / k_grid_reduce / k_grid_finish (bi_k_grid.h): one chunk of a tensor-product grid; every pointer is device memory
 constexpr int kGridMaxVars = 16;
 
-struct GridArgs {
+struct GridArgs : VarMap {     // the variables (F), the entries' settings, the chunk's rows
     int64_t g0, n;             // the chunk: grid points [g0, g0 + n)
     int64_t R, GK;             // points of a cell (product of the reduced node counts), points of a dataset entry (K R)
-    int F, d, S, n_keep;       // variables, shape parameters and sources of the model, kept variables (the first n_keep)
+    int n_keep;                // kept variables (the first n_keep)
     int32_t n_nodes[kGridMaxVars];   // nodes of variable j
     int64_t node_off[kGridMaxVars];  // where they start in nodes / term / logw
     int64_t stride[kGridMaxVars];    // grid points per step of variable j: i_j = (g / stride_j) mod n_j
-    int32_t var_kind[kGridMaxVars];  // 0: shape parameter var_index, 1: rate multiplier of source var_index
-    int32_t var_index[kGridMaxVars];
-    const double* z0;          // [E][d]  the entries' other shape settings
-    const double* scale0;      // [E][S]  ... rate scales of the sources whose multiplier is no variable
-    const double* unit;        // [E][S]  rate scale per unit multiplier
-    const int64_t* dataset;    // [E] or NULL
     const double* nodes;       // concatenated
     const double* term;        // concatenated or NULL
     const double* logw;        // concatenated or NULL
-    double* z_dev;             // [n][d]   the chunk's points, in the layouts the resident planner reads
-    double* rs_dev;            // [n][S]
-    int64_t* ds_dev;           // [n]
     double* p;                 // [n] or NULL (no term): the additive terms of the points
     double* q;                 // [n] or NULL (no logw)
     // the reduction

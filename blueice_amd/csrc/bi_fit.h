@@ -374,13 +374,7 @@ int minimize_batched(bi_objective_fn fun, void* user, int64_t P, int F, const do
 // the device likelihood as the objective: f = -(ll + p), g = -d (ll + p) / d x, p the Gaussian constraint terms (none: p = 0)
 struct DeviceObjective {
     bi_ctx* c;
-    int F;
-    const int32_t* var_kind;    // [F] 0: shape parameter (axis var_index), 1: rate multiplier (source var_index)
-    const int32_t* var_index;
-    const double* z0;           // [P][d]   the problems' shape settings (the floating ones are overwritten)
-    const double* scale0;       // [P][S]   the problems' rate scales for FIXED multipliers
-    const double* unit;         // [P][S]   d rate_scale / d multiplier (live time, efficiency)
-    const int64_t* dataset;     // [P] or NULL
+    VarMap m;                   // host pointers; one entry per problem; unit is d rate_scale / d multiplier (live time, efficiency)
     const double* prior_mean;   // [F]      Gaussian constraint on variable j (all three NULL: no terms) ...
     const double* prior_sigma;  // [F]      ... +inf: none on that variable
     const double* prior_const;  // [P] or NULL: what of p does not depend on x
@@ -400,19 +394,12 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
     o->ll.resize((size_t)n);
     o->grad.resize((size_t)n * (d + S));
     o->st.resize((size_t)n);
-    if (o->dataset) o->ds.resize((size_t)n);
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t p = rows[i];
-        for (int k = 0; k < d; ++k) o->z[(size_t)i * d + k] = o->z0[p * d + k];
-        for (int s = 0; s < S; ++s) o->sc[(size_t)i * S + s] = o->scale0[p * S + s];
-        for (int j = 0; j < F; ++j) {
-            if (o->var_kind[j] == 0) o->z[(size_t)i * d + o->var_index[j]] = x[i * F + j];
-            else o->sc[(size_t)i * S + o->var_index[j]] = x[i * F + j] * o->unit[p * S + o->var_index[j]];
-        }
-        if (o->dataset) o->ds[(size_t)i] = o->dataset[p];
-    }
+    o->ds.resize((size_t)n);
+    VarMap& m = o->m;
+    m.z_dev = o->z.data(); m.rs_dev = o->sc.data(); m.ds_dev = o->ds.data();
+    for (int64_t i = 0; i < n; ++i) varmap_write_point(m, i, rows[i], [&](int j) { return x[i * F + j]; });
     o->evaluations += n;
-    const int rc = (o->real ? bi_eval_real : bi_eval_grad)(c, n, d ? o->z.data() : nullptr, o->sc.data(), o->dataset ? o->ds.data() : nullptr,
+    const int rc = (o->real ? bi_eval_real : bi_eval_grad)(c, n, d ? o->z.data() : nullptr, o->sc.data(), m.dataset ? o->ds.data() : nullptr,
                                                            o->ll.data(), o->grad.data(), o->st.data());
     if (rc) return rc;
     if (o->real) {
@@ -439,8 +426,8 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
         }
         f[i] = bad ? std::numeric_limits<double>::infinity() : -ll;
         for (int j = 0; j < F; ++j) {
-            double v = o->var_kind[j] == 0 ? o->grad[(size_t)i * (d + S) + o->var_index[j]]
-                                           : o->grad[(size_t)i * (d + S) + d + o->var_index[j]] * o->unit[p * S + o->var_index[j]];
+            double v = m.var_kind[j] == 0 ? o->grad[(size_t)i * (d + S) + m.var_index[j]]
+                                          : o->grad[(size_t)i * (d + S) + d + m.var_index[j]] * m.unit[p * S + m.var_index[j]];
             v = -v;
             if (o->prior_sigma && std::isfinite(o->prior_sigma[j]))
                 v = v + ((x[i * F + j] - o->prior_mean[j]) / o->prior_sigma[j]) / o->prior_sigma[j];
@@ -487,31 +474,37 @@ bool gauss_terms_empty(int F, const double* sigma, const double* konst) {
     return true;
 }
 
-// bi_fit_batched (no terms: the three prior arrays NULL) and bi_fit_batched_gauss
-int fit_batched(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0, const double* scale0,
-                const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi, const int32_t* n_kinks,
-                const double* kinks, double gtol, int max_iter, const double* prior_mean, const double* prior_sigma,
+// bi_fit_batched (no terms: the three prior arrays NULL), bi_fit_batched_gauss and, real: against the real-valued store,
+// bi_fit_batched_real (bi_real.h).  That one's terms are optional and its datasets the store's: both are checked here, behind
+// the checks the three share, so that a call with several defects is refused for the first of them in this order
+int fit_batched(bi_ctx* c, const char* who, bool real, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
+                const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, const double* prior_mean, const double* prior_sigma,
                 const double* prior_const, double* x_out, double* f_out, int32_t* flags_out, int64_t* counters) {
-    int rc = check_ready(c, true);
+    int rc = check_ready(c, !real);
     if (rc) return rc;
     if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !x_out ||
         !f_out || !flags_out)
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched: bad arguments");
-    for (int j = 0; j < F; ++j)
-        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
-            (var_kind[j] != 0 && var_kind[j] != 1))
-            return fail(c, BI_ERR_INVALID, "bi_fit_batched: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
-    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "bi_fit_batched: n_kinks must be >= 0 and the kinks of a variable ascending");
+        return fail(c, BI_ERR_INVALID, "%s: bad arguments", who);
+    if ((rc = check_var_map(c, who, F, var_kind, var_index))) return rc;
+    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "%s: n_kinks must be >= 0 and the kinks of a variable ascending", who);
+    if (real && (prior_mean || prior_sigma || prior_const)) {
+        if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "%s: %s", who, why);
+        if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
+    }
+    if (real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->real_T))) return rc;
     if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
     DeviceObjective o{};
-    o.c = c; o.F = F; o.var_kind = var_kind; o.var_index = var_index; o.z0 = z0; o.scale0 = scale0; o.unit = unit; o.dataset = dataset;
+    o.c = c; o.real = real;
+    o.m.F = F; o.m.d = c->d; o.m.S = c->S;
+    o.m.var_kind = var_kind; o.m.var_index = var_index; o.m.z0 = z0; o.m.scale0 = scale0; o.m.unit = unit; o.m.dataset = dataset;
     o.prior_mean = prior_mean; o.prior_sigma = prior_sigma; o.prior_const = prior_const;
     try {
         rc = minimize_batched(device_objective, &o, P, F, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x_out, f_out, flags_out, counters);
     } catch (const std::bad_alloc&) {
-        return fail(c, BI_ERR_NOMEM, "bi_fit_batched: out of host memory for %lld problems of %d variables", (long long)P, F);
+        return fail(c, BI_ERR_NOMEM, "%s: out of host memory for %lld problems of %d variables", who, (long long)P, F);
     } catch (const std::exception& e) {
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched: %s", e.what());
+        return fail(c, BI_ERR_INVALID, "%s: %s", who, e.what());
     }
     if (counters) counters[3] = o.evaluations;
     return rc;
@@ -541,8 +534,8 @@ int bi_fit_batched(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const i
                    const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                    const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, double* x_out,
                    double* f_out, int32_t* flags_out, int64_t* counters) {
-    return fit_batched(c, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, nullptr, nullptr,
-                       nullptr, x_out, f_out, flags_out, counters);
+    return fit_batched(c, "bi_fit_batched", false, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+                       nullptr, nullptr, nullptr, x_out, f_out, flags_out, counters);
 }
 
 int bi_fit_batched_gauss(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
@@ -555,8 +548,8 @@ int bi_fit_batched_gauss(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, c
     if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: bad arguments");
     if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: %s", why);
     if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
-    return fit_batched(c, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, prior_mean,
-                       prior_sigma, prior_const, x_out, f_out, flags_out, counters);
+    return fit_batched(c, "bi_fit_batched", false, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+                       prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);
 }
 
 }  // extern "C"

@@ -2,8 +2,9 @@
 // F variables, reduced over the last F - n_keep of them on the device.  The grid is never held anywhere: k_grid_points writes
 // one chunk of it into the layouts the resident planner reads, the planner and the evaluation kernels of
 // bi_plan_points_resident / bi_run_plan take the points where they lie, k_grid_reduce folds the chunk's result vector and
-// status words into the per-cell state in HBM, and the three output arrays are copied to the host once, at the end.  What a
-// chunk costs on the host is the planner's (see bi_sampler.h): its counts, the status OR, making and destroying the plan.
+// status words into the per-cell state in HBM, and the three output arrays are copied to the host once, at the end.  The
+// variables' map, the chunk's rows and their evaluation are ResidentPoints' (bi_varmap.h), shared with bi_sampler.h, whose
+// header says what a chunk costs on the host: the planner's counts, the status OR, making and destroying the plan.
 // (The reference's counterpart is the Python double loop of blueice/inference.py:424-432, one scalar call per grid point.)
 #pragma once
 
@@ -55,41 +56,30 @@ int grid_state_end(bi_ctx* c, GridArgs& a, double* log_marginal, double* profile
     return BI_OK;
 }
 
-int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_t n_total, const double* z0, const double* scale0,
-                const double* unit, const double* nodes, const double* term, const double* logw, int64_t chunk, double* log_marginal,
-                double* profile, int64_t* argmax, int64_t* counters) {
-    const int d = c->d, S = c->S;
-    const size_t nE = (size_t)E, nn = (size_t)n_total;
+int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_t n_total, const int32_t* var_kind, const int32_t* var_index,
+                const double* z0, const double* scale0, const double* unit, const double* nodes, const double* term, const double* logw,
+                int64_t chunk, double* log_marginal, double* profile, int64_t* argmax, int64_t* counters) {
+    const size_t nn = (size_t)n_total;
     const int64_t G = E * a.GK;
     if (chunk == 0) chunk = kGridDefaultChunk;
     chunk = std::min(chunk, G);
-    ScratchBuf b_z0, b_scale0, b_unit, b_ds, b_nodes, b_term, b_logw, b_zp, b_rsp, b_dsp, b_llp, b_p, b_q;
+    const size_t nc = (size_t)chunk;
+    ResidentPoints pts;
+    ScratchBuf b_nodes, b_term, b_logw, b_p, b_q;
     int rc;
     // (host copies that live until the uploads have been waited for)
-    const std::vector<double> h_z0 = host_copy(z0, nE * d, 0.0), h_scale0(scale0, scale0 + nE * S), h_unit(unit, unit + nE * S),
-                              h_nodes(nodes, nodes + nn), h_term = host_copy(term, term ? nn : 0, 0.0),
-                              h_logw = host_copy(logw, logw ? nn : 0, 0.0);
-    const std::vector<int64_t> h_ds = host_copy(dataset, nE, (int64_t)0);
-    if ((rc = dev_upload(c, b_z0, h_z0)) || (rc = dev_upload(c, b_scale0, h_scale0)) || (rc = dev_upload(c, b_unit, h_unit)) ||
-        (rc = dev_upload(c, b_ds, h_ds)) || (rc = dev_upload(c, b_nodes, h_nodes)) || (term && (rc = dev_upload(c, b_term, h_term))) ||
-        (logw && (rc = dev_upload(c, b_logw, h_logw))))
+    const std::vector<double> h_nodes(nodes, nodes + nn), h_term = host_copy(term, term ? nn : 0, 0.0), h_logw = host_copy(logw, logw ? nn : 0, 0.0);
+    if ((rc = pts.bind(c, a, E, chunk, a.F, var_kind, var_index, z0, scale0, unit, dataset)) || (rc = dev_upload(c, b_nodes, h_nodes)) ||
+        (term && (rc = dev_upload(c, b_term, h_term))) || (logw && (rc = dev_upload(c, b_logw, h_logw))))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const size_t nc = (size_t)chunk;
-    if ((rc = dev_alloc(c, b_zp, nc * std::max(d, 1) * sizeof(double))) || (rc = dev_alloc(c, b_rsp, nc * S * sizeof(double))) ||
-        (rc = dev_alloc(c, b_dsp, nc * sizeof(int64_t))) || (rc = dev_alloc(c, b_llp, nc * sizeof(double))) ||
-        (term && (rc = dev_alloc(c, b_p, nc * sizeof(double)))) || (logw && (rc = dev_alloc(c, b_q, nc * sizeof(double)))))
-        return rc;
-    a.d = d; a.S = S;
-    a.z0 = (const double*)b_z0.p; a.scale0 = (const double*)b_scale0.p; a.unit = (const double*)b_unit.p;
-    a.dataset = dataset ? (const int64_t*)b_ds.p : nullptr;
+    if ((term && (rc = dev_alloc(c, b_p, nc * sizeof(double)))) || (logw && (rc = dev_alloc(c, b_q, nc * sizeof(double))))) return rc;
     a.nodes = (const double*)b_nodes.p;
     a.term = term ? (const double*)b_term.p : nullptr;
     a.logw = logw ? (const double*)b_logw.p : nullptr;
-    a.z_dev = (double*)b_zp.p; a.rs_dev = (double*)b_rsp.p; a.ds_dev = (int64_t*)b_dsp.p;
     a.p = term ? (double*)b_p.p : nullptr;
     a.q = logw ? (double*)b_q.p : nullptr;
-    a.ll = (const double*)b_llp.p;
+    a.ll = (const double*)pts.llp.p;
     GridState st;
     if ((rc = grid_state_begin(c, st, a, G / a.R))) return rc;
     if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0;
@@ -100,19 +90,8 @@ int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_
         launch_grid_points(c, a);
         HIP_TRY(c, hipGetLastError());                          // (nothing is launched after a failed launch)
         bi_plan* plan = nullptr;
-        if ((rc = plan_points_resident_impl(c, a.n, d > 0 ? (const double*)a.z_dev : nullptr, (const double*)a.rs_dev,
-                                            (const int64_t*)a.ds_dev, 0, 1, &plan, false)))
-            return rc;
-        int32_t any = 0;
-        if ((rc = bi_run_plan(c, plan, (double*)b_llp.p)) || (rc = bi_plan_status(c, plan, &any))) {
-            bi_plan_destroy(c, plan);
-            return rc;
-        }
-        if (counters) { ++counters[0]; counters[1] += a.n; counters[3] += bi_plan_launches(plan); }
-        if (any & BI_ST_INTERNAL) {
-            bi_plan_destroy(c, plan);
-            return fail(c, BI_ERR_HIP, "bi_grid_reduce: the device gave up waiting for a partial sum (in-launch reduction): GPU fault");
-        }
+        if ((rc = pts.evaluate(c, a.n, "bi_grid_reduce", &plan, counters))) return rc;
+        if (counters) ++counters[0];
         a.st = (const int32_t*)plan->status.p;
         launch_grid_reduce(c, a);
         const hipError_t e = hipGetLastError();
@@ -149,14 +128,9 @@ int bi_grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_ke
     GridArgs a{};
     a.F = F; a.n_keep = n_keep;
     for (int j = 0; j < F; ++j) {
-        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
-            (var_kind[j] != 0 && var_kind[j] != 1))
-            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
-        for (int i = 0; i < j; ++i)
-            if (var_kind[i] == var_kind[j] && var_index[i] == var_index[j])
-                return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variables %d and %d are the same parameter", i, j);
+        if ((rc = check_variable(c, "bi_grid_reduce", j, var_kind, var_index, true))) return rc;
         if (n_nodes[j] < 1) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variable %d has %d nodes: need at least 1", j, (int)n_nodes[j]);
-        a.var_kind[j] = var_kind[j]; a.var_index[j] = var_index[j]; a.n_nodes[j] = n_nodes[j];
+        a.n_nodes[j] = n_nodes[j];
     }
     int64_t n_total = 0, K = 1, R = 1, cells = 0, G = 0;
     for (int j = 0; j < F; ++j) {
@@ -180,14 +154,13 @@ int bi_grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_ke
         if (logw && !(logw[i] < std::numeric_limits<double>::infinity()))
             return fail(c, BI_ERR_INVALID, "bi_grid_reduce: logw %lld is %g: a log weight is finite or -inf", (long long)i, logw[i]);
     }
-    if (multi_set(c) && (E > 1 || (dataset && dataset[0] != 0)))
-        return refuse_sets(c, "bi_grid_reduce with more than one dataset entry, or with another set than 0,");
-    if (dataset)
-        for (int64_t e = 0; e < E; ++e)
-            if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: dataset %lld of entry %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);
+    if ((rc = check_single_set(c, "bi_grid_reduce", "dataset entry", E, dataset)) ||
+        (rc = check_entry_datasets(c, "bi_grid_reduce", "entry", E, dataset, c->T)))
+        return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     try {
-        return grid_reduce(c, E, dataset, a, n_total, z0, scale0, unit, nodes, term, logw, chunk, log_marginal, profile, argmax, counters);
+        return grid_reduce(c, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk, log_marginal, profile, argmax,
+                           counters);
     } catch (const std::bad_alloc&) {
         return fail(c, BI_ERR_NOMEM, "bi_grid_reduce: out of host memory");
     }

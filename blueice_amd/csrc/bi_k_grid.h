@@ -64,20 +64,13 @@ __global__ __launch_bounds__(kThreads) void k_grid_points(const GridArgs a) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const int64_t g = a.g0 + i;
-    const int64_t e = g / a.GK;
-    for (int k = 0; k < a.d; ++k) a.z_dev[i * a.d + k] = a.z0[e * a.d + k];
-    for (int s = 0; s < a.S; ++s) a.rs_dev[i * a.S + s] = a.scale0[e * a.S + s];
     double p = 0.0, q = 0.0;
-    for (int j = 0; j < a.F; ++j) {
+    varmap_write_point(a, i, g / a.GK, [&](int j) {
         const int64_t at = a.node_off[j] + (g / a.stride[j]) % a.n_nodes[j];
-        const double y = a.nodes[at];
-        const int k = a.var_index[j];
-        if (a.var_kind[j] == 0) a.z_dev[i * a.d + k] = y;
-        else a.rs_dev[i * a.S + k] = __dmul_rn(y, a.unit[e * a.S + k]);
         if (a.term) p = __dadd_rn(p, a.term[at]);
         if (a.logw && j >= a.n_keep) q = __dadd_rn(q, a.logw[at]);
-    }
-    a.ds_dev[i] = a.dataset ? a.dataset[e] : 0;
+        return a.nodes[at];
+    });
     if (a.p) a.p[i] = p;
     if (a.q) a.q[i] = q;
 }

@@ -76,15 +76,7 @@ __global__ __launch_bounds__(kThreads) void k_stretch_propose(const StretchArgs 
         m.k = (int)(i % a.W);
     } else if (!stretch_move(a, i, m))
         return;
-    for (int q = 0; q < a.d; ++q) a.z_dev[i * a.d + q] = a.z0[m.e * a.d + q];
-    for (int s = 0; s < a.S; ++s) a.rs_dev[i * a.S + s] = a.scale0[m.e * a.S + s];
-    for (int v = 0; v < a.F; ++v) {
-        const double y = a.h < 0 ? a.x[(m.e * a.W + m.k) * a.F + v] : stretch_coord(a, m, v);
-        const int q = a.var_index[v];
-        if (a.var_kind[v] == 0) a.z_dev[i * a.d + q] = y;
-        else a.rs_dev[i * a.S + q] = __dmul_rn(y, a.unit[m.e * a.S + q]);
-    }
-    a.ds_dev[i] = a.dataset ? a.dataset[m.e] : 0;
+    varmap_write_point(a, i, m.e, [&](int v) { return a.h < 0 ? a.x[(m.e * a.W + m.k) * a.F + v] : stretch_coord(a, m, v); });
 }
 
 // accept or reject the proposals of a half-step, and append the moved walkers' state to row t of the chain (the other half's

@@ -208,36 +208,8 @@ int bi_fit_batched_real(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, co
                         double* f_out, int32_t* flags_out, int64_t* counters) {
     int rc = real_check(c, "bi_fit_batched_real", true);
     if (rc) return rc;
-    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi ||
-        !x_out || !f_out || !flags_out)
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: bad arguments");
-    for (int j = 0; j < F; ++j)
-        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
-            (var_kind[j] != 0 && var_kind[j] != 1))
-            return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
-    if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: n_kinks must be >= 0 and the kinks of a variable ascending");
-    if (prior_mean || prior_sigma || prior_const) {
-        if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: %s", why);
-        if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
-    }
-    for (int64_t p = 0; dataset && p < P; ++p)
-        if (dataset[p] < 0 || dataset[p] >= c->real_T)
-            return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: dataset[%lld] = %lld outside the %lld real-valued sets", (long long)p,
-                        (long long)dataset[p], (long long)c->real_T);
-    if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
-    DeviceObjective o{};
-    o.c = c; o.F = F; o.var_kind = var_kind; o.var_index = var_index; o.z0 = z0; o.scale0 = scale0; o.unit = unit; o.dataset = dataset;
-    o.prior_mean = prior_mean; o.prior_sigma = prior_sigma; o.prior_const = prior_const;
-    o.real = true;
-    try {
-        rc = minimize_batched(device_objective, &o, P, F, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x_out, f_out, flags_out, counters);
-    } catch (const std::bad_alloc&) {
-        return fail(c, BI_ERR_NOMEM, "bi_fit_batched_real: out of host memory for %lld problems of %d variables", (long long)P, F);
-    } catch (const std::exception& e) {
-        return fail(c, BI_ERR_INVALID, "bi_fit_batched_real: %s", e.what());
-    }
-    if (counters) counters[3] = o.evaluations;
-    return rc;
+    return fit_batched(c, "bi_fit_batched_real", true, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+                       prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);
 }
 
 }  // extern "C"

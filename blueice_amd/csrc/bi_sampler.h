@@ -2,56 +2,29 @@
 // likelihood as the target density.  The points never leave the device: k_stretch_propose writes the proposals of the moving
 // half into the layouts the resident planner reads, the planner and the evaluation kernels of bi_plan_points_resident /
 // bi_run_plan take them where they lie, k_stretch_accept moves the walkers and appends to the chain in HBM, and chain, log
-// likelihoods and counters are copied to the host once, at the end.  What a half-step still costs on the host is the
+// likelihoods and counters are copied to the host once, at the end.  The variables' map, the proposals' rows and their
+// evaluation are ResidentPoints' (bi_varmap.h), shared with bi_grid.h.  What a half-step still costs on the host is the
 // planner's: it reads its counts back to size its launches (plan_report), the plan's status OR is a second read
 // (bi_plan_status), the plan is made and destroyed (buffers from the context's recycle cache, one stream synchronisation)
-// every half-step.  A plan reused across half-steps would remove most of that; it is not part of this file.  (The
+// every half-step.  A plan reused across half-steps would remove most of that; its place is ResidentPoints::evaluate.  (The
 // reference's counterpart is emcee's loop of n_walkers x n_steps scalar likelihood calls, blueice/inference.py:254-321.)
 #pragma once
 
 namespace {
 
+// what only the sampler keeps on the device
 struct SamplerBuffers {
-    DevBuf kind, index, z0, scale0, unit, dataset, lo, hi, x, ll, nacc, zp, rsp, dsp, llp, chain, chain_ll, pmean, psigma, pconst;
-    ~SamplerBuffers() {
-        for (DevBuf* b : {&kind, &index, &z0, &scale0, &unit, &dataset, &lo, &hi, &x, &ll, &nacc, &zp, &rsp, &dsp, &llp, &chain, &chain_ll, &pmean,
-                          &psigma, &pconst})
-            dev_free(*b);
-    }
+    ScratchBuf lo, hi, x, ll, nacc, chain, chain_ll, pmean, psigma, pconst;
 };
-
-template <class T>
-std::vector<T> host_copy(const T* p, size_t n, T fill) {
-    return p ? std::vector<T>(p, p + n) : std::vector<T>(n, fill);
-}
-
-// plan and evaluate the n points staged in the proposal buffers into b.llp; the plan is handed back for its status words
-int sampler_evaluate(bi_ctx* c, SamplerBuffers& b, int64_t n, bi_plan** plan, int64_t* counters) {
-    int rc = plan_points_resident_impl(c, n, c->d > 0 ? (const double*)b.zp.p : nullptr, (const double*)b.rsp.p, (const int64_t*)b.dsp.p, 0, 1,
-                                       plan, false);
-    if (rc) return rc;
-    int32_t any = 0;
-    if ((rc = bi_run_plan(c, *plan, (double*)b.llp.p)) || (rc = bi_plan_status(c, *plan, &any))) {
-        bi_plan_destroy(c, *plan);
-        *plan = nullptr;
-        return rc;
-    }
-    if (counters) { counters[1] += n; counters[3] += bi_plan_launches(*plan); }
-    if (any & BI_ST_INTERNAL) {
-        bi_plan_destroy(c, *plan);
-        *plan = nullptr;
-        return fail(c, BI_ERR_HIP, "bi_sample_stretch: the device gave up waiting for a partial sum (in-launch reduction): GPU fault");
-    }
-    return BI_OK;
-}
 
 int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                    const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
                    int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, const double* prior_mean, const double* prior_sigma,
                    const double* prior_const, double* chain, double* ll, int64_t* n_accepted, int64_t* counters) {
-    const int d = c->d, S = c->S;
     const size_t nE = (size_t)E, nW = (size_t)E * W;
     SamplerBuffers b;
+    ResidentPoints pts;
+    StretchArgs s{};
     int rc;
     // the chain stays in HBM until the end: it has to fit there
     {
@@ -62,14 +35,10 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
             return fail(c, BI_ERR_NOMEM, "bi_sample_stretch: the chain (%lld steps x %lld walkers x %d variables: %.3g bytes) is larger than the free "
                                          "device memory (%zu bytes): run fewer steps per call", (long long)n_steps, (long long)nW, F, need, free_b);
     }
-    // (host copies that live until the uploads have been waited for; absent optional arrays take their defaults)
-    const std::vector<int32_t> h_kind = host_copy(var_kind, (size_t)F, 0), h_index = host_copy(var_index, (size_t)F, 0);
-    const std::vector<double> h_z0 = host_copy(z0, nE * d, 0.0), h_scale0 = host_copy(scale0, nE * S, 1.0), h_unit = host_copy(unit, nE * S, 1.0),
-                              h_lo = host_copy(lo, (size_t)F, 0.0), h_hi = host_copy(hi, (size_t)F, 0.0), h_x = host_copy(x0, nW * F, 0.0);
-    const std::vector<int64_t> h_ds = host_copy(dataset, nE, (int64_t)0);
-    if ((rc = dev_upload(c, b.kind, h_kind)) || (rc = dev_upload(c, b.index, h_index)) || (rc = dev_upload(c, b.z0, h_z0)) ||
-        (rc = dev_upload(c, b.scale0, h_scale0)) || (rc = dev_upload(c, b.unit, h_unit)) || (rc = dev_upload(c, b.dataset, h_ds)) ||
-        (rc = dev_upload(c, b.lo, h_lo)) || (rc = dev_upload(c, b.hi, h_hi)) || (rc = dev_upload(c, b.x, h_x)))
+    // (host copies that live until the uploads have been waited for)
+    const std::vector<double> h_lo = host_copy(lo, (size_t)F, 0.0), h_hi = host_copy(hi, (size_t)F, 0.0), h_x = host_copy(x0, nW * F, 0.0);
+    if ((rc = pts.bind(c, s, E, (int64_t)nW, F, var_kind, var_index, z0, scale0, unit, dataset)) || (rc = dev_upload(c, b.lo, h_lo)) ||
+        (rc = dev_upload(c, b.hi, h_hi)) || (rc = dev_upload(c, b.x, h_x)))
         return rc;
     // Gaussian constraint terms (prior_sigma NULL here: none on any variable)
     const std::vector<double> h_pmean = host_copy(prior_sigma ? prior_mean : nullptr, (size_t)F, 0.0),
@@ -81,24 +50,17 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     const size_t steps = (size_t)n_steps;
     if ((rc = dev_alloc(c, b.ll, nW * sizeof(double))) || (rc = dev_alloc(c, b.nacc, nW * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, b.zp, nW * std::max(d, 1) * sizeof(double))) || (rc = dev_alloc(c, b.rsp, nW * S * sizeof(double))) ||
-        (rc = dev_alloc(c, b.dsp, nW * sizeof(int64_t))) || (rc = dev_alloc(c, b.llp, nW * sizeof(double))) ||
         (rc = dev_alloc(c, b.chain, std::max<size_t>(steps, 1) * nW * F * sizeof(double))) ||
         (rc = dev_alloc(c, b.chain_ll, std::max<size_t>(steps, 1) * nW * sizeof(double))))
         return rc;
     HIP_TRY(c, hipMemsetAsync(b.nacc.p, 0, nW * sizeof(int64_t), c->stream));
-    StretchArgs s{};
-    s.E = E; s.W = W; s.F = F; s.d = d; s.S = S;
+    s.E = E; s.W = W;
     s.first_ensemble = first_ensemble;
     s.k0 = (uint32_t)seed; s.k1 = (uint32_t)(seed >> 32);
     s.a = a;
-    s.var_kind = (const int32_t*)b.kind.p; s.var_index = (const int32_t*)b.index.p;
-    s.z0 = (const double*)b.z0.p; s.scale0 = (const double*)b.scale0.p; s.unit = (const double*)b.unit.p;
-    s.dataset = dataset ? (const int64_t*)b.dataset.p : nullptr;
     s.lo = (const double*)b.lo.p; s.hi = (const double*)b.hi.p;
     s.x = (double*)b.x.p; s.ll = (double*)b.ll.p; s.n_accepted = (int64_t*)b.nacc.p;
-    s.z_dev = (double*)b.zp.p; s.rs_dev = (double*)b.rsp.p; s.ds_dev = (int64_t*)b.dsp.p;
-    s.ll_prop = (const double*)b.llp.p;
+    s.ll_prop = (const double*)pts.llp.p;
     s.prior_mean = prior_sigma ? (const double*)b.pmean.p : nullptr;
     s.prior_sigma = prior_sigma ? (const double*)b.psigma.p : nullptr;
     s.prior_const = prior_const ? (const double*)b.pconst.p : nullptr;
@@ -109,7 +71,7 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
     s.h = -1;
     launch_stretch_propose(c, s);
     HIP_TRY(c, hipGetLastError());
-    if ((rc = sampler_evaluate(c, b, (int64_t)nW, &plan, counters))) return rc;
+    if ((rc = pts.evaluate(c, (int64_t)nW, "bi_sample_stretch", &plan, counters))) return rc;
     {
         std::vector<double> h_ll(nW);
         std::vector<int32_t> h_st(nW);
@@ -118,7 +80,7 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
             launch_stretch_start_density(c, s);                 // b.ll = b.llp + p
             e = hipGetLastError();
         } else
-            e = hipMemcpyAsync(b.ll.p, b.llp.p, nW * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
+            e = hipMemcpyAsync(b.ll.p, pts.llp.p, nW * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(h_ll.data(), b.ll.p, nW * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(h_st.data(), plan->status.p, nW * sizeof(int32_t), hipMemcpyDefault, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
@@ -146,7 +108,7 @@ int sample_stretch(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, 
             s.chain_ll = (double*)b.chain_ll.p + (size_t)t * nW;
             launch_stretch_propose(c, s);
             HIP_TRY(c, hipGetLastError());                      // (nothing is launched after a failed launch)
-            if ((rc = sampler_evaluate(c, b, n, &plan, counters))) return rc;
+            if ((rc = pts.evaluate(c, n, "bi_sample_stretch", &plan, counters))) return rc;
             s.st_prop = (const int32_t*)plan->status.p;
             launch_stretch_accept(c, s);
             const hipError_t e = hipGetLastError();
@@ -188,15 +150,9 @@ int bi_sample_stretch_gauss(bi_ctx* c, int64_t E, int W, int F, const int32_t* v
         return fail(c, BI_ERR_INVALID, "bi_sample_stretch: need E >= 1, E * W <= 2^30, 0 <= n_steps <= 2^31 and ensembles within [0, 2^32)");
     if (!var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !n_accepted || (n_steps > 0 && (!chain || !ll)))
         return fail(c, BI_ERR_INVALID, "bi_sample_stretch: NULL argument");
-    for (int j = 0; j < F; ++j)
-        if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
-            (var_kind[j] != 0 && var_kind[j] != 1))
-            return fail(c, BI_ERR_INVALID, "bi_sample_stretch: variable %d is neither a shape parameter nor a rate multiplier of this model", j);
-    if (multi_set(c) && (E > 1 || (dataset && dataset[0] != 0)))
-        return refuse_sets(c, "bi_sample_stretch with more than one ensemble, or with another set than 0,");
-    if (dataset)
-        for (int64_t e = 0; e < E; ++e)
-            if (dataset[e] < 0 || dataset[e] >= c->T) return fail(c, BI_ERR_INVALID, "bi_sample_stretch: dataset %lld of ensemble %lld outside [0, %lld)", (long long)dataset[e], (long long)e, (long long)c->T);
+    if ((rc = check_var_map(c, "bi_sample_stretch", F, var_kind, var_index)) || (rc = check_single_set(c, "bi_sample_stretch", "ensemble", E, dataset)) ||
+        (rc = check_entry_datasets(c, "bi_sample_stretch", "ensemble", E, dataset, c->T)))
+        return rc;
     // the constraint terms: all three arrays NULL is bi_sample_stretch; otherwise mean and sigma are required
     if (prior_mean || prior_sigma || prior_const) {
         if (const char* why = gauss_terms_invalid(F, E, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_sample_stretch_gauss: %s", why);

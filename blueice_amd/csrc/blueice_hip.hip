@@ -1842,6 +1842,7 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 
 }  // extern "C"
 
+#include "bi_varmap.h"
 #include "bi_fit.h"
 #include "bi_hess.h"
 #include "bi_gof.h"

@@ -564,6 +564,18 @@ class DeviceContext:
                                              ptr(x), ptr(f), ptr(flags), ptr(counters)))
         return 0
 
+    def _map_entries(self, E, z0, scale0, unit):
+        """the variable map's per-entry arrays with their rows broadcast to E entries -> z0 [E, d], scale0 [E, S], unit [E, S]"""
+        def rows(a, n):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1, n), (E, n)))
+        return rows(z0, self.d) if self.d else np.zeros((E, 0)), rows(scale0, self.S), rows(unit, self.S)
+
+    def _check_resident(self, rc):
+        """`_check` for the loops over resident points: the resident planner's two refusals are a PlannerRefused"""
+        if rc == _capi.ERR_INVALID and self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:
+            raise PlannerRefused(self._lib.bi_last_error(self._h).decode())
+        self._check(rc)
+
     def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0, priors=None):
         """bi_sample_stretch: n_steps stretch-move steps of E ensembles of W walkers with this context's likelihood as the
         target.  x0 [E, W, F]; z0 [E, d], scale0 / unit [E, S], dataset [E] or None as `fit_batched`.
@@ -575,9 +587,7 @@ class DeviceContext:
         if W2 != W:
             raise ValueError("x0 must be [E, W, F]")
         kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
-        z0 = np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64).reshape(-1, self.d), (E, self.d))) if self.d else np.zeros((E, 0))
-        scale0 = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
-        unit = np.ascontiguousarray(np.broadcast_to(np.asarray(unit, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        z0, scale0, unit = self._map_entries(E, z0, scale0, unit)
         if dataset is not None:
             dataset = np.ascontiguousarray(np.broadcast_to(np.asarray(dataset, dtype=np.int64), (E,)))
         lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
@@ -596,11 +606,7 @@ class DeviceContext:
             rc = self._lib.bi_sample_stretch_gauss(*head, ptr(mean), ptr(sigma), ptr(const), *tail)
         else:
             rc = self._lib.bi_sample_stretch(*head, *tail)
-        if rc == _capi.ERR_INVALID:
-            msg = self._lib.bi_last_error(self._h).decode()
-            if self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:             # the resident planner's two refusals
-                raise PlannerRefused(msg)
-        self._check(rc)
+        self._check_resident(rc)
         return chain, ll, n_acc, counters
 
     def grid_reduce(self, kind, index, z0, scale0, unit, dataset, n_keep, nodes, term=None, logw=None, chunk=0):
@@ -627,9 +633,7 @@ class DeviceContext:
         if dataset is not None:
             dataset = np.ascontiguousarray(np.atleast_1d(np.asarray(dataset, dtype=np.int64)))
         E = 1 if dataset is None else len(dataset)
-        z0 = np.ascontiguousarray(np.broadcast_to(np.asarray(z0, dtype=np.float64).reshape(-1, self.d), (E, self.d))) if self.d else np.zeros((E, 0))
-        scale0 = np.ascontiguousarray(np.broadcast_to(np.asarray(scale0, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
-        unit = np.ascontiguousarray(np.broadcast_to(np.asarray(unit, dtype=np.float64).reshape(-1, self.S), (E, self.S)))
+        z0, scale0, unit = self._map_entries(E, z0, scale0, unit)
         K = int(np.prod(n_nodes[:max(0, min(n_keep, F))], dtype=np.int64)) if F and np.all(n_nodes >= 1) else 1
         if E * K > 2 ** 24:                                   # (refused by the library too; here before the outputs are made)
             raise ValueError("bi_grid_reduce: E * K (%d dataset entries x %d kept points) is more than 2^24 cells" % (E, K))
@@ -639,11 +643,7 @@ class DeviceContext:
         rc = self._lib.bi_grid_reduce(self._h, E, ptr(dataset), F, n_keep, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
                                       ptr(unit), ptr(n_nodes), ptr(nodes_flat), ptr(term), ptr(logw), int(chunk), ptr(log_marginal),
                                       ptr(profile), ptr(argmax), ptr(counters))
-        if rc == _capi.ERR_INVALID:
-            msg = self._lib.bi_last_error(self._h).decode()
-            if self._lib.bi_get_param(self._h, b'last_plan_refused') > 0:             # the resident planner's two refusals
-                raise PlannerRefused(msg)
-        self._check(rc)
+        self._check_resident(rc)
         return log_marginal, profile, argmax, counters
 
     def selftest_grid_reduce(self, t, q=None, chunk=0):

@@ -165,23 +165,17 @@ def _native_plan(lf, axes, fixed, livetime_days):
     settings, the priors at the nodes (term) and the fixed parameters' priors (a constant) -- or None where Python sits
     between the parameters and the device call (the conditions of BatchObjective.native(), without its restriction on priors)."""
     from .likelihood import DeviceLogLikelihood, _prior_of
+    from .profile import variable_map
     ok = isinstance(lf, DeviceLogLikelihood) and getattr(lf, 'ctx', None) is not None and hasattr(lf.ctx, 'grid_reduce') and \
         not any(getattr(lf, 'source_apply_efficiency', [])) and lf.config.get('unphysical_behaviour') != 'error'
     if not ok:
         return None
-    shape_names = list(lf.shape_parameters)
-    kind, index, term = [], [], []
-    for name, nodes in axes:
-        if name in lf.shape_parameters:
-            kind.append(0)
-            index.append(shape_names.index(name))
-            prior = lf.shape_parameters[name][1]
-        elif name.endswith('_rate_multiplier') and name[:-16] in lf.source_name_list:
-            kind.append(1)
-            index.append(lf.source_name_list.index(name[:-16]))
-            prior = lf.rate_parameters.get(name[:-16])
-        else:
-            return None
+    var_map = variable_map(lf, [name for name, _ in axes])
+    if var_map is None:
+        return None
+    term = []
+    for (name, nodes), kind in zip(axes, var_map[0]):
+        prior = lf.rate_parameters.get(name[:-16]) if kind else lf.shape_parameters[name][1]
         term.append(np.zeros(len(nodes)) if prior is None else _prior_of(prior, nodes))
     z0, scale0, _, unit = lf._batch_terms(dict(fixed), livetime_days, want_unit=True)
     # the priors of the parameters that are no axis of the grid, at their values
@@ -198,8 +192,7 @@ def _native_plan(lf, axes, fixed, livetime_days):
         return None                                          # (a prior that is nan or +inf somewhere: the host engine reports it)
     if all(not np.any(t) for t in term):
         term = None
-    return dict(kind=np.array(kind, dtype=np.int32), index=np.array(index, dtype=np.int32), z0=z0, scale0=scale0, unit=unit,
-                term=term, const=const)
+    return dict(kind=var_map[0], index=var_map[1], z0=z0, scale0=scale0, unit=unit, term=term, const=const)
 
 
 def _host_engine(lf, axes, n_keep, logw, datasets, livetime_days, chunk, fixed):

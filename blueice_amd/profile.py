@@ -37,6 +37,21 @@ def supports_batched_fits(lf):
     return hasattr(lf, 'eval_points') and hasattr(lf, 'get_bounds')
 
 
+def variable_map(lf, names):
+    """Which native variable is which parameter of `lf`: (kind [F], index [F]) -- kind 0: shape parameter `index`, kind 1: the
+    rate multiplier of source `index` -- or None where a name is neither."""
+    shape_names, found = list(lf.shape_parameters), []
+    for n in names:
+        if n in shape_names:
+            found.append((0, shape_names.index(n)))
+        elif n.endswith('_rate_multiplier') and n[:-16] in lf.source_name_list:
+            found.append((1, lf.source_name_list.index(n[:-16])))
+        else:
+            return None
+    found = np.array(found, dtype=np.int32).reshape(-1, 2)
+    return np.ascontiguousarray(found[:, 0]), np.ascontiguousarray(found[:, 1])
+
+
 class BatchObjective:
     """f(x [n, F], rows [n]) -> (-ll [n], d(-ll)/dx [n, F]) for problems `rows` of P, whose fixed parameters are
     `points` (name -> array [P]) and `fixed` (name -> scalar)."""
@@ -84,17 +99,9 @@ class BatchObjective:
         pts.update(self.fixed)
         z0, scale0, prior, unit = lf._batch_terms(pts, self.livetime_days, want_unit=True)
         z0, scale0, unit = (np.ascontiguousarray(np.broadcast_to(a, (P,) + a.shape[1:]), dtype=float) for a in (z0, scale0, unit))
-        kind, index = [], []
-        shape_names = list(lf.shape_parameters)
-        for n in self.names:
-            if n in lf.shape_parameters:
-                kind.append(0)
-                index.append(shape_names.index(n))
-            elif n.endswith('_rate_multiplier') and n[:-16] in lf.source_name_list:
-                kind.append(1)
-                index.append(lf.source_name_list.index(n[:-16]))
-            else:
-                return None
+        var_map = variable_map(lf, self.names)
+        if var_map is None:
+            return None
         # the constraint terms: the fixed parameters' priors at the problems' values (the multipliers as given: not scale0,
         # which carries live time), the floating ones' as mean / sigma on their variable
         mult = np.ones_like(scale0)
@@ -102,7 +109,7 @@ class BatchObjective:
             if n + '_rate_multiplier' in pts:
                 mult[:, s] = pts[n + '_rate_multiplier']
         mean, sigma, const = gaussian_terms(lf, self.names, z0, mult)
-        self._native = dict(P=P, z0=z0, scale0=scale0, unit=unit, kind=np.array(kind, dtype=np.int32), index=np.array(index, dtype=np.int32),
+        self._native = dict(P=P, z0=z0, scale0=scale0, unit=unit, kind=var_map[0], index=var_map[1],
                             prior_mean=mean, prior_sigma=sigma, prior_const=const)
         return self._native
 
