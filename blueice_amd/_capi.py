@@ -68,6 +68,8 @@ SIGNATURES = {
     'bi_real_count_sets': (_i64, [_p]),
     'bi_download_real_counts': (C.c_int, [_p, _i64, _p]),
     'bi_eval_real': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_eval_fisher': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_fisher_variant': (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'bi_minimize_batched': (C.c_int, [_p, _p, _i64, C.c_int, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p, _p]),
     'bi_fit_batched_gauss': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,

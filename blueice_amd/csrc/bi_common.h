@@ -14,6 +14,7 @@
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
+//     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
 //     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
@@ -79,6 +80,9 @@ void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, cons
 int launch_morph_bbgrad(bi_ctx* c, int G, int DZ, const LaunchArgs& a, dim3 grid, bool nt);
 // k_morph_hess<G, DM, UNB, NT>: value, gradient and Hessian of one point per item; BI_ERR_INVALID for a (G, DM) without a variant
 int launch_morph_hess(bi_ctx* c, int G, int DM, const HessArgs& a, dim3 grid, bool nt);
+// k_morph_fisher<G, DM, NT>: the expected information of one point per item (HessArgs, no counts read); G = 4, 8, 16 coefficient
+// columns, DM first-order columns; BI_ERR_INVALID for a (G, DM) without a variant
+int launch_morph_fisher(bi_ctx* c, int G, int DM, const HessArgs& a, dim3 grid, bool nt);
 // k_morph_gof<NT>: half-deviance and Pearson chi2 of one (point, dataset) per item, HessArgs with ONE coefficient column
 void launch_morph_gof(bi_ctx* c, const HessArgs& a, dim3 grid, bool nt);
 // k_morph_expect: the per-bin expectation of n_items (<= 65 535) points, a.R groups of rows each

@@ -440,6 +440,21 @@ class DeviceContext:
         self._check(self._lib.bi_expected_counts(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
         return out
 
+    def eval_fisher(self, z, rate_scale=None):
+        """The expected (Fisher) information over (z, rate_scale) at P truths, no data needed (bi_eval_fisher) ->
+        (info [P, d + S, d + S], total expectation [P], unbounded [P, d + S] bins that expect nothing but move with the
+        parameter and are left out of `info`, status [P]); nan matrices for points outside the anchor box, with unphysical
+        rates or with a negative expectation.  Raises ValueError (BI_ERR_INVALID) for Beeston-Barlow and unbinned contexts
+        and for more than 16 coefficient columns."""
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        F = self.d + self.S
+        info = np.empty((P, F, F), dtype=np.float64)
+        total = np.empty(P, dtype=np.float64)
+        unbounded = np.zeros((P, F), dtype=np.int64)
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_eval_fisher(self._h, P, ptr(z), ptr(rate_scale), ptr(info), ptr(total), ptr(unbounded), ptr(status)))
+        return info, total, unbounded, status
+
     # -- coarse views: the expectation and the data summed over groups of fine bins (bi_set_coarse_binning ...) --
     def set_coarse_binning(self, n_fine=None, groups=None):
         """The context's coarse binning: n_fine [k] fine bins per analysis axis, groups: per axis the ascending fine-bin

@@ -40,7 +40,7 @@ from scipy import stats
 from scipy.optimize import brentq, minimize
 
 from .exceptions import NoOpimizationNecessary, NotPreparedException, OptimizationFailed
-from .hessian import to_log10
+from .hessian import chain_rule_information, chain_rule_unbounded, covariance_from_information, prior_derivatives, to_log10
 from .profile import bestfit_batched, supports_batched_fits
 from .sampler import sample_posterior
 from .utils import is_numeric
@@ -50,6 +50,7 @@ __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', '
            'toy_test_statistics', 'neyman_thresholds', 'expected_counts', 'expected_counts_points', 'gof_statistics', 'goodness_of_fit',
            'expected_coarse', 'expected_coarse_points', 'coarse_counts',
            'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
+           'fisher_information_points', 'fisher_information', 'expected_covariance', 'expected_errors',
            'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
            'plot_likelihood_ratio']
 
@@ -657,7 +658,7 @@ def _covariance(lf, values, livetime_days=None, datasets=None, log_rates=False, 
     return order, cov, scalar
 
 
-def hesse(lf, values, livetime_days=None, datasets=None, **fixed):
+def hesse(lf, values, livetime_days=None, datasets=None, information='observed', **fixed):
     """Covariance of the floating parameters at fitted values: (-H)^-1, H the Hessian of the log likelihood from the device
     (`lf.values_gradients_hessians`, one call for all points).
 
@@ -665,9 +666,113 @@ def hesse(lf, values, livetime_days=None, datasets=None, **fixed):
     named there float, `fixed` holds others at given values.  datasets: the dataset of every point, e.g. np.arange(T) for
     the T toys fitted by `bestfit_toys`.  -> (names [F], covariance [F, F] for scalar values, [P, F, F] for arrays).  The
     covariance is nan (with one warning per call) where -H is not positive definite or ll = -inf.  On an anchor the
-    Hessian is that of the cell the point is assigned to."""
+    Hessian is that of the cell the point is assigned to.
+
+    information='expected': the inverse of the Fisher information at `values` instead (`expected_covariance`'s, all points
+    in one device call; the data and `datasets` are not looked at) -- positive semi-definite by construction, the
+    alternative where -H of sparse data or of a fit that ended on a kink of the morph is not positive definite."""
+    if information == 'expected':
+        cols = {k: np.atleast_1d(np.asarray(v, dtype=float)) for k, v in values.items()}
+        scalar = all(np.ndim(v) == 0 for v in values.values()) and datasets is None
+        P = max([len(c) for c in cols.values()] + [1 if datasets is None else len(np.atleast_1d(datasets))])
+        points = {k: np.broadcast_to(c, (P,)) for k, c in cols.items()}
+        points.update((k, np.broadcast_to(np.asarray(v, dtype=float), (P,))) for k, v in fixed.items())
+        names, cov = _expected_covariance_points(lf, points, list(values.keys()), livetime_days, True, False, 'hesse')
+        return names, (cov[0] if scalar else cov)
+    if information != 'observed':
+        raise ValueError("hesse: information = %r (it is 'observed' or 'expected')" % (information,))
     names, cov, scalar = _covariance(lf, values, livetime_days=livetime_days, datasets=datasets, **fixed)
     return names, (cov[0] if scalar else cov)
+
+
+# ---- expected (Fisher) information ------------------------------------------------------------------------------------
+
+def fisher_information_points(lf, points, livetime_days=None, priors=True):
+    """The expected (Fisher) information of the binned likelihood at P truths, before any data exist:
+        I_qr = sum_b d_q mu_b d_r mu_b / mu_b    (- the curvature of the log priors on the diagonal, unless priors=False)
+    over every registered rate multiplier, then every shape parameter.  points = dict parameter name -> array [P] (as
+    `eval_points`; absent parameters at their defaults).  -> (names [F], I [P, F, F], unbounded [P, F] bool).  The sum over
+    the bins runs on the device (bi_eval_fisher: one pass over the corner rows of every truth, no data needed); live time,
+    efficiencies and shape parameters that double as efficiencies enter by the chain rule of `values_gradients_hessians`
+    (`chain_rule_information`), priors through `prior_derivatives`.  A bin that expects nothing at the truth but would with
+    another value of a parameter (a signal multiplier of 0, a truth on an anchor) holds unbounded information on it: it is
+    left out of I and the parameter is flagged.  A truth outside the anchor box, with unphysical rates or with a negative
+    expectation gives a nan matrix.  On an anchor I is that of the cell the point is assigned to."""
+    _binned_for_gof(lf, 'fisher_information_points')
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    P = len(z)
+    info, _, unb, _ = lf.ctx.eval_fisher(z if z.shape[1] else None, scale)
+    mult, L, eff, eff_axis, rate_sources = lf._chain_rule_terms(points, P, livetime_days)
+    curvature = None
+    if priors:
+        nr = len(rate_sources)
+        curvature = np.zeros((P, nr + z.shape[1]))
+        for j, s in enumerate(rate_sources):
+            lp = lf.rate_parameters[lf.source_name_list[s]]
+            if lp is not None:
+                curvature[:, j] = prior_derivatives(lp, mult[:, s])[1]
+        for i, (_, (_, lp, _)) in enumerate(lf.shape_parameters.items()):
+            if lp is not None:
+                curvature[:, nr + i] = prior_derivatives(lp, z[:, i])[1]
+    out = chain_rule_information(info, mult, L, eff, eff_axis, rate_sources, curvature)
+    return lf._parameter_names(), out, chain_rule_unbounded(unb, mult, L, eff, eff_axis, rate_sources)
+
+
+def fisher_information(lf, livetime_days=None, priors=True, **truth):
+    """`fisher_information_points` at one truth (parameter values; absent parameters at their defaults) ->
+    (names [F], I [F, F], unbounded [F] bool)."""
+    names, info, unb = fisher_information_points(lf, {k: np.array([v], dtype=float) for k, v in truth.items()},
+                                                 livetime_days=livetime_days, priors=priors)
+    return names, info[0], unb[0]
+
+
+def _expected_covariance_points(lf, points, floating, livetime_days, priors, log_rates, what):
+    """-> (names of the floating parameters, covariance [P, F, F]) from the Fisher information at `points`; one warning."""
+    names, info, unb = fisher_information_points(lf, points, livetime_days=livetime_days, priors=priors)
+    floating = names if floating is None else list(floating)
+    missing = [k for k in floating if k not in names]
+    if missing:
+        raise ValueError("not parameters of the likelihood: %s" % ', '.join(missing))
+    order = [k for k in names if k in floating]
+    idx = np.array([names.index(k) for k in order], dtype=int)
+    If = info[:, idx[:, None], idx[None, :]]
+    uf = unb[:, idx]
+    if log_rates:            # y = log10 x: dx / dy = x ln 10 on both sides (no second-order term: the expected score is zero)
+        P = len(info)
+        x = np.stack([np.broadcast_to(np.asarray(points.get(k, 1.0), dtype=float), (P,)) * np.log(10.0) if k.endswith('_rate_multiplier')
+                      else np.ones(P) for k in order], axis=1) if order else np.zeros((P, 0))
+        If = If * x[:, :, None] * x[:, None, :]
+    cov = covariance_from_information(If, uf)
+    bad = ~np.all(np.isfinite(cov), axis=(1, 2))
+    if uf.any() or bad.any():
+        said = []
+        if uf.any():
+            said.append("unbounded information on %s at %d of %d points (bins that expect nothing there but would with another value: "
+                        "variance 0)" % (', '.join(k for k, u in zip(order, uf.any(axis=0)) if u), int(np.count_nonzero(uf.any(axis=1))), len(cov)))
+        if bad.any():
+            said.append("the information is singular or nan at %d of %d points: their covariance is nan" % (int(np.count_nonzero(bad)), len(cov)))
+        warnings.warn("%s: %s" % (what, '; '.join(said)), RuntimeWarning, stacklevel=3)
+    return order, cov
+
+
+def expected_covariance(lf, floating=None, livetime_days=None, priors=True, rates_in_log_space=False, **truth):
+    """The expected covariance of the parameters at a truth, before any data exist: the inverse of the Fisher information
+    (`fisher_information`) -> (names [F], covariance [F, F]), `hesse`'s format.  floating: the names that float (default:
+    every registered parameter); the others are held at their truth -- their rows and columns are struck before the
+    inversion.  A parameter with unbounded information gets variance 0 (`covariance_from_information`); the covariance is nan
+    where the floating block is singular.  Either issues one warning.  rates_in_log_space: rate multipliers as log10 values,
+    as `bestfit_minuit` reports them."""
+    order, cov = _expected_covariance_points(lf, {k: np.array([v], dtype=float) for k, v in truth.items()}, floating, livetime_days,
+                                             priors, rates_in_log_space, 'expected_covariance')
+    return order, cov[0]
+
+
+def expected_errors(lf, floating=None, livetime_days=None, priors=True, rates_in_log_space=False, **truth):
+    """The expected standard deviations at a truth -> OrderedDict name -> sigma: the square roots of the diagonal of
+    `expected_covariance` (same arguments)."""
+    order, cov = _expected_covariance_points(lf, {k: np.array([v], dtype=float) for k, v in truth.items()}, floating, livetime_days,
+                                             priors, rates_in_log_space, 'expected_errors')
+    return OrderedDict(zip(order, np.sqrt(np.diag(cov[0]))))
 
 
 _MINUIT_DISPLAY_OPTIONS = ('print_level', 'pedantic', 'errordef')

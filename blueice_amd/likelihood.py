@@ -720,6 +720,31 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         return [self.rate_parameters[s] for s in self.source_name_list if s in self.rate_parameters] + \
             [sp[1] for sp in self.shape_parameters.values()]
 
+    def _chain_rule_terms(self, points, P, livetime_days):
+        """What the chain rule from (z, rate_scale) to the user's parameters needs (blueice_amd.hessian.user_jacobian), of the
+        P points last passed to `_batch_terms`: -> (mult [P, S], live-time factor, eff [P, S], eff_axis [S], rate_sources)"""
+        S = len(self.source_name_list)
+        mult = np.ones((P, S))
+        for s, name in enumerate(self.source_name_list):
+            key = name + '_rate_multiplier'
+            if key in points:
+                mult[:, s] = np.broadcast_to(np.asarray(points[key], dtype=float), (P,))
+        L = 1.0
+        if livetime_days is not None and self.pdf_base_config.get('livetime_days'):
+            L = livetime_days / self.pdf_base_config['livetime_days']
+        eff, eff_axis = np.ones((P, S)), [-1] * S
+        shape_names = list(self.shape_parameters)
+        defaults = self._batch_names[2]
+        for s in np.flatnonzero(self.source_apply_efficiency):
+            en = self.source_efficiency_names[s]
+            v = points[en] if en in points else defaults.get(en)
+            if v is not None:
+                eff[:, s] = np.broadcast_to(np.asarray(v, dtype=float), (P,))
+            if en in shape_names:
+                eff_axis[s] = shape_names.index(en)
+        rate_sources = [s for s, name in enumerate(self.source_name_list) if name in self.rate_parameters]
+        return mult, L, eff, eff_axis, rate_sources
+
     @_needs_data
     def value_gradient_hessian(self, livetime_days=None, **kwargs):
         """-> (ll, OrderedDict name -> d ll / d parameter, names, H [F, F]) at one point: `values_gradients_hessians` with
@@ -752,27 +777,8 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         bad = (st & (_capi.ST_OUT_OF_BOUNDS | _capi.ST_UNPHYSICAL)) != 0
         if np.any(st & _capi.ST_UNPHYSICAL) and self.config.get('unphysical_behaviour') == 'error':
             raise ValueError("Unphysical rates at %d of %d points" % (int(np.count_nonzero(st & _capi.ST_UNPHYSICAL)), P))
-        S = len(self.source_name_list)
-        mult = np.ones((P, S))
-        for s, name in enumerate(self.source_name_list):
-            key = name + '_rate_multiplier'
-            if key in points:
-                mult[:, s] = np.broadcast_to(np.asarray(points[key], dtype=float), (P,))
-        L = 1.0
-        if livetime_days is not None and self.pdf_base_config.get('livetime_days'):
-            L = livetime_days / self.pdf_base_config['livetime_days']
-        eff, eff_axis = np.ones((P, S)), [-1] * S
-        shape_names = list(self.shape_parameters)
-        defaults = self._batch_names[2]
-        for s in np.flatnonzero(self.source_apply_efficiency):
-            en = self.source_efficiency_names[s]
-            v = points[en] if en in points else defaults.get(en)
-            if v is not None:
-                eff[:, s] = np.broadcast_to(np.asarray(v, dtype=float), (P,))
-            if en in shape_names:
-                eff_axis[s] = shape_names.index(en)
-        rate_sources = [s for s, name in enumerate(self.source_name_list) if name in self.rate_parameters]
-        F = len(rate_sources) + len(shape_names)
+        mult, L, eff, eff_axis, rate_sources = self._chain_rule_terms(points, P, livetime_days)
+        F = len(rate_sources) + len(self.shape_parameters)
         prior_g, prior_h = np.zeros((P, F)), np.zeros((P, F))
         for j, s in enumerate(rate_sources):
             lp = self.rate_parameters[self.source_name_list[s]]

@@ -418,6 +418,31 @@ int bi_download_real_counts(bi_ctx* ctx, int64_t t, double* out);
 int bi_eval_real(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
                  double* half_deviance, double* grad, int32_t* status);
 
+/* The expected (Fisher) information of the binned Poisson likelihood at P truths, without data:
+ *   info [P][F][F], F = d + S     I_qr = sum_b d_q mu_b d_r mu_b / mu_b      over the bins with mu_b > 0
+ *   total [P] or NULL             sum_b mu_b
+ *   unbounded [P][F] or NULL      the number of bins with mu_b == 0 and d_q mu_b != 0
+ * q, r over z_0 .. z_{d-1}, then the rate scales (bi_eval_hess's order; rate_scale NULL: ones).  Minus the expectation of
+ * bi_eval_hess's Hessian over data drawn at the point itself; every diagonal entry is a sum of non-negative terms and the
+ * matrix is positive semi-definite by construction.  A bin that expects nothing and whose expectation does not move with any
+ * parameter (a bin no template fills) adds nothing.  A bin that expects nothing but would with another value of parameter q
+ * (a rate scale of 0 for the only source in the bin; a point on an anchor and a bin only the cell's other anchor fills)
+ * holds unbounded information on q -- one event there would decide it: such a bin is left out of the sums of `info` and
+ * counted in unbounded[p][q], and the caller decides what that means (blueice_amd.hessian.covariance_from_information: variance
+ * 0).  A negative or nan mu_b in any bin (sources that may go negative) makes the point's whole matrix and its total nan.
+ * Rows and columns of single-anchor axes are zero; on an anchor the matrix is that of the cell the point is assigned to
+ * (bi_eval_grad's convention).  Points outside the anchor box or with unphysical rates get their bi_eval_grad status bit in
+ * status [P] (nullable; 0 for a live point), a nan matrix, a nan total and zero counts.  The context needs a model and nothing
+ * else: no dataset, no real-valued store, and none of them is touched.  The dense template rows are streamed once per point,
+ * no floating-point atomics: a repeated call is bitwise identical and a point's result does not depend on the other points of
+ * the call.  Limits: 1 + d_eff + S <= 16 coefficient columns (d_eff: the axes with more than one anchor), BI_ERR_INVALID
+ * naming the figure otherwise; Beeston-Barlow and unbinned contexts: BI_ERR_INVALID, as bi_expected_counts.
+ * bi_fisher_variant: the kernel variant bi_eval_fisher takes for D = d_eff + S first-order columns -- *G (nullable) the padded
+ * 1 + D of {4, 8, 16}, *DM (nullable) the padded D of {4, 8, 16}; BI_ERR_INVALID when 1 + D > 16.  Needs no context. */
+int bi_eval_fisher(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, double* info, double* total,
+                   int64_t* unbounded, int32_t* status);
+int bi_fisher_variant(int D, int* G, int* DM);
+
 /* The batched profile-fit engine's inner loop (host code): P minimisations of F variables each advance in lock-step, every
  * optimiser iteration ONE evaluation call over the problems still running -- what replaces the reference's loops of sequential
  * scipy fits (bestfit_scipy, blueice/inference.py:131-178, inside one_parameter_interval / plot_likelihood_ratio, :332-443).
