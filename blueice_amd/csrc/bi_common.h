@@ -15,7 +15,9 @@
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
 //     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
-//     tu_prim.hip         the rocPRIM sorts and scans (instantiated once, behind plain functions)
+//     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
+// bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
+// chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h and bi_k_coarse.h.
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 

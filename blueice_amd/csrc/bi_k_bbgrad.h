@@ -1,6 +1,8 @@
 // bi_k_bbgrad.h -- value + analytic gradient with Beeston-Barlow (k_morph_bbgrad): translation unit tu_grad.hip.
 #pragma once
 
+#include "bi_k_item.h"
+
 namespace {
 
 // ---- value + analytic gradient with Beeston-Barlow (bi_eval_grad, bb_source >= 0) ----------------------------------
@@ -36,11 +38,9 @@ __global__ __launch_bounds__(kThreads) void k_morph_bbgrad(LaunchArgs a) {
     for (int g = 0; g < G; ++g) sum[g] = 0.0;
     const double p_cal = aux[0], Ntot = aux[1];
     const double r_i = p_cal * Ntot;
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
+    for (ItemTiles w(a, n_tiles); w.more(); w.step()) {
+        const int tile = w.tile();
+        if (tile < 0) continue;
         const int64_t bin0 = (int64_t)tile * kTile + threadIdx.x * kBinsPerThread;
         double acc[G][2], pi[DZ][2], ai[DZ][2];
 #pragma unroll
@@ -137,17 +137,13 @@ __global__ __launch_bounds__(kThreads) void k_morph_bbgrad(LaunchArgs a) {
         }
     }
 
+    // item_reduce_store (bi_k_item.h) with the status word: its store written out, the waves' flags ORed into slot 0's
     __shared__ double s_sum[kThreads / 64][G];
     __shared__ unsigned s_flg[kThreads / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const double s = wave_sum(sum[g]);
-        if (lane == 0) s_sum[wave][g] = s;
-    }
+    item_wave_sums(sum, s_sum, 0);
     {
         const unsigned f = wave_or(flg);
-        if (lane == 0) s_flg[wave] = f;
+        if ((threadIdx.x & 63) == 0) s_flg[threadIdx.x >> 6] = f;
     }
     __syncthreads();
     if (threadIdx.x < G) {

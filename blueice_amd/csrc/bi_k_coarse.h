@@ -11,7 +11,7 @@
 //   -- read with 8-byte loads (r L is not 16-byte aligned in general).  The 256 threads are TY = 256 / TX sub-rows of
 //   TX = 64, 128 or 256 lanes (the smallest that covers the Lx live columns, or 256 with several x-tiles): sub-row ty walks
 //   the fine rows lo + ty, lo + ty + TY, ... of the block's share in list order, forms
-//       mu_b = sum_k a_k row_k[r L + x]       (k_morph_expect's fma chain, k ascending from 0.0: the same bits)
+//       mu_b = sum_k a_k row_k[r L + x]       (item_chain, bi_k_item.h: k_morph_expect's bits)
 //   and adds it to its lane's sum; the TY sums of a column are then added in ty order through LDS, and the block writes
 //   partial[item][r][coarse row][share][x].  A share without rows writes zeros.
 // k_coarse_finish: one thread per output cell: the shares in order, inside a share the columns of the cell's group in order.
@@ -34,6 +34,8 @@
 //     k_coarse_list     21 VGPRs, 43 SGPRs, no LDS
 //     k_coarse_table     6 VGPRs, 12 SGPRs, no LDS
 #pragma once
+
+#include "bi_k_item.h"
 
 namespace {
 
@@ -59,11 +61,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_coarse(CoarseArgs a) {
     double acc = 0.0;
     if (live)
         for (int64_t i = i0 + ty; i < i1; i += TY) {
-            const double* __restrict__ p = a.ps + ((int64_t)a.row_list[lo + i] * a.L + a.x_lo + xr);
-            double mu = 0.0;
-#pragma unroll 8
-            for (int k = k0; k < a.NS; k += step) mu = fma(coef[k], p[rowoff[k]], mu);
-            acc += mu;
+            acc += item_chain<8>(coef, rowoff, a.ps, (int64_t)a.row_list[lo + i] * a.L + a.x_lo + xr, k0, a.NS, step);
         }
 
     double* __restrict__ out = a.partial + ((((item * a.R + r) * a.CR + crow) * a.nsplit + split) * a.Lx + xr);

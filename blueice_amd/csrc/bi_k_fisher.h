@@ -11,11 +11,12 @@
 // 0 * inf is formed; with a non-zero slope it is left out of the Gram sums and counted.  The counts are whole numbers in a
 // double, exact far beyond any number of bins, and reduced like every other slot.  A negative or nan mu_b makes sum[0] nan:
 // the host half reports the point's whole matrix as nan then.  The result slots of an item are k_morph_hess's,
-// [G columns][DM (DM + 1) / 2 Gram pairs], its block reduction and the order of its partials too; k_finish reduces them.
-// One bin in flight per thread, the tile's 512 bins in two passes of 256, dense rows only.
+// [G columns][DM (DM + 1) / 2 Gram pairs].  Tile walk, column sums and block reduction: bi_k_item.h; dense rows only.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): profiles/fisher_kernel_resources.txt; no scratch in any
 // variant.
 #pragma once
+
+#include "bi_k_item.h"
 
 namespace {
 
@@ -25,7 +26,6 @@ constexpr int fisher_pairs() { return DM * (DM + 1) / 2; }
 template <int G, int DM, bool NT>
 __global__ __launch_bounds__(kThreads) void k_morph_fisher(HessArgs a) {
     constexpr int NP = fisher_pairs<DM>();
-    constexpr int NSL = G + NP;
     static_assert(DM <= G, "the first-order columns are a part of the G columns");
     const int item = blockIdx.y;
     const int64_t* __restrict__ rowoff = a.rowoff + (int64_t)item * a.NS;
@@ -39,25 +39,14 @@ __global__ __launch_bounds__(kThreads) void k_morph_fisher(HessArgs a) {
 #pragma unroll
     for (int q = 0; q < NP; ++q) gram[q] = 0.0;
 
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
-        // the tile's 512 bins in two passes of 256 consecutive bins, every row element read once
+    for (ItemTiles w(a, n_tiles); w.more(); w.step()) {
+        const int tile = w.tile();
+        if (tile < 0) continue;
 #pragma unroll 1
         for (int half = 0; half < kBinsPerThread; ++half) {
             const int64_t bin = (int64_t)tile * kTile + half * kThreads + threadIdx.x;
             double acc[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[g] = 0.0;
-#pragma unroll 4
-            for (int k = 0; k < a.NS; ++k) {
-                const double* p = a.ps + rowoff[k] + bin;
-                const double v = NT ? __builtin_nontemporal_load(p) : *p;
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[g] = fma(coef[k * G + g], v, acc[g]);
-            }
+            item_columns<G, NT>(a, rowoff, coef, bin, acc);
             const double mu = acc[0];
             sum[0] += mu >= 0.0 ? mu : __builtin_nan("");
             const bool empty = mu == 0.0;
@@ -76,28 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_fisher(HessArgs a) {
         }
     }
 
-    // block reduction: wave sums, then the four waves in order
-    __shared__ double s_sum[kThreads / 64][NSL];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const double s = wave_sum(sum[g]);
-        if (lane == 0) s_sum[wave][g] = s;
-    }
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const double s = wave_sum(gram[q]);
-        if (lane == 0) s_sum[wave][G + q] = s;
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < NSL; j += kThreads) {
-        double s = s_sum[0][j];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) s += s_sum[w][j];
-        const int64_t o = ((int64_t)item * gridDim.x + blockIdx.x) * NSL + j;
-        a.partial[o] = s;
-        a.pflags[o] = 0u;
-    }
+    item_reduce_store(sum, gram, item, a.partial, a.pflags);
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // bi_k_gof.h -- goodness of fit on the device.  Translation unit tu_gof.hip.
 //
 // k_morph_gof<NT>: the half-deviance and Pearson's chi2 of ONE (point, dataset) per work item in one pass over the corner
-// rows of the point's cell -- the structure of k_morph_hess (bi_k_hess.h) with one coefficient column, a_k = w_corner r_source,
-// and two sums.  Per bin, mu = sum_k a_k row_k[b]:
+// rows of the point's cell: tile walk and block reduction of bi_k_item.h around a row loop of its own, one coefficient
+// column, a_k = w_corner r_source, and two sums.  Per bin, mu = sum_k a_k row_k[b]:
 //     slot 0 (half-deviance)   n > 0: (mu - n) - n log(mu / n)      n = 0: mu
 //     slot 1 (Pearson)         n > 0: (n - mu)^2 / mu               n = 0: mu
 // Both forms are free of cancellation between large numbers: the deviance is NOT formed as a difference of two
@@ -14,9 +14,12 @@
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 62 VGPRs and 86 SGPRs in both instantiations, no scratch,
 // 4160 bytes of LDS (the logarithm's table and the block reduction), 8 waves per SIMD.
 //
-// k_morph_expect: the expectation itself, out[item][r][b] = sum over the rows of group r of a_k row_k[b] from the dense
-// template tensor: one group (every row: mu_b) or one group per source (mu_{s,b}).  14 VGPRs, no scratch, no LDS.
+// k_morph_expect: the expectation itself, out[item][r][b] = sum over the rows of group r of a_k row_k[b] (item_chain,
+// bi_k_item.h) from the dense template tensor: one group (every row: mu_b) or one group per source (mu_{s,b}).  14 VGPRs, no
+// scratch, no LDS.
 #pragma once
+
+#include "bi_k_item.h"
 
 namespace {
 
@@ -42,12 +45,10 @@ __global__ __launch_bounds__(kThreads) void k_morph_gof(HessArgs a) {
     const int n_tiles = a.item_tiles[item];
     log_table_load();
 
-    double dev = 0.0, chi = 0.0;
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
+    double sum[2] = {0.0, 0.0};      // half-deviance, Pearson
+    for (ItemTiles w(a, n_tiles); w.more(); w.step()) {
+        const int tile = w.tile();
+        if (tile < 0) continue;
         const int64_t bin0 = (int64_t)tile * kTile + threadIdx.x * kBinsPerThread;
         const double2 n = stream_load<NT>(cnt + bin0);
         double mu0 = 0.0, mu1 = 0.0;
@@ -58,25 +59,11 @@ __global__ __launch_bounds__(kThreads) void k_morph_gof(HessArgs a) {
             mu0 = fma(c, v.x, mu0);
             mu1 = fma(c, v.y, mu1);
         }
-        gof_terms(n.x, mu0, dev, chi);
-        gof_terms(n.y, mu1, dev, chi);
+        gof_terms(n.x, mu0, sum[0], sum[1]);
+        gof_terms(n.y, mu1, sum[0], sum[1]);
     }
 
-    // block reduction: wave sums, then the four waves in order
-    __shared__ double s_sum[kThreads / 64][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    dev = wave_sum(dev);
-    chi = wave_sum(chi);
-    if (lane == 0) { s_sum[wave][0] = dev; s_sum[wave][1] = chi; }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        double s = s_sum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) s += s_sum[w][threadIdx.x];
-        const int64_t o = ((int64_t)item * gridDim.x + blockIdx.x) * 2 + threadIdx.x;
-        a.partial[o] = s;
-        a.pflags[o] = 0u;
-    }
+    item_reduce_store(sum, item, a.partial, a.pflags);
 }
 
 __global__ __launch_bounds__(kThreads) void k_morph_expect(ExpectArgs a) {
@@ -86,11 +73,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_expect(ExpectArgs a) {
     const int64_t item = blockIdx.z;
     const int64_t* __restrict__ rowoff = a.rowoff + item * a.NS;
     const double* __restrict__ coef = a.coef + item * a.NS;
-    const int step = a.R > 1 ? a.S : 1;
-    double mu = 0.0;
-#pragma unroll 4
-    for (int k = a.R > 1 ? r : 0; k < a.NS; k += step) mu = fma(coef[k], a.ps[rowoff[k] + bin], mu);
-    a.out[(item * a.R + r) * a.B + bin] = mu;
+    a.out[(item * a.R + r) * a.B + bin] = item_chain<4>(coef, rowoff, a.ps, bin, a.R > 1 ? r : 0, a.NS, a.R > 1 ? a.S : 1);
 }
 
 }  // namespace

@@ -9,8 +9,11 @@
 //     sum[0]   += the log-likelihood term
 //     sum[g]   += f * acc[g]                                    every derivative column (first and second order)
 //     gram[qr] -= wn * (inv * acc[1 + q]) * (inv * acc[1 + r])   q >= r, both < D
-// The result slots of an item are [G columns][DM (DM + 1) / 2 Gram pairs]; k_finish reduces the blocks' partials.
+// The result slots of an item are [G columns][DM (DM + 1) / 2 Gram pairs].  Tile walk, column sums and block reduction:
+// bi_k_item.h; what is written here is the per-bin mathematics.
 #pragma once
+
+#include "bi_k_item.h"
 
 namespace {
 
@@ -20,7 +23,6 @@ constexpr int hess_pairs() { return DM * (DM + 1) / 2; }
 template <int G, int DM, bool UNB, bool NT>
 __global__ __launch_bounds__(kThreads) void k_morph_hess(HessArgs a) {
     constexpr int NP = hess_pairs<DM>();
-    constexpr int NSL = G + NP;
     static_assert(DM <= G, "the first-order columns are a part of the G columns");
     const int item = blockIdx.y;
     const int64_t* __restrict__ rowoff = a.rowoff + (int64_t)item * a.NS;
@@ -36,28 +38,17 @@ __global__ __launch_bounds__(kThreads) void k_morph_hess(HessArgs a) {
 #pragma unroll
     for (int q = 0; q < NP; ++q) gram[q] = 0.0;
 
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
-        // one bin in flight per thread (the G columns and the Gram sums already hold ~2 G + DM^2 / 2 doubles): the
-        // tile's 512 bins in two passes of 256 consecutive bins, every row element read once
+    for (ItemTiles w(a, n_tiles); w.more(); w.step()) {
+        const int tile = w.tile();
+        if (tile < 0) continue;
+        // one bin in flight per thread (the G columns and the Gram sums already hold ~2 G + DM^2 / 2 doubles)
 #pragma unroll 1
         for (int half = 0; half < kBinsPerThread; ++half) {
             const int64_t bin = (int64_t)tile * kTile + half * kThreads + threadIdx.x;
             double n = 0.0;
             if constexpr (!UNB) n = NT ? __builtin_nontemporal_load(cnt + bin) : cnt[bin];
             double acc[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[g] = 0.0;
-#pragma unroll 4
-            for (int k = 0; k < a.NS; ++k) {
-                const double* p = a.ps + rowoff[k] + bin;
-                const double v = NT ? __builtin_nontemporal_load(p) : *p;
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[g] = fma(coef[k * G + g], v, acc[g]);
-            }
+            item_columns<G, NT>(a, rowoff, coef, bin, acc);
             // f: the weight of every derivative column; inv, wn: the Gram term is -wn (inv d_q mu)(inv d_r mu), with the first
             // derivatives scaled by inv before the product (1 / lambda^2 alone overflows for densities below 1e-154)
             double f, inv, wn;
@@ -92,28 +83,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_hess(HessArgs a) {
         }
     }
 
-    // block reduction: wave sums, then the four waves in order
-    __shared__ double s_sum[kThreads / 64][NSL];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const double s = wave_sum(sum[g]);
-        if (lane == 0) s_sum[wave][g] = s;
-    }
-#pragma unroll
-    for (int q = 0; q < NP; ++q) {
-        const double s = wave_sum(gram[q]);
-        if (lane == 0) s_sum[wave][G + q] = s;
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < NSL; j += kThreads) {
-        double s = s_sum[0][j];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) s += s_sum[w][j];
-        const int64_t o = ((int64_t)item * gridDim.x + blockIdx.x) * NSL + j;
-        a.partial[o] = s;
-        a.pflags[o] = 0u;
-    }
+    item_reduce_store(sum, gram, item, a.partial, a.pflags);
 }
 
 }  // namespace

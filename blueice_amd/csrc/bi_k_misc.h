@@ -43,7 +43,7 @@ __global__ __launch_bounds__(kThreads) void k_read_rows(const double* __restrict
                                                         int64_t first, int rows, int n_tiles, int chunks_in,
                                                         double* __restrict__ sink) {
     const int64_t row0 = first + (int64_t)blockIdx.y * rows;
-    const int chunks = (chunks_in > 1 && n_tiles >= 64 * chunks_in) ? chunks_in : 1;
+    const int chunks = (chunks_in > 1 && n_tiles >= 64 * chunks_in) ? chunks_in : 1;      // (ItemTiles, bi_k_item.h, written out)
     const int per_chunk = (n_tiles + chunks - 1) / chunks;
     double s = 0.0;
     for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {

@@ -24,9 +24,7 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
     double4 tab = {0.0, 0.0, 0.0, 0.0};
     if (threadIdx.x < 128) tab = kLogTable[threadIdx.x];
     bool tab_pending = true;
-    // XCD-aware tile order: with 8 chunks block b -- dispatched to XCD b % 8 -- streams the b % 8-th contiguous region of
-    // every row instead of every 8th tile (measured +6 % on the 113-stream BB pass, +1 % on C2); short rows keep the
-    // plain order, where the padded chunk count would cost some blocks a second tile
+    // XCD-aware tile order: ItemTiles (bi_k_item.h: the rule and its measurements) written out, the headline path's own instruction stream
     const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
     const int per_chunk = (n_tiles + chunks - 1) / chunks;
     for (int lt = tile0; lt < per_chunk * chunks; lt += tile_step) {     // (the trip count is the same for a whole block)

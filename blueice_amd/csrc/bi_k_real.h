@@ -7,10 +7,10 @@
 //     slot q      n > 0: d_q mu (1 - n / mu)             n = 0: d_q mu
 // n is any real number >= 0 (bi_set_real_counts / bi_set_asimov_counts admit nothing else): there is no integer test.
 // n > 0 and mu = 0 gives +inf in slot 0, mu negative or nan gives nan; the derivative slots of such an item are whatever
-// the arithmetic makes of them, and the host half (bi_real.h) reports nan for them.  mu_b is formed by the fma chain of
-// k_morph_expect, k = 0 .. NS - 1 from 0.0 with a_k = w_corner r_source: at the truth of an Asimov dataset mu_b == n_b
+// the arithmetic makes of them, and the host half (bi_real.h) reports nan for them.  mu_b is column 0 of item_columns, the
+// fma chain of item_chain (bi_k_item.h) with a_k = w_corner r_source: at the truth of an Asimov dataset mu_b == n_b
 // bit for bit, mu / n == 1.0, bin_log(1.0) == 0.0 and 1 - n / mu == 0.0, so slot 0 and every derivative slot are 0.0
-// exactly.  One bin in flight per thread (the structure of k_morph_hess: 2 G doubles of sums and columns), dense rows only.
+// exactly.  Tile walk, column sums and block reduction: bi_k_item.h (2 G doubles of sums and columns); dense rows only.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), both NT instantiations alike:
 //     G = 1 (value only)   38 VGPRs,  78 SGPRs, 4128 bytes of LDS
 //     G = 4                50 VGPRs, 105 SGPRs, 4224 bytes
@@ -18,10 +18,12 @@
 //     G = 16               99 VGPRs, 106 SGPRs, 4608 bytes
 // no scratch in any of them (LDS: the logarithm's table and the block reduction's 4 x G sums).
 //
-// k_real_expect: the Asimov datasets themselves, out[item][Bp] = mu_b of truth `item`: k_morph_expect's arithmetic (the same
-// host-built coefficients, the same fma chain over k) written with the store's row stride, and bad[item] = 1 + a bin whose
-// expectation is negative or nan (any one of them; 0: none).
+// k_real_expect: the Asimov datasets themselves, out[item][Bp] = mu_b of truth `item`: k_morph_expect's host-built
+// coefficients through the same item_chain, written with the store's row stride, and bad[item] = 1 + a bin whose expectation
+// is negative or nan (any one of them; 0: none).
 #pragma once
+
+#include "bi_k_item.h"
 
 namespace {
 
@@ -38,26 +40,15 @@ __global__ __launch_bounds__(kThreads) void k_morph_real(HessArgs a) {
 #pragma unroll
     for (int g = 0; g < G; ++g) sum[g] = 0.0;
 
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
-        // the tile's 512 bins in two passes of 256 consecutive bins, every row element read once
+    for (ItemTiles w(a, n_tiles); w.more(); w.step()) {
+        const int tile = w.tile();
+        if (tile < 0) continue;
 #pragma unroll 1
         for (int half = 0; half < kBinsPerThread; ++half) {
             const int64_t bin = (int64_t)tile * kTile + half * kThreads + threadIdx.x;
             const double n = NT ? __builtin_nontemporal_load(cnt + bin) : cnt[bin];
             double acc[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc[g] = 0.0;
-#pragma unroll 4
-            for (int k = 0; k < a.NS; ++k) {
-                const double* p = a.ps + rowoff[k] + bin;
-                const double v = NT ? __builtin_nontemporal_load(p) : *p;
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc[g] = fma(coef[k * G + g], v, acc[g]);
-            }
+            item_columns<G, NT>(a, rowoff, coef, bin, acc);
             const double mu = acc[0];
             double dev = mu, f = 1.0;
             if (n > 0.0) {
@@ -71,23 +62,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_real(HessArgs a) {
         }
     }
 
-    // block reduction: wave sums, then the four waves in order
-    __shared__ double s_sum[kThreads / 64][G];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const double s = wave_sum(sum[g]);
-        if (lane == 0) s_sum[wave][g] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < G) {
-        double s = s_sum[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) s += s_sum[w][threadIdx.x];
-        const int64_t o = ((int64_t)item * gridDim.x + blockIdx.x) * G + threadIdx.x;
-        a.partial[o] = s;
-        a.pflags[o] = 0u;
-    }
+    item_reduce_store(sum, item, a.partial, a.pflags);
 }
 
 __global__ __launch_bounds__(kThreads) void k_real_expect(RealExpectArgs a) {
@@ -96,9 +71,7 @@ __global__ __launch_bounds__(kThreads) void k_real_expect(RealExpectArgs a) {
     const int64_t item = blockIdx.y;
     const int64_t* __restrict__ rowoff = a.rowoff + item * a.NS;
     const double* __restrict__ coef = a.coef + item * a.NS;
-    double mu = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < a.NS; ++k) mu = fma(coef[k], a.ps[rowoff[k] + bin], mu);
+    const double mu = item_chain<4>(coef, rowoff, a.ps, bin, 0, a.NS, 1);
     a.out[item * a.Bp + bin] = mu;
     if (!(mu >= 0.0)) a.bad[item] = bin + 1;       // (any of the offending bins: the lanes' stores of one word race harmlessly)
 }

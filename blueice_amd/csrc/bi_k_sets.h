@@ -2,6 +2,8 @@
 // (translation unit tu_morph.hip, behind bi_k_morph.h).
 #pragma once
 
+#include "bi_k_item.h"
+
 namespace {
 
 // An unbinned context can hold T event sets side by side on the event axis (include/blueice_hip.h, bi_score_event_sets):
@@ -13,7 +15,7 @@ namespace {
 // -- MODE 2 (G = 1: the value) or MODE 3 (value + G - 1 gradient columns), so the nan-skipping sum over sources, the
 // outlier clamp and the checked / fast logarithm are the single-set kernels' own, instruction for instruction; the row
 // loop keeps eight 16-byte loads in flight per lane, which is what a toy of 10^3 .. 10^4 events (latency, not bandwidth)
-// needs.  Partials go to partial[item][block][g] for k_finish, as k_morph_reduce writes them.
+// needs.  Partials go to partial[item][block][g] for k_finish, as k_morph_reduce writes them (item_reduce_store, bi_k_item.h).
 template <int G, int MODE>
 __global__ __launch_bounds__(kThreads) void k_morph_sets(LaunchArgs a) {
     const int item = blockIdx.y;
@@ -36,22 +38,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_sets(LaunchArgs a) {
     morph_tiles<G, false, false, MODE>(b, a.rowoff + (int64_t)item * NS, a.coef + (int64_t)item * NS * G, nullptr, a.ps, nullptr, n_tiles,
                                        (int)blockIdx.x, (int)gridDim.x, sum, flg);
 
-    __shared__ double s_sum[kThreads / 64][G];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const double s = wave_sum(sum[g]);
-        if (lane == 0) s_sum[wave][g] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < G) {
-        const int g = threadIdx.x;
-        double s = s_sum[0][g];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) s += s_sum[w][g];
-        a.partial[o + g] = s;
-        a.pflags[o + g] = 0u;
-    }
+    item_reduce_store(sum, item, a.partial, a.pflags);
 }
 
 }  // namespace

@@ -48,7 +48,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_logmu_multi(LaunchArgs a, co
     for (int g = 0; g < GC; ++g) { sum[g] = 0.0; bad[g] = 0u; }
     log_table_load();
     const int n_tiles = a.n_tiles;
-    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;
+    const int chunks = (a.chunks > 1 && n_tiles >= 64 * a.chunks) ? a.chunks : 1;      // (ItemTiles, bi_k_item.h, written out)
     const int per_chunk = (n_tiles + chunks - 1) / chunks;
     if (ncol == 1) {
         // (block-uniform) a point alone in its cell: one column -- the other GC - 1 accumulators would be most of the

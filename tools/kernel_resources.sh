@@ -3,9 +3,9 @@
 # metadata (no GPU needed):   tools/kernel_resources.sh [name filter]
 set -e
 cd "$(dirname "$0")/.."
-# (the library is six translation units, blueice_amd/csrc/bi_common.h: each is compiled device-only, side by side, and the
-#  notes of all code objects are read together; UNITS="tu_scan_sorted" limits the run to one of them)
-UNITS=${UNITS:-"blueice_hip tu_morph tu_scan tu_scan_sorted tu_grad tu_prim tu_hess"}
+# (the library's translation units are blueice_amd.build.UNITS, blueice_amd/csrc/bi_common.h: each is compiled device-only,
+#  side by side, and the notes of all code objects are read together; UNITS="tu_scan_sorted" limits the run to one of them)
+UNITS=${UNITS:-$(python3 -c "import runpy; print(' '.join(runpy.run_path('blueice_amd/build.py')['UNITS']))")}
 OUT=${TMPDIR:-/tmp}/blueice_hip_gfx950
 for u in $UNITS; do
     ( /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -c -ffp-contract=off -mllvm --amdgpu-mfma-vgpr-form \
