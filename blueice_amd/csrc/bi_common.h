@@ -15,6 +15,7 @@
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
 //     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
+//     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
 // chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h and bi_k_coarse.h.
@@ -22,8 +23,6 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <sched.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -43,6 +42,7 @@
 
 #define BI_VERSION "blueice_hip 0.1 (gfx950)"
 
+#include "bi_wait.h"
 #include "bi_context.h"
 #include "bi_log_table.h"
 #include "bi_dev_common.h"
@@ -125,3 +125,28 @@ void launch_grid_finish(bi_ctx* c, const GridArgs& a);
 void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items);
 // k_coarse_list + k_coarse_table: the non-empty-bin lists of n (<= 65 535) datasets into the cells, out [n][C] (device memory)
 void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out);
+// ---- the toy-MC evaluation kernels (bi_k_toys.h).  No launcher times its kernel: the host half (bi_toys.h) opens the EventScopes.
+// k_csr_tile_offsets, k_tm_counts (16 / a.width entries per group), k_tm_scatter<a.width bytes per entry>
+void launch_csr_tile_offsets(bi_ctx* c, const TileListArgs& a);
+void launch_tm_counts(bi_ctx* c, const TileListArgs& a);
+void launch_tm_scatter(bi_ctx* c, const TileListArgs& a);
+// k_morph_logmu on nmu blocks (store_mu = 1: the expectation itself, for the toy generator), or with pd != NULL k_morph_logmu_desc
+void launch_morph_logmu(bi_ctx* c, int nmu, const LaunchArgs& a, const PointDesc* pd, double* logmu, int store_mu);
+// the row kernels: k_dataset_dot (dense counts, grid = blocks per group x groups of kDotGroup datasets), k_dataset_dot_csr (n blocks)
+void launch_dataset_dot(bi_ctx* c, dim3 grid, const double* counts, const double* logmu, int64_t Bp, int n_tiles, int64_t t0, int64_t n, double* partial);
+void launch_dataset_dot_csr(bi_ctx* c, int64_t n, const int32_t* nz_idx, const double* nz_n, const int64_t* nz_off, const double* logmu, int64_t t0, double* partial);
+// k_dataset_dot_tiled<L, AHEAD, W>: the variant follows the context's tm_width and dot_lanes; grid (a.n_tl, by).  ..._resident: blocks
+// of that variant one CU holds at a time (dot_blocks_per_cu if set, else asked from the runtime once)
+int dataset_dot_tiled_resident(bi_ctx* c);
+void launch_dataset_dot_tiled(bi_ctx* c, unsigned by, const ToyDotArgs& a);
+// k_dataset_finish (blocks of 256 datasets) / k_dataset_finish_tiled (blocks of 64 datasets, publishes a.done when set)
+void launch_dataset_finish(bi_ctx* c, const ToyFinishArgs& a);
+void launch_dataset_finish_tiled(bi_ctx* c, const ToyFinishArgs& a);
+// the multi-point form, on stream s (the context's or its second one): k_morph_logmu_multi<GC, NT> (GC = 4 or 8 rows per group),
+// k_dataset_dot_multi<L, AHEAD, W, PP, kDotTileMulti> (variant by tmm_width, PP and toy_points_lanes; grid (a.n_tl, by, np passes);
+// the error of the LDS attribute, if any) and k_dataset_finish_multi<PP> (blocks of kPartBlock datasets x np passes)
+void launch_morph_logmu_multi(bi_ctx* c, hipStream_t s, int GC, bool nt, dim3 grid, const LaunchArgs& a, const int32_t* meta, double* lm);
+hipError_t launch_dataset_dot_multi(bi_ctx* c, hipStream_t s, int PP, unsigned by, int np, const ToyDotArgs& a, const MuTotals& mt);
+void launch_dataset_finish_multi(bi_ctx* c, hipStream_t s, int PP, int np, const ToyFinishArgs& a);
+// k_fill_rows: out[rows[r]][0 .. n) = v
+void launch_fill_rows(bi_ctx* c, double* out, int64_t out_stride, const int32_t* rows, int n_rows, int64_t n, double v);

@@ -192,6 +192,72 @@ struct RealExpectArgs {
     int NS;
 };
 
+// ---- toy-MC evaluation (bi_k_toys.h; the host half is bi_toys.h, which sizes its lists and buffers by the same constants) ----
+constexpr int kDotTile = 8192;               // bins per tile of the single-point lists: 64 KB of LDS
+constexpr int kDotTileMulti = 4096;          // bins per tile of the multi-point lists: 4096 x 4 points x 8 B = 128 KB of LDS
+constexpr int kDotPad = 64 * 2 + 16;         // entries behind the lists that the read-ahead may touch (read, masked, never used): the largest of the variants
+constexpr int kDotGroup = 8;                 // datasets per block of the dense row kernel k_dataset_dot
+constexpr int kPartBlock = 32;               // datasets per block of the multi-point per-(tile, dataset) partial sums
+
+// k_morph_logmu_desc: the descriptors of one point in the kernel arguments
+struct PointDesc {
+    int64_t rowoff[kMaxSingleStreams];
+    double coef[kMaxSingleStreams];
+};
+
+// k_dataset_dot_multi: sum mu of the points of a group of passes, added up by the first block of every pass
+struct MuTotals {
+    const int32_t* colmap;        // [passes of the group][PP][2] = {work item of the log mu kernel, output row} (-1: no point)
+    const double* partial;        // [items][nmu][GC]
+    const unsigned* flags;
+    int nmu, GC;
+    double* tot;
+    unsigned* flag;
+};
+
+// k_csr_tile_offsets, k_tm_counts, k_tm_scatter: the tile-major copy of the non-empty-bin lists
+struct TileListArgs {
+    const int32_t* nz_idx;        // the dataset-major lists
+    const double* nz_n;
+    const int64_t* nz_off;        // [T + 1]
+    int32_t* tile_off;            // [T][n_tl + 1] first entry of every tile within a dataset's list
+    int64_t* cnt;                 // [n_tl T + 1] padded length of every (tile, dataset) run
+    const int64_t* tm_off;        // [n_tl T + 1] their exclusive sum
+    void* entries;                // the tile-major entries, `width` bytes each, pre-filled with padding entries
+    int* bad;                     // set to 1 where a count does not fit the entry format
+    int64_t T;
+    int n_tl, tile_shift, width;
+};
+
+// k_dataset_dot_tiled / k_dataset_dot_multi
+struct ToyDotArgs {
+    const void* entries;          // tile-major lists and their offsets [n_tl][T]
+    const int64_t* off;
+    int64_t T;
+    int n_tl;
+    const double* lm;             // log mu [Bp], or [passes][PP][Bp]
+    int64_t B, Bp, t0, n;
+    double* partial;
+};
+
+// k_dataset_finish / k_dataset_finish_tiled / k_dataset_finish_multi
+struct ToyFinishArgs {
+    const double* partial;
+    int nbx;                      // partial sums per dataset (tiles)
+    int64_t t_stride, b_stride;   // k_dataset_finish: partial[t * t_stride + b * b_stride]
+    const double* mu;             // the log mu pass's block partials [nmu]; multi: MuTotals::tot [passes][PP]
+    const unsigned* mu_flags;
+    int nmu;
+    const int32_t* colmap;        // multi: [passes][PP][2]
+    const double* lgsum;
+    int64_t t0, n;
+    double* out;
+    int64_t out_stride;           // multi: out[row * out_stride + dataset]
+    unsigned* blocks_done;        // the tiled and multi forms: see publish_when_last
+    unsigned long long* done;
+    unsigned long long seq;
+};
+
 // The free-variable map of the native loops (fit, sampler, grid): which variable is which model parameter, the other settings
 // of every entry (problem, ensemble, dataset entry) and the staging rows, in the layouts bi_eval_grad and the resident planner
 // read.  The device loops hold device pointers, the fit's objective host pointers.  Its host side is bi_varmap.h.

@@ -474,306 +474,6 @@ __global__ void k_pad_copy(const double* __restrict__ src, int64_t n, int64_t np
     if (j < np) dst[j] = j < n ? src[j] : 0.0;
 }
 
-// toy-MC, CSR form: for dataset t: sum_j xlogy(n_j, mu[idx_j]); one block per dataset
-__global__ __launch_bounds__(kThreads) void k_dataset_dot_csr(const int32_t* __restrict__ nz_idx,
-                                                              const double* __restrict__ nz_n,
-                                                              const int64_t* __restrict__ nz_off,
-                                                              const double* __restrict__ logmu, int64_t t0,
-                                                              double* __restrict__ partial) {
-    const int64_t t = t0 + blockIdx.x;
-    const int64_t lo = nz_off[t], hi = nz_off[t + 1];
-    double s = 0.0;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += kThreads) {
-        const double n = nz_n[j];
-        double term = n * logmu[nz_idx[j]];
-        if (n != n) term = __builtin_nan("");
-        else if (n < 0.0 || n != floor(n)) term = -__builtin_inf();
-        s += term;
-    }
-    __shared__ double sh[kThreads / 64];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double r = sh[0];
-        for (int w = 1; w < kThreads / 64; ++w) r += sh[w];
-        partial[blockIdx.x] = r;
-    }
-}
-
-// ---- toy-MC, CSR form, bin tiles staged through LDS --------------------------------------------------------------
-// The row kernel above gathers log mu[idx] from an 8 MB table with one 8-byte element per cache line: at C2 (10^4
-// datasets x ~9 400 non-empty bins) that gather, not HBM, sets its 0.54 ms.  Here a block owns a TILE of kDotTile bins:
-// it stages that part of log mu in LDS once and walks the entries of many datasets that fall into the tile -- a
-// dataset's non-empty-bin list is sorted by bin, so they are one contiguous run, found through a per-dataset table
-// of tile offsets (k_csr_tile_offsets, built once per data upload).  One wave per (dataset, tile); its sum goes to
-// partial[dataset][tile], which k_dataset_finish adds up in tile order: fixed order, reproducible.
-constexpr int kDotTile = 8192;      // bins per tile: 64 KB of LDS
-
-__global__ __launch_bounds__(kThreads) void k_csr_tile_offsets(const int32_t* __restrict__ nz_idx, const int64_t* __restrict__ nz_off,
-                                                               int n_tl, int32_t* __restrict__ tile_off /*[T][n_tl + 1]*/,
-                                                               int tile_shift /* log2 of the bins per tile */) {
-    const int64_t t = blockIdx.x;
-    const int64_t lo = nz_off[t], hi = nz_off[t + 1];
-    int32_t* __restrict__ dst = tile_off + t * (n_tl + 1);
-    if (hi == lo) {
-        for (int tl = threadIdx.x; tl <= n_tl; tl += kThreads) dst[tl] = 0;
-        return;
-    }
-    for (int64_t j = lo + threadIdx.x; j < hi; j += kThreads) {
-        const int cur = nz_idx[j] >> tile_shift;
-        const int prev = j > lo ? nz_idx[j - 1] >> tile_shift : -1;
-        for (int tl = prev + 1; tl <= cur; ++tl) dst[tl] = (int32_t)(j - lo);     // first entry at or beyond the start of tile tl
-        if (j == hi - 1)
-            for (int tl = cur + 1; tl <= n_tl; ++tl) dst[tl] = (int32_t)(hi - lo);
-    }
-}
-
-// sum of a double over the 16 lanes of a DPP row (lanes 16r .. 16r+15): four rotate-and-add steps on the cross-lane
-// data path; every lane of the row ends up with the total
-__device__ __forceinline__ double row16_sum(double v) {
-#define BI_ROR_ADD(N)                                                                                              \
-    do {                                                                                                           \
-        const unsigned long long u = __double_as_longlong(v);                                                      \
-        const unsigned lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, 0x120 + N, 0xF, 0xF, true);           \
-        const unsigned hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), 0x120 + N, 0xF, 0xF, true);   \
-        v += __longlong_as_double(((unsigned long long)hi << 32) | lo);                                            \
-    } while (0)
-    BI_ROR_ADD(8);
-    BI_ROR_ADD(4);
-    BI_ROR_ADD(2);
-    BI_ROR_ADD(1);
-#undef BI_ROR_ADD
-    return v;
-}
-
-// Tile-major copy of the non-empty-bin lists: all entries of bin tile 0 (dataset 0, 1, ...), then tile 1, ... -- the
-// block that owns a tile reads ONE contiguous stream instead of a sub-kilobyte run per dataset scattered over the
-// dataset-major lists (which held the first tiled version at 2.6 TB/s).  An entry is 4 bytes: the byte offset of the bin
-// within the staged tile (bits 3..16: bin * 8) and the count (15 bits, from bit 17), so that the kernel gets the LDS
-// address with one AND and the count with one shift; data whose counts do not fit (or are not positive integers) keep
-// the row kernel.  Every (dataset, tile) run is padded to a multiple of FOUR entries with kTmPadEntry -- count 0, and the
-// offset of an extra LDS slot behind the tile that holds 0.0, never log mu = -inf -- so that a lane's 16-byte load is
-// wholly inside its run or wholly outside it (one test per load, not per entry) and every load is 16-byte aligned.
-// Round 4, measured: with the entry loads taken out the kernel runs in 24 us instead of 86 -- the ENTRY STREAM is its time
-// (376 MB at C2: 54 us of HBM at best), neither the LDS gathers nor the arithmetic.  So where every count is at most 7 -- toys
-// of sparse expectations: all of them -- an entry is TWO bytes: bin * 8 (the LDS byte offset, bits 3..15) | count (bits
-// 0..2), eight entries per 16-byte load, runs padded to multiples of eight with 0 (count 0: the term is dropped by a select,
-// there is no room for the offset of the extra slot).  Data with a larger count anywhere keeps the 4-byte entries.
-constexpr uint32_t kTmPadEntry = (uint32_t)kDotTile << 3;
-__global__ void k_tm_counts(const int32_t* __restrict__ tile_off, int64_t T, int n_tl, int64_t* __restrict__ cnt /*[n_tl * T + 1]*/,
-                            int group /* entries per 16-byte load: 4 or 8 */) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > (int64_t)n_tl * T) return;
-    if (i == (int64_t)n_tl * T) { cnt[i] = 0; return; }
-    const int64_t tl = i / T, t = i % T;
-    const int32_t* __restrict__ o = tile_off + t * (n_tl + 1) + tl;
-    cnt[i] = (o[1] - o[0] + group - 1) & ~(group - 1);     // (the run's padded length: the list is pre-filled with padding entries)
-}
-
-template <typename ENTRY>
-__global__ __launch_bounds__(kThreads) void k_tm_scatter(const int32_t* __restrict__ nz_idx, const double* __restrict__ nz_n,
-                                                         const int64_t* __restrict__ nz_off, const int32_t* __restrict__ tile_off,
-                                                         int64_t T, int n_tl, const int64_t* __restrict__ tm_off,
-                                                         ENTRY* __restrict__ tm_entries, int* __restrict__ bad, int tile_shift) {
-    const int64_t t = blockIdx.x;
-    const int64_t lo = nz_off[t], hi = nz_off[t + 1];
-    const int32_t* __restrict__ o = tile_off + t * (n_tl + 1);
-    bool any_bad = false;
-    for (int64_t j = lo + threadIdx.x; j < hi; j += kThreads) {
-        const int idx = nz_idx[j];
-        const double n = nz_n[j];
-        const int tl = idx >> tile_shift;
-        if constexpr (sizeof(ENTRY) == 2) {
-            if (!(n >= 1.0 && n <= 7.0 && n == floor(n))) any_bad = true;
-            tm_entries[tm_off[(int64_t)tl * T + t] + (j - lo - o[tl])] = (ENTRY)(((uint32_t)(idx - (tl << tile_shift)) << 3) | ((uint32_t)n & 7u));
-        } else {
-            if (!(n >= 1.0 && n < 32768.0 && n == floor(n))) any_bad = true;
-            tm_entries[tm_off[(int64_t)tl * T + t] + (j - lo - o[tl])] = ((uint32_t)(idx - (tl << tile_shift)) << 3) | ((uint32_t)n << 17);
-        }
-    }
-    if (any_bad) atomicOr(bad, 1);
-}
-
-// 1024 threads: 16 waves share one staged tile; every 16-lane row of a wave takes its own dataset, so a wave has four
-// (dataset, tile) runs in flight and a block 64.  The runs are short (~80 entries at C2) and each starts with a chain of
-// dependent loads (offsets -> entries -> LDS): with one run after the other per row the kernel sat at 134 us for 0.4 GB
-// (3 TB/s), every wave waiting a full memory latency two or three times per run.  Now a row keeps the loads of THREE
-// runs in flight (ring buffers in registers, the loop unrolled over the ring so that nothing is copied and nothing
-// newer than what it needs is waited for): offsets four runs ahead, entries two runs ahead.  Every load is
-// unconditional -- a run behind the row's last one is the last one again (requested, never stored), an entry load
-// reads up to kDotPad entries past its run (the lists are padded by that much) and its 4-entry sum is dropped afterwards
-// (runs are whole 16-byte groups: round 4) -- because a branch around a load makes the compiler wait for ALL outstanding
-// loads.  Index arithmetic is 32-bit, relative to the
-// block's first entry (the launch keeps a block below 2^31 entries).  Per lane the entries are added in ascending
-// order with fma, four at a time (one 16-byte load), the groups' sums then in ascending order: a fixed order, independent of
-// the launch geometry.
-typedef uint32_t bi_uint4 __attribute__((ext_vector_type(4)));
-constexpr int kDotThreads = 1024;
-#ifndef BI_DOT_DEPTH
-#define BI_DOT_DEPTH 2
-#endif
-constexpr int kDotPad = 64 * 2 + 16;           // entries behind the lists that the read-ahead may touch (read, masked, never used): the largest of the variants below
-
-// sum over the L lanes of a group inside a 16-lane DPP row (L = 16, or 8: groups start at lanes 0 and 8) on the cross-lane
-// data path; every lane of the group ends up with the total.  L = 16: four rotate-and-add steps; L = 8: the mirror image
-// within the half row (lane i <-> 7 - i), then the two exchanges within quads -- three steps, in a fixed order.
-template <int L>
-__device__ __forceinline__ double row_group_sum(double v) {
-#define BI_DPP_ADD(CTRL)                                                                                           \
-    do {                                                                                                           \
-        const unsigned long long u = __double_as_longlong(v);                                                      \
-        const unsigned lo = __builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xF, 0xF, true);                \
-        const unsigned hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xF, 0xF, true);        \
-        v += __longlong_as_double(((unsigned long long)hi << 32) | lo);                                            \
-    } while (0)
-    if constexpr (L == 16) {
-        BI_DPP_ADD(0x120 + 8);        // row_ror:8
-        BI_DPP_ADD(0x120 + 4);
-        BI_DPP_ADD(0x120 + 2);
-        BI_DPP_ADD(0x120 + 1);
-    } else if constexpr (L == 8) {
-        BI_DPP_ADD(0x141);            // row_half_mirror
-        BI_DPP_ADD(0xB1);             // quad_perm:[1,0,3,2]
-        BI_DPP_ADD(0x4E);             // quad_perm:[2,3,0,1]
-    } else if constexpr (L == 4) {
-        BI_DPP_ADD(0xB1);             // quad_perm:[1,0,3,2]
-        BI_DPP_ADD(0x4E);             // quad_perm:[2,3,0,1]
-    } else {
-        static_assert(L == 2, "groups of 2, 4, 8 or 16 lanes");
-        BI_DPP_ADD(0xB1);             // quad_perm:[1,0,3,2]
-    }
-#undef BI_DPP_ADD
-    return v;
-}
-
-// L lanes per (dataset, tile) run, AHEAD 16-byte loads per lane requested up front: 4 L AHEAD entry slots per run.
-// <16, 2>: 128 slots, 64 runs in flight per block (round 3).  <8, 3>: 96 slots -- a run at C2 is ~76 entries, so 79 % of the
-// slots carry an entry instead of 59 % --, 128 runs in flight per block, three rotate-and-add steps instead of four (round 4).
-// W: bytes per entry (4, or 2: counts up to 7) -- 16 / W entries per 16-byte load, (16 / W) L AHEAD slots per run.
-template <int L, int AHEAD, int W = 4>
-__global__ __launch_bounds__(kDotThreads) void k_dataset_dot_tiled(const void* __restrict__ tm_entries_v,
-                                                                   const int64_t* __restrict__ tm_off, int64_t T, int n_tl,
-                                                                   const double* __restrict__ logmu, int64_t B, int64_t t0,
-                                                                   int64_t n, double* __restrict__ partial /*[n_tl][n]*/) {
-    typedef typename std::conditional<W == 2, uint16_t, uint32_t>::type entry_t;
-    constexpr int EPL = 16 / W;                                        // entries per lane and load
-    static_assert(EPL * L * AHEAD + 16 <= kDotPad, "the lists' padding must cover the read-ahead");
-    const entry_t* __restrict__ tm_entries = static_cast<const entry_t*>(tm_entries_v);
-    __shared__ double s_mu[kDotTile + 1];                              // (+ the slot of the padding entries: 0.0)
-    const int tl = blockIdx.x;
-    const int64_t bin0 = (int64_t)tl * kDotTile;
-    const int row = threadIdx.x / L, gl = threadIdx.x % L;             // kDotThreads / L rows of L lanes
-    const int per = (int)((n + gridDim.y - 1) / gridDim.y);
-    const int c0u = (int)blockIdx.y * per, c1 = min((int)n, c0u + per);
-    const int c0 = min(c0u, (int)n - 1);                               // (clamped: a block without datasets still loads validly)
-    const int64_t* __restrict__ off = tm_off + (int64_t)tl * T + t0;
-    const int64_t base = off[c0];                                  // block-uniform: the entries of this block start here
-    const entry_t* __restrict__ ent = tm_entries + base;
-    const uint32_t* __restrict__ off32 = reinterpret_cast<const uint32_t*>(off);   // low words: all a block-relative index needs
-    const uint32_t base32 = (uint32_t)base;
-    constexpr int kStep = kDotThreads / L, kAhead = AHEAD, kDepth = BI_DOT_DEPTH, kRing = 2 * (kDepth + 1);   // entries kDepth runs ahead, offsets 2 kDepth; the ring a multiple of the entry buffers
-    const int q_last = max(c0, c1 - 1);
-    // (a step only ISSUES loads into the rings; whatever touches a loaded value -- the subtraction of the base, the mask
-    //  of the entries past the run's end -- happens in the step that consumes it, two or four steps later: the compiler
-    //  waits where a value is first used, and it does not move that use out of the step it was written in)
-    auto load_offsets = [&](int q, uint32_t& ra, uint32_t& rb) {
-        const int qc = min(q, q_last);
-        ra = off32[2 * qc];
-        rb = off32[2 * qc + 2];
-    };
-    // (a lane takes EPL consecutive entries per load: a group's load covers 16 L contiguous bytes of its run)
-    auto load_entries = [&](uint32_t ra, bi_uint4 (&e)[kAhead]) {
-        const entry_t* __restrict__ p = ent + (int)(ra - base32) + EPL * gl;
-#pragma unroll
-        for (int k = 0; k < kAhead; ++k) __builtin_memcpy(&e[k], p + EPL * L * k, 16);   // (16-byte load, 16-byte aligned: runs are whole groups)
-    };
-    bi_uint4 E[kDepth + 1][kAhead];
-    uint32_t RA[kRing], RB[kRing];
-    const int q0 = c0 + row;
-    // the pipeline's first requests go out before the tile is staged: their latency passes under the staging
-#pragma unroll
-    for (int u = 0; u < 2 * kDepth; ++u) load_offsets(q0 + u * kStep, RA[u], RB[u]);
-    {   // (all loads first, addresses clamped instead of predicated: eight loads in flight per thread, not one at a time)
-        double v[kDotTile / kDotThreads];
-#pragma unroll
-        for (int k = 0; k < kDotTile / kDotThreads; ++k) v[k] = logmu[min(bin0 + threadIdx.x + k * kDotThreads, B - 1)];
-#pragma unroll
-        for (int k = 0; k < kDotTile / kDotThreads; ++k)
-            s_mu[threadIdx.x + k * kDotThreads] = bin0 + threadIdx.x + k * kDotThreads < B ? v[k] : 0.0;
-        if (threadIdx.x == 0) s_mu[kDotTile] = 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < kDepth; ++u) load_entries(RA[u], E[u]);
-    __syncthreads();
-    if (c0u >= c1) return;
-    const int n_iter = (c1 - c0 + kStep - 1) / kStep;             // block-uniform: rows past their last run idle along
-    for (int it = 0; it < n_iter; it += kRing) {
-#pragma unroll
-        for (int u = 0; u < kRing; ++u) {
-            if (it + u < n_iter) {                               // (scalar condition)
-                const int q = q0 + (it + u) * kStep;
-                load_offsets(q + 2 * kDepth * kStep, RA[(u + 2 * kDepth) % kRing], RB[(u + 2 * kDepth) % kRing]);
-                load_entries(RA[(u + kDepth) % kRing], E[(u + kDepth) % (kDepth + 1)]);
-                __builtin_amdgcn_sched_barrier(0);               // the requests go out BEFORE this step's arithmetic, not after it
-                const bi_uint4 (&e)[kAhead] = E[u % (kDepth + 1)];
-                const int a = (int)(RA[u % kRing] - base32), b = (int)(RB[u % kRing] - base32);
-                const int len = b - a - EPL * gl;                // (padded) entries of the run from this lane's first on
-                double s = 0.0;
-                if constexpr (W == 4) {
-                    double lm[4 * kAhead];
-#define BI_TM_LOG(x) (*reinterpret_cast<const double*>(reinterpret_cast<const char*>(s_mu) + ((x) & 0x1FFF8u)))
-#pragma unroll
-                    for (int k = 0; k < 4 * kAhead; ++k) lm[k] = BI_TM_LOG(e[k >> 2][k & 3]);      // LDS reads in flight together
-#pragma unroll
-                    for (int g = 0; g < kAhead; ++g) {
-                        double sg = (double)(e[g][0] >> 17) * lm[4 * g];
-#pragma unroll
-                        for (int k = 1; k < 4; ++k) sg = __builtin_fma((double)(e[g][k] >> 17), lm[4 * g + k], sg);
-                        s += 4 * L * g < len ? sg : 0.0;         // (a load behind the run's end read other runs' entries: dropped whole)
-                    }
-                    for (int j = a + gl + 4 * L * kAhead; j < b; j += L) {                  // (runs beyond 4 L AHEAD entries)
-                        const uint32_t x = ent[j];
-                        s = __builtin_fma((double)(x >> 17), BI_TM_LOG(x), s);
-                    }
-#undef BI_TM_LOG
-                } else {
-                    // two entries per word: LDS byte offset = entry & 0xFFF8, count = entry & 7 (0 = padding: its term is dropped,
-                    // whatever log mu of bin 0 is)
-                    double lm[8 * kAhead];
-#define BI_TM_LOG16(x) (*reinterpret_cast<const double*>(reinterpret_cast<const char*>(s_mu) + ((x) & 0xFFF8u)))
-#pragma unroll
-                    for (int k = 0; k < 4 * kAhead; ++k) {
-                        const uint32_t x = e[k >> 2][k & 3];
-                        lm[2 * k] = BI_TM_LOG16(x);
-                        lm[2 * k + 1] = BI_TM_LOG16(x >> 16);
-                    }
-#pragma unroll
-                    for (int g = 0; g < kAhead; ++g) {
-                        double sg = 0.0;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const uint32_t x = e[g][k];
-                            const uint32_t n0 = x & 7u, n1 = (x >> 16) & 7u;
-                            sg = __builtin_fma((double)n0, n0 ? lm[8 * g + 2 * k] : 0.0, sg);
-                            sg = __builtin_fma((double)n1, n1 ? lm[8 * g + 2 * k + 1] : 0.0, sg);
-                        }
-                        s += 8 * L * g < len ? sg : 0.0;         // (a load behind the run's end read other runs' entries: dropped whole)
-                    }
-                    for (int j = a + gl + 8 * L * kAhead; j < b; j += L) {                  // (runs beyond 8 L AHEAD entries)
-                        const uint32_t x = ent[j];
-                        const uint32_t n0 = x & 7u;
-                        s = __builtin_fma((double)n0, n0 ? BI_TM_LOG16(x) : 0.0, s);
-                    }
-#undef BI_TM_LOG16
-                }
-                s = row_group_sum<L>(s);
-                if (gl == 0 && q < c1) partial[(int64_t)tl * n + q] = s;
-            }
-        }
-    }
-}
-
 // ---- toy-MC generation on the device ---------------------------------------------------------
 // n_{t,b} ~ Poisson(mu_b): the binned equivalent of Model.simulate (blueice/model.py:69-91: Poisson number of
 // events per source, each drawn from the source's pdf) followed by set_data's binning (likelihood.py:603-609).
@@ -1424,249 +1124,6 @@ __global__ void k_csr_to_dense(const int32_t* __restrict__ idx, const double* __
                                double* __restrict__ out) {
     const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j < nnz) out[idx[j]] = n[j];
-}
-
-// ---- toy-MC form: one parameter point, many datasets --------------------------------------
-// pass 1: mu_b -> logmu[b] (log mu, or -inf for mu == 0, or nan for invalid mu), partial sum mu
-__device__ __forceinline__ void morph_logmu_body(const LaunchArgs& a, const int64_t* __restrict__ rowoff, const double* __restrict__ coef,
-                                                 double* __restrict__ logmu, int store_mu) {
-    double sum = 0.0;
-    unsigned bad = 0u;
-    log_table_load();
-    for (int tile = blockIdx.x; tile < a.n_tiles; tile += gridDim.x) {
-        const int64_t bin0 = (int64_t)tile * kTile + threadIdx.x * kBinsPerThread;
-        double m0 = 0.0, m1 = 0.0;
-#pragma unroll 8
-        for (int k = 0; k < a.n0; ++k) {
-            const double2 v = *reinterpret_cast<const double2*>(a.ps + rowoff[k] + bin0);
-            const double c = coef[k];
-            m0 = fma(c, v.x, m0);
-            m1 = fma(c, v.y, m1);
-        }
-        double2 l;
-        if (store_mu) {  // toy generation wants the expectation itself
-            l.x = m0;
-            l.y = m1;
-        } else {
-            l.x = (m0 >= 0.0) ? bin_log(m0) : __builtin_nan("");
-            l.y = (m1 >= 0.0) ? bin_log(m1) : __builtin_nan("");
-        }
-        if (!(m0 >= 0.0) || !(m1 >= 0.0)) bad = 1u;
-        *reinterpret_cast<double2*>(logmu + bin0) = l;
-        sum += m0 + m1;
-    }
-    __shared__ double sh[kThreads / 64];
-    __shared__ unsigned shf[kThreads / 64];
-    sum = wave_sum(sum);
-    bad = wave_or(bad);
-    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = sum; shf[threadIdx.x >> 6] = bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = sh[0];
-        unsigned f = shf[0];
-        for (int w = 1; w < kThreads / 64; ++w) { t += sh[w]; f |= shf[w]; }
-        a.partial[blockIdx.x] = t;
-        a.pflags[blockIdx.x] = f;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_morph_logmu(LaunchArgs a, double* __restrict__ logmu, int store_mu) {
-    morph_logmu_body(a, a.rowoff, a.coef, logmu, store_mu);
-}
-
-// The point's descriptors in the kernel arguments (up to kMaxSingleStreams streams): a toy-MC call is ONE point, and a
-// host-to-device copy of its 512 bytes ahead of the launch costs more than the launch (10 ... 15 us on this runtime).
-struct PointDesc {
-    int64_t rowoff[kMaxSingleStreams];
-    double coef[kMaxSingleStreams];
-};
-
-__global__ __launch_bounds__(kThreads) void k_morph_logmu_desc(LaunchArgs a, PointDesc d, double* __restrict__ logmu, int store_mu) {
-    morph_logmu_body(a, d.rowoff, d.coef, logmu, store_mu);
-}
-
-// pass 2: for dataset t: sum_b xlogy(n_tb, mu_b).  blockIdx.y = group of kDotGroup datasets, x strides tiles: the
-// log mu tile is loaded once per group (it stays in L2 / Infinity Cache: 8 MB), the counts rows stream through once
-// with the nontemporal hint; XCD-aware tile order as in morph_tiles.
-constexpr int kDotGroup = 8;
-
-__device__ __forceinline__ double xlogy_term(double n, double l) {
-    double t = (n > 0.0) ? n * l : 0.0;
-    if (n != n) t = __builtin_nan("");
-    else if (n < 0.0 || n != floor(n)) t = -__builtin_inf();
-    return t;
-}
-
-__global__ __launch_bounds__(kThreads) void k_dataset_dot(const double* __restrict__ counts,
-                                                          const double* __restrict__ logmu, int64_t Bp, int n_tiles,
-                                                          int64_t t0, int64_t n_sets, double* __restrict__ partial) {
-    const int64_t d0 = (int64_t)blockIdx.y * kDotGroup;
-    const double* __restrict__ c[kDotGroup];
-#pragma unroll
-    for (int g = 0; g < kDotGroup; ++g) c[g] = counts + (t0 + min(d0 + g, n_sets - 1)) * Bp;   // tail group: repeats the last row
-    double s[kDotGroup];
-#pragma unroll
-    for (int g = 0; g < kDotGroup; ++g) s[g] = 0.0;
-    const int chunks = n_tiles >= 64 * 8 ? 8 : 1;
-    const int per_chunk = (n_tiles + chunks - 1) / chunks;
-    for (int lt = blockIdx.x; lt < per_chunk * chunks; lt += gridDim.x) {
-        const int tile = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
-        if (tile >= n_tiles) continue;
-        const int64_t bin0 = (int64_t)tile * kTile + threadIdx.x * kBinsPerThread;
-        double2 n[kDotGroup];
-#pragma unroll
-        for (int g = 0; g < kDotGroup; ++g) n[g] = stream_load<true>(c[g] + bin0);
-        const double2 l = *reinterpret_cast<const double2*>(logmu + bin0);
-#pragma unroll
-        for (int g = 0; g < kDotGroup; ++g) s[g] += xlogy_term(n[g].x, l.x) + xlogy_term(n[g].y, l.y);
-    }
-    __shared__ double sh[kThreads / 64][kDotGroup];
-#pragma unroll
-    for (int g = 0; g < kDotGroup; ++g) {
-        const double w = wave_sum(s[g]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][g] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < kDotGroup && d0 + threadIdx.x < n_sets) {
-        double t = sh[0][threadIdx.x];
-        for (int w = 1; w < kThreads / 64; ++w) t += sh[w][threadIdx.x];
-        partial[(d0 + threadIdx.x) * gridDim.x + blockIdx.x] = t;
-    }
-}
-
-// out[t] = sum_blocks partial[t][:] - summu - lgsum[t0 + t]   (nan if any mu invalid).  256 threads per block: the
-// block first sums the mu partials of pass 1 together (fixed tree), then every thread finishes one dataset.
-// (partial[t * t_stride + b * b_stride]: dataset-major from the row kernels, block-major from the tiled one, whose 123
-// partials per dataset would otherwise be read with a stride of 123 doubles between neighbouring threads)
-__global__ __launch_bounds__(kThreads) void k_dataset_finish(const double* __restrict__ partial, int nbx, int64_t t_stride, int64_t b_stride,
-                                                             const double* __restrict__ mu_partial,
-                                                             const unsigned* __restrict__ mu_flags, int nmu,
-                                                             const double* __restrict__ lgsum, int64_t t0, int64_t n,
-                                                             double* __restrict__ out) {
-    __shared__ double sh[kThreads / 64];
-    __shared__ unsigned shf[kThreads / 64];
-    double m = 0.0;
-    unsigned f = 0u;
-    {   // (four loads in flight per thread: every block of this kernel repeats this sum before it can start on its datasets)
-        double m4[4] = {0.0, 0.0, 0.0, 0.0};
-        int b = threadIdx.x;
-        for (; b + 3 * kThreads < nmu; b += 4 * kThreads) {
-            double v[4];
-            unsigned g[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v[k] = mu_partial[b + k * kThreads]; g[k] = mu_flags[b + k * kThreads]; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { m4[k] += v[k]; f |= g[k]; }
-        }
-        for (; b < nmu; b += kThreads) { m4[0] += mu_partial[b]; f |= mu_flags[b]; }
-        m = (m4[0] + m4[1]) + (m4[2] + m4[3]);
-    }
-    m = wave_sum(m);
-    f = wave_or(f);
-    if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = m; shf[threadIdx.x >> 6] = f; }
-    __syncthreads();
-    m = sh[0];
-    f = shf[0];
-#pragma unroll
-    for (int w = 1; w < kThreads / 64; ++w) { m += sh[w]; f |= shf[w]; }
-    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (t >= n) return;
-    // eight running sums: the loads of a thread do not wait for one another (123 block-major partials per dataset from
-    // the tiled kernel are 123 trips to L2 otherwise); fixed order all the same
-    const double* __restrict__ p = partial + t * t_stride;
-    double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    int b = 0;
-    for (; b + 7 < nbx; b += 8) {
-        double v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = p[(int64_t)(b + k) * b_stride];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] += v[k];
-    }
-    for (; b < nbx; ++b) acc[0] += p[(int64_t)b * b_stride];
-    const double s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-    double r = (s - m) - lgsum[t0 + t];
-    if (f) r = __builtin_nan("");
-    out[t] = r;
-}
-
-// The finish of the tiled toy-MC pass, partial[tile][dataset] (block-major): 64 datasets per block, the tiles of a
-// dataset split over the block's four waves (k_dataset_finish has one thread walk all ~123 tiles of its dataset, 16 trips
-// to L2 one after the other on 40 blocks: 10 ... 15 us for 10^4 datasets; here 157 blocks and four trips).  Fixed order:
-// a wave's range in steps of eight with eight running sums, then the four waves' sums ((0 + 1) + (2 + 3)).
-// done != NULL: out is pinned host memory; the block that finishes last publishes `seq` there with a system-scope
-// release once every block's results are on their way (the host polls the word instead of synchronising the stream).
-__global__ __launch_bounds__(kThreads) void k_dataset_finish_tiled(const double* __restrict__ partial, int nbx,
-                                                                   const double* __restrict__ mu_partial,
-                                                                   const unsigned* __restrict__ mu_flags, int nmu,
-                                                                   const double* __restrict__ lgsum, int64_t t0, int64_t n,
-                                                                   double* __restrict__ out, unsigned* __restrict__ blocks_done,
-                                                                   unsigned long long* done, unsigned long long seq) {
-    static_assert(kThreads == 256, "four waves per block");
-    __shared__ double sh[kThreads / 64];
-    __shared__ unsigned shf[kThreads / 64];
-    __shared__ double part[kThreads / 64][64];
-    double m = 0.0;
-    unsigned f = 0u;
-    {
-        double m4[4] = {0.0, 0.0, 0.0, 0.0};
-        int b = threadIdx.x;
-        for (; b + 3 * kThreads < nmu; b += 4 * kThreads) {
-            double v[4];
-            unsigned g[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { v[k] = mu_partial[b + k * kThreads]; g[k] = mu_flags[b + k * kThreads]; }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { m4[k] += v[k]; f |= g[k]; }
-        }
-        for (; b < nmu; b += kThreads) { m4[0] += mu_partial[b]; f |= mu_flags[b]; }
-        m = (m4[0] + m4[1]) + (m4[2] + m4[3]);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t t = (int64_t)blockIdx.x * 64 + lane;
-    const int per = (nbx + 3) / 4;
-    const int b0 = wave * per, b1 = min(nbx, b0 + per);
-    double s = 0.0;
-    if (t < n) {
-        const double* __restrict__ p = partial + t;
-        double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        int b = b0;
-        for (; b + 7 < b1; b += 8) {
-            double v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = p[(int64_t)(b + k) * n];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) acc[k] += v[k];
-        }
-        for (; b < b1; ++b) acc[0] += p[(int64_t)b * n];
-        s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-    }
-    part[wave][lane] = s;
-    m = wave_sum(m);
-    f = wave_or(f);
-    if (lane == 0) { sh[wave] = m; shf[wave] = f; }
-    __syncthreads();
-    if (wave == 0 && t < n) {
-        double mm = sh[0];
-        unsigned ff = shf[0];
-#pragma unroll
-        for (int w = 1; w < kThreads / 64; ++w) { mm += sh[w]; ff |= shf[w]; }
-        const double tot = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-        double r = (tot - mm) - lgsum[t0 + t];
-        if (ff) r = __builtin_nan("");
-        out[t] = r;
-    }
-    if (!done) return;
-    if (wave == 0) {
-        __threadfence_system();                        // this wave's results have left before the block is counted
-        if (lane == 0) {
-            const unsigned before = __hip_atomic_fetch_add(blocks_done, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (before == gridDim.x - 1) {
-                __hip_atomic_store(blocks_done, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (ready for the next call)
-                __hip_atomic_store(done, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
 }
 
 // The finish of a scan plan: partial is [items][nslots][16] (point fastest), one wave per item.  Lane l takes point

@@ -560,25 +560,9 @@ hipError_t plan_report(bi_ctx* c, ReportPiece a, ReportPiece b = ReportPiece{nul
     hipLaunchKernelGGL(k_plan_report, dim3(1), dim3(kThreads), 0, c->stream, a, b, c3, (uint32_t*)c->plan_host, flag, seq);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (c->poll_result && !c->profiling) {
-        const volatile unsigned long long* f = flag;
-        const auto t_start = std::chrono::steady_clock::now();
-        const auto t_spin = t_start + std::chrono::microseconds(100), t_end = t_start + std::chrono::milliseconds(20);
-        bool yielding = false;                 // (the planning kernels of a large batch take a while: the core is given away after 100 us)
-        for (unsigned spin = 0; *f != seq; ++spin) {
-            if (yielding) {
-                sched_yield();
-                if (std::chrono::steady_clock::now() > t_end) break;                           // (a fault upstream: the synchronisation below reports it)
-                continue;
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-            if ((spin & 63u) == 63u && std::chrono::steady_clock::now() > t_spin) yielding = true;
-        }
-        if (*f == seq) {
-            std::atomic_thread_fence(std::memory_order_acquire);
-            return hipSuccess;
-        }
+        // (the planning kernels of a large batch take a while: the core is given away after 100 us; a word that has not come
+        //  after 20 ms -- a fault upstream -- leaves it to the synchronisation below, which reports it)
+        if (wait_word(flag, seq, std::chrono::microseconds(100), std::chrono::milliseconds(20))) return hipSuccess;
     }
     return hipStreamSynchronize(c->stream);
 }

@@ -15,15 +15,9 @@ int single_wait(bi_ctx* c, unsigned long long seq, double* out, int32_t* status)
     char* res = (char*)c->slot_host;
     bool arrived = false;
     if (c->poll_result && !c->profiling) {
-        const volatile unsigned long long* done = (const volatile unsigned long long*)(res + 16);
-        const auto t_end = std::chrono::steady_clock::now() + std::chrono::milliseconds(20);
-        for (unsigned spin = 0; !(arrived = (*done == seq)); ++spin) {
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-            if ((spin & 1023u) == 1023u && std::chrono::steady_clock::now() > t_end) break;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
+        // (20 ms without a yield phase: the word of a single point is microseconds away; the clock every 1024 looks)
+        const std::chrono::milliseconds limit(20);
+        arrived = wait_word((const volatile unsigned long long*)(res + 16), seq, limit, limit, 1024);
     }
     if (!arrived || (seq & 255ull) == 0) HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (*(const volatile unsigned long long*)(res + 16) != seq)

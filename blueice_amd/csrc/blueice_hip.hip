@@ -33,6 +33,7 @@
 #include "bi_grad.h"
 #include "bi_params.h"
 #include "bi_events.h"
+#include "bi_toys.h"
 
 namespace {
 
@@ -836,273 +837,7 @@ int bi_eval_end(bi_ctx* c, double* out, int32_t* status) {
     return single_wait(c, c->pending_seq, out, status);
 }
 
-// ---- toy-MC form ---------------------------------------------------------------------------
-
-}  // extern "C"
-
-namespace {
-
-// Tile-major copy of the context's non-empty-bin lists for tiles of `tile_bins` bins (a power of two, at most kDotTile): the
-// entries of bin tile 0 (dataset 0, 1, ...), then tile 1, ... -- see k_tm_scatter.  Two-byte entries where every count is at
-// most 7 (toys of sparse expectations), four-byte entries otherwise; ok = false (and nothing kept) when some count fits neither.
-int build_tile_major(bi_ctx* c, int tile_bins, DevBuf& entries, DevBuf& off, bool& ok, int& width_out) {
-    int tile_shift = 0;
-    while ((1 << tile_shift) < tile_bins) ++tile_shift;
-    const int n_tl = (int)((c->B + tile_bins - 1) / tile_bins);
-    const int64_t nnz = c->h_nz_off.back(), cells = (int64_t)n_tl * c->T;
-    const uint32_t pad_entry = (uint32_t)tile_bins << 3;          // four-byte lists: the offset of the extra LDS slot behind the tile (0.0), count 0
-    int rc;
-    ScratchBuf d_tile, d_cnt, d_tmp, d_bad;
-    size_t scan_bytes = 0;
-    (void)prim_exclusive_scan_sum(nullptr, scan_bytes, (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t)0, (size_t)(cells + 1), c->stream);
-    if ((rc = dev_alloc(c, d_tile, (size_t)c->T * (n_tl + 1) * sizeof(int32_t))) || (rc = dev_alloc(c, d_cnt, (size_t)(cells + 1) * sizeof(int64_t))) ||
-        (rc = dev_alloc(c, d_tmp, std::max<size_t>(scan_bytes, 256))) || (rc = dev_alloc(c, d_bad, 64)) ||
-        (rc = dev_alloc(c, off, (size_t)(cells + 1) * sizeof(int64_t)))) return rc;
-    hipLaunchKernelGGL(k_csr_tile_offsets, dim3((unsigned)c->T), dim3(kThreads), 0, c->stream, (const int32_t*)c->nz_idx.p,
-                       (const int64_t*)c->nz_off.p, n_tl, (int32_t*)d_tile.p, tile_shift);
-    hipError_t e = hipGetLastError();
-    // two-byte entries where every count is at most 7 (toys of sparse expectations), four-byte entries otherwise: the first
-    // format is tried, and a count that does not fit sends the build to the second
-    ok = false;
-    for (int width = c->dot_entry16 ? 2 : 4; e == hipSuccess && !ok; width = 4) {
-        const int group = 16 / width;
-        const size_t n_entries = (size_t)(nnz + (group - 1) * cells + kDotPad);     // (every run padded to whole 16-byte groups; + the kernel's read-ahead)
-        if ((rc = dev_alloc(c, entries, n_entries * width))) return rc;
-        e = hipMemsetAsync(d_bad.p, 0, 64, c->stream);
-        // (two-byte entries: 13 bits of offset -- tiles of 8192 bins use them all, their padding is entry 0, dropped by a select on
-        //  the count; tiles of up to 4096 bins leave the bit for the offset of the extra zero slot behind the tile, as four-byte
-        //  entries have it)
-        if (e == hipSuccess && width == 2 && tile_bins > 4096) e = hipMemsetAsync(entries.p, 0, n_entries * 2, c->stream);
-        if (e == hipSuccess && width == 2 && tile_bins <= 4096) e = hipMemsetD16Async((hipDeviceptr_t)entries.p, (unsigned short)pad_entry, n_entries, c->stream);
-        if (e == hipSuccess && width == 4) e = hipMemsetD32Async((hipDeviceptr_t)entries.p, (int)pad_entry, n_entries, c->stream);
-        hipLaunchKernelGGL(k_tm_counts, dim3((unsigned)((cells + 1 + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)d_tile.p, c->T,
-                           n_tl, (int64_t*)d_cnt.p, group);
-        size_t tb = d_tmp.bytes;
-        if (e == hipSuccess) e = prim_exclusive_scan_sum(d_tmp.p, tb, (const int64_t*)d_cnt.p, (int64_t*)off.p, (int64_t)0, (size_t)(cells + 1), c->stream);
-        if (width == 2)
-            hipLaunchKernelGGL((k_tm_scatter<uint16_t>), dim3((unsigned)c->T), dim3(kThreads), 0, c->stream, (const int32_t*)c->nz_idx.p,
-                               (const double*)c->nz_n.p, (const int64_t*)c->nz_off.p, (const int32_t*)d_tile.p, c->T, n_tl,
-                               (const int64_t*)off.p, (uint16_t*)entries.p, (int*)d_bad.p, tile_shift);
-        else
-            hipLaunchKernelGGL((k_tm_scatter<uint32_t>), dim3((unsigned)c->T), dim3(kThreads), 0, c->stream, (const int32_t*)c->nz_idx.p,
-                               (const double*)c->nz_n.p, (const int64_t*)c->nz_off.p, (const int32_t*)d_tile.p, c->T, n_tl,
-                               (const int64_t*)off.p, (uint32_t*)entries.p, (int*)d_bad.p, tile_shift);
-        int bad = 0;
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) break;
-        ok = bad == 0;
-        width_out = width;
-        if (width == 4) break;
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets (tile-major lists): %s", hipGetErrorString(e));
-    if (!ok) { dev_free(entries); dev_free(off); }
-    return BI_OK;
-}
-
-// out_dev != NULL: results stay in HBM at out_dev[0 .. t1 - t0) (the call still returns after the stream has drained:
-// its descriptors travel through the context's pinned staging block, which the next call reuses)
-int eval_datasets_impl(bi_ctx* c, const double* z, const double* rate_scale, int64_t t0, int64_t t1, double* out,
-                       double* out_dev, int32_t* status) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (c->bb_source >= 0) return fail(c, BI_ERR_INVALID, "bi_eval_datasets is not available with Beeston-Barlow");
-    if (multi_set(c)) return refuse_sets(c, "bi_eval_datasets");
-    if (c->unbinned) return fail(c, BI_ERR_INVALID, "bi_eval_datasets needs a binned likelihood");
-    if (t0 < 0 || t1 > c->T || t0 > t1) return fail(c, BI_ERR_INVALID, "dataset range [%lld,%lld) outside [0,%lld)", (long long)t0, (long long)t1, (long long)c->T);
-    if (c->d > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
-    if (t1 > t0 && !out && !out_dev) return fail(c, BI_ERR_INVALID, "out is NULL");
-    HIP_TRY(c, hipSetDevice(c->device));
-    const int64_t n = t1 - t0;
-    if (status) *status = 0;
-    const double ninf = -std::numeric_limits<double>::infinity();
-    auto reject = [&](int32_t bit) -> int {          // the reference returns -inf before it looks at any data
-        if (status) *status = bit;
-        if (out_dev) {
-            // on the context's stream, like every other write to (and the caller's collectives on) that buffer
-            if (n) {
-                hipLaunchKernelGGL(k_fill_value, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, out_dev, n, ninf);
-                hipError_t e = hipGetLastError();
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets_device: %s", hipGetErrorString(e));
-            }
-        } else {
-            std::fill(out, out + n, ninf);
-        }
-        return BI_OK;
-    };
-    PointGeom g;
-    std::vector<double> r((size_t)c->S);
-    if (const int32_t bit = screen_point(c, z, rate_scale, 0, g, r.data())) return reject(bit);
-    const int nc = (int)g.w.size();
-    const int NS = nc * c->S;
-    std::vector<int64_t> rowoff((size_t)NS);
-    std::vector<double> coef((size_t)NS);
-    int k = 0;
-    for (int corner = 0; corner < nc; ++corner)
-        for (int s = 0; s < c->S; ++s) {
-            rowoff[(size_t)k] = ((g.cell_anchor + corner_offset(c, corner)) * c->S + s) * c->Bp;
-            coef[(size_t)k++] = g.w[(size_t)corner] * r[(size_t)s];
-        }
-    const int n_tiles = n_tiles_of(c);
-    const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
-    const int nmu = (int)std::min<int64_t>(n_tiles, slots);
-    ScratchBuf d_out;
-    const bool csr = (c->sparse && c->csr_ready) || !c->dense_counts;
-    if (csr && !c->csr_ready) return fail(c, BI_ERR_STATE, "no counts resident");
-    // Non-empty-bin lists with enough entries per (dataset, bin tile): the tiled kernel (log mu staged through LDS, the
-    // lists re-ordered tile by tile once per data upload).
-    const int n_tl = (int)((c->B + kDotTile - 1) / kDotTile);
-    bool tiled = csr && c->dot_tiled && n >= 64 && n_tl >= 4 && c->h_nz_off.size() == (size_t)c->T + 1 &&
-                 c->h_nz_off.back() >= (int64_t)16 * c->T * n_tl && (int64_t)c->T * (n_tl + 1) <= ((int64_t)1 << 28);
-    if (tiled && c->nz_tile_epoch != c->epoch) {
-        if ((rc = build_tile_major(c, kDotTile, c->tm_entries, c->tm_off, c->tm_ok, c->tm_width))) return rc;
-        c->nz_tile_epoch = c->epoch;
-    }
-    tiled = tiled && c->tm_ok;
-    const int64_t chunk = tiled ? std::max<int64_t>(64, ((int64_t)1 << 27) / n_tl) : (csr ? 1048576 : 16384);
-    const int nbx = tiled ? n_tl : csr ? 1 : (int)std::min<int64_t>(n_tiles, std::max<int64_t>(1, 4 * slots / std::max<int64_t>(1, (std::min(n, chunk) + kDotGroup - 1) / kDotGroup)));
-    // descriptors in one packed copy; up to 4 MB of results are written straight into pinned host memory
-    const bool host_out = !out_dev && (size_t)n * sizeof(double) <= ((size_t)4 << 20);
-    // (up to kMaxSingleStreams streams the point's descriptors ride in the kernel arguments: no copy ahead of the launch)
-    const bool by_value = NS <= kMaxSingleStreams && (c->toy_fast_call & 1);
-    PackedUpload pu;
-    std::vector<std::pair<const void*, size_t>> parts;
-    if (!by_value) parts = {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)}};
-    if ((rc = packed_upload(c, parts, host_out ? (size_t)n * sizeof(double) : 0, pu)) ||
-        (rc = dev_alloc(c, c->logmu, (size_t)c->Bp * sizeof(double))) ||
-        (rc = dev_alloc(c, c->scratch, (size_t)nmu * sizeof(double) + (size_t)nmu * sizeof(unsigned) + 64)) ||
-        (rc = dev_alloc(c, c->scratch2, (size_t)std::min(n, chunk) * nbx * sizeof(double))) ||
-        (!host_out && !out_dev && (rc = dev_alloc(c, d_out, (size_t)std::max<int64_t>(n, 1) * sizeof(double))))) return rc;
-    double* res = out_dev ? out_dev : (host_out ? (double*)pu.host_out() : (double*)d_out.p);
-    LaunchArgs a{};
-    a.ps = (const double*)c->ps.p;
-    a.rowoff = by_value ? nullptr : pu.dev<int64_t>(0);
-    a.coef = by_value ? nullptr : pu.dev<double>(1);
-    a.partial = (double*)c->scratch.p;
-    a.pflags = (unsigned*)((char*)c->scratch.p + (((size_t)nmu * sizeof(double) + 63) / 64) * 64);
-    a.B = c->B; a.Bp = c->Bp; a.n0 = NS; a.n_tiles = n_tiles;
-    // One chunk of tiled partials whose results go to pinned host memory: the finish kernel's last block publishes a
-    // sequence number behind them, and the call polls that word (as single evaluations do) instead of synchronising
-    unsigned long long* done_word = nullptr;
-    unsigned long long seq = 0;
-    if (tiled && host_out && n <= chunk && c->poll_result && !c->profiling && (c->toy_fast_call & 6) == 6) {
-        if ((rc = dev_alloc(c, c->toy_blocks_done, 64))) return rc;
-        if (!c->toy_blocks_done_zeroed) {
-            HIP_TRY(c, hipMemsetAsync(c->toy_blocks_done.p, 0, 64, c->stream));
-            c->toy_blocks_done_zeroed = true;
-        }
-        done_word = (unsigned long long*)((char*)pu.host_out() + ((size_t)n * sizeof(double) + 63) / 64 * 64);   // (packed_upload keeps 64 spare bytes behind the results)
-        seq = ++c->toy_seq;
-        *(volatile unsigned long long*)done_word = 0ull;
-    }
-    auto launch_logmu = [&]() {
-        EventScope ev(c);
-        if (by_value) {
-            PointDesc pd;
-            memcpy(pd.rowoff, rowoff.data(), rowoff.size() * sizeof(int64_t));
-            memcpy(pd.coef, coef.data(), coef.size() * sizeof(double));
-            hipLaunchKernelGGL(k_morph_logmu_desc, dim3((unsigned)nmu), dim3(kThreads), 0, c->stream, a, pd, (double*)c->logmu.p, 0);
-        } else
-            hipLaunchKernelGGL(k_morph_logmu, dim3((unsigned)nmu), dim3(kThreads), 0, c->stream, a, (double*)c->logmu.p, 0);
-    };
-    launch_logmu();
-    for (int64_t s0 = 0; s0 < n; s0 += chunk) {
-        const int64_t ni = std::min(chunk, n - s0);
-        {
-            EventScope ev(c);
-            if (tiled) {
-                // datasets split over blockIdx.y so that ~4 blocks per CU exist; every block stages its tile once
-                // (and few enough datasets per block for its 32-bit entry indices: datasets x kDotTile < 2^31)
-                // as many blocks as are resident at once (the 8-lane variant's registers allow one per CU, the 16-lane
-                // variant's two; asked from the runtime once): ONE round, every block's start-up paid once
-                // variant: 4-byte entries <8, 3> (96 slots per run) or <16, 2>; 2-byte entries <8, 2, 2> (128 slots) or, dot_lanes 4,
-                // <4, 3, 2> (96 slots)
-                // (dot_lanes 0 = the best measured for the entry width: 8 lanes with four-byte entries, 4 with two-byte ones)
-                const int variant = c->tm_width == 2 ? ((c->dot_lanes == 4 || c->dot_lanes == 0) ? 3 : 2) : (c->dot_lanes == 16 ? 1 : 0);
-                static std::atomic<int> resident_cache[4];
-                std::atomic<int>& rslot = resident_cache[variant];
-                int resident = c->dot_blocks_per_cu > 0 ? (int)c->dot_blocks_per_cu : rslot.load();
-                if (resident <= 0) {
-                    int r = 0;
-                    const void* f = variant == 0 ? (const void*)k_dataset_dot_tiled<8, 3, 4> : variant == 1 ? (const void*)k_dataset_dot_tiled<16, 2, 4>
-                                  : variant == 2 ? (const void*)k_dataset_dot_tiled<8, 2, 2> : (const void*)k_dataset_dot_tiled<4, 3, 2>;
-                    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&r, f, kDotThreads, 0) != hipSuccess || r < 1) r = 1;
-                    rslot.store(r);
-                    resident = r;
-                }
-                const unsigned by = (unsigned)std::max<int64_t>({1, std::min<int64_t>((ni + 255) / 256, (int64_t)resident * c->prop.multiProcessorCount / n_tl),
-                                                                 (ni + 262143) / 262144});
-#define BI_DOT(L, AHEAD, W)                                                                                        \
-    hipLaunchKernelGGL((k_dataset_dot_tiled<L, AHEAD, W>), dim3((unsigned)n_tl, by), dim3(kDotThreads), 0, c->stream, \
-                       (const void*)c->tm_entries.p, (const int64_t*)c->tm_off.p, c->T, n_tl,                      \
-                       (const double*)c->logmu.p, c->B, t0 + s0, ni, (double*)c->scratch2.p)
-                if (variant == 0) BI_DOT(8, 3, 4); else if (variant == 1) BI_DOT(16, 2, 4); else if (variant == 2) BI_DOT(8, 2, 2); else BI_DOT(4, 3, 2);
-#undef BI_DOT
-            } else if (csr)
-                hipLaunchKernelGGL(k_dataset_dot_csr, dim3((unsigned)ni), dim3(kThreads), 0, c->stream,
-                                   (const int32_t*)c->nz_idx.p, (const double*)c->nz_n.p, (const int64_t*)c->nz_off.p,
-                                   (const double*)c->logmu.p, t0 + s0, (double*)c->scratch2.p);
-            else
-                hipLaunchKernelGGL(k_dataset_dot, dim3((unsigned)nbx, (unsigned)((ni + kDotGroup - 1) / kDotGroup)), dim3(kThreads), 0,
-                                   c->stream, (const double*)c->counts.p, (const double*)c->logmu.p, c->Bp, n_tiles, t0 + s0, ni,
-                                   (double*)c->scratch2.p);
-        }
-        if (tiled && (c->toy_fast_call & 2))
-            hipLaunchKernelGGL(k_dataset_finish_tiled, dim3((unsigned)((ni + 63) / 64)), dim3(kThreads), 0, c->stream,
-                               (const double*)c->scratch2.p, nbx, (const double*)a.partial, (const unsigned*)a.pflags, nmu,
-                               (const double*)c->lgsum.p, t0 + s0, ni, res + s0, (unsigned*)c->toy_blocks_done.p, done_word, seq);
-        else
-            hipLaunchKernelGGL(k_dataset_finish, dim3((unsigned)((ni + 255) / 256)), dim3(256), 0, c->stream,
-                               (const double*)c->scratch2.p, nbx, tiled ? (int64_t)1 : (int64_t)nbx, tiled ? ni : (int64_t)1,
-                               (const double*)a.partial, (const unsigned*)a.pflags, nmu,
-                               (const double*)c->lgsum.p, t0 + s0, ni, res + s0);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && n && !host_out && !out_dev) e = hipMemcpyAsync(out, d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    bool arrived = false;
-    if (e == hipSuccess && done_word) {
-        // The word arrives ~0.1 ms after the launches for 10^4 datasets: spin for the first ~30 us (a yield costs more than
-        // the wait is worth there), then give the core away between looks -- eight ranks of a node each burning a core per
-        // call is what the launcher's thread cap exists to prevent -- and fall back to the stream synchronise (which also
-        // reports a faulted kernel) after a time that scales with the work: 2 ms + 1 us per dataset, at most 50 ms.
-        const volatile unsigned long long* dw = done_word;
-        const auto t_start = std::chrono::steady_clock::now();
-        const auto t_spin = t_start + std::chrono::microseconds(30);
-        const auto t_end = t_start + std::chrono::microseconds(std::min<int64_t>(50000, 2000 + n));
-        bool yielding = false;
-        for (unsigned spin = 0; !(arrived = (*dw == seq)); ++spin) {
-            if (yielding) {
-                sched_yield();
-                if (std::chrono::steady_clock::now() > t_end) break;
-                continue;
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#endif
-            if ((spin & 63u) == 63u && std::chrono::steady_clock::now() > t_spin) yielding = true;
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        ++c->n_toy_polled;
-    }
-    // (falls back to the stream sync, which also reports a faulted kernel; every 256th call synchronises anyway, so the
-    //  runtime retires its completed commands at a steady pace)
-    if (e == hipSuccess && (!arrived || (seq & 255ull) == 0)) e = hipStreamSynchronize(c->stream);
-    // (a completion word that never came -- a launch that failed part way -- leaves the finish kernel's block counter in an
-    //  unknown state: it is zeroed again before the next call, which would otherwise wait out its 50 ms every time)
-    if (done_word && !arrived) c->toy_blocks_done_zeroed = false;
-    if (e == hipSuccess && n && host_out) memcpy(out, res, (size_t)n * sizeof(double));
-    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_eval_datasets: %s", hipGetErrorString(e));
-    return BI_OK;
-}
-
-}  // namespace
-
-#include "bi_toy_points.h"
-
-extern "C" {
+// ---- toy-MC form (bi_toys.h) ----------------------------------------------------------------
 
 int bi_eval_datasets_points(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, int64_t t0, int64_t t1, double* out,
                             int32_t* status) {
@@ -1149,11 +884,10 @@ static int draw_toy_lists(bi_ctx* c, const std::vector<ToyTruth>& truths, const 
     std::vector<double> coef;
     for (int64_t h = 0; h < H; ++h) {
         const PointGeom& g = truths[(size_t)h].g;
-        for (int corner = 0; corner < (int)g.w.size(); ++corner)
-            for (int s = 0; s < c->S; ++s) {
-                rowoff.push_back(((g.cell_anchor + corner_offset(c, corner)) * c->S + s) * Bp);
-                coef.push_back(g.w[(size_t)corner] * truths[(size_t)h].r[(size_t)s]);
-            }
+        const size_t k0 = rowoff.size(), NS = g.w.size() * (size_t)c->S;
+        rowoff.resize(k0 + NS);
+        coef.resize(k0 + NS);
+        point_streams(c, g, truths[(size_t)h].r.data(), rowoff.data() + k0, coef.data() + k0);
         first_row[(size_t)h + 1] = (int64_t)rowoff.size();
         first_toy[(size_t)h + 1] = first_toy[(size_t)h] + n_toys[h];
     }
@@ -1178,7 +912,7 @@ static int draw_toy_lists(bi_ctx* c, const std::vector<ToyTruth>& truths, const 
         a.rowoff = (const int64_t*)d_row.p + first_row[(size_t)h];
         a.coef = (const double*)d_coef.p + first_row[(size_t)h];
         a.n0 = (int)(first_row[(size_t)h + 1] - first_row[(size_t)h]);
-        hipLaunchKernelGGL(k_morph_logmu, dim3((unsigned)nmu), dim3(kThreads), 0, c->stream, a, (double*)d_mu.p + h * Bp, 1);
+        launch_morph_logmu(c, nmu, a, nullptr, (double*)d_mu.p + h * Bp, 1);
     }
     hipLaunchKernelGGL(k_exp_neg, dim3((unsigned)((H * Bp + 255) / 256)), dim3(256), 0, c->stream, mu, H * Bp, (double*)d_p0.p);
     // Sparse expectations (M = sum mu << B, templates and rates >= 0): event by event -- N ~ Poisson(M), the bins by bisection

@@ -1,4 +1,4 @@
-"""The toy-MC form over several parameter points (bi_eval_datasets_points, csrc/bi_toy_points.h): P hypotheses x T datasets
+"""The toy-MC form over several parameter points (bi_eval_datasets_points, csrc/bi_toys.h): P hypotheses x T datasets
 in one call -- what the reference runs as the double loop of blueice/inference.py:392-443 around blueice/model.py:69-91 --
 against the oracle (1e-10), against P single-point calls (the same sums grouped by other tiles: 1e-13), with points in one grid
 cell and in several, rejected points, two- and four-byte list entries, dataset ranges, results left in HBM, and the
