@@ -76,6 +76,13 @@ SIGNATURES = {
                                        _p, _p, _p, _p]),
     'bi_fit_batched_real': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                       _p, _p, _p, _p]),
+    'bi_factored_begin': (C.c_int, [_p, C.c_int, _p, _p, C.c_int, _i64, _p, _p]),
+    'bi_factored_set_anchor': (C.c_int, [_p, C.c_int, _i64, _p, C.c_double]),
+    'bi_factored_end': (C.c_int, [_p]),
+    'bi_factored_set_counts': (C.c_int, [_p, _i64, _p]),
+    'bi_eval_factored': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_fit_batched_factored': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
+                                          _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
                                     _p, _p, _p, _p]),
     'bi_sample_stretch_gauss': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,

@@ -11,6 +11,7 @@
 //     tu_hess.hip         k_morph_hess (value + gradient + Hessian of one point per item)    bi_k_hess.h
 //     tu_gof.hip          k_morph_gof (deviance + Pearson chi2 of one point per item), k_morph_expect   bi_k_gof.h
 //     tu_real.hip         k_morph_real (half-deviance + gradient against real-valued counts), k_real_expect   bi_k_real.h
+//     tu_factored.hip     k_morph_factored (value + gradient sums of one point of a source-wise model per item)   bi_k_factored.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
@@ -18,7 +19,8 @@
 //     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
-// chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h and bi_k_coarse.h.
+// chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h and
+// bi_k_factored.h.
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 
@@ -94,6 +96,11 @@ void launch_morph_expect(bi_ctx* c, const ExpectArgs& a, int64_t n_items);
 int launch_morph_real(bi_ctx* c, int G, const HessArgs& a, dim3 grid, bool nt);
 // k_real_expect: the expectation of n_items (<= 65 535) truths into rows of the real-valued store
 void launch_real_expect(bi_ctx* c, const RealExpectArgs& a, int64_t n_items);
+// k_morph_factored<SC, EM, GRAD, NT>: value (and the gradient's partial sums) of one point of a source-wise model per item;
+// SC = 2, 4, 8 source slots, EM = 1, 2, 3 own axes at most; BI_ERR_INVALID for another (SC, EM).  factored_slots: its result
+// slots per item
+int launch_morph_factored(bi_ctx* c, int SC, int EM, bool grad, const FactoredArgs& a, dim3 grid, bool nt);
+inline int factored_slots(int SC, int EM, bool grad) { return grad ? 1 + SC * (1 + EM) : 1; }
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -8,6 +8,9 @@ constexpr int kBinsPerThread = 2;       // one 16-byte load per stream per lane
 constexpr int kTile = kThreads * kBinsPerThread;  // 512 bins = 4 KiB per stream per block tile
 constexpr int kMaxDim = 8;              // shape parameters
 constexpr int kMaxG = 16;               // points per cell pass
+constexpr int kFacMaxDim = 32;          // source-wise models (bi_factored.h): shape axes,
+constexpr int kFacMaxSources = 8;       // ... sources,
+constexpr int kFacMaxOwn = 3;           // ... and axes one source responds to
 
 // (the library is several translation units -- one per heavy kernel family, compiled in parallel: types that cross them
 //  sit at global scope, state that must exist once is `inline`)
@@ -124,6 +127,28 @@ struct bi_ctx {
     // `counts`, read by bi_eval_real / bi_fit_batched_real only and released by a new model
     DevBuf real_counts;
     int64_t real_T = 0;
+
+    // the source-wise (factored) model and its counts (bi_factored.h): one anchor grid per source over the axes that source
+    // owns.  A store of its own beside the grid model: model_ready says nothing about it, no other entry point reads it, and
+    // a new grid model leaves it alone.  Released by bi_factored_begin and bi_destroy.
+    struct Factored {
+        bool ready = false, open = false;
+        int d = 0, S = 0;
+        int64_t B = 0, Bp = 0;
+        std::vector<std::vector<double>> grid;       // [d] anchors of every axis, ascending
+        std::vector<int> n_own;                      // [S] e_s
+        std::vector<int> own;                        // [S][kFacMaxOwn] the owned axes, ascending
+        std::vector<int64_t> row_first;              // [S + 1] first row of source s in `ps` / `h_mus` (C order over its own axes)
+        std::vector<int64_t> own_stride;             // [S][kFacMaxOwn] row stride of every owned axis
+        std::vector<double> h_mus;                   // [rows]
+        std::vector<char> row_set;                   // [rows] the anchor has been uploaded
+        DevBuf ps;                                   // [rows][Bp], zero behind B
+        int64_t T = 0;
+        DevBuf counts;                               // [T][Bp], zero behind B
+        std::vector<double> h_lgsum;                 // [T] sum_b lgamma(n_b + 1)
+        int n_rows_point = 0;                        // rows one evaluation reads: sum_s 2^e_s
+        int max_own = 0;                             // largest e_s
+    } fac;
 
     // the coarse binning of bi_set_coarse_binning (bi_coarse.h): tensor-product groups of fine bins, b = r L + x with L the
     // fine bins of the last analysis axis.  Released by a new model.

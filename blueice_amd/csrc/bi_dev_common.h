@@ -136,6 +136,24 @@ struct HessArgs {
     int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (as morph_tiles)
 };
 
+// k_morph_factored (bi_k_factored.h): one point of a source-wise model per item.  The rows of an item are its sources' corner
+// rows back to back, source s contributing 1 << e[s] of them (e[s] < 0: a padded source, no rows); EM is the kernel's
+// template argument, the largest e[s] it is built for.
+struct FactoredArgs {
+    const double* ps;          // [rows][Bp] every source's anchor rows
+    const double* counts;      // [T][Bp]
+    const int64_t* rowoff;     // [items][NR] element offsets of the item's corner rows
+    const double* coef;        // [items][NR][1 + EM] per row: w_c, then d w_c / d (own axis j), zero for j >= e[s]
+    const double* rates;       // [items][SC] r_s = M_s(z) rs_s (zero for padded sources)
+    const int64_t* item_cnt;   // [items] element offset of the item's counts row
+    double* partial;           // [items][nbx][NSL]
+    unsigned* pflags;          // [items][nbx][NSL] (zeroes: k_finish reads them)
+    int n_tiles;               // 512-bin tiles of every row
+    int NR;                    // rows per item
+    int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (ItemTiles)
+    int e[8];                  // own axes of every source
+};
+
 // k_morph_expect (bi_k_gof.h)
 struct ExpectArgs {
     const double* ps;          // [rows][Bp] the dense template tensor

@@ -1,0 +1,434 @@
+// bi_factored.h -- source-wise binned models: one anchor grid per source (host half; the kernel is k_morph_factored,
+// bi_k_factored.h).  bi_factored_begin / _set_anchor / _end, bi_factored_set_counts, bi_eval_factored, bi_fit_batched_factored.
+//
+// The grid model of this library is one tensor product of all d shape axes: a point reads S 2^d rows and the tensor holds
+// prod n_i anchor models.  Here source s has rows over the e_s axes IT owns only, p_s [n_{O_s[0]}] .. [B] in C order, and a
+// point reads sum_s 2^e_s rows; the expectation is mu_b = sum_s r_s tau_s,b with tau_s the multilinear interpolation of source
+// s over its own axes and r_s = M_s(z) rs_s.  That is the per-source interpolation of the reference's
+// source_wise_interpolation, for binned Poisson likelihoods.
+//
+// The store (bi_ctx::fac) lies beside the grid model and is read by nothing else: a context that holds only a source-wise
+// model has model_ready == false, so every other entry point refuses it with its usual BI_ERR_STATE.
+//
+// Limits: d <= 32 axes, S <= 8 sources, e_s <= 3 own axes (a source that responds to more belongs on the full grid).  The
+// geometry arrays here are sized by those, not by kMaxDim (PointGeom).  Out of scope, refused where they can be asked for:
+// sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
+// Beeston-Barlow, unbinned data, device-generated toys (the counts are dense doubles from the caller).
+//
+// bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own: screen, fill on host threads, one
+// packed upload, run_item_chunks + k_finish.  The blocks per item depend on the rows' length alone (not on the batch), so a
+// point's sums are added in the same order whatever batch it is evaluated in.
+#pragma once
+
+namespace {
+
+constexpr int kFacBlocks = 1024;                       // blocks per item at most: one per tile for rows up to 512 K bins
+constexpr int64_t kFacPartialDoubles = (int64_t)1 << 23;   // partial sums in flight per run_item_chunks call (64 MiB)
+
+struct FacGeom {
+    int k[kFacMaxDim];
+    double t[kFacMaxDim], inv_delta[kFacMaxDim];
+};
+
+// the box test of all d axes (owned or not), then cell and fraction per axis: find_cell's convention (bi_geometry.h)
+bool fac_geometry(const bi_ctx::Factored& m, const double* z, FacGeom& g) {
+    for (int i = 0; i < m.d; ++i) {
+        const auto& gr = m.grid[(size_t)i];
+        if (!(gr.front() <= z[i] && z[i] <= gr.back())) return false;
+    }
+    for (int i = 0; i < m.d; ++i) {
+        const auto& gr = m.grid[(size_t)i];
+        find_cell(gr, z[i], g.k[i], g.t[i]);
+        g.inv_delta[i] = gr.size() > 1 ? 1.0 / (gr[(size_t)g.k[i] + 1] - gr[(size_t)g.k[i]]) : 0.0;
+    }
+    return true;
+}
+
+// One source at one point: its corner rows, w_c, d w_c / d (own axis j), the rate M_s(z) and its slopes.  Corner c: bit of
+// the first own axis most significant; w_c the product of t or 1 - t in own-axis order from 1.0; M_s left to right from 0.0
+// (interp_mus); the slopes as PointDerivs forms them.
+struct FacSource {
+    int e, nc;
+    int64_t row[1 << kFacMaxOwn];
+    double w[1 << kFacMaxOwn], dw[1 << kFacMaxOwn][kFacMaxOwn];
+    double M, dM[kFacMaxOwn];
+
+    void at(const bi_ctx::Factored& m, int s, const FacGeom& g, bool slopes) {
+        e = m.n_own[(size_t)s];
+        nc = 1 << e;
+        const int* ax = &m.own[(size_t)s * kFacMaxOwn];
+        const int64_t* st = &m.own_stride[(size_t)s * kFacMaxOwn];
+        int64_t base = m.row_first[(size_t)s];
+        for (int j = 0; j < e; ++j) base += (int64_t)g.k[ax[j]] * st[j];
+        auto factor = [&](int c, int j, bool diff) {
+            const bool up = (c >> (e - 1 - j)) & 1;
+            if (diff) return (up ? 1.0 : -1.0) * g.inv_delta[ax[j]];
+            return up ? g.t[ax[j]] : (1 - g.t[ax[j]]);
+        };
+        for (int c = 0; c < nc; ++c) {
+            int64_t r = base;
+            double wc = 1.0;
+            for (int j = 0; j < e; ++j) {
+                if ((c >> (e - 1 - j)) & 1) r += st[j];
+                wc = wc * factor(c, j, false);
+            }
+            row[c] = r;
+            w[c] = wc;
+            for (int i = 0; slopes && i < e; ++i) {
+                double v = factor(c, i, true);
+                for (int j = 0; j < e; ++j)
+                    if (j != i) v *= factor(c, j, false);
+                dw[c][i] = v;
+            }
+        }
+        double v = 0.0;
+        for (int c = 0; c < nc; ++c) {
+            const double term = m.h_mus[(size_t)row[c]] * w[c];
+            v = v + term;
+        }
+        M = v;
+        for (int i = 0; slopes && i < e; ++i) {
+            double dv = 0.0;
+            for (int c = 0; c < nc; ++c) dv += dw[c][i] * m.h_mus[(size_t)row[c]];
+            dM[i] = dv;
+        }
+    }
+};
+
+// the early exits of one point, in screen_point's order: dataset, anchor box (every axis), rates
+int32_t fac_screen(const bi_ctx::Factored& m, const double* z, const double* rs, int64_t ds, FacGeom& g) {
+    if (ds < 0 || ds >= m.T) return BI_ST_BAD_DATASET;
+    if (!fac_geometry(m, z, g)) return BI_ST_OUT_OF_BOUNDS;
+    const double inf = std::numeric_limits<double>::infinity();
+    FacSource fs;
+    for (int s = 0; s < m.S; ++s) {
+        fs.at(m, s, g, false);
+        const double r = rs ? fs.M * rs[s] : fs.M;
+        if (!(r >= 0 && r < inf)) return BI_ST_UNPHYSICAL;
+    }
+    return 0;
+}
+
+int fac_check(bi_ctx* c, const char* who, bool need_counts) {
+    if (!c) return BI_ERR_INVALID;
+    if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
+    if (!c->fac.ready) return fail(c, BI_ERR_STATE, "%s: no source-wise model uploaded (bi_factored_begin ... bi_factored_end first)", who);
+    if (need_counts && (c->fac.T < 1 || !c->fac.counts.p))
+        return fail(c, BI_ERR_STATE, "%s: no counts uploaded (bi_factored_set_counts first)", who);
+    return BI_OK;
+}
+
+int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
+                  int32_t* status) {
+    const bi_ctx::Factored& m = c->fac;
+    const int d = m.d, S = m.S;
+    const bool want_grad = grad != nullptr;
+    const int SC = S <= 2 ? 2 : S <= 4 ? 4 : 8;
+    const int EM = std::max(1, m.max_own);
+    const int W = 1 + EM, NR = m.n_rows_point, NSL = factored_slots(SC, EM, want_grad);
+    const double inf = std::numeric_limits<double>::infinity();
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    std::vector<int32_t> st((size_t)P);
+    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
+        FacGeom g;
+        for (int64_t p = lo; p < hi; ++p) {
+            ll[p] = -inf;
+            for (int j = 0; want_grad && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
+            st[(size_t)p] = fac_screen(m, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, dataset ? dataset[p] : 0, g);
+        }
+    });
+    std::vector<int64_t> live;
+    live.reserve((size_t)P);
+    for (int64_t p = 0; p < P; ++p) {
+        if (status) status[p] = st[(size_t)p];
+        if (!st[(size_t)p]) live.push_back(p);
+    }
+    const int64_t n_items = (int64_t)live.size();
+    if (n_items == 0) return BI_OK;
+
+    // descriptors of the live points, and what the chain rule needs of them on the host: M_s and its slopes
+    const size_t n = (size_t)n_items;
+    std::vector<int64_t> rowoff(n * NR), cnt_off(n), perm(n * NSL, -1);
+    std::vector<double> coef(n * NR * W, 0.0), rates(n * SC, 0.0), slot_lg(n * NSL, 0.0);
+    std::vector<double> hM(want_grad ? n * S : 0), hdM(want_grad ? n * S * kFacMaxOwn : 0);
+    parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
+        FacGeom g;
+        FacSource fs;
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t p = live[(size_t)i];
+            const int64_t ds = dataset ? dataset[p] : 0;
+            fac_geometry(m, z ? z + p * d : nullptr, g);
+            int k = 0;
+            for (int s = 0; s < S; ++s) {
+                fs.at(m, s, g, want_grad);
+                for (int cnr = 0; cnr < fs.nc; ++cnr, ++k) {
+                    rowoff[(size_t)i * NR + k] = fs.row[cnr] * m.Bp;
+                    double* q = &coef[((size_t)i * NR + k) * W];
+                    q[0] = fs.w[cnr];
+                    for (int j = 0; want_grad && j < fs.e; ++j) q[1 + j] = fs.dw[cnr][j];
+                }
+                rates[(size_t)i * SC + s] = rate_scale ? fs.M * rate_scale[p * S + s] : fs.M;
+                if (want_grad) {
+                    hM[(size_t)i * S + s] = fs.M;
+                    for (int j = 0; j < fs.e; ++j) hdM[((size_t)i * S + s) * kFacMaxOwn + j] = fs.dM[j];
+                }
+            }
+            cnt_off[(size_t)i] = ds * m.Bp;
+            for (int q = 0; q < NSL; ++q) perm[(size_t)i * NSL + q] = i * NSL + q;
+            slot_lg[(size_t)i * NSL] = m.h_lgsum[(size_t)ds];
+        }
+    });
+    PackedUpload pu;
+    int rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
+                               {rates.data(), rates.size() * sizeof(double)}, {cnt_off.data(), cnt_off.size() * sizeof(int64_t)},
+                               {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
+                           n * NSL * sizeof(double), pu);
+    if (rc) return rc;
+
+    FactoredArgs a{};
+    a.ps = (const double*)m.ps.p;
+    a.counts = (const double*)m.counts.p;
+    a.n_tiles = (int)(m.Bp / kTile);
+    a.NR = NR;
+    a.chunks = (int)c->tile_chunks;
+    for (int s = 0; s < 8; ++s) a.e[s] = s < S ? m.n_own[(size_t)s] : -1;
+    const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
+    // the blocks of an item: by the rows' length alone.  Sub-batches keep the partial sums of one run_item_chunks call bounded.
+    const int nbx = std::min(a.n_tiles, kFacBlocks);
+    const int64_t per_call = std::max<int64_t>(1, kFacPartialDoubles / ((int64_t)nbx * NSL));
+    for (int64_t j0 = 0; j0 < n_items; j0 += per_call) {
+        const int64_t nj = std::min(per_call, n_items - j0);
+        rc = run_item_chunks(c, nj, a.n_tiles, NSL, pu.dev<int64_t>(4) + j0 * NSL, pu.dev<double>(5) + j0 * NSL, (double*)pu.host_out(), nullptr,
+                             "bi_eval_factored",
+                             [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
+                                 FactoredArgs b = a;
+                                 const int64_t at = j0 + i0;
+                                 b.rowoff = pu.dev<int64_t>(0) + at * NR;
+                                 b.coef = pu.dev<double>(1) + at * NR * W;
+                                 b.rates = pu.dev<double>(2) + at * SC;
+                                 b.item_cnt = pu.dev<int64_t>(3) + at;
+                                 b.partial = partial;
+                                 b.pflags = pflags;
+                                 const int e = launch_morph_factored(c, SC, EM, want_grad, b, grid, nt);
+                                 return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", SC, EM) : BI_OK;
+                             },
+                             nbx);
+        if (rc) return rc;
+    }
+
+    // the chain rule to [d + S], sources ascending, own axes ascending within a source
+    const double* out = (const double*)pu.host_out();
+    std::vector<double> gz((size_t)std::max(d, 1));
+    for (int64_t i = 0; i < n_items; ++i) {
+        const int64_t p = live[(size_t)i];
+        const double* h = out + (size_t)i * NSL;
+        ll[p] = h[0];
+        if (!want_grad || !std::isfinite(h[0])) continue;
+        double* gp = grad + p * (d + S);
+        std::fill(gz.begin(), gz.end(), 0.0);
+        for (int s = 0; s < S; ++s) {
+            const double M = hM[(size_t)i * S + s], G = h[1 + s];
+            const double rs = rate_scale ? rate_scale[p * S + s] : 1.0;
+            gp[d + s] = M * G;
+            for (int j = 0; j < m.n_own[(size_t)s]; ++j) {
+                const int ax = m.own[(size_t)s * kFacMaxOwn + j];
+                const double U = h[1 + SC + s * EM + j], dM = hdM[((size_t)i * S + s) * kFacMaxOwn + j];
+                gz[(size_t)ax] = gz[(size_t)ax] + rs * (M * U + dM * G);
+            }
+        }
+        for (int i2 = 0; i2 < d; ++i2) gp[i2] = gz[(size_t)i2];
+    }
+    return BI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anchor_z, int S, int64_t B, const int32_t* n_own,
+                      const int32_t* own_axes) {
+    if (!c) return BI_ERR_INVALID;
+    if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
+    if (d < 0 || d > kFacMaxDim) return fail(c, BI_ERR_INVALID, "bi_factored_begin: d=%d outside [0,%d]", d, kFacMaxDim);
+    if (S < 1 || S > kFacMaxSources) return fail(c, BI_ERR_INVALID, "bi_factored_begin: S=%d outside [1,%d]", S, kFacMaxSources);
+    if (B < 1) return fail(c, BI_ERR_INVALID, "bi_factored_begin: B=%lld (at least one bin)", (long long)B);
+    if (d > 0 && (!n_anchor || !anchor_z)) return fail(c, BI_ERR_INVALID, "bi_factored_begin: anchor arrays are NULL");
+    if (!n_own) return fail(c, BI_ERR_INVALID, "bi_factored_begin: n_own is NULL");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    bi_ctx::Factored& m = c->fac;
+    m.ready = m.open = false;
+    dev_free(m.counts);
+    m.T = 0;
+    m.h_lgsum.clear();
+    m.d = d; m.S = S; m.B = B;
+    m.Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
+    m.grid.assign((size_t)d, {});
+    const double* zp = anchor_z;
+    for (int i = 0; i < d; ++i) {
+        if (n_anchor[i] < 1) return fail(c, BI_ERR_INVALID, "bi_factored_begin: axis %d has %d anchors", i, n_anchor[i]);
+        m.grid[(size_t)i].assign(zp, zp + n_anchor[i]);
+        for (int j = 1; j < n_anchor[i]; ++j)
+            if (!(zp[j] > zp[j - 1])) return fail(c, BI_ERR_INVALID, "bi_factored_begin: anchor z values of axis %d are not strictly ascending", i);
+        zp += n_anchor[i];
+    }
+    m.n_own.assign((size_t)S, 0);
+    m.own.assign((size_t)S * kFacMaxOwn, 0);
+    m.own_stride.assign((size_t)S * kFacMaxOwn, 0);
+    m.row_first.assign((size_t)S + 1, 0);
+    m.n_rows_point = 0;
+    m.max_own = 0;
+    const int32_t* op = own_axes;
+    for (int s = 0; s < S; ++s) {
+        const int e = n_own[s];
+        if (e < 0 || e > kFacMaxOwn)
+            return fail(c, BI_ERR_INVALID, "bi_factored_begin: source %d owns %d axes, outside [0,%d] (more belongs on the full grid)", s, e, kFacMaxOwn);
+        if (e > 0 && !own_axes) return fail(c, BI_ERR_INVALID, "bi_factored_begin: own_axes is NULL");
+        int64_t rows = 1;
+        for (int j = 0; j < e; ++j) {
+            const int ax = op[j];
+            if (ax < 0 || ax >= d) return fail(c, BI_ERR_INVALID, "bi_factored_begin: source %d owns axis %d, outside [0,%d)", s, ax, d);
+            if (j > 0 && ax <= op[j - 1]) return fail(c, BI_ERR_INVALID, "bi_factored_begin: the axes of source %d are not strictly ascending", s);
+            if (m.grid[(size_t)ax].size() < 2)
+                return fail(c, BI_ERR_INVALID, "bi_factored_begin: source %d owns axis %d, which has a single anchor", s, ax);
+            m.own[(size_t)s * kFacMaxOwn + j] = ax;
+            rows *= (int64_t)m.grid[(size_t)ax].size();
+        }
+        int64_t stride = 1;
+        for (int j = e - 1; j >= 0; --j) {
+            m.own_stride[(size_t)s * kFacMaxOwn + j] = stride;
+            stride *= (int64_t)m.grid[(size_t)m.own[(size_t)s * kFacMaxOwn + j]].size();
+        }
+        m.n_own[(size_t)s] = e;
+        m.row_first[(size_t)s + 1] = m.row_first[(size_t)s] + rows;
+        m.n_rows_point += 1 << e;
+        m.max_own = std::max(m.max_own, e);
+        op += e;
+    }
+    const int64_t rows = m.row_first[(size_t)S];
+    m.h_mus.assign((size_t)rows, 0.0);
+    m.row_set.assign((size_t)rows, 0);
+    dev_free(m.ps);
+    int rc = dev_alloc(c, m.ps, (size_t)rows * m.Bp * sizeof(double));
+    if (rc) return rc;
+    HIP_TRY(c, hipMemsetAsync(m.ps.p, 0, (size_t)rows * m.Bp * sizeof(double), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    m.open = true;
+    return BI_OK;
+}
+
+int bi_factored_set_anchor(bi_ctx* c, int s, int64_t local_index, const double* ps_row, double mu) {
+    if (!c) return BI_ERR_INVALID;
+    if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
+    bi_ctx::Factored& m = c->fac;
+    if (!m.open) return fail(c, BI_ERR_STATE, "bi_factored_set_anchor: bi_factored_begin first");
+    if (s < 0 || s >= m.S) return fail(c, BI_ERR_INVALID, "bi_factored_set_anchor: source %d outside [0,%d)", s, m.S);
+    const int64_t rows = m.row_first[(size_t)s + 1] - m.row_first[(size_t)s];
+    if (local_index < 0 || local_index >= rows)
+        return fail(c, BI_ERR_INVALID, "bi_factored_set_anchor: anchor %lld of source %d outside [0,%lld)", (long long)local_index, s, (long long)rows);
+    if (!ps_row) return fail(c, BI_ERR_INVALID, "bi_factored_set_anchor: ps_row is NULL");
+    const int64_t r = m.row_first[(size_t)s] + local_index;
+    if (m.row_set[(size_t)r])
+        return fail(c, BI_ERR_INVALID, "bi_factored_set_anchor: anchor %lld of source %d was set before (each anchor exactly once)", (long long)local_index, s);
+    for (int64_t b = 0; b < m.B; ++b)
+        if (!(ps_row[b] >= 0.0 && ps_row[b] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "bi_factored_set_anchor: source %d, anchor %lld, bin %lld holds %g: template entries must be finite and >= 0 "
+                        "(sources that may go negative are out of scope of source-wise models)", s, (long long)local_index, (long long)b, ps_row[b]);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync((double*)m.ps.p + (size_t)r * m.Bp, ps_row, (size_t)m.B * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    // the host buffer is borrowed only for the duration of the call
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    m.h_mus[(size_t)r] = mu;
+    m.row_set[(size_t)r] = 1;
+    return BI_OK;
+}
+
+int bi_factored_end(bi_ctx* c) {
+    if (!c) return BI_ERR_INVALID;
+    if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
+    bi_ctx::Factored& m = c->fac;
+    if (!m.open) return fail(c, BI_ERR_STATE, "bi_factored_end: bi_factored_begin first");
+    for (int s = 0; s < m.S; ++s)
+        for (int64_t r = m.row_first[(size_t)s]; r < m.row_first[(size_t)s + 1]; ++r)
+            if (!m.row_set[(size_t)r])
+                return fail(c, BI_ERR_STATE, "bi_factored_end: anchor %lld of source %d was never set", (long long)(r - m.row_first[(size_t)s]), s);
+    m.open = false;
+    m.ready = true;
+    return BI_OK;
+}
+
+int bi_factored_set_counts(bi_ctx* c, int64_t T, const double* counts) {
+    int rc = fac_check(c, "bi_factored_set_counts", false);
+    if (rc) return rc;
+    bi_ctx::Factored& m = c->fac;
+    if (T < 1 || !counts) return fail(c, BI_ERR_INVALID, "bi_factored_set_counts: T = %lld (at least one dataset) or counts is NULL", (long long)T);
+    const int64_t B = m.B, Bp = m.Bp;
+    for (int64_t t = 0; t < T; ++t)
+        for (int64_t b = 0; b < B; ++b) {
+            const double n = counts[t * B + b];
+            if (!(n >= 0.0 && n < std::numeric_limits<double>::infinity()))
+                return fail(c, BI_ERR_INVALID, "bi_factored_set_counts: dataset %lld, bin %lld holds %g: every count must be finite and >= 0",
+                            (long long)t, (long long)b, n);
+        }
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<double> padded((size_t)(T * Bp), 0.0);
+    for (int64_t t = 0; t < T; ++t) std::copy(counts + t * B, counts + (t + 1) * B, padded.begin() + (size_t)(t * Bp));
+    DevBuf fresh;
+    if ((rc = dev_alloc(c, fresh, padded.size() * sizeof(double)))) return rc;
+    // sum_b lgamma(n + 1) per dataset, once: the kernels of the grid model's counts (finish_counts)
+    const int nblk = (int)std::min<int64_t>(256, (B + kThreads - 1) / kThreads);
+    const int64_t chunk = 32768;
+    ScratchBuf part, lg;
+    std::vector<double> lgsum((size_t)T, 0.0);
+    hipError_t e = hipSuccess;
+    if ((rc = dev_alloc(c, part, (size_t)std::min(T, chunk) * nblk * sizeof(double))) || (rc = dev_alloc(c, lg, (size_t)T * sizeof(double)))) {
+        dev_free(fresh);
+        return rc;
+    }
+    e = hipMemcpyAsync(fresh.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    for (int64_t t0 = 0; t0 < T && e == hipSuccess; t0 += chunk) {
+        const int64_t nt = std::min(chunk, T - t0);
+        hipLaunchKernelGGL(k_counts_lgamma, dim3(nblk, (unsigned)nt), dim3(kThreads), 0, c->stream, (const double*)fresh.p + t0 * Bp, B, Bp,
+                           (double*)part.p, nblk);
+        hipLaunchKernelGGL(k_rows_sum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, (const double*)part.p, nblk,
+                           (double*)lg.p + t0, nt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(lgsum.data(), lg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        dev_free(fresh);
+        return fail(c, BI_ERR_HIP, "bi_factored_set_counts: %s", hipGetErrorString(e));
+    }
+    dev_free(m.counts);
+    m.counts = fresh;
+    m.T = T;
+    m.h_lgsum.swap(lgsum);
+    return BI_OK;
+}
+
+int bi_eval_factored(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
+                     int32_t* status) {
+    int rc = fac_check(c, "bi_eval_factored", true);
+    if (rc) return rc;
+    if (P < 0 || (P > 0 && !ll)) return fail(c, BI_ERR_INVALID, "bi_eval_factored: bad P / output pointer");
+    if (c->fac.d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "bi_eval_factored: z is NULL");
+    if (P == 0) return BI_OK;
+    return factored_eval(c, P, z, rate_scale, dataset, ll, grad, status);
+}
+
+int bi_fit_batched_factored(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                            const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                            const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
+                            const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
+                            double* f_out, int32_t* flags_out, int64_t* counters) {
+    int rc = fac_check(c, "bi_fit_batched_factored", true);
+    if (rc) return rc;
+    return fit_batched(c, "bi_fit_batched_factored", kFitFactored, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks,
+                       gtol, max_iter, prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);
+}
+
+}  // extern "C"

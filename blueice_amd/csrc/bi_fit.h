@@ -13,6 +13,7 @@
 //                         variable j is a shape parameter (z_i = x_j) or a rate multiplier (rate_scale_s = x_j * unit_s)
 //   bi_fit_batched_gauss  ... plus Gaussian constraint terms on the optimiser variables: f = -(ll + p)
 //   bi_fit_batched_real   (bi_real.h) ... against a real-valued dataset: f = half_deviance - p
+//   bi_fit_batched_factored   (bi_factored.h) ... with a source-wise model's likelihood (bi_eval_factored) as the objective
 #pragma once
 
 #include <new>
@@ -371,14 +372,19 @@ int minimize_batched(bi_objective_fn fun, void* user, int64_t P, int F, const do
     return BI_OK;
 }
 
+// which evaluation the objective stands on: the grid model's likelihood (bi_eval_grad), the real-valued store's half-deviance
+// (bi_eval_real, bi_real.h: ll stands for -half_deviance) or the source-wise model's likelihood (bi_eval_factored, bi_factored.h)
+enum FitEval { kFitLikelihood = 0, kFitReal = 1, kFitFactored = 2 };
+
 // the device likelihood as the objective: f = -(ll + p), g = -d (ll + p) / d x, p the Gaussian constraint terms (none: p = 0)
 struct DeviceObjective {
     bi_ctx* c;
+    FitEval eval = kFitLikelihood;
+    int d = 0, S = 0;           // shape axes and sources of the model `eval` reads (the grid model's, or the source-wise one's)
     VarMap m;                   // host pointers; one entry per problem; unit is d rate_scale / d multiplier (live time, efficiency)
     const double* prior_mean;   // [F]      Gaussian constraint on variable j (all three NULL: no terms) ...
     const double* prior_sigma;  // [F]      ... +inf: none on that variable
     const double* prior_const;  // [P] or NULL: what of p does not depend on x
-    bool real = false;          // the data are the real-valued store's (bi_fit_batched_real, bi_real.h): ll stands for -half_deviance (bi_eval_real)
     std::vector<double> z, sc, ll, grad;
     std::vector<int64_t> ds;
     std::vector<int32_t> st;
@@ -388,7 +394,7 @@ struct DeviceObjective {
 int device_objective(void* user, int64_t n, int F, const double* x, const int64_t* rows, double* f, double* g) {
     DeviceObjective* o = (DeviceObjective*)user;
     bi_ctx* c = o->c;
-    const int d = c->d, S = c->S;
+    const int d = o->d, S = o->S;
     o->z.resize((size_t)n * std::max(d, 1));
     o->sc.resize((size_t)n * S);
     o->ll.resize((size_t)n);
@@ -399,10 +405,10 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
     m.z_dev = o->z.data(); m.rs_dev = o->sc.data(); m.ds_dev = o->ds.data();
     for (int64_t i = 0; i < n; ++i) varmap_write_point(m, i, rows[i], [&](int j) { return x[i * F + j]; });
     o->evaluations += n;
-    const int rc = (o->real ? bi_eval_real : bi_eval_grad)(c, n, d ? o->z.data() : nullptr, o->sc.data(), m.dataset ? o->ds.data() : nullptr,
-                                                           o->ll.data(), o->grad.data(), o->st.data());
+    const auto eval = o->eval == kFitReal ? bi_eval_real : o->eval == kFitFactored ? bi_eval_factored : bi_eval_grad;
+    const int rc = eval(c, n, d ? o->z.data() : nullptr, o->sc.data(), m.dataset ? o->ds.data() : nullptr, o->ll.data(), o->grad.data(), o->st.data());
     if (rc) return rc;
-    if (o->real) {
+    if (o->eval == kFitReal) {
         for (double& v : o->ll) v = -v;
         for (double& v : o->grad) v = -v;
     }
@@ -474,29 +480,34 @@ bool gauss_terms_empty(int F, const double* sigma, const double* konst) {
     return true;
 }
 
-// bi_fit_batched (no terms: the three prior arrays NULL), bi_fit_batched_gauss and, real: against the real-valued store,
-// bi_fit_batched_real (bi_real.h).  That one's terms are optional and its datasets the store's: both are checked here, behind
-// the checks the three share, so that a call with several defects is refused for the first of them in this order
-int fit_batched(bi_ctx* c, const char* who, bool real, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+// bi_fit_batched (no terms: the three prior arrays NULL), bi_fit_batched_gauss and, by `eval`, bi_fit_batched_real (bi_real.h:
+// against the real-valued store) and bi_fit_batched_factored (bi_factored.h: a source-wise model; its entry point has checked
+// that model and its counts).  Those two's terms are optional and their datasets their own store's: both are checked here,
+// behind the checks all share, so that a call with several defects is refused for the first of them in this order
+int fit_batched(bi_ctx* c, const char* who, FitEval eval, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                 const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
                 const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, const double* prior_mean, const double* prior_sigma,
                 const double* prior_const, double* x_out, double* f_out, int32_t* flags_out, int64_t* counters) {
-    int rc = check_ready(c, !real);
+    const bool real = eval == kFitReal, factored = eval == kFitFactored;
+    // (check_ready holds the NULL-context test: nothing of c is read before it; the source-wise entry point has made its own)
+    int rc = factored ? (c ? BI_OK : BI_ERR_INVALID) : check_ready(c, !real);
     if (rc) return rc;
-    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !x0 || !lo || !hi || !x_out ||
+    const int d = factored ? c->fac.d : c->d, S = factored ? c->fac.S : c->S;
+    if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64 || !var_kind || !var_index || !scale0 || !unit || (d > 0 && !z0) || !x0 || !lo || !hi || !x_out ||
         !f_out || !flags_out)
         return fail(c, BI_ERR_INVALID, "%s: bad arguments", who);
-    if ((rc = check_var_map(c, who, F, var_kind, var_index))) return rc;
+    if ((rc = check_var_map(c, who, F, var_kind, var_index, d, S))) return rc;
     if (!kinks_are_valid(F, n_kinks, kinks)) return fail(c, BI_ERR_INVALID, "%s: n_kinks must be >= 0 and the kinks of a variable ascending", who);
-    if (real && (prior_mean || prior_sigma || prior_const)) {
+    if ((real || factored) && (prior_mean || prior_sigma || prior_const)) {
         if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "%s: %s", who, why);
         if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
     }
     if (real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->real_T))) return rc;
+    if (factored && (rc = check_entry_datasets(c, who, "problem", P, dataset, c->fac.T))) return rc;
     if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
     DeviceObjective o{};
-    o.c = c; o.real = real;
-    o.m.F = F; o.m.d = c->d; o.m.S = c->S;
+    o.c = c; o.eval = eval; o.d = d; o.S = S;
+    o.m.F = F; o.m.d = d; o.m.S = S;
     o.m.var_kind = var_kind; o.m.var_index = var_index; o.m.z0 = z0; o.m.scale0 = scale0; o.m.unit = unit; o.m.dataset = dataset;
     o.prior_mean = prior_mean; o.prior_sigma = prior_sigma; o.prior_const = prior_const;
     try {
@@ -534,7 +545,7 @@ int bi_fit_batched(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, const i
                    const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                    const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, double* x_out,
                    double* f_out, int32_t* flags_out, int64_t* counters) {
-    return fit_batched(c, "bi_fit_batched", false, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+    return fit_batched(c, "bi_fit_batched", kFitLikelihood, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
                        nullptr, nullptr, nullptr, x_out, f_out, flags_out, counters);
 }
 
@@ -548,7 +559,7 @@ int bi_fit_batched_gauss(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, c
     if (P < 0 || P > kFitMaxProblems || F < 1 || F > 64) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: bad arguments");
     if (const char* why = gauss_terms_invalid(F, P, prior_mean, prior_sigma, prior_const)) return fail(c, BI_ERR_INVALID, "bi_fit_batched_gauss: %s", why);
     if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
-    return fit_batched(c, "bi_fit_batched", false, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+    return fit_batched(c, "bi_fit_batched", kFitLikelihood, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
                        prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);
 }
 

@@ -186,12 +186,14 @@ struct PointDerivs {
 // about four blocks per CU slot in all).  Per chunk of at most 65 535 items (gridDim.y), launch(i0, grid, partial, pflags)
 // points its kernel's arguments at items i0 ... and launches it on the grid; the kernel assigns every (item, block, slot)
 // of partial / pflags, so the chunks, in order on one stream, share one chunk's buffers.  k_finish then adds the partials up
-// into out[perm] - slot_lg (status |= their flag bits when given).  Synchronises the stream.
+// into out[perm] - slot_lg (status |= their flag bits when given).  Synchronises the stream.  fixed_nbx > 0: that many blocks
+// per item whatever the batch (the order in which an item's sums are added then does not depend on n_items).
 template <class L>
 int run_item_chunks(bi_ctx* c, int64_t n_items, int max_tiles, int nsl, const int64_t* perm, const double* slot_lg, double* out,
-                    int32_t* status, const char* what, L launch) {
+                    int32_t* status, const char* what, L launch, int fixed_nbx = 0) {
     const int64_t slots = (int64_t)c->prop.multiProcessorCount * c->blocks_per_cu;
-    const int nbx = (int)std::min<int64_t>(max_tiles, n_items == 1 ? slots : std::max<int64_t>(1, (4 * slots + n_items - 1) / n_items));
+    const int nbx = fixed_nbx > 0 ? fixed_nbx
+                                  : (int)std::min<int64_t>(max_tiles, n_items == 1 ? slots : std::max<int64_t>(1, (4 * slots + n_items - 1) / n_items));
     const int64_t chunk = 65535, part_items = std::min(chunk, n_items);
     ScratchBuf d_part, d_flag;
     int rc;

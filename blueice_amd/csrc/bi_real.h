@@ -208,7 +208,7 @@ int bi_fit_batched_real(bi_ctx* c, int64_t P, int F, const int32_t* var_kind, co
                         double* f_out, int32_t* flags_out, int64_t* counters) {
     int rc = real_check(c, "bi_fit_batched_real", true);
     if (rc) return rc;
-    return fit_batched(c, "bi_fit_batched_real", true, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
+    return fit_batched(c, "bi_fit_batched_real", kFitReal, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter,
                        prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);
 }
 

@@ -11,9 +11,12 @@ std::vector<T> host_copy(const T* p, size_t n, T fill) {
     return p ? std::vector<T>(p, p + n) : std::vector<T>(n, fill);
 }
 
-// variable j is a shape parameter or a rate multiplier of this model (distinct: and none of the variables before it)
-int check_variable(bi_ctx* c, const char* who, int j, const int32_t* var_kind, const int32_t* var_index, bool distinct) {
-    if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= c->d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= c->S)) ||
+// variable j is a shape parameter or a rate multiplier of this model (distinct: and none of the variables before it); d, S:
+// the model's axes and sources (< 0: the grid model's; the source-wise model has its own, bi_factored.h)
+int check_variable(bi_ctx* c, const char* who, int j, const int32_t* var_kind, const int32_t* var_index, bool distinct, int d = -1, int S = -1) {
+    if (d < 0) d = c->d;
+    if (S < 0) S = c->S;
+    if ((var_kind[j] == 0 && (var_index[j] < 0 || var_index[j] >= d)) || (var_kind[j] == 1 && (var_index[j] < 0 || var_index[j] >= S)) ||
         (var_kind[j] != 0 && var_kind[j] != 1))
         return fail(c, BI_ERR_INVALID, "%s: variable %d is neither a shape parameter nor a rate multiplier of this model", who, j);
     for (int i = 0; distinct && i < j; ++i)
@@ -22,9 +25,9 @@ int check_variable(bi_ctx* c, const char* who, int j, const int32_t* var_kind, c
     return BI_OK;
 }
 
-int check_var_map(bi_ctx* c, const char* who, int F, const int32_t* var_kind, const int32_t* var_index) {
+int check_var_map(bi_ctx* c, const char* who, int F, const int32_t* var_kind, const int32_t* var_index, int d = -1, int S = -1) {
     int rc = BI_OK;
-    for (int j = 0; j < F && !rc; ++j) rc = check_variable(c, who, j, var_kind, var_index, false);
+    for (int j = 0; j < F && !rc; ++j) rc = check_variable(c, who, j, var_kind, var_index, false, d, S);
     return rc;
 }
 

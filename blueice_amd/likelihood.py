@@ -184,13 +184,11 @@ class LogLikelihoodBase:
             full[i] = z
         return tuple(full)
 
-    def _prepare_source_wise(self, build_all):
-        """Models only at the anchors some source needs (a setting no source of the model reads at that anchor stays at
-        its base value), then per full-grid anchor a view that takes every source from the model built at ITS
-        projection of the anchor.  The device tensor stays the full Cartesian grid: interpolating a source over an
-        axis it does not respond to returns its value unchanged (the weights along that axis sum to one), so the
-        result is the reference's per-source interpolation (likelihood.py:152-171,210-240,534-563) and the kernels
-        do not change; the reduced set of models is what the user's sources see built."""
+    def _build_source_anchors(self, build_all):
+        """The first half of source-wise preparation: models only at the anchors some source needs (a setting no source
+        of the model reads at that anchor stays at its base value), and per source the Source object at each of ITS
+        anchors (self.source_morphers, self.anchor_sources: source name -> own z tuple -> Source).  The product grid is
+        not touched."""
         own_params = self.source_shape_parameters
         own_morphers = OrderedDict((name, MORPHERS[self.config['morpher']](self.config.get('morpher_config', {}), sp))
                                    for name, sp in own_params.items())
@@ -208,6 +206,17 @@ class LogLikelihoodBase:
             self.anchor_sources[name] = OrderedDict(
                 (tuple(anchor), built[self._get_model_anchor(tuple(anchor), name)].sources[i])
                 for anchor in morpher.get_anchor_points(bounds=None))
+
+    def _prepare_source_wise(self, build_all):
+        """Models only at the anchors some source needs (`_build_source_anchors`), then per full-grid anchor a view that
+        takes every source from the model built at ITS projection of the anchor.  The device tensor stays the full
+        Cartesian grid: interpolating a source over an axis it does not respond to returns its value unchanged (the
+        weights along that axis sum to one), so the result is the reference's per-source interpolation
+        (likelihood.py:152-171,210-240,534-563) and the kernels do not change; the reduced set of models is what the
+        user's sources see built.  (source_wise.SourceWiseBinnedLogLikelihood keeps one grid per source on the device
+        instead, for binned likelihoods.)"""
+        self._build_source_anchors(build_all)
+        own_params = self.source_shape_parameters
         for zs in (tuple(z) for z in self.morpher.get_anchor_points(bounds=self.get_bounds())):
             sources = []
             for i, name in enumerate(self.source_name_list):
@@ -218,6 +227,25 @@ class LogLikelihoodBase:
             self.anchor_models[zs] = _SourceWiseModel(self.base_model, sources)
 
     # -- anchor models ---------------------------------------------------------------------
+    def _anchor_model_builder(self, n_cores=1):
+        """-> build_all(points): the Models at a list of z tuples, in that order (None in a tuple: no source built there
+        reads this setting, it stays at its base value); n_cores > 1: on a pool of threads."""
+        def build(zs):
+            conf = deepcopy(self.pdf_base_config)
+            for z, (name, (anchors, _, _)) in zip(zs, self.shape_parameters.items()):
+                if z is not None:                      # None: no source built here reads this setting
+                    conf[name] = anchors[z]
+            return Model(conf)
+
+        def build_all(points):
+            with self._template_building():
+                if n_cores and n_cores > 1 and len(points) > 1:
+                    from concurrent.futures import ThreadPoolExecutor
+                    with ThreadPoolExecutor(max_workers=int(n_cores)) as pool:
+                        return list(pool.map(build, points))
+                return [build(zs) for zs in points]
+        return build_all
+
     def prepare(self, n_cores=1, ipp_client=None):
         """Compute the model at every anchor point.  n_cores > 1 builds the anchor models on a pool of THREADS
         (numpy-heavy sources release the interpreter lock while they histogram / sample); the reference's
@@ -227,22 +255,7 @@ class LogLikelihoodBase:
         if len(self.shape_parameters):
             self.morpher = MORPHERS[self.config['morpher']](self.config.get('morpher_config', {}),
                                                             self.shape_parameters)
-
-            def build(zs):
-                conf = deepcopy(self.pdf_base_config)
-                for z, (name, (anchors, _, _)) in zip(zs, self.shape_parameters.items()):
-                    if z is not None:                      # None: no source built here reads this setting
-                        conf[name] = anchors[z]
-                return Model(conf)
-
-            def build_all(points):
-                with self._template_building():
-                    if n_cores and n_cores > 1 and len(points) > 1:
-                        from concurrent.futures import ThreadPoolExecutor
-                        with ThreadPoolExecutor(max_workers=int(n_cores)) as pool:
-                            return list(pool.map(build, points))
-                    return [build(zs) for zs in points]
-
+            build_all = self._anchor_model_builder(n_cores)
             if self.source_wise_interpolation:
                 self._prepare_source_wise(build_all)
             else:

@@ -1,0 +1,299 @@
+"""Source-wise binned likelihoods on the device: one anchor grid per source.
+
+    lf = SourceWiseBinnedLogLikelihood(pdf_base_config, likelihood_config=None, **overrides)
+    lf.add_rate_parameter(...); lf.add_shape_parameter(...); lf.prepare(); lf.set_data(d)
+    lf(**params), lf.eval_points, lf.value_and_gradient, lf.values_and_gradients,
+    lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval
+
+`BinnedLogLikelihood` morphs over ONE tensor-product grid of all shape parameters: prod n_i anchor models in HBM and S 2^d
+rows per evaluation, which caps the number of shape parameters at a handful.  Here every source morphs over the parameters
+IT responds to only (`source_shape_parameters`: all of them except the settings its config lists under dont_hash_settings --
+the reference's `source_wise_interpolation`, which the reference and `BinnedLogLikelihood` refuse for binned likelihoods):
+source s keeps prod_{i in O_s} n_i rows, and an evaluation reads sum_s 2^e_s of them (libblueice_hip's bi_factored_* /
+bi_eval_factored / bi_fit_batched_factored, include/blueice_hip.h).  `prepare()` builds models only at the anchors some source
+needs and never enumerates the product grid.
+
+Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
+full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
+full_output calls, toys, Hessians and hesse, goodness of fit, Asimov data, Fisher information, grids, coarse views and the
+ensemble sampler.
+"""
+from collections import OrderedDict
+
+import numpy as np
+
+from ._capi import as_f64, ptr
+from .device import DeviceContext
+from .histdd import Histdd, device_histograms
+from .likelihood import DeviceLogLikelihood, LogLikelihoodBase, _needs_data, _needs_preparation
+
+__all__ = ['SourceWiseBinnedLogLikelihood', 'SourceWiseContext', 'MAX_SHAPE_PARAMETERS', 'MAX_SOURCES', 'MAX_OWN_PARAMETERS']
+
+MAX_SHAPE_PARAMETERS, MAX_SOURCES, MAX_OWN_PARAMETERS = 32, 8, 3
+
+
+def _find_cell(g, z):
+    """scipy's find_indices on one axis, the last cell closed -> (k, t)"""
+    n = len(g)
+    if z == g[n - 1]:
+        k = n - 2
+    else:
+        k = min(max(int(np.searchsorted(g, z, side='right')) - 1, 0), n - 2)
+    return k, (z - g[k]) / (g[k + 1] - g[k])
+
+
+class SourceWiseContext:
+    """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
+    a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
+    eval_grad, fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the DeviceContext (plans, toys,
+    Hessians, the sampler ...) has a meaning here and is an AttributeError."""
+
+    def __init__(self, device=None):
+        self._dev = DeviceContext(device)
+        self.device = self._dev.device
+        self.d = self.S = self.B = None
+        self.T = 0
+
+    def close(self):
+        self._dev.close()
+
+    def info(self):
+        return self._dev.info()
+
+    def histogram_events(self, edges, coords):
+        return self._dev.histogram_events(edges, coords)
+
+    # -- model -----------------------------------------------------------------------------
+    def begin_model(self, anchor_z, S, B, own_axes):
+        """anchor_z: d ascending arrays; own_axes: per source the ascending indices of the axes it owns"""
+        dev = self._dev
+        anchor_z, n_anchor, flat = dev._grid_args(anchor_z)
+        own_axes = [tuple(int(i) for i in own) for own in own_axes]
+        n_own = np.array([len(own) for own in own_axes], dtype=np.int32)
+        own_flat = np.array([i for own in own_axes for i in own], dtype=np.int32)
+        dev._check(dev._lib.bi_factored_begin(dev._h, len(anchor_z), ptr(n_anchor), ptr(flat), int(S), int(B), ptr(n_own),
+                                              ptr(own_flat) if len(own_flat) else None))
+        self.d, self.S, self.B = len(anchor_z), int(S), int(B)
+        self.anchor_z, self.own_axes = anchor_z, own_axes
+        self.mus = [np.zeros(tuple(len(anchor_z[i]) for i in own)) for own in own_axes]      # host copy of the rates
+        self.T = 0
+
+    def set_anchor(self, s, local_index, ps_row, mu):
+        dev = self._dev
+        ps_row = as_f64(ps_row).reshape(self.B)
+        dev._check(dev._lib.bi_factored_set_anchor(dev._h, int(s), int(local_index), ptr(ps_row), float(mu)))
+        self.mus[s].reshape(-1)[int(local_index)] = float(mu)
+
+    def end_model(self):
+        self._dev._check(self._dev._lib.bi_factored_end(self._dev._h))
+
+    def set_counts(self, counts):
+        """counts: [*bins] (one dataset) or [T, *bins]"""
+        dev = self._dev
+        c = as_f64(counts)
+        if c.size == 0 or c.size % self.B:
+            raise ValueError("counts size %d is not a positive multiple of B=%d" % (c.size, self.B))
+        T = c.size // self.B
+        c = c.reshape(T, self.B)
+        dev._check(dev._lib.bi_factored_set_counts(dev._h, T, ptr(c)))
+        self._counts = c.copy()
+        self.T = T
+
+    def download_counts(self, t=0):
+        return self._counts[int(t)].copy()
+
+    # -- evaluation ------------------------------------------------------------------------
+    def _point_args(self, z, rate_scale, dataset):
+        if self.d:
+            z = as_f64(z).reshape(-1, self.d)
+            P = len(z)
+        else:
+            P = 1 if rate_scale is None else len(np.atleast_2d(rate_scale))
+            z = None
+        if rate_scale is not None:
+            rate_scale = np.ascontiguousarray(np.broadcast_to(as_f64(np.atleast_2d(rate_scale)), (P, self.S)))
+        if dataset is not None:
+            dataset = np.ascontiguousarray(np.broadcast_to(np.asarray(dataset, dtype=np.int64), (P,)))
+        return P, z, rate_scale, dataset
+
+    def eval(self, z, rate_scale=None, dataset=None):
+        """-> (ll [P], status [P])"""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        ll = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_factored(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), None, ptr(status)))
+        return ll, status
+
+    def eval_grad(self, z, rate_scale=None, dataset=None):
+        """-> (ll [P], dll/dz [P, d], dll/drate_scale [P, S], status [P])"""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        ll = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, self.d + self.S), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_factored(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(status)))
+        return ll, grad[:, :self.d], grad[:, self.d:], status
+
+    def fit_batched(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters,
+                    priors=None):
+        """bi_fit_batched_factored: DeviceContext.fit_batched with the source-wise likelihood as the objective"""
+        dev = self._dev
+        mean = sigma = const = None
+        if priors is not None:
+            mean, sigma, const = dev._gauss_terms(priors, int(F), int(P))
+        dev._check(dev._lib.bi_fit_batched_factored(dev._h, int(P), int(F), ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
+                                                    ptr(unit), ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks), ptr(kinks), float(gtol),
+                                                    int(max_iter), ptr(mean), ptr(sigma), ptr(const), ptr(x), ptr(f), ptr(flags), ptr(counters)))
+        return 0
+
+    def interpolate(self, which, z):
+        """'mus': the interpolated rates [S] at z [d], from the host copy of the anchors' rates"""
+        if which != 'mus':
+            raise NotImplementedError("a source-wise model interpolates 'mus' only (the morphed templates are never materialised)")
+        z = np.asarray(z, dtype=float).reshape(self.d)
+        out = np.zeros(self.S)
+        for s, own in enumerate(self.own_axes):
+            cells = [_find_cell(self.anchor_z[i], z[i]) for i in own]
+            v = 0.0
+            for c in range(1 << len(own)):
+                w, idx = 1.0, []
+                for j, (k, t) in enumerate(cells):
+                    up = (c >> (len(own) - 1 - j)) & 1
+                    idx.append(k + up)
+                    w = w * (t if up else 1 - t)
+                v = v + self.mus[s][tuple(idx)] * w
+            out[s] = v
+        return out
+
+
+def _refused(name):
+    def method(self, *args, **kwargs):
+        raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient and "
+                                  "the fit, scan and interval layers are" % name)
+    method.__name__ = name
+    return method
+
+
+class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
+    """Binned Poisson likelihood whose sources each morph over their own shape parameters (see the module's docstring)."""
+
+    _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'toy_test_statistics', 'neyman_thresholds', 'expected_counts',
+                'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
+                'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance', 'fisher_information_points',
+                'fisher_information', 'expected_covariance', 'expected_errors', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
+                'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'simulate_toys_points', 'eval_toys', 'eval_toys_points',
+                'value_gradient_hessian', 'values_gradients_hessians', 'ps_interpolator', 'n_model_events_interpolator')
+
+    supports_gradient = True
+    supports_hessian = False
+
+    def __init__(self, pdf_base_config, likelihood_config=None, **kwargs):
+        super().__init__(pdf_base_config, likelihood_config, **kwargs)
+        self.source_wise_interpolation = True
+        if self.config.get('model_statistical_uncertainty_handling') is not None:
+            raise NotImplementedError("Beeston-Barlow (model_statistical_uncertainty_handling) is not available for a source-wise model")
+        self._binned = None
+
+    def _context(self):
+        if self.ctx is None:
+            self.ctx = SourceWiseContext(self.config.get('device'))
+        return self.ctx
+
+    def _template_building(self):
+        from contextlib import nullcontext
+        if not self.config.get('device_histograms', True):
+            return nullcontext()
+        return device_histograms(self._context(), self.config.get('device_histograms_min_events', 32768))
+
+    # -- lifecycle -------------------------------------------------------------------------
+    def prepare(self, n_cores=1, ipp_client=None):
+        """Models at the anchors some source needs only (one per distinct projection of a source's own anchors), then every
+        source's rows streamed to the device from there.  The product grid of all shape parameters is never enumerated."""
+        names = list(self.shape_parameters)
+        own_params = self.source_shape_parameters
+        if any(self.source_allowed_negative):
+            raise NotImplementedError("sources that may go negative (allow_negative) are not available for a source-wise model")
+        if len(names) > MAX_SHAPE_PARAMETERS or len(self.source_name_list) > MAX_SOURCES:
+            raise ValueError("a source-wise model takes at most %d shape parameters and %d sources (got %d and %d)"
+                             % (MAX_SHAPE_PARAMETERS, MAX_SOURCES, len(names), len(self.source_name_list)))
+        for name, own in own_params.items():
+            if len(own) > MAX_OWN_PARAMETERS:
+                raise ValueError("source %s responds to %d shape parameters (%s); a source-wise model takes at most %d per source: a source "
+                                 "that responds to more belongs on the full grid (BinnedLogLikelihood)"
+                                 % (name, len(own), ', '.join(own), MAX_OWN_PARAMETERS))
+        self.anchor_models = OrderedDict()
+        self.morpher = None
+        self.anchor_sources = OrderedDict()
+        if own_params:
+            self._build_source_anchors(self._anchor_model_builder(n_cores))
+        self.ps, self.n_model_events = self.base_model.pmf_grids()
+        self.bin_shape = self.ps.shape[1:]
+        n_bins = int(np.prod(self.bin_shape, dtype=np.int64))
+        anchor_z = [np.array(sorted(anchors.keys()), dtype=float) for anchors, _, _ in self.shape_parameters.values()]
+        own_axes = [tuple(names.index(k) for k in own_params.get(name, ())) for name in self.source_name_list]
+        ctx = self._context()
+        ctx.begin_model(anchor_z, len(self.source_name_list), n_bins, own_axes)
+        for s, name in enumerate(self.source_name_list):
+            if name in own_params:
+                # (the source's own morpher lists its anchors in C order over its own parameters, each ascending)
+                for local, source in enumerate(self.anchor_sources[name].values()):
+                    ctx.set_anchor(s, local, source.get_pmf_grid()[0], source.expected_events)
+            else:
+                source = self.base_model.sources[s]
+                ctx.set_anchor(s, 0, source.get_pmf_grid()[0], source.expected_events)
+        ctx.end_model()
+        self._binned = None
+        self.is_data_set = False
+        self.is_prepared = True
+
+    @_needs_preparation
+    def set_data(self, d):
+        """Bin the events of `d` in the analysis space on the device (numpy.histogramdd semantics) and make the counts
+        dataset 0."""
+        LogLikelihoodBase.set_data(self, d)
+        edges = [e for _, e in self.base_model.config['analysis_space']]
+        self.ctx.set_counts(self.ctx.histogram_events(edges, self.base_model.to_analysis_dimensions(d)))
+        self._binned = None
+
+    @_needs_preparation
+    def set_binned_data(self, counts):
+        """Upload already-binned counts: [*bins] or [T, *bins] for T datasets.  Dataset 0 is what plain `lf(**params)`
+        evaluates."""
+        counts = np.asarray(counts, dtype=float)
+        if counts.shape[-len(self.bin_shape):] != tuple(self.bin_shape):
+            raise ValueError("counts must end in the analysis-space shape %s" % (tuple(self.bin_shape),))
+        self._data = None
+        self.ctx.set_counts(counts)
+        self._binned = None
+        self.is_data_set = True
+
+    @property
+    def data_events_per_bin(self):
+        if self._binned is None:
+            names, edges = zip(*self.base_model.config['analysis_space'])
+            self._binned = Histdd(bins=edges, axis_names=names)
+            self._binned.histogram = self.ctx.download_counts(0).reshape(self.bin_shape)
+        return self._binned
+
+    # -- evaluation ------------------------------------------------------------------------
+    @_needs_data
+    def __call__(self, livetime_days=None, compute_pdf=False, full_output=False, **kwargs):
+        if compute_pdf or full_output:
+            raise NotImplementedError("a source-wise model (SourceWiseBinnedLogLikelihood) evaluates the morphed model only: no "
+                                      "compute_pdf=True / full_output=True")
+        prior, zs, scale = self._host_terms(livetime_days, kwargs)
+        if prior is None:
+            return -float('inf')
+        ll, st = self.ctx.eval(zs if len(zs) else None, scale[None, :])
+        return self._finish_call(prior, zs, scale, float(ll[0]), int(st[0]))
+
+    def _call_begin(self, livetime_days=None, **kwargs):
+        return self(livetime_days=livetime_days, **kwargs)
+
+    def _call_end(self, token):
+        return token
+
+
+for _name in SourceWiseBinnedLogLikelihood._REFUSED:
+    setattr(SourceWiseBinnedLogLikelihood, _name, _refused(_name))

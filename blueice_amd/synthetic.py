@@ -15,7 +15,7 @@ import numpy as np
 
 from .source import Source
 
-__all__ = ['SyntheticModel', 'CONFIGS', 'TemplateSource']
+__all__ = ['SyntheticModel', 'CONFIGS', 'TemplateSource', 'NuisanceBlobSource', 'many_nuisances_config']
 
 _MU_SLOPES = (0.02, -0.01, 0.005, 0.0025, -0.00125, 0.0006, 0.0003, 0.0001)
 
@@ -269,3 +269,54 @@ def _likelihood(self, likelihood_config=None, device=0, **kwargs):
 
 SyntheticModel.anchor_ps_cached = _anchor_ps_cached
 SyntheticModel.likelihood = _likelihood
+
+
+# -- a model with many nuisance parameters, each moving one source (source_wise.SourceWiseBinnedLogLikelihood) ---------
+
+class NuisanceBlobSource(Source):
+    """A Gaussian blob in a two-dimensional analysis space (x, y) whose position, width and rate respond to the settings
+    named in config['own_settings'] (one or two of them) and to nothing else: the closed-form stand-in for a source with
+    its own nuisance parameters.  The PMF is the blob integrated over every bin."""
+
+    def _moments(self):
+        c = self.config
+        z = [float(c[name]) for name in c['own_settings']] + [0.0, 0.0]
+        cx, cy = c['centre']
+        return (cx + 0.04 * z[0], cy + 0.03 * z[1]), (c['width'] * (1 + 0.08 * z[1]), c['width'] * (1 - 0.05 * z[0]))
+
+    def compute_pdf(self):
+        z = [float(self.config[name]) for name in self.config['own_settings']] + [0.0, 0.0]
+        self.events_per_day = self.config['events_per_day'] * (1 + 0.03 * z[0] - 0.02 * z[1])      # (from the config's value: not cumulative)
+        super().compute_pdf()
+
+    def get_pmf_grid(self):
+        from scipy.stats import norm
+        (mx, my), (sx, sy) = self._moments()
+        (_, ex), (_, ey) = self.config['analysis_space']
+        px = np.diff(norm(mx, sx).cdf(np.asarray(ex, dtype=float)))
+        py = np.diff(norm(my, sy).cdf(np.asarray(ey, dtype=float)))
+        pmf = np.outer(px, py)
+        return pmf, np.full(pmf.shape, np.inf)
+
+    def simulate(self, n_events):
+        (mx, my), (sx, sy) = self._moments()
+        (nx, _), (ny, _) = self.config['analysis_space']
+        d = np.zeros(int(n_events), dtype=[('source', int), (nx, float), (ny, float)])
+        d[nx] = np.random.normal(mx, sx, int(n_events))
+        d[ny] = np.random.normal(my, sy, int(n_events))
+        return d
+
+
+def many_nuisances_config(n_bins=(20, 20), n_params=8, n_sources=4, own_per_source=2, events_per_day=400.):
+    """-> (model config, shape-parameter names, per source the names it responds to): `n_sources` NuisanceBlobSources in the
+    unit square, source s responding to the `own_per_source` settings np(s * own_per_source) ... only (every other one is
+    listed in its dont_hash_settings).  Every setting's base value is 0."""
+    names = ['np%d' % i for i in range(n_params)]
+    own = [tuple(names[(s * own_per_source + j) % n_params] for j in range(own_per_source)) for s in range(n_sources)]
+    conf = dict(analysis_space=[('x', np.linspace(0., 1., n_bins[0] + 1)), ('y', np.linspace(0., 1., n_bins[1] + 1))],
+                default_source_class=NuisanceBlobSource, livetime_days=1., sources=[], **{n: 0. for n in names})
+    for s in range(n_sources):
+        conf['sources'].append(dict(name='s%d' % s, events_per_day=events_per_day * (1 + 0.5 * s), own_settings=list(own[s]),
+                                    centre=(0.3 + 0.4 * (s % 2), 0.3 + 0.4 * ((s // 2) % 2)), width=0.12 + 0.02 * s,
+                                    extra_dont_hash_settings=[n for n in names if n not in own[s]]))
+    return conf, names, own

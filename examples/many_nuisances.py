@@ -1,0 +1,135 @@
+"""A binned likelihood with many nuisance shape parameters, each moving one source -- run as
+
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--measure [--rounds 31]]
+
+Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
+grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
+1 + d + S = 16 columns; `SourceWiseBinnedLogLikelihood` keeps one 5 x 5 grid per source -- 100 rows resident, 16 rows per
+evaluation -- and the native fit loop floats all twelve parameters.
+
+(1) prepare(): models at the 100 projected anchors only; set_data(): the events binned on the device;
+(2) bestfit_batched: every rate and every constrained shape parameter floating;
+(3) likelihood_ratio_scan over the signal's rate multiplier: --scan hypotheses profiled in lock-step (bi_fit_batched_factored).
+
+--measure times the C ABI instead, at a shape BOTH routes can hold: d = 4, S = 4, one own axis per source, 5 anchors, 100^3
+bins, dense data, 64 points per call -- bi_eval_factored with its gradient (8 rows per point) against bi_eval_grad on the
+expanded 5^4 grid (64 rows per point; 20 GB of templates), alternated calls, medians with quartiles, and the kernel's bytes
+per second against the stream_bandwidth(items = 64, rows = 8) probe of the same device.
+"""
+import argparse
+import time
+
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--bins', type=int, default=20, help='bins per analysis axis (two axes)')
+ap.add_argument('--scan', type=int, default=33, help='hypotheses of the profile scan')
+ap.add_argument('--measure', action='store_true', help='time bi_eval_factored against bi_eval_grad on the expanded grid')
+ap.add_argument('--rounds', type=int, default=31)
+ap.add_argument('--measure-bins', type=int, default=100, help='bins per axis (three axes) of the measured shape')
+args = ap.parse_args()
+
+
+def quartiles(t):
+    q = np.percentile(np.asarray(t) * 1e3, [50, 25, 75])
+    return '%.3f ms [%.3f, %.3f]' % tuple(q)
+
+
+def measure():
+    from blueice_amd.device import DeviceContext
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B, P = 5, args.measure_bins ** 3, 64
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    full = DeviceContext(0)
+    t0 = time.perf_counter()
+    full.begin_model([g] * d, S, B)
+    for lin, idx in enumerate(np.ndindex(*(n_a,) * d)):          # the same likelihood on the product grid: source s from ITS anchor
+        full.set_anchor(lin, np.stack([rows[s, idx[s]] for s in range(S)]), np.array([mus[s, idx[s]] for s in range(S)]))
+    full.end_model()
+    print('expanded grid resident: %d anchor models, %.1f GB, %.1f s to stream; source-wise: %d rows, %.2f GB'
+          % (n_a ** d, n_a ** d * S * B * 8 / 1e9, time.perf_counter() - t0, S * n_a, S * n_a * B * 8 / 1e9), flush=True)
+    z = rng.uniform(-1.9, 1.9, (P, d))
+    r = rng.uniform(0.8, 1.2, (P, S))
+    mid = n_a // 2
+    counts = rng.poisson(sum(mus[s, mid] * rows[s, mid] for s in range(S))).astype(float)
+    fac.set_counts(counts)
+    full.upload_counts(counts)
+    a, b = fac.eval_grad(z, r), full.eval_grad(z, r)
+    print('agreement of the two routes over %d points: max |ll difference| / |ll| %.2g, max |gradient difference| %.2g of the largest entry'
+          % (P, np.max(np.abs(a[0] - b[0]) / np.abs(b[0])), max(np.max(np.abs(a[1] - b[1])), np.max(np.abs(a[2] - b[2]))) /
+             max(np.max(np.abs(b[1])), np.max(np.abs(b[2])))))
+    calls = [('bi_eval_factored + gradient', lambda: fac.eval_grad(z, r)), ('bi_eval_grad, expanded 5^%d grid' % d, lambda: full.eval_grad(z, r)),
+             ('bi_eval_factored, values', lambda: fac.eval(z, r)), ('bi_eval, expanded grid', lambda: full.eval(z, r))]
+    times = {name: [] for name, _ in calls}
+    for rnd in range(3 + args.rounds):              # three warm-up rounds; the calls alternate inside every round
+        for name, call in calls:
+            t0 = time.perf_counter()
+            call()                                   # (every one of them ends in a stream synchronise)
+            if rnd >= 3:
+                times[name].append(time.perf_counter() - t0)
+    for name, _ in calls:
+        print('%2d points per call, %-34s %s' % (P, name, quartiles(times[name])))
+    # the kernels alone, from device events around the launches, in a pass of their own
+    Bp = (B + 511) // 512 * 512
+    for name, ctx, call, n_rows in (('k_morph_factored', fac._dev, calls[0][1], 2 * S + 1), ('expanded route', full, calls[1][1], S * 2 ** d + 1)):
+        ctx.profile(True)
+        ks = []
+        for _ in range(args.rounds):
+            call()
+            ks.append(ctx.profile_read()[1] * 1e-3)
+        ctx.profile(False)
+        med = np.median(ks)
+        print('%-18s kernels %s per call: %d rows (counts included) x %d bins x 8 bytes x %d points = %.2f GB -> %.2f TB/s'
+              % (name, quartiles(ks), n_rows, Bp, P, n_rows * Bp * 8 * P / 1e9, n_rows * Bp * 8 * P / med / 1e12))
+    for nt in (True, False):
+        print('stream_bandwidth(items = 64, rows = 8, nontemporal = %s): %.2f TB/s' % (nt, full.stream_bandwidth(items=64, rows=8, nontemporal=nt) / 1e3))
+
+
+if args.measure:
+    measure()
+    raise SystemExit(0)
+
+from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood  # noqa: E402
+from blueice_amd.synthetic import many_nuisances_config  # noqa: E402
+
+conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins))
+lf = SourceWiseBinnedLogLikelihood(conf)
+for s in range(4):
+    lf.add_rate_parameter('s%d' % s)
+for n in names:
+    lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+t0 = time.perf_counter()
+lf.prepare()
+print('(1) prepare(): %d shape parameters x 5 anchors, %d sources responding to %s: %d rows on the device instead of 5^%d x %d, %.2f s'
+      % (len(names), 4, ', '.join('/'.join(o) for o in own), sum(5 ** len(o) for o in own), len(names), 4, time.perf_counter() - t0))
+np.random.seed(3)
+data = lf.base_model.simulate()
+lf.set_data(data)
+print('    set_data(): %d events binned on the device into %d x %d bins' % (len(data), args.bins, args.bins))
+
+t0 = time.perf_counter()
+best, ll, info = lf.bestfit_batched(return_info=True)
+print('(2) bestfit_batched, %d parameters floating: max ll %.4f, converged %s, %d evaluations in %d device calls, %.3f s'
+      % (len(best), ll[0], bool(info['converged'][0]), info['evaluations'], info['calls'], time.perf_counter() - t0))
+print('    ' + ', '.join('%s %.3f' % (k.replace('_rate_multiplier', ''), v[0]) for k, v in best.items()))
+
+grid = np.linspace(0.7, 1.3, args.scan)
+t0 = time.perf_counter()
+scan = lf.likelihood_ratio_scan(('s0_rate_multiplier', grid))
+dt = time.perf_counter() - t0
+inside = grid[2 * scan <= 1.0]
+print('(3) likelihood_ratio_scan over s0_rate_multiplier: %d hypotheses, 11 nuisances profiled at each, %.3f s; minimum at %.3f, '
+      '2 dlnL <= 1 on [%.3f, %.3f]' % (args.scan, dt, grid[np.argmin(scan)], inside.min(), inside.max()))
+limit = lf.one_parameter_interval('s0_rate_multiplier', 3.0, confidence_level=0.9, kind='upper')
+print('    90 %% upper limit on s0_rate_multiplier (one_parameter_interval): %.4f' % limit)

@@ -500,6 +500,60 @@ int bi_fit_batched_real(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, 
                         const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
                         double* f_out, int32_t* flags_out, int64_t* counters);
 
+/* ---- source-wise (factored) binned models: one anchor grid per source --------------------------------------------------
+ * The grid model above is ONE tensor product of all d shape axes: it holds prod_i n_i anchor models and a point reads
+ * S 2^d rows.  A source-wise model lets every source morph over the axes IT responds to only (the reference's
+ * source_wise_interpolation, for binned likelihoods): source s owns the axes O_s (ascending, e_s = |O_s|, possibly none;
+ * every owned axis has at least two anchors), keeps p_s [n_{O_s[0]}] .. [n_{O_s[e_s - 1]}][B] template rows and as many
+ * rates M_s in C order, and a point reads sum_s 2^e_s rows.  At (z [d], rs [S]) against counts n [B]:
+ *     per axis           cell k and fraction t as everywhere (scipy's convention, the last cell closed)
+ *     per source         corners numbered with the first own axis as the most significant bit; w_c = the product of t or
+ *                        1 - t in own-axis order from 1.0; M_s(z) = sum_c M_s,c w_c left to right from 0.0; r_s = M_s(z) rs_s;
+ *                        tau_s,b = sum_c w_c p_s,c,b, one fused multiply-add per corner from 0.0
+ *     mu_b               = sum_s r_s tau_s,b, one fused multiply-add per source from 0.0
+ *     ll                 = sum_b [n_b log mu_b - mu_b] - sum_b lgamma(n_b + 1)     (n_b = 0: -mu_b; n_b > 0, mu_b = 0: -inf)
+ *     d ll / d rs_s      = M_s sum_b f_b tau_s,b,   f_b = n_b / mu_b - 1  (n_b = 0: -1)
+ *     d ll / d z_i       = sum_{s: i in O_s} rs_s (M_s sum_b f_b ups_s,i,b + d_i M_s sum_b f_b tau_s,b),
+ *                        ups_s,i,b = sum_c d_i w_c p_s,c,b; an axis nobody owns has slope 0; on an anchor the slope of the cell
+ *                        the point is assigned to (bi_eval_grad's convention)
+ * Early exits, in this order: dataset outside [0, T) BI_ST_BAD_DATASET; a z_i outside its axis' anchors or nan, on any of
+ * the d axes, BI_ST_OUT_OF_BOUNDS; an r_s not in [0, inf) BI_ST_UNPHYSICAL.  All three give ll = -inf.  Wherever ll is not
+ * finite the gradient entries are nan.  A point's result does not depend on the batch it is evaluated in, and repeated
+ * calls agree bit for bit.
+ *
+ * Limits: d <= 32, S <= 8, e_s <= 3 (a source that responds to more axes belongs on the grid model).  Out of scope, and
+ * refused where they can be asked for: sources that may go negative (template entries must be finite and >= 0),
+ * Beeston-Barlow, unbinned data, device-generated toys.
+ *
+ * The model is a store of its own inside the context, beside the grid model and released by bi_destroy (or the next
+ * bi_factored_begin).  It does not make the context "ready": every other entry point of this header keeps refusing a context
+ * without a grid model with BI_ERR_STATE, and none of them reads this store.
+ *   bi_factored_begin        n_anchor [d], anchor_z: the axes' anchors back to back; n_own [S] = e_s; own_axes: the sources' O_s
+ *                            back to back.  Drops the previous source-wise model and its counts.
+ *   bi_factored_set_anchor   row `local_index` (C order over the source's own axes) of source s: ps_row [B] and its rate mu;
+ *                            in any order, each anchor exactly once (a second upload of one: BI_ERR_INVALID)
+ *   bi_factored_end          BI_ERR_STATE naming the first anchor that is missing
+ *   bi_factored_set_counts   counts [T][B], T >= 1, dense doubles, every count finite and >= 0 (a count that is no integer
+ *                            gives -inf, scipy's poisson.logpmf); replaces earlier counts; sum_b lgamma(n_b + 1) per dataset is
+ *                            computed once, here
+ *   bi_eval_factored         ll [P], grad [P][d + S] or NULL (values only: the same bits of ll), status [P] or NULL;
+ *                            rate_scale NULL: ones; dataset NULL: dataset 0
+ *   bi_fit_batched_factored  bi_fit_batched_gauss with this likelihood as the objective: the same optimiser and the same
+ *                            constraint terms; the three prior arrays may all be NULL (no terms); `dataset` indexes the
+ *                            counts of bi_factored_set_counts; var_index refers to the d axes and S sources of this model */
+int bi_factored_begin(bi_ctx* ctx, int d, const int32_t* n_anchor, const double* anchor_z, int S, int64_t B,
+                      const int32_t* n_own, const int32_t* own_axes);
+int bi_factored_set_anchor(bi_ctx* ctx, int s, int64_t local_index, const double* ps_row, double mu);
+int bi_factored_end(bi_ctx* ctx);
+int bi_factored_set_counts(bi_ctx* ctx, int64_t T, const double* counts);
+int bi_eval_factored(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                     double* grad, int32_t* status);
+int bi_fit_batched_factored(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                            const double* scale0, const double* unit, const int64_t* dataset, const double* x0,
+                            const double* lo, const double* hi, const int32_t* n_kinks, const double* kinks, double gtol,
+                            int max_iter, const double* prior_mean, const double* prior_sigma, const double* prior_const,
+                            double* x_out, double* f_out, int32_t* flags_out, int64_t* counters);
+
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
  * n_walkers x n_steps scalar likelihood calls (bestfit_emcee, blueice/inference.py:254-321).  The variables are described as
