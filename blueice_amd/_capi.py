@@ -62,6 +62,7 @@ SIGNATURES = {
     'bi_expected_counts': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p]),
     'bi_set_coarse_binning': (C.c_int, [_p, C.c_int, _p, _p, _p, C.POINTER(_i64)]),
     'bi_expected_coarse': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p, _p]),
+    'bi_expected_coarse_jacobian': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p]),
     'bi_coarse_counts': (C.c_int, [_p, _i64, _p, _p]),
     'bi_set_real_counts': (C.c_int, [_p, _i64, _p]),
     'bi_set_asimov_counts': (C.c_int, [_p, _i64, _p, _p]),

@@ -5,17 +5,27 @@ analysis dimension.  `expected_coarse` / `expected_coarse_points` return the mor
 `coarse_counts` the resident data summed the same way -- both reduced on the device (bi_expected_coarse, bi_coarse_counts:
 the corner rows of a point are streamed once and summed as they arrive, the fine bins never cross the bus) --, and
 `coarse_statistics` forms the deviance and Pearson's chi2 over the cells, which `gof_statistics(..., binning=)` and
-`goodness_of_fit(..., binning=)` use (blueice_amd.inference).  Plain binned likelihoods only.
+`goodness_of_fit(..., binning=)` use (blueice_amd.inference).  `expected_coarse_jacobian` / `_points` add the first
+derivatives of every cell in the user's parameters, summed over the cells in the same single pass
+(bi_expected_coarse_jacobian); `expected_coarse_band` turns a covariance of the parameters (`hesse`, `expected_covariance`)
+into the uncertainty band of a coarse view and the impact of every parameter on it, and `coarse_information` gives the Fisher
+information of the likelihood at that binning, cell by cell.  Plain binned likelihoods only.
 
     box = CoarseBinning(lf, keep=['cs1'], rebin={'cs1': 4}, ranges={'cs2': (2.0, 3.5)})
     mu = lf.expected_coarse(box, per_source=True, **best)            # [S, n_cs1 / 4]
     band = np.percentile(lf.expected_coarse_points(box, samples), [16, 50, 84], axis=0)
+    mu, sigma, impacts = lf.expected_coarse_band(box, *lf.hesse(best), **best)
 """
+from collections import OrderedDict
+
 import numpy as np
 
 from .exceptions import NotPreparedException
+from .hessian import user_jacobian
 
-__all__ = ['CoarseBinning', 'expected_coarse', 'expected_coarse_points', 'coarse_counts', 'coarse_statistics']
+__all__ = ['CoarseBinning', 'expected_coarse', 'expected_coarse_points', 'coarse_counts', 'coarse_statistics',
+           'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
+           'propagate_covariance', 'information_per_cell']
 
 EDGE_TOLERANCE = 1e-9          # an edge value must lie within this fraction of the bin's width of a fine edge
 
@@ -165,6 +175,89 @@ def expected_coarse(lf, binning, per_source=False, livetime_days=None, **params)
         return np.full(shape, np.nan)
     mu, _ = lf.ctx.expected_coarse(binning.n_cells, zs if len(zs) else None, scale[None, :], per_source=per_source)
     return mu[0].reshape(shape)
+
+
+def expected_coarse_jacobian_points(lf, binning, points, livetime_days=None):
+    """The expected events per cell of `binning` and their first derivatives in the user's parameters at P points (as
+    `expected_coarse_points`) -> (names [F], mu [P, *binning.shape], J [P, F, *binning.shape]): names is every registered rate
+    multiplier, then every shape parameter (`hesse`'s and `fisher_information`'s order), J[p, f] = d mu_C / d names[f].  The
+    derivatives over theta = (z, rate_scale) are summed over the cells on the device in the one pass over the corner rows that
+    forms mu (bi_expected_coarse_jacobian: mu has the bits of `expected_coarse_points`), and carried to the user's parameters by
+    the chain rule of `values_gradients_hessians` (`hessian.user_jacobian`: live time, efficiencies, shape parameters that
+    double as efficiencies).  On an anchor the slopes are those of the cell the point is assigned to.  A point outside the
+    anchor box or with unphysical rates is nan throughout."""
+    _prepared(lf, binning, 'expected_coarse_jacobian_points')
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    P = len(z)
+    mu, jac, _ = lf.ctx.expected_coarse_jacobian(binning.n_cells, z if z.shape[1] else None, scale)
+    mult, L, eff, eff_axis, rate_sources = lf._chain_rule_terms(points, P, livetime_days)
+    U = user_jacobian(P, z.shape[1], scale.shape[1], mult, L, eff, eff_axis, rate_sources)
+    J = np.einsum('pfk,pkc->pfc', U, jac)
+    return lf._parameter_names(), mu.reshape((P,) + binning.shape), J.reshape(J.shape[:2] + binning.shape)
+
+
+def expected_coarse_jacobian(lf, binning, livetime_days=None, **params):
+    """`expected_coarse_jacobian_points` at one point (parameter values; absent parameters at their defaults) ->
+    (names [F], mu [*binning.shape], J [F, *binning.shape])."""
+    names, mu, J = expected_coarse_jacobian_points(lf, binning, {k: np.array([v], dtype=float) for k, v in params.items()},
+                                                   livetime_days=livetime_days)
+    return names, mu[0], J[0]
+
+
+def propagate_covariance(jacobian_names, J, names, covariance):
+    """Linear propagation of a parameter covariance to the cells (pure numpy, no device): J [F, ...] = d mu / d parameter with
+    rows named `jacobian_names`, (names [K], covariance [K, K]) what `hesse` / `expected_covariance` return -> (sigma [...],
+    impacts): sigma^2 = J_K^T covariance J_K over the K named parameters (the others are held fixed), impacts an OrderedDict
+    name -> J_name sqrt(covariance_name,name), the shift of every cell when that parameter alone moves by its standard
+    deviation (signed).  A name that is no row of J is a ValueError; nan in the covariance gives nan."""
+    jacobian_names, names = list(jacobian_names), list(names)
+    missing = [k for k in names if k not in jacobian_names]
+    if missing:
+        raise ValueError("not parameters of the likelihood: %s" % ', '.join(str(k) for k in missing))
+    if len(set(names)) != len(names):
+        raise ValueError("a parameter is named twice: %s" % (names,))
+    J = np.asarray(J, dtype=float)
+    covariance = np.asarray(covariance, dtype=float)
+    if covariance.shape != (len(names), len(names)):
+        raise ValueError("the covariance of %d parameters is [%d, %d], not %s" % (len(names), len(names), len(names), covariance.shape))
+    Jk = J[[jacobian_names.index(k) for k in names]] if names else np.zeros((0,) + J.shape[1:])
+    with np.errstate(invalid='ignore'):
+        variance = np.einsum('k...,kl,l...->...', Jk, covariance, Jk)
+        sigma = np.sqrt(np.where(variance < 0, 0.0, variance))            # (a rounded zero is no negative variance)
+        impacts = OrderedDict((k, Jk[i] * np.sqrt(covariance[i, i])) for i, k in enumerate(names))
+    return sigma, impacts
+
+
+def expected_coarse_band(lf, binning, names, covariance, livetime_days=None, **params):
+    """The uncertainty band of a coarse view from a covariance of the parameters, without a posterior chain:
+    (names [K], covariance [K, K]) as `hesse` / `expected_covariance` return them, `params` the point (fitted values plus fixed
+    ones) -> (mu [*binning.shape], sigma [*binning.shape], impacts: OrderedDict name -> [*binning.shape]), by
+    `propagate_covariance` of `expected_coarse_jacobian` -- one device call.  Linear propagation: the band of a model whose
+    cells are far from linear over one standard deviation is the posterior's (`expected_coarse_points` over samples)."""
+    all_names, mu, J = expected_coarse_jacobian(lf, binning, livetime_days=livetime_days, **params)
+    sigma, impacts = propagate_covariance(all_names, J, names, covariance)
+    return mu, sigma, impacts
+
+
+def information_per_cell(J, mu):
+    """The Fisher information of independent Poisson cells, cell by cell (pure numpy): J [F, ...], mu [...] ->
+    (I [F, F, ...] = J J^T / mu where mu > 0, unbounded [F, ...] bool).  A cell with mu = 0 contributes 0, and the parameters
+    that move it (J != 0) are flagged: one event there would decide them.  A negative or nan mu gives nan in that cell."""
+    J, mu = np.asarray(J, dtype=float), np.asarray(mu, dtype=float)
+    with np.errstate(all='ignore'):
+        info = np.where(mu > 0, J[:, None] * J[None, :] / np.where(mu > 0, mu, 1.0), np.where(mu == 0, 0.0, np.nan))
+    return info, (mu == 0) & (J != 0)
+
+
+def coarse_information(lf, binning, livetime_days=None, **truth):
+    """The expected (Fisher) information of the likelihood AT THAT BINNING, cell by cell, at a truth (parameter values; absent
+    parameters at their defaults) -> (names [F], I [F, F, *binning.shape], unbounded [F, *binning.shape] bool):
+    I_C = J_C J_C^T / mu_C (`information_per_cell` of `expected_coarse_jacobian`), no priors.  Its sum over the cells is what
+    an analysis in those cells can know; with the identity binning that is `fisher_information(priors=False)`, and no
+    rebinning adds to it.  Where the cells show which part of the analysis space constrains which parameter."""
+    names, mu, J = expected_coarse_jacobian(lf, binning, livetime_days=livetime_days, **truth)
+    info, unbounded = information_per_cell(J, mu)
+    return names, info, unbounded
 
 
 def coarse_counts(lf, binning, datasets=None):

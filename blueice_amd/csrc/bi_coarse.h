@@ -7,7 +7,9 @@
 //     the boundaries of the column groups xb [Cx + 1] and x_map [L].
 // bi_expected_coarse: per live point the value rows of bi_items.h, bi_expected_counts's (row offsets and a_k = w_corner r_source
 // of the 2^d_eff S corner rows), one launch pair and one download of the live runs per chunk of points; the chunk is sized so that the x-resolved partial sums of
-// k_morph_coarse and the output stay within ~64 MB each.  bi_coarse_counts: the dense counts rows through the same kernels,
+// k_morph_coarse and the output stay within ~64 MB each.  bi_expected_coarse_jacobian: the same with the G = 1 + D padded
+// first-order columns of bi_fisher.h per corner row (ItemBatch / PointDerivs::first_order) and k_morph_coarse_jac<G>, whose G
+// columns the finish kernels take for R = G groups of rows: mu and d mu / d theta of every cell.  bi_coarse_counts: the dense counts rows through the same kernels,
 // or the non-empty-bin lists through k_coarse_list where only those exist.
 #pragma once
 
@@ -45,9 +47,9 @@ int coarse_check(bi_ctx* c, const char* what, bool need_data) {
     return BI_OK;
 }
 
-// one launch pair over n_items items whose descriptors lie at rowoff / coef (device): partial -> d_out [n_items][R][C]
-void coarse_launch(bi_ctx* c, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R, int64_t n_items,
-                   double* partial, double* d_out) {
+// the arguments of one launch pair over n_items items whose descriptors lie at rowoff / coef (device): partial -> d_out [n_items][R][C]
+CoarseArgs coarse_args(bi_ctx* c, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R, int64_t n_items,
+                       double* partial, double* d_out) {
     const bi_ctx::Coarse& q = c->coarse;
     const CoarseGeometry g = coarse_geometry(c);
     CoarseArgs a{};
@@ -58,7 +60,12 @@ void coarse_launch(bi_ctx* c, const double* rows, const int64_t* rowoff, const d
     a.n_out = n_items * R * q.C;
     a.NS = NS; a.S = S; a.R = R;
     a.nsplit = g.nsplit; a.n_xt = g.n_xt; a.tx_shift = g.tx_shift; a.wide = g.wide;
-    launch_morph_coarse(c, a, n_items);
+    return a;
+}
+
+void coarse_launch(bi_ctx* c, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R, int64_t n_items,
+                   double* partial, double* d_out) {
+    launch_morph_coarse(c, coarse_args(c, rows, rowoff, coef, NS, S, R, n_items, partial, d_out), n_items);
 }
 
 // items per launch: the partial sums and the output of a chunk within ~64 MB each, a launch at most 32 768 items
@@ -211,6 +218,70 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
         // (the staging block of packed_upload, d_partial and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, &live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse: %s", hipGetErrorString(e));
+    }
+    return BI_OK;
+}
+
+int bi_expected_coarse_jacobian(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, double* mu, double* jac, int32_t* status) {
+    int rc = coarse_check(c, "bi_expected_coarse_jacobian", false);
+    if (rc) return rc;
+    if (P < 0 || (P > 0 && (!mu || !jac))) return fail(c, BI_ERR_INVALID, "bad P / output pointer");
+    if (c->d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "z is NULL");
+    const int S = c->S, d = c->d;
+    const int de = (int)c->eff_axes.size();
+    const int D = de + S, F = d + S;
+    int G, DM;
+    if (!fisher_variant(D, G, DM))
+        return fail(c, BI_ERR_INVALID, "bi_expected_coarse_jacobian: 1 + d_eff + S = %d exceeds %d coefficient columns", 1 + D, kMaxG);
+    const int NS = (1 << de) * S;
+    const int64_t C = c->coarse.C;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, nullptr, status, [&](int64_t p) {
+        std::fill(mu + p * C, mu + (p + 1) * C, qnan);
+        std::fill(jac + p * F * C, jac + (p + 1) * F * C, qnan);
+    }, false);
+    const int64_t n_items = (int64_t)live.size();
+    if (n_items == 0) return BI_OK;
+
+    // full parameter index of first-order index q, and the columns of the effective axes (bi_fisher.h's)
+    std::vector<int> full((size_t)D), axis_col((size_t)de);
+    for (int q = 0; q < D; ++q) full[(size_t)q] = q < de ? c->eff_axes[(size_t)q] : d + (q - de);
+    for (int i = 0; i < de; ++i) axis_col[(size_t)i] = 1 + i;
+    const ItemRoute rt = ItemRoute::dense(c);
+    const int64_t chunk = coarse_chunk(c, n_items, G);
+    const CoarseGeometry geo = coarse_geometry(c);
+    ScratchBuf d_partial, d_out;
+    if ((rc = dev_alloc(c, d_partial, (size_t)(chunk * G * c->coarse.CR * geo.nsplit * c->coarse.Lx) * sizeof(double))) ||
+        (rc = dev_alloc(c, d_out, (size_t)(chunk * G * C) * sizeof(double)))) return rc;
+    // The device holds a chunk's cells as [item][G][C], the padded columns; the caller's arrays are [P][C] and [P][F][C].  The
+    // chunk comes down as one run and is dealt out here.
+    std::vector<double> stage((size_t)(chunk * G * C));
+    std::vector<int64_t> run((size_t)chunk);
+    for (int64_t i = 0; i < chunk; ++i) run[(size_t)i] = i;
+    for (int64_t i0 = 0; i0 < n_items; i0 += chunk) {
+        const int64_t ni = std::min(chunk, n_items - i0);
+        const std::vector<int64_t> part(live.begin() + i0, live.begin() + i0 + ni);
+        ItemBatch batch(c, part, G, 1, 0);                 // (rowoff and coef are what is used: no result slot is wanted)
+        batch.fill(rt, z, rate_scale, nullptr, false, 1024, 0,
+                   [&](const PointDerivs& pd, double* col, int corner, int s) { pd.first_order(col, corner, s, axis_col.data(), 1 + de + s); },
+                   [](const PointDerivs&, double*, int64_t) {});
+        if ((rc = batch.upload(c))) return rc;
+        const CoarseArgs a = coarse_args(c, rt.ps, batch.pu.dev<int64_t>(0), batch.pu.dev<double>(1), NS, S, G, ni, (double*)d_partial.p,
+                                         (double*)d_out.p);
+        if (launch_morph_coarse_jac(c, G, a, ni)) return fail(c, BI_ERR_INVALID, "bi_expected_coarse_jacobian: no kernel variant for G = %d", G);
+        // (the staging block of the batch, d_partial and d_out are reused by the next chunk: the download synchronises)
+        const hipError_t e = download_live_runs(c, run.data(), ni, (const double*)d_out.p, (int64_t)G * C, stage.data(), hipGetLastError());
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse_jacobian: %s", hipGetErrorString(e));
+        parallel_for(ni, 64, [&](int64_t lo, int64_t hi) {
+            for (int64_t i = lo; i < hi; ++i) {
+                const int64_t p = part[(size_t)i];
+                const double* h = stage.data() + i * G * C;
+                std::copy(h, h + C, mu + p * C);
+                std::fill(jac + p * F * C, jac + (p + 1) * F * C, 0.0);            // rows of single-anchor axes stay zero
+                for (int q = 0; q < D; ++q) std::copy(h + (1 + q) * C, h + (2 + q) * C, jac + (p * F + full[(size_t)q]) * C);
+            }
+        });
     }
     return BI_OK;
 }

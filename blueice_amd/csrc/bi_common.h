@@ -14,7 +14,7 @@
 //     tu_factored.hip     k_morph_factored (value + gradient sums of one point of a source-wise model per item)   bi_k_factored.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
-//     tu_coarse.hip       k_morph_coarse, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning)   bi_k_coarse.h
+//     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
 //     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
 //     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
@@ -130,6 +130,9 @@ void launch_grid_init(bi_ctx* c, const GridArgs& a);
 void launch_grid_finish(bi_ctx* c, const GridArgs& a);
 // k_morph_coarse + k_coarse_finish: the expectation (or a row of counts) of n_items (<= 65 535) items summed over the groups of a coarse binning
 void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items);
+// k_morph_coarse_jac<G> + k_coarse_finish: the same with G = 4, 8 or 16 coefficient columns per corner row (a.R = G; a.coef [items][NS][G]);
+// BI_ERR_INVALID for another G
+int launch_morph_coarse_jac(bi_ctx* c, int G, const CoarseArgs& a, int64_t n_items);
 // k_coarse_list + k_coarse_table: the non-empty-bin lists of n (<= 65 535) datasets into the cells, out [n][C] (device memory)
 void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out);
 // ---- the toy-MC evaluation kernels (bi_k_toys.h).  No launcher times its kernel: the host half (bi_toys.h) opens the EventScopes.

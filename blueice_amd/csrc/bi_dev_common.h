@@ -170,7 +170,7 @@ struct ExpectArgs {
 struct CoarseArgs {
     const double* ps;          // [rows][Bp] the dense template tensor (or the dense counts [T][Bp])
     const int64_t* rowoff;     // [items][NS] element offsets of the rows, k = corner * S + source
-    const double* coef;        // [items][NS] a_k
+    const double* coef;        // [items][NS] a_k (k_morph_coarse_jac<G>: [items][NS][G], and R = G)
     const int64_t* row_off;    // [CR + 1] the fine rows of coarse row q are row_list[row_off[q] .. row_off[q + 1])
     const int32_t* row_list;
     const int32_t* xb;         // [Cx + 1] fine columns [xb[j], xb[j + 1]) make coarse column j; xb[0] = x_lo

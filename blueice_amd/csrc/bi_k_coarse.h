@@ -14,6 +14,14 @@
 //       mu_b = sum_k a_k row_k[r L + x]       (item_chain, bi_k_item.h: k_morph_expect's bits)
 //   and adds it to its lane's sum; the TY sums of a column are then added in ty order through LDS, and the block writes
 //   partial[item][r][coarse row][share][x].  A share without rows writes zeros.
+// k_morph_coarse_jac<G>: the first derivatives of the same cells, J_C = d mu_C / d theta (bi_expected_coarse_jacobian).  The
+//   blocks, the lanes and the order of every sum are k_morph_coarse's; a block handles all G = 4, 8 or 16 columns, so a
+//   point's corner rows are read once for all of them.  Per fine bin the G = 1 + D padded coefficient columns of
+//   PointDerivs::first_order (bi_items.h; D = d_eff + S) are formed as item_columns forms them (bi_k_item.h):
+//       col_g = sum_k coef[k][g] row_k[r L + x]      0 -> mu_b, 1 .. d_eff -> d mu_b / d z, then d mu_b / d rate_scale_s
+//   and added to G per-lane sums in registers; the TY sums of every column go through LDS in ty order, and column g is written
+//   as group g of an R = G call, partial[item][g][coarse row][share][x]: the finish kernels below are unchanged.  Column 0 is
+//   k_morph_coarse's chain and order, so mu_C has the bits of bi_expected_coarse's total.  No per-bin derivative is written.
 // k_coarse_finish: one thread per output cell: the shares in order, inside a share the columns of the cell's group in order.
 // k_coarse_finish_wide: one block per output cell, for binnings whose cells gather many partials (everything summed: 10^5).
 // There is no floating-point atomic anywhere: every sum runs in a fixed order and a repeated identical call is bitwise
@@ -29,6 +37,9 @@
 //
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), no scratch in any of them:
 //     k_morph_coarse    34 VGPRs, 86 SGPRs, 2048 bytes of LDS (the TY sums of every column), 8 waves per SIMD
+//     k_morph_coarse_jac<4>    38 VGPRs,  96 SGPRs,  8192 bytes of LDS (G x 256 doubles), 8 waves per SIMD
+//     k_morph_coarse_jac<8>    60 VGPRs, 104 SGPRs, 16384 bytes of LDS, 7 waves per SIMD
+//     k_morph_coarse_jac<16>   87 VGPRs, 106 SGPRs, 32768 bytes of LDS, 5 waves per SIMD (profiles/coarse_jacobian_kernel_resources.txt)
 //     k_coarse_finish   16 VGPRs, 25 SGPRs, no LDS
 //     k_coarse_finish_wide   20 VGPRs, 44 SGPRs, 32 bytes of LDS (the four waves' sums)
 //     k_coarse_list     21 VGPRs, 43 SGPRs, no LDS
@@ -76,6 +87,60 @@ __global__ __launch_bounds__(kThreads) void k_morph_coarse(CoarseArgs a) {
         double s = s_acc[tx];
         for (int j = 1; j < TY; ++j) s += s_acc[j * TX + tx];
         *out = s;
+    }
+}
+
+// The same blocks with G coefficient columns per corner row instead of one: a.coef [items][NS][G] (see the header comment).
+// Column g of a block goes to partial[item][g][coarse row][share][x]: group g of an R = G call, for the finish kernels.
+template <int G>
+__global__ __launch_bounds__(kThreads) void k_morph_coarse_jac(CoarseArgs a) {
+    const int TX = 1 << a.tx_shift, TY = kThreads >> a.tx_shift;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> a.tx_shift;
+    unsigned bx = blockIdx.x;
+    const int xt = (int)(bx % (unsigned)a.n_xt);
+    bx /= (unsigned)a.n_xt;
+    const int split = (int)(bx % (unsigned)a.nsplit);
+    const int64_t crow = bx / (unsigned)a.nsplit;
+    const int64_t item = blockIdx.z;
+    const int64_t* __restrict__ rowoff = a.rowoff + item * a.NS;
+    const double* __restrict__ coef = a.coef + item * a.NS * G;
+    const int64_t xr = (int64_t)xt * TX + tx;
+    const bool live = xr < a.Lx;
+    const int64_t lo = a.row_off[crow], n = a.row_off[crow + 1] - lo;
+    const int64_t per = (n + a.nsplit - 1) / a.nsplit;
+    const int64_t i0 = (int64_t)split * per, i1 = i0 + per < n ? i0 + per : n;
+
+    double sum[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) sum[g] = 0.0;
+    if (live)
+        for (int64_t i = i0 + ty; i < i1; i += TY) {
+            double acc[G];
+            item_columns<G, false>(a, rowoff, coef, (int64_t)a.row_list[lo + i] * a.L + a.x_lo + xr, acc);
+#pragma unroll
+            for (int g = 0; g < G; ++g) sum[g] += acc[g];
+        }
+
+    const int64_t column = a.CR * a.nsplit * a.Lx;                              // from one column's partials to the next one's
+    double* __restrict__ out = a.partial + (item * G * column + (crow * a.nsplit + split) * a.Lx + xr);
+    if (TY == 1) {
+        if (live) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) out[g * column] = sum[g];
+        }
+        return;
+    }
+    __shared__ double s_acc[G][kThreads];
+#pragma unroll
+    for (int g = 0; g < G; ++g) s_acc[g][threadIdx.x] = sum[g];
+    __syncthreads();
+    if (ty == 0 && live) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            double s = s_acc[g][tx];
+            for (int j = 1; j < TY; ++j) s += s_acc[g][j * TX + tx];
+            out[g * column] = s;
+        }
     }
 }
 

@@ -30,8 +30,9 @@ struct ItemTiles {
 };
 
 // acc[g] = sum_k coef[k][g] row_k[bin], k ascending from 0.0 with one fma per row: column 0 is item_chain's mu_b bit for bit
-template <int G, bool NT>
-__device__ __forceinline__ void item_columns(const HessArgs& a, const int64_t* __restrict__ rowoff, const double* __restrict__ coef,
+// (Args: HessArgs, or k_morph_coarse_jac's CoarseArgs -- a.ps and a.NS are what is read)
+template <int G, bool NT, class Args>
+__device__ __forceinline__ void item_columns(const Args& a, const int64_t* __restrict__ rowoff, const double* __restrict__ coef,
                                              int64_t bin, double (&acc)[G]) {
 #pragma unroll
     for (int g = 0; g < G; ++g) acc[g] = 0.0;

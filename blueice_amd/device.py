@@ -490,6 +490,18 @@ class DeviceContext:
         self._check(self._lib.bi_expected_coarse(self._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out), ptr(status)))
         return out, status
 
+    def expected_coarse_jacobian(self, n_cells, z, rate_scale=None):
+        """The expectation per cell of the coarse binning and its first derivatives over theta = (z [d], rate_scale [S])
+        (bi_expected_coarse_jacobian) -> (mu [P, C], jac [P, d + S, C], status [P]); mu has the bits of `expected_coarse`'s
+        total, rows of single-anchor axes are 0, a dead point is nan throughout.  Raises ValueError (BI_ERR_INVALID) for more
+        than 16 coefficient columns, and what `expected_coarse` raises."""
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        mu = np.empty((P, int(n_cells)), dtype=np.float64)
+        jac = np.empty((P, self.d + self.S, int(n_cells)), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        self._check(self._lib.bi_expected_coarse_jacobian(self._h, P, ptr(z), ptr(rate_scale), ptr(mu), ptr(jac), ptr(status)))
+        return mu, jac, status
+
     def coarse_counts(self, n_cells, datasets=None):
         """The resident datasets' counts per cell of the coarse binning (bi_coarse_counts) -> [n, C]; datasets: indices [n]
         (None: all T)."""

@@ -44,11 +44,13 @@ from .hessian import chain_rule_information, chain_rule_unbounded, covariance_fr
 from .profile import bestfit_batched, supports_batched_fits
 from .sampler import sample_posterior
 from .utils import is_numeric
-from .coarse import _binned_for_gof, _prepared, coarse_counts, coarse_statistics, expected_coarse, expected_coarse_points
+from .coarse import (_binned_for_gof, _prepared, coarse_counts, coarse_information, coarse_statistics, expected_coarse,
+                     expected_coarse_band, expected_coarse_jacobian, expected_coarse_jacobian_points, expected_coarse_points)
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
            'toy_test_statistics', 'neyman_thresholds', 'expected_counts', 'expected_counts_points', 'gof_statistics', 'goodness_of_fit',
            'expected_coarse', 'expected_coarse_points', 'coarse_counts',
+           'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
            'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
            'fisher_information_points', 'fisher_information', 'expected_covariance', 'expected_errors',
            'one_parameter_interval', 'likelihood_ratio_scan', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',

@@ -180,6 +180,7 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
 
     _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'toy_test_statistics', 'neyman_thresholds', 'expected_counts',
                 'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
+                'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
                 'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance', 'fisher_information_points',
                 'fisher_information', 'expected_covariance', 'expected_errors', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
                 'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'simulate_toys_points', 'eval_toys', 'eval_toys_points',

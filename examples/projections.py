@@ -7,12 +7,17 @@ on a C2-like synthetic model (4 sources, three shape parameters with --anchors a
 data are fitted, `sample_posterior` draws samples, and for each of the three analysis dimensions `expected_coarse_points`
 returns the per-source 1-D projection at every sample -- summed over the other two dimensions on the device, a few hundred
 numbers per sample instead of the 4 x 10^6 of `expected_counts_points` -- from which the 16 / 50 / 84 % bands are taken.
+Next to the posterior's bands stand the ones `expected_coarse_band` makes from `hesse`'s covariance -- sigma_C^2 = J_C^T Sigma J_C with
+J_C = d mu_C / d theta summed over the cells on the device, no chain -- and the impact table of the expectation in a signal box.
 `goodness_of_fit(binning=)` then tests the fit on 10^3 cells of 10^3 fine bins each.
 
 --measure times `expected_coarse_points` for 64 points (total and per source) against the only route to the same numbers
 without it, `expected_counts_points` followed by the NumPy reduction, for the three projections, the 10^3 rebinning, everything summed into one cell and a
 signal box: the calls alternate, medians with quartiles are printed, and the fused kernel's achieved bytes/s (template bytes inside the
 cells over the time between the device events around its launches) stands against `stream_bandwidth` for the same rows.
+A second leg times `expected_coarse_jacobian_points` at the same points against `expected_coarse_points` (the value alone: the
+floor) and against the 2F + 1 calls of central differences, with the kernels' time the same way (--sources 9 --anchors 3: the
+16-column variant).
 """
 import argparse
 import time
@@ -24,6 +29,7 @@ from blueice_amd.synthetic import SyntheticModel
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--anchors', type=int, default=5, help='anchors per shape parameter (5: the C2 tensor, 4 GB)')
+ap.add_argument('--sources', type=int, default=4, help='sources (9 with three shape parameters: the 16-column variant of the Jacobian kernel)')
 ap.add_argument('--samples', type=int, default=2000, help='posterior samples the bands are made of')
 ap.add_argument('--toys', type=int, default=200)
 ap.add_argument('--seed', type=int, default=1)
@@ -32,7 +38,7 @@ ap.add_argument('--reps', type=int, default=7)
 ap.add_argument('--plot', default=None, help='write the projections to this file (needs matplotlib)')
 args = ap.parse_args()
 
-m = SyntheticModel(4, (args.anchors,) * 3, (100, 100, 100))
+m = SyntheticModel(args.sources, (args.anchors,) * 3, (100, 100, 100))
 t = time.perf_counter()
 lf = m.likelihood()
 lf.set_binned_data(m.counts().reshape(m.bins))
@@ -70,6 +76,28 @@ for d in dims:
     print('  %s: %d events, expected %.1f (%s per source); widest band %.2f events; largest pull in bin %d: n = %d, mu = %.1f [%.1f, %.1f]'
           % (d, n_proj[d].sum(), at_best[d].sum(), ', '.join('%.1f' % v for v in at_best[d].sum(axis=1)),
              np.max(total[2] - total[0]), worst, n_proj[d][worst], total[1][worst], total[0][worst], total[2][worst]))
+
+# the same bands without a chain: hesse's covariance carried to the cells by d mu_C / d theta (expected_coarse_band: one pass over
+# the corner rows per projection), and the impact table of the background estimate in a signal box
+t = time.perf_counter()
+cov_names, cov = lf.hesse(best, **fixed)
+at = dict(fixed, **best)
+linear = {d: lf.expected_coarse_band(projections[d], cov_names, cov, **at) for d in dims}
+signal_box = CoarseBinning(lf, keep=[], ranges={d: (40., 60.) for d in dims})                  # one cell of 20^3 fine bins
+box_mu, box_sigma, box_impacts = lf.expected_coarse_band(signal_box, cov_names, cov, **at)
+dt = time.perf_counter() - t
+print('hesse, three post-fit bands and the signal box: %.3f s' % dt)
+for d in dims:
+    chain = 0.5 * (bands[d][2, -1] - bands[d][0, -1])                                         # half the 16-84 % width of the total
+    mu_d, sigma_d, _ = linear[d]
+    widest = int(np.argmax(sigma_d))
+    print('  %s: widest band in bin %d: sigma = %.3f events from hesse, %.3f from the posterior samples (mu = %.1f)'
+          % (d, widest, sigma_d[widest], chain[widest], mu_d[widest]))
+box_chain = lf.expected_coarse_points(signal_box, samples)
+print('signal box: %.2f +- %.2f events expected (posterior samples: %.2f +- %.2f); impacts, largest first:'
+      % (box_mu, box_sigma, np.median(box_chain), 0.5 * np.diff(np.percentile(box_chain, [16, 84]))[0]))
+for name, shift in sorted(box_impacts.items(), key=lambda kv: -abs(kv[1])):
+    print('  %-22s %+8.3f events per sigma (%.1f %% of the estimate)' % (name, shift, 100 * abs(shift) / box_mu))
 
 # goodness of fit on 10 x 10 x 10 cells, against the fine binning's
 t = time.perf_counter()
@@ -127,6 +155,59 @@ if args.measure:
             print('%-5s %-10s fused %s   expected_counts_points + numpy %s   kernels %.2f ms in %d launches: %.0f GB/s (%.0f %% of the stream ceiling)'
                   % (label, 'per source' if per_source else 'total', quartiles(times['fused']), quartiles(times['host']), ms, launches,
                      gbytes / (ms * 1e-3), 100 * gbytes / (ms * 1e-3) / ceiling))
+
+    # The derivatives of the same views.  expected_coarse_jacobian_points against (a) expected_coarse_points (total) at the same
+    # points -- the value kernel over the same bytes: the floor -- and (b) the only route to the same numbers without it, central
+    # differences: 2F + 1 calls of expected_coarse_points, each of which streams every corner row again.
+    names = lf._parameter_names()
+    F = len(names)
+    d_eff = sum(1 for g in ctx.anchor_z if len(g) > 1)
+    G = 4 if 1 + d_eff + S <= 4 else 8 if 1 + d_eff + S <= 8 else 16
+    print('derivatives: F = %d parameters, G = %d coefficient columns per corner row (1 + %d + %d padded)' % (F, G, d_eff, S))
+    step = 1e-6
+    for label, b in list(projections.items()) + [('10^3', rebinned), ('all', CoarseBinning(lf, keep=[])), ('box', box)]:
+        inside = b.bin_map() >= 0
+
+        def jacobian():
+            return lf.expected_coarse_jacobian_points(b, pts)
+
+        def value():
+            return lf.expected_coarse_points(b, pts)
+
+        def differences():
+            out = [lf.expected_coarse_points(b, pts)]
+            for k in names:
+                h = step * (pts[k] if k.endswith('_rate_multiplier') else 1.0)
+                up, down = dict(pts), dict(pts)
+                up[k], down[k] = pts[k] + h, pts[k] - h
+                out.append((lf.expected_coarse_points(b, up) - lf.expected_coarse_points(b, down))
+                           / (up[k] - down[k]).reshape((P,) + (1,) * len(b.shape)))
+            return out
+
+        (_, mu, J), fd = jacobian(), differences()                                 # warm-up, and the same numbers
+        assert np.array_equal(mu, value())
+        off = max(np.max(np.abs(J[:, f] - fd[1 + f])) / np.max(np.abs(J[:, f])) for f in range(F))
+        times = {'jacobian': [], 'value': [], 'differences': []}
+        for _ in range(args.reps):                                                  # alternating
+            for key, f in (('jacobian', jacobian), ('value', value), ('differences', differences)):
+                t = time.perf_counter()
+                f()
+                times[key].append(time.perf_counter() - t)
+        kernel = {}
+        for key, f in (('jacobian', jacobian), ('value', value)):
+            ctx.profile(True)
+            ctx.profile_read()
+            f()
+            kernel[key] = ctx.profile_read()[1]
+            ctx.profile(False)
+        gbytes = P * NS * np.count_nonzero(inside) * 8 / 1e9
+        med = {k: np.median(v) for k, v in times.items()}
+        print('%-5s jacobian %s   value alone %s (x %.2f)   %d-call differences %s (x %.1f)   kernels %.2f ms: %.0f GB/s (%.0f %% of the '
+              'stream ceiling; the value kernel %.2f ms, %.0f %%)   largest |J - differences| / max |J| %.1e'
+              % (label, quartiles(times['jacobian']), quartiles(times['value']), med['jacobian'] / med['value'], 2 * F + 1,
+                 quartiles(times['differences']), med['differences'] / med['jacobian'], kernel['jacobian'],
+                 gbytes / (kernel['jacobian'] * 1e-3), 100 * gbytes / (kernel['jacobian'] * 1e-3) / ceiling,
+                 kernel['value'], 100 * gbytes / (kernel['value'] * 1e-3) / ceiling, off))
 
 if args.plot:
     import matplotlib

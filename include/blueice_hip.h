@@ -381,7 +381,21 @@ int bi_expected_counts(bi_ctx* ctx, int64_t P, const double* z, const double* ra
  *   bi_coarse_counts        out [n][C]: the counts of datasets dataset[0 .. n) (NULL: all of them, n = T) in the cells, from
  *                           the resident data in whichever form they are held (dense, or the non-empty-bin lists of
  *                           device-generated toys); a dataset index outside [0, T) is BI_ERR_INVALID.
- * Without a binning the last two return BI_ERR_STATE. */
+ *   bi_expected_coarse_jacobian   mu [P][C], bit for bit bi_expected_coarse's total, and jac [P][d + S][C], its first
+ *                           derivatives J_C = d mu_C / d theta over theta = (z_0 .. z_{d-1}, then the rate scales; bi_eval_hess's
+ *                           order; rate_scale NULL: ones): what turns a covariance of the parameters into an uncertainty band of
+ *                           a projection, sigma_C^2 = J_C^T Sigma J_C, and J_C J_C^T / mu_C is the Fisher information of the
+ *                           likelihood at that binning, cell by cell.  One pass over the corner rows of a point for all
+ *                           columns: the per-bin derivative columns of bi_eval_fisher are summed over the cells as they are
+ *                           formed, and no per-bin derivative is ever written.  Rows of single-anchor axes are 0; on an anchor
+ *                           the slopes are those of the cell the point is assigned to (bi_eval_grad's convention).  Screen,
+ *                           status [P] (nullable) and order of every sum as bi_expected_coarse: a dead point gets nan in every
+ *                           entry of mu and jac, a repeated call is bitwise identical, and a point's result does not depend on
+ *                           the other points of the call.  Limit: 1 + d_eff + S <= 16 coefficient columns, BI_ERR_INVALID
+ *                           naming the figure otherwise (as bi_eval_fisher).
+ * Without a binning the last three return BI_ERR_STATE. */
+int bi_expected_coarse_jacobian(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, double* mu, double* jac,
+                                int32_t* status);
 int bi_set_coarse_binning(bi_ctx* ctx, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds, int64_t* n_cells);
 int bi_expected_coarse(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out,
                        int32_t* status);
