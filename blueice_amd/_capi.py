@@ -82,6 +82,8 @@ SIGNATURES = {
     'bi_factored_end': (C.c_int, [_p]),
     'bi_factored_set_counts': (C.c_int, [_p, _i64, _p]),
     'bi_eval_factored': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_eval_sourcewise_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'bi_eval_sourcewise_fisher': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_fit_batched_factored': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                           _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,

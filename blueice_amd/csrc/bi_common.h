@@ -12,6 +12,8 @@
 //     tu_gof.hip          k_morph_gof (deviance + Pearson chi2 of one point per item), k_morph_expect   bi_k_gof.h
 //     tu_real.hip         k_morph_real (half-deviance + gradient against real-valued counts), k_real_expect   bi_k_real.h
 //     tu_factored.hip     k_morph_factored (value + gradient sums of one point of a source-wise model per item)   bi_k_factored.h
+//     tu_factored_curv.hip, tu_factored_fisher.hip   k_factored_curv, observed and Fisher form (Hessian and expected-information sums of
+//                         one point of a source-wise model per item)                         bi_k_factored_curv.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -19,8 +21,8 @@
 //     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
-// chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h and
-// bi_k_factored.h.
+// chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h,
+// bi_k_factored.h and (through it) bi_k_factored_curv.h.
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 
@@ -101,6 +103,17 @@ void launch_real_expect(bi_ctx* c, const RealExpectArgs& a, int64_t n_items);
 // slots per item
 int launch_morph_factored(bi_ctx* c, int SC, int EM, bool grad, const FactoredArgs& a, dim3 grid, bool nt);
 inline int factored_slots(int SC, int EM, bool grad) { return grad ? 1 + SC * (1 + EM) : 1; }
+// k_factored_curv<SC, EM, FISHER, PS, PANEL>: the Hessian's (fisher = false) or the expected information's sums of one point of a
+// source-wise model per item, Gram panel `panel` of factored_curv_panels(SC, EM); BI_ERR_INVALID for another (SC, EM, panel).
+// factored_curv_linear: the linear slots in front of panel 0's pairs; factored_curv_panel_rows: the Gram rows [lo, hi) of a panel
+int launch_factored_curv_observed(bi_ctx* c, int SC, int EM, int panel, const FactoredArgs& a, dim3 grid);
+int launch_factored_curv_fisher(bi_ctx* c, int SC, int EM, int panel, const FactoredArgs& a, dim3 grid);
+inline int launch_factored_curv(bi_ctx* c, int SC, int EM, bool fisher, int panel, const FactoredArgs& a, dim3 grid) {
+    return fisher ? launch_factored_curv_fisher(c, SC, EM, panel, a, grid) : launch_factored_curv_observed(c, SC, EM, panel, a, grid);
+}
+constexpr int factored_curv_linear(int SC, int EM, bool fisher) { return 1 + SC * (1 + EM) + (fisher ? 0 : SC * (EM * (EM - 1) / 2)); }
+constexpr int factored_curv_panel_sources(int SC, int EM) { return SC * (1 + EM) <= 16 ? SC : EM == 2 ? 2 : 1; }
+constexpr int factored_curv_panels(int SC, int EM) { return SC / factored_curv_panel_sources(SC, EM); }
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -136,7 +136,7 @@ struct HessArgs {
     int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (as morph_tiles)
 };
 
-// k_morph_factored (bi_k_factored.h): one point of a source-wise model per item.  The rows of an item are its sources' corner
+// k_morph_factored (bi_k_factored.h), k_factored_curv (bi_k_factored_curv.h): one point of a source-wise model per item.  The rows of an item are its sources' corner
 // rows back to back, source s contributing 1 << e[s] of them (e[s] < 0: a padded source, no rows); EM is the kernel's
 // template argument, the largest e[s] it is built for.
 struct FactoredArgs {
@@ -152,6 +152,11 @@ struct FactoredArgs {
     int NR;                    // rows per item
     int chunks;                // > 1: consecutive blocks work in far-apart regions of long rows (ItemTiles)
     int e[8];                  // own axes of every source
+    // k_factored_curv (bi_k_factored_curv.h) alone: coef is [items][NR][1 + EM + EM (EM - 1) / 2] in its observed form, and its
+    // Fisher form reads
+    const double* chain;       // [items][SC][1 + EM] per source: M_s, then rs_s d M_s / d (own axis j)
+    unsigned lead;             // bit s * 3 + j: slot (s, j) is the first slot of its axis (the one that counts for it)
+    signed char ax[8][3];      // the axis of slot (s, j), -1 for none
 };
 
 // k_morph_expect (bi_k_gof.h)

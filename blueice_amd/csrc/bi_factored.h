@@ -15,9 +15,10 @@
 // sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
 // Beeston-Barlow, unbinned data, device-generated toys (the counts are dense doubles from the caller).
 //
-// bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own: screen, fill on host threads, one
-// packed upload, run_item_chunks + k_finish.  The blocks per item depend on the rows' length alone (not on the batch), so a
-// point's sums are added in the same order whatever batch it is evaluated in.
+// bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own (FacBatch, which the curvature calls of
+// bi_factored_curv.h share): screen, fill on host threads, one packed upload, run_item_chunks + k_finish.  The blocks per item
+// depend on the rows' length alone (not on the batch), so a point's sums are added in the same order whatever batch it is
+// evaluated in.
 #pragma once
 
 namespace {
@@ -44,16 +45,19 @@ bool fac_geometry(const bi_ctx::Factored& m, const double* z, FacGeom& g) {
     return true;
 }
 
-// One source at one point: its corner rows, w_c, d w_c / d (own axis j), the rate M_s(z) and its slopes.  Corner c: bit of
-// the first own axis most significant; w_c the product of t or 1 - t in own-axis order from 1.0; M_s left to right from 0.0
-// (interp_mus); the slopes as PointDerivs forms them.
+// One source at one point: its corner rows, w_c, d w_c / d (own axis j), the rate M_s(z) and its slopes; with order 2 also the
+// mixed second derivatives d2 w_c / d (own axes j < k) and d2M of them, pair (j, k) at k (k - 1) / 2 + j (the morph is
+// multilinear: d_jj = 0).  Corner c: bit of the first own axis most significant; w_c the product of t or 1 - t in own-axis order
+// from 1.0; M_s left to right from 0.0 (interp_mus); the slopes as PointDerivs forms them.
 struct FacSource {
     int e, nc;
     int64_t row[1 << kFacMaxOwn];
-    double w[1 << kFacMaxOwn], dw[1 << kFacMaxOwn][kFacMaxOwn];
-    double M, dM[kFacMaxOwn];
+    double w[1 << kFacMaxOwn], dw[1 << kFacMaxOwn][kFacMaxOwn], d2w[1 << kFacMaxOwn][kFacMaxOwn];
+    double M, dM[kFacMaxOwn], d2M[kFacMaxOwn];
 
-    void at(const bi_ctx::Factored& m, int s, const FacGeom& g, bool slopes) {
+    // order: 0 the weights and M alone, 1 with the slopes, 2 with the second derivatives
+    void at(const bi_ctx::Factored& m, int s, const FacGeom& g, int order) {
+        const bool slopes = order >= 1;
         e = m.n_own[(size_t)s];
         nc = 1 << e;
         const int* ax = &m.own[(size_t)s * kFacMaxOwn];
@@ -80,6 +84,12 @@ struct FacSource {
                     if (j != i) v *= factor(c, j, false);
                 dw[c][i] = v;
             }
+            for (int k = 1; order >= 2 && k < e; ++k)
+                for (int i = 0; i < k; ++i) {
+                    double v = 1.0;
+                    for (int j = 0; j < e; ++j) v *= factor(c, j, j == i || j == k);
+                    d2w[c][k * (k - 1) / 2 + i] = v;
+                }
         }
         double v = 0.0;
         for (int c = 0; c < nc; ++c) {
@@ -92,17 +102,22 @@ struct FacSource {
             for (int c = 0; c < nc; ++c) dv += dw[c][i] * m.h_mus[(size_t)row[c]];
             dM[i] = dv;
         }
+        for (int x = 0; order >= 2 && x < e * (e - 1) / 2; ++x) {
+            double dv = 0.0;
+            for (int c = 0; c < nc; ++c) dv += d2w[c][x] * m.h_mus[(size_t)row[c]];
+            d2M[x] = dv;
+        }
     }
 };
 
-// the early exits of one point, in screen_point's order: dataset, anchor box (every axis), rates
-int32_t fac_screen(const bi_ctx::Factored& m, const double* z, const double* rs, int64_t ds, FacGeom& g) {
-    if (ds < 0 || ds >= m.T) return BI_ST_BAD_DATASET;
+// the early exits of one point, in screen_point's order: dataset (where the call reads data), anchor box (every axis), rates
+int32_t fac_screen(const bi_ctx::Factored& m, const double* z, const double* rs, int64_t ds, bool dataset_test, FacGeom& g) {
+    if (dataset_test && (ds < 0 || ds >= m.T)) return BI_ST_BAD_DATASET;
     if (!fac_geometry(m, z, g)) return BI_ST_OUT_OF_BOUNDS;
     const double inf = std::numeric_limits<double>::infinity();
     FacSource fs;
     for (int s = 0; s < m.S; ++s) {
-        fs.at(m, s, g, false);
+        fs.at(m, s, g, 0);
         const double r = rs ? fs.M * rs[s] : fs.M;
         if (!(r >= 0 && r < inf)) return BI_ST_UNPHYSICAL;
     }
@@ -118,115 +133,157 @@ int fac_check(bi_ctx* c, const char* who, bool need_counts) {
     return BI_OK;
 }
 
-int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
-                  int32_t* status) {
-    const bi_ctx::Factored& m = c->fac;
-    const int d = m.d, S = m.S;
-    const bool want_grad = grad != nullptr;
-    const int SC = S <= 2 ? 2 : S <= 4 ? 4 : 8;
-    const int EM = std::max(1, m.max_own);
-    const int W = 1 + EM, NR = m.n_rows_point, NSL = factored_slots(SC, EM, want_grad);
-    const double inf = std::numeric_limits<double>::infinity();
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    HIP_TRY(c, hipSetDevice(c->device));
-
-    std::vector<int32_t> st((size_t)P);
-    parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
-        FacGeom g;
-        for (int64_t p = lo; p < hi; ++p) {
-            ll[p] = -inf;
-            for (int j = 0; want_grad && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
-            st[(size_t)p] = fac_screen(m, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, dataset ? dataset[p] : 0, g);
-        }
-    });
+// What bi_eval_factored, bi_eval_sourcewise_hess and bi_eval_sourcewise_fisher share: the screen of the P points, the descriptors
+// of the live ones (filled on host threads), their one packed upload, and the launch of a kernel over them in sub-batches.
+//   order 0 / 1    value / with the gradient's columns (k_morph_factored)
+//   order 2        with the second-order columns chi and d2M (k_factored_curv, observed form)
+//   order 3        no data: the first-order columns and the chain coefficients of the unbounded counts (k_factored_curv, Fisher form)
+struct FacBatch {
+    bi_ctx* c;
+    const bi_ctx::Factored& m;
+    int order, d, S, SC, EM, W, NX, WC, NR;
     std::vector<int64_t> live;
-    live.reserve((size_t)P);
-    for (int64_t p = 0; p < P; ++p) {
-        if (status) status[p] = st[(size_t)p];
-        if (!st[(size_t)p]) live.push_back(p);
-    }
-    const int64_t n_items = (int64_t)live.size();
-    if (n_items == 0) return BI_OK;
+    int64_t n_items = 0;
+    std::vector<int64_t> rowoff, cnt_off;
+    std::vector<double> coef, rates, chain;
+    std::vector<double> hM, hdM, hd2M;          // [n][S], [n][S][kFacMaxOwn] (order >= 1), [n][S][kFacMaxOwn] (order 2): the chain rule's
+    PackedUpload pu;
+    size_t first_extra = 0;                     // index of the caller's first own part in pu
 
-    // descriptors of the live points, and what the chain rule needs of them on the host: M_s and its slopes
-    const size_t n = (size_t)n_items;
-    std::vector<int64_t> rowoff(n * NR), cnt_off(n), perm(n * NSL, -1);
-    std::vector<double> coef(n * NR * W, 0.0), rates(n * SC, 0.0), slot_lg(n * NSL, 0.0);
-    std::vector<double> hM(want_grad ? n * S : 0), hdM(want_grad ? n * S * kFacMaxOwn : 0);
-    parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
-        FacGeom g;
-        FacSource fs;
-        for (int64_t i = lo; i < hi; ++i) {
-            const int64_t p = live[(size_t)i];
-            const int64_t ds = dataset ? dataset[p] : 0;
-            fac_geometry(m, z ? z + p * d : nullptr, g);
-            int k = 0;
-            for (int s = 0; s < S; ++s) {
-                fs.at(m, s, g, want_grad);
-                for (int cnr = 0; cnr < fs.nc; ++cnr, ++k) {
-                    rowoff[(size_t)i * NR + k] = fs.row[cnr] * m.Bp;
-                    double* q = &coef[((size_t)i * NR + k) * W];
-                    q[0] = fs.w[cnr];
-                    for (int j = 0; want_grad && j < fs.e; ++j) q[1 + j] = fs.dw[cnr][j];
+    FacBatch(bi_ctx* ctx, int order_)
+        : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
+          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point) {}
+
+    // reset(p) writes the caller's defaults of point p; status [P] (nullable) gets every point's bits
+    template <class F>
+    void screen(int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, int32_t* status, F reset) {
+        std::vector<int32_t> st((size_t)P);
+        const bool dataset_test = order != 3;
+        parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
+            FacGeom g;
+            for (int64_t p = lo; p < hi; ++p) {
+                reset(p);
+                st[(size_t)p] = fac_screen(m, z ? z + p * d : nullptr, rate_scale ? rate_scale + p * S : nullptr, dataset ? dataset[p] : 0,
+                                           dataset_test, g);
+            }
+        });
+        live.reserve((size_t)P);
+        for (int64_t p = 0; p < P; ++p) {
+            if (status) status[p] = st[(size_t)p];
+            if (!st[(size_t)p]) live.push_back(p);
+        }
+        n_items = (int64_t)live.size();
+    }
+
+    // the descriptors of the live points, and what the chain rule needs of them on the host: M_s, its slopes and second differences
+    void fill(const double* z, const double* rate_scale, const int64_t* dataset) {
+        const size_t n = (size_t)n_items;
+        const int so = order == 0 ? 0 : order == 2 ? 2 : 1;      // what FacSource::at computes (the Fisher form: first order)
+        rowoff.assign(n * NR, 0);
+        cnt_off.assign(n, 0);
+        coef.assign(n * NR * WC, 0.0);
+        rates.assign(n * SC, 0.0);
+        if (order == 3) chain.assign(n * SC * W, 0.0);
+        if (order >= 1) { hM.resize(n * S); hdM.resize(n * S * kFacMaxOwn); }
+        if (order == 2) hd2M.resize(n * S * kFacMaxOwn);
+        parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
+            FacGeom g;
+            FacSource fs;
+            for (int64_t i = lo; i < hi; ++i) {
+                const int64_t p = live[(size_t)i];
+                const int64_t ds = dataset ? dataset[p] : 0;
+                fac_geometry(m, z ? z + p * d : nullptr, g);
+                int k = 0;
+                for (int s = 0; s < S; ++s) {
+                    fs.at(m, s, g, so);
+                    const double rs = rate_scale ? rate_scale[p * S + s] : 1.0;
+                    for (int cnr = 0; cnr < fs.nc; ++cnr, ++k) {
+                        rowoff[(size_t)i * NR + k] = fs.row[cnr] * m.Bp;
+                        double* q = &coef[((size_t)i * NR + k) * WC];
+                        q[0] = fs.w[cnr];
+                        for (int j = 0; order >= 1 && j < fs.e; ++j) q[1 + j] = fs.dw[cnr][j];
+                        for (int x = 0; order == 2 && x < fs.e * (fs.e - 1) / 2; ++x) q[W + x] = fs.d2w[cnr][x];
+                    }
+                    rates[(size_t)i * SC + s] = rate_scale ? fs.M * rate_scale[p * S + s] : fs.M;
+                    if (order >= 1) {
+                        hM[(size_t)i * S + s] = fs.M;
+                        for (int j = 0; j < fs.e; ++j) hdM[((size_t)i * S + s) * kFacMaxOwn + j] = fs.dM[j];
+                    }
+                    for (int x = 0; order == 2 && x < fs.e * (fs.e - 1) / 2; ++x) hd2M[((size_t)i * S + s) * kFacMaxOwn + x] = fs.d2M[x];
+                    if (order == 3) {
+                        double* q = &chain[((size_t)i * SC + s) * W];
+                        q[0] = fs.M;
+                        for (int j = 0; j < fs.e; ++j) q[1 + j] = rs * fs.dM[j];
+                    }
                 }
-                rates[(size_t)i * SC + s] = rate_scale ? fs.M * rate_scale[p * S + s] : fs.M;
-                if (want_grad) {
-                    hM[(size_t)i * S + s] = fs.M;
-                    for (int j = 0; j < fs.e; ++j) hdM[((size_t)i * S + s) * kFacMaxOwn + j] = fs.dM[j];
+                cnt_off[(size_t)i] = order == 3 ? 0 : ds * m.Bp;
+            }
+        });
+    }
+
+    // one packed copy of the descriptors and of the caller's `extra` parts (pu.dev(first_extra + k)); out_doubles results behind them
+    int upload(std::vector<std::pair<const void*, size_t>> extra, size_t out_doubles) {
+        std::vector<std::pair<const void*, size_t>> parts = {
+            {rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
+            {rates.data(), rates.size() * sizeof(double)}, {cnt_off.data(), cnt_off.size() * sizeof(int64_t)},
+            {chain.data(), chain.size() * sizeof(double)}};
+        first_extra = parts.size();
+        parts.insert(parts.end(), extra.begin(), extra.end());
+        return packed_upload(c, parts, out_doubles * sizeof(double), pu);
+    }
+    const double* out() const { return (const double*)pu.host_out(); }
+
+    // One kernel over the live points: nsl result slots per item, perm / slot_lg [n][nsl] (device) where a slot's sum goes and
+    // what k_finish subtracts from it.  The blocks of an item depend on the rows' length alone; sub-batches keep the partial
+    // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.
+    template <class L>
+    int run(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+        FactoredArgs a{};
+        a.ps = (const double*)m.ps.p;
+        a.counts = (const double*)m.counts.p;
+        a.n_tiles = (int)(m.Bp / kTile);
+        a.NR = NR;
+        a.chunks = (int)c->tile_chunks;
+        a.lead = 0u;
+        bool seen[kFacMaxDim] = {};
+        for (int s = 0; s < 8; ++s) {
+            a.e[s] = s < S ? m.n_own[(size_t)s] : -1;
+            for (int j = 0; j < kFacMaxOwn; ++j) {
+                const int ax = (s < S && j < m.n_own[(size_t)s]) ? m.own[(size_t)s * kFacMaxOwn + j] : -1;
+                a.ax[s][j] = (signed char)ax;
+                if (ax >= 0 && !seen[ax]) {
+                    seen[ax] = true;
+                    a.lead |= 1u << (s * 3 + j);
                 }
             }
-            cnt_off[(size_t)i] = ds * m.Bp;
-            for (int q = 0; q < NSL; ++q) perm[(size_t)i * NSL + q] = i * NSL + q;
-            slot_lg[(size_t)i * NSL] = m.h_lgsum[(size_t)ds];
         }
-    });
-    PackedUpload pu;
-    int rc = packed_upload(c, {{rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
-                               {rates.data(), rates.size() * sizeof(double)}, {cnt_off.data(), cnt_off.size() * sizeof(int64_t)},
-                               {perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}},
-                           n * NSL * sizeof(double), pu);
-    if (rc) return rc;
-
-    FactoredArgs a{};
-    a.ps = (const double*)m.ps.p;
-    a.counts = (const double*)m.counts.p;
-    a.n_tiles = (int)(m.Bp / kTile);
-    a.NR = NR;
-    a.chunks = (int)c->tile_chunks;
-    for (int s = 0; s < 8; ++s) a.e[s] = s < S ? m.n_own[(size_t)s] : -1;
-    const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
-    // the blocks of an item: by the rows' length alone.  Sub-batches keep the partial sums of one run_item_chunks call bounded.
-    const int nbx = std::min(a.n_tiles, kFacBlocks);
-    const int64_t per_call = std::max<int64_t>(1, kFacPartialDoubles / ((int64_t)nbx * NSL));
-    for (int64_t j0 = 0; j0 < n_items; j0 += per_call) {
-        const int64_t nj = std::min(per_call, n_items - j0);
-        rc = run_item_chunks(c, nj, a.n_tiles, NSL, pu.dev<int64_t>(4) + j0 * NSL, pu.dev<double>(5) + j0 * NSL, (double*)pu.host_out(), nullptr,
-                             "bi_eval_factored",
-                             [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
-                                 FactoredArgs b = a;
-                                 const int64_t at = j0 + i0;
-                                 b.rowoff = pu.dev<int64_t>(0) + at * NR;
-                                 b.coef = pu.dev<double>(1) + at * NR * W;
-                                 b.rates = pu.dev<double>(2) + at * SC;
-                                 b.item_cnt = pu.dev<int64_t>(3) + at;
-                                 b.partial = partial;
-                                 b.pflags = pflags;
-                                 const int e = launch_morph_factored(c, SC, EM, want_grad, b, grid, nt);
-                                 return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", SC, EM) : BI_OK;
-                             },
-                             nbx);
-        if (rc) return rc;
+        const int nbx = std::min(a.n_tiles, kFacBlocks);
+        const int64_t per_call = std::max<int64_t>(1, kFacPartialDoubles / ((int64_t)nbx * nsl));
+        for (int64_t j0 = 0; j0 < n_items; j0 += per_call) {
+            const int64_t nj = std::min(per_call, n_items - j0);
+            const int rc = run_item_chunks(c, nj, a.n_tiles, nsl, perm + j0 * nsl, slot_lg + j0 * nsl, (double*)pu.host_out(), nullptr, what,
+                                           [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
+                                               FactoredArgs b = a;
+                                               const int64_t at = j0 + i0;
+                                               b.rowoff = pu.dev<int64_t>(0) + at * NR;
+                                               b.coef = pu.dev<double>(1) + at * NR * WC;
+                                               b.rates = pu.dev<double>(2) + at * SC;
+                                               b.item_cnt = pu.dev<int64_t>(3) + at;
+                                               b.chain = pu.dev<double>(4) + at * SC * W;
+                                               b.partial = partial;
+                                               b.pflags = pflags;
+                                               return launch(b, grid);
+                                           },
+                                           nbx);
+            if (rc) return rc;
+        }
+        return BI_OK;
     }
 
-    // the chain rule to [d + S], sources ascending, own axes ascending within a source
-    const double* out = (const double*)pu.host_out();
-    std::vector<double> gz((size_t)std::max(d, 1));
-    for (int64_t i = 0; i < n_items; ++i) {
+    // the chain rule of item i's gradient sums h (the slots of k_morph_factored<.., GRAD>) to gp [d + S]: sources ascending, own
+    // axes ascending within a source; gz [max(d, 1)] is the caller's scratch
+    void gradient(int64_t i, const double* h, const double* rate_scale, double* gp, std::vector<double>& gz) const {
         const int64_t p = live[(size_t)i];
-        const double* h = out + (size_t)i * NSL;
-        ll[p] = h[0];
-        if (!want_grad || !std::isfinite(h[0])) continue;
-        double* gp = grad + p * (d + S);
         std::fill(gz.begin(), gz.end(), 0.0);
         for (int s = 0; s < S; ++s) {
             const double M = hM[(size_t)i * S + s], G = h[1 + s];
@@ -239,6 +296,48 @@ int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scal
             }
         }
         for (int i2 = 0; i2 < d; ++i2) gp[i2] = gz[(size_t)i2];
+    }
+};
+
+int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
+                  int32_t* status) {
+    const bool want_grad = grad != nullptr;
+    FacBatch b(c, want_grad ? 1 : 0);
+    const int d = b.d, S = b.S, NSL = factored_slots(b.SC, b.EM, want_grad);
+    const double inf = std::numeric_limits<double>::infinity();
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    b.screen(P, z, rate_scale, dataset, status, [&](int64_t p) {
+        ll[p] = -inf;
+        for (int j = 0; want_grad && j < d + S; ++j) grad[p * (d + S) + j] = qnan;
+    });
+    const int64_t n_items = b.n_items;
+    if (n_items == 0) return BI_OK;
+    b.fill(z, rate_scale, dataset);
+    const size_t n = (size_t)n_items;
+    std::vector<int64_t> perm(n * NSL);
+    std::vector<double> slot_lg(n * NSL, 0.0);
+    for (size_t q = 0; q < perm.size(); ++q) perm[q] = (int64_t)q;
+    for (size_t i = 0; i < n; ++i) slot_lg[i * NSL] = b.m.h_lgsum[(size_t)(dataset ? dataset[b.live[i]] : 0)];
+    int rc = b.upload({{perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}}, n * NSL);
+    if (rc) return rc;
+    const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
+    rc = b.run(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
+               [&](const FactoredArgs& a, dim3 grid) {
+                   const int e = launch_morph_factored(c, b.SC, b.EM, want_grad, a, grid, nt);
+                   return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", b.SC, b.EM) : BI_OK;
+               });
+    if (rc) return rc;
+
+    const double* out = b.out();
+    std::vector<double> gz((size_t)std::max(d, 1));
+    for (int64_t i = 0; i < n_items; ++i) {
+        const int64_t p = b.live[(size_t)i];
+        const double* h = out + (size_t)i * NSL;
+        ll[p] = h[0];
+        if (!want_grad || !std::isfinite(h[0])) continue;
+        b.gradient(i, h, rate_scale, grad + p * (d + S), gz);
     }
     return BI_OK;
 }

@@ -689,6 +689,17 @@ def hesse(lf, values, livetime_days=None, datasets=None, information='observed',
 
 # ---- expected (Fisher) information ------------------------------------------------------------------------------------
 
+def _binned_for_fisher(lf, what):
+    """The gate of the expected information: a `BinnedLogLikelihood` without Beeston-Barlow (`_binned_for_gof`), or a prepared
+    source-wise model (its context has eval_fisher; everything else behind `_binned_for_gof` keeps refusing it)."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if isinstance(lf, SourceWiseBinnedLogLikelihood):
+        if not lf.is_prepared:
+            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+        return lf
+    return _binned_for_gof(lf, what)
+
+
 def fisher_information_points(lf, points, livetime_days=None, priors=True):
     """The expected (Fisher) information of the binned likelihood at P truths, before any data exist:
         I_qr = sum_b d_q mu_b d_r mu_b / mu_b    (- the curvature of the log priors on the diagonal, unless priors=False)
@@ -700,7 +711,7 @@ def fisher_information_points(lf, points, livetime_days=None, priors=True):
     another value of a parameter (a signal multiplier of 0, a truth on an anchor) holds unbounded information on it: it is
     left out of I and the parameter is flagged.  A truth outside the anchor box, with unphysical rates or with a negative
     expectation gives a nan matrix.  On an anchor I is that of the cell the point is assigned to."""
-    _binned_for_gof(lf, 'fisher_information_points')
+    _binned_for_fisher(lf, 'fisher_information_points')
     z, scale, _ = lf._batch_terms(points, livetime_days)
     P = len(z)
     info, _, unb, _ = lf.ctx.eval_fisher(z if z.shape[1] else None, scale)

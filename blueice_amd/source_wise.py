@@ -3,7 +3,9 @@
     lf = SourceWiseBinnedLogLikelihood(pdf_base_config, likelihood_config=None, **overrides)
     lf.add_rate_parameter(...); lf.add_shape_parameter(...); lf.prepare(); lf.set_data(d)
     lf(**params), lf.eval_points, lf.value_and_gradient, lf.values_and_gradients,
-    lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval
+    lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval,
+    lf.value_gradient_hessian, lf.values_gradients_hessians, lf.bestfit_minuit, blueice_amd.inference.hesse(lf, values),
+    lf.fisher_information_points, lf.expected_covariance, lf.expected_errors
 
 `BinnedLogLikelihood` morphs over ONE tensor-product grid of all shape parameters: prod n_i anchor models in HBM and S 2^d
 rows per evaluation, which caps the number of shape parameters at a handful.  Here every source morphs over the parameters
@@ -13,10 +15,14 @@ source s keeps prod_{i in O_s} n_i rows, and an evaluation reads sum_s 2^e_s of 
 bi_eval_factored / bi_fit_batched_factored, include/blueice_hip.h).  `prepare()` builds models only at the anchors some source
 needs and never enumerates the product grid.
 
+Second derivatives are analytic (bi_eval_sourcewise_hess, bi_eval_sourcewise_fisher): each source is multilinear over at most
+three own axes, so the Hessian and the expected information over all d + S parameters follow from one Gram matrix over at most
+32 per-source basis columns and a few linear sums, whatever the number of shape parameters.  `lf.hesse` and
+`lf.fisher_information` stay unbound (their messages name the spellings that work).
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, toys, Hessians and hesse, goodness of fit, Asimov data, Fisher information, grids, coarse views and the
-ensemble sampler.
+full_output calls, toys, goodness of fit, Asimov data, grids, coarse views, expected counts and the ensemble sampler.
 """
 from collections import OrderedDict
 
@@ -45,8 +51,8 @@ def _find_cell(g, z):
 class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
-    eval_grad, fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the DeviceContext (plans, toys,
-    Hessians, the sampler ...) has a meaning here and is an AttributeError."""
+    eval_grad, eval_hess, eval_fisher, fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the
+    DeviceContext (plans, toys, the sampler ...) has a meaning here and is an AttributeError."""
 
     def __init__(self, device=None):
         self._dev = DeviceContext(device)
@@ -135,6 +141,35 @@ class SourceWiseContext:
         dev._check(dev._lib.bi_eval_factored(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], status
 
+    def eval_hess(self, z, rate_scale=None, dataset=None):
+        """Value, gradient and analytic Hessian (bi_eval_sourcewise_hess) -> (ll [P], dll/dz [P, d], dll/drate_scale [P, S],
+        H [P, d + S, d + S] over (z, rate_scale), status [P]): DeviceContext.eval_hess's shapes.  ll, the gradient and the status
+        are eval_grad's bits; H is nan wherever ll is not finite."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        F = self.d + self.S
+        ll = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, F), dtype=np.float64)
+        hess = np.empty((P, F, F), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_hess(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(hess),
+                                                    ptr(status)))
+        return ll, grad[:, :self.d], grad[:, self.d:], hess, status
+
+    def eval_fisher(self, z, rate_scale=None):
+        """The expected (Fisher) information at P truths, no counts needed (bi_eval_sourcewise_fisher) -> (info [P, d + S, d + S],
+        total expectation [P], unbounded [P, d + S], status [P]): DeviceContext.eval_fisher's shapes and meaning."""
+        dev = self._dev
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        F = self.d + self.S
+        info = np.empty((P, F, F), dtype=np.float64)
+        total = np.empty(P, dtype=np.float64)
+        unbounded = np.zeros((P, F), dtype=np.int64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_fisher(dev._h, P, ptr(z), ptr(rate_scale), ptr(info), ptr(total), ptr(unbounded),
+                                                      ptr(status)))
+        return info, total, unbounded, status
+
     def fit_batched(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters,
                     priors=None):
         """bi_fit_batched_factored: DeviceContext.fit_batched with the source-wise likelihood as the objective"""
@@ -167,10 +202,20 @@ class SourceWiseContext:
         return out
 
 
+# the two bound names that stay refused although the layer behind them exists, and the spellings that work
+_REFUSED_SPELLINGS = {
+    'hesse': "blueice_amd.inference.hesse(lf, values) (or lf.bestfit_minuit for the errors of a fit)",
+    'fisher_information': "lf.fisher_information_points(points), lf.expected_covariance(**truth) or lf.expected_errors(**truth)",
+}
+
+
 def _refused(name):
     def method(self, *args, **kwargs):
-        raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient and "
-                                  "the fit, scan and interval layers are" % name)
+        if name in _REFUSED_SPELLINGS:
+            raise NotImplementedError("lf.%s is not bound on a source-wise model (SourceWiseBinnedLogLikelihood); call %s"
+                                      % (name, _REFUSED_SPELLINGS[name]))
+        raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
+                                  "Hessian, expected information and the fit, scan and interval layers are" % name)
     method.__name__ = name
     return method
 
@@ -181,13 +226,17 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
     _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'toy_test_statistics', 'neyman_thresholds', 'expected_counts',
                 'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
                 'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
-                'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance', 'fisher_information_points',
-                'fisher_information', 'expected_covariance', 'expected_errors', 'hesse', 'bestfit_minuit', 'sample_posterior', 'bestfit_emcee',
+                'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
+                'fisher_information', 'hesse', 'sample_posterior', 'bestfit_emcee',
                 'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'simulate_toys_points', 'eval_toys', 'eval_toys_points',
-                'value_gradient_hessian', 'values_gradients_hessians', 'ps_interpolator', 'n_model_events_interpolator')
+                'ps_interpolator', 'n_model_events_interpolator')
 
     supports_gradient = True
-    supports_hessian = False
+
+    @property
+    def supports_hessian(self):
+        """True once data are set: the analytic Hessian of bi_eval_sourcewise_hess (`hessian_method` is 'analytic')"""
+        return self.ctx is not None and bool(self.is_data_set)
 
     def __init__(self, pdf_base_config, likelihood_config=None, **kwargs):
         super().__init__(pdf_base_config, likelihood_config, **kwargs)

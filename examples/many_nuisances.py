@@ -9,12 +9,17 @@ evaluation -- and the native fit loop floats all twelve parameters.
 
 (1) prepare(): models at the 100 projected anchors only; set_data(): the events binned on the device;
 (2) bestfit_batched: every rate and every constrained shape parameter floating;
-(3) likelihood_ratio_scan over the signal's rate multiplier: --scan hypotheses profiled in lock-step (bi_fit_batched_factored).
+(3) likelihood_ratio_scan over the signal's rate multiplier: --scan hypotheses profiled in lock-step (bi_fit_batched_factored);
+(4) bestfit_minuit: the fit with its parabolic errors from the analytic Hessian (bi_eval_sourcewise_hess), the correlation matrix
+    (inference.hesse), and expected_errors at the truth before any data (bi_eval_sourcewise_fisher).
 
 --measure times the C ABI instead, at a shape BOTH routes can hold: d = 4, S = 4, one own axis per source, 5 anchors, 100^3
 bins, dense data, 64 points per call -- bi_eval_factored with its gradient (8 rows per point) against bi_eval_grad on the
 expanded 5^4 grid (64 rows per point; 20 GB of templates), alternated calls, medians with quartiles, and the kernel's bytes
-per second against the stream_bandwidth(items = 64, rows = 8) probe of the same device.
+per second against the stream_bandwidth(items = 64, rows = 8) probe of the same device.  Then the second-order calls at the same
+shape: bi_eval_sourcewise_hess against the (2 F + 1) P gradient points of the central differences it replaces (one bi_eval_factored
+call, as the class takes them) and against bi_eval_hess on the expanded grid, bi_eval_sourcewise_fisher against bi_eval_fisher
+there; and both on a panelled class (8 sources x 2 own axes of the same 4, four Gram panels), which only the source-wise route holds.
 """
 import argparse
 import time
@@ -94,6 +99,66 @@ def measure():
               % (name, quartiles(ks), n_rows, Bp, P, n_rows * Bp * 8 * P / 1e9, n_rows * Bp * 8 * P / med / 1e12))
     for nt in (True, False):
         print('stream_bandwidth(items = 64, rows = 8, nontemporal = %s): %.2f TB/s' % (nt, full.stream_bandwidth(items=64, rows=8, nontemporal=nt) / 1e3))
+    measure_curvature(fac, full, z, r, d, S, P, rng, g, B)
+
+
+def alternate(calls, P):
+    times = {name: [] for name, _ in calls}
+    for rnd in range(3 + args.rounds):              # three warm-up rounds; the calls alternate inside every round
+        for name, call in calls:
+            t0 = time.perf_counter()
+            call()
+            if rnd >= 3:
+                times[name].append(time.perf_counter() - t0)
+    for name, _ in calls:
+        print('%2d points per call, %-58s %s' % (P, name, quartiles(times[name])), flush=True)
+
+
+def measure_curvature(fac, full, z, r, d, S, P, rng, g, B):
+    F = d + S
+    a, b = fac.eval_hess(z, r), full.eval_hess(z, r)
+    i1, i2 = fac.eval_fisher(z, r), full.eval_fisher(z, r)
+    print('agreement over %d points: max |Hessian difference| %.2g, max |information difference| %.2g of the largest entry'
+          % (P, np.max(np.abs(a[3] - b[3])) / np.max(np.abs(b[3])), np.max(np.abs(i1[0] - i2[0])) / np.max(np.abs(i2[0]))))
+    # the points of central gradient differences: every point itself and displaced along each of the F parameters, both ways
+    zz, rr = np.tile(z, (2 * F + 1, 1)), np.tile(r, (2 * F + 1, 1))
+    for j in range(F):
+        for k, sign in enumerate((1.0, -1.0)):
+            rows = slice((1 + 2 * j + k) * P, (2 + 2 * j + k) * P)
+            if j < d:
+                zz[rows, j] = np.clip(zz[rows, j] + sign * 1e-4, -2.0, 2.0)
+            else:
+                rr[rows, j - d] += sign * 1e-5
+    alternate([('bi_eval_sourcewise_hess', lambda: fac.eval_hess(z, r)),
+               ('bi_eval_factored + gradient at (2 F + 1) P = %d points' % len(zz), lambda: fac.eval_grad(zz, rr)),
+               ('bi_eval_hess, expanded 5^%d grid' % d, lambda: full.eval_hess(z, r)),
+               ('bi_eval_sourcewise_fisher', lambda: fac.eval_fisher(z, r)),
+               ('bi_eval_fisher, expanded grid', lambda: full.eval_fisher(z, r))], P)
+    full.close()
+    fac.close()
+    # a panelled class: 8 sources that own two of the four axes each (24 basis columns, four Gram panels of two sources)
+    from blueice_amd.source_wise import SourceWiseContext
+    own = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3), (0, 1), (2, 3)]
+    n_a = len(g)
+    pan = SourceWiseContext(0)
+    pan.begin_model([g] * d, 8, B, own)
+    total = np.zeros(B)
+    for s in range(8):
+        for k in range(n_a * n_a):
+            row = rng.random(B) + 0.05
+            row /= row.sum()
+            mu = 1.25e6 * (1 + s % 4) * (1 + 0.02 * g[k // n_a]) * (1 + 0.01 * g[k % n_a])
+            pan.set_anchor(s, k, row, mu)
+            if k == (n_a * n_a) // 2:
+                total += mu * row
+    pan.end_model()
+    pan.set_counts(rng.poisson(total).astype(float))
+    r8 = rng.uniform(0.8, 1.2, (P, 8))
+    print('panelled class <8, 2>: %d rows, %.2f GB resident, 32 rows per point, four launches per call' % (8 * n_a * n_a, 8 * n_a * n_a * B * 8 / 1e9))
+    alternate([('bi_eval_sourcewise_hess, <8, 2> in four panels', lambda: pan.eval_hess(z, r8)),
+               ('bi_eval_factored + gradient, <8, 2>', lambda: pan.eval_grad(z, r8)),
+               ('bi_eval_sourcewise_fisher, <8, 2> in four panels', lambda: pan.eval_fisher(z, r8))], P)
+    pan.close()
 
 
 if args.measure:
@@ -133,3 +198,18 @@ print('(3) likelihood_ratio_scan over s0_rate_multiplier: %d hypotheses, 11 nuis
       '2 dlnL <= 1 on [%.3f, %.3f]' % (args.scan, dt, grid[np.argmin(scan)], inside.min(), inside.max()))
 limit = lf.one_parameter_interval('s0_rate_multiplier', 3.0, confidence_level=0.9, kind='upper')
 print('    90 %% upper limit on s0_rate_multiplier (one_parameter_interval): %.4f' % limit)
+
+t0 = time.perf_counter()
+fit, ll_fit = lf.bestfit_minuit()
+order = [k for k in fit if not k.endswith('_error')]
+print('(4) bestfit_minuit: max ll %.4f, errors from the analytic Hessian over all %d parameters, %.3f s' % (ll_fit, len(order), time.perf_counter() - t0))
+truth = dict([('s%d_rate_multiplier' % s, 1.0) for s in range(4)] + [(n, 0.0) for n in names])
+expected = lf.expected_errors(**truth)
+for k in order:
+    print('    %-20s %8.4f +- %.4f     expected error at the truth %.4f' % (k, fit[k], fit[k + '_error'], expected[k]))
+from blueice_amd.inference import hesse  # noqa: E402
+cov_names, cov = hesse(lf, {k: fit[k] for k in order})
+sigma = np.sqrt(np.diag(cov))
+print('    correlation matrix (%s):' % ', '.join(k.replace('_rate_multiplier', '') for k in cov_names))
+for row in cov / np.outer(sigma, sigma):
+    print('    ' + ' '.join('%6.2f' % v for v in row))

@@ -568,6 +568,36 @@ int bi_fit_batched_factored(bi_ctx* ctx, int64_t P, int F, const int32_t* var_ki
                             int max_iter, const double* prior_mean, const double* prior_sigma, const double* prior_const,
                             double* x_out, double* f_out, int32_t* flags_out, int64_t* counters);
 
+/* ... second derivatives of a source-wise model.  theta = (z_0 .. z_{d-1}, rs_0 .. rs_{S-1}), F = d + S.  Source s is multilinear
+ * over its own axes, so with the per-bin basis columns tau_s, ups_s,j (above) and chi_s,jk = sum_c d_j d_k w_c p_s,c,b (j < k;
+ * d_jj = 0) every derivative of mu_b is a fixed combination of at most sum_s (1 + e_s) <= 32 columns, whatever d is:
+ *     d_q mu_b = sum_a C_qa u_a,b      u = (tau_s, ups_s,j);   C[rs_s, tau_s] = M_s;   for i = O_s[j]:   C[z_i, tau_s] += rs_s d_j M_s,
+ *                                      C[z_i, ups_s,j] += rs_s M_s
+ * The device forms the linear sums L_x = sum_b f_b x_b over x = tau_s, ups_s,j, chi_s,jk and the Gram matrix of u (in panels of
+ * whole sources where it exceeds the registers of a thread), the host contracts them in extended precision in a fixed order.
+ *   bi_eval_sourcewise_hess     ll [P], grad [P][F]: bit for bit what bi_eval_factored returns with a gradient, and the same status
+ *                               [P] (nullable), early exits and defaults.  hess [P][F][F] = -C Q C^T + the second-order terms,
+ *                               Q = sum_b (n_b / mu_b^2) u u^T:
+ *                                   (rs_s, z_i)   d_j M_s L_tau_s + M_s L_ups_s,j
+ *                                   (z_i, z_i)    2 rs_s d_j M_s L_ups_s,j
+ *                                   (z_i, z_k)    rs_s (d_j d_k M_s L_tau_s + d_j M_s L_ups_s,k + d_k M_s L_ups_s,j + M_s L_chi_s,jk)
+ *                               summed over the sources that own the axes; full and exactly symmetric (written from one
+ *                               triangle); rows and columns of axes nobody owns are 0; nan wherever ll is not finite; on an
+ *                               anchor the Hessian of the cell the point is assigned to.  Needs counts (BI_ERR_STATE without).
+ *   bi_eval_sourcewise_fisher   bi_eval_fisher's contract for this model: info [P][F][F] = C Q' C^T, Q' = sum_{mu_b > 0} u u^T / mu_b,
+ *                               positive semi-definite by construction; total [P] or NULL = sum_b mu_b, from the fma chain of
+ *                               the value kernel's mu_b; unbounded [P][F] or NULL = the number of bins with mu_b == 0 and
+ *                               d_q mu_b != 0, which are left out of info; rejected points: a nan matrix, a nan total, zero
+ *                               counts and their status bit (box and rate tests alone: no dataset).  Needs the source-wise
+ *                               model and nothing else: no counts are read or touched.
+ * Both: P = 0 returns BI_OK with no device work; no floating-point atomics; a repeated call is bitwise identical and a point's
+ * result does not depend on the batch it is evaluated in.  The limits are the model's own (d <= 32, S <= 8, e_s <= 3).
+ * (The names say "sourcewise": these two are layers over the model, not parts of the bi_factored_* store's life cycle.) */
+int bi_eval_sourcewise_hess(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                            double* grad, double* hess, int32_t* status);
+int bi_eval_sourcewise_fisher(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, double* info, double* total,
+                              int64_t* unbounded, int32_t* status);
+
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
  * n_walkers x n_steps scalar likelihood calls (bestfit_emcee, blueice/inference.py:254-321).  The variables are described as
