@@ -175,7 +175,7 @@ struct bi_ctx {
     DevBuf nz_idx, nz_n, nz_off, ps_c, cnt_c;
     DevBuf tm_entries, tm_off;                // tile-major copy of the non-empty-bin lists (k_dataset_dot_tiled): 4-byte entries, [n_tiles * T + 1] offsets
     int64_t nz_tile_epoch = -1;               // data epoch the copy was built for
-    bool tm_ok = false;                       // ... and whether every count fits its 19 bits
+    bool tm_ok = false;                       // ... and whether every count fits an entry (1 ... 32767: 15 bits)
     // the same lists over tiles of kDotTileMulti bins, for the toy-MC call over several parameter points (bi_eval_datasets_points:
     // the log mu tiles of four points side by side in LDS)
     DevBuf tmm_entries, tmm_off;

@@ -112,7 +112,7 @@ const ParamDef kParams[] = {
     BI_P_RO("n_set_launches", c->n_set_launches),
     BI_P_RO("last_plan_refused", c->plan_refused),
     BI_P_RO("tmm_entry_bytes", c->tmm_ok ? c->tmm_width : 0),
-    BI_P_RO("tm_entry_bytes", c->tm_width),
+    BI_P_RO("tm_entry_bytes", c->tm_ok ? c->tm_width : 0),
     BI_P_RO("events_sorted", c->ev_sorted ? 1 : 0),
     BI_P_RO("n_grad_mfma_launches", c->n_grad_mfma_launches),
     BI_P_RO("n_valid_launches", c->n_valid_launches),

@@ -847,7 +847,8 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     two-byte ones), or 4 / 8 / 16 (16: 128 slots, round 3's shape)
  *   dot_entry16       ... the tile-major lists hold TWO-byte entries (bin within the tile, count) where every count of every dataset is
  *                     at most 7 -- the kernel is bound by reading the lists --, four-byte entries otherwise (1, default; 0 = always
- *                     four bytes; read-only `tm_entry_bytes`: the width of the lists as built).  With two-byte entries dot_lanes
+ *                     four bytes; read-only `tm_entry_bytes`: the width of the lists as built, 0 = none: not built yet, or the last
+ *                     build met a count outside 1 ... 32767, which fits neither width).  With two-byte entries dot_lanes
  *                     8 and 16 mean 128 entry slots per run (8 lanes, two loads each), 4 means 96 (three loads per lane)
  *   dot_blocks_per_cu ... blocks of that kernel per CU its split of the datasets aims at: 0 = as many as are resident at once (one
  *                     round of blocks; default), n = n per CU

@@ -102,8 +102,10 @@ def test_simulate_toys_through_the_likelihood_class():
 
 def test_uploaded_dataset_batches_tiled_and_row_kernels():
     """bi_eval_datasets over UPLOADED sparse datasets large enough for the tiled kernel (bin tiles of log mu staged through
-    LDS over tile-major 4-byte entries): every dataset against the oracle; a count beyond the 19 bits of an entry, a
-    non-integer and a nan count send the whole batch back to the row kernel, with scipy's values for those datasets."""
+    LDS over tile-major 4-byte entries): every dataset against the oracle; a count beyond the 15 bits of an entry (32767 is the
+    largest it holds), a non-integer and a nan count send the whole batch back to the row kernel, with scipy's values for those
+    datasets.  Each half asserts the route it took (tm_entry_bytes: 0 after a build that failed; n_toy_polled: the tiled call
+    polls its completion word, the row kernel's does not)."""
     from oracle import blueice_oracle as orc
     from blueice_amd.device import DeviceContext
     from blueice_amd.synthetic import SyntheticModel
@@ -118,26 +120,39 @@ def test_uploaded_dataset_batches_tiled_and_row_kernels():
             hit = rng.choice(B, size=int(rng.integers(1500, 3000)), replace=False)
             counts[t, hit] = rng.integers(1, 6, size=len(hit))
         counts[7, :] = 0                                              # an empty dataset in the middle
-        counts[11, 123] = 524287.                                     # the largest count an entry holds
+        counts[11, 123] = 32767.                                      # the largest count an entry holds (15 bits)
         z, r = m.random_points(1, seed=3)
         z, r = z[0], r[0]
         dense = m.dense_model()
         ctx.set_param('sparse', 1)
         ctx.upload_counts(counts)
+        polled = ctx.get_param('n_toy_polled')
         ll, st = ctx.eval_datasets(z, r)
         assert st == 0
+        # the tiled kernel took the call, over four-byte entries -- asserted BEFORE anything is compared with the row kernel
+        assert ctx.get_param('tm_entry_bytes') == 4 and ctx.get_param('n_toy_polled') == polled + 1
         for t in (0, 7, 11, 40, T - 1):
             want = orc.loglikelihood(dense, counts[t], z, r)
             assert abs(ll[t] - want) <= 1e-10 * max(1.0, abs(want)), (t, ll[t], want)
         ctx.set_param('dot_tiled', 0)
         rows, _ = ctx.eval_datasets(z, r)
         ctx.set_param('dot_tiled', 1)
+        assert ctx.get_param('n_toy_polled') == polled + 1            # (the row kernel's call does not poll)
         np.testing.assert_allclose(rows, ll, rtol=1e-13, atol=0)
-        counts[11, 123] = 524288.                                     # one more: does not fit
+        counts[11, 123] = 32768.                                      # one more: does not fit
+        ctx.upload_counts(counts)
+        ll3, st = ctx.eval_datasets(z, r)
+        # the route changed, for this count alone: the build of the tile-major lists failed, the row kernel took the call
+        assert st == 0 and ctx.get_param('tm_entry_bytes') == 0 and ctx.get_param('n_toy_polled') == polled + 1
+        want = orc.loglikelihood(dense, counts[11], z, r)
+        assert abs(ll3[11] - want) <= 1e-10 * abs(want)
+        np.testing.assert_array_equal(np.delete(ll3, 11), np.delete(rows, 11))
         counts[12, 77] = 2.5                                          # scipy: -inf
         counts[13, 5] = np.nan                                        # scipy: nan
         ctx.upload_counts(counts)
         ll2, st = ctx.eval_datasets(z, r)
+        # the route changed: the build of the tile-major lists failed, the row kernel took the call
+        assert ctx.get_param('tm_entry_bytes') == 0 and ctx.get_param('n_toy_polled') == polled + 1
         assert ll2[12] == -np.inf and np.isnan(ll2[13])
         want = orc.loglikelihood(dense, counts[11], z, r)
         assert abs(ll2[11] - want) <= 1e-10 * abs(want)
