@@ -118,6 +118,7 @@ SIGNATURES = {
     'bi_memcpy_to_host': (C.c_int, [_p, _p, _p, _i64]),
     'bi_memcpy_to_device': (C.c_int, [_p, _p, _p, _i64]),
     'bi_selftest_log': (C.c_int, [_p, _i64, _p, _p]),
+    'bi_unpack_rows': (C.c_int, [_p, _p]),
     'bi_selftest_sort': (C.c_int, [_p, C.c_int, _i64, _p, _p, C.c_int, C.c_int, _p, _p]),
     'bi_selftest_scan': (C.c_int, [_p, C.c_int, _i64, _p, _i64, _p]),
     'bi_selftest_grid_reduce': (C.c_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _p]),

@@ -119,6 +119,15 @@ struct bi_ctx {
     int64_t narrow_counts = 1;                   // parameter: 0 = never read the narrow copy
     int64_t last_streamed_bytes = 0;             // read-only: bytes the last bi_run_plan streamed (plan bytes less 7 per bin of every item read narrow)
     int64_t n_narrow_launches = 0;               // read-only: morph launches that read the narrow copy
+    // the packed shadow of the template rows: 7 bytes per value of ps in 3584-byte chunks and one exponent base per chunk
+    // (build_packed_rows, at the end of every model upload); the dense value kernels stream it instead of ps when every chunk
+    // of the model has a packed form
+    DevBuf pk, pk_base, pk_bad;
+    bool pk_valid = false;                       // the shadow matches `ps` and represents it exactly (false: never read)
+    bool pk_skip = false;                        // the model being closed is an event tensor (score_events_impl): no shadow
+    int64_t packed_rows = 1;                     // parameter: 0 = never build or read the shadow
+    int64_t n_packed_launches = 0;               // read-only: morph launches that read the shadow
+    int64_t last_packed_saved = 0;               // read-only: bytes the last bi_run_plan did NOT stream thanks to it (Bp per row and item)
     // read-only: the grid of the most recent k_morph_reduce / k_morph_single launch (gridDim.x blocks per item, gridDim.y items)
     // and whether it finished through the mailbox (0: k_finish, k_finish_single or the two-kernel fallback ran behind it)
     int64_t last_morph_nbx = 0, last_morph_items = 0, last_morph_fused = 0;

@@ -39,7 +39,19 @@ struct LaunchArgs {
     int skip_post = -1, late_post = -1;   // fault injection (tests): this block never posts / posts after the collector gave up; -1 = off
     // (last, so that no other member moves in the kernel-argument block: the existing instantiations compile as before)
     const uint8_t* cnt8 = nullptr;   // [T][Bp] the counts as one byte per bin, or NULL: the launch reads the doubles (build_narrow_counts)
+    const uint8_t* pk = nullptr;     // the packed shadow of ps (build_packed_rows), 7 bytes per value, or NULL: the launch reads ps
+    const uint32_t* pk_base = nullptr; // ... and its exponent bases, one uint16_t per (row, tile), read two at a time
 };
+
+// ---- the packed shadow of the template rows ----
+// One 3584-byte chunk per 512-bin tile of a row, chunks in the order of the tiles in ps (chunk q = elements [512 q, 512 q + 512)
+// of ps): [512 x u32: mantissa bits 0..31][512 x u16: bits 32..47][512 x u8: bits 48..51 | code << 4].  code 0: the value is
+// +0.0 (every stored bit 0); code 1..15: biased exponent base + code - 1, base = the smallest exponent of the chunk's non-zero
+// values (pk_base[q], 11 bits in a uint16_t).
+constexpr int kPkChunk = 3584;       // 7 * kTile
+constexpr int kPkMidOff = 2048;      // 4 * kTile
+constexpr int kPkTopOff = 3072;      // 6 * kTile
+constexpr int kPkSpan = 15;          // exponents a chunk's non-zero values may take
 
 constexpr int kMaxSingleStreams = 128;
 
@@ -492,6 +504,49 @@ __device__ __forceinline__ double2 stream_load(const double* p) {
     } else {
         return *reinterpret_cast<const double2*>(p);
     }
+}
+
+// ---- the packed template rows: a lane's two bins of one chunk (the layout is described at kPkChunk) ----
+// What the three loads bring, nothing decoded yet: a batch of rows keeps all of its loads in flight before the first decode.
+struct PkRaw {
+    unsigned lo0, lo1;         // mantissa bits 0..31 of the two bins
+    unsigned mid;              // bits 32..47 of both
+    unsigned top;              // bits 48..51 | code << 4 of both (low half-word)
+};
+
+// chunk: the tile's number in ps, (row's element offset >> 9) + tile -- wave-uniform.  Buffer loads: the chunk's address stays
+// in scalar registers (a descriptor per chunk), the three lane offsets are the same for every row, so a row costs no vector
+// address arithmetic; and the descriptor's 3584 bytes bound every access to the chunk.
+template <bool NT>
+__device__ __forceinline__ PkRaw pk_load(const uint8_t* __restrict__ pk, int64_t chunk) {
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(pk + chunk * kPkChunk), 0, kPkChunk, 0x00020000);
+    constexpr int aux = NT ? 2 : 0;                                  // (the nontemporal hint the fp64 rows carry)
+    const auto lo = __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)threadIdx.x * 8, 0, aux);
+    PkRaw r;
+    r.lo0 = lo[0];
+    r.lo1 = lo[1];
+    r.mid = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)threadIdx.x * 4, kPkMidOff, aux);
+    r.top = __builtin_amdgcn_raw_buffer_load_b16(rsrc, (int)threadIdx.x * 2, kPkTopOff, aux);
+    return r;
+}
+
+// the word that holds a chunk's base (two bases per word: a scalar load), and (base - 1) << 20 from it -- wave-uniform
+__device__ __forceinline__ unsigned pk_base_word(const uint32_t* __restrict__ pk_base, int64_t chunk) { return pk_base[chunk >> 1]; }
+__device__ __forceinline__ unsigned pk_exp_add(unsigned word, int64_t chunk) {
+    return (((word >> (((unsigned)chunk & 1u) * 16u)) & 0xffffu) - 1u) << 20;
+}
+
+// the stored doubles, bit for bit.  High word = [mid half-word | top byte << 16], which has the code in bits 20..23: a non-zero
+// code c becomes the exponent base + c - 1 by adding (base - 1) << 20; code 0 is +0.0, all bits 0.  `add` stays a scalar operand.
+__device__ __forceinline__ double2 pk_decode(const PkRaw& r, unsigned add) {
+    unsigned hx = __builtin_amdgcn_perm(r.top, r.mid, 0x0c040100u);
+    unsigned hy = __builtin_amdgcn_perm(r.top, r.mid, 0x0c050302u);
+    hx = hx ? hx + add : 0u;                 // (code 0 <=> every stored bit of the value is 0)
+    hy = hy ? hy + add : 0u;
+    double2 v;
+    v.x = __longlong_as_double(((unsigned long long)hx << 32) | r.lo0);
+    v.y = __longlong_as_double(((unsigned long long)hy << 32) | r.lo1);
+    return v;
 }
 
 // Poisson log-pmf without the data-only lgamma(n+1) term, scipy semantics

@@ -164,7 +164,10 @@ int score_events_impl(bi_ctx* tp, bi_ctx* c, int method, int k, const int32_t* n
     }                                                                          // (the scratch goes back before the model is closed)
     c->h_mus = tp->h_mus;
     std::fill(c->anchor_set.begin(), c->anchor_set.end(), 1);
-    if ((rc = bi_model_end(c))) return rc;
+    c->pk_skip = true;                 // (an event tensor: bi_set_unbinned below would drop a packed shadow at once)
+    rc = bi_model_end(c);
+    c->pk_skip = false;
+    if (rc) return rc;
     c->allow_neg = tp->allow_neg;
     return bi_set_unbinned(c, outlier_likelihood);
 }

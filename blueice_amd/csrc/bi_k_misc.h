@@ -212,6 +212,63 @@ __global__ __launch_bounds__(kThreads) void k_counts_narrow(const double* __rest
     if (__ballot(lossy) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad + t, 1u);
 }
 
+// The packed shadow of the template rows (build_packed_rows; the format is described at kPkChunk in bi_dev_common.h): one
+// block per chunk = 512-bin tile of a row, a thread takes the two bins a lane of morph_tiles owns.  A chunk has a packed
+// form when each of its values is +0.0 or a positive normal double and the biased exponents of the non-zero ones lie within
+// kPkSpan consecutive values; -0.0, negative values, subnormals, inf and nan have none.  One chunk without a packed form
+// raises *bad, and the model keeps streaming ps (the shadow is then never read).
+__global__ __launch_bounds__(kThreads) void k_pack_rows(const double* __restrict__ ps, int64_t chunk0, uint8_t* __restrict__ pk,
+                                                        uint16_t* __restrict__ pk_base, unsigned* __restrict__ bad) {
+    const int64_t q = chunk0 + blockIdx.x;
+    const double2 v = *reinterpret_cast<const double2*>(ps + q * kTile + threadIdx.x * kBinsPerThread);
+    const unsigned long long u[2] = {(unsigned long long)__double_as_longlong(v.x), (unsigned long long)__double_as_longlong(v.y)};
+    unsigned emin = 0xFFFFu, emax = 0u;
+    bool lossy = false;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (u[j] == 0ull) continue;
+        const unsigned e = (unsigned)(u[j] >> 52);           // the sign bit rides on top: a negative value reads as e >= 2048
+        lossy |= e < 1u || e > 2046u;
+        emin = min(emin, e);
+        emax = max(emax, e);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        emin = min(emin, (unsigned)__shfl_xor((int)emin, off, 64));
+        emax = max(emax, (unsigned)__shfl_xor((int)emax, off, 64));
+    }
+    __shared__ unsigned s_min[kThreads / 64], s_max[kThreads / 64];
+    if ((threadIdx.x & 63) == 0) { s_min[threadIdx.x >> 6] = emin; s_max[threadIdx.x >> 6] = emax; }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) { emin = min(emin, s_min[w]); emax = max(emax, s_max[w]); }
+    const unsigned base = emax == 0u ? 0u : emin;             // (a chunk of zeros: no exponent to store)
+    lossy |= emax > emin && emax - emin > (unsigned)(kPkSpan - 1);
+    unsigned long long lo = 0ull;
+    unsigned mid = 0u, top = 0u;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (u[j] == 0ull) continue;
+        const unsigned code = ((unsigned)(u[j] >> 52) - base + 1u) & 15u;
+        lo |= (u[j] & 0xFFFFFFFFull) << (32 * j);
+        mid |= (unsigned)((u[j] >> 32) & 0xFFFFull) << (16 * j);
+        top |= ((unsigned)((u[j] >> 48) & 0xFull) | (code << 4)) << (8 * j);
+    }
+    uint8_t* __restrict__ p = pk + q * kPkChunk;
+    reinterpret_cast<unsigned long long*>(p)[threadIdx.x] = lo;
+    reinterpret_cast<unsigned*>(p + kPkMidOff)[threadIdx.x] = mid;
+    reinterpret_cast<uint16_t*>(p + kPkTopOff)[threadIdx.x] = (uint16_t)top;
+    if (threadIdx.x == 0) pk_base[q] = (uint16_t)base;
+    if (__ballot(lossy) != 0ull && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+}
+
+// the shadow expanded back to doubles, out[chunk][512] (bi_unpack_rows: tests)
+__global__ __launch_bounds__(kThreads) void k_unpack_rows(const uint8_t* __restrict__ pk, const uint32_t* __restrict__ pk_base,
+                                                          int64_t chunk0, double* __restrict__ out) {
+    const int64_t q = chunk0 + blockIdx.x;
+    *reinterpret_cast<double2*>(out + q * kTile + threadIdx.x * kBinsPerThread) = pk_decode(pk_load<false>(pk, q), pk_exp_add(pk_base_word(pk_base, q), q));
+}
+
 __global__ void k_rows_sum(const double* __restrict__ partial, int nblk, double* __restrict__ out, int64_t T) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;

@@ -14,7 +14,47 @@ namespace {
 // tile0, tile0 + tile_step, ... of one work item.
 // CNT8: the counts row is read from the narrow copy (one byte per bin, build_narrow_counts) instead of the doubles; the
 // conversion back is exact, everything after the load is the same instruction stream.
-template <int G, bool BB, bool NT, int MODE, bool CNT8 = false>
+// PACKED (MODE 0 without Beeston-Barlow): the template rows are read from the packed shadow of ps (7 bytes per value,
+// build_packed_rows) and decoded to the stored doubles, bit for bit; the FMAs behind them run as before, in the same order.
+
+// rows [k_lo, k_hi) of one tile from the packed shadow: eight rows per batch, the loads of a batch ahead of its decodes
+template <int G, bool NT>
+__device__ __forceinline__ void packed_rows_fma(const LaunchArgs& a, const int64_t* __restrict__ rowoff, const double* __restrict__ coef,
+                                                int tile, int k_lo, int k_hi, double (&acc)[G][2]) {
+    static_assert(kTile == 512, "a chunk of the packed shadow is one 512-bin tile");
+    int k = k_lo;
+    for (; k + 8 <= k_hi; k += 8) {
+        PkRaw raw[8];
+        unsigned word[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) word[u] = pk_base_word(a.pk_base, (rowoff[k + u] >> 9) + tile);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) raw[u] = pk_load<NT>(a.pk, (rowoff[k + u] >> 9) + tile);
+        __builtin_amdgcn_sched_barrier(0);       // every request of the batch is out before the first base word is waited for
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const double2 v = pk_decode(raw[u], pk_exp_add(word[u], (rowoff[k + u] >> 9) + tile));
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                const double c = coef[(k + u) * G + g];
+                acc[g][0] = fma(c, v.x, acc[g][0]);
+                acc[g][1] = fma(c, v.y, acc[g][1]);
+            }
+        }
+    }
+    for (; k < k_hi; ++k) {
+        const int64_t chunk = (rowoff[k] >> 9) + tile;
+        const double2 v = pk_decode(pk_load<NT>(a.pk, chunk), pk_exp_add(pk_base_word(a.pk_base, chunk), chunk));
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const double c = coef[k * G + g];
+            acc[g][0] = fma(c, v.x, acc[g][0]);
+            acc[g][1] = fma(c, v.y, acc[g][1]);
+        }
+    }
+}
+
+template <int G, bool BB, bool NT, int MODE, bool CNT8 = false, bool PACKED = false>
 __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* __restrict__ rowoff,
                                             const double* __restrict__ coef, const double* __restrict__ aux_base,
                                             const double* __restrict__ cnt, const uint8_t* __restrict__ cnt8, int n_tiles, int tile0,
@@ -53,12 +93,16 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
         if constexpr (NT && G == 1 && MODE != 2 && MODE != 3) {
             // rows meant to stay in the Infinity Cache between calls (repeated evaluations in one cell): default policy
             k0 = a.n_keep;
+            if constexpr (PACKED) {
+                packed_rows_fma<G, false>(a, rowoff, coef, tile, 0, k0, acc);
+            } else {
 #pragma unroll 8
-            for (int k = 0; k < k0; ++k) {
-                const double2 v = stream_load<false>(a.ps + rowoff[k] + bin0);
-                const double c = coef[k];
-                acc[0][0] = fma(c, v.x, acc[0][0]);
-                acc[0][1] = fma(c, v.y, acc[0][1]);
+                for (int k = 0; k < k0; ++k) {
+                    const double2 v = stream_load<false>(a.ps + rowoff[k] + bin0);
+                    const double c = coef[k];
+                    acc[0][0] = fma(c, v.x, acc[0][0]);
+                    acc[0][1] = fma(c, v.y, acc[0][1]);
+                }
             }
         }
         if constexpr (MODE == 2 || MODE == 3) if (a.nan_S > 0) {
@@ -96,14 +140,18 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
             }
             k0 = a.n0;
         }
+        if constexpr (PACKED) {
+            packed_rows_fma<G, NT>(a, rowoff, coef, tile, k0, a.n0, acc);
+        } else {
 #pragma unroll 8
-        for (int k = k0; k < a.n0; ++k) {
-            const double2 v = stream_load<NT>(a.ps + rowoff[k] + bin0);
+            for (int k = k0; k < a.n0; ++k) {
+                const double2 v = stream_load<NT>(a.ps + rowoff[k] + bin0);
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const double c = coef[k * G + g];
-                acc[g][0] = fma(c, v.x, acc[g][0]);
-                acc[g][1] = fma(c, v.y, acc[g][1]);
+                for (int g = 0; g < G; ++g) {
+                    const double c = coef[k * G + g];
+                    acc[g][0] = fma(c, v.x, acc[g][0]);
+                    acc[g][1] = fma(c, v.y, acc[g][1]);
+                }
             }
         }
         if (tab_pending) {
@@ -238,8 +286,14 @@ __device__ __forceinline__ void morph_tiles(const LaunchArgs& a, const int64_t* 
 // MODE 0: G parameter points of one cell.  MODE 1 (gradient): ONE point; column 0 of the coefficient matrix
 // gives mu, columns 1.. give d mu / d theta_j (theta = shape parameters, then rate scales), and the per-bin
 // chain rule d ll / d theta_j = (n / mu - 1) * d mu / d theta_j is reduced alongside the likelihood.
-template <int G, bool BB, bool NT, int MODE = 0, bool CNT8 = false>
-__global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
+// The waves per SIMD the fp64-row value kernel of the same G reaches (its registers: 69, 76, 89, 115, 173): the PACKED form,
+// which holds a batch's raw words and decodes them, is asked to fit the same budget -- occupancy is what keeps 8 TB/s in flight.
+constexpr int packed_min_waves(int G) { return G == 1 ? 7 : G == 2 ? 6 : G == 4 ? 5 : G == 8 ? 4 : 2; }
+
+template <int G, bool BB, bool NT, int MODE = 0, bool CNT8 = false, bool PACKED = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PACKED ? packed_min_waves(G) : 1)))
+void k_morph_reduce(LaunchArgs a) {
+    static_assert(!PACKED || (MODE == 0 && !BB), "the packed rows serve the dense value kernels only");
     const int item = blockIdx.y;
     const int NS = a.n0 + a.n1 + a.n2;
     const int64_t* __restrict__ rowoff = a.rowoff + (int64_t)item * NS;
@@ -254,7 +308,7 @@ __global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
 #pragma unroll
     for (int g = 0; g < G; ++g) { sum[g] = 0.0; flg[g] = 0u; }
 
-    morph_tiles<G, BB, NT, MODE, CNT8>(a, rowoff, coef, a.aux + (int64_t)item * G * 2, cnt, cnt8, n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
+    morph_tiles<G, BB, NT, MODE, CNT8, PACKED>(a, rowoff, coef, a.aux + (int64_t)item * G * 2, cnt, cnt8, n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
 
     __shared__ double s_sum[kThreads / 64][G];
     __shared__ unsigned s_flg[kThreads / 64][G];
@@ -351,11 +405,13 @@ __global__ __launch_bounds__(kThreads) void k_morph_reduce(LaunchArgs a) {
 // launch: every block posts its partial into a mailbox slot and leaves, the last block in dispatch order collects
 // them in block order (fixed order => bitwise reproducible; see mail_post) and writes {ll, status} straight into
 // pinned host memory.
-template <bool BB, bool NT, int MODE, bool FUSE, bool CNT8 = false>
-__global__ __launch_bounds__(kThreads) void k_morph_single(LaunchArgs a, SingleDesc d) {
+template <bool BB, bool NT, int MODE, bool FUSE, bool CNT8 = false, bool PACKED = false>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(PACKED ? packed_min_waves(1) : 1)))
+void k_morph_single(LaunchArgs a, SingleDesc d) {
+    static_assert(!PACKED || (MODE == 0 && !BB), "the packed rows serve the dense value kernels only");
     double sum[1] = {0.0};
     unsigned flg[1] = {0u};
-    morph_tiles<1, BB, NT, MODE, CNT8>(a, d.rowoff, d.coef, d.aux, a.counts, a.cnt8, a.n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
+    morph_tiles<1, BB, NT, MODE, CNT8, PACKED>(a, d.rowoff, d.coef, d.aux, a.counts, a.cnt8, a.n_tiles, (int)blockIdx.x, (int)gridDim.x, sum, flg);
 
     __shared__ double s_sum[kThreads / 64];
     __shared__ unsigned s_flg[kThreads / 64];

@@ -96,6 +96,57 @@ bool narrow_has_all(bi_ctx* c) {
     return c->cnt8_all == 1;
 }
 
+// ---- the packed shadow of the template rows ----
+// Called at the end of every model upload (bi_model_end), after the last write to c->ps is queued; every writer of c->ps runs
+// between bi_model_begin -- which drops the shadow -- and bi_model_end.  Not having one is never an error: parameter off,
+// more than a quarter of the free device memory, a failed allocation or a model without a packed form all leave the
+// context streaming ps.  Synchronises the stream (the eligibility word comes to the host).
+void drop_packed_rows(bi_ctx* c, bool release) {
+    c->pk_valid = false;
+    if (release) { dev_free(c->pk); dev_free(c->pk_base); }
+}
+
+void build_packed_rows(bi_ctx* c) {
+    c->pk_valid = false;
+    if (!c->packed_rows || c->pk_skip || c->unbinned || c->bb_source >= 0 || !c->ps.p || c->B < 1) { drop_packed_rows(c, true); return; }
+    const int64_t n_chunks = c->A * c->S * (c->Bp / kTile);
+    const size_t pk_bytes = (size_t)n_chunks * kPkChunk;
+    const size_t base_bytes = ((size_t)n_chunks + 2) / 2 * sizeof(uint32_t);        // (read two bases at a time)
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); drop_packed_rows(c, true); return; }
+    if (!(c->pk.p && c->pk.bytes >= pk_bytes) && pk_bytes > free_b / 4) { drop_packed_rows(c, true); return; }
+    const std::string keep = c->err;
+    if (dev_alloc(c, c->pk, pk_bytes) || dev_alloc(c, c->pk_base, base_bytes) || dev_alloc(c, c->pk_bad, sizeof(unsigned))) {
+        (void)hipGetLastError();
+        c->err = keep;
+        drop_packed_rows(c, true);
+        return;
+    }
+    unsigned bad = 1u;
+    hipError_t e = hipMemsetAsync(c->pk_bad.p, 0, sizeof(unsigned), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(c->pk_base.p, 0, base_bytes, c->stream);
+    const int64_t per_launch = (int64_t)1 << 30;             // chunks per launch (gridDim.x limit)
+    for (int64_t q0 = 0; q0 < n_chunks && e == hipSuccess; q0 += per_launch) {
+        hipLaunchKernelGGL(k_pack_rows, dim3((unsigned)std::min(per_launch, n_chunks - q0)), dim3(kThreads), 0, c->stream,
+                           (const double*)c->ps.p, q0, (uint8_t*)c->pk.p, (uint16_t*)c->pk_base.p, (unsigned*)c->pk_bad.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, c->pk_bad.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); drop_packed_rows(c, true); return; }
+    if (bad != 0u) { drop_packed_rows(c, true); return; }    // no packed form: the memory goes back
+    c->pk_valid = true;
+}
+
+// may a dense value launch read the shadow (a property of the model, not of the batch)
+bool packed_on(const bi_ctx* c) { return c->packed_rows && c->pk_valid && !c->unbinned && c->bb_source < 0 && c->pk.p; }
+
+void use_packed_rows(bi_ctx* c, LaunchArgs& a) {
+    a.pk = (const uint8_t*)c->pk.p;
+    a.pk_base = (const uint32_t*)c->pk_base.p;
+    ++c->n_packed_launches;
+}
+
 // k_finish over n_slots (item, slot) sums, G slots per item, of nbx per-block partials each: 64 lanes per slot up to 64
 // blocks, else a whole block
 void launch_finish(bi_ctx* c, const double* partial, const unsigned* pflags, int nbx, int G, int64_t n_slots, const int64_t* perm,

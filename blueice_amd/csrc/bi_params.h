@@ -90,6 +90,7 @@ const ParamDef kParams[] = {
     {"compact_budget", kParamRW, BI_P_GET(c->compact_budget), BI_P_SET(c->compact_budget = v)},
     {"toy_offset", kParamRW, BI_P_GET(c->toy_offset), BI_P_RANGE(0, INT64_MAX, toy_offset, "toy_offset >= 0")},
     {"narrow_counts", kParamRW, BI_P_GET(c->narrow_counts), BI_P_FLAG(narrow_counts)},
+    {"packed_rows", kParamRW, BI_P_GET(c->packed_rows), BI_P_FLAG(packed_rows)},
     {"mail_timeout_ms", kParamRW, BI_P_GET(c->mail_timeout_ms),
      BI_P_RANGE(1, 60000, mail_timeout_ms, "mail_timeout_ms in [1, 60000]")},
     // ---- triggers (write-only) ---------------------------------------------------------------------------------
@@ -121,6 +122,9 @@ const ParamDef kParams[] = {
     BI_P_RO("n_mail_resets", c->n_mail_resets),
     BI_P_RO("last_streamed_bytes", c->last_streamed_bytes),
     BI_P_RO("n_narrow_launches", c->n_narrow_launches),
+    BI_P_RO("n_packed_launches", c->n_packed_launches),
+    BI_P_RO("packed_rows_valid", c->pk_valid ? 1 : 0),
+    BI_P_RO("last_packed_saved_bytes", c->last_packed_saved),
     BI_P_RO("last_morph_nbx", c->last_morph_nbx),
     BI_P_RO("last_morph_items", c->last_morph_items),
     BI_P_RO("last_morph_fused", c->last_morph_fused),

@@ -274,6 +274,7 @@ int eval_single_fused(bi_ctx* c, const PointGeom& g, const double* rates, int64_
         a.cnt8 = (const uint8_t*)c->cnt8.p + ds * c->Bp;
         ++c->n_narrow_launches;
     }
+    if (!sparse && !bb && packed_on(c)) use_packed_rows(c, a);
     const bool nt = !sparse && c->nt_loads != 0;
     // Repeated evaluations in one grid cell (a minimizer's access pattern): let most of the cell's rows keep the default
     // cache policy so that they stay in the 256 MiB Infinity Cache between calls (the rest, and every call into a new
@@ -439,6 +440,7 @@ int eval_single(bi_ctx* c, const double* z, const double* rate_scale, int64_t ds
         a.cnt8 = (const uint8_t*)c->cnt8.p;
         ++c->n_narrow_launches;
     }
+    if (!sparse && !bb && packed_on(c)) use_packed_rows(c, a);
     launch_morph_g(c, 1, a, dim3((unsigned)nbx, 1), bb, !sparse && c->nt_loads != 0);
     c->last_morph_nbx = nbx; c->last_morph_items = 1; c->last_morph_fused = 0;
     launch_finish(c, a.partial, a.pflags, nbx, 1, 1, (const int64_t*)(dev + (o + 2) * 8), (const double*)(dev + (o + 3) * 8),

@@ -98,6 +98,7 @@ void bi_destroy(bi_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     dev_free(c->ps); dev_free(c->nm); dev_free(c->nm_tot); dev_free(c->counts); dev_free(c->lgsum); dev_free(c->cnt8); dev_free(c->cnt8_bad);
+    dev_free(c->pk); dev_free(c->pk_base); dev_free(c->pk_bad);
     dev_free(c->scratch); dev_free(c->scratch2); dev_free(c->logmu); dev_free(c->toy_blocks_done); dev_free(c->ev_perm);
     dev_free(c->slot_dev); dev_free(c->slot_partial); dev_free(c->slot_pflags); dev_free(c->slot_counter); dev_free(c->space_edges);
     dev_free(c->mail); dev_free(c->mail_flags);
@@ -188,6 +189,7 @@ int bi_model_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* anch
     c->model_ready = false;
     c->data_ready = false;  // a new model invalidates the data (likelihood.py:253)
     c->cnt8_valid = false;
+    c->pk_valid = false;        // (the packed shadow of the previous model's rows: bi_model_end builds the new one)
     dev_free(c->real_counts);   // (rows of the previous model's padded length)
     c->real_T = 0;
     release_coarse(c);          // (groups of the previous model's bins)
@@ -293,6 +295,7 @@ int bi_model_end(bi_ctx* c) {
         }
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    build_packed_rows(c);       // (ps is final: no writer of it runs outside bi_model_begin ... bi_model_end)
     c->model_open = false;
     c->model_ready = true;
     return BI_OK;
@@ -570,6 +573,9 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
     c->last_streamed_bytes = plan->bytes;
     // the morph launches below read the one-byte copy of the counts when every dataset of the plan has an exact one
     const bool narrow = plan->narrow && !plan->sparse && narrow_on(c);
+    // ... and the packed shadow of the template rows when the model has a valid one: one byte less per value of every row
+    const bool packed = !plan->sparse && !bb && packed_on(c);
+    c->last_packed_saved = 0;
     if (plan->use_scan) {
         bi_plan::Class& k = plan->classes[0];
         ScanArgs sa{};
@@ -661,6 +667,10 @@ int bi_run_plan(bi_ctx* c, bi_plan* plan, double* out_dev) {
                 b.cnt8 = (const uint8_t*)c->cnt8.p;
                 c->last_streamed_bytes -= 7 * c->Bp * ni;
                 ++c->n_narrow_launches;
+            }
+            if (packed) {
+                use_packed_rows(c, b);
+                c->last_packed_saved += c->Bp * (int64_t)a.n0 * ni;
             }
             launch_morph_g(c, k.G, b, dim3((unsigned)k.nbx, (unsigned)ni), bb, nt);
             c->last_morph_nbx = k.nbx; c->last_morph_items = ni; c->last_morph_fused = fuse ? 1 : 0;
@@ -1171,6 +1181,7 @@ int bi_set_unbinned(bi_ctx* c, double outlier_likelihood) {
     ++c->epoch;
     c->unbinned = true;
     c->cnt8_valid = false;
+    drop_packed_rows(c, true);  // (the rows now hold pdf values at events, read by the unbinned kernels only)
     c->outlier = outlier_likelihood;
     c->csr_ready = c->compact_ready = false;
     // one pseudo dataset with zero lgamma sum; the counts row is never read in this mode
@@ -1388,6 +1399,22 @@ int bi_selftest_log(bi_ctx* c, int64_t n, const double* x, double* out) {
     if (e == hipSuccess && n) e = hipMemcpyAsync(out, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_selftest_log: %s", hipGetErrorString(e));
+    return BI_OK;
+}
+
+// the packed shadow of the template rows expanded back to doubles on the device: out_dev [anchors x sources][padded bins]
+int bi_unpack_rows(bi_ctx* c, double* out_dev) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!out_dev) return fail(c, BI_ERR_INVALID, "bi_unpack_rows: out_dev is NULL");
+    if (!c->pk_valid || !c->pk.p) return fail(c, BI_ERR_STATE, "bi_unpack_rows: the model has no packed rows (packed_rows_valid = 0)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int64_t n_chunks = c->A * c->S * (c->Bp / kTile), per_launch = (int64_t)1 << 30;
+    for (int64_t q0 = 0; q0 < n_chunks; q0 += per_launch)
+        hipLaunchKernelGGL(k_unpack_rows, dim3((unsigned)std::min(per_launch, n_chunks - q0)), dim3(kThreads), 0, c->stream,
+                           (const uint8_t*)c->pk.p, (const uint32_t*)c->pk_base.p, q0, out_dev);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BI_OK;
 }
 

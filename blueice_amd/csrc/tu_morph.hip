@@ -14,6 +14,13 @@ void launch_morph(bi_ctx* c, const LaunchArgs& a, dim3 grid, bool bb, bool nt) {
         else hipLaunchKernelGGL((k_morph_reduce<G, false, false, 2>), grid, dim3(kThreads), 0, c->stream, a);
         return;
     }
+    if (a.pk && !bb) {  // the model has a valid packed shadow of its template rows: the dense value kernels read it instead of ps
+        if (a.cnt8 && nt) hipLaunchKernelGGL((k_morph_reduce<G, false, true, 0, true, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else if (a.cnt8) hipLaunchKernelGGL((k_morph_reduce<G, false, false, 0, true, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else if (nt) hipLaunchKernelGGL((k_morph_reduce<G, false, true, 0, false, true>), grid, dim3(kThreads), 0, c->stream, a);
+        else hipLaunchKernelGGL((k_morph_reduce<G, false, false, 0, false, true>), grid, dim3(kThreads), 0, c->stream, a);
+        return;
+    }
     if (a.cnt8) {      // every dataset of the launch has an exact one-byte copy of its counts: the same kernels, narrow counts load
         if (bb && nt) hipLaunchKernelGGL((k_morph_reduce<G, true, true, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
         else if (bb) hipLaunchKernelGGL((k_morph_reduce<G, true, false, 0, true>), grid, dim3(kThreads), 0, c->stream, a);
@@ -65,18 +72,20 @@ void launch_morph_g(bi_ctx* c, int G, const LaunchArgs& a, dim3 grid, bool bb, b
 
 void launch_morph_single(bi_ctx* c, bool bb, bool nt, bool fuse, dim3 grid, const LaunchArgs& a, const SingleDesc& d) {
     const dim3 block(kThreads);
-#define BI_SINGLE(BBv, MODEv, C8v)                                                                                          \
+#define BI_SINGLE(BBv, MODEv, C8v, PKv)                                                                                        \
     do {                                                                                                               \
-        if (nt && fuse) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, true, C8v>), grid, block, 0, c->stream, a, d);    \
-        else if (nt) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, false, C8v>), grid, block, 0, c->stream, a, d);      \
-        else if (fuse) hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, true, C8v>), grid, block, 0, c->stream, a, d);    \
-        else hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, false, C8v>), grid, block, 0, c->stream, a, d);             \
+        if (nt && fuse) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, true, C8v, PKv>), grid, block, 0, c->stream, a, d);    \
+        else if (nt) hipLaunchKernelGGL((k_morph_single<BBv, true, MODEv, false, C8v, PKv>), grid, block, 0, c->stream, a, d);      \
+        else if (fuse) hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, true, C8v, PKv>), grid, block, 0, c->stream, a, d);    \
+        else hipLaunchKernelGGL((k_morph_single<BBv, false, MODEv, false, C8v, PKv>), grid, block, 0, c->stream, a, d);             \
     } while (0)
-    if (c->unbinned) BI_SINGLE(false, 2, false);
-    else if (a.cnt8 && bb) BI_SINGLE(true, 0, true);          // (the binned forms with an exact one-byte copy of the counts)
-    else if (a.cnt8) BI_SINGLE(false, 0, true);
-    else if (bb) BI_SINGLE(true, 0, false);
-    else BI_SINGLE(false, 0, false);
+    if (c->unbinned) BI_SINGLE(false, 2, false, false);
+    else if (a.pk && !bb && a.cnt8) BI_SINGLE(false, 0, true, true);   // (the model has a valid packed shadow of its template rows)
+    else if (a.pk && !bb) BI_SINGLE(false, 0, false, true);
+    else if (a.cnt8 && bb) BI_SINGLE(true, 0, true, false);   // (the binned forms with an exact one-byte copy of the counts)
+    else if (a.cnt8) BI_SINGLE(false, 0, true, false);
+    else if (bb) BI_SINGLE(true, 0, false, false);
+    else BI_SINGLE(false, 0, false, false);
 #undef BI_SINGLE
 }
 

@@ -342,6 +342,18 @@ class DeviceContext:
         self._check(self._lib.bi_download_counts(self._h, int(t), ptr(out)))
         return out
 
+    def unpack_rows(self):
+        """The packed shadow of the template rows (parameter `packed_rows`) expanded back to doubles -> [anchors x sources,
+        padded bins]; raises when the resident model has none (`packed_rows_valid` = 0).  For tests."""
+        rows = (int(np.prod([len(g) for g in self.anchor_z], dtype=np.int64)) if self.anchor_z else 1) * self.S
+        Bp = self.get_param('padded_bins')
+        buf = self.device_alloc(rows * Bp * 8)
+        try:
+            self._check(self._lib.bi_unpack_rows(self._h, C.c_void_p(buf.ptr)))
+            return buf.to_host(np.float64).reshape(rows, Bp)
+        finally:
+            buf.free()
+
     # -- evaluation ------------------------------------------------------------------------
     def _point_args(self, z, rate_scale, dataset):
         if self.d:

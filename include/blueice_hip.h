@@ -775,6 +775,10 @@ int bi_memcpy_to_device(bi_ctx* ctx, void* dst_dev, const void* src_host, int64_
 /* self-test of the device logarithm used in the per-bin terms: out[i] = log(x[i]) as the kernels compute it */
 int bi_selftest_log(bi_ctx* ctx, int64_t n, const double* x, double* out);
 
+/* debug / tests: the packed shadow of the template rows (parameter packed_rows) expanded back to doubles on the device,
+ * out_dev [anchors x sources][padded_bins]; BI_ERR_STATE when the resident model has none (packed_rows_valid = 0) */
+int bi_unpack_rows(bi_ctx* ctx, double* out_dev);
+
 /* self-tests of the library's own device-wide primitives (csrc/tu_prim.hip: the stable radix sort of (64-bit key, value) pairs over
  * the key bits [begin_bit, end_bit) and the scans behind the device planner, the list builders and toy generation), on caller data:
  *   sort kind 0: uint64 keys, int64 values | 1: int64 keys, int32 values | 2: double keys (numpy's sort order, -nan < -inf ... +inf < +nan), int32 values
@@ -903,6 +907,17 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     narrow_ready (the copy exists for the resident data), n_narrow_launches (launches that read it),
  *                     last_streamed_bytes (bytes the last bi_run_plan streamed: bi_plan_bytes -- the algorithmic bytes of the
  *                     all-double formulation -- less 7 x padded bins for every work item read narrow)
+ *   packed_rows       the dense value kernels (k_morph_reduce / k_morph_single without Beeston-Barlow: single points, batches,
+ *                     plans) stream the template rows as 7 bytes per value instead of 8 where that is exact: the end of a model
+ *                     upload builds a packed shadow of the tensor on the device -- per 512-bin tile of a row the 52 mantissa
+ *                     bits of every value, a 4-bit exponent code, and one exponent base -- if it takes at most a quarter of the
+ *                     free device memory and can be allocated (else no shadow, not an error).  A model has one iff in every
+ *                     tile of every row each value is +0.0 or a positive normal double and the exponents of the non-zero ones
+ *                     span at most 15 values (no -0.0, negative value, subnormal, inf or nan); decoding returns the stored
+ *                     doubles, so every result bit is the same (1, default; 0 = never build or read it; read at upload and at
+ *                     every launch).  Read-only: packed_rows_valid (the resident model has a shadow), n_packed_launches
+ *                     (launches that read it), last_packed_saved_bytes (bytes the last bi_run_plan did not stream thanks to it:
+ *                     padded bins x rows x work items; last_streamed_bytes does not include this saving)
  *   single_timing_reset   (write) zero the single-call wall-time accumulators below
  *   bb_max_group      points per work item of a Beeston-Barlow batch (the points of a grid cell share a pass over the streams):
  *                     1, 2, 4, 8 (default) or 16 -- sixteen keep their accumulators partly in AGPRs, one wave per SIMD
