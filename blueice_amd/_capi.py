@@ -84,6 +84,10 @@ SIGNATURES = {
     'bi_eval_factored': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_eval_sourcewise_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     'bi_eval_sourcewise_fisher': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_sourcewise_expected_counts': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p]),
+    'bi_eval_sourcewise_gof': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_sourcewise_generate_toys': (C.c_int, [_p, _i64, _p, _p, _p, C.c_uint64]),
+    'bi_sourcewise_download_counts': (C.c_int, [_p, _i64, _p]),
     'bi_fit_batched_factored': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                           _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,

@@ -14,6 +14,8 @@
 //     tu_factored.hip     k_morph_factored (value + gradient sums of one point of a source-wise model per item)   bi_k_factored.h
 //     tu_factored_curv.hip, tu_factored_fisher.hip   k_factored_curv, observed and Fisher form (Hessian and expected-information sums of
 //                         one point of a source-wise model per item)                         bi_k_factored_curv.h
+//     tu_sourcewise_expect.hip, tu_sourcewise_gof.hip   k_sourcewise_expect (the per-bin expectation of a source-wise model, written
+//                         out), k_sourcewise_gof (its deviance + Pearson chi2 per item)      bi_k_sourcewise.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -22,7 +24,7 @@
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
 // chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h,
-// bi_k_factored.h and (through it) bi_k_factored_curv.h.
+// bi_k_factored.h and (through it) bi_k_factored_curv.h, and bi_k_sourcewise.h (which shares gof_terms, bi_k_gof_terms.h, with bi_k_gof.h).
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 
@@ -114,6 +116,11 @@ inline int launch_factored_curv(bi_ctx* c, int SC, int EM, bool fisher, int pane
 constexpr int factored_curv_linear(int SC, int EM, bool fisher) { return 1 + SC * (1 + EM) + (fisher ? 0 : SC * (EM * (EM - 1) / 2)); }
 constexpr int factored_curv_panel_sources(int SC, int EM) { return SC * (1 + EM) <= 16 ? SC : EM == 2 ? 2 : 1; }
 constexpr int factored_curv_panels(int SC, int EM) { return SC / factored_curv_panel_sources(SC, EM); }
+// k_sourcewise_expect<SC, EM, PS, NT>: the per-bin expectation of n_items (<= 65 535) points of a source-wise model into a.out,
+// one row per point or (per_source) one per source; k_sourcewise_gof<SC, EM, NT>: half-deviance and Pearson chi2 of one point
+// per item (two result slots).  BI_ERR_INVALID for an (SC, EM) without a variant, as launch_morph_factored
+int launch_sourcewise_expect(bi_ctx* c, int SC, int EM, bool per_source, const SourcewiseExpectArgs& a, int64_t n_items, bool nt);
+int launch_sourcewise_gof(bi_ctx* c, int SC, int EM, const FactoredArgs& a, dim3 grid, bool nt);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -171,6 +171,15 @@ struct FactoredArgs {
     signed char ax[8][3];      // the axis of slot (s, j), -1 for none
 };
 
+// k_sourcewise_expect (bi_k_sourcewise.h): the descriptors of FactoredArgs (rowoff, coef [items][NR][1 + EM], rates, e; no
+// counts, partials or chain) and where the expectation goes
+struct SourcewiseExpectArgs {
+    FactoredArgs f;
+    double* out;               // [items][R][Bp]: R = 1 (mu_b) or S (r_s tau_s,b); the pad bins behind B are written too (zeros)
+    int64_t Bp;
+    int R;
+};
+
 // k_morph_expect (bi_k_gof.h)
 struct ExpectArgs {
     const double* ps;          // [rows][Bp] the dense template tensor

@@ -13,7 +13,8 @@
 // Limits: d <= 32 axes, S <= 8 sources, e_s <= 3 own axes (a source that responds to more belongs on the full grid).  The
 // geometry arrays here are sized by those, not by kMaxDim (PointGeom).  Out of scope, refused where they can be asked for:
 // sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
-// Beeston-Barlow, unbinned data, device-generated toys (the counts are dense doubles from the caller).
+// Beeston-Barlow, unbinned data.  The counts are dense doubles [T][Bp]: the caller's (bi_factored_set_counts) or toys drawn
+// on the device (bi_sourcewise_generate_toys, bi_sourcewise.h, which also holds the expectation and goodness-of-fit layers).
 //
 // bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own (FacBatch, which the curvature calls of
 // bi_factored_curv.h share): screen, fill on host threads, one packed upload, run_item_chunks + k_finish.  The blocks per item
@@ -133,6 +134,33 @@ int fac_check(bi_ctx* c, const char* who, bool need_counts) {
     return BI_OK;
 }
 
+// sum_b lgamma(n + 1) of the T dense datasets counts [T][Bp] (device) -> lgsum [T], once per upload or generator call: the kernels
+// of the grid model's counts (finish_counts).  e: the error state of what the caller queued before; synchronises the stream.
+int fac_counts_lgsum(bi_ctx* c, const char* who, const double* counts, int64_t T, hipError_t e, std::vector<double>& lgsum) {
+    const int64_t B = c->fac.B, Bp = c->fac.Bp;
+    const int nblk = (int)std::min<int64_t>(256, (B + kThreads - 1) / kThreads);
+    const int64_t chunk = 32768;
+    ScratchBuf part, lg;
+    lgsum.assign((size_t)T, 0.0);
+    int rc;
+    if ((rc = dev_alloc(c, part, (size_t)std::min(T, chunk) * nblk * sizeof(double))) || (rc = dev_alloc(c, lg, (size_t)T * sizeof(double)))) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    for (int64_t t0 = 0; t0 < T && e == hipSuccess; t0 += chunk) {
+        const int64_t nt = std::min(chunk, T - t0);
+        hipLaunchKernelGGL(k_counts_lgamma, dim3(nblk, (unsigned)nt), dim3(kThreads), 0, c->stream, counts + t0 * Bp, B, Bp, (double*)part.p, nblk);
+        hipLaunchKernelGGL(k_rows_sum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, (const double*)part.p, nblk,
+                           (double*)lg.p + t0, nt);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(lgsum.data(), lg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    else (void)hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return BI_OK;
+}
+
 // What bi_eval_factored, bi_eval_sourcewise_hess and bi_eval_sourcewise_fisher share: the screen of the P points, the descriptors
 // of the live ones (filled on host threads), their one packed upload, and the launch of a kernel over them in sub-batches.
 //   order 0 / 1    value / with the gradient's columns (k_morph_factored)
@@ -150,15 +178,16 @@ struct FacBatch {
     PackedUpload pu;
     size_t first_extra = 0;                     // index of the caller's first own part in pu
 
-    FacBatch(bi_ctx* ctx, int order_)
+    bool dataset_test;                          // the screen tests the dataset index (calls that read counts)
+
+    FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true)
         : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
-          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point) {}
+          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts) {}
 
     // reset(p) writes the caller's defaults of point p; status [P] (nullable) gets every point's bits
     template <class F>
     void screen(int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, int32_t* status, F reset) {
         std::vector<int32_t> st((size_t)P);
-        const bool dataset_test = order != 3;
         parallel_for(P, 2048, [&](int64_t lo, int64_t hi) {
             FacGeom g;
             for (int64_t p = lo; p < hi; ++p) {
@@ -216,7 +245,7 @@ struct FacBatch {
                         for (int j = 0; j < fs.e; ++j) q[1 + j] = rs * fs.dM[j];
                     }
                 }
-                cnt_off[(size_t)i] = order == 3 ? 0 : ds * m.Bp;
+                cnt_off[(size_t)i] = dataset_test ? ds * m.Bp : 0;
             }
         });
     }
@@ -233,11 +262,8 @@ struct FacBatch {
     }
     const double* out() const { return (const double*)pu.host_out(); }
 
-    // One kernel over the live points: nsl result slots per item, perm / slot_lg [n][nsl] (device) where a slot's sum goes and
-    // what k_finish subtracts from it.  The blocks of an item depend on the rows' length alone; sub-batches keep the partial
-    // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.
-    template <class L>
-    int run(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+    // what every launch over this batch shares: the model, the tile geometry, the sources' own axes
+    FactoredArgs args() const {
         FactoredArgs a{};
         a.ps = (const double*)m.ps.p;
         a.counts = (const double*)m.counts.p;
@@ -257,6 +283,23 @@ struct FacBatch {
                 }
             }
         }
+        return a;
+    }
+    // ... and the descriptors of the items from `at` on
+    void point_at(FactoredArgs& b, int64_t at) const {
+        b.rowoff = pu.dev<int64_t>(0) + at * NR;
+        b.coef = pu.dev<double>(1) + at * NR * WC;
+        b.rates = pu.dev<double>(2) + at * SC;
+        b.item_cnt = pu.dev<int64_t>(3) + at;
+        b.chain = pu.dev<double>(4) + at * SC * W;
+    }
+
+    // One kernel over the live points: nsl result slots per item, perm / slot_lg [n][nsl] (device) where a slot's sum goes and
+    // what k_finish subtracts from it.  The blocks of an item depend on the rows' length alone; sub-batches keep the partial
+    // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.
+    template <class L>
+    int run(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+        const FactoredArgs a = args();
         const int nbx = std::min(a.n_tiles, kFacBlocks);
         const int64_t per_call = std::max<int64_t>(1, kFacPartialDoubles / ((int64_t)nbx * nsl));
         for (int64_t j0 = 0; j0 < n_items; j0 += per_call) {
@@ -264,12 +307,7 @@ struct FacBatch {
             const int rc = run_item_chunks(c, nj, a.n_tiles, nsl, perm + j0 * nsl, slot_lg + j0 * nsl, (double*)pu.host_out(), nullptr, what,
                                            [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
                                                FactoredArgs b = a;
-                                               const int64_t at = j0 + i0;
-                                               b.rowoff = pu.dev<int64_t>(0) + at * NR;
-                                               b.coef = pu.dev<double>(1) + at * NR * WC;
-                                               b.rates = pu.dev<double>(2) + at * SC;
-                                               b.item_cnt = pu.dev<int64_t>(3) + at;
-                                               b.chain = pu.dev<double>(4) + at * SC * W;
+                                               point_at(b, j0 + i0);
                                                b.partial = partial;
                                                b.pflags = pflags;
                                                return launch(b, grid);
@@ -476,31 +514,11 @@ int bi_factored_set_counts(bi_ctx* c, int64_t T, const double* counts) {
     for (int64_t t = 0; t < T; ++t) std::copy(counts + t * B, counts + (t + 1) * B, padded.begin() + (size_t)(t * Bp));
     DevBuf fresh;
     if ((rc = dev_alloc(c, fresh, padded.size() * sizeof(double)))) return rc;
-    // sum_b lgamma(n + 1) per dataset, once: the kernels of the grid model's counts (finish_counts)
-    const int nblk = (int)std::min<int64_t>(256, (B + kThreads - 1) / kThreads);
-    const int64_t chunk = 32768;
-    ScratchBuf part, lg;
-    std::vector<double> lgsum((size_t)T, 0.0);
-    hipError_t e = hipSuccess;
-    if ((rc = dev_alloc(c, part, (size_t)std::min(T, chunk) * nblk * sizeof(double))) || (rc = dev_alloc(c, lg, (size_t)T * sizeof(double)))) {
+    hipError_t e = hipMemcpyAsync(fresh.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    std::vector<double> lgsum;
+    if ((rc = fac_counts_lgsum(c, "bi_factored_set_counts", (const double*)fresh.p, T, e, lgsum))) {
         dev_free(fresh);
         return rc;
-    }
-    e = hipMemcpyAsync(fresh.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
-    for (int64_t t0 = 0; t0 < T && e == hipSuccess; t0 += chunk) {
-        const int64_t nt = std::min(chunk, T - t0);
-        hipLaunchKernelGGL(k_counts_lgamma, dim3(nblk, (unsigned)nt), dim3(kThreads), 0, c->stream, (const double*)fresh.p + t0 * Bp, B, Bp,
-                           (double*)part.p, nblk);
-        hipLaunchKernelGGL(k_rows_sum, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream, (const double*)part.p, nblk,
-                           (double*)lg.p + t0, nt);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(lgsum.data(), lg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    else (void)hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        dev_free(fresh);
-        return fail(c, BI_ERR_HIP, "bi_factored_set_counts: %s", hipGetErrorString(e));
     }
     dev_free(m.counts);
     m.counts = fresh;

@@ -1611,6 +1611,7 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_real.h"
 #include "bi_factored.h"
 #include "bi_factored_curv.h"
+#include "bi_sourcewise.h"
 #include "bi_fisher.h"
 #include "bi_sampler.h"
 #include "bi_grid.h"

@@ -207,6 +207,31 @@ def bestfit_device(lf, guess=None, **kwargs):
     return OrderedDict((k, float(v[0])) for k, v in best.items()), float(ll[0])
 
 
+def _simulate_toys_at(lf, n_toys, seed, livetime_days, truth):
+    """`lf.simulate_toys(n_toys, seed=, livetime_days=, **truth)` -- spelled as `simulate_toys_points` with a one-row `points`
+    dict for a class that says so (`toys_through_points`: a source-wise model, whose bound `simulate_toys` stays refused).  The
+    toys are the same either way: toy t of the call is toy toy_offset + t of the seed's ensemble."""
+    if getattr(type(lf), 'toys_through_points', False):
+        lf.simulate_toys_points({k: np.array([float(v)]) for k, v in truth.items()}, [int(n_toys)], seed=seed, livetime_days=livetime_days)
+    else:
+        lf.simulate_toys(n_toys, seed=seed, livetime_days=livetime_days, **truth)
+
+
+def _binned_or_source_wise(lf, what, binning=None):
+    """The gate of the layers that also take a source-wise model (toy fits, goodness of fit, expected_counts_points): a
+    `BinnedLogLikelihood` without Beeston-Barlow (`_binned_for_gof`), or a prepared `SourceWiseBinnedLogLikelihood`, which has no
+    coarse views: `binning` must be None for it."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if isinstance(lf, SourceWiseBinnedLogLikelihood):
+        if binning is not None:
+            raise NotImplementedError("%s(binning=...) is not available for a source-wise model (SourceWiseBinnedLogLikelihood): it "
+                                      "has no coarse views" % what)
+        if not lf.is_prepared:
+            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+        return lf
+    return _binned_for_gof(lf, what)
+
+
 def bestfit_toys(lf, t0=0, t1=None, **kwargs):
     """Fit every dataset the likelihood holds -- the toys of `simulate_toys`, or a stack handed to `set_binned_data` --
     at the same time: one problem per dataset on the batched profile-fit engine, one device call per optimiser iteration
@@ -248,7 +273,7 @@ def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, f
         for t0 in range(0, int(n_toys), int(chunk)):
             n = min(int(chunk), int(n_toys) - t0)
             ctx.set_param('toy_offset', int(first_toy) + t0)
-            lf.simulate_toys(n, seed=seed, livetime_days=livetime_days, **(truth or {}))
+            _simulate_toys_at(lf, n, seed, livetime_days, truth or {})
             b, ll = bestfit_toys(lf, livetime_days=livetime_days, **fit_kwargs)
             lls.append(ll)
             if best is None:
@@ -357,8 +382,8 @@ def toy_test_statistics(lf, target, hypotheses, n_toys, seed=0, kind='central', 
                 pts[target] = hyp[i_a:i_b]
                 lf.simulate_toys_points(pts, np.bincount(i_of - i_a, minlength=i_b - i_a), seed=seed, livetime_days=livetime_days)
             else:
-                lf.simulate_toys(f1 - f0, seed=seed, livetime_days=livetime_days,
-                                 **dict({k: float(v[i_a]) for k, v in truth.items()}, **{target: float(hyp[i_a])}))
+                _simulate_toys_at(lf, f1 - f0, seed, livetime_days,
+                                  dict({k: float(v[i_a]) for k, v in truth.items()}, **{target: float(hyp[i_a])}))
             ds, h_of_toy = np.arange(f1 - f0), hyp[i_of]
             try:
                 start, ll_cond, info_c = bestfit_batched(lf, points={target: h_of_toy}, datasets=ds, livetime_days=livetime_days,
@@ -458,8 +483,9 @@ def expected_counts_points(lf, points, per_source=False, livetime_days=None):
     absent parameters take their defaults), as `eval_points` -> mu [P, *bin_shape], or [P, S, *bin_shape] with per_source
     (source order: `source_name_list`; the sum over sources is the total).  Live time, rate multipliers and efficiencies
     enter exactly as in `lf(**params)` (the same host terms); the morph runs on the device (bi_expected_counts), where the
-    dense templates lie -- no data are needed.  A point outside the anchor box or with unphysical rates gets nan."""
-    _binned_for_gof(lf, 'expected_counts_points')
+    dense templates lie -- no data are needed.  A point outside the anchor box or with unphysical rates gets nan.
+    Also for a prepared source-wise model (bi_sourcewise_expected_counts)."""
+    _binned_or_source_wise(lf, 'expected_counts_points')
     z, scale, _ = lf._batch_terms(points, livetime_days)
     mu = lf.ctx.expected_counts(z if z.shape[1] else None, scale, per_source=per_source)
     return mu.reshape(mu.shape[:-1] + tuple(lf.bin_shape))
@@ -468,7 +494,8 @@ def expected_counts_points(lf, points, per_source=False, livetime_days=None):
 def expected_counts(lf, per_source=False, livetime_days=None, **params):
     """The expected events per bin at one parameter point -> array of `lf.bin_shape`, or [S, *bin_shape] with per_source:
     the best-fit histogram, the denominator of a pull.  As `expected_counts_points`, with the host terms of the scalar
-    call `lf(**params)`; nan outside the anchor box or where the rates are unphysical."""
+    call `lf(**params)`; nan outside the anchor box or where the rates are unphysical.  Refused for a source-wise model
+    (SourceWiseBinnedLogLikelihood): call `expected_counts_points(lf, points, per_source=)` with one-row arrays there."""
     _binned_for_gof(lf, 'expected_counts')
     _, zs, scale = lf._host_terms(livetime_days, params)
     S = len(lf.source_name_list)
@@ -494,8 +521,9 @@ def gof_statistics(lf, points=None, datasets=None, livetime_days=None, binning=N
     over the fine bins of every cell on the device (bi_expected_coarse, bi_coarse_counts) and the same per-cell forms
     (`coarse_statistics`); n_bins is C, and n_events counts the events inside the cells.  THE STATISTIC IS THEN A STATEMENT
     ABOUT THE COARSE CELLS ONLY: what happens inside a cell, or in fine bins that belong to no cell, is invisible to it -- in
-    particular an event in a fine bin with no expectation no longer forces +inf, unless its whole cell expects nothing."""
-    _binned_for_gof(lf, 'gof_statistics')
+    particular an event in a fine bin with no expectation no longer forces +inf, unless its whole cell expects nothing.
+    A prepared source-wise model is taken too (bi_eval_sourcewise_gof), without `binning`."""
+    _binned_or_source_wise(lf, 'gof_statistics', binning)
     if not lf.is_data_set:
         raise NotPreparedException("gof_statistics requires you to first set the data using set_data()")
     pts = dict(fixed)
@@ -582,8 +610,9 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
 
     binning: a `CoarseBinning` -- the data and every toy are still FITTED on the fine bins, but the statistic of steps 2 and 5
     is formed over the cells of the binning (`gof_statistics(..., binning=)`: a statement about the coarse cells only), where
-    a test on ~10^4 events has power that it lacks on 10^6 fine bins; ndof = n_cells - n_floating."""
-    _binned_for_gof(lf, 'goodness_of_fit')
+    a test on ~10^4 events has power that it lacks on 10^6 fine bins; ndof = n_cells - n_floating.
+    A prepared source-wise model is taken too, without `binning` (its toys: `simulate_toys_points` with one truth)."""
+    _binned_or_source_wise(lf, 'goodness_of_fit', binning)
     if statistic not in ('deviance', 'pearson'):
         raise ValueError("statistic must be 'deviance' or 'pearson'")
     n, chunk = int(n_toys), max(int(chunk), 1)
@@ -606,7 +635,7 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
         for t0 in range(0, n, chunk):
             m = min(chunk, n - t0)
             ctx.set_param('toy_offset', int(first_toy) + t0)
-            lf.simulate_toys(m, seed=seed, livetime_days=livetime_days, **truth)
+            _simulate_toys_at(lf, m, seed, livetime_days, truth)
             fitted = {}
             if best:
                 fitted, _, info = bestfit_toys(lf, livetime_days=livetime_days, return_info=True, **fit_options, **fixed)

@@ -5,7 +5,9 @@
     lf(**params), lf.eval_points, lf.value_and_gradient, lf.values_and_gradients,
     lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval,
     lf.value_gradient_hessian, lf.values_gradients_hessians, lf.bestfit_minuit, blueice_amd.inference.hesse(lf, values),
-    lf.fisher_information_points, lf.expected_covariance, lf.expected_errors
+    lf.fisher_information_points, lf.expected_covariance, lf.expected_errors,
+    lf.simulate_toys_points, lf.toy_test_statistics, lf.neyman_thresholds, and as functions of blueice_amd.inference:
+    bestfit_toys(lf), toy_mc_fits(lf, n), gof_statistics(lf, ...), goodness_of_fit(lf, ...), expected_counts_points(lf, points)
 
 `BinnedLogLikelihood` morphs over ONE tensor-product grid of all shape parameters: prod n_i anchor models in HBM and S 2^d
 rows per evaluation, which caps the number of shape parameters at a handful.  Here every source morphs over the parameters
@@ -20,9 +22,17 @@ three own axes, so the Hessian and the expected information over all d + S param
 32 per-source basis columns and a few linear sums, whatever the number of shape parameters.  `lf.hesse` and
 `lf.fisher_information` stay unbound (their messages name the spellings that work).
 
+Toys, goodness of fit and the expectation per bin run on the device too (bi_sourcewise_generate_toys, bi_eval_sourcewise_gof,
+bi_sourcewise_expected_counts): toy ensembles at truth points replace the counts as dense datasets and are fitted in lock-step by
+the layers that exist for the grid model, which duck-type on the context.  The bound names the earlier tests pin -- lf.simulate_toys,
+lf.bestfit_toys, lf.toy_mc_fits, lf.gof_statistics, lf.goodness_of_fit, lf.expected_counts, lf.expected_counts_points -- stay
+refused and name the spelling that works; `blueice_amd.inference.expected_counts(lf, **params)` stays refused as well (use the
+`_points` form with one-row arrays).
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, toys, goodness of fit, Asimov data, grids, coarse views, expected counts and the ensemble sampler.
+full_output calls, eval_toys*, Asimov and real-valued data, grids, coarse views (and `binning=` in the goodness-of-fit calls) and
+the ensemble sampler.
 """
 from collections import OrderedDict
 
@@ -51,14 +61,23 @@ def _find_cell(g, z):
 class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
-    eval_grad, eval_hess, eval_fisher, fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the
-    DeviceContext (plans, toys, the sampler ...) has a meaning here and is an AttributeError."""
+    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, generate_toys_points, download_counts, set_param / get_param,
+    fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
+    meaning here and is an AttributeError."""
 
     def __init__(self, device=None):
         self._dev = DeviceContext(device)
         self.device = self._dev.device
         self.d = self.S = self.B = None
         self.T = 0
+        self._counts = None
+
+    def set_param(self, name, value):
+        """a parameter of the underlying context (`toy_offset`: the number of a generator call's first toy in the seed's ensemble)"""
+        self._dev.set_param(name, value)
+
+    def get_param(self, name):
+        return self._dev.get_param(name)
 
     def close(self):
         self._dev.close()
@@ -83,6 +102,7 @@ class SourceWiseContext:
         self.anchor_z, self.own_axes = anchor_z, own_axes
         self.mus = [np.zeros(tuple(len(anchor_z[i]) for i in own)) for own in own_axes]      # host copy of the rates
         self.T = 0
+        self._counts = None
 
     def set_anchor(self, s, local_index, ps_row, mu):
         dev = self._dev
@@ -106,7 +126,28 @@ class SourceWiseContext:
         self.T = T
 
     def download_counts(self, t=0):
-        return self._counts[int(t)].copy()
+        """dataset t [B] of whatever the store holds: the host copy of uploaded counts, or toys read from the device"""
+        if self._counts is not None:
+            return self._counts[int(t)].copy()
+        dev = self._dev
+        out = np.empty(self.B, dtype=np.float64)
+        dev._check(dev._lib.bi_sourcewise_download_counts(dev._h, int(t), ptr(out)))
+        return out
+
+    def generate_toys_points(self, z, rate_scale=None, n_toys=1, seed=0):
+        """Replace the counts by sum(n_toys) toy datasets drawn on the device, n_toys[h] of them at truth (z[h], rate_scale[h]),
+        truth-major (bi_sourcewise_generate_toys: always one draw per bin; toy t is toy toy_offset + t of the seed's ensemble).
+        -> methods [H]: 0, or -1 for a truth without toys (DeviceContext.generate_toys_points' shape)."""
+        dev = self._dev
+        n_toys = np.ascontiguousarray(np.atleast_1d(n_toys), dtype=np.int64)
+        H = len(n_toys)
+        z = np.ascontiguousarray(as_f64(z).reshape(H, self.d)) if self.d else None
+        if rate_scale is not None:
+            rate_scale = np.ascontiguousarray(np.broadcast_to(as_f64(np.atleast_2d(rate_scale)), (H, self.S)))
+        dev._check(dev._lib.bi_sourcewise_generate_toys(dev._h, H, ptr(z), ptr(rate_scale), ptr(n_toys), int(seed) & (2**64 - 1)))
+        self._counts = None                     # the toys exist on the device only
+        self.T = int(n_toys.sum())
+        return np.where(n_toys > 0, 0, -1).astype(np.int32)
 
     # -- evaluation ------------------------------------------------------------------------
     def _point_args(self, z, rate_scale, dataset):
@@ -156,6 +197,27 @@ class SourceWiseContext:
                                                     ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], hess, status
 
+    def eval_gof(self, z, rate_scale=None, dataset=None):
+        """Goodness of fit of the data term (bi_eval_sourcewise_gof) -> (half-deviance [P], Pearson chi2 [P], status [P]) of point
+        p against dataset[p]; +inf / nan where the likelihood is -inf / nan: DeviceContext.eval_gof's shapes."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        half_deviance = np.empty(P, dtype=np.float64)
+        pearson = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_gof(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(half_deviance), ptr(pearson),
+                                                   ptr(status)))
+        return half_deviance, pearson, status
+
+    def expected_counts(self, z, rate_scale=None, per_source=False):
+        """The expectation per bin (bi_sourcewise_expected_counts) -> mu [P, B], or r_s tau_s [P, S, B] per source; nan rows for
+        points outside the anchor box or with unphysical rates.  No counts are needed."""
+        dev = self._dev
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        out = np.empty((P, self.S, self.B) if per_source else (P, self.B), dtype=np.float64)
+        dev._check(dev._lib.bi_sourcewise_expected_counts(dev._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
+        return out
+
     def eval_fisher(self, z, rate_scale=None):
         """The expected (Fisher) information at P truths, no counts needed (bi_eval_sourcewise_fisher) -> (info [P, d + S, d + S],
         total expectation [P], unbounded [P, d + S], status [P]): DeviceContext.eval_fisher's shapes and meaning."""
@@ -202,10 +264,17 @@ class SourceWiseContext:
         return out
 
 
-# the two bound names that stay refused although the layer behind them exists, and the spellings that work
+# the bound names that stay refused although the layer behind them exists, and the spellings that work
 _REFUSED_SPELLINGS = {
     'hesse': "blueice_amd.inference.hesse(lf, values) (or lf.bestfit_minuit for the errors of a fit)",
     'fisher_information': "lf.fisher_information_points(points), lf.expected_covariance(**truth) or lf.expected_errors(**truth)",
+    'simulate_toys': "lf.simulate_toys_points(points, n_toys, seed) with one-row arrays in `points`",
+    'bestfit_toys': "blueice_amd.inference.bestfit_toys(lf, ...)",
+    'toy_mc_fits': "blueice_amd.inference.toy_mc_fits(lf, n_toys, ...)",
+    'gof_statistics': "blueice_amd.inference.gof_statistics(lf, points, datasets=...)",
+    'goodness_of_fit': "blueice_amd.inference.goodness_of_fit(lf, n_toys=...)",
+    'expected_counts': "blueice_amd.inference.expected_counts_points(lf, points, per_source=) with one-row arrays in `points`",
+    'expected_counts_points': "blueice_amd.inference.expected_counts_points(lf, points, per_source=)",
 }
 
 
@@ -215,7 +284,8 @@ def _refused(name):
             raise NotImplementedError("lf.%s is not bound on a source-wise model (SourceWiseBinnedLogLikelihood); call %s"
                                       % (name, _REFUSED_SPELLINGS[name]))
         raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
-                                  "Hessian, expected information and the fit, scan and interval layers are" % name)
+                                  "Hessian, expected information, the fit, scan and interval layers, toys at truth points and "
+                                  "goodness of fit are" % name)
     method.__name__ = name
     return method
 
@@ -223,15 +293,16 @@ def _refused(name):
 class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
     """Binned Poisson likelihood whose sources each morph over their own shape parameters (see the module's docstring)."""
 
-    _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'toy_test_statistics', 'neyman_thresholds', 'expected_counts',
+    _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'expected_counts',
                 'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
                 'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
                 'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
                 'fisher_information', 'hesse', 'sample_posterior', 'bestfit_emcee',
-                'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'simulate_toys_points', 'eval_toys', 'eval_toys_points',
+                'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'eval_toys', 'eval_toys_points',
                 'ps_interpolator', 'n_model_events_interpolator')
 
     supports_gradient = True
+    toys_through_points = True      # inference draws its toys with simulate_toys_points (the bound simulate_toys stays refused)
 
     @property
     def supports_hessian(self):
@@ -325,6 +396,31 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
             self._binned = Histdd(bins=edges, axis_names=names)
             self._binned.histogram = self.ctx.download_counts(0).reshape(self.bin_shape)
         return self._binned
+
+    @_needs_preparation
+    def simulate_toys_points(self, points, n_toys, seed=0, livetime_days=None):
+        """Draw toys ON THE DEVICE at H truth points in one generator call (bi_sourcewise_generate_toys) and make them the
+        likelihood's data: n_toys[h] toys (an int: the same number everywhere) at truth h, truth-major.  points: dict parameter
+        name -> array [H] (scalars broadcast; absent parameters take their defaults), as `eval_points`.  Per bin n ~ Poisson(mu_b),
+        always one draw per bin; toy t of the call is toy `toy_offset + t` (the context parameter) of the seed's ensemble, so an
+        ensemble over many hypotheses does not depend on how they are grouped into calls -- `BinnedLogLikelihood
+        .simulate_toys_points`' contract.  Afterwards `toy_truth` [T] holds the truth index of every dataset.
+        -> methods [H]: 0 = drawn bin by bin, -1 = no toys."""
+        z, scale, _ = self._batch_terms(points, livetime_days)
+        H = max(len(z), np.size(n_toys))
+        n_toys = np.ascontiguousarray(np.broadcast_to(np.asarray(n_toys, dtype=np.int64), (H,)))
+        z, scale = np.broadcast_to(z, (H, z.shape[1])), np.broadcast_to(scale, (H, scale.shape[1]))
+        for i, name in enumerate(self.shape_parameters):
+            lo, hi = self.get_bounds(name)
+            outside = np.flatnonzero(~((z[:, i] >= lo) & (z[:, i] <= hi)))
+            if len(outside):
+                raise ValueError("cannot simulate outside the anchor box (truth %d: %s = %r)" % (outside[0], name, z[outside[0], i]))
+        methods = self.ctx.generate_toys_points(z if z.shape[1] else None, scale, n_toys, seed)
+        self._data = None
+        self._binned = None
+        self.is_data_set = True
+        self.toy_truth = np.repeat(np.arange(H), n_toys)
+        return methods
 
     # -- evaluation ------------------------------------------------------------------------
     @_needs_data

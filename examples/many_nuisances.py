@@ -1,6 +1,6 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--measure [--rounds 31]]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--measure | --measure-toys [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
 grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
@@ -11,7 +11,11 @@ evaluation -- and the native fit loop floats all twelve parameters.
 (2) bestfit_batched: every rate and every constrained shape parameter floating;
 (3) likelihood_ratio_scan over the signal's rate multiplier: --scan hypotheses profiled in lock-step (bi_fit_batched_factored);
 (4) bestfit_minuit: the fit with its parabolic errors from the analytic Hessian (bi_eval_sourcewise_hess), the correlation matrix
-    (inference.hesse), and expected_errors at the truth before any data (bi_eval_sourcewise_fisher).
+    (inference.hesse), and expected_errors at the truth before any data (bi_eval_sourcewise_fisher);
+(5) goodness_of_fit: the deviance of the data at their fit and its p-value from --toys toys drawn at the fit on the device
+    (bi_sourcewise_generate_toys), each fitted in lock-step and scored (bi_eval_sourcewise_gof), beside the asymptotic reading;
+(6) neyman_thresholds: the test statistic's critical values from toys at a few hypotheses of the signal's rate multiplier,
+    handed to one_parameter_interval in place of Wilks' chi-square.
 
 --measure times the C ABI instead, at a shape BOTH routes can hold: d = 4, S = 4, one own axis per source, 5 anchors, 100^3
 bins, dense data, 64 points per call -- bi_eval_factored with its gradient (8 rows per point) against bi_eval_grad on the
@@ -20,6 +24,10 @@ per second against the stream_bandwidth(items = 64, rows = 8) probe of the same 
 shape: bi_eval_sourcewise_hess against the (2 F + 1) P gradient points of the central differences it replaces (one bi_eval_factored
 call, as the class takes them) and against bi_eval_hess on the expanded grid, bi_eval_sourcewise_fisher against bi_eval_fisher
 there; and both on a panelled class (8 sources x 2 own axes of the same 4, four Gram panels), which only the source-wise route holds.
+
+--measure-toys times, at the same source-wise shape (no expanded grid is built), bi_eval_sourcewise_gof against bi_eval_factored
+values-only, bi_sourcewise_expected_counts against the bytes it must write, and bi_sourcewise_generate_toys for 64 toys against
+numpy.random.Generator.poisson on the same expectation on the host plus the upload through bi_factored_set_counts.
 """
 import argparse
 import time
@@ -30,6 +38,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--bins', type=int, default=20, help='bins per analysis axis (two axes)')
 ap.add_argument('--scan', type=int, default=33, help='hypotheses of the profile scan')
 ap.add_argument('--measure', action='store_true', help='time bi_eval_factored against bi_eval_grad on the expanded grid')
+ap.add_argument('--measure-toys', action='store_true', help='time the goodness-of-fit, expected-counts and toy-generator calls')
+ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
 ap.add_argument('--rounds', type=int, default=31)
 ap.add_argument('--measure-bins', type=int, default=100, help='bins per axis (three axes) of the measured shape')
 args = ap.parse_args()
@@ -161,8 +171,74 @@ def measure_curvature(fac, full, z, r, d, S, P, rng, g, B):
     pan.close()
 
 
+def measure_toys():
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B, P = 5, args.measure_bins ** 3, 64
+    Bp = (B + 511) // 512 * 512
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    z = rng.uniform(-1.9, 1.9, (P, d))
+    r = rng.uniform(0.8, 1.2, (P, S))
+    mid = n_a // 2
+    fac.set_counts(rng.poisson(sum(mus[s, mid] * rows[s, mid] for s in range(S))).astype(float))
+    print('source-wise model: %d rows, %.2f GB resident (it stays in the 256 MB Infinity Cache: every figure below is cache-assisted)'
+          % (S * n_a, S * n_a * Bp * 8 / 1e9), flush=True)
+    half, pearson, _ = fac.eval_gof(z, r)
+    ll, _ = fac.eval(z, r)
+    print('deviance of the %d points: %.6g .. %.6g; ll %.6g .. %.6g' % (P, 2 * half.min(), 2 * half.max(), ll.min(), ll.max()))
+    truth_z, truth_r = np.tile(z[:1], (1, 1)), np.tile(r[:1], (1, 1))
+
+    def host_toys():
+        mu = fac.expected_counts(truth_z, truth_r)[0]
+        fac.set_counts(np.random.default_rng(5).poisson(mu, size=(64, B)).astype(float))
+
+    def host_toys_draw_only():
+        np.random.default_rng(5).poisson(mu_host, size=(64, B))
+
+    mu_host = fac.expected_counts(truth_z, truth_r)[0]
+    alternate([('bi_eval_sourcewise_gof', lambda: fac.eval_gof(z, r)),
+               ('bi_eval_factored, values', lambda: fac.eval(z, r)),
+               ('bi_sourcewise_expected_counts (with its download of %.2f GB)' % (P * B * 8 / 1e9), lambda: fac.expected_counts(z, r)),
+               ('bi_sourcewise_expected_counts, one point', lambda: fac.expected_counts(truth_z, truth_r))], P)
+    rounds, args.rounds = args.rounds, max(3, args.rounds // 10)         # the host route takes seconds per call
+    alternate([('bi_sourcewise_generate_toys, 64 toys at one truth', lambda: fac.generate_toys_points(truth_z, truth_r, [64], 7)),
+               ('numpy poisson of 64 x B on the host + bi_factored_set_counts', host_toys),
+               ('    of which numpy.random.Generator.poisson alone', host_toys_draw_only)], 1)
+    args.rounds = rounds
+    # the kernels alone, from device events around the launches, in a pass of their own
+    dev = fac._dev
+    for name, call, gb in (('k_sourcewise_gof', lambda: fac.eval_gof(z, r), (2 * S + 1) * Bp * 8 * P / 1e9),
+                           ('k_morph_factored, values', lambda: fac.eval(z, r), (2 * S + 1) * Bp * 8 * P / 1e9),
+                           ('k_sourcewise_expect', lambda: fac.expected_counts(z, r), (2 * S + 1) * Bp * 8 * P / 1e9),
+                           ('toy generator kernels', lambda: fac.generate_toys_points(truth_z, truth_r, [64], 7), (2 * 64 + 2 * S + 4) * Bp * 8 / 1e9)):
+        dev.profile(True)
+        ks = []
+        for _ in range(args.rounds):
+            call()
+            ks.append(dev.profile_read()[1] * 1e-3)
+        dev.profile(False)
+        print('%-26s kernels %s per call; %.2f GB read and written -> %.2f TB/s' % (name, quartiles(ks), gb, gb / np.median(ks) / 1e3), flush=True)
+    print('(bytes: gof and values read 2 S rows and the counts per point; expect reads 2 S rows and writes one; the generator writes 64 rows, '
+          'reads them once for the lgamma sums, and reads 2 S rows and reads and writes mu and exp(-mu))')
+    print('not measured: the panelled classes <8, 2> and <8, 3>, per_source = 1, more than one truth per generator call')
+    fac.close()
+
+
 if args.measure:
     measure()
+    raise SystemExit(0)
+if args.measure_toys:
+    measure_toys()
     raise SystemExit(0)
 
 from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood  # noqa: E402
@@ -213,3 +289,24 @@ sigma = np.sqrt(np.diag(cov))
 print('    correlation matrix (%s):' % ', '.join(k.replace('_rate_multiplier', '') for k in cov_names))
 for row in cov / np.outer(sigma, sigma):
     print('    ' + ' '.join('%6.2f' % v for v in row))
+
+from blueice_amd import inference  # noqa: E402
+t0 = time.perf_counter()
+gof = inference.goodness_of_fit(lf, n_toys=args.toys, seed=1)
+print('(5) goodness_of_fit: deviance %.2f over %d bins - %d floating = %d degrees of freedom; p = %.3f from %d toys (%d failed fits), '
+      'asymptotic p = %.3f, %.3f s' % (gof.observed, args.bins ** 2, len(gof.best), gof.ndof, gof.p_value, len(gof.toys), gof.n_failed,
+                                     gof.p_value_chi2, time.perf_counter() - t0))
+mu = inference.expected_counts_points(lf, {k: np.array([v]) for k, v in gof.best.items()}, per_source=True)[0]
+print('    expected events per source at the fit: ' + ', '.join('%.1f' % v for v in mu.reshape(4, -1).sum(axis=1))
+      + '; observed %d' % len(data))
+
+hyp = np.linspace(0.8, 1.6, 5)
+n_per = max(args.toys // 5, 10)
+t0 = time.perf_counter()
+table = lf.neyman_thresholds('s0_rate_multiplier', hyp, n_per, kind='upper', seed=2)
+print('(6) neyman_thresholds: %d toys at each of %d hypotheses of s0_rate_multiplier, two fits per toy in lock-step, %.3f s'
+      % (n_per, len(hyp), time.perf_counter() - t0))
+print('    critical values of the 90 % upper limit: ' + ', '.join('%.2f' % v for v in table.critical_values(0.9))
+      + '   (Wilks: 1.64)')
+limit_toys = lf.one_parameter_interval('s0_rate_multiplier', 3.0, confidence_level=0.9, kind='upper', t_ppf=table)
+print('    90 %% upper limit with the toy-calibrated thresholds: %.4f (Wilks: %.4f)' % (limit_toys, limit))

@@ -537,7 +537,9 @@ int bi_fit_batched_real(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, 
  *
  * Limits: d <= 32, S <= 8, e_s <= 3 (a source that responds to more axes belongs on the grid model).  Out of scope, and
  * refused where they can be asked for: sources that may go negative (template entries must be finite and >= 0),
- * Beeston-Barlow, unbinned data, device-generated toys.
+ * Beeston-Barlow, unbinned data.  The store's counts are dense doubles, [T][B]: the caller's (bi_factored_set_counts) or toys
+ * drawn on the device at truth points of this model (bi_sourcewise_generate_toys below, with the expectation per bin and the
+ * goodness-of-fit sums).
  *
  * The model is a store of its own inside the context, beside the grid model and released by bi_destroy (or the next
  * bi_factored_begin).  It does not make the context "ready": every other entry point of this header keeps refusing a context
@@ -597,6 +599,49 @@ int bi_eval_sourcewise_hess(bi_ctx* ctx, int64_t P, const double* z, const doubl
                             double* grad, double* hess, int32_t* status);
 int bi_eval_sourcewise_fisher(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, double* info, double* total,
                               int64_t* unbounded, int32_t* status);
+
+/* ... the expectation per bin, goodness of fit and toy ensembles of a source-wise model.  mu_b is the chain stated above, to the
+ * bit: w_c from 1.0 in own-axis order, tau_s,b one fused multiply-add per corner from 0.0, M_s left to right, r_s = M_s rs_s,
+ * mu_b one fused multiply-add per source from 0.0.  rate_scale NULL: ones.
+ *   bi_sourcewise_expected_counts   out [P][B] = mu_b, or with per_source != 0 out [P][S][B] = r_s tau_s,b (ONE multiplication of
+ *                               the two; the S rows sum to mu_b up to rounding).  Rows of a rejected point -- the box test on
+ *                               all d axes, then the rates; no dataset test -- are nan in every entry; no status is reported.
+ *                               Needs the source-wise model and nothing else: no counts are read or touched.  The points are
+ *                               processed in sub-batches: the device scratch is bounded (64 MiB of rows, or one point's) however
+ *                               large P B is.
+ *   bi_eval_sourcewise_gof      bi_eval_gof's contract on the store's dense counts: per point p, against dataset[p] (NULL: dataset 0),
+ *                                   half_deviance [P]   sum_b  (mu_b - n_b) - n_b log(mu_b / n_b)     (n_b = 0: mu_b)
+ *                                   pearson [P]         sum_b  (n_b - mu_b)^2 / mu_b                  (n_b = 0: mu_b)
+ *                               both summed bin by bin without the cancellation of two log-likelihoods.  n_b = 0 and mu_b = 0
+ *                               adds 0 to both; wherever ll at the point is -inf (an event where mu_b = 0, a count that is
+ *                               negative or no integer) BOTH are +inf, wherever it is nan both are nan.  Early exits in
+ *                               bi_eval_factored's order and with its status bits (status [P] or NULL): dataset outside [0, T),
+ *                               box, rates; all three give +inf in both.  Needs counts (BI_ERR_STATE without).
+ *   bi_sourcewise_generate_toys     T = sum_h n_toys[h] toys at H truths, n_toys[h] >= 0 of them at (z[h], rate_scale[h]),
+ *                               truth-major; z [H][d] (NULL when d = 0), rate_scale [H][S] or NULL; 1 <= T < 2^31.  Toy t of the
+ *                               call is toy D = toy_offset + t of the seed's ensemble (the context parameter), and its counts are
+ *                               ALWAYS stream A of bi_generate_toys' text with mu_b the expectation above: bins 2q and 2q + 1
+ *                               share one Philox block, a bin with 0 < mu_b < 10 draws poisson_small, one with mu_b >= 10
+ *                               poisson_ptrs with its own bin number, mu_b = 0 gives 0.  The ensemble does not depend on how
+ *                               truths are grouped into calls: the toys of truth h are bit for bit those of an H = 1 call with
+ *                               toy_offset advanced by the toys before it.  All truths are validated before the store changes:
+ *                               one outside the anchor box, or with a rate outside [0, inf), refuses the whole call with
+ *                               BI_ERR_INVALID naming the truth ("... (truth 1): point is outside the anchor box") and the
+ *                               counts held so far stay usable.  The toys REPLACE the store's counts as T dense datasets
+ *                               ([T][Bp] doubles on the device, Bp = B rounded up to 512), with sum_b lgamma(n_b + 1) per
+ *                               dataset as bi_factored_set_counts computes it; where those T Bp 8 bytes cannot be allocated the
+ *                               call fails with BI_ERR_NOMEM and the old counts stay.  Scratch: H Bp doubles each for mu and
+ *                               exp(-mu): callers bound H per call.  Needs no counts.
+ *   bi_sourcewise_download_counts   out [B] = dataset t of whatever the store holds (uploaded counts or toys); t outside [0, T):
+ *                               BI_ERR_INVALID.
+ * All four: P = 0 / H = 0 returns BI_OK with no device work; no floating-point atomics; a repeated call is bitwise identical
+ * and a point's result does not depend on the batch it is evaluated in.  The limits are the model's own. */
+int bi_sourcewise_expected_counts(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out);
+int bi_eval_sourcewise_gof(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                           double* half_deviance, double* pearson, int32_t* status);
+int bi_sourcewise_generate_toys(bi_ctx* ctx, int64_t H, const double* z, const double* rate_scale, const int64_t* n_toys,
+                                uint64_t seed);
+int bi_sourcewise_download_counts(bi_ctx* ctx, int64_t t, double* out /*[B]*/);
 
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
