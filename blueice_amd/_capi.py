@@ -90,6 +90,13 @@ SIGNATURES = {
     'bi_sourcewise_download_counts': (C.c_int, [_p, _i64, _p]),
     'bi_fit_batched_factored': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                           _p, _p, _p, _p]),
+    'bi_sourcewise_set_real_counts': (C.c_int, [_p, _i64, _p]),
+    'bi_sourcewise_set_asimov_counts': (C.c_int, [_p, _i64, _p, _p]),
+    'bi_sourcewise_real_count_sets': (_i64, [_p]),
+    'bi_sourcewise_download_real_counts': (C.c_int, [_p, _i64, _p]),
+    'bi_eval_sourcewise_real': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_fit_batched_sourcewise_real': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
+                                                 _p, _p, _p, _p]),
     'bi_sample_stretch': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,
                                     _p, _p, _p, _p]),
     'bi_sample_stretch_gauss': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64, _i64,

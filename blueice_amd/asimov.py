@@ -21,6 +21,12 @@ DeviceLogLikelihood: priors, live time, efficiencies, status words) over a conte
 log-likelihood, and whose `fit_batched` is bi_fit_batched_real: the batched profile-fit engine (blueice_amd.profile) runs on
 its native loop unchanged.  `lf` itself is not touched: its data stay resident and usable.
 
+A prepared `SourceWiseBinnedLogLikelihood` is taken by the three module functions as well (`asimov(lf, **truth)`,
+`asimov_points(lf, points)`, `real_data(lf, counts)`): its context keeps a store of the same kind beside its counts
+(bi_sourcewise_set_real_counts / bi_sourcewise_set_asimov_counts, evaluated by bi_eval_sourcewise_real and fitted by
+bi_fit_batched_sourcewise_real), and the view works over it unchanged.  Of the bound names, `lf.asimov_points` is bound on that
+class; `lf.asimov` and `lf.real_data` stay refused there and name these functions.
+
 There is one store per likelihood: making a new view replaces it, and an older view then raises instead of reading another
 truth's data.  Beeston-Barlow (the expectation depends on the data), unbinned likelihoods, sums and re-parametrisations are
 refused; a LogLikelihoodSum OF views of different likelihoods works through the host combinator.
@@ -79,8 +85,8 @@ class _RealStoreContext:
 
 
 class AsimovLikelihood:
-    """A view of a BinnedLogLikelihood on real-valued data (see the module's docstring).  Made by `lf.asimov`,
-    `lf.asimov_points` and `lf.real_data`, not directly."""
+    """A view of a BinnedLogLikelihood, or of a prepared SourceWiseBinnedLogLikelihood, on real-valued data (see the module's
+    docstring).  Made by `asimov`, `asimov_points` and `real_data`, not directly."""
     # the parent's state a view shares (read through to the parent: a parameter added later is seen)
     _SHARED = ('shape_parameters', 'rate_parameters', 'config', 'pdf_base_config', 'source_name_list', 'source_list',
                'source_apply_efficiency', 'source_efficiency_names', 'source_allowed_negative', 'bin_shape', 'is_prepared',
@@ -141,9 +147,21 @@ for _name in inference.__all__:
     setattr(AsimovLikelihood, _name, getattr(inference, _name))
 
 
+def _binned_or_source_wise(lf, what):
+    """The gate of the factories: a `BinnedLogLikelihood` without Beeston-Barlow (`inference._binned_for_gof`), or a prepared
+    `SourceWiseBinnedLogLikelihood`, whose context keeps a real-valued store of its own under the same method names
+    (bi_sourcewise_set_real_counts ... bi_fit_batched_sourcewise_real).  `_binned_for_gof` itself keeps refusing that class."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if isinstance(lf, SourceWiseBinnedLogLikelihood):
+        if not lf.is_prepared:
+            raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+        return lf
+    return inference._binned_for_gof(lf, what)
+
+
 def _new_view(lf, what, fill):
     """The factories' common part: refuse what has no real-valued path, fill the store (fill(ctx) -> sets), hand out the view."""
-    inference._binned_for_gof(lf, what)
+    _binned_or_source_wise(lf, what)
     n_sets = fill(lf.ctx)
     lf._real_store_generation = generation = object()
     return AsimovLikelihood(lf, n_sets, generation)

@@ -16,6 +16,8 @@
 //                         one point of a source-wise model per item)                         bi_k_factored_curv.h
 //     tu_sourcewise_expect.hip, tu_sourcewise_gof.hip   k_sourcewise_expect (the per-bin expectation of a source-wise model, written
 //                         out), k_sourcewise_gof (its deviance + Pearson chi2 per item)      bi_k_sourcewise.h
+//     tu_sourcewise_real.hip   k_sourcewise_real (half-deviance + gradient sums of one point of a source-wise model against
+//                         real-valued counts per item)                                       bi_k_sourcewise_real.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -24,7 +26,7 @@
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
 // chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h,
-// bi_k_factored.h and (through it) bi_k_factored_curv.h, and bi_k_sourcewise.h (which shares gof_terms, bi_k_gof_terms.h, with bi_k_gof.h).
+// bi_k_factored.h and (through it) bi_k_factored_curv.h and bi_k_sourcewise_real.h, and bi_k_sourcewise.h (which shares gof_terms, bi_k_gof_terms.h, with bi_k_gof.h).
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 
@@ -121,6 +123,10 @@ constexpr int factored_curv_panels(int SC, int EM) { return SC / factored_curv_p
 // per item (two result slots).  BI_ERR_INVALID for an (SC, EM) without a variant, as launch_morph_factored
 int launch_sourcewise_expect(bi_ctx* c, int SC, int EM, bool per_source, const SourcewiseExpectArgs& a, int64_t n_items, bool nt);
 int launch_sourcewise_gof(bi_ctx* c, int SC, int EM, const FactoredArgs& a, dim3 grid, bool nt);
+// k_sourcewise_real<SC, EM, GRAD, NT>: the half-deviance (and the gradient's partial sums) of one point of a source-wise model
+// against the real-valued dataset a.counts + a.item_cnt[item] per item; classes and result slots (factored_slots) as
+// launch_morph_factored
+int launch_sourcewise_real(bi_ctx* c, int SC, int EM, bool grad, const FactoredArgs& a, dim3 grid, bool nt);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

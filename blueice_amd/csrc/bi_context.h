@@ -155,6 +155,10 @@ struct bi_ctx {
         int64_t T = 0;
         DevBuf counts;                               // [T][Bp], zero behind B
         std::vector<double> h_lgsum;                 // [T] sum_b lgamma(n_b + 1)
+        // real-valued datasets (bi_sourcewise_set_real_counts / bi_sourcewise_set_asimov_counts; bi_sourcewise_real.h): a store
+        // of its own beside `counts`, read by bi_eval_sourcewise_real / bi_fit_batched_sourcewise_real only
+        int64_t real_T = 0;
+        DevBuf real_counts;                          // [real_T][Bp], zero behind B
         int n_rows_point = 0;                        // rows one evaluation reads: sum_s 2^e_s
         int max_own = 0;                             // largest e_s
     } fac;

@@ -400,6 +400,8 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     dev_free(m.counts);
     m.T = 0;
     m.h_lgsum.clear();
+    dev_free(m.real_counts);    // (rows of the previous model's padded length)
+    m.real_T = 0;
     m.d = d; m.S = S; m.B = B;
     m.Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
     m.grid.assign((size_t)d, {});

@@ -14,6 +14,7 @@
 //   bi_fit_batched_gauss  ... plus Gaussian constraint terms on the optimiser variables: f = -(ll + p)
 //   bi_fit_batched_real   (bi_real.h) ... against a real-valued dataset: f = half_deviance - p
 //   bi_fit_batched_factored   (bi_factored.h) ... with a source-wise model's likelihood (bi_eval_factored) as the objective
+//   bi_fit_batched_sourcewise_real   (bi_sourcewise_real.h) ... a source-wise model against a real-valued dataset of its store
 #pragma once
 
 #include <new>
@@ -373,8 +374,9 @@ int minimize_batched(bi_objective_fn fun, void* user, int64_t P, int F, const do
 }
 
 // which evaluation the objective stands on: the grid model's likelihood (bi_eval_grad), the real-valued store's half-deviance
-// (bi_eval_real, bi_real.h: ll stands for -half_deviance) or the source-wise model's likelihood (bi_eval_factored, bi_factored.h)
-enum FitEval { kFitLikelihood = 0, kFitReal = 1, kFitFactored = 2 };
+// (bi_eval_real, bi_real.h: ll stands for -half_deviance), the source-wise model's likelihood (bi_eval_factored, bi_factored.h)
+// or its half-deviance against its own real-valued store (bi_eval_sourcewise_real, bi_sourcewise_real.h)
+enum FitEval { kFitLikelihood = 0, kFitReal = 1, kFitFactored = 2, kFitSourcewiseReal = 3 };
 
 // the device likelihood as the objective: f = -(ll + p), g = -d (ll + p) / d x, p the Gaussian constraint terms (none: p = 0)
 struct DeviceObjective {
@@ -405,10 +407,11 @@ int device_objective(void* user, int64_t n, int F, const double* x, const int64_
     m.z_dev = o->z.data(); m.rs_dev = o->sc.data(); m.ds_dev = o->ds.data();
     for (int64_t i = 0; i < n; ++i) varmap_write_point(m, i, rows[i], [&](int j) { return x[i * F + j]; });
     o->evaluations += n;
-    const auto eval = o->eval == kFitReal ? bi_eval_real : o->eval == kFitFactored ? bi_eval_factored : bi_eval_grad;
+    const auto eval = o->eval == kFitReal ? bi_eval_real : o->eval == kFitFactored ? bi_eval_factored
+                      : o->eval == kFitSourcewiseReal ? bi_eval_sourcewise_real : bi_eval_grad;
     const int rc = eval(c, n, d ? o->z.data() : nullptr, o->sc.data(), m.dataset ? o->ds.data() : nullptr, o->ll.data(), o->grad.data(), o->st.data());
     if (rc) return rc;
-    if (o->eval == kFitReal) {
+    if (o->eval == kFitReal || o->eval == kFitSourcewiseReal) {
         for (double& v : o->ll) v = -v;
         for (double& v : o->grad) v = -v;
     }
@@ -481,14 +484,15 @@ bool gauss_terms_empty(int F, const double* sigma, const double* konst) {
 }
 
 // bi_fit_batched (no terms: the three prior arrays NULL), bi_fit_batched_gauss and, by `eval`, bi_fit_batched_real (bi_real.h:
-// against the real-valued store) and bi_fit_batched_factored (bi_factored.h: a source-wise model; its entry point has checked
-// that model and its counts).  Those two's terms are optional and their datasets their own store's: both are checked here,
+// against the real-valued store), bi_fit_batched_factored (bi_factored.h: a source-wise model; its entry point has checked
+// that model and its counts) and bi_fit_batched_sourcewise_real (bi_sourcewise_real.h: that model against its real-valued
+// store, likewise checked).  Those three's terms are optional and their datasets their own store's: both are checked here,
 // behind the checks all share, so that a call with several defects is refused for the first of them in this order
 int fit_batched(bi_ctx* c, const char* who, FitEval eval, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                 const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo, const double* hi,
                 const int32_t* n_kinks, const double* kinks, double gtol, int max_iter, const double* prior_mean, const double* prior_sigma,
                 const double* prior_const, double* x_out, double* f_out, int32_t* flags_out, int64_t* counters) {
-    const bool real = eval == kFitReal, factored = eval == kFitFactored;
+    const bool real = eval == kFitReal, sw_real = eval == kFitSourcewiseReal, factored = eval == kFitFactored || sw_real;
     // (check_ready holds the NULL-context test: nothing of c is read before it; the source-wise entry point has made its own)
     int rc = factored ? (c ? BI_OK : BI_ERR_INVALID) : check_ready(c, !real);
     if (rc) return rc;
@@ -503,7 +507,8 @@ int fit_batched(bi_ctx* c, const char* who, FitEval eval, int64_t P, int F, cons
         if (gauss_terms_empty(F, prior_sigma, prior_const)) prior_mean = prior_sigma = nullptr;
     }
     if (real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->real_T))) return rc;
-    if (factored && (rc = check_entry_datasets(c, who, "problem", P, dataset, c->fac.T))) return rc;
+    if (sw_real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->fac.real_T))) return rc;
+    if (factored && !sw_real && (rc = check_entry_datasets(c, who, "problem", P, dataset, c->fac.T))) return rc;
     if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
     DeviceObjective o{};
     o.c = c; o.eval = eval; o.d = d; o.S = S;

@@ -1082,7 +1082,8 @@ def asimov_test_statistic(lf, target, hypotheses, truth=None, fit_options=None, 
     ~1e-10 max(1, D), not to 1e-10 of a log-likelihood.  `lf`'s own data are not touched."""
     hypotheses = np.atleast_1d(np.asarray(hypotheses, dtype=float))
     truth, _ = _asimov_truth(lf, target, truth)
-    view = lf.asimov(livetime_days=livetime_days, **truth)
+    from .asimov import asimov              # (the module function: it takes a source-wise model too, whose bound name refuses)
+    view = asimov(lf, livetime_days=livetime_days, **truth)
     free, cond = _asimov_fits(view, target, hypotheses, truth, fit_options, livetime_days, fixed)
     return 2.0 * (free - cond)
 
@@ -1096,7 +1097,8 @@ def expected_upper_limit(lf, target, bound, confidence_level=0.9, n_sigma=(-2, -
     crossing above the truth and returns the truth's value of the target.  bound: the far end of the search, as
     `one_parameter_interval`."""
     truth, at_truth = _asimov_truth(lf, target, truth)
-    view = lf.asimov(livetime_days=livetime_days, **truth)
+    from .asimov import asimov              # (the module function: it takes a source-wise model too, whose bound name refuses)
+    view = asimov(lf, livetime_days=livetime_days, **truth)
     more = dict(fixed)
     if livetime_days is not None:
         more['livetime_days'] = livetime_days

@@ -7,7 +7,9 @@
     lf.value_gradient_hessian, lf.values_gradients_hessians, lf.bestfit_minuit, blueice_amd.inference.hesse(lf, values),
     lf.fisher_information_points, lf.expected_covariance, lf.expected_errors,
     lf.simulate_toys_points, lf.toy_test_statistics, lf.neyman_thresholds, and as functions of blueice_amd.inference:
-    bestfit_toys(lf), toy_mc_fits(lf, n), gof_statistics(lf, ...), goodness_of_fit(lf, ...), expected_counts_points(lf, points)
+    bestfit_toys(lf), toy_mc_fits(lf, n), gof_statistics(lf, ...), goodness_of_fit(lf, ...), expected_counts_points(lf, points),
+    lf.asimov_points, lf.asimov_test_statistic, lf.expected_discovery_significance, blueice_amd.asimov.asimov(lf, **truth),
+    blueice_amd.asimov.real_data(lf, counts), blueice_amd.inference.expected_upper_limit(lf, target, bound)
 
 `BinnedLogLikelihood` morphs over ONE tensor-product grid of all shape parameters: prod n_i anchor models in HBM and S 2^d
 rows per evaluation, which caps the number of shape parameters at a handful.  Here every source morphs over the parameters
@@ -29,9 +31,17 @@ lf.bestfit_toys, lf.toy_mc_fits, lf.gof_statistics, lf.goodness_of_fit, lf.expec
 refused and name the spelling that works; `blueice_amd.inference.expected_counts(lf, **params)` stays refused as well (use the
 `_points` form with one-row arrays).
 
+Asimov and real-valued data live in a store of their own beside the counts (bi_sourcewise_set_real_counts,
+bi_sourcewise_set_asimov_counts), evaluated by bi_eval_sourcewise_real and fitted by bi_fit_batched_sourcewise_real: the factories
+of blueice_amd.asimov take a prepared source-wise model and return the `AsimovLikelihood` view they return for a
+`BinnedLogLikelihood`, and `asimov_test_statistic`, `expected_upper_limit` and `expected_discovery_significance` of
+blueice_amd.inference run over it -- one profile scan where an ensemble of toys per hypothesis would be needed otherwise.  No
+observed data are needed for them.  The bound lf.asimov, lf.real_data and lf.expected_upper_limit stay refused and name these
+spellings; lf.asimov_points, lf.asimov_test_statistic and lf.expected_discovery_significance are bound.
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, eval_toys*, Asimov and real-valued data, grids, coarse views (and `binning=` in the goodness-of-fit calls) and
+full_output calls, eval_toys*, grids, coarse views (and `binning=` in the goodness-of-fit calls), Hessians on an Asimov view and
 the ensemble sampler.
 """
 from collections import OrderedDict
@@ -62,7 +72,8 @@ class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
     eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, generate_toys_points, download_counts, set_param / get_param,
-    fit_batched, interpolate('mus', z), T -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
+    fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
+    real_count_sets, download_real_counts, eval_real, fit_batched_real) -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
     meaning here and is an AttributeError."""
 
     def __init__(self, device=None):
@@ -244,6 +255,66 @@ class SourceWiseContext:
                                                     int(max_iter), ptr(mean), ptr(sigma), ptr(const), ptr(x), ptr(f), ptr(flags), ptr(counters)))
         return 0
 
+    # -- real-valued datasets: a store of its own beside the counts (bi_sourcewise_set_real_counts ... bi_fit_batched_sourcewise_real),
+    #    under the names DeviceContext uses, so that blueice_amd.asimov's context proxy works over either --
+    def set_real_counts(self, counts):
+        """counts: [*bins] (one set) or [T, *bins], every count finite and >= 0 (ValueError otherwise); None drops the store."""
+        dev = self._dev
+        if counts is None:
+            dev._check(dev._lib.bi_sourcewise_set_real_counts(dev._h, 0, None))
+            return
+        c = as_f64(counts)
+        if c.size == 0 or c.size % self.B:
+            raise ValueError("counts size %d is not a positive multiple of B=%d" % (c.size, self.B))
+        T = c.size // self.B
+        dev._check(dev._lib.bi_sourcewise_set_real_counts(dev._h, T, ptr(c.reshape(T, self.B))))
+
+    def set_asimov_counts(self, z, rate_scale=None):
+        """H Asimov datasets made on the device (bi_sourcewise_set_asimov_counts): set h holds the expectation at truth (z[h],
+        rate_scale[h]), bit for bit the row of `expected_counts`.  ValueError names a truth outside the anchor box, with
+        unphysical rates or with an expectation that is not finite; the previous store then stays.  -> H"""
+        dev = self._dev
+        H, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        dev._check(dev._lib.bi_sourcewise_set_asimov_counts(dev._h, H, ptr(z), ptr(rate_scale)))
+        return H
+
+    @property
+    def real_count_sets(self):
+        return int(self._dev._lib.bi_sourcewise_real_count_sets(self._dev._h))
+
+    def download_real_counts(self, t=0):
+        dev = self._dev
+        out = np.empty(self.B, dtype=np.float64)
+        dev._check(dev._lib.bi_sourcewise_download_real_counts(dev._h, int(t), ptr(out)))
+        return out
+
+    def eval_real(self, z, rate_scale=None, dataset=None, gradient=True):
+        """Half-deviance against the real-valued store (bi_eval_sourcewise_real) -> (half_deviance [P], d/dz [P, d],
+        d/drate_scale [P, S], status [P]); gradient=False: the two slope arrays are None.  +inf outside the box / for unphysical
+        rates / where a filled bin expects nothing: DeviceContext.eval_real's shapes and meaning."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        half = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, self.d + self.S), dtype=np.float64) if gradient else None
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_real(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(half), ptr(grad), ptr(status)))
+        if not gradient:
+            return half, None, None, status
+        return half, grad[:, :self.d], grad[:, self.d:], status
+
+    def fit_batched_real(self, P, F, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks, gtol, max_iter, x, f, flags, counters,
+                         priors=None):
+        """bi_fit_batched_sourcewise_real: `fit_batched` with f = half_deviance - p against the real-valued store."""
+        dev = self._dev
+        mean = sigma = const = None
+        if priors is not None:
+            mean, sigma, const = dev._gauss_terms(priors, int(F), int(P))
+        dev._check(dev._lib.bi_fit_batched_sourcewise_real(dev._h, int(P), int(F), ptr(kind), ptr(index), ptr(z0) if self.d else None,
+                                                           ptr(scale0), ptr(unit), ptr(dataset), ptr(x0), ptr(lo), ptr(hi), ptr(n_kinks),
+                                                           ptr(kinks), float(gtol), int(max_iter), ptr(mean), ptr(sigma), ptr(const), ptr(x),
+                                                           ptr(f), ptr(flags), ptr(counters)))
+        return 0
+
     def interpolate(self, which, z):
         """'mus': the interpolated rates [S] at z [d], from the host copy of the anchors' rates"""
         if which != 'mus':
@@ -275,6 +346,9 @@ _REFUSED_SPELLINGS = {
     'goodness_of_fit': "blueice_amd.inference.goodness_of_fit(lf, n_toys=...)",
     'expected_counts': "blueice_amd.inference.expected_counts_points(lf, points, per_source=) with one-row arrays in `points`",
     'expected_counts_points': "blueice_amd.inference.expected_counts_points(lf, points, per_source=)",
+    'asimov': "blueice_amd.asimov.asimov(lf, **truth)",
+    'real_data': "blueice_amd.asimov.real_data(lf, counts)",
+    'expected_upper_limit': "blueice_amd.inference.expected_upper_limit(lf, target, bound)",
 }
 
 
@@ -284,8 +358,8 @@ def _refused(name):
             raise NotImplementedError("lf.%s is not bound on a source-wise model (SourceWiseBinnedLogLikelihood); call %s"
                                       % (name, _REFUSED_SPELLINGS[name]))
         raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
-                                  "Hessian, expected information, the fit, scan and interval layers, toys at truth points and "
-                                  "goodness of fit are" % name)
+                                  "Hessian, expected information, the fit, scan and interval layers, toys at truth points, "
+                                  "goodness of fit and Asimov data are" % name)
     method.__name__ = name
     return method
 
@@ -296,9 +370,9 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
     _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'expected_counts',
                 'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
                 'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
-                'asimov_test_statistic', 'expected_upper_limit', 'expected_discovery_significance',
+                'expected_upper_limit',
                 'fisher_information', 'hesse', 'sample_posterior', 'bestfit_emcee',
-                'grid_scan', 'asimov', 'asimov_points', 'real_data', 'simulate_toys', 'eval_toys', 'eval_toys_points',
+                'grid_scan', 'asimov', 'real_data', 'simulate_toys', 'eval_toys', 'eval_toys_points',
                 'ps_interpolator', 'n_model_events_interpolator')
 
     supports_gradient = True

@@ -1,6 +1,6 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--measure | --measure-toys [--rounds 31]]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--measure | --measure-toys | --measure-asimov [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
 grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
@@ -17,6 +17,12 @@ evaluation -- and the native fit loop floats all twelve parameters.
 (6) neyman_thresholds: the test statistic's critical values from toys at a few hypotheses of the signal's rate multiplier,
     handed to one_parameter_interval in place of Wilks' chi-square.
 
+--asimov prints, instead of (2) - (6), the expected 90 % upper limit on the signal's rate multiplier without any data: the
+-1 sigma ... +2 sigma band from the background-only Asimov dataset (blueice_amd.inference.expected_upper_limit: one profile
+search per band edge on the view of blueice_amd.asimov, bi_fit_batched_sourcewise_real), and beside it the same band from
+--toys background-only toys drawn on the device, every toy profiled at a ladder of hypotheses in lock-step and its own limit
+read off where its test statistic crosses Wilks' threshold, then the toy-calibrated one of neyman_thresholds; wall times of all.
+
 --measure times the C ABI instead, at a shape BOTH routes can hold: d = 4, S = 4, one own axis per source, 5 anchors, 100^3
 bins, dense data, 64 points per call -- bi_eval_factored with its gradient (8 rows per point) against bi_eval_grad on the
 expanded 5^4 grid (64 rows per point; 20 GB of templates), alternated calls, medians with quartiles, and the kernel's bytes
@@ -28,6 +34,10 @@ there; and both on a panelled class (8 sources x 2 own axes of the same 4, four 
 --measure-toys times, at the same source-wise shape (no expanded grid is built), bi_eval_sourcewise_gof against bi_eval_factored
 values-only, bi_sourcewise_expected_counts against the bytes it must write, and bi_sourcewise_generate_toys for 64 toys against
 numpy.random.Generator.poisson on the same expectation on the host plus the upload through bi_factored_set_counts.
+
+--measure-asimov times, at the same source-wise shape, bi_eval_sourcewise_real with and without its gradient against
+bi_eval_factored with and without its gradient and against bi_eval_sourcewise_gof, all on the same rows (the same counts in the
+real-valued store and in the ordinary one), at 64 points per call and at one, and the kernels alone by device events.
 """
 import argparse
 import time
@@ -39,6 +49,8 @@ ap.add_argument('--bins', type=int, default=20, help='bins per analysis axis (tw
 ap.add_argument('--scan', type=int, default=33, help='hypotheses of the profile scan')
 ap.add_argument('--measure', action='store_true', help='time bi_eval_factored against bi_eval_grad on the expanded grid')
 ap.add_argument('--measure-toys', action='store_true', help='time the goodness-of-fit, expected-counts and toy-generator calls')
+ap.add_argument('--measure-asimov', action='store_true', help='time bi_eval_sourcewise_real against bi_eval_factored on the same rows')
+ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
 ap.add_argument('--rounds', type=int, default=31)
 ap.add_argument('--measure-bins', type=int, default=100, help='bins per axis (three axes) of the measured shape')
@@ -234,8 +246,126 @@ def measure_toys():
     fac.close()
 
 
+def measure_asimov():
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B, P = 5, args.measure_bins ** 3, 64
+    Bp = (B + 511) // 512 * 512
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    z = rng.uniform(-1.9, 1.9, (P, d))
+    r = rng.uniform(0.8, 1.2, (P, S))
+    mid = n_a // 2
+    counts = rng.poisson(sum(mus[s, mid] * rows[s, mid] for s in range(S))).astype(float)
+    fac.set_counts(counts)                        # the same rows in both stores
+    fac.set_real_counts(counts)
+    print('source-wise model: %d rows, %.2f GB resident (it stays in the 256 MB Infinity Cache: every figure below is cache-assisted)'
+          % (S * n_a, S * n_a * Bp * 8 / 1e9), flush=True)
+    half, gz, gs, _ = fac.eval_real(z, r)
+    half_gof, _, _ = fac.eval_gof(z, r)
+    ll, lz, ls, _ = fac.eval_grad(z, r)
+    print('agreement over %d points: max |half-deviance - that of bi_eval_sourcewise_gof| / it %.2g; max |gradient + d ll| %.2g of the largest entry'
+          % (P, np.max(np.abs(half - half_gof) / half_gof), max(np.max(np.abs(gz + lz)), np.max(np.abs(gs + ls))) /
+             max(np.max(np.abs(lz)), np.max(np.abs(ls)))))
+    for n in (P, 1):
+        zn, rn = z[:n], r[:n]
+        alternate([('bi_eval_sourcewise_real + gradient', lambda: fac.eval_real(zn, rn)),
+                   ('bi_eval_factored + gradient', lambda: fac.eval_grad(zn, rn)),
+                   ('bi_eval_sourcewise_real, values', lambda: fac.eval_real(zn, rn, gradient=False)),
+                   ('bi_eval_factored, values', lambda: fac.eval(zn, rn)),
+                   ('bi_eval_sourcewise_gof', lambda: fac.eval_gof(zn, rn))], n)
+    # the kernels alone, from device events around the launches, in a pass of their own
+    dev = fac._dev
+    gb = (2 * S + 1) * Bp * 8 * P / 1e9
+    for name, call in (('k_sourcewise_real, gradient', lambda: fac.eval_real(z, r)), ('k_morph_factored, gradient', lambda: fac.eval_grad(z, r)),
+                       ('k_sourcewise_real, values', lambda: fac.eval_real(z, r, gradient=False)), ('k_morph_factored, values', lambda: fac.eval(z, r)),
+                       ('k_sourcewise_gof', lambda: fac.eval_gof(z, r))):
+        dev.profile(True)
+        ks = []
+        for _ in range(args.rounds):
+            call()
+            ks.append(dev.profile_read()[1] * 1e-3)
+        dev.profile(False)
+        print('%-28s kernels %s per call of %d points; %.2f GB read -> %.2f TB/s' % (name, quartiles(ks), P, gb, gb / np.median(ks) / 1e3), flush=True)
+    print('(bytes: every kernel reads 2 S rows and the counts per point)')
+    print('not measured: the other kernel classes (more sources, more own axes, the one-bin-in-flight classes), shapes beyond the '
+          'Infinity Cache, several real-valued datasets per call')
+    fac.close()
+
+
+def asimov_band():
+    from scipy import stats
+    from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood, inference
+    from blueice_amd.synthetic import many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins))
+    lf = SourceWiseBinnedLogLikelihood(conf)
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    lf.prepare()
+    target, sigmas = 's0_rate_multiplier', (-1, 0, 1, 2)
+    t0 = time.perf_counter()
+    limits = inference.expected_upper_limit(lf, target, 3.0, confidence_level=0.9, n_sigma=sigmas)
+    dt_asimov = time.perf_counter() - t0
+    print('expected 90 %% upper limit on %s, background only, %d x %d bins, 11 nuisances profiled' % (target, args.bins, args.bins))
+    print('    Asimov dataset (expected_upper_limit, no data): ' + ', '.join('%+d sigma %.4f' % (n, limits[n]) for n in sigmas)
+          + '   %.3f s' % dt_asimov, flush=True)
+    # the same band from toys: background-only toys, each profiled at a ladder of hypotheses, its limit where t crosses the threshold
+    N, hyps = args.toys, np.linspace(0.0, 1.6 * limits[2], 14)[1:]
+    t0 = time.perf_counter()
+    lf.simulate_toys_points({target: np.array([0.0])}, [N], seed=4)
+    best, ll_free = lf.bestfit_batched(datasets=np.arange(N))
+    _, ll_cond = lf.bestfit_batched(points={target: np.repeat(hyps, N)}, datasets=np.tile(np.arange(N), len(hyps)))
+    t = 2.0 * (ll_free[None, :] - ll_cond.reshape(len(hyps), N))
+    t[best[target][None, :] >= hyps[:, None]] = 0.0                 # one-sided: no exclusion below the best fit
+
+    def band_of(crit):
+        """every toy's limit: where its t first crosses crit [H] along the ladder -> the band's quantiles, toys without a crossing"""
+        per_toy = np.full(N, np.inf)
+        for j in range(N):
+            above = np.flatnonzero(t[:, j] >= crit)
+            if len(above) and above[0] > 0:
+                i = above[0]
+                lo, hi = t[i - 1, j] - crit[i - 1], t[i, j] - crit[i]
+                per_toy[j] = hyps[i - 1] - lo * (hyps[i] - hyps[i - 1]) / (hi - lo)
+            elif len(above):
+                per_toy[j] = hyps[0]
+        return np.quantile(per_toy, stats.norm.cdf(sigmas)), int(np.sum(~np.isfinite(per_toy)))
+
+    wilks, beyond = band_of(np.full(len(hyps), stats.norm.ppf(0.9) ** 2))
+    dt_toys = time.perf_counter() - t0
+    print('    %d toys x %d hypotheses in lock-step, Wilks\' threshold:  ' % (N, len(hyps)) + ', '.join('%+d sigma %.4f' % (n, v) for n, v in zip(sigmas, wilks))
+          + '   %.3f s   (%d toys with a limit beyond the ladder)' % (dt_toys, beyond), flush=True)
+    # ... and with the threshold itself from toys at every hypothesis of the ladder (neyman_thresholds): no asymptotics left
+    n_per = max(N // 5, 20)
+    t0 = time.perf_counter()
+    table = lf.neyman_thresholds(target, hyps, n_per, kind='upper', seed=2)
+    neyman, beyond = band_of(table.critical_values(0.9))
+    dt_neyman = time.perf_counter() - t0
+    print('    ... thresholds from %d toys at each hypothesis (neyman_thresholds): ' % n_per + ', '.join('%+d sigma %.4f' % (n, v) for n, v in zip(sigmas, neyman))
+          + '   + %.3f s   (%d beyond the ladder)' % (dt_neyman, beyond))
+    print('    median expected limit: Asimov %.4f in %.3f s; toys %.4f (Wilks) in %.3f s, %.4f (toy-calibrated) in %.3f s'
+          % (limits[0], dt_asimov, wilks[1], dt_toys, neyman[1], dt_toys + dt_neyman))
+
+
 if args.measure:
     measure()
+    raise SystemExit(0)
+if args.measure_asimov:
+    measure_asimov()
+    raise SystemExit(0)
+if args.asimov:
+    asimov_band()
     raise SystemExit(0)
 if args.measure_toys:
     measure_toys()

@@ -643,6 +643,52 @@ int bi_sourcewise_generate_toys(bi_ctx* ctx, int64_t H, const double* z, const d
                                 uint64_t seed);
 int bi_sourcewise_download_counts(bi_ctx* ctx, int64_t t, double* out /*[B]*/);
 
+/* ... and real-valued datasets of a source-wise model: Asimov data (n_b = mu_b(truth)) and weighted histograms, the layer that
+ * bi_set_real_counts ... bi_fit_batched_real are for the grid model.  The store is [T][Bp] doubles (Bp = B rounded up to 512,
+ * zero behind B) inside the source-wise model BESIDE its ordinary counts, which stay resident and keep scipy's integer
+ * semantics; nothing else reads it, and none of these calls needs ordinary counts.  bi_factored_begin and bi_destroy release
+ * it.  A new store replaces the previous one; on ANY refusal the previous one stays as it was.
+ *   bi_sourcewise_set_real_counts      counts [T][B], every one finite and >= 0: otherwise BI_ERR_INVALID naming dataset and
+ *                                  bin.  T = 0 or counts = NULL drops the store.
+ *   bi_sourcewise_set_asimov_counts    H >= 1 sets, set h = mu_b at truth (z[h], rate_scale[h]) (rate_scale NULL: ones), written
+ *                                  on the device straight into the store by the kernel of bi_sourcewise_expected_counts: bit
+ *                                  for bit the row that call returns with per_source = 0.  All truths are screened (box on all
+ *                                  d axes, then the rates) before the store changes: a refused call returns BI_ERR_INVALID
+ *                                  naming the truth ("... (truth 1): point is outside the anchor box"), as does a truth whose
+ *                                  expectation is not finite in some bin.  BI_ERR_NOMEM where the H Bp 8 bytes cannot be
+ *                                  allocated; the old store stays.
+ *   bi_sourcewise_real_count_sets      the number of sets in the store (0: none)
+ *   bi_sourcewise_download_real_counts out [B] = set t; t outside the store: BI_ERR_INVALID; no store: BI_ERR_STATE
+ *   bi_eval_sourcewise_real        bi_eval_real's contract on this model: per point p, against set dataset[p] (NULL: set 0),
+ *                                      half_deviance [P]   sum_b  (mu_b - n_b) - n_b log(mu_b / n_b)         (n_b = 0: mu_b)
+ *                                      grad [P][d + S]     sum_b  d_q mu_b (1 - n_b / mu_b)                  (n_b = 0: d_q mu_b)
+ *                                  grad may be NULL; it is formed from per-source sums by bi_eval_factored's chain rule, in its
+ *                                  fixed order.  There is no integer test on n_b.  n_b > 0 where mu_b = 0 gives +inf, an
+ *                                  expectation that comes out negative or nan gives nan; the gradient is nan wherever the value
+ *                                  is not finite.  Box and rate rejections give +inf with bi_eval_factored's status bits
+ *                                  (status [P] or NULL); a dataset index outside the store is BI_ERR_INVALID for the whole
+ *                                  call, no store at all BI_ERR_STATE.  mu_b is the chain stated above to the bit, so at the
+ *                                  truth of an Asimov set mu_b == n_b and the value and every gradient entry are exactly 0.0.
+ *                                  No 16-column limit: the limits are the model's own (d <= 32, S <= 8, e_s <= 3).  The value
+ *                                  of a call without the gradient has the bits of the value of the call with it; P = 0 returns
+ *                                  BI_OK with no device work; no floating-point atomics; a repeated call is bitwise identical
+ *                                  and a point's result does not depend on the batch it is evaluated in.
+ *   bi_fit_batched_sourcewise_real bi_fit_batched_real's signature and contract with this evaluation as the objective:
+ *                                  f = half_deviance - p, `dataset` [P] or NULL indexes the real-valued store (outside it:
+ *                                  BI_ERR_INVALID), and prior_mean / prior_sigma / prior_const may all be NULL (no terms). */
+int bi_sourcewise_set_real_counts(bi_ctx* ctx, int64_t T, const double* counts /*[T][B]*/);
+int bi_sourcewise_set_asimov_counts(bi_ctx* ctx, int64_t H, const double* z, const double* rate_scale);
+int64_t bi_sourcewise_real_count_sets(bi_ctx* ctx);
+int bi_sourcewise_download_real_counts(bi_ctx* ctx, int64_t t, double* out /*[B]*/);
+int bi_eval_sourcewise_real(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                            double* half_deviance, double* grad, int32_t* status);
+int bi_fit_batched_sourcewise_real(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, const int32_t* var_index,
+                                   const double* z0, const double* scale0, const double* unit, const int64_t* dataset,
+                                   const double* x0, const double* lo, const double* hi, const int32_t* n_kinks,
+                                   const double* kinks, double gtol, int max_iter, const double* prior_mean,
+                                   const double* prior_sigma, const double* prior_const, double* x_out, double* f_out,
+                                   int32_t* flags_out, int64_t* counters);
+
 /* The ensemble sampler: n_steps steps of Goodman & Weare's affine-invariant stretch move for E independent ensembles of W
  * walkers over F variables, the context's log likelihood as the log density -- what the reference hands to emcee as
  * n_walkers x n_steps scalar likelihood calls (bestfit_emcee, blueice/inference.py:254-321).  The variables are described as
