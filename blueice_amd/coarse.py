@@ -9,7 +9,9 @@ the corner rows of a point are streamed once and summed as they arrive, the fine
 derivatives of every cell in the user's parameters, summed over the cells in the same single pass
 (bi_expected_coarse_jacobian); `expected_coarse_band` turns a covariance of the parameters (`hesse`, `expected_covariance`)
 into the uncertainty band of a coarse view and the impact of every parameter on it, and `coarse_information` gives the Fisher
-information of the likelihood at that binning, cell by cell.  Plain binned likelihoods only.
+information of the likelihood at that binning, cell by cell.  Plain binned likelihoods; a source-wise model
+(`SourceWiseBinnedLogLikelihood`) has the binning, the expectation and the counts per cell (bi_sourcewise_expected_coarse,
+bi_sourcewise_coarse_counts) and with them the rebinned goodness of fit, not the derivatives.
 
     box = CoarseBinning(lf, keep=['cs1'], rebin={'cs1': 4}, ranges={'cs2': (2.0, 3.5)})
     mu = lf.expected_coarse(box, per_source=True, **best)            # [S, n_cs1 / 4]
@@ -46,6 +48,22 @@ def _binned_for_gof(lf, what, prepared=True):
     return lf
 
 
+def _binned_for_coarse(lf, what, prepared=True, derivatives=False):
+    """The gate of the coarse views proper (the binning, the expectation and the counts per cell): what `_binned_for_gof` lets
+    through, or a `SourceWiseBinnedLogLikelihood`, whose context has the three calls under the same names
+    (bi_sourcewise_set_coarse_binning, bi_sourcewise_expected_coarse, bi_sourcewise_coarse_counts).  derivatives=True: the call
+    needs the per-cell derivatives, which a source-wise model does not have.  `_binned_for_gof` itself keeps refusing the class."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if not isinstance(lf, SourceWiseBinnedLogLikelihood):
+        return _binned_for_gof(lf, what, prepared)
+    if derivatives:
+        raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): the derivatives of "
+                                  "its coarse views are not summed on the device" % what)
+    if prepared and not lf.is_prepared:
+        raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
+    return lf
+
+
 def _edge_index(name, fine, value):
     """-> the index of the fine edge `value` coincides with; ValueError if there is none"""
     value = float(value)
@@ -58,7 +76,7 @@ def _edge_index(name, fine, value):
 
 
 class CoarseBinning:
-    """A coarse binning of the analysis space of a plain `BinnedLogLikelihood`.
+    """A coarse binning of the analysis space of a plain `BinnedLogLikelihood` or a `SourceWiseBinnedLogLikelihood`.
 
     keep    names of the analysis dimensions that stay as axes of the result, in the order of the analysis space; the others
             are summed over.  Default: all.
@@ -73,7 +91,7 @@ class CoarseBinning:
     `bin_map()` is the executable specification: fine flat index -> coarse flat index, both in C order."""
 
     def __init__(self, lf, keep=None, rebin=None, ranges=None):
-        _binned_for_gof(lf, 'CoarseBinning', prepared=False)
+        _binned_for_coarse(lf, 'CoarseBinning', prepared=False)
         space = [(str(n), np.asarray(e, dtype=float)) for n, e in lf.base_model.config['analysis_space']]
         names = [n for n, _ in space]
         keep = names if keep is None else ([keep] if isinstance(keep, str) else list(keep))
@@ -132,10 +150,11 @@ class CoarseBinning:
             out = out | left_out.reshape(shape)
         return np.where(out, -1, cell).astype(np.int32).ravel()
 
-    def attach(self, lf, what):
-        """Refuse what has no coarse view, then make this the coarse binning of lf's device context -- a no-op while the context
-        still holds it (a new model releases it).  ValueError for a likelihood with another analysis space."""
-        _binned_for_gof(lf, what)
+    def attach(self, lf, what, derivatives=False):
+        """Refuse what has no coarse view (derivatives=True: or not its derivatives), then make this the coarse binning of lf's
+        device context -- a no-op while the context still holds it (a new model releases it).  ValueError for a likelihood with
+        another analysis space."""
+        _binned_for_coarse(lf, what, derivatives=derivatives)
         space = lf.base_model.config['analysis_space']
         if [str(n) for n, _ in space] != self.fine_dims or tuple(lf.bin_shape) != self.fine_shape or \
                 not all(np.array_equal(np.asarray(e, dtype=float), mine) for (_, e), mine in zip(space, self.fine_edges)):
@@ -145,11 +164,11 @@ class CoarseBinning:
         return lf
 
 
-def _prepared(lf, binning, what):
+def _prepared(lf, binning, what, derivatives=False):
     if not isinstance(binning, CoarseBinning):
-        _binned_for_gof(lf, what)                   # (the likelihood's own refusal comes first)
+        _binned_for_coarse(lf, what, derivatives=derivatives)                   # (the likelihood's own refusal comes first)
         raise TypeError("%s needs a CoarseBinning, not a %s" % (what, type(binning).__name__))
-    return binning.attach(lf, what)
+    return binning.attach(lf, what, derivatives=derivatives)
 
 
 def expected_coarse_points(lf, binning, points, per_source=False, livetime_days=None):
@@ -168,6 +187,10 @@ def expected_coarse(lf, binning, per_source=False, livetime_days=None, **params)
     """The expected events per cell of `binning` at one parameter point -> array of `binning.shape`, or [S, *binning.shape]
     with per_source: a projection of the fitted model with its components.  As `expected_coarse_points`, with the host terms
     of the scalar call `lf(**params)`; nan outside the anchor box or where the rates are unphysical."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if isinstance(lf, SourceWiseBinnedLogLikelihood):            # (the one-row `_points` form, as its other layers)
+        return expected_coarse_points(lf, binning, {k: np.array([v], dtype=float) for k, v in params.items()}, per_source=per_source,
+                                      livetime_days=livetime_days)[0]
     _prepared(lf, binning, 'expected_coarse')
     _, zs, scale = lf._host_terms(livetime_days, params)
     shape = ((len(lf.source_name_list),) if per_source else ()) + binning.shape
@@ -186,7 +209,7 @@ def expected_coarse_jacobian_points(lf, binning, points, livetime_days=None):
     the chain rule of `values_gradients_hessians` (`hessian.user_jacobian`: live time, efficiencies, shape parameters that
     double as efficiencies).  On an anchor the slopes are those of the cell the point is assigned to.  A point outside the
     anchor box or with unphysical rates is nan throughout."""
-    _prepared(lf, binning, 'expected_coarse_jacobian_points')
+    _prepared(lf, binning, 'expected_coarse_jacobian_points', derivatives=True)
     z, scale, _ = lf._batch_terms(points, livetime_days)
     P = len(z)
     mu, jac, _ = lf.ctx.expected_coarse_jacobian(binning.n_cells, z if z.shape[1] else None, scale)

@@ -11,6 +11,8 @@
 // first-order columns of bi_fisher.h per corner row (ItemBatch / PointDerivs::first_order) and k_morph_coarse_jac<G>, whose G
 // columns the finish kernels take for R = G groups of rows: mu and d mu / d theta of every cell.  bi_coarse_counts: the dense counts rows through the same kernels,
 // or the non-empty-bin lists through k_coarse_list where only those exist.
+// The builder of a binning (coarse_build), the launch geometry, the chunks and the launch pair take the binning they work on as
+// an argument: bi_sourcewise_coarse.h runs them over the source-wise store's own binning (bi_ctx::sw_coarse).
 #pragma once
 
 namespace {
@@ -27,8 +29,7 @@ struct CoarseGeometry {
     int tx_shift, n_xt, nsplit, wide;
 };
 
-CoarseGeometry coarse_geometry(const bi_ctx* c) {
-    const bi_ctx::Coarse& q = c->coarse;
+CoarseGeometry coarse_geometry(const bi_ctx* c, const bi_ctx::Coarse& q) {
     CoarseGeometry g;
     g.tx_shift = q.Lx <= 64 ? 6 : (q.Lx <= 128 ? 7 : 8);
     const int64_t TX = (int64_t)1 << g.tx_shift, TY = kThreads >> g.tx_shift;
@@ -47,11 +48,11 @@ int coarse_check(bi_ctx* c, const char* what, bool need_data) {
     return BI_OK;
 }
 
-// the arguments of one launch pair over n_items items whose descriptors lie at rowoff / coef (device): partial -> d_out [n_items][R][C]
-CoarseArgs coarse_args(bi_ctx* c, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R, int64_t n_items,
-                       double* partial, double* d_out) {
-    const bi_ctx::Coarse& q = c->coarse;
-    const CoarseGeometry g = coarse_geometry(c);
+// the arguments of one launch pair over n_items items whose descriptors lie at rowoff / coef (device): partial -> d_out [n_items][R][C];
+// q: the binning, the grid model's (c->coarse) or the source-wise store's (c->sw_coarse)
+CoarseArgs coarse_args(bi_ctx* c, const bi_ctx::Coarse& q, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R,
+                       int64_t n_items, double* partial, double* d_out) {
+    const CoarseGeometry g = coarse_geometry(c, q);
     CoarseArgs a{};
     a.ps = rows; a.rowoff = rowoff; a.coef = coef;
     a.row_off = (const int64_t*)q.row_off.p; a.row_list = (const int32_t*)q.row_list.p; a.xb = (const int32_t*)q.xb.p;
@@ -63,56 +64,45 @@ CoarseArgs coarse_args(bi_ctx* c, const double* rows, const int64_t* rowoff, con
     return a;
 }
 
-void coarse_launch(bi_ctx* c, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R, int64_t n_items,
-                   double* partial, double* d_out) {
-    launch_morph_coarse(c, coarse_args(c, rows, rowoff, coef, NS, S, R, n_items, partial, d_out), n_items);
+void coarse_launch(bi_ctx* c, const bi_ctx::Coarse& q, const double* rows, const int64_t* rowoff, const double* coef, int NS, int S, int R,
+                   int64_t n_items, double* partial, double* d_out) {
+    launch_morph_coarse(c, coarse_args(c, q, rows, rowoff, coef, NS, S, R, n_items, partial, d_out), n_items);
 }
 
 // items per launch: the partial sums and the output of a chunk within ~64 MB each, a launch at most 32 768 items
-int64_t coarse_chunk(const bi_ctx* c, int64_t n_items, int R) {
-    const bi_ctx::Coarse& q = c->coarse;
-    const int64_t per_item = std::max<int64_t>((int64_t)R * q.CR * coarse_geometry(c).nsplit * q.Lx, (int64_t)R * q.C);
+int64_t coarse_chunk(const bi_ctx* c, const bi_ctx::Coarse& q, int64_t n_items, int R) {
+    const int64_t per_item = std::max<int64_t>((int64_t)R * q.CR * coarse_geometry(c, q).nsplit * q.Lx, (int64_t)R * q.C);
     return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_items, 32768), ((int64_t)1 << 23) / per_item));
 }
 
-}  // namespace
-
-extern "C" {
-
-int bi_set_coarse_binning(bi_ctx* c, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds, int64_t* n_cells) {
-    if (!c) return BI_ERR_INVALID;
-    if (n_cells) *n_cells = 0;
-    if (k == 0) {
-        if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
-        HIP_TRY(c, hipSetDevice(c->device));
-        release_coarse(c);
-        return BI_OK;
-    }
-    int rc = gof_check(c, "bi_set_coarse_binning", false);
-    if (rc) return rc;
-    if (k < 1 || k > kMaxDim || !n_fine || !n_groups || !bounds) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: need 0..%d axes with their bins, groups and boundaries", kMaxDim);
+// What bi_set_coarse_binning and bi_sourcewise_set_coarse_binning (bi_sourcewise_coarse.h) share: the checks of the axes against the
+// B fine bins of the caller's model, the per-axis group maps, the CSR of fine rows per coarse row, xb and the launch-size check,
+// into the binning q (the grid model's or the source-wise store's).  The caller has checked that its model is ready.
+int coarse_build(bi_ctx* c, bi_ctx::Coarse& q, const char* who, int64_t B, int k, const int32_t* n_fine, const int32_t* n_groups,
+                 const int32_t* bounds, int64_t* n_cells) {
+    int rc;
+    if (k < 1 || k > kMaxDim || !n_fine || !n_groups || !bounds) return fail(c, BI_ERR_INVALID, "%s: need 0..%d axes with their bins, groups and boundaries", who, kMaxDim);
     int64_t bins = 1;
     int off[kMaxDim];
     for (int j = 0, at = 0; j < k; ++j) {
-        if (n_fine[j] < 1) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: axis %d has %d fine bins", j, n_fine[j]);
-        if (n_groups[j] < 1) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: axis %d has %d groups (need >= 1)", j, n_groups[j]);
-        if (n_groups[j] > n_fine[j]) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: axis %d has more groups (%d) than fine bins (%d)", j, n_groups[j], n_fine[j]);
+        if (n_fine[j] < 1) return fail(c, BI_ERR_INVALID, "%s: axis %d has %d fine bins", who, j, n_fine[j]);
+        if (n_groups[j] < 1) return fail(c, BI_ERR_INVALID, "%s: axis %d has %d groups (need >= 1)", who, j, n_groups[j]);
+        if (n_groups[j] > n_fine[j]) return fail(c, BI_ERR_INVALID, "%s: axis %d has more groups (%d) than fine bins (%d)", who, j, n_groups[j], n_fine[j]);
         const int32_t* e = bounds + at;
         if (e[0] < 0 || e[n_groups[j]] > n_fine[j])
-            return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: the boundaries of axis %d leave [0, %d]", j, n_fine[j]);
+            return fail(c, BI_ERR_INVALID, "%s: the boundaries of axis %d leave [0, %d]", who, j, n_fine[j]);
         for (int i = 1; i <= n_groups[j]; ++i)
-            if (!(e[i] > e[i - 1])) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: the boundaries of axis %d are not strictly ascending", j);
+            if (!(e[i] > e[i - 1])) return fail(c, BI_ERR_INVALID, "%s: the boundaries of axis %d are not strictly ascending", who, j);
         off[j] = at;
         at += n_groups[j] + 1;
         bins *= n_fine[j];
-        if (bins > c->B) break;         // (already too many: the product cannot overflow)
+        if (bins > B) break;         // (already too many: the product cannot overflow)
     }
-    if (bins != c->B) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: the axes have %s%lld fine bins, the model %lld", bins > c->B ? "more than " : "", (long long)std::min(bins, c->B), (long long)c->B);
-    const int64_t L = n_fine[k - 1], NR = c->B / L;
-    if (NR > (int64_t)std::numeric_limits<int32_t>::max()) return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: %lld fine rows are more than a 32-bit index holds", (long long)NR);
+    if (bins != B) return fail(c, BI_ERR_INVALID, "%s: the axes have %s%lld fine bins, the model %lld", who, bins > B ? "more than " : "", (long long)std::min(bins, B), (long long)B);
+    const int64_t L = n_fine[k - 1], NR = B / L;
+    if (NR > (int64_t)std::numeric_limits<int32_t>::max()) return fail(c, BI_ERR_INVALID, "%s: %lld fine rows are more than a 32-bit index holds", who, (long long)NR);
     HIP_TRY(c, hipSetDevice(c->device));
-    release_coarse(c);
-    bi_ctx::Coarse& q = c->coarse;
+    release_coarse(q);
 
     // fine index -> group (-1: left out), per axis
     std::vector<std::vector<int32_t>> group_of((size_t)k);
@@ -168,20 +158,38 @@ int bi_set_coarse_binning(bi_ctx* c, int k, const int32_t* n_fine, const int32_t
     if ((rc = dev_upload(c, q.row_off, row_off)) || (rc = dev_upload(c, q.row_list, row_list)) || (rc = dev_upload(c, q.xb, xb)) ||
         (rc = dev_upload(c, q.row_map, row_map)) || (rc = dev_upload(c, q.x_map, group_of[(size_t)k - 1]))) {
         (void)hipStreamSynchronize(c->stream);
-        release_coarse(c);
+        release_coarse(q);
         return rc;
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the host vectors are alive until here)
     q.set = true;
-    const CoarseGeometry g = coarse_geometry(c);
+    const CoarseGeometry g = coarse_geometry(c, q);
     // (a launch's threads along x must stay below 2^32: 2^24 blocks of 256)
     if (q.CR * g.nsplit * g.n_xt >= ((int64_t)1 << 32) / kThreads) {
-        release_coarse(c);
-        return fail(c, BI_ERR_INVALID, "bi_set_coarse_binning: %lld coarse rows x %d x-tiles are more blocks than one launch holds (2^24)",
+        release_coarse(q);
+        return fail(c, BI_ERR_INVALID, "%s: %lld coarse rows x %d x-tiles are more blocks than one launch holds (2^24)", who,
                     (long long)q.CR, g.n_xt);
     }
     if (n_cells) *n_cells = q.C;
     return BI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_set_coarse_binning(bi_ctx* c, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds, int64_t* n_cells) {
+    if (!c) return BI_ERR_INVALID;
+    if (n_cells) *n_cells = 0;
+    if (k == 0) {
+        if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
+        HIP_TRY(c, hipSetDevice(c->device));
+        release_coarse(c);
+        return BI_OK;
+    }
+    int rc = gof_check(c, "bi_set_coarse_binning", false);
+    if (rc) return rc;
+    return coarse_build(c, c->coarse, "bi_set_coarse_binning", c->B, k, n_fine, n_groups, bounds, n_cells);
 }
 
 int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, int per_source, double* out, int32_t* status) {
@@ -200,8 +208,8 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
                                                     [&](int64_t p) { std::fill(out + p * per_item, out + (p + 1) * per_item, qnan); }, false);
     const int64_t n_items = (int64_t)live.size();
     if (n_items == 0) return BI_OK;
-    const int64_t chunk = coarse_chunk(c, n_items, R);
-    const CoarseGeometry geo = coarse_geometry(c);
+    const int64_t chunk = coarse_chunk(c, c->coarse, n_items, R);
+    const CoarseGeometry geo = coarse_geometry(c, c->coarse);
     ScratchBuf d_partial, d_out;
     if ((rc = dev_alloc(c, d_partial, (size_t)(chunk * R * c->coarse.CR * geo.nsplit * c->coarse.Lx) * sizeof(double))) ||
         (rc = dev_alloc(c, d_out, (size_t)(chunk * per_item) * sizeof(double)))) return rc;
@@ -214,7 +222,7 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
         PackedUpload pu;
         if ((rc = packed_upload(c, {{rowoff.data(), (size_t)ni * NS * sizeof(int64_t)}, {coef.data(), (size_t)ni * NS * sizeof(double)}}, 0, pu)))
             return rc;
-        coarse_launch(c, (const double*)c->ps.p, pu.dev<int64_t>(0), pu.dev<double>(1), NS, S, R, ni, (double*)d_partial.p, (double*)d_out.p);
+        coarse_launch(c, c->coarse, (const double*)c->ps.p, pu.dev<int64_t>(0), pu.dev<double>(1), NS, S, R, ni, (double*)d_partial.p, (double*)d_out.p);
         // (the staging block of packed_upload, d_partial and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, &live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse: %s", hipGetErrorString(e));
@@ -249,8 +257,8 @@ int bi_expected_coarse_jacobian(bi_ctx* c, int64_t P, const double* z, const dou
     for (int q = 0; q < D; ++q) full[(size_t)q] = q < de ? c->eff_axes[(size_t)q] : d + (q - de);
     for (int i = 0; i < de; ++i) axis_col[(size_t)i] = 1 + i;
     const ItemRoute rt = ItemRoute::dense(c);
-    const int64_t chunk = coarse_chunk(c, n_items, G);
-    const CoarseGeometry geo = coarse_geometry(c);
+    const int64_t chunk = coarse_chunk(c, c->coarse, n_items, G);
+    const CoarseGeometry geo = coarse_geometry(c, c->coarse);
     ScratchBuf d_partial, d_out;
     if ((rc = dev_alloc(c, d_partial, (size_t)(chunk * G * c->coarse.CR * geo.nsplit * c->coarse.Lx) * sizeof(double))) ||
         (rc = dev_alloc(c, d_out, (size_t)(chunk * G * C) * sizeof(double)))) return rc;
@@ -267,7 +275,7 @@ int bi_expected_coarse_jacobian(bi_ctx* c, int64_t P, const double* z, const dou
                    [&](const PointDerivs& pd, double* col, int corner, int s) { pd.first_order(col, corner, s, axis_col.data(), 1 + de + s); },
                    [](const PointDerivs&, double*, int64_t) {});
         if ((rc = batch.upload(c))) return rc;
-        const CoarseArgs a = coarse_args(c, rt.ps, batch.pu.dev<int64_t>(0), batch.pu.dev<double>(1), NS, S, G, ni, (double*)d_partial.p,
+        const CoarseArgs a = coarse_args(c, c->coarse, rt.ps, batch.pu.dev<int64_t>(0), batch.pu.dev<double>(1), NS, S, G, ni, (double*)d_partial.p,
                                          (double*)d_out.p);
         if (launch_morph_coarse_jac(c, G, a, ni)) return fail(c, BI_ERR_INVALID, "bi_expected_coarse_jacobian: no kernel variant for G = %d", G);
         // (the staging block of the batch, d_partial and d_out are reused by the next chunk: the download synchronises)
@@ -299,10 +307,10 @@ int bi_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, double* out) 
     HIP_TRY(c, hipSetDevice(c->device));
     const bi_ctx::Coarse& q = c->coarse;
     const bool dense = c->dense_counts;
-    const int64_t chunk = dense ? coarse_chunk(c, n, 1) : std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 32768), ((int64_t)1 << 23) / q.C));
+    const int64_t chunk = dense ? coarse_chunk(c, c->coarse, n, 1) : std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 32768), ((int64_t)1 << 23) / q.C));
     ScratchBuf d_partial, d_out, d_table;
     if ((rc = dev_alloc(c, d_out, (size_t)(chunk * q.C) * sizeof(double)))) return rc;
-    if (dense && (rc = dev_alloc(c, d_partial, (size_t)(chunk * q.CR * coarse_geometry(c).nsplit * q.Lx) * sizeof(double)))) return rc;
+    if (dense && (rc = dev_alloc(c, d_partial, (size_t)(chunk * q.CR * coarse_geometry(c, q).nsplit * q.Lx) * sizeof(double)))) return rc;
     if (!dense && (rc = dev_alloc(c, d_table, (size_t)(chunk * q.C) * sizeof(unsigned long long)))) return rc;
     std::vector<int64_t> first((size_t)chunk);        // dense: the element offset of the dataset's counts row; lists: the dataset
     const std::vector<double> ones(dense ? (size_t)chunk : 0, 1.0);
@@ -316,7 +324,7 @@ int bi_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, double* out) 
         if ((rc = packed_upload(c, {{first.data(), (size_t)ni * sizeof(int64_t)}, {ones.data(), dense ? (size_t)ni * sizeof(double) : 0}}, 0, pu))) return rc;
         hipError_t e = hipSuccess;
         if (dense) {
-            coarse_launch(c, (const double*)c->counts.p, pu.dev<int64_t>(0), pu.dev<double>(1), 1, 1, 1, ni, (double*)d_partial.p, (double*)d_out.p);
+            coarse_launch(c, q, (const double*)c->counts.p, pu.dev<int64_t>(0), pu.dev<double>(1), 1, 1, 1, ni, (double*)d_partial.p, (double*)d_out.p);
         } else {
             e = hipMemsetAsync(d_table.p, 0, (size_t)(ni * q.C) * sizeof(unsigned long long), c->stream);
             CoarseListArgs a{};

@@ -21,6 +21,7 @@
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
+//     tu_sourcewise_coarse.hip   k_sourcewise_coarse (coarse views of a source-wise model; finished by tu_coarse.hip's kernels)   bi_k_sourcewise_coarse.h
 //     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
 //     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
@@ -159,6 +160,11 @@ void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items);
 // k_morph_coarse_jac<G> + k_coarse_finish: the same with G = 4, 8 or 16 coefficient columns per corner row (a.R = G; a.coef [items][NS][G]);
 // BI_ERR_INVALID for another G
 int launch_morph_coarse_jac(bi_ctx* c, int G, const CoarseArgs& a, int64_t n_items);
+// k_coarse_finish or (a.wide) k_coarse_finish_wide over a.partial: what the two launchers above end with, and launch_sourcewise_coarse
+void launch_coarse_finish(bi_ctx* c, const CoarseArgs& a);
+// k_sourcewise_coarse<SC, EM, PS> + k_coarse_finish: the expectation of n_items (<= 65 535) points of a source-wise model summed over
+// the groups of a coarse binning, a.g.R = 1 (the total) or S (per source: PS); BI_ERR_INVALID for an (SC, EM) without a variant
+int launch_sourcewise_coarse(bi_ctx* c, int SC, int EM, bool per_source, const SourcewiseCoarseArgs& a, int64_t n_items);
 // k_coarse_list + k_coarse_table: the non-empty-bin lists of n (<= 65 535) datasets into the cells, out [n][C] (device memory)
 void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out);
 // ---- the toy-MC evaluation kernels (bi_k_toys.h).  No launcher times its kernel: the host half (bi_toys.h) opens the EventScopes.

@@ -176,6 +176,9 @@ struct bi_ctx {
         DevBuf xb;                       // [Cx + 1] int32: the column groups' boundaries
         DevBuf row_map, x_map;           // [NR], [L] int32: fine row -> coarse row, fine column -> coarse column, -1 = left out
     } coarse;
+    // ... and the one of bi_sourcewise_set_coarse_binning (bi_sourcewise_coarse.h) over the bins of the source-wise store `fac`:
+    // a second binning beside the grid model's, released by bi_factored_begin and bi_destroy
+    Coarse sw_coarse;
 
     // model statistics (for the sparse forms)
     std::vector<double> h_rowsum;  // [A*S] sum over bins of every ps row
@@ -386,11 +389,12 @@ struct ScratchBuf : DevBuf {
     ~ScratchBuf() { dev_free(*this); }
 };
 
-void release_coarse(bi_ctx* c) {
-    dev_free(c->coarse.row_off); dev_free(c->coarse.row_list); dev_free(c->coarse.xb); dev_free(c->coarse.row_map); dev_free(c->coarse.x_map);
-    c->coarse.set = false;
-    c->coarse.C = 0;
+void release_coarse(bi_ctx::Coarse& q) {
+    dev_free(q.row_off); dev_free(q.row_list); dev_free(q.xb); dev_free(q.row_map); dev_free(q.x_map);
+    q.set = false;
+    q.C = 0;
 }
+void release_coarse(bi_ctx* c) { release_coarse(c->coarse); }
 
 void drop_recycle_cache(bi_ctx* c) {
     (void)hipGetLastError();

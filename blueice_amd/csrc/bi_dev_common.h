@@ -213,6 +213,13 @@ struct CoarseArgs {
     int wide;                  // the finish kernel: 0 one thread per cell, 1 one block per cell (k_coarse_finish_wide)
 };
 
+// k_sourcewise_coarse (bi_k_sourcewise_coarse.h): the descriptors of FactoredArgs (rowoff, coef [items][NR][1 + EM], rates, e) and
+// the binning, geometry and partial sums of CoarseArgs (g.ps, g.rowoff, g.coef, g.NS and g.S are not read; g.R = 1 or S)
+struct SourcewiseCoarseArgs {
+    FactoredArgs f;
+    CoarseArgs g;
+};
+
 // k_coarse_list (bi_k_coarse.h): the non-empty-bin lists of n datasets into 64-bit integer tables [n][C]
 struct CoarseListArgs {
     const int32_t* nz_idx;     // fine bin of every entry

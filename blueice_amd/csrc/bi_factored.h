@@ -15,6 +15,8 @@
 // sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
 // Beeston-Barlow, unbinned data.  The counts are dense doubles [T][Bp]: the caller's (bi_factored_set_counts) or toys drawn
 // on the device (bi_sourcewise_generate_toys, bi_sourcewise.h, which also holds the expectation and goodness-of-fit layers).
+// Coarse views of the expectation and of these counts: bi_sourcewise_coarse.h, with a coarse binning of the store's own
+// (bi_ctx::sw_coarse), which bi_factored_begin releases.
 //
 // bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own (FacBatch, which the curvature calls of
 // bi_factored_curv.h share): screen, fill on host threads, one packed upload, run_item_chunks + k_finish.  The blocks per item
@@ -402,6 +404,7 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     m.h_lgsum.clear();
     dev_free(m.real_counts);    // (rows of the previous model's padded length)
     m.real_T = 0;
+    release_coarse(c->sw_coarse);   // (groups of the previous model's bins)
     m.d = d; m.S = S; m.B = B;
     m.Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
     m.grid.assign((size_t)d, {});

@@ -6,7 +6,8 @@
 // ascending -- so mu_b here has the bits of the mu_b the likelihood kernel forms.  The descriptors are FacBatch's of order 0
 // (bi_factored.h): row offsets, coef [NR][1 + EM] of which column 0 (w_c) is read, rates [SC]; all uniform per item and read
 // through scalar loads.  Both kernels keep two bins in flight at every (SC, EM) class, one 16-byte load per row: without the
-// gradient's ups columns a thread holds at most SC = 8 tau pairs.
+// gradient's ups columns a thread holds at most SC = 8 tau pairs.  sourcewise_chain_bin<SC, EM> restates the chain for one bin per
+// thread (k_sourcewise_coarse, bi_k_sourcewise_coarse.h): the same statements, the same bits.
 //
 // k_sourcewise_expect<SC, EM, PS, NT>: grid (tile, item); out[item][0][b] = mu_b, or with PS out[item][s][b] = r_s tau_s,b (one
 // multiply) for the sources the model has, one 16-byte store per row of stride Bp.  Nothing is reduced and no counts are read.
@@ -46,6 +47,33 @@ __device__ __forceinline__ void sourcewise_chain(const FactoredArgs& a, const in
         const double r = rate[s];
         mu[0] = fma(r, tau[s][0], mu[0]);
         mu[1] = fma(r, tau[s][1], mu[1]);
+    }
+}
+
+// The same chain for ONE bin per thread, statement for statement: k_sourcewise_coarse (bi_k_sourcewise_coarse.h), whose lanes lie
+// along the last analysis axis at bins r L + x that are not 16-byte aligned in general (8-byte loads).
+template <int SC, int EM>
+__device__ __forceinline__ void sourcewise_chain_bin(const FactoredArgs& a, const int64_t* __restrict__ rowoff, const double* __restrict__ coef,
+                                                     const double* __restrict__ rate, int64_t bin, double (&tau)[SC], double& mu) {
+    constexpr int NC = 1 << EM, W = 1 + EM;
+    static_assert(SC <= 8, "FactoredArgs::e holds 8 sources");
+    mu = 0.0;
+    int k = 0;                  // the source's first row: uniform
+#pragma unroll
+    for (int s = 0; s < SC; ++s) {
+        tau[s] = 0.0;
+        const int nc = a.e[s] < 0 ? 0 : 1 << a.e[s];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            if (c < nc) {
+                const double p = a.ps[rowoff[k + c] + bin];
+                const double w = coef[(int64_t)(k + c) * W];
+                tau[s] = fma(w, p, tau[s]);
+            }
+        }
+        k += nc;
+        const double r = rate[s];
+        mu = fma(r, tau[s], mu);
     }
 }
 

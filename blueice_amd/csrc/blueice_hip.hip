@@ -107,6 +107,7 @@ void bi_destroy(bi_ctx* c) {
     dev_free(c->real_counts);
     dev_free(c->fac.ps); dev_free(c->fac.counts); dev_free(c->fac.real_counts);
     release_coarse(c);
+    release_coarse(c->sw_coarse);
     if (c->slot_host) (void)hipHostFree(c->slot_host);
     if (c->pack_host) (void)hipHostFree(c->pack_host);
     if (c->bounce_host) (void)hipHostFree(c->bounce_host);
@@ -1617,3 +1618,4 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_sampler.h"
 #include "bi_grid.h"
 #include "bi_coarse.h"
+#include "bi_sourcewise_coarse.h"

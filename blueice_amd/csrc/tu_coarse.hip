@@ -3,12 +3,17 @@
 #include "bi_common.h"
 #include "bi_k_coarse.h"
 
+// (no EventScope of its own: the launcher of the kernel that wrote a.partial holds one around the pair)
+void launch_coarse_finish(bi_ctx* c, const CoarseArgs& a) {
+    if (a.wide) hipLaunchKernelGGL(k_coarse_finish_wide, dim3((unsigned)a.n_out), dim3(kThreads), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_coarse_finish, dim3((unsigned)((a.n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+}
+
 void launch_morph_coarse(bi_ctx* c, const CoarseArgs& a, int64_t n_items) {
     EventScope ev(c);
     const dim3 grid((unsigned)(a.CR * a.nsplit * a.n_xt), (unsigned)a.R, (unsigned)n_items);
     hipLaunchKernelGGL(k_morph_coarse, grid, dim3(kThreads), 0, c->stream, a);
-    if (a.wide) hipLaunchKernelGGL(k_coarse_finish_wide, dim3((unsigned)a.n_out), dim3(kThreads), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_coarse_finish, dim3((unsigned)((a.n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    launch_coarse_finish(c, a);
 }
 
 // G coefficient columns per corner row (a.R = G: the finish kernels take the columns for groups); BI_ERR_INVALID for a G
@@ -20,8 +25,7 @@ int launch_morph_coarse_jac(bi_ctx* c, int G, const CoarseArgs& a, int64_t n_ite
     if (G == 4) hipLaunchKernelGGL(k_morph_coarse_jac<4>, grid, dim3(kThreads), 0, c->stream, a);
     else if (G == 8) hipLaunchKernelGGL(k_morph_coarse_jac<8>, grid, dim3(kThreads), 0, c->stream, a);
     else hipLaunchKernelGGL(k_morph_coarse_jac<16>, grid, dim3(kThreads), 0, c->stream, a);
-    if (a.wide) hipLaunchKernelGGL(k_coarse_finish_wide, dim3((unsigned)a.n_out), dim3(kThreads), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_coarse_finish, dim3((unsigned)((a.n_out + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, a);
+    launch_coarse_finish(c, a);
     return BI_OK;
 }
 

@@ -44,7 +44,7 @@ from .hessian import chain_rule_information, chain_rule_unbounded, covariance_fr
 from .profile import bestfit_batched, supports_batched_fits
 from .sampler import sample_posterior
 from .utils import is_numeric
-from .coarse import (_binned_for_gof, _prepared, coarse_counts, coarse_information, coarse_statistics, expected_coarse,
+from .coarse import (CoarseBinning, _binned_for_gof, _prepared, coarse_counts, coarse_information, coarse_statistics, expected_coarse,
                      expected_coarse_band, expected_coarse_jacobian, expected_coarse_jacobian_points, expected_coarse_points)
 
 __all__ = ['best_anchor', 'make_objective', 'bestfit_scipy', 'bestfit_device', 'bestfit_batched', 'bestfit_toys', 'toy_mc_fits',
@@ -219,13 +219,13 @@ def _simulate_toys_at(lf, n_toys, seed, livetime_days, truth):
 
 def _binned_or_source_wise(lf, what, binning=None):
     """The gate of the layers that also take a source-wise model (toy fits, goodness of fit, expected_counts_points): a
-    `BinnedLogLikelihood` without Beeston-Barlow (`_binned_for_gof`), or a prepared `SourceWiseBinnedLogLikelihood`, which has no
-    coarse views: `binning` must be None for it."""
+    `BinnedLogLikelihood` without Beeston-Barlow (`_binned_for_gof`), or a prepared `SourceWiseBinnedLogLikelihood`, for which
+    `binning` must be None or a `CoarseBinning` (bi_sourcewise_expected_coarse, bi_sourcewise_coarse_counts)."""
     from .source_wise import SourceWiseBinnedLogLikelihood
     if isinstance(lf, SourceWiseBinnedLogLikelihood):
-        if binning is not None:
-            raise NotImplementedError("%s(binning=...) is not available for a source-wise model (SourceWiseBinnedLogLikelihood): it "
-                                      "has no coarse views" % what)
+        if binning is not None and not isinstance(binning, CoarseBinning):
+            raise NotImplementedError("%s(binning=...) is not available for a source-wise model (SourceWiseBinnedLogLikelihood) with a "
+                                      "%s: its coarse views take a blueice_amd.coarse.CoarseBinning" % (what, type(binning).__name__))
         if not lf.is_prepared:
             raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
         return lf
@@ -522,7 +522,8 @@ def gof_statistics(lf, points=None, datasets=None, livetime_days=None, binning=N
     (`coarse_statistics`); n_bins is C, and n_events counts the events inside the cells.  THE STATISTIC IS THEN A STATEMENT
     ABOUT THE COARSE CELLS ONLY: what happens inside a cell, or in fine bins that belong to no cell, is invisible to it -- in
     particular an event in a fine bin with no expectation no longer forces +inf, unless its whole cell expects nothing.
-    A prepared source-wise model is taken too (bi_eval_sourcewise_gof), without `binning`."""
+    A prepared source-wise model is taken too (bi_eval_sourcewise_gof; with `binning` bi_sourcewise_expected_coarse and
+    bi_sourcewise_coarse_counts)."""
     _binned_or_source_wise(lf, 'gof_statistics', binning)
     if not lf.is_data_set:
         raise NotPreparedException("gof_statistics requires you to first set the data using set_data()")
@@ -611,7 +612,7 @@ def goodness_of_fit(lf, n_toys=1000, statistic='deviance', chunk=256, seed=0, fi
     binning: a `CoarseBinning` -- the data and every toy are still FITTED on the fine bins, but the statistic of steps 2 and 5
     is formed over the cells of the binning (`gof_statistics(..., binning=)`: a statement about the coarse cells only), where
     a test on ~10^4 events has power that it lacks on 10^6 fine bins; ndof = n_cells - n_floating.
-    A prepared source-wise model is taken too, without `binning` (its toys: `simulate_toys_points` with one truth)."""
+    A prepared source-wise model is taken too, with or without `binning` (its toys: `simulate_toys_points` with one truth)."""
     _binned_or_source_wise(lf, 'goodness_of_fit', binning)
     if statistic not in ('deviance', 'pearson'):
         raise ValueError("statistic must be 'deviance' or 'pearson'")

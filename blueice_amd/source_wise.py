@@ -9,7 +9,9 @@
     lf.simulate_toys_points, lf.toy_test_statistics, lf.neyman_thresholds, and as functions of blueice_amd.inference:
     bestfit_toys(lf), toy_mc_fits(lf, n), gof_statistics(lf, ...), goodness_of_fit(lf, ...), expected_counts_points(lf, points),
     lf.asimov_points, lf.asimov_test_statistic, lf.expected_discovery_significance, blueice_amd.asimov.asimov(lf, **truth),
-    blueice_amd.asimov.real_data(lf, counts), blueice_amd.inference.expected_upper_limit(lf, target, bound)
+    blueice_amd.asimov.real_data(lf, counts), blueice_amd.inference.expected_upper_limit(lf, target, bound),
+    blueice_amd.coarse.CoarseBinning(lf, ...), expected_coarse_points(lf, binning, points), expected_coarse(lf, binning, **params),
+    coarse_counts(lf, binning), and gof_statistics(lf, ..., binning=) / goodness_of_fit(lf, ..., binning=)
 
 `BinnedLogLikelihood` morphs over ONE tensor-product grid of all shape parameters: prod n_i anchor models in HBM and S 2^d
 rows per evaluation, which caps the number of shape parameters at a handful.  Here every source morphs over the parameters
@@ -39,11 +41,19 @@ blueice_amd.inference run over it -- one profile scan where an ensemble of toys 
 observed data are needed for them.  The bound lf.asimov, lf.real_data and lf.expected_upper_limit stay refused and name these
 spellings; lf.asimov_points, lf.asimov_test_statistic and lf.expected_discovery_significance are bound.
 
+Coarse views -- projections, a rebinned analysis space, a signal box -- are summed on the device as well
+(bi_sourcewise_set_coarse_binning, bi_sourcewise_expected_coarse, bi_sourcewise_coarse_counts): the functions of blueice_amd.coarse
+take a prepared source-wise model and a `CoarseBinning` made for it, and `gof_statistics` / `goodness_of_fit` of
+blueice_amd.inference take that binning as `binning=` (the toys are still fitted on the fine bins).  A projection comes down as
+its cells, not as every fine bin.  The bound lf.expected_coarse, lf.expected_coarse_points and lf.coarse_counts stay refused and
+name these spellings.  The derivatives of coarse views (expected_coarse_jacobian*, expected_coarse_band, coarse_information) are
+not available.
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, eval_toys*, grids, coarse views (and `binning=` in the goodness-of-fit calls), Hessians on an Asimov view and
-the ensemble sampler.
+full_output calls, eval_toys*, grids, derivatives of coarse views, Hessians on an Asimov view and the ensemble sampler.
 """
+import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
@@ -71,7 +81,8 @@ def _find_cell(g, z):
 class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
-    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, generate_toys_points, download_counts, set_param / get_param,
+    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, coarse_counts,
+    generate_toys_points, download_counts, set_param / get_param,
     fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
     real_count_sets, download_real_counts, eval_real, fit_batched_real) -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
     meaning here and is an AttributeError."""
@@ -82,6 +93,7 @@ class SourceWiseContext:
         self.d = self.S = self.B = None
         self.T = 0
         self._counts = None
+        self._coarse_key = None
 
     def set_param(self, name, value):
         """a parameter of the underlying context (`toy_offset`: the number of a generator call's first toy in the seed's ensemble)"""
@@ -107,6 +119,7 @@ class SourceWiseContext:
         own_axes = [tuple(int(i) for i in own) for own in own_axes]
         n_own = np.array([len(own) for own in own_axes], dtype=np.int32)
         own_flat = np.array([i for own in own_axes for i in own], dtype=np.int32)
+        self._coarse_key = None                 # (bi_factored_begin releases the store's coarse binning)
         dev._check(dev._lib.bi_factored_begin(dev._h, len(anchor_z), ptr(n_anchor), ptr(flat), int(S), int(B), ptr(n_own),
                                               ptr(own_flat) if len(own_flat) else None))
         self.d, self.S, self.B = len(anchor_z), int(S), int(B)
@@ -229,6 +242,54 @@ class SourceWiseContext:
         dev._check(dev._lib.bi_sourcewise_expected_counts(dev._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out)))
         return out
 
+    # -- coarse views: the expectation and the data summed over groups of fine bins (bi_sourcewise_set_coarse_binning ...), under
+    #    DeviceContext's names and shapes --
+    def set_coarse_binning(self, fine_shape=None, groups=None):
+        """The coarse binning of the source-wise store: fine_shape [k] fine bins per analysis axis, groups: per axis the ascending
+        fine-bin boundaries e_0 < ... < e_m (`CoarseBinning.groups`) -> the number of cells.  No arguments: clear it.  A new model
+        releases it.  ValueError (BI_ERR_INVALID) for boundaries that do not fit the model."""
+        dev = self._dev
+        cells = C.c_int64(0)
+        if fine_shape is None:
+            self._coarse_key = None
+            dev._check(dev._lib.bi_sourcewise_set_coarse_binning(dev._h, 0, None, None, None, C.byref(cells)))
+            return 0
+        n_fine = np.ascontiguousarray(fine_shape, dtype=np.int32)
+        groups = [np.ascontiguousarray(g, dtype=np.int32).ravel() for g in groups]
+        if len(groups) != len(n_fine) or not len(n_fine):
+            raise ValueError("need the boundaries of every one of the %d axes" % len(n_fine))
+        n_groups = np.array([len(g) - 1 for g in groups], dtype=np.int32)
+        bounds = np.ascontiguousarray(np.concatenate(groups), dtype=np.int32)
+        # the binning the store holds already (begin_model forgets it, as bi_factored_begin releases it): nothing to build or upload
+        key = (n_fine.tobytes(), n_groups.tobytes(), bounds.tobytes())
+        if self._coarse_key is not None and self._coarse_key[0] == key:
+            return self._coarse_key[1]
+        self._coarse_key = None
+        dev._check(dev._lib.bi_sourcewise_set_coarse_binning(dev._h, len(n_fine), ptr(n_fine), ptr(n_groups), ptr(bounds), C.byref(cells)))
+        self._coarse_key = (key, int(cells.value))
+        return int(cells.value)
+
+    def expected_coarse(self, n_cells, z, rate_scale=None, per_source=False):
+        """The expectation per cell of the coarse binning (bi_sourcewise_expected_coarse) -> (mu [P, C] or [P, S, C], status [P]);
+        nan rows and the status bit for points outside the anchor box or with unphysical rates.  No counts are needed."""
+        dev = self._dev
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        out = np.empty((P, self.S, int(n_cells)) if per_source else (P, int(n_cells)), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_sourcewise_expected_coarse(dev._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out), ptr(status)))
+        return out, status
+
+    def coarse_counts(self, n_cells, datasets=None):
+        """The counts of the store's datasets -- uploaded, or toys drawn on the device -- per cell of the coarse binning
+        (bi_sourcewise_coarse_counts) -> [n, C]; datasets: indices [n] (None: all T)."""
+        dev = self._dev
+        if datasets is not None:
+            datasets = np.ascontiguousarray(np.atleast_1d(datasets), dtype=np.int64)
+        n = int(self.T) if datasets is None else len(datasets)
+        out = np.empty((n, int(n_cells)), dtype=np.float64)
+        dev._check(dev._lib.bi_sourcewise_coarse_counts(dev._h, n, ptr(datasets), ptr(out)))
+        return out
+
     def eval_fisher(self, z, rate_scale=None):
         """The expected (Fisher) information at P truths, no counts needed (bi_eval_sourcewise_fisher) -> (info [P, d + S, d + S],
         total expectation [P], unbounded [P, d + S], status [P]): DeviceContext.eval_fisher's shapes and meaning."""
@@ -346,6 +407,9 @@ _REFUSED_SPELLINGS = {
     'goodness_of_fit': "blueice_amd.inference.goodness_of_fit(lf, n_toys=...)",
     'expected_counts': "blueice_amd.inference.expected_counts_points(lf, points, per_source=) with one-row arrays in `points`",
     'expected_counts_points': "blueice_amd.inference.expected_counts_points(lf, points, per_source=)",
+    'expected_coarse': "blueice_amd.coarse.expected_coarse(lf, binning, **params)",
+    'expected_coarse_points': "blueice_amd.coarse.expected_coarse_points(lf, binning, points)",
+    'coarse_counts': "blueice_amd.coarse.coarse_counts(lf, binning, datasets=)",
     'asimov': "blueice_amd.asimov.asimov(lf, **truth)",
     'real_data': "blueice_amd.asimov.real_data(lf, counts)",
     'expected_upper_limit': "blueice_amd.inference.expected_upper_limit(lf, target, bound)",
@@ -359,7 +423,7 @@ def _refused(name):
                                       % (name, _REFUSED_SPELLINGS[name]))
         raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
                                   "Hessian, expected information, the fit, scan and interval layers, toys at truth points, "
-                                  "goodness of fit and Asimov data are" % name)
+                                  "goodness of fit, coarse views and Asimov data are" % name)
     method.__name__ = name
     return method
 

@@ -1,6 +1,6 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--measure | --measure-toys | --measure-asimov [--rounds 31]]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--measure | --measure-toys | --measure-asimov | --measure-coarse [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
 grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
@@ -38,6 +38,10 @@ numpy.random.Generator.poisson on the same expectation on the host plus the uplo
 --measure-asimov times, at the same source-wise shape, bi_eval_sourcewise_real with and without its gradient against
 bi_eval_factored with and without its gradient and against bi_eval_sourcewise_gof, all on the same rows (the same counts in the
 real-valued store and in the ordinary one), at 64 points per call and at one, and the kernels alone by device events.
+
+--measure-coarse times, at the same source-wise shape, bi_sourcewise_expected_coarse (the projection on the first analysis axis, the
+10^3 rebinning and everything in one cell; total and per source) against bi_sourcewise_expected_counts plus the NumPy reduction it
+replaces, and k_sourcewise_coarse with its finish kernel alone, by device events, against k_sourcewise_expect on the same points.
 """
 import argparse
 import time
@@ -50,6 +54,7 @@ ap.add_argument('--scan', type=int, default=33, help='hypotheses of the profile 
 ap.add_argument('--measure', action='store_true', help='time bi_eval_factored against bi_eval_grad on the expanded grid')
 ap.add_argument('--measure-toys', action='store_true', help='time the goodness-of-fit, expected-counts and toy-generator calls')
 ap.add_argument('--measure-asimov', action='store_true', help='time bi_eval_sourcewise_real against bi_eval_factored on the same rows')
+ap.add_argument('--measure-coarse', action='store_true', help='time bi_sourcewise_expected_coarse against expected_counts + the NumPy reduction')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
 ap.add_argument('--rounds', type=int, default=31)
@@ -246,6 +251,70 @@ def measure_toys():
     fac.close()
 
 
+def measure_coarse():
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    nb = args.measure_bins
+    n_a, B, P = 5, nb ** 3, 64
+    Bp = (B + 511) // 512 * 512
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    z = rng.uniform(-1.9, 1.9, (P, d))
+    r = rng.uniform(0.8, 1.2, (P, S))
+    print('source-wise model: %d rows, %.2f GB resident (it stays in the 256 MB Infinity Cache: every figure below is cache-assisted)'
+          % (S * n_a, S * n_a * Bp * 8 / 1e9), flush=True)
+    shape = (nb, nb, nb)
+    fine, whole = np.arange(nb + 1), np.array([0, nb])
+    k = max(nb // 10, 1)
+    tens = np.array(list(range(0, nb, k)) + [nb])
+    m = len(tens) - 1
+    even = nb % k == 0
+    views = [('x0 projection (%d cells)' % nb, [fine, whole, whole], lambda mu: mu.reshape(mu.shape[:-1] + shape).sum(axis=(-2, -1))),
+             ('%d^3 rebinning' % m, [tens, tens, tens],
+              (lambda mu: mu.reshape(mu.shape[:-1] + (m, k, m, k, m, k)).sum(axis=(-5, -3, -1)).reshape(mu.shape[:-1] + (m ** 3,))) if even else None),
+             ('everything in one cell', [whole, whole, whole], lambda mu: mu.sum(axis=-1, keepdims=True))]
+    dev = fac._dev
+    gb = 2 * S * Bp * 8 * P / 1e9                     # the rows a call reads: two corner rows per source and point
+    for label, groups, reduce_host in views:
+        cells = fac.set_coarse_binning(shape, groups)
+        got, _ = fac.expected_coarse(cells, z, r)
+        if reduce_host is not None:
+            want = reduce_host(fac.expected_counts(z, r))
+            print('%s: max |device - host reduction| / value %.2g' % (label, np.max(np.abs(got - want) / want)), flush=True)
+        calls = [('expected_coarse, %s' % label, lambda: fac.expected_coarse(cells, z, r)),
+                 ('expected_coarse per source, %s' % label, lambda: fac.expected_coarse(cells, z, r, per_source=True))]
+        if reduce_host is not None:
+            calls.append(('expected_counts (%.2f GB down) + numpy sum, %s' % (P * B * 8 / 1e9, label), lambda: reduce_host(fac.expected_counts(z, r))))
+        alternate(calls, P)
+        for name, call in (('k_sourcewise_coarse + finish', calls[0][1]), ('k_sourcewise_coarse<PS> + finish', calls[1][1]),
+                           ('k_sourcewise_expect', lambda: fac.expected_counts(z, r))):
+            dev.profile(True)
+            ks = []
+            for _ in range(args.rounds):
+                call()
+                ks.append(dev.profile_read()[1] * 1e-3)
+            dev.profile(False)
+            print('%-32s kernels %s per call; %.2f GB of rows read -> %.2f TB/s' % (name, quartiles(ks), gb, gb / np.median(ks) / 1e3), flush=True)
+    rounds, args.rounds = args.rounds, max(3, args.rounds // 10)         # the per-source fine route moves 2 GB and takes a second per call
+    project = views[0][2]
+    fac.set_coarse_binning(shape, views[0][1])
+    alternate([('expected_coarse per source, x0 projection', lambda: fac.expected_coarse(nb, z, r, per_source=True)),
+               ('expected_counts per source (%.2f GB down) + numpy sum' % (P * S * B * 8 / 1e9), lambda: project(fac.expected_counts(z, r, per_source=True)))], P)
+    args.rounds = rounds
+    print('(k_sourcewise_expect also writes %.2f GB, which k_sourcewise_coarse does not)' % (P * Bp * 8 / 1e9))
+    print('not measured: the other kernel classes (more sources, more own axes), other shapes, coarse_counts, ranges and irregular groups')
+    fac.close()
+
+
 def measure_asimov():
     from blueice_amd.source_wise import SourceWiseContext
     d = S = 4
@@ -363,6 +432,9 @@ if args.measure:
     raise SystemExit(0)
 if args.measure_asimov:
     measure_asimov()
+    raise SystemExit(0)
+if args.measure_coarse:
+    measure_coarse()
     raise SystemExit(0)
 if args.asimov:
     asimov_band()

@@ -643,6 +643,27 @@ int bi_sourcewise_generate_toys(bi_ctx* ctx, int64_t H, const double* z, const d
                                 uint64_t seed);
 int bi_sourcewise_download_counts(bi_ctx* ctx, int64_t t, double* out /*[B]*/);
 
+/* ... and its coarse views: the expectation and the data summed over tensor-product groups of fine bins, the layer that
+ * bi_set_coarse_binning ... bi_coarse_counts are for the grid model, without a bin tensor in between.
+ *   bi_sourcewise_set_coarse_binning   bi_set_coarse_binning's contract over the B bins of the source-wise model (the product of
+ *                               n_fine must be that B; the same boundaries, errors and n_cells).  The binning is a state of its
+ *                               own beside the grid model's: neither call touches the other's.  k = 0 clears it; a new
+ *                               bi_factored_begin releases it.
+ *   bi_sourcewise_expected_coarse   out [P][C] (per_source = 0) or [P][S][C]: the cells of mu_b, or of r_s tau_s,b, formed per fine
+ *                               bin with the bits of bi_sourcewise_expected_counts and summed in an order that the binning and
+ *                               the device fix (never the number of points).  The screen is bi_sourcewise_expected_counts's; a
+ *                               dead point gets nan in every cell and its bit in status [P] (nullable).
+ *   bi_sourcewise_coarse_counts out [n][C]: the counts of datasets dataset[0 .. n) (NULL: all of them, n = T) of the store --
+ *                               uploaded or drawn on the device -- in the cells; sums of integer counts are exact.  A dataset
+ *                               outside [0, T): BI_ERR_INVALID.
+ * The last two without a binning: BI_ERR_STATE.  No floating-point atomics; a repeated call is bitwise identical and a point's
+ * cells do not depend on the batch it is evaluated in.  The real-valued store has no coarse view. */
+int bi_sourcewise_set_coarse_binning(bi_ctx* ctx, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds,
+                                     int64_t* n_cells);
+int bi_sourcewise_expected_coarse(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out,
+                                  int32_t* status);
+int bi_sourcewise_coarse_counts(bi_ctx* ctx, int64_t n, const int64_t* dataset, double* out);
+
 /* ... and real-valued datasets of a source-wise model: Asimov data (n_b = mu_b(truth)) and weighted histograms, the layer that
  * bi_set_real_counts ... bi_fit_batched_real are for the grid model.  The store is [T][Bp] doubles (Bp = B rounded up to 512,
  * zero behind B) inside the source-wise model BESIDE its ordinary counts, which stay resident and keep scipy's integer
