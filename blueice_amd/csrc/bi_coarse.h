@@ -207,6 +207,7 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
     const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, nullptr, status,
                                                     [&](int64_t p) { std::fill(out + p * per_item, out + (p + 1) * per_item, qnan); }, false);
     const int64_t n_items = (int64_t)live.size();
+    c->last_point_pieces = 0;
     if (n_items == 0) return BI_OK;
     const int64_t chunk = coarse_chunk(c, c->coarse, n_items, R);
     const CoarseGeometry geo = coarse_geometry(c, c->coarse);
@@ -223,6 +224,7 @@ int bi_expected_coarse(bi_ctx* c, int64_t P, const double* z, const double* rate
         if ((rc = packed_upload(c, {{rowoff.data(), (size_t)ni * NS * sizeof(int64_t)}, {coef.data(), (size_t)ni * NS * sizeof(double)}}, 0, pu)))
             return rc;
         coarse_launch(c, c->coarse, (const double*)c->ps.p, pu.dev<int64_t>(0), pu.dev<double>(1), NS, S, R, ni, (double*)d_partial.p, (double*)d_out.p);
+        ++c->last_point_pieces;
         // (the staging block of packed_upload, d_partial and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, &live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse: %s", hipGetErrorString(e));
@@ -250,6 +252,7 @@ int bi_expected_coarse_jacobian(bi_ctx* c, int64_t P, const double* z, const dou
         std::fill(jac + p * F * C, jac + (p + 1) * F * C, qnan);
     }, false);
     const int64_t n_items = (int64_t)live.size();
+    c->last_point_pieces = 0;
     if (n_items == 0) return BI_OK;
 
     // full parameter index of first-order index q, and the columns of the effective axes (bi_fisher.h's)
@@ -278,6 +281,7 @@ int bi_expected_coarse_jacobian(bi_ctx* c, int64_t P, const double* z, const dou
         const CoarseArgs a = coarse_args(c, c->coarse, rt.ps, batch.pu.dev<int64_t>(0), batch.pu.dev<double>(1), NS, S, G, ni, (double*)d_partial.p,
                                          (double*)d_out.p);
         if (launch_morph_coarse_jac(c, G, a, ni)) return fail(c, BI_ERR_INVALID, "bi_expected_coarse_jacobian: no kernel variant for G = %d", G);
+        ++c->last_point_pieces;
         // (the staging block of the batch, d_partial and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, run.data(), ni, (const double*)d_out.p, (int64_t)G * C, stage.data(), hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_coarse_jacobian: %s", hipGetErrorString(e));
@@ -303,6 +307,7 @@ int bi_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, double* out) 
         if (dataset[i] < 0 || dataset[i] >= c->T)
             return fail(c, BI_ERR_INVALID, "bi_coarse_counts: dataset %lld outside [0,%lld)", (long long)dataset[i], (long long)c->T);
     if (!c->dense_counts && !c->csr_ready) return fail(c, BI_ERR_STATE, "no counts resident");
+    c->last_point_pieces = 0;
     if (n == 0) return BI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const bi_ctx::Coarse& q = c->coarse;
@@ -335,6 +340,7 @@ int bi_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, double* out) 
             a.L = q.L; a.Cx = q.Cx; a.C = q.C;
             if (e == hipSuccess) launch_coarse_list(c, a, ni, (double*)d_out.p);
         }
+        ++c->last_point_pieces;
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(out + i0 * q.C, d_out.p, (size_t)(ni * q.C) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -131,6 +131,9 @@ struct bi_ctx {
     // read-only: the grid of the most recent k_morph_reduce / k_morph_single launch (gridDim.x blocks per item, gridDim.y items)
     // and whether it finished through the mailbox (0: k_finish, k_finish_single or the two-kernel fallback ran behind it)
     int64_t last_morph_nbx = 0, last_morph_items = 0, last_morph_fused = 0;
+    // read-only: the device pieces the most recent per-point entry point cut its live items into on the host (the chunks of
+    // run_item_chunks, summed over FacBatch::run's sub-batches and panels; the iterations of a bin-writing call's chunk loop)
+    int64_t last_point_pieces = 0;
 
     // real-valued datasets [real_T][Bp] (bi_set_real_counts / bi_set_asimov_counts; bi_real.h): a store of its own beside
     // `counts`, read by bi_eval_real / bi_fit_batched_real only and released by a new model

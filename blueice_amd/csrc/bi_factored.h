@@ -181,10 +181,13 @@ struct FacBatch {
     size_t first_extra = 0;                     // index of the caller's first own part in pu
 
     bool dataset_test;                          // the screen tests the dataset index (calls that read counts)
+    mutable int64_t pieces = 0;                 // run_item_chunks' chunks over every run() so far: last_point_pieces
 
     FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true)
         : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
-          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts) {}
+          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts) {
+        c->last_point_pieces = 0;               // (a call with no live item launches nothing)
+    }
 
     // reset(p) writes the caller's defaults of point p; status [P] (nullable) gets every point's bits
     template <class F>
@@ -298,7 +301,8 @@ struct FacBatch {
 
     // One kernel over the live points: nsl result slots per item, perm / slot_lg [n][nsl] (device) where a slot's sum goes and
     // what k_finish subtracts from it.  The blocks of an item depend on the rows' length alone; sub-batches keep the partial
-    // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.
+    // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.  last_point_pieces counts
+    // the chunks of every sub-batch of every run() of this batch (the curvature calls run once per Gram panel).
     template <class L>
     int run(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
         const FactoredArgs a = args();
@@ -316,6 +320,8 @@ struct FacBatch {
                                            },
                                            nbx);
             if (rc) return rc;
+            pieces += c->last_point_pieces;
+            c->last_point_pieces = pieces;
         }
         return BI_OK;
     }

@@ -92,6 +92,7 @@ int bi_expected_counts(bi_ctx* c, int64_t P, const double* z, const double* rate
     const std::vector<int64_t> live = screen_points(c, P, z, rate_scale, nullptr, nullptr,
                                                     [&](int64_t p) { std::fill(out + p * per_item, out + (p + 1) * per_item, qnan); }, false);
     const int64_t n_items = (int64_t)live.size();
+    c->last_point_pieces = 0;
     if (n_items == 0) return BI_OK;
     // chunks of points: the device buffer holds at most ~64 MB of expectations (and a launch at most 65 535 items)
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_items, 32768), ((int64_t)1 << 23) / per_item));
@@ -113,6 +114,7 @@ int bi_expected_counts(bi_ctx* c, int64_t P, const double* z, const double* rate
         a.out = (double*)d_out.p;
         a.B = B; a.NS = NS; a.S = S; a.R = R;
         launch_morph_expect(c, a, ni);
+        ++c->last_point_pieces;
         // (the staging block of packed_upload and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, &live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_expected_counts: %s", hipGetErrorString(e));

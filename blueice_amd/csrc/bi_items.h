@@ -187,7 +187,8 @@ struct PointDerivs {
 // points its kernel's arguments at items i0 ... and launches it on the grid; the kernel assigns every (item, block, slot)
 // of partial / pflags, so the chunks, in order on one stream, share one chunk's buffers.  k_finish then adds the partials up
 // into out[perm] - slot_lg (status |= their flag bits when given).  Synchronises the stream.  fixed_nbx > 0: that many blocks
-// per item whatever the batch (the order in which an item's sums are added then does not depend on n_items).
+// per item whatever the batch (the order in which an item's sums are added then does not depend on n_items).  The chunks
+// launched are counted in last_point_pieces.
 template <class L>
 int run_item_chunks(bi_ctx* c, int64_t n_items, int max_tiles, int nsl, const int64_t* perm, const double* slot_lg, double* out,
                     int32_t* status, const char* what, L launch, int fixed_nbx = 0) {
@@ -200,9 +201,11 @@ int run_item_chunks(bi_ctx* c, int64_t n_items, int max_tiles, int nsl, const in
     if ((rc = dev_alloc(c, d_part, (size_t)part_items * nbx * nsl * sizeof(double))) ||
         (rc = dev_alloc(c, d_flag, (size_t)part_items * nbx * nsl * sizeof(unsigned)))) return rc;
     hipError_t e = hipSuccess;
+    c->last_point_pieces = 0;
     for (int64_t i0 = 0; i0 < n_items && e == hipSuccess; i0 += chunk) {
         const int64_t ni = std::min(chunk, n_items - i0);
         if ((rc = launch(i0, dim3((unsigned)nbx, (unsigned)ni), (double*)d_part.p, (unsigned*)d_flag.p))) return rc;
+        ++c->last_point_pieces;
         launch_finish(c, (const double*)d_part.p, (const unsigned*)d_flag.p, nbx, nsl, ni * nsl, perm + i0 * nsl, slot_lg + i0 * nsl,
                       out, status);
         e = hipGetLastError();

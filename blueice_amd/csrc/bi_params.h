@@ -128,6 +128,7 @@ const ParamDef kParams[] = {
     BI_P_RO("last_morph_nbx", c->last_morph_nbx),
     BI_P_RO("last_morph_items", c->last_morph_items),
     BI_P_RO("last_morph_fused", c->last_morph_fused),
+    BI_P_RO("last_point_pieces", c->last_point_pieces),
     BI_P_RO("narrow_ready", c->cnt8_valid ? 1 : 0),
     // "ready" = prepared AND in use as an evaluation path (with sparse = 0 at upload they serve split scans only)
     BI_P_RO("csr_ready", (c->csr_ready && (c->sparse_at_upload != 0 || !c->dense_counts)) ? 1 : 0),

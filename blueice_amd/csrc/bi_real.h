@@ -153,6 +153,7 @@ int bi_set_asimov_counts(bi_ctx* c, int64_t H, const double* z, const double* ra
         (rc = dev_upload(c, d_coef, coef)) || (rc = dev_upload(c, d_bad, bad)))
         return rc;
     hipError_t e = hipMemsetAsync(fresh.p, 0, (size_t)(H * Bp) * sizeof(double), c->stream);
+    c->last_point_pieces = 0;
     for (int64_t h0 = 0; h0 < H && e == hipSuccess; h0 += 65535) {
         const int64_t nh = std::min<int64_t>(65535, H - h0);
         RealExpectArgs a{};
@@ -163,6 +164,7 @@ int bi_set_asimov_counts(bi_ctx* c, int64_t H, const double* z, const double* ra
         a.bad = (int64_t*)d_bad.p + h0;
         a.B = c->B; a.Bp = Bp; a.NS = NS;
         launch_real_expect(c, a, nh);
+        ++c->last_point_pieces;
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(bad.data(), d_bad.p, (size_t)H * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream);

@@ -73,6 +73,7 @@ int bi_sourcewise_expected_counts(bi_ctx* c, int64_t P, const double* z, const d
             (void)hipStreamSynchronize(c->stream);
             return rc;
         }
+        ++c->last_point_pieces;
         // rows of stride Bp -> the caller's rows of stride B; runs of consecutive live points are consecutive in `out` too.  The
         // copies synchronise: d_out is reused by the next sub-batch
         hipError_t e = hipGetLastError();
@@ -172,7 +173,7 @@ int bi_sourcewise_generate_toys(bi_ctx* c, int64_t H, const double* z, const dou
         dev_free(fresh);
         return rc;
     }
-    for (int64_t h0 = 0; h0 < H && !rc; h0 += kSwLaunchItems)
+    for (int64_t h0 = 0; h0 < H && !rc; h0 += kSwLaunchItems, ++c->last_point_pieces)
         rc = sourcewise_expect_rows(c, b, h0, std::min(kSwLaunchItems, H - h0), false, (double*)d_mu.p + h0 * Bp, false, who);
     hipError_t e = hipSuccess;
     if (!rc) {

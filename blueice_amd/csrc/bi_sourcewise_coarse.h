@@ -71,6 +71,7 @@ int bi_sourcewise_expected_coarse(bi_ctx* c, int64_t P, const double* z, const d
             (void)hipStreamSynchronize(c->stream);
             return fail(c, BI_ERR_INVALID, "%s: no kernel variant for %d source slots with %d own axes", who, b.SC, b.EM);
         }
+        ++c->last_point_pieces;
         // (d_partial and d_out are reused by the next chunk: the download synchronises)
         const hipError_t e = download_live_runs(c, &b.live[(size_t)i0], ni, (const double*)d_out.p, per_item, out, hipGetLastError());
         if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
@@ -88,6 +89,7 @@ int bi_sourcewise_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, do
     for (int64_t i = 0; dataset && i < n; ++i)
         if (dataset[i] < 0 || dataset[i] >= m.T)
             return fail(c, BI_ERR_INVALID, "%s: dataset %lld outside [0,%lld)", who, (long long)dataset[i], (long long)m.T);
+    c->last_point_pieces = 0;
     if (n == 0) return BI_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const bi_ctx::Coarse& q = c->sw_coarse;
@@ -103,6 +105,7 @@ int bi_sourcewise_coarse_counts(bi_ctx* c, int64_t n, const int64_t* dataset, do
         PackedUpload pu;
         if ((rc = packed_upload(c, {{first.data(), (size_t)ni * sizeof(int64_t)}, {ones.data(), (size_t)ni * sizeof(double)}}, 0, pu))) return rc;
         coarse_launch(c, q, (const double*)m.counts.p, pu.dev<int64_t>(0), pu.dev<double>(1), 1, 1, 1, ni, (double*)d_partial.p, (double*)d_out.p);
+        ++c->last_point_pieces;
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(out + i0 * q.C, d_out.p, (size_t)(ni * q.C) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);

@@ -144,7 +144,7 @@ int bi_sourcewise_set_asimov_counts(bi_ctx* c, int64_t H, const double* z, const
     DevBuf fresh;                                    // the old store stays until everything has succeeded
     if ((rc = dev_alloc(c, fresh, (size_t)H * (size_t)Bp * sizeof(double)))) return rc;
     // k_sourcewise_expect writes whole rows of stride Bp, the pad bins behind B included (zeros: the templates are zero there)
-    for (int64_t h0 = 0; h0 < H && !rc; h0 += kSwLaunchItems)
+    for (int64_t h0 = 0; h0 < H && !rc; h0 += kSwLaunchItems, ++c->last_point_pieces)
         rc = sourcewise_expect_rows(c, b, h0, std::min(kSwLaunchItems, H - h0), false, (double*)fresh.p + h0 * Bp, false, who);
     hipError_t e = rc ? hipSuccess : hipGetLastError();
     // an expectation that is not finite is no dataset (the rates and templates are >= 0: it cannot be negative); the rows come to

@@ -1044,6 +1044,13 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total, dense_counts (the resident datasets are held as dense rows; 0: as non-empty-bin lists only, device-generated toys), coarse_cells (cells of the coarse binning set by bi_set_coarse_binning, 0: none);
  *            last_morph_nbx / last_morph_items / last_morph_fused (the most recent k_morph_reduce or k_morph_single launch: blocks per
  *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it);
+ *            last_point_pieces (the device pieces that the most recent per-point entry point cut its live items into on the host:
+ *            launches of at most 65 535 or 32 768 items, within sub-batches of about 2^23 doubles in flight -- summed over the
+ *            sub-batches and Gram panels of a source-wise call.  Set by every source-wise evaluation and by the calls that write
+ *            bins or cells -- bi_expected_counts, bi_expected_coarse, bi_expected_coarse_jacobian, bi_coarse_counts,
+ *            bi_set_asimov_counts and their bi_sourcewise_ forms, where bi_sourcewise_generate_toys counts the launches over its
+ *            truths --, 0 after such a call with no live item; the grid model's item-kernel evaluations (the host route of
+ *            bi_eval_grad, bi_eval_hess, bi_eval_fisher, bi_eval_gof, bi_eval_real) set it when they launch);
  *            last_scan_nslots / last_valid_nslots / last_scan_resident (waves per cell the planner chose for the scan kernels of
  *            the last plan, and the resident blocks per CU it sized them by), last_toy_method (1 = event by event);
  *            last_scan_groups / last_scan_max_items (groups of work items of the last scan LAUNCH and the items of the longest
