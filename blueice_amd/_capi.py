@@ -90,6 +90,7 @@ SIGNATURES = {
     'bi_sourcewise_download_counts': (C.c_int, [_p, _i64, _p]),
     'bi_sourcewise_set_coarse_binning': (C.c_int, [_p, C.c_int, _p, _p, _p, C.POINTER(_i64)]),
     'bi_sourcewise_expected_coarse': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p, _p]),
+    'bi_sourcewise_expected_coarse_jacobian': (C.c_int, [_p, _i64, _p, _p, C.c_int, _p, _p, _p]),
     'bi_sourcewise_coarse_counts': (C.c_int, [_p, _i64, _p, _p]),
     'bi_fit_batched_factored': (C.c_int, [_p, _i64, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, C.c_double, C.c_int, _p, _p, _p,
                                           _p, _p, _p, _p]),

@@ -11,7 +11,10 @@ derivatives of every cell in the user's parameters, summed over the cells in the
 into the uncertainty band of a coarse view and the impact of every parameter on it, and `coarse_information` gives the Fisher
 information of the likelihood at that binning, cell by cell.  Plain binned likelihoods; a source-wise model
 (`SourceWiseBinnedLogLikelihood`) has the binning, the expectation and the counts per cell (bi_sourcewise_expected_coarse,
-bi_sourcewise_coarse_counts) and with them the rebinned goodness of fit, not the derivatives.
+bi_sourcewise_coarse_counts) and with them the rebinned goodness of fit.  Its derivatives have spellings of their own --
+`sourcewise_coarse_jacobian` / `_points` (per source as well), `sourcewise_coarse_band`, `sourcewise_coarse_information`, over
+bi_sourcewise_expected_coarse_jacobian, whose device work does not grow with the number of shape parameters -- and the four
+grid-model names keep refusing a source-wise model, naming them.
 
     box = CoarseBinning(lf, keep=['cs1'], rebin={'cs1': 4}, ranges={'cs2': (2.0, 3.5)})
     mu = lf.expected_coarse(box, per_source=True, **best)            # [S, n_cs1 / 4]
@@ -27,7 +30,8 @@ from .hessian import user_jacobian
 
 __all__ = ['CoarseBinning', 'expected_coarse', 'expected_coarse_points', 'coarse_counts', 'coarse_statistics',
            'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
-           'propagate_covariance', 'information_per_cell']
+           'propagate_covariance', 'information_per_cell', 'sourcewise_coarse_jacobian', 'sourcewise_coarse_jacobian_points',
+           'sourcewise_coarse_band', 'sourcewise_coarse_information']
 
 EDGE_TOLERANCE = 1e-9          # an edge value must lie within this fraction of the bin's width of a fine edge
 
@@ -52,16 +56,51 @@ def _binned_for_coarse(lf, what, prepared=True, derivatives=False):
     """The gate of the coarse views proper (the binning, the expectation and the counts per cell): what `_binned_for_gof` lets
     through, or a `SourceWiseBinnedLogLikelihood`, whose context has the three calls under the same names
     (bi_sourcewise_set_coarse_binning, bi_sourcewise_expected_coarse, bi_sourcewise_coarse_counts).  derivatives=True: the call
-    needs the per-cell derivatives, which a source-wise model does not have.  `_binned_for_gof` itself keeps refusing the class."""
+    is one of the grid model's derivative functions, which a source-wise model has under spellings of its own (`_SOURCEWISE_SPELLINGS`).
+    `_binned_for_gof` itself keeps refusing the class."""
     from .source_wise import SourceWiseBinnedLogLikelihood
     if not isinstance(lf, SourceWiseBinnedLogLikelihood):
         return _binned_for_gof(lf, what, prepared)
     if derivatives:
-        raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): the derivatives of "
-                                  "its coarse views are not summed on the device" % what)
+        _refuse_sourcewise(lf, what)
     if prepared and not lf.is_prepared:
         raise NotPreparedException("%s requires you to first prepare the likelihood function using prepare()" % what)
     return lf
+
+
+# the grid model's derivative functions -> what a source-wise model has in their place, and back
+_SOURCEWISE_SPELLINGS = {
+    'expected_coarse_jacobian_points': 'sourcewise_coarse_jacobian_points(lf, binning, points, per_source=)',
+    'expected_coarse_jacobian': 'sourcewise_coarse_jacobian(lf, binning, per_source=, **params)',
+    'expected_coarse_band': 'sourcewise_coarse_band(lf, binning, names, covariance, **params)',
+    'coarse_information': 'sourcewise_coarse_information(lf, binning, **truth)',
+}
+_GRID_SPELLINGS = {
+    'sourcewise_coarse_jacobian_points': 'expected_coarse_jacobian_points(lf, binning, points)',
+    'sourcewise_coarse_jacobian': 'expected_coarse_jacobian(lf, binning, **params)',
+    'sourcewise_coarse_band': 'expected_coarse_band(lf, binning, names, covariance, **params)',
+    'sourcewise_coarse_information': 'coarse_information(lf, binning, **truth)',
+}
+
+
+def _refuse_sourcewise(lf, what):
+    """NotImplementedError for a source-wise model in one of the grid model's derivative functions, naming the spelling that works;
+    any other likelihood passes (its own gates follow)"""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if isinstance(lf, SourceWiseBinnedLogLikelihood):
+        raise NotImplementedError("%s is the grid model's spelling and is not available for a source-wise model "
+                                  "(SourceWiseBinnedLogLikelihood); call blueice_amd.coarse.%s" % (what, _SOURCEWISE_SPELLINGS[what]))
+
+
+def _sourcewise_prepared(lf, binning, what):
+    """The gate of the `sourcewise_coarse_*` functions, before any device work: a prepared `SourceWiseBinnedLogLikelihood`
+    (NotImplementedError naming the grid spelling for anything else, NotPreparedException for an unprepared one) and a
+    `CoarseBinning` (TypeError), which becomes the binning of the likelihood's context."""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if not isinstance(lf, SourceWiseBinnedLogLikelihood):
+        raise NotImplementedError("%s needs a source-wise model (SourceWiseBinnedLogLikelihood), not a %s; for a BinnedLogLikelihood "
+                                  "call blueice_amd.coarse.%s" % (what, type(lf).__name__, _GRID_SPELLINGS[what]))
+    return _prepared(lf, binning, what)
 
 
 def _edge_index(name, fine, value):
@@ -222,6 +261,7 @@ def expected_coarse_jacobian_points(lf, binning, points, livetime_days=None):
 def expected_coarse_jacobian(lf, binning, livetime_days=None, **params):
     """`expected_coarse_jacobian_points` at one point (parameter values; absent parameters at their defaults) ->
     (names [F], mu [*binning.shape], J [F, *binning.shape])."""
+    _refuse_sourcewise(lf, 'expected_coarse_jacobian')
     names, mu, J = expected_coarse_jacobian_points(lf, binning, {k: np.array([v], dtype=float) for k, v in params.items()},
                                                    livetime_days=livetime_days)
     return names, mu[0], J[0]
@@ -257,6 +297,7 @@ def expected_coarse_band(lf, binning, names, covariance, livetime_days=None, **p
     ones) -> (mu [*binning.shape], sigma [*binning.shape], impacts: OrderedDict name -> [*binning.shape]), by
     `propagate_covariance` of `expected_coarse_jacobian` -- one device call.  Linear propagation: the band of a model whose
     cells are far from linear over one standard deviation is the posterior's (`expected_coarse_points` over samples)."""
+    _refuse_sourcewise(lf, 'expected_coarse_band')
     all_names, mu, J = expected_coarse_jacobian(lf, binning, livetime_days=livetime_days, **params)
     sigma, impacts = propagate_covariance(all_names, J, names, covariance)
     return mu, sigma, impacts
@@ -278,7 +319,63 @@ def coarse_information(lf, binning, livetime_days=None, **truth):
     I_C = J_C J_C^T / mu_C (`information_per_cell` of `expected_coarse_jacobian`), no priors.  Its sum over the cells is what
     an analysis in those cells can know; with the identity binning that is `fisher_information(priors=False)`, and no
     rebinning adds to it.  Where the cells show which part of the analysis space constrains which parameter."""
+    _refuse_sourcewise(lf, 'coarse_information')
     names, mu, J = expected_coarse_jacobian(lf, binning, livetime_days=livetime_days, **truth)
+    info, unbounded = information_per_cell(J, mu)
+    return names, info, unbounded
+
+
+def sourcewise_coarse_jacobian_points(lf, binning, points, per_source=False, livetime_days=None):
+    """`expected_coarse_jacobian_points` for a prepared `SourceWiseBinnedLogLikelihood` -> (names [F], mu [P, *binning.shape],
+    J [P, F, *binning.shape]), or with per_source (names, mu [P, S, *binning.shape], J [P, S, F, *binning.shape]): every source's
+    cells and their derivatives, J[p, s, f] = d mu_s,C / d names[f] -- an impact table per component.  names and the chain rule
+    to the user's parameters are those of the grid model (`hessian.user_jacobian`; with per_source the same U is applied to every
+    source's block).  On the device one pass over the point's rows sums the sources' basis columns per cell
+    (bi_sourcewise_expected_coarse_jacobian); the contraction to the d + S derivatives is the host's, so the number of shape
+    parameters does not enter the device work and has no limit but the model's.  The total mu has the bits of
+    `expected_coarse_points`; the per-source mu equals its per-source form to rounding.  A point outside the anchor box or with
+    unphysical rates is nan throughout."""
+    return _sourcewise_jacobian(lf, binning, points, per_source, livetime_days, 'sourcewise_coarse_jacobian_points')
+
+
+def _sourcewise_jacobian(lf, binning, points, per_source, livetime_days, what):
+    """`sourcewise_coarse_jacobian_points` behind the gate of the public function `what`: one gate, one context call"""
+    _sourcewise_prepared(lf, binning, what)
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    P = len(z)
+    mu, jac, _ = lf.ctx.expected_coarse_jacobian(binning.n_cells, z if z.shape[1] else None, scale, per_source=per_source)
+    mult, L, eff, eff_axis, rate_sources = lf._chain_rule_terms(points, P, livetime_days)
+    U = user_jacobian(P, z.shape[1], scale.shape[1], mult, L, eff, eff_axis, rate_sources)
+    J = np.einsum('pfk,pskc->psfc', U, jac) if per_source else np.einsum('pfk,pkc->pfc', U, jac)
+    return lf._parameter_names(), mu.reshape(mu.shape[:-1] + binning.shape), J.reshape(J.shape[:-1] + binning.shape)
+
+
+def sourcewise_coarse_jacobian(lf, binning, per_source=False, livetime_days=None, **params):
+    """`sourcewise_coarse_jacobian_points` at one point (parameter values; absent parameters at their defaults) ->
+    (names [F], mu [(S,) *binning.shape], J [(S,) F, *binning.shape])."""
+    return _sourcewise_one(lf, binning, params, per_source, livetime_days, 'sourcewise_coarse_jacobian')
+
+
+def _sourcewise_one(lf, binning, params, per_source, livetime_days, what):
+    names, mu, J = _sourcewise_jacobian(lf, binning, {k: np.array([v], dtype=float) for k, v in params.items()}, per_source,
+                                        livetime_days, what)
+    return names, mu[0], J[0]
+
+
+def sourcewise_coarse_band(lf, binning, names, covariance, livetime_days=None, **params):
+    """`expected_coarse_band` for a prepared `SourceWiseBinnedLogLikelihood`: (names [K], covariance [K, K]) as
+    `inference.hesse(lf, ...)` / `inference.expected_covariance(lf, ...)` return them, `params` the point ->
+    (mu [*binning.shape], sigma [*binning.shape], impacts: OrderedDict name -> [*binning.shape]) by `propagate_covariance` of
+    `sourcewise_coarse_jacobian` -- one device call for all parameters."""
+    all_names, mu, J = _sourcewise_one(lf, binning, params, False, livetime_days, 'sourcewise_coarse_band')
+    sigma, impacts = propagate_covariance(all_names, J, names, covariance)
+    return mu, sigma, impacts
+
+
+def sourcewise_coarse_information(lf, binning, livetime_days=None, **truth):
+    """`coarse_information` for a prepared `SourceWiseBinnedLogLikelihood` -> (names [F], I [F, F, *binning.shape],
+    unbounded [F, *binning.shape] bool): `information_per_cell` of `sourcewise_coarse_jacobian`, no priors."""
+    names, mu, J = _sourcewise_one(lf, binning, truth, False, livetime_days, 'sourcewise_coarse_information')
     info, unbounded = information_per_cell(J, mu)
     return names, info, unbounded
 

@@ -22,12 +22,14 @@
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
 //     tu_sourcewise_coarse.hip   k_sourcewise_coarse (coarse views of a source-wise model; finished by tu_coarse.hip's kernels)   bi_k_sourcewise_coarse.h
+//     tu_sourcewise_coarse_jac.hip   k_sourcewise_coarse_jac (the per-cell sums behind the derivatives of those views)   bi_k_sourcewise_coarse_jac.h
 //     tu_fisher.hip       k_morph_fisher (expected information of one point per item, no data)   bi_k_fisher.h
 //     tu_toys.hip         the toy-MC evaluation kernels (k_morph_logmu*, k_dataset_dot*, k_dataset_finish*, k_tm_*)   bi_k_toys.h
 //     tu_prim.hip         the hand-written sorts and scans (behind plain functions)                  bi_prim.h
 // bi_k_item.h is the device skeleton the per-point item kernels share (tile walk, column sums, block reduction, expectation
 // chain): included by bi_k_hess.h, bi_k_fisher.h, bi_k_real.h, bi_k_gof.h, bi_k_bbgrad.h, bi_k_sets.h, bi_k_coarse.h,
-// bi_k_factored.h and (through it) bi_k_factored_curv.h and bi_k_sourcewise_real.h, and bi_k_sourcewise.h (which shares gof_terms, bi_k_gof_terms.h, with bi_k_gof.h).
+// bi_k_factored.h and (through it) bi_k_factored_curv.h and bi_k_sourcewise_real.h, and bi_k_sourcewise.h (which shares gof_terms, bi_k_gof_terms.h, with bi_k_gof.h; bi_k_sourcewise_coarse.h and
+// bi_k_sourcewise_coarse_jac.h include it).
 // gfx950 only; no kernel is defined in two translation units.
 #pragma once
 
@@ -165,6 +167,10 @@ void launch_coarse_finish(bi_ctx* c, const CoarseArgs& a);
 // k_sourcewise_coarse<SC, EM, PS> + k_coarse_finish: the expectation of n_items (<= 65 535) points of a source-wise model summed over
 // the groups of a coarse binning, a.g.R = 1 (the total) or S (per source: PS); BI_ERR_INVALID for an (SC, EM) without a variant
 int launch_sourcewise_coarse(bi_ctx* c, int SC, int EM, bool per_source, const SourcewiseCoarseArgs& a, int64_t n_items);
+// k_sourcewise_coarse_jac<SC, EM> + k_coarse_finish: the sums of mu_b and of the basis columns tau_s,b, ups_s,j,b of n_items (<= 65 535)
+// points of a source-wise model over the groups of a coarse binning; a.g.R = K live columns, slot -> group by a.group;
+// BI_ERR_INVALID for an (SC, EM) without a variant
+int launch_sourcewise_coarse_jac(bi_ctx* c, int SC, int EM, const SourcewiseCoarseJacArgs& a, int64_t n_items);
 // k_coarse_list + k_coarse_table: the non-empty-bin lists of n (<= 65 535) datasets into the cells, out [n][C] (device memory)
 void launch_coarse_list(bi_ctx* c, const CoarseListArgs& a, int64_t n, double* out);
 // ---- the toy-MC evaluation kernels (bi_k_toys.h).  No launcher times its kernel: the host half (bi_toys.h) opens the EventScopes.

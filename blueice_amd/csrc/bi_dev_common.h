@@ -220,6 +220,16 @@ struct SourcewiseCoarseArgs {
     CoarseArgs g;
 };
 
+// k_sourcewise_coarse_jac (bi_k_sourcewise_coarse_jac.h): the same with FacBatch's descriptors of order 1 (coef's columns 1 .. EM
+// are read too) and the map from k_morph_factored's result slots ([0] mu, [1 + s] tau_s, [1 + SC + s EM + j] ups_s,j) to the
+// g.R = K = 1 + S + sum_s e_s groups that are written; -1: a padding slot (s >= S or j >= e_s), never written
+constexpr int kCoarseJacSlots = 33;          // 1 + 8 (1 + 3)
+struct SourcewiseCoarseJacArgs {
+    FactoredArgs f;
+    CoarseArgs g;
+    signed char group[kCoarseJacSlots];
+};
+
 // k_coarse_list (bi_k_coarse.h): the non-empty-bin lists of n datasets into 64-bit integer tables [n][C]
 struct CoarseListArgs {
     const int32_t* nz_idx;     // fine bin of every entry

@@ -46,12 +46,15 @@ Coarse views -- projections, a rebinned analysis space, a signal box -- are summ
 take a prepared source-wise model and a `CoarseBinning` made for it, and `gof_statistics` / `goodness_of_fit` of
 blueice_amd.inference take that binning as `binning=` (the toys are still fitted on the fine bins).  A projection comes down as
 its cells, not as every fine bin.  The bound lf.expected_coarse, lf.expected_coarse_points and lf.coarse_counts stay refused and
-name these spellings.  The derivatives of coarse views (expected_coarse_jacobian*, expected_coarse_band, coarse_information) are
-not available.
+name these spellings.  The derivatives of coarse views are summed in the same kind of pass (bi_sourcewise_expected_coarse_jacobian:
+the per-cell sums of the sources' basis columns, contracted on the host, so the number of shape parameters does not enter the
+device work), per source as well: blueice_amd.coarse.sourcewise_coarse_jacobian / _points, sourcewise_coarse_band and
+sourcewise_coarse_information.  The grid model's names (expected_coarse_jacobian*, expected_coarse_band, coarse_information), as
+functions of blueice_amd.coarse and as bound names, stay refused and name those spellings.
 
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, eval_toys*, grids, derivatives of coarse views, Hessians on an Asimov view and the ensemble sampler.
+full_output calls, eval_toys*, grids, Hessians on an Asimov view and the ensemble sampler.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -81,7 +84,8 @@ def _find_cell(g, z):
 class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
-    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, coarse_counts,
+    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, expected_coarse_jacobian,
+    coarse_counts,
     generate_toys_points, download_counts, set_param / get_param,
     fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
     real_count_sets, download_real_counts, eval_real, fit_batched_real) -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
@@ -279,6 +283,22 @@ class SourceWiseContext:
         dev._check(dev._lib.bi_sourcewise_expected_coarse(dev._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(out), ptr(status)))
         return out, status
 
+    def expected_coarse_jacobian(self, n_cells, z, rate_scale=None, per_source=False):
+        """The expectation per cell of the coarse binning and its first derivatives over theta = (z [d], then rate_scale [S])
+        (bi_sourcewise_expected_coarse_jacobian) -> (mu [P, C], jac [P, d + S, C], status [P]), or with per_source
+        (mu [P, S, C], jac [P, S, d + S, C]): the single terms of every source, which summed over the sources in ascending order
+        in long double give the total rows bit for bit.  The total mu has the bits of `expected_coarse`.  nan throughout and the
+        status bit for points outside the anchor box or with unphysical rates.  No counts are needed."""
+        dev = self._dev
+        P, z, rate_scale, _ = self._point_args(z, rate_scale, None)
+        C_, F = int(n_cells), self.d + self.S
+        mu = np.empty((P, self.S, C_) if per_source else (P, C_), dtype=np.float64)
+        jac = np.empty((P, self.S, F, C_) if per_source else (P, F, C_), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_sourcewise_expected_coarse_jacobian(dev._h, P, ptr(z), ptr(rate_scale), 1 if per_source else 0, ptr(mu),
+                                                                   ptr(jac), ptr(status)))
+        return mu, jac, status
+
     def coarse_counts(self, n_cells, datasets=None):
         """The counts of the store's datasets -- uploaded, or toys drawn on the device -- per cell of the coarse binning
         (bi_sourcewise_coarse_counts) -> [n, C]; datasets: indices [n] (None: all T)."""
@@ -410,6 +430,10 @@ _REFUSED_SPELLINGS = {
     'expected_coarse': "blueice_amd.coarse.expected_coarse(lf, binning, **params)",
     'expected_coarse_points': "blueice_amd.coarse.expected_coarse_points(lf, binning, points)",
     'coarse_counts': "blueice_amd.coarse.coarse_counts(lf, binning, datasets=)",
+    'expected_coarse_jacobian': "blueice_amd.coarse.sourcewise_coarse_jacobian(lf, binning, per_source=, **params)",
+    'expected_coarse_jacobian_points': "blueice_amd.coarse.sourcewise_coarse_jacobian_points(lf, binning, points, per_source=)",
+    'expected_coarse_band': "blueice_amd.coarse.sourcewise_coarse_band(lf, binning, names, covariance, **params)",
+    'coarse_information': "blueice_amd.coarse.sourcewise_coarse_information(lf, binning, **truth)",
     'asimov': "blueice_amd.asimov.asimov(lf, **truth)",
     'real_data': "blueice_amd.asimov.real_data(lf, counts)",
     'expected_upper_limit': "blueice_amd.inference.expected_upper_limit(lf, target, bound)",

@@ -1,6 +1,7 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--measure | --measure-toys | --measure-asimov | --measure-coarse [--rounds 31]]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band]
+        [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
 grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
@@ -42,6 +43,15 @@ real-valued store and in the ordinary one), at 64 points per call and at one, an
 --measure-coarse times, at the same source-wise shape, bi_sourcewise_expected_coarse (the projection on the first analysis axis, the
 10^3 rebinning and everything in one cell; total and per source) against bi_sourcewise_expected_counts plus the NumPy reduction it
 replaces, and k_sourcewise_coarse with its finish kernel alone, by device events, against k_sourcewise_expect on the same points.
+
+--band prints, after the fit (2) and inference.hesse over all twelve parameters, the post-fit uncertainty band of the projection on
+the first analysis axis and the impact table of a signal box -- which nuisance moves which source's events in the box by how much
+-- from ONE device call each (blueice_amd.coarse.sourcewise_coarse_band, sourcewise_coarse_jacobian(per_source=True);
+bi_sourcewise_expected_coarse_jacobian), beside the same numbers from central differences of expected_coarse_points.
+
+--measure-coarse-jacobian times, at the same source-wise shape, bi_sourcewise_expected_coarse_jacobian (total and per source) for the x0
+projection, the 10^3 rebinning, one cell and a box, against bi_sourcewise_expected_coarse on the same points and against the
+(2 F + 1) P-point bi_sourcewise_expected_coarse call of the central differences it replaces, and the kernel pairs alone by device events.
 """
 import argparse
 import time
@@ -55,6 +65,9 @@ ap.add_argument('--measure', action='store_true', help='time bi_eval_factored ag
 ap.add_argument('--measure-toys', action='store_true', help='time the goodness-of-fit, expected-counts and toy-generator calls')
 ap.add_argument('--measure-asimov', action='store_true', help='time bi_eval_sourcewise_real against bi_eval_factored on the same rows')
 ap.add_argument('--measure-coarse', action='store_true', help='time bi_sourcewise_expected_coarse against expected_counts + the NumPy reduction')
+ap.add_argument('--measure-coarse-jacobian', action='store_true',
+                help='time bi_sourcewise_expected_coarse_jacobian against bi_sourcewise_expected_coarse and the central differences it replaces')
+ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
 ap.add_argument('--rounds', type=int, default=31)
@@ -315,6 +328,158 @@ def measure_coarse():
     fac.close()
 
 
+def measure_coarse_jacobian():
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    F = d + S
+    nb = args.measure_bins
+    n_a, B, P = 5, nb ** 3, 64
+    Bp = (B + 511) // 512 * 512
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    z = rng.uniform(0.1, 0.9, (P, d)) + rng.integers(-2, 2, (P, d))              # strictly inside cells: the differences stay in them
+    r = rng.uniform(0.8, 1.2, (P, S))
+    print('source-wise model: %d rows, %.2f GB resident (it stays in the 256 MB Infinity Cache: every figure below is cache-assisted)'
+          % (S * n_a, S * n_a * Bp * 8 / 1e9), flush=True)
+    # the points of central differences: every point itself and displaced along each of the F parameters, both ways
+    hz, hr = 1e-3, 1e-3
+    zz, rr = np.tile(z, (2 * F + 1, 1)), np.tile(r, (2 * F + 1, 1))
+    for j in range(F):
+        for k, sign in enumerate((1.0, -1.0)):
+            at = slice((1 + 2 * j + k) * P, (2 + 2 * j + k) * P)
+            if j < d:
+                zz[at, j] += sign * hz
+            else:
+                rr[at, j - d] += sign * hr
+    shape = (nb, nb, nb)
+    fine, whole = np.arange(nb + 1), np.array([0, nb])
+    k = max(nb // 10, 1)
+    tens = np.array(list(range(0, nb, k)) + [nb])
+    box = np.array([nb // 4, max(3 * nb // 4, nb // 4 + 1)])
+    views = [('x0 projection (%d cells)' % nb, [fine, whole, whole]), ('%d^3 rebinning' % (len(tens) - 1), [tens, tens, tens]),
+             ('everything in one cell', [whole, whole, whole]), ('a box of %d^3 bins' % (box[1] - box[0]), [box, box, box])]
+    dev = fac._dev
+    slower = []
+    for label, groups in views:
+        cells = fac.set_coarse_binning(shape, groups)
+        inside = np.prod([float(e[-1] - e[0]) / nb for e in groups])
+        gb = 2 * S * B * inside * 8 * P / 1e9         # the bins a call reads: two corner rows per source and point, inside the binning's ranges
+        mu, jac, _ = fac.expected_coarse_jacobian(cells, z, r)
+        mu_s, jac_s, _ = fac.expected_coarse_jacobian(cells, z, r, per_source=True)
+        stencil = fac.expected_coarse(cells, zz, rr)[0].reshape(2 * F + 1, P, cells)
+        diff = np.stack([(stencil[1 + 2 * j] - stencil[2 + 2 * j]) / (2 * (hz if j < d else hr)) for j in range(F)], axis=1)
+        print('%s: mu bitwise bi_sourcewise_expected_coarse: %s; max |jac - central difference| %.2g of the largest entry; max |sum of the '
+              'sources - total| %.2g of it' % (label, np.array_equal(mu, stencil[0]), np.max(np.abs(jac - diff)) / np.max(np.abs(diff)),
+                                               np.max(np.abs(jac_s.sum(axis=1) - jac)) / np.max(np.abs(jac))), flush=True)
+        calls = [('expected_coarse_jacobian, %s' % label, lambda: fac.expected_coarse_jacobian(cells, z, r)),
+                 ('expected_coarse_jacobian per source, %s' % label, lambda: fac.expected_coarse_jacobian(cells, z, r, per_source=True)),
+                 ('expected_coarse, %s' % label, lambda: fac.expected_coarse(cells, z, r)),
+                 ('expected_coarse at (2 F + 1) P = %d points, %s' % (len(zz), label), lambda: fac.expected_coarse(cells, zz, rr))]
+        times = {name: [] for name, _ in calls}
+        for rnd in range(3 + args.rounds):              # three warm-up rounds; the calls alternate inside every round
+            for name, call in calls:
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 3:
+                    times[name].append(time.perf_counter() - t0)
+        for name, _ in calls:
+            print('%2d points per call, %-72s %s' % (P, name, quartiles(times[name])), flush=True)
+        med = [np.median(times[name]) for name, _ in calls]
+        print('    Jacobian / mu alone %.2f (per source %.2f); central differences / Jacobian %.2f' % (med[0] / med[2], med[1] / med[2], med[3] / med[0]))
+        if not med[0] < med[3]:
+            slower.append(label)
+        for name, call in (('k_sourcewise_coarse_jac + finish', calls[0][1]), ('k_sourcewise_coarse + finish', calls[2][1]),
+                           ('k_sourcewise_coarse + finish, (2 F + 1) P points', calls[3][1])):
+            dev.profile(True)
+            ks = []
+            for _ in range(args.rounds):
+                call()
+                ks.append(dev.profile_read()[1] * 1e-3)
+            dev.profile(False)
+            n_gb = gb * (2 * F + 1 if name.endswith('points') else 1)
+            print('%-50s kernels %s per call; %.2f GB of rows read -> %.2f TB/s' % (name, quartiles(ks), n_gb, n_gb / np.median(ks) / 1e3), flush=True)
+    print('the Jacobian call is faster than the central-difference call at every binning: %s' % ('yes' if not slower else 'NO (%s)' % ', '.join(slower)))
+    print('not measured: the other kernel classes (more sources, more own axes: up to 33 sums per lane in three passes through LDS), '
+          'shapes beyond the Infinity Cache, more shape parameters than sources own (they cost the host contraction alone)')
+    fac.close()
+
+
+def band():
+    from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood, coarse, inference
+    from blueice_amd.synthetic import many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins))
+    lf = SourceWiseBinnedLogLikelihood(conf)
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    lf.prepare()
+    np.random.seed(3)
+    lf.set_data(lf.base_model.simulate())
+    best, ll = inference.bestfit_device(lf)
+    cov_names, cov = inference.hesse(lf, best)
+    print('fit of %d parameters: max ll %.4f; covariance from the analytic Hessian (inference.hesse)' % (len(best), ll))
+    space = lf.base_model.config['analysis_space']
+    (x, ex), (y, ey) = [(str(n), np.asarray(e, dtype=float)) for n, e in space]
+    nb = args.bins
+
+    def differences(binning, per_source):
+        """central differences of expected_coarse_points around the fit, h = 1e-3 (of the value for a multiplier): 2 F points"""
+        h = {k: 1e-3 * (best[k] if k.endswith('_rate_multiplier') else 1.0) for k in cov_names}
+        pts = {k: np.concatenate([np.full(2, best[k]) + (np.array([h[f], -h[f]]) if f == k else 0.0) for f in cov_names]) for k in cov_names}
+        mu = coarse.expected_coarse_points(lf, binning, pts, per_source=per_source)
+        return np.stack([(mu[2 * i] - mu[2 * i + 1]) / (2 * h[k]) for i, k in enumerate(cov_names)])
+
+    # the post-fit band of the projection on the first analysis axis
+    proj = coarse.CoarseBinning(lf, keep=[x], rebin={x: max(nb // 10, 1)})
+    t0 = time.perf_counter()
+    mu, sigma, impacts = coarse.sourcewise_coarse_band(lf, proj, cov_names, cov, **best)
+    dt = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sigma_fd, _ = coarse.propagate_covariance(cov_names, differences(proj, False), cov_names, cov)
+    dt_fd = time.perf_counter() - t0
+    n = coarse.coarse_counts(lf, proj)[0]
+    print('post-fit band of the projection on %s (%d cells): one device call, %.4f s; from central differences (%d points), %.4f s'
+          % (x, proj.n_cells, dt, 2 * len(cov_names), dt_fd))
+    print('    %-16s %10s %10s %10s %12s' % (x, 'observed', 'expected', '+- band', 'differences'))
+    for c in range(proj.n_cells):
+        print('    [%5.2f, %5.2f) %10d %10.2f %10.3f %12.3f' % (proj.edges[0][c], proj.edges[0][c + 1], n[c], mu[c], sigma[c], sigma_fd[c]))
+    print('    largest impact per cell: ' + ', '.join(max(impacts, key=lambda k: abs(impacts[k][c])).replace('_rate_multiplier', '')
+                                                       for c in range(proj.n_cells)))
+
+    # the impact table of a signal box around the first source, per source: which nuisance moves which component by how much
+    q = max(nb // 5, 1)
+    box = coarse.CoarseBinning(lf, keep=[], ranges={x: (ex[q], ex[min(2 * q + q // 2 + 1, nb)]), y: (ey[q], ey[min(2 * q + q // 2 + 1, nb)])})
+    t0 = time.perf_counter()
+    all_names, mu_s, J_s = coarse.sourcewise_coarse_jacobian(lf, box, per_source=True, **best)
+    dt = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    J_fd = differences(box, True)                                                 # [F, S]
+    dt_fd = time.perf_counter() - t0
+    order = [all_names.index(k) for k in cov_names]
+    std = np.sqrt(np.diag(cov))
+    table = J_s[:, order] * std[None, :]                                          # [S, F]: the shift of source s when the parameter moves by its sigma
+    print('impact table of the box %s in [%.2f, %.2f), %s in [%.2f, %.2f): one device call, %.4f s; from central differences, %.4f s'
+          % (x, box.groups[0][0] / nb, box.groups[0][1] / nb, y, box.groups[1][0] / nb, box.groups[1][1] / nb, dt, dt_fd))
+    print('    expected in the box: ' + ', '.join('s%d %.2f' % (s, mu_s[s]) for s in range(4)) + '; total %.2f, observed %d'
+          % (mu_s.sum(), coarse.coarse_counts(lf, box)[0]))
+    print('    %-10s %8s ' % ('parameter', 'sigma') + ' '.join('%9s' % ('d s%d' % s) for s in range(4)) + ' %9s %12s' % ('d total', 'differences'))
+    for i, k in enumerate(cov_names):
+        print('    %-10s %8.4f ' % (k.replace('_rate_multiplier', ''), std[i]) + ' '.join('%9.3f' % table[s, i] for s in range(4))
+              + ' %9.3f %12.3f' % (table[:, i].sum(), J_fd[i].sum() * std[i]))
+    _, sigma_box, _ = coarse.sourcewise_coarse_band(lf, box, cov_names, cov, **best)
+    print('    post-fit uncertainty of the total in the box (with the correlations): +- %.3f' % float(sigma_box))
+
+
 def measure_asimov():
     from blueice_amd.source_wise import SourceWiseContext
     d = S = 4
@@ -438,6 +603,12 @@ if args.measure_coarse:
     raise SystemExit(0)
 if args.asimov:
     asimov_band()
+    raise SystemExit(0)
+if args.measure_coarse_jacobian:
+    measure_coarse_jacobian()
+    raise SystemExit(0)
+if args.band:
+    band()
     raise SystemExit(0)
 if args.measure_toys:
     measure_toys()

@@ -656,12 +656,28 @@ int bi_sourcewise_download_counts(bi_ctx* ctx, int64_t t, double* out /*[B]*/);
  *   bi_sourcewise_coarse_counts out [n][C]: the counts of datasets dataset[0 .. n) (NULL: all of them, n = T) of the store --
  *                               uploaded or drawn on the device -- in the cells; sums of integer counts are exact.  A dataset
  *                               outside [0, T): BI_ERR_INVALID.
- * The last two without a binning: BI_ERR_STATE.  No floating-point atomics; a repeated call is bitwise identical and a point's
+ *   bi_sourcewise_expected_coarse_jacobian   the cells and their first derivatives over theta = (z [d], then rate_scale [S]), the
+ *                               order of bi_eval_factored's gradient, in one pass over the point's rows.  With R = per_source ? S : 1
+ *                               and F = d + S: mu [P][R][C], jac [P][R][F][C].  per_source = 0: mu has the bits of
+ *                               bi_sourcewise_expected_coarse's total; jac[p][d + s] = M_s T_s and jac[p][i] = the sum over the
+ *                               sources s that own axis i (ascending) of rs_s (M_s Y_s,j + dM_s,j T_s), with T_s, Y_s,j the cell
+ *                               sums of tau_s,b and d tau_s,b / d z_i the device forms and M_s the source's rate at rate scale 1;
+ *                               an axis nobody owns has a row of exactly 0.0.  per_source = 1: mu[p][s] = r_s T_s (equal to
+ *                               bi_sourcewise_expected_coarse's per-source cells to rounding, not to the bit) and jac[p][s] holds
+ *                               the single terms of source s: every entry of another source's scale, or of an axis s does not
+ *                               own, is exactly 0.0, and the per-source rows summed over s in ascending order in long double
+ *                               reproduce the per_source = 0 rows bit for bit.  The contraction runs per cell on the host in long
+ *                               double; no limit on the columns beyond the model's own.  The screen and the status are
+ *                               bi_sourcewise_expected_coarse's; a dead point is nan throughout mu and jac.  mu or jac NULL with
+ *                               P > 0: BI_ERR_INVALID.  On an anchor the slopes are those of the cell the point is assigned to.
+ * The last three without a binning: BI_ERR_STATE.  No floating-point atomics; a repeated call is bitwise identical and a point's
  * cells do not depend on the batch it is evaluated in.  The real-valued store has no coarse view. */
 int bi_sourcewise_set_coarse_binning(bi_ctx* ctx, int k, const int32_t* n_fine, const int32_t* n_groups, const int32_t* bounds,
                                      int64_t* n_cells);
 int bi_sourcewise_expected_coarse(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source, double* out,
                                   int32_t* status);
+int bi_sourcewise_expected_coarse_jacobian(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, int per_source,
+                                           double* mu, double* jac, int32_t* status);
 int bi_sourcewise_coarse_counts(bi_ctx* ctx, int64_t n, const int64_t* dataset, double* out);
 
 /* ... and real-valued datasets of a source-wise model: Asimov data (n_b = mu_b(truth)) and weighted histograms, the layer that
