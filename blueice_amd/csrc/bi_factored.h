@@ -302,7 +302,8 @@ struct FacBatch {
     // One kernel over the live points: nsl result slots per item, perm / slot_lg [n][nsl] (device) where a slot's sum goes and
     // what k_finish subtracts from it.  The blocks of an item depend on the rows' length alone; sub-batches keep the partial
     // sums of one run_item_chunks call within kFacPartialDoubles.  launch(args, grid) -> error code.  last_point_pieces counts
-    // the chunks of every sub-batch of every run() of this batch (the curvature calls run once per Gram panel).
+    // the chunks of every sub-batch of every run() of this batch (the curvature calls run once per Gram panel);
+    // last_morph_nbx / last_morph_items / last_morph_fused (= 0) describe the grid of the most recent launch, as bi_grad.h's do.
     template <class L>
     int run(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
         const FactoredArgs a = args();
@@ -316,6 +317,7 @@ struct FacBatch {
                                                point_at(b, j0 + i0);
                                                b.partial = partial;
                                                b.pflags = pflags;
+                                               c->last_morph_nbx = grid.x; c->last_morph_items = grid.y; c->last_morph_fused = 0;
                                                return launch(b, grid);
                                            },
                                            nbx);

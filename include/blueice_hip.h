@@ -1059,7 +1059,11 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *            bi_sample_stretch planning refused its batch: 1 Beeston-Barlow points that need exact totals, 2 infinite rates of sources that may
  *            go negative; 0 otherwise -- how a caller tells the refusals that the host path answers from other BI_ERR_INVALID), tile_bins, padded_bins, n_scan_launches, n_toy_polled (bi_eval_datasets calls that returned on the completion word), tm_entry_bytes, events_sorted, n_valid_launches, n_sorted_scans, n_bb_exact, n_mail_resets, user_allocations, csr_ready, compact_ready, compact_sorted (the compacted copy is ordered by count), split_ready, ps_nonneg, nnz_total, dense_counts (the resident datasets are held as dense rows; 0: as non-empty-bin lists only, device-generated toys), coarse_cells (cells of the coarse binning set by bi_set_coarse_binning, 0: none);
  *            last_morph_nbx / last_morph_items / last_morph_fused (the most recent k_morph_reduce or k_morph_single launch: blocks per
- *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it);
+ *            work item, work items of the launch, and 1 if it finished through the mailbox, 0 if a finish kernel ran behind it;
+ *            the host route of bi_eval_grad sets them for its kernels, and every source-wise evaluation that adds up per-item
+ *            sums -- bi_eval_factored, bi_eval_sourcewise_gof, bi_eval_sourcewise_real, bi_eval_sourcewise_hess and
+ *            bi_eval_sourcewise_fisher, the last two once per Gram panel -- for the grid of its most recent launch, fused = 0:
+ *            the blocks per item there depend on the rows' length alone);
  *            last_point_pieces (the device pieces that the most recent per-point entry point cut its live items into on the host:
  *            launches of at most 65 535 or 32 768 items, within sub-batches of about 2^23 doubles in flight -- summed over the
  *            sub-batches and Gram panels of a source-wise call.  Set by every source-wise evaluation and by the calls that write
