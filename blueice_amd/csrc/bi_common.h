@@ -18,6 +18,8 @@
 //                         out), k_sourcewise_gof (its deviance + Pearson chi2 per item)      bi_k_sourcewise.h
 //     tu_sourcewise_real.hip   k_sourcewise_real (half-deviance + gradient sums of one point of a source-wise model against
 //                         real-valued counts per item)                                       bi_k_sourcewise_real.h
+//     tu_sourcewise_plan.hip   k_sourcewise_plan (staged points of a source-wise model -> status words and k_morph_factored's
+//                         descriptors, on the device)                                        bi_k_sourcewise_plan.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -130,6 +132,9 @@ int launch_sourcewise_gof(bi_ctx* c, int SC, int EM, const FactoredArgs& a, dim3
 // against the real-valued dataset a.counts + a.item_cnt[item] per item; classes and result slots (factored_slots) as
 // launch_morph_factored
 int launch_sourcewise_real(bi_ctx* c, int SC, int EM, bool grad, const FactoredArgs& a, dim3 grid, bool nt);
+// k_sourcewise_plan<SC>: the status words and k_morph_factored's value-order descriptors of a.n staged points of a source-wise model,
+// one thread per (point, source slot); BI_ERR_INVALID for another SC than 2, 4, 8
+int launch_sourcewise_plan(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

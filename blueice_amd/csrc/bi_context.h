@@ -164,6 +164,11 @@ struct bi_ctx {
         DevBuf real_counts;                          // [real_T][Bp], zero behind B
         int n_rows_point = 0;                        // rows one evaluation reads: sum_s 2^e_s
         int max_own = 0;                             // largest e_s
+        // the device planner's copy of the geometry (k_sourcewise_plan, bi_sourcewise_plan.h): one slab of anchors, anchor_off,
+        // n_own, own, own_stride, row_first, h_mus at geom_off[0 .. 7), uploaded by bi_factored_end; and of h_lgsum, uploaded
+        // wherever that changes (fac_sync_lgsum)
+        DevBuf geom, lgsum_dev;
+        size_t geom_off[7] = {};
     } fac;
 
     // the coarse binning of bi_set_coarse_binning (bi_coarse.h): tensor-product groups of fine bins, b = r L + x with L the

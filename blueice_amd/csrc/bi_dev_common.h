@@ -169,6 +169,41 @@ struct FactoredArgs {
     const double* chain;       // [items][SC][1 + EM] per source: M_s, then rs_s d M_s / d (own axis j)
     unsigned lead;             // bit s * 3 + j: slot (s, j) is the first slot of its axis (the one that counts for it)
     signed char ax[8][3];      // the axis of slot (s, j), -1 for none
+    // k_morph_factored<.., GRAD = false, ..> alone: items planned on the device (k_sourcewise_plan).  NULL on every other path.
+    const unsigned* live;      // [items] 0: a rejected point -- its blocks return at once: no row is read, no partial posted
+};
+
+// k_sourcewise_plan (bi_k_sourcewise_plan.h): the device copy of what fac_geometry and FacSource::at read (bi_factored.h) ...
+struct SourcewiseGeom {
+    const double* anchors;     // the d axes' anchors back to back
+    const int32_t* anchor_off; // [d + 1] where an axis' anchors start
+    const int32_t* n_own;      // [S] e_s
+    const int32_t* own;        // [S][3] the owned axes, ascending
+    const int64_t* own_stride; // [S][3] row stride of every owned axis
+    const int64_t* row_first;  // [S] first row of source s
+    const double* mus;         // [rows] the anchors' rates
+    const double* lgsum;       // [T] sum_b lgamma(n_b + 1) of every dataset
+    int64_t T, Bp;
+    int d, S;
+};
+// ... and n staged points in VarMap's layouts -> their status words and FacBatch's value-order descriptors
+struct SourcewisePlanArgs {
+    SourcewiseGeom g;
+    const double* z;           // [n][d]
+    const double* rs;          // [n][S]
+    const int64_t* ds;         // [n]
+    int64_t n;
+    int NR, W;                 // rows per item, coefficient columns per row (1 + EM)
+    int e[8];                  // own axes of every source slot, -1: padded (FactoredArgs::e)
+    int32_t* status;           // [n]
+    unsigned* live;            // [n] status == 0
+    int64_t* rowoff;           // [n][NR]
+    double* coef;              // [n][NR][W]
+    double* rates;             // [n][SC]
+    int64_t* cnt_off;          // [n]
+    double* slot_lg;           // [n]
+    int64_t* perm;             // [n] k_finish's: i, or -1 for a rejected point (neither summed nor written)
+    double* out;               // [n] where k_finish writes the results: the planner writes a rejected point's -inf
 };
 
 // k_sourcewise_expect (bi_k_sourcewise.h): the descriptors of FactoredArgs (rowoff, coef [items][NR][1 + EM], rates, e; no

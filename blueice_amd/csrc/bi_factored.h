@@ -21,7 +21,8 @@
 // bi_eval_factored is the per-item host path of bi_items.h with descriptors of its own (FacBatch, which the curvature calls of
 // bi_factored_curv.h share): screen, fill on host threads, one packed upload, run_item_chunks + k_finish.  The blocks per item
 // depend on the rows' length alone (not on the batch), so a point's sums are added in the same order whatever batch it is
-// evaluated in.
+// evaluated in.  The loops over staged points that make their work items on the device instead (k_sourcewise_plan over the device
+// copy of the geometry, fac_upload_geometry / fac_sync_lgsum below): bi_sourcewise_plan.h.
 #pragma once
 
 namespace {
@@ -159,6 +160,40 @@ int fac_counts_lgsum(bi_ctx* c, const char* who, const double* counts, int64_t T
     if (e == hipSuccess) e = hipMemcpyAsync(lgsum.data(), lg.p, (size_t)T * sizeof(double), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     else (void)hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    return BI_OK;
+}
+
+// The device planner's copy (k_sourcewise_plan, bi_sourcewise_plan.h) of what fac_geometry and FacSource::at read, one slab:
+// anchors, anchor_off [d + 1], n_own [S], own [S][3], own_stride [S][3], row_first [S], h_mus [rows] at geom_off[0 .. 7).
+// Waits for the copy (the staging block is the context's).
+int fac_upload_geometry(bi_ctx* c) {
+    bi_ctx::Factored& m = c->fac;
+    std::vector<double> anchors;
+    std::vector<int32_t> anchor_off(1, 0), n_own(m.n_own.begin(), m.n_own.end()), own(m.own.begin(), m.own.end());
+    for (const auto& g : m.grid) {
+        anchors.insert(anchors.end(), g.begin(), g.end());
+        anchor_off.push_back((int32_t)anchors.size());
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    PackedUpload pu;
+    int rc = packed_upload(c, {{anchors.data(), anchors.size() * sizeof(double)}, {anchor_off.data(), anchor_off.size() * sizeof(int32_t)},
+                               {n_own.data(), n_own.size() * sizeof(int32_t)}, {own.data(), own.size() * sizeof(int32_t)},
+                               {m.own_stride.data(), m.own_stride.size() * sizeof(int64_t)}, {m.row_first.data(), (size_t)m.S * sizeof(int64_t)},
+                               {m.h_mus.data(), m.h_mus.size() * sizeof(double)}},
+                           0, pu, &m.geom);
+    if (rc) return rc;
+    for (size_t q = 0; q < 7; ++q) m.geom_off[q] = pu.off[q];
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BI_OK;
+}
+
+// ... and of h_lgsum, wherever that changes: a planned evaluation after new counts or toys must not subtract the old sums
+int fac_sync_lgsum(bi_ctx* c, const char* who) {
+    bi_ctx::Factored& m = c->fac;
+    int rc = dev_upload(c, m.lgsum_dev, m.h_lgsum);
+    if (rc) return rc;
+    const hipError_t e = hipStreamSynchronize(c->stream);      // (h_lgsum is pageable and may be swapped again)
     if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
     return BI_OK;
 }
@@ -410,6 +445,8 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     dev_free(m.counts);
     m.T = 0;
     m.h_lgsum.clear();
+    dev_free(m.geom);           // (the device planner's copies: the next bi_factored_end and set_counts upload them again)
+    dev_free(m.lgsum_dev);
     dev_free(m.real_counts);    // (rows of the previous model's padded length)
     m.real_T = 0;
     release_coarse(c->sw_coarse);   // (groups of the previous model's bins)
@@ -504,6 +541,8 @@ int bi_factored_end(bi_ctx* c) {
         for (int64_t r = m.row_first[(size_t)s]; r < m.row_first[(size_t)s + 1]; ++r)
             if (!m.row_set[(size_t)r])
                 return fail(c, BI_ERR_STATE, "bi_factored_end: anchor %lld of source %d was never set", (long long)(r - m.row_first[(size_t)s]), s);
+    int rc = fac_upload_geometry(c);
+    if (rc) return rc;
     m.open = false;
     m.ready = true;
     return BI_OK;
@@ -537,7 +576,7 @@ int bi_factored_set_counts(bi_ctx* c, int64_t T, const double* counts) {
     m.counts = fresh;
     m.T = T;
     m.h_lgsum.swap(lgsum);
-    return BI_OK;
+    return fac_sync_lgsum(c, "bi_factored_set_counts");
 }
 
 int bi_eval_factored(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,

@@ -41,6 +41,12 @@ __global__ __launch_bounds__(kThreads) void k_morph_factored(FactoredArgs a) {
     constexpr int NSL = GRAD ? 1 + SC * W : 1;
     static_assert(SC <= 8 && kBinsPerThread == 2, "FactoredArgs::e holds 8 sources; a tile is two bins per thread");
     const int item = blockIdx.y;
+    if constexpr (!GRAD) {
+        // items planned on the device (a.live; NULL on every host path): a rejected point reads none of its descriptors, streams
+        // no row and posts no partial (its perm is -1: k_finish skips it).  Uniform for the block; the register counts of
+        // profiles/factored_kernel_resources.txt are those of the kernel without this line.
+        if (a.live && !a.live[item]) return;
+    }
     const int64_t* __restrict__ rowoff = a.rowoff + (int64_t)item * a.NR;
     const double* __restrict__ coef = a.coef + (int64_t)item * a.NR * W;
     const double* __restrict__ rate = a.rates + (int64_t)item * SC;

@@ -1,0 +1,127 @@
+// bi_k_sourcewise_plan.h -- k_sourcewise_plan<SC>: the device path from a staged point of a source-wise model to a work item of
+// k_morph_factored.  Translation unit tu_sourcewise_plan.hip; host half bi_sourcewise_plan.h.
+//
+// Input: n points in VarMap's layouts (z [n][d], rs [n][S], ds [n]) and the device copy of the model's geometry
+// (SourcewiseGeom).  Output per point: the status word of fac_screen (bi_factored.h) -- dataset, then the anchor box over all d
+// axes with nan outside, then the rates -- and the value-order descriptors of FacBatch::fill, bit for bit: rowoff [n][NR],
+// coef [n][NR][W] (column 0 = w_c, the others zero), rates [n][SC], cnt_off [n], slot_lg [n]; the live word [n] that
+// k_morph_factored<.., GRAD = false, ..> reads at block entry; and k_finish's perm [n]: i for a live point, -1 for a rejected
+// one, whose result k_finish then neither sums nor writes -- the planner writes its -inf into out [n] itself.
+//
+// One thread per (point, source slot): the SC lanes of a point are neighbours in one wave.  A lane tests the box of the axes
+// a = slot, slot + SC, ..., computes its own source, and the group ORs its flags with log2(SC) lane exchanges.  So the dependent
+// loads of a point are one binary search per own axis (at most three, side by side) and one rate per corner, whatever d and S
+// are, and a half-step of the sampler is one launch of ceil(n SC / 256) blocks.  The limits e_s <= 3 and 8 corners are unrolled,
+// so every index into t[], st[] is a compile-time constant (no scratch: profiles/sourcewise_plan_kernel_resources.txt); the
+// geometry arrays are indexed by the run-time slot from global memory, not from the kernel arguments.
+//
+// The arithmetic, every operation rounded on its own (the host is compiled without contraction):
+//     k      = (number of anchors <= z) - 1, clamped to [0, n - 2]      find_cell: the upper bound, the last cell closed
+//     t      = (z - g_k) / (g_{k+1} - g_k)                              one IEEE division
+//     w_c    = prod_j (t_j or 1 - t_j), own-axis order from 1.0; first own axis = most significant corner bit
+//     M_s    = sum_c mus[row_c] w_c, left to right from 0.0;   r_s = M_s rs_s
+// A rejected point gets the same in-range descriptors (k is clamped whatever z is, nan included) with cnt_off = 0 and
+// slot_lg = 0, and never runs: live = 0, perm = -1.
+#pragma once
+
+namespace {
+
+// (k, t) of z on the axis whose n >= 2 anchors are g[0 .. n)
+__device__ __forceinline__ void plan_find_cell(const double* __restrict__ g, int n, double z, int& k, double& t) {
+    int lo = 0, hi = n;                    // std::upper_bound: the first anchor with z < g
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (!(z < g[mid])) lo = mid + 1;
+        else hi = mid;
+    }
+    k = min(max(lo - 1, 0), n - 2);
+    const double gk = g[k];
+    t = __ddiv_rn(__dsub_rn(z, gk), __dsub_rn(g[k + 1], gk));
+}
+
+template <int SC>
+__global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePlanArgs a) {
+    static_assert(SC == 2 || SC == 4 || SC == 8, "the source slots of a point share a wave");
+    const int64_t gid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int64_t i = gid / SC;
+    const int s = (int)(gid % SC);
+    if (i >= a.n) return;                  // (whole groups: the lane exchanges below stay inside a point)
+    const SourcewiseGeom& m = a.g;
+
+    // the box test, this lane's share of the d axes (owned or not); nan is outside
+    unsigned flags = 0u;
+    for (int ax = s; ax < m.d; ax += SC) {
+        const int o = m.anchor_off[ax], n = m.anchor_off[ax + 1] - o;
+        const double v = a.z[i * m.d + ax];
+        if (!(m.anchors[o] <= v && v <= m.anchors[o + n - 1])) flags |= (unsigned)BI_ST_OUT_OF_BOUNDS;
+    }
+
+    // this lane's source: cell and fraction of its own axes, then its corner rows, weights and rate
+    const bool real = s < m.S;
+    const int e = real ? m.n_own[s] : -1;
+    int first = 0;                         // the source's first row within the item
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+        if (q < s && a.e[q] >= 0) first += 1 << a.e[q];
+    double rate = 0.0;
+    if (real) {
+        int64_t base = m.row_first[s];
+        double t[kFacMaxOwn];
+        int64_t st[kFacMaxOwn];
+#pragma unroll
+        for (int j = 0; j < kFacMaxOwn; ++j) {
+            t[j] = 0.0;
+            st[j] = 0;
+            if (j < e) {
+                const int ax = m.own[s * kFacMaxOwn + j];
+                const int o = m.anchor_off[ax], n = m.anchor_off[ax + 1] - o;
+                int k;
+                plan_find_cell(m.anchors + o, n, a.z[i * m.d + ax], k, t[j]);
+                st[j] = m.own_stride[s * kFacMaxOwn + j];
+                base += (int64_t)k * st[j];
+            }
+        }
+        const int nc = 1 << e;
+        double M = 0.0;
+#pragma unroll
+        for (int c = 0; c < (1 << kFacMaxOwn); ++c) {
+            if (c < nc) {
+                int64_t r = base;
+                double wc = 1.0;
+#pragma unroll
+                for (int j = 0; j < kFacMaxOwn; ++j)
+                    if (j < e) {
+                        const bool up = (c >> (e - 1 - j)) & 1;
+                        if (up) r += st[j];
+                        wc = __dmul_rn(wc, up ? t[j] : __dsub_rn(1.0, t[j]));
+                    }
+                const int64_t row = i * a.NR + first + c;
+                a.rowoff[row] = r * m.Bp;
+                a.coef[row * a.W] = wc;
+                for (int x = 1; x < a.W; ++x) a.coef[row * a.W + x] = 0.0;
+                M = __dadd_rn(M, __dmul_rn(m.mus[r], wc));
+            }
+        }
+        rate = __dmul_rn(M, a.rs[i * m.S + s]);
+        if (!(rate >= 0.0 && rate < __builtin_huge_val())) flags |= (unsigned)BI_ST_UNPHYSICAL;
+    }
+    a.rates[i * SC + s] = rate;            // (a padded slot: zero)
+
+#pragma unroll
+    for (int x = 1; x < SC; x <<= 1) flags |= (unsigned)__shfl_xor((int)flags, x);
+    if (s == 0) {
+        const int64_t ds = a.ds[i];
+        const int32_t status = (ds < 0 || ds >= m.T) ? BI_ST_BAD_DATASET
+                               : (flags & BI_ST_OUT_OF_BOUNDS) ? BI_ST_OUT_OF_BOUNDS
+                               : (flags & BI_ST_UNPHYSICAL)    ? BI_ST_UNPHYSICAL
+                                                               : 0;
+        a.status[i] = status;
+        a.live[i] = status == 0 ? 1u : 0u;
+        a.cnt_off[i] = status == 0 ? ds * m.Bp : 0;
+        a.slot_lg[i] = status == 0 ? m.lgsum[ds] : 0.0;
+        a.perm[i] = status == 0 ? i : -1;
+        if (status != 0) a.out[i] = -__builtin_huge_val();
+    }
+}
+
+}  // namespace

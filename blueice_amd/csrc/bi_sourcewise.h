@@ -201,7 +201,7 @@ int bi_sourcewise_generate_toys(bi_ctx* c, int64_t H, const double* z, const dou
     m.counts = fresh;
     m.T = T;
     m.h_lgsum.swap(lgsum);
-    return BI_OK;
+    return fac_sync_lgsum(c, who);
 }
 
 int bi_sourcewise_download_counts(bi_ctx* c, int64_t t, double* out) {

@@ -52,10 +52,13 @@ int check_entry_datasets(bi_ctx* c, const char* who, const char* what, int64_t E
 struct ResidentPoints {
     ScratchBuf map, zp, rsp, dsp, llp;
 
-    // the map in one copy (the caller waits for the stream before its arrays go), room for n_max points, m pointed at both
+    // the map in one copy (the caller waits for the stream before its arrays go), room for n_max points, m pointed at both;
+    // model_d, model_S: the model's axes and sources as check_variable takes them (< 0: the grid model's)
     int bind(bi_ctx* c, VarMap& m, int64_t E, int64_t n_max, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
-             const double* scale0, const double* unit, const int64_t* dataset) {
-        const size_t nE = (size_t)E, n = (size_t)n_max, d = (size_t)c->d, S = (size_t)c->S;
+             const double* scale0, const double* unit, const int64_t* dataset, int model_d = -1, int model_S = -1) {
+        if (model_d < 0) model_d = c->d;
+        if (model_S < 0) model_S = c->S;
+        const size_t nE = (size_t)E, n = (size_t)n_max, d = (size_t)model_d, S = (size_t)model_S;
         PackedUpload pu;
         int rc;
         if ((rc = packed_upload(c, {{var_kind, (size_t)F * sizeof(int32_t)}, {var_index, (size_t)F * sizeof(int32_t)}, {z0, nE * d * sizeof(double)},
@@ -64,7 +67,7 @@ struct ResidentPoints {
             (rc = dev_alloc(c, zp, n * std::max<size_t>(d, 1) * sizeof(double))) || (rc = dev_alloc(c, rsp, n * S * sizeof(double))) ||
             (rc = dev_alloc(c, dsp, n * sizeof(int64_t))) || (rc = dev_alloc(c, llp, n * sizeof(double))))
             return rc;
-        m.F = F; m.d = c->d; m.S = c->S;
+        m.F = F; m.d = model_d; m.S = model_S;
         m.var_kind = pu.dev<int32_t>(0); m.var_index = pu.dev<int32_t>(1);
         m.z0 = pu.dev<double>(2); m.scale0 = pu.dev<double>(3); m.unit = pu.dev<double>(4);
         m.dataset = dataset ? pu.dev<int64_t>(5) : nullptr;

@@ -8,7 +8,8 @@ documented with `bi_sample_stretch` in include/blueice_hip.h):
 
     'native'   bi_sample_stretch: propose, evaluate, accept and the chain stay on the device; taken whenever nothing but
                the device call sits between the parameters and the likelihood (`BatchObjective.native()`); Gaussian
-               constraints (`priors.GaussianPrior`) are added on the device (bi_sample_stretch_gauss)
+               constraints (`priors.GaussianPrior`) are added on the device (bi_sample_stretch_gauss); a source-wise model
+               (`SourceWiseBinnedLogLikelihood`) has bi_sample_stretch_sourcewise behind the same `ctx.sample_stretch`
     'host'     the restatement below in NumPy, one `lf.eval_points` call per half-step -- for likelihoods with other
                Python callables as priors, sums, re-parametrisations, efficiencies, unphysical_behaviour='error', and
                models whose batches the device planner refuses

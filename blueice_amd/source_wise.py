@@ -52,9 +52,16 @@ device work), per source as well: blueice_amd.coarse.sourcewise_coarse_jacobian 
 sourcewise_coarse_information.  The grid model's names (expected_coarse_jacobian*, expected_coarse_band, coarse_information), as
 functions of blueice_amd.coarse and as bound names, stay refused and name those spellings.
 
+The ensemble sampler runs on this model too (bi_sample_stretch_sourcewise): a planner kernel turns the proposals into work items
+on the device (k_sourcewise_plan; `ctx.eval_planned` is the same path for points given by the host), so a half-step is five
+launches queued on one stream and the step loop waits for nothing.  `blueice_amd.sampler.sample_posterior(lf, ...)` and
+`blueice_amd.inference.bestfit_emcee(lf, ...)` reach it through `BatchObjective.native()` like any other likelihood, with
+`datasets=` after `simulate_toys_points` and with `GaussianPrior` constraints on the device.  The bound lf.sample_posterior and
+lf.bestfit_emcee stay refused and name these spellings.
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, eval_toys*, grids, Hessians on an Asimov view and the ensemble sampler.
+full_output calls, eval_toys*, grids (grid_scan), Hessians and sampling on an Asimov view.
 """
 import ctypes as C
 from collections import OrderedDict
@@ -88,8 +95,9 @@ class SourceWiseContext:
     coarse_counts,
     generate_toys_points, download_counts, set_param / get_param,
     fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
-    real_count_sets, download_real_counts, eval_real, fit_batched_real) -- and the uploads; nothing else of the DeviceContext (plans, the sampler ...) has a
-    meaning here and is an AttributeError."""
+    real_count_sets, download_real_counts, eval_real, fit_batched_real), sample_stretch (with eval_planned, the same device planner
+    for points given by the host) -- and the uploads; nothing else of the DeviceContext (plans, grids ...) has a meaning here and is
+    an AttributeError."""
 
     def __init__(self, device=None):
         self._dev = DeviceContext(device)
@@ -199,6 +207,51 @@ class SourceWiseContext:
         status = np.zeros(P, dtype=np.int32)
         dev._check(dev._lib.bi_eval_factored(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), None, ptr(status)))
         return ll, status
+
+    def eval_planned(self, z, rate_scale=None, dataset=None):
+        """`eval` with the work items made on the device (bi_eval_sourcewise_planned: the rows are uploaded as they are, the
+        planner kernel screens them and writes the descriptors) -> (ll [P], status [P]), bit for bit `eval`'s."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        ll = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_planned(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(status)))
+        return ll, status
+
+    def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0, priors=None):
+        """bi_sample_stretch_sourcewise: DeviceContext.sample_stretch with the source-wise likelihood as the target -- the same
+        arguments, random stream and return value (chain [n_steps, E, W, F], ll [n_steps, E, W], n_accepted [E, W], counters),
+        `priors` included.  counters has five entries here: half-steps, evaluations, accepted moves, launches, and the stream
+        synchronisations inside the step loop (0: the loop is queued without a host wait)."""
+        dev = self._dev
+        x0 = np.ascontiguousarray(x0, dtype=np.float64)
+        E, W2, F = x0.shape
+        if W2 != W:
+            raise ValueError("x0 must be [E, W, F]")
+        kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
+
+        def rows(v, n):
+            return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1, n), (E, n)))
+        z0 = rows(z0, self.d) if self.d else None
+        scale0, unit = rows(scale0, self.S), rows(unit, self.S)
+        if dataset is not None:
+            dataset = np.ascontiguousarray(np.broadcast_to(np.asarray(dataset, dtype=np.int64), (E,)))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float64), np.ascontiguousarray(hi, dtype=np.float64)
+        if len(kind) != F or len(index) != F or len(lo) != F or len(hi) != F:
+            raise ValueError("kind, index, lo and hi must have one entry per variable")
+        n_steps = int(n_steps)
+        chain = np.empty((max(n_steps, 0), E, W, F))
+        ll = np.empty((max(n_steps, 0), E, W))
+        n_acc = np.zeros((E, W), dtype=np.int64)
+        counters = np.zeros(5, dtype=np.int64)
+        mean = sigma = const = None
+        if priors is not None:
+            mean, sigma, const = dev._gauss_terms(priors, F, E)
+        dev._check(dev._lib.bi_sample_stretch_sourcewise(dev._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0), ptr(scale0), ptr(unit), ptr(dataset),
+                                                         ptr(x0), ptr(lo), ptr(hi), n_steps, float(a), int(seed) & (2 ** 64 - 1),
+                                                         int(first_ensemble), ptr(mean), ptr(sigma), ptr(const), ptr(chain), ptr(ll),
+                                                         ptr(n_acc), ptr(counters)))
+        return chain, ll, n_acc, counters
 
     def eval_grad(self, z, rate_scale=None, dataset=None):
         """-> (ll [P], dll/dz [P, d], dll/drate_scale [P, S], status [P])"""
@@ -437,6 +490,8 @@ _REFUSED_SPELLINGS = {
     'asimov': "blueice_amd.asimov.asimov(lf, **truth)",
     'real_data': "blueice_amd.asimov.real_data(lf, counts)",
     'expected_upper_limit': "blueice_amd.inference.expected_upper_limit(lf, target, bound)",
+    'sample_posterior': "blueice_amd.sampler.sample_posterior(lf, n_walkers=, n_steps=, ...)",
+    'bestfit_emcee': "blueice_amd.inference.bestfit_emcee(lf, ...) (or blueice_amd.sampler.sample_posterior(lf, ...) for the chain)",
 }
 
 
@@ -447,7 +502,7 @@ def _refused(name):
                                       % (name, _REFUSED_SPELLINGS[name]))
         raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
                                   "Hessian, expected information, the fit, scan and interval layers, toys at truth points, "
-                                  "goodness of fit, coarse views and Asimov data are" % name)
+                                  "goodness of fit, coarse views, Asimov data and the ensemble sampler are" % name)
     method.__name__ = name
     return method
 

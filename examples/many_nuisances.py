@@ -1,7 +1,7 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band]
-        [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian [--rounds 31]]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band] [--posterior]
+        [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian | --measure-sampler [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
 grid that is 5^8 = 390 625 anchor models and 4 x 2^8 = 1024 template rows per evaluation, and the gradient path stops at
@@ -52,6 +52,15 @@ bi_sourcewise_expected_coarse_jacobian), beside the same numbers from central di
 --measure-coarse-jacobian times, at the same source-wise shape, bi_sourcewise_expected_coarse_jacobian (total and per source) for the x0
 projection, the 10^3 rebinning, one cell and a box, against bi_sourcewise_expected_coarse on the same points and against the
 (2 F + 1) P-point bi_sourcewise_expected_coarse call of the central differences it replaces, and the kernel pairs alone by device events.
+
+--posterior draws, instead of (2) - (6), a chain over all twelve parameters with their constraints (blueice_amd.sampler.sample_posterior:
+bi_sample_stretch_sourcewise, the proposals planned on the device) and prints the 90 % credible upper limit on the signal's
+multiplier beside one_parameter_interval's, and the posterior band of the projection on the first analysis axis from one
+blueice_amd.coarse.expected_coarse_points call over draws of the chain.
+
+--measure-sampler times, at the same source-wise shape, bi_sample_stretch_sourcewise against the host engine (the same move in
+NumPy, one bi_eval_factored call per half-step) at 40 and 1024 walkers for 50 steps, and bi_eval_sourcewise_planned against
+bi_eval_factored values-only at 1, 64 and 4096 points per call; the lines go to profiles/sourcewise_sampler_measure.txt too.
 """
 import argparse
 import time
@@ -67,6 +76,9 @@ ap.add_argument('--measure-asimov', action='store_true', help='time bi_eval_sour
 ap.add_argument('--measure-coarse', action='store_true', help='time bi_sourcewise_expected_coarse against expected_counts + the NumPy reduction')
 ap.add_argument('--measure-coarse-jacobian', action='store_true',
                 help='time bi_sourcewise_expected_coarse_jacobian against bi_sourcewise_expected_coarse and the central differences it replaces')
+ap.add_argument('--posterior', action='store_true', help='a posterior chain over all twelve parameters: credible limit and projection band')
+ap.add_argument('--measure-sampler', action='store_true',
+                help='time bi_sample_stretch_sourcewise against the host engine, and bi_eval_sourcewise_planned against bi_eval_factored')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -592,6 +604,130 @@ def asimov_band():
           % (limits[0], dt_asimov, wilks[1], dt_toys, neyman[1], dt_toys + dt_neyman))
 
 
+def measure_sampler():
+    """The ensemble sampler at the measured source-wise shape, on the C ABI: bi_sample_stretch_sourcewise (propose, device planner,
+    evaluation, accept queued on one stream) against the host engine of blueice_amd.sampler -- the same stretch move in NumPy with
+    one bi_eval_factored call per half-step, which is what sample_posterior(engine='host') runs and what the code before the device
+    planner ran -- alternated calls, medians with quartiles; then bi_eval_sourcewise_planned against bi_eval_factored values-only.
+    Written to profiles/sourcewise_sampler_measure.txt as well."""
+    import os
+    from blueice_amd import sampler
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B, steps = 5, args.measure_bins ** 3, 50
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = 2.5e6 * (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])          # ~10 events per bin in all
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    mid = n_a // 2
+    fac.set_counts(rng.poisson(sum(mus[s, mid] * rows[s, mid] for s in range(S))).astype(float))
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    say('# examples/many_nuisances.py --measure-sampler --measure-bins %d --rounds %d on %s' % (args.measure_bins, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>), %d anchors, %d bins, dense data; every other class: not measured' % (d, S, n_a, B))
+    kind = np.array([1] * S + [0] * d, dtype=np.int32)
+    index = np.array(list(range(S)) + list(range(d)), dtype=np.int32)
+    names = ['r%d' % s for s in range(S)] + ['z%d' % i for i in range(d)]
+    lo, hi = np.array([0.] * S + [-2.] * d), np.array([np.inf] * S + [2.] * d)
+    z0, one = np.zeros(d), np.ones(S)
+
+    class HostLikelihood:
+        """what _host_engine asks of a likelihood: eval_points over the variables' columns, through bi_eval_factored"""
+        def eval_points(self, call, livetime_days=None):
+            return fac.eval(np.stack([call[n] for n in names[S:]], axis=1), np.stack([call[n] for n in names[:S]], axis=1))[0]
+
+    for W in (40, 1024):
+        x0 = np.concatenate([rng.uniform(0.999, 1.001, (W, S)), rng.uniform(-0.01, 0.01, (W, d))], axis=1)[None]
+        native = lambda: fac.sample_stretch(W, kind, index, z0, one, one, None, x0, lo, hi, steps, seed=7)
+        host = lambda: sampler._host_engine(HostLikelihood(), names, {}, None, None, x0.copy(), lo, hi, steps, 2.0, 7, 0)
+        a, b = native(), host()
+        same = np.mean(a[0] == b[0])
+        say('W = %4d, %d steps: counters of the device loop %s (half-steps, evaluations, accepted, launches, stream waits in the loop); '
+            'accepted on the host %d; %.1f %% of the chain entries equal bit for bit' % (W, steps, [int(v) for v in a[3]], b[3][2], 100 * same))
+        times = {'native': [], 'host': []}
+        for rnd in range(2 + args.rounds):
+            for name, call in (('native', native), ('host', host)):
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 2:
+                    times[name].append(time.perf_counter() - t0)
+        for name, what in (('native', 'bi_sample_stretch_sourcewise'), ('host', 'host engine, bi_eval_factored per half-step')):
+            say('W = %4d, %d steps, %-46s %s per call, %.1f us per half-step' % (W, steps, what, quartiles(times[name]),
+                                                                                np.median(times[name]) * 1e6 / (2 * steps)))
+    for P in (1, 64, 4096):
+        z, r = rng.uniform(-1.9, 1.9, (P, d)), rng.uniform(0.8, 1.2, (P, S))
+        assert np.array_equal(fac.eval_planned(z, r)[0], fac.eval(z, r)[0])
+        times = {'planned': [], 'host': []}
+        for rnd in range(3 + args.rounds):
+            for name, call in (('planned', lambda: fac.eval_planned(z, r)), ('host', lambda: fac.eval(z, r))):
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 3:
+                    times[name].append(time.perf_counter() - t0)
+        say('%4d points per call, bi_eval_sourcewise_planned  %s' % (P, quartiles(times['planned'])))
+        say('%4d points per call, bi_eval_factored, values    %s' % (P, quartiles(times['host'])))
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_sampler_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+
+
+def posterior():
+    """A chain over all twelve parameters with their constraints on the device; the credible upper limit on the signal's
+    multiplier beside one_parameter_interval's; the posterior band of the projection on the first analysis axis."""
+    from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood, coarse, sampler
+    from blueice_amd.synthetic import many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins))
+    lf = SourceWiseBinnedLogLikelihood(conf)
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    lf.prepare()
+    np.random.seed(3)
+    lf.set_data(lf.base_model.simulate())
+    _, floating, _, _ = lf.make_objective(minus=False)
+    rng = np.random.default_rng(1)
+    W, steps, burn = 48, 1500, 500
+    p0 = np.array([rng.uniform(0.95, 1.05, W) if n.endswith('_rate_multiplier') else rng.uniform(-0.2, 0.2, W) for n in floating]).T
+    t0 = time.perf_counter()
+    run = sampler.sample_posterior(lf, n_walkers=W, n_steps=steps, seed=4, p0=p0)
+    dt = time.perf_counter() - t0
+    kept = run.flat(discard=burn)
+    print('posterior over %d parameters: %d walkers x %d steps on the %s engine in %.3f s (%d launches, %d stream waits in the loop), '
+          'acceptance %.3f' % (len(run.names), W, steps, run.engine, dt, run.counters[3], run.counters[4] if len(run.counters) > 4 else -1,
+                               run.acceptance_fraction.mean()))
+    s0 = kept[:, run.names.index('s0_rate_multiplier')]
+    limit = lf.one_parameter_interval('s0_rate_multiplier', 3.0, confidence_level=0.9, kind='upper')
+    print('    90 %% upper limit on s0_rate_multiplier: credible (posterior quantile, flat prior on the multiplier) %.4f; '
+          'one_parameter_interval (profile likelihood, Wilks) %.4f' % (np.quantile(s0, 0.9), limit))
+    (x, _), _ = lf.base_model.config['analysis_space']
+    proj = coarse.CoarseBinning(lf, keep=[str(x)], rebin={str(x): max(args.bins // 10, 1)})
+    draws = kept[rng.choice(len(kept), 512, replace=False)]
+    mu = coarse.expected_coarse_points(lf, proj, {n: draws[:, v] for v, n in enumerate(run.names)})
+    q16, q50, q84 = np.quantile(mu.reshape(len(draws), -1), [0.1587, 0.5, 0.8413], axis=0)
+    print('    posterior band of the projection on %s from 512 draws (one expected_coarse_points call): cell, median, -1 sigma, +1 sigma' % x)
+    for c in range(len(q50)):
+        print('      %2d  %10.2f  %+8.2f  %+8.2f' % (c, q50[c], q16[c] - q50[c], q84[c] - q50[c]))
+
+
+if args.measure_sampler:
+    measure_sampler()
+    raise SystemExit(0)
+if args.posterior:
+    posterior()
+    raise SystemExit(0)
 if args.measure:
     measure()
     raise SystemExit(0)

@@ -776,6 +776,37 @@ int bi_sample_stretch_gauss(bi_ctx* ctx, int64_t E, int W, int F, const int32_t*
                             const double* prior_mean, const double* prior_sigma, const double* prior_const, double* chain,
                             double* ll, int64_t* n_accepted, int64_t* counters);
 
+/* ... of a source-wise model (bi_factored_begin above), with a planner on the device between the staged points and the work items
+ * of the evaluation kernel.  The geometry that bi_eval_factored's host screen reads -- anchors, own axes, row strides, the
+ * anchors' rates, sum_b lgamma(n_b + 1) per dataset -- has a device copy (uploaded by bi_factored_end; the sums by
+ * bi_factored_set_counts and bi_sourcewise_generate_toys), and one kernel turns n points into status words and descriptors: no
+ * descriptor crosses the bus, and no result is read to size a launch.
+ *   bi_eval_sourcewise_planned    bi_eval_factored's values-only contract through that planner: z [P][d], rate_scale [P][S] or
+ *                                 NULL (ones), dataset [P] or NULL (dataset 0) are uploaded as they are; ll [P] and status [P]
+ *                                 (or NULL) are bit for bit bi_eval_factored's -- the early exits in its order with its bits and
+ *                                 ll = -inf, the same blocks per item and sub-batches.  P = 0: BI_OK without device work;
+ *                                 BI_ERR_STATE without counts.  A rejected point streams no row.
+ *   bi_sample_stretch_sourcewise  bi_sample_stretch_gauss's arguments, random stream, arithmetic and acceptance rule (above) with
+ *                                 this model's likelihood as the log density; the three prior arrays may all be NULL (no terms);
+ *                                 var_index refers to the d axes and S sources of this model, `dataset` [E] (or NULL) to the
+ *                                 sets of bi_factored_set_counts or of the toy generator.  The same argument errors, reported
+ *                                 under this name.  A half-step is k_stretch_propose, the planner, the evaluation kernel
+ *                                 (values only), k_finish and k_stretch_accept, queued on one stream: after the start -- whose
+ *                                 log densities and status words are read back once, to refuse a walker outside [lo, hi] or of
+ *                                 zero likelihood -- the host reads nothing and waits for nothing until the one copy of chain, ll
+ *                                 and n_accepted at the end.  counters [5] or NULL: [0] half-steps, [1] likelihood evaluations,
+ *                                 [2] accepted moves, [3] launches (counted on the host from what was queued), [4] stream
+ *                                 synchronisations inside the step loop: 0.  n_sampler_half_steps advances.  The chain must fit
+ *                                 the free device memory (BI_ERR_NOMEM).  No floating-point atomics: a repeated call gives the
+ *                                 same bits, and ensemble e is ensemble first_ensemble + e of the seed's stream whatever E is. */
+int bi_eval_sourcewise_planned(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                               double* ll, int32_t* status);
+int bi_sample_stretch_sourcewise(bi_ctx* ctx, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index,
+                                 const double* z0, const double* scale0, const double* unit, const int64_t* dataset,
+                                 const double* x0, const double* lo, const double* hi, int64_t n_steps, double a, uint64_t seed,
+                                 int64_t first_ensemble, const double* prior_mean, const double* prior_sigma,
+                                 const double* prior_const, double* chain, double* ll, int64_t* n_accepted, int64_t* counters);
+
 /* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
  * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
  * lists one after the other; any order, finite).  The first n_keep variables are kept, the others reduced:
