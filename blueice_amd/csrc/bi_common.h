@@ -20,6 +20,8 @@
 //                         real-valued counts per item)                                       bi_k_sourcewise_real.h
 //     tu_sourcewise_plan.hip   k_sourcewise_plan (staged points of a source-wise model -> status words and k_morph_factored's
 //                         descriptors, on the device)                                        bi_k_sourcewise_plan.h
+//     tu_sourcewise_nonempty.hip   k_sourcewise_nonempty (value + gradient sums of one point of a source-wise model over the
+//                         non-empty bins of its dataset), k_sourcewise_gather (the compacted copies)   bi_k_sourcewise_nonempty.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -135,6 +137,14 @@ int launch_sourcewise_real(bi_ctx* c, int SC, int EM, bool grad, const FactoredA
 // k_sourcewise_plan<SC>: the status words and k_morph_factored's value-order descriptors of a.n staged points of a source-wise model,
 // one thread per (point, source slot); BI_ERR_INVALID for another SC than 2, 4, 8
 int launch_sourcewise_plan(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
+// ... k_sourcewise_plan<SC, NE = true>: the same for k_sourcewise_nonempty (rows, counts and tiles of the dataset's compacted copy,
+// slot_lg = sum_s lambda_s + lgsum; a.g.rowsum and a.g.ne_* set)
+int launch_sourcewise_plan_nonempty(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
+// k_sourcewise_nonempty<SC, EM, GRAD>: the sums of one point of a source-wise model over the non-empty bins of its dataset per item;
+// classes and result slots (factored_slots) as launch_morph_factored.  grid.x: the largest block count of the launch's items
+int launch_sourcewise_nonempty(bi_ctx* c, int SC, int EM, bool grad, const SourcewiseNonemptyArgs& a, dim3 grid);
+// k_sourcewise_gather: the compacted copies of grid.z datasets from a.t0 on
+void launch_sourcewise_gather(bi_ctx* c, const SourcewiseGatherArgs& a, dim3 grid);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -168,8 +168,20 @@ struct bi_ctx {
         // n_own, own, own_stride, row_first, h_mus at geom_off[0 .. 7), uploaded by bi_factored_end; and of h_lgsum, uploaded
         // wherever that changes (fac_sync_lgsum)
         DevBuf geom, lgsum_dev;
-        size_t geom_off[7] = {};
+        size_t geom_off[8] = {};                     // (the eighth part: h_rowsum, for the non-empty-bin form's planner)
+        // the non-empty-bin form of the data (bi_sourcewise_build_nonempty; bi_sourcewise_nonempty.h): h_rowsum [rows], the total
+        // R_{s,c} of every anchor row over all bins (long double, rounded once; bi_factored_set_anchor); per dataset t the
+        // compacted copy ne_ps + ne_off[t] of all rows over its list, [rows][ne_np[t]] with ne_np[t] the list length padded to
+        // whole tiles (at least one; zeros in the padding), and its compacted counts ne_cnt + ne_cnt_off[t] [ne_np[t]].  ne_tab:
+        // the three tables back to back [3][T] for the device planner.  ne_max_nbx: the most blocks an item of any dataset takes.
+        std::vector<double> h_rowsum;
+        bool ne_ready = false;
+        int64_t ne_bytes = 0;
+        int ne_max_nbx = 1;
+        std::vector<int64_t> ne_off, ne_np, ne_cnt_off;
+        DevBuf ne_ps, ne_cnt, ne_tab;
     } fac;
+    int64_t sourcewise_form = 1;                 // 0: source-wise evaluations read the dense store although the non-empty-bin form is built
 
     // the coarse binning of bi_set_coarse_binning (bi_coarse.h): tensor-product groups of fine bins, b = r L + x with L the
     // fine bins of the last analysis axis.  Released by a new model.

@@ -185,6 +185,11 @@ struct SourcewiseGeom {
     const double* lgsum;       // [T] sum_b lgamma(n_b + 1) of every dataset
     int64_t T, Bp;
     int d, S;
+    // k_sourcewise_plan<SC, NE = true> alone (the non-empty-bin form, bi_sourcewise_nonempty.h)
+    const double* rowsum;      // [rows] R_{s,c}: the anchor rows' totals over all bins
+    const int64_t* ne_off;     // [T] where the dataset's compacted rows start
+    const int64_t* ne_np;      // [T] its list length padded to whole tiles
+    const int64_t* ne_cnt_off; // [T] where its compacted counts start
 };
 // ... and n staged points in VarMap's layouts -> their status words and FacBatch's value-order descriptors
 struct SourcewisePlanArgs {
@@ -204,6 +209,40 @@ struct SourcewisePlanArgs {
     double* slot_lg;           // [n]
     int64_t* perm;             // [n] k_finish's: i, or -1 for a rejected point (neither summed nor written)
     double* out;               // [n] where k_finish writes the results: the planner writes a rejected point's -inf
+    int32_t* tiles;            // [n] (NE alone) the 512-bin tiles of the item's dataset's list
+};
+
+// k_sourcewise_nonempty (bi_k_sourcewise_nonempty.h): FactoredArgs' descriptors over the compacted copies of the non-empty bins.
+// The rows of an item lie in ITS dataset's copy (rowoff holds the copy's offset), and so does the number of tiles: per item.
+struct SourcewiseNonemptyArgs {
+    const double* ps;          // the compacted rows of every dataset
+    const double* counts;      // the compacted counts of every dataset
+    const int64_t* rowoff;     // [items][NR] element offsets of the item's corner rows in ps
+    const double* coef;        // [items][NR][1 + EM] as FactoredArgs::coef
+    const double* rates;       // [items][SC]
+    const int64_t* item_cnt;   // [items] element offset of the item's compacted counts
+    const int32_t* item_tiles; // [items] tiles of the item's list (>= 1)
+    double* partial;           // [items][gridDim.x][NSL]
+    unsigned* pflags;          // [items][gridDim.x][NSL]
+    int NR;                    // rows per item
+    int chunks;                // ItemTiles' chunks
+    int max_blocks;            // an item's tiles are walked by min(tiles, max_blocks) blocks, whatever gridDim.x is
+    int e[8];                  // own axes of every source
+    const unsigned* live;      // [items] planned items (GRAD = false): 0 = rejected; NULL on the host paths
+};
+
+// k_sourcewise_gather (bi_k_sourcewise_nonempty.h): the compacted copies of the datasets t0 + blockIdx.z
+struct SourcewiseGatherArgs {
+    const double* ps;          // [rows][Bp] the dense rows
+    const int32_t* nz_idx;     // the datasets' lists back to back, ascending bins
+    const double* nz_n;        // ... and their counts
+    const int64_t* nz_off;     // [T + 1]
+    const int64_t* ne_off;     // [T]
+    const int64_t* ne_np;      // [T]
+    const int64_t* ne_cnt_off; // [T]
+    double* out_ps;
+    double* out_cnt;
+    int64_t Bp, rows, t0;
 };
 
 // k_sourcewise_expect (bi_k_sourcewise.h): the descriptors of FactoredArgs (rowoff, coef [items][NR][1 + EM], rates, e; no

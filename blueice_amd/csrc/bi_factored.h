@@ -15,6 +15,9 @@
 // sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
 // Beeston-Barlow, unbinned data.  The counts are dense doubles [T][Bp]: the caller's (bi_factored_set_counts) or toys drawn
 // on the device (bi_sourcewise_generate_toys, bi_sourcewise.h, which also holds the expectation and goodness-of-fit layers).
+// Beside them, when asked for, the non-empty-bin form of the same counts (bi_sourcewise_build_nonempty, bi_sourcewise_nonempty.h:
+// per dataset its list of bins with events and a compacted copy of the rows over it), on which factored_eval, and through it the
+// native fit, then run (FacBatch with nonempty = true; fac_nonempty_on).
 // Coarse views of the expectation and of these counts: bi_sourcewise_coarse.h, with a coarse binning of the store's own
 // (bi_ctx::sw_coarse), which bi_factored_begin releases.
 //
@@ -137,6 +140,18 @@ int fac_check(bi_ctx* c, const char* who, bool need_counts) {
     return BI_OK;
 }
 
+// The non-empty-bin form (bi_sourcewise_nonempty.h) belongs to the counts and the model it was built from: whatever replaces
+// either releases it (bi_factored_begin, bi_factored_set_counts, bi_sourcewise_generate_toys), and bi_sourcewise_drop_nonempty.
+void fac_drop_nonempty(bi_ctx::Factored& m) {
+    m.ne_ready = false;
+    m.ne_bytes = 0;
+    m.ne_max_nbx = 1;
+    m.ne_off.clear(); m.ne_np.clear(); m.ne_cnt_off.clear();
+    dev_free(m.ne_ps); dev_free(m.ne_cnt); dev_free(m.ne_tab);
+}
+// do bi_eval_factored (and with it the native fit), bi_eval_sourcewise_planned and bi_sample_stretch_sourcewise run on it
+bool fac_nonempty_on(const bi_ctx* c) { return c->fac.ne_ready && c->sourcewise_form == 1; }
+
 // sum_b lgamma(n + 1) of the T dense datasets counts [T][Bp] (device) -> lgsum [T], once per upload or generator call: the kernels
 // of the grid model's counts (finish_counts).  e: the error state of what the caller queued before; synchronises the stream.
 int fac_counts_lgsum(bi_ctx* c, const char* who, const double* counts, int64_t T, hipError_t e, std::vector<double>& lgsum) {
@@ -165,7 +180,8 @@ int fac_counts_lgsum(bi_ctx* c, const char* who, const double* counts, int64_t T
 }
 
 // The device planner's copy (k_sourcewise_plan, bi_sourcewise_plan.h) of what fac_geometry and FacSource::at read, one slab:
-// anchors, anchor_off [d + 1], n_own [S], own [S][3], own_stride [S][3], row_first [S], h_mus [rows] at geom_off[0 .. 7).
+// anchors, anchor_off [d + 1], n_own [S], own [S][3], own_stride [S][3], row_first [S], h_mus [rows], h_rowsum [rows] at
+// geom_off[0 .. 8).
 // Waits for the copy (the staging block is the context's).
 int fac_upload_geometry(bi_ctx* c) {
     bi_ctx::Factored& m = c->fac;
@@ -180,10 +196,10 @@ int fac_upload_geometry(bi_ctx* c) {
     int rc = packed_upload(c, {{anchors.data(), anchors.size() * sizeof(double)}, {anchor_off.data(), anchor_off.size() * sizeof(int32_t)},
                                {n_own.data(), n_own.size() * sizeof(int32_t)}, {own.data(), own.size() * sizeof(int32_t)},
                                {m.own_stride.data(), m.own_stride.size() * sizeof(int64_t)}, {m.row_first.data(), (size_t)m.S * sizeof(int64_t)},
-                               {m.h_mus.data(), m.h_mus.size() * sizeof(double)}},
+                               {m.h_mus.data(), m.h_mus.size() * sizeof(double)}, {m.h_rowsum.data(), m.h_rowsum.size() * sizeof(double)}},
                            0, pu, &m.geom);
     if (rc) return rc;
-    for (size_t q = 0; q < 7; ++q) m.geom_off[q] = pu.off[q];
+    for (size_t q = 0; q < 8; ++q) m.geom_off[q] = pu.off[q];
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BI_OK;
 }
@@ -217,10 +233,16 @@ struct FacBatch {
 
     bool dataset_test;                          // the screen tests the dataset index (calls that read counts)
     mutable int64_t pieces = 0;                 // run_item_chunks' chunks over every run() so far: last_point_pieces
+    // the non-empty-bin form (order 0 / 1, bi_sourcewise_nonempty.h): the descriptors point into the dataset's compacted copy
+    bool nonempty;
+    std::vector<int32_t> tiles;                 // [n] tiles of the item's dataset's list
+    std::vector<double> lam_sum;                // [n] sum_s lambda_s, sources ascending from 0.0
+    std::vector<double> hN, hdN;                // [n][S] N_s = sum_c w_c R_{s,c}; [n][S][kFacMaxOwn] d_j N_s (order 1)
 
-    FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true)
+    FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true, bool nonempty_ = false)
         : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
-          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts) {
+          NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts),
+          nonempty(nonempty_ && order_ <= 1 && reads_counts) {
         c->last_point_pieces = 0;               // (a call with no live item launches nothing)
     }
 
@@ -255,6 +277,12 @@ struct FacBatch {
         if (order == 3) chain.assign(n * SC * W, 0.0);
         if (order >= 1) { hM.resize(n * S); hdM.resize(n * S * kFacMaxOwn); }
         if (order == 2) hd2M.resize(n * S * kFacMaxOwn);
+        if (nonempty) {
+            tiles.assign(n, 1);
+            lam_sum.assign(n, 0.0);
+            hN.assign(n * S, 0.0);
+            if (order >= 1) hdN.assign(n * S * kFacMaxOwn, 0.0);
+        }
         parallel_for(n_items, 1024, [&](int64_t lo, int64_t hi) {
             FacGeom g;
             FacSource fs;
@@ -262,12 +290,29 @@ struct FacBatch {
                 const int64_t p = live[(size_t)i];
                 const int64_t ds = dataset ? dataset[p] : 0;
                 fac_geometry(m, z ? z + p * d : nullptr, g);
+                // the rows of the item: the dense tensor's, or those of its dataset's compacted copy
+                const int64_t row_base = nonempty ? m.ne_off[(size_t)ds] : 0, row_stride = nonempty ? m.ne_np[(size_t)ds] : m.Bp;
+                double lam = 0.0;
                 int k = 0;
                 for (int s = 0; s < S; ++s) {
                     fs.at(m, s, g, so);
                     const double rs = rate_scale ? rate_scale[p * S + s] : 1.0;
+                    if (nonempty) {
+                        // N_s = sum_c w_c R_{s,c} and its slopes, one fma per corner from 0.0; lambda_s = r_s N_s, sources ascending
+                        double N = 0.0;
+                        for (int cnr = 0; cnr < fs.nc; ++cnr) N = std::fma(fs.w[cnr], m.h_rowsum[(size_t)fs.row[cnr]], N);
+                        hN[(size_t)i * S + s] = N;
+                        for (int j = 0; order >= 1 && j < fs.e; ++j) {
+                            double dN = 0.0;
+                            for (int cnr = 0; cnr < fs.nc; ++cnr) dN = std::fma(fs.dw[cnr][j], m.h_rowsum[(size_t)fs.row[cnr]], dN);
+                            hdN[((size_t)i * S + s) * kFacMaxOwn + j] = dN;
+                        }
+                        const double r = rate_scale ? fs.M * rate_scale[p * S + s] : fs.M;
+                        const double lambda = r * N;
+                        lam = lam + lambda;
+                    }
                     for (int cnr = 0; cnr < fs.nc; ++cnr, ++k) {
-                        rowoff[(size_t)i * NR + k] = fs.row[cnr] * m.Bp;
+                        rowoff[(size_t)i * NR + k] = row_base + fs.row[cnr] * row_stride;
                         double* q = &coef[((size_t)i * NR + k) * WC];
                         q[0] = fs.w[cnr];
                         for (int j = 0; order >= 1 && j < fs.e; ++j) q[1 + j] = fs.dw[cnr][j];
@@ -285,7 +330,11 @@ struct FacBatch {
                         for (int j = 0; j < fs.e; ++j) q[1 + j] = rs * fs.dM[j];
                     }
                 }
-                cnt_off[(size_t)i] = dataset_test ? ds * m.Bp : 0;
+                cnt_off[(size_t)i] = nonempty ? m.ne_cnt_off[(size_t)ds] : dataset_test ? ds * m.Bp : 0;
+                if (nonempty) {
+                    tiles[(size_t)i] = (int32_t)(m.ne_np[(size_t)ds] / kTile);
+                    lam_sum[(size_t)i] = lam;
+                }
             }
         });
     }
@@ -295,7 +344,7 @@ struct FacBatch {
         std::vector<std::pair<const void*, size_t>> parts = {
             {rowoff.data(), rowoff.size() * sizeof(int64_t)}, {coef.data(), coef.size() * sizeof(double)},
             {rates.data(), rates.size() * sizeof(double)}, {cnt_off.data(), cnt_off.size() * sizeof(int64_t)},
-            {chain.data(), chain.size() * sizeof(double)}};
+            {chain.data(), chain.size() * sizeof(double)}, {tiles.data(), tiles.size() * sizeof(int32_t)}};
         first_extra = parts.size();
         parts.insert(parts.end(), extra.begin(), extra.end());
         return packed_upload(c, parts, out_doubles * sizeof(double), pu);
@@ -363,6 +412,45 @@ struct FacBatch {
         return BI_OK;
     }
 
+    // run() on the non-empty-bin form: k_sourcewise_nonempty over the items' compacted copies.  An item's blocks are
+    // min(its tiles, kFacBlocks) -- its dataset's list alone decides; the grid's x is the largest of them over the batch (the
+    // other blocks post +0.0), which sizes the partial buffers and the sub-batches and changes no bit of any item.
+    template <class L>
+    int run_nonempty(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+        SourcewiseNonemptyArgs a{};
+        a.ps = (const double*)m.ne_ps.p;
+        a.counts = (const double*)m.ne_cnt.p;
+        a.NR = NR;
+        a.chunks = (int)c->tile_chunks;
+        a.max_blocks = kFacBlocks;
+        for (int s = 0; s < 8; ++s) a.e[s] = s < S ? m.n_own[(size_t)s] : -1;
+        int nbx = 1;
+        for (int32_t t : tiles) nbx = std::max(nbx, std::min((int)t, kFacBlocks));
+        const int64_t per_call = std::max<int64_t>(1, kFacPartialDoubles / ((int64_t)nbx * nsl));
+        for (int64_t j0 = 0; j0 < n_items; j0 += per_call) {
+            const int64_t nj = std::min(per_call, n_items - j0);
+            const int rc = run_item_chunks(c, nj, nbx, nsl, perm + j0 * nsl, slot_lg + j0 * nsl, (double*)pu.host_out(), nullptr, what,
+                                           [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
+                                               SourcewiseNonemptyArgs b = a;
+                                               const int64_t at = j0 + i0;
+                                               b.rowoff = pu.dev<int64_t>(0) + at * NR;
+                                               b.coef = pu.dev<double>(1) + at * NR * WC;
+                                               b.rates = pu.dev<double>(2) + at * SC;
+                                               b.item_cnt = pu.dev<int64_t>(3) + at;
+                                               b.item_tiles = pu.dev<int32_t>(5) + at;
+                                               b.partial = partial;
+                                               b.pflags = pflags;
+                                               c->last_morph_nbx = grid.x; c->last_morph_items = grid.y; c->last_morph_fused = 0;
+                                               return launch(b, grid);
+                                           },
+                                           nbx);
+            if (rc) return rc;
+            pieces += c->last_point_pieces;
+            c->last_point_pieces = pieces;
+        }
+        return BI_OK;
+    }
+
     // the chain rule of item i's gradient sums h (the slots of k_morph_factored<.., GRAD>) to gp [d + S]: sources ascending, own
     // axes ascending within a source; gz [max(d, 1)] is the caller's scratch
     void gradient(int64_t i, const double* h, const double* rate_scale, double* gp, std::vector<double>& gz) const {
@@ -385,7 +473,8 @@ struct FacBatch {
 int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
                   int32_t* status) {
     const bool want_grad = grad != nullptr;
-    FacBatch b(c, want_grad ? 1 : 0);
+    const bool ne = fac_nonempty_on(c);         // the non-empty-bin form (bi_sourcewise_nonempty.h), where it is built and chosen
+    FacBatch b(c, want_grad ? 1 : 0, true, ne);
     const int d = b.d, S = b.S, NSL = factored_slots(b.SC, b.EM, want_grad);
     const double inf = std::numeric_limits<double>::infinity();
     const double qnan = std::numeric_limits<double>::quiet_NaN();
@@ -402,24 +491,45 @@ int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scal
     std::vector<int64_t> perm(n * NSL);
     std::vector<double> slot_lg(n * NSL, 0.0);
     for (size_t q = 0; q < perm.size(); ++q) perm[q] = (int64_t)q;
-    for (size_t i = 0; i < n; ++i) slot_lg[i * NSL] = b.m.h_lgsum[(size_t)(dataset ? dataset[b.live[i]] : 0)];
+    for (size_t i = 0; i < n; ++i) {
+        const double lg = b.m.h_lgsum[(size_t)(dataset ? dataset[b.live[i]] : 0)];
+        slot_lg[i * NSL] = ne ? b.lam_sum[i] + lg : lg;         // (k_finish subtracts sum_s lambda_s + lgsum: one number per item)
+    }
     int rc = b.upload({{perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}}, n * NSL);
     if (rc) return rc;
     const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
-    rc = b.run(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
-               [&](const FactoredArgs& a, dim3 grid) {
-                   const int e = launch_morph_factored(c, b.SC, b.EM, want_grad, a, grid, nt);
-                   return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", b.SC, b.EM) : BI_OK;
-               });
+    if (ne)
+        rc = b.run_nonempty(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
+                            [&](const SourcewiseNonemptyArgs& a, dim3 grid) {
+                                const int e = launch_sourcewise_nonempty(c, b.SC, b.EM, want_grad, a, grid);
+                                return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", b.SC, b.EM) : BI_OK;
+                            });
+    else
+        rc = b.run(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
+                   [&](const FactoredArgs& a, dim3 grid) {
+                       const int e = launch_morph_factored(c, b.SC, b.EM, want_grad, a, grid, nt);
+                       return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", b.SC, b.EM) : BI_OK;
+                   });
     if (rc) return rc;
 
     const double* out = b.out();
-    std::vector<double> gz((size_t)std::max(d, 1));
+    std::vector<double> gz((size_t)std::max(d, 1)), h_ne((size_t)NSL);
     for (int64_t i = 0; i < n_items; ++i) {
         const int64_t p = b.live[(size_t)i];
         const double* h = out + (size_t)i * NSL;
         ll[p] = h[0];
         if (!want_grad || !std::isfinite(h[0])) continue;
+        if (ne) {
+            // the sums over the listed bins less the rows' totals: sum_Z g tau_s - N_s and sum_Z g ups_s,j - d_j N_s are what the
+            // dense kernel's slots hold (sum_b f tau_s, sum_b f ups_s,j); then the same chain rule
+            std::copy(h, h + NSL, h_ne.begin());
+            for (int s = 0; s < S; ++s) {
+                h_ne[(size_t)(1 + s)] = h[1 + s] - b.hN[(size_t)i * S + s];
+                for (int j = 0; j < b.m.n_own[(size_t)s]; ++j)
+                    h_ne[(size_t)(1 + b.SC + s * b.EM + j)] = h[1 + b.SC + s * b.EM + j] - b.hdN[((size_t)i * S + s) * kFacMaxOwn + j];
+            }
+            h = h_ne.data();
+        }
         b.gradient(i, h, rate_scale, grad + p * (d + S), gz);
     }
     return BI_OK;
@@ -450,6 +560,7 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     dev_free(m.real_counts);    // (rows of the previous model's padded length)
     m.real_T = 0;
     release_coarse(c->sw_coarse);   // (groups of the previous model's bins)
+    fac_drop_nonempty(m);           // (compacted copies of the previous model's rows)
     m.d = d; m.S = S; m.B = B;
     m.Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
     m.grid.assign((size_t)d, {});
@@ -496,6 +607,7 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     }
     const int64_t rows = m.row_first[(size_t)S];
     m.h_mus.assign((size_t)rows, 0.0);
+    m.h_rowsum.assign((size_t)rows, 0.0);
     m.row_set.assign((size_t)rows, 0);
     dev_free(m.ps);
     int rc = dev_alloc(c, m.ps, (size_t)rows * m.Bp * sizeof(double));
@@ -528,6 +640,9 @@ int bi_factored_set_anchor(bi_ctx* c, int s, int64_t local_index, const double* 
     // the host buffer is borrowed only for the duration of the call
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     m.h_mus[(size_t)r] = mu;
+    long double total = 0.0L;       // R_{s,c}: the row's total over all bins, rounded once (the non-empty-bin form's lambda_s)
+    for (int64_t b = 0; b < m.B; ++b) total += (long double)ps_row[b];
+    m.h_rowsum[(size_t)r] = (double)total;
     m.row_set[(size_t)r] = 1;
     return BI_OK;
 }
@@ -576,6 +691,7 @@ int bi_factored_set_counts(bi_ctx* c, int64_t T, const double* counts) {
     m.counts = fresh;
     m.T = T;
     m.h_lgsum.swap(lgsum);
+    fac_drop_nonempty(m);           // (lists of the previous counts)
     return fac_sync_lgsum(c, "bi_factored_set_counts");
 }
 

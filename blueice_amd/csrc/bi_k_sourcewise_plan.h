@@ -39,7 +39,13 @@ __device__ __forceinline__ void plan_find_cell(const double* __restrict__ g, int
     t = __ddiv_rn(__dsub_rn(z, gk), __dsub_rn(g[k + 1], gk));
 }
 
-template <int SC>
+//
+// NE = true: the descriptors of k_sourcewise_nonempty instead (the non-empty-bin form, bi_sourcewise_nonempty.h), bit for bit
+// FacBatch::fill's on that route: rowoff = ne_off[ds] + row ne_np[ds], cnt_off = ne_cnt_off[ds], tiles = ne_np[ds] / 512, and
+//     N_s      = sum_c w_c R_{s,c}, one fma per corner from 0.0;   lambda_s = r_s N_s
+//     slot_lg  = (sum_s lambda_s, sources ascending from 0.0) + lgsum[ds]
+// (the lane of source slot s computes lambda_s, lane 0 collects them in order).  NE = false is the code it was.
+template <int SC, bool NE = false>
 __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePlanArgs a) {
     static_assert(SC == 2 || SC == 4 || SC == 8, "the source slots of a point share a wave");
     const int64_t gid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -64,6 +70,14 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
     for (int q = 0; q < 8; ++q)
         if (q < s && a.e[q] >= 0) first += 1 << a.e[q];
     double rate = 0.0;
+    [[maybe_unused]] double lambda = 0.0;
+    [[maybe_unused]] int64_t ne_off = 0, ne_np = 0;
+    if constexpr (NE) {
+        const int64_t ds = a.ds[i];
+        const int64_t t = (ds < 0 || ds >= m.T) ? 0 : ds;      // (a rejected point: in-range descriptors that never run)
+        ne_off = m.ne_off[t];
+        ne_np = m.ne_np[t];
+    }
     if (real) {
         int64_t base = m.row_first[s];
         double t[kFacMaxOwn];
@@ -83,6 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
         }
         const int nc = 1 << e;
         double M = 0.0;
+        [[maybe_unused]] double N = 0.0;
 #pragma unroll
         for (int c = 0; c < (1 << kFacMaxOwn); ++c) {
             if (c < nc) {
@@ -96,19 +111,30 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
                         wc = __dmul_rn(wc, up ? t[j] : __dsub_rn(1.0, t[j]));
                     }
                 const int64_t row = i * a.NR + first + c;
-                a.rowoff[row] = r * m.Bp;
+                if constexpr (NE) {
+                    a.rowoff[row] = ne_off + r * ne_np;
+                    N = __fma_rn(wc, m.rowsum[r], N);
+                } else {
+                    a.rowoff[row] = r * m.Bp;
+                }
                 a.coef[row * a.W] = wc;
                 for (int x = 1; x < a.W; ++x) a.coef[row * a.W + x] = 0.0;
                 M = __dadd_rn(M, __dmul_rn(m.mus[r], wc));
             }
         }
         rate = __dmul_rn(M, a.rs[i * m.S + s]);
+        if constexpr (NE) lambda = __dmul_rn(rate, N);
         if (!(rate >= 0.0 && rate < __builtin_huge_val())) flags |= (unsigned)BI_ST_UNPHYSICAL;
     }
     a.rates[i * SC + s] = rate;            // (a padded slot: zero)
 
 #pragma unroll
     for (int x = 1; x < SC; x <<= 1) flags |= (unsigned)__shfl_xor((int)flags, x);
+    [[maybe_unused]] double lam_sum = 0.0;
+    if constexpr (NE) {
+#pragma unroll
+        for (int q = 0; q < SC; ++q) lam_sum = __dadd_rn(lam_sum, __shfl(lambda, q, SC));      // (a padded slot adds +0.0)
+    }
     if (s == 0) {
         const int64_t ds = a.ds[i];
         const int32_t status = (ds < 0 || ds >= m.T) ? BI_ST_BAD_DATASET
@@ -117,8 +143,14 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
                                                                : 0;
         a.status[i] = status;
         a.live[i] = status == 0 ? 1u : 0u;
-        a.cnt_off[i] = status == 0 ? ds * m.Bp : 0;
-        a.slot_lg[i] = status == 0 ? m.lgsum[ds] : 0.0;
+        if constexpr (NE) {
+            a.cnt_off[i] = status == 0 ? m.ne_cnt_off[ds] : 0;
+            a.slot_lg[i] = status == 0 ? __dadd_rn(lam_sum, m.lgsum[ds]) : 0.0;
+            a.tiles[i] = (int32_t)(ne_np / kTile);
+        } else {
+            a.cnt_off[i] = status == 0 ? ds * m.Bp : 0;
+            a.slot_lg[i] = status == 0 ? m.lgsum[ds] : 0.0;
+        }
         a.perm[i] = status == 0 ? i : -1;
         if (status != 0) a.out[i] = -__builtin_huge_val();
     }

@@ -88,6 +88,7 @@ const ParamDef kParams[] = {
     {"dot_blocks_per_cu", kParamRW, BI_P_GET(c->dot_blocks_per_cu), BI_P_RANGE(0, 16, dot_blocks_per_cu, "dot_blocks_per_cu in [0, 16]")},
     {"dot_lanes", kParamRW, BI_P_GET(c->dot_lanes), BI_P_SET(c->dot_lanes = (v == 16 || v == 8 || v == 4) ? v : 0)},
     {"compact_budget", kParamRW, BI_P_GET(c->compact_budget), BI_P_SET(c->compact_budget = v)},
+    {"sourcewise_form", kParamRW, BI_P_GET(c->sourcewise_form), BI_P_RANGE(0, 1, sourcewise_form, "sourcewise_form: 0 dense, 1 the non-empty-bin form where it is built")},
     {"toy_offset", kParamRW, BI_P_GET(c->toy_offset), BI_P_RANGE(0, INT64_MAX, toy_offset, "toy_offset >= 0")},
     {"narrow_counts", kParamRW, BI_P_GET(c->narrow_counts), BI_P_FLAG(narrow_counts)},
     {"packed_rows", kParamRW, BI_P_GET(c->packed_rows), BI_P_FLAG(packed_rows)},
@@ -137,6 +138,8 @@ const ParamDef kParams[] = {
     BI_P_RO("ps_nonneg", c->ps_nonneg ? 1 : 0),
     BI_P_RO("dense_counts", (c->data_ready && c->dense_counts) ? 1 : 0),
     BI_P_RO("coarse_cells", c->coarse.set ? c->coarse.C : 0),
+    BI_P_RO("sourcewise_nonempty_ready", c->fac.ne_ready ? 1 : 0),
+    BI_P_RO("sourcewise_nonempty_bytes", c->fac.ne_ready ? c->fac.ne_bytes : 0),
     BI_P_RO("compact_sorted", (c->compact_ready && c->compact_sorted) ? 1 : 0),
     BI_P_RO("nnz_total", c->csr_ready ? c->h_nz_off.back() : -1),
     BI_P_RO("last_scan_nslots", c->last_scan_nslots),

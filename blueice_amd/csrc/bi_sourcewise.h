@@ -201,6 +201,7 @@ int bi_sourcewise_generate_toys(bi_ctx* c, int64_t H, const double* z, const dou
     m.counts = fresh;
     m.T = T;
     m.h_lgsum.swap(lgsum);
+    fac_drop_nonempty(m);           // (lists of the previous counts)
     return fac_sync_lgsum(c, who);
 }
 

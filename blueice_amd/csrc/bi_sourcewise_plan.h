@@ -10,6 +10,10 @@
 // without a stream synchronisation (counters[4]).  A live point's sums are the blocks' of bi_eval_factored, added in its order:
 // ll is bit for bit the host path's.  A rejected point's blocks return at entry and k_finish skips it (perm -1, written by the
 // planner with the point's -inf: so the perm is the planner's, per call of queue(), not an identity filled once).
+// Where the non-empty-bin form is built and chosen (fac_nonempty_on; bi_sourcewise_nonempty.h) the same queue runs the planner's NE
+// variant -> k_sourcewise_nonempty -> k_finish: the descriptors point into the datasets' compacted copies, the tile count is per
+// item, and the grid's x is the most blocks an item of any dataset of the store takes -- known when the form is built, so still
+// nothing is read and nothing waited for.
 #pragma once
 
 namespace {
@@ -17,15 +21,18 @@ namespace {
 struct PlannedItems {
     bi_ctx* c;
     const bi_ctx::Factored& m;
-    int SC, EM, W, NR, nbx;
+    int SC, EM, W, NR;
+    bool ne;                    // the non-empty-bin form (bi_sourcewise_nonempty.h): the planner's NE variant and k_sourcewise_nonempty
+    int nbx;                    // (ne: the most blocks an item of ANY dataset of the store takes -- known without a host read)
     int64_t n_max = 0, per_call = 1;
-    ScratchBuf status, live, rowoff, coef, rates, cnt_off, slot_lg, perm, partial, pflags;
+    ScratchBuf status, live, rowoff, coef, rates, cnt_off, slot_lg, perm, partial, pflags, tiles;
     FactoredArgs fa{};
+    SourcewiseNonemptyArgs na{};
     SourcewisePlanArgs pa{};
 
     explicit PlannedItems(bi_ctx* ctx)
         : c(ctx), m(ctx->fac), SC(m.S <= 2 ? 2 : m.S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM), NR(m.n_rows_point),
-          nbx(std::min((int)(m.Bp / kTile), kFacBlocks)) {}
+          ne(fac_nonempty_on(ctx)), nbx(ne ? m.ne_max_nbx : std::min((int)(m.Bp / kTile), kFacBlocks)) {}
 
     // room for n_max items, both argument blocks
     int init(int64_t n) {
@@ -39,6 +46,7 @@ struct PlannedItems {
             (rc = dev_alloc(c, slot_lg, un * sizeof(double))) || (rc = dev_alloc(c, perm, un * sizeof(int64_t))) ||
             (rc = dev_alloc(c, partial, part * sizeof(double))) || (rc = dev_alloc(c, pflags, part * sizeof(unsigned))))
             return rc;
+        if (ne && (rc = dev_alloc(c, tiles, un * sizeof(int32_t)))) return rc;
         fa = FacBatch(c, 0).args();
         const char* g = (const char*)m.geom.p;
         pa.g.anchors = (const double*)(g + m.geom_off[0]);
@@ -54,6 +62,19 @@ struct PlannedItems {
         for (int s = 0; s < 8; ++s) pa.e[s] = fa.e[s];
         pa.status = (int32_t*)status.p; pa.live = (unsigned*)live.p; pa.rowoff = (int64_t*)rowoff.p; pa.coef = (double*)coef.p;
         pa.rates = (double*)rates.p; pa.cnt_off = (int64_t*)cnt_off.p; pa.slot_lg = (double*)slot_lg.p; pa.perm = (int64_t*)perm.p;
+        if (ne) {
+            pa.g.rowsum = (const double*)(g + m.geom_off[7]);
+            pa.g.ne_off = (const int64_t*)m.ne_tab.p;
+            pa.g.ne_np = pa.g.ne_off + m.T;
+            pa.g.ne_cnt_off = pa.g.ne_off + 2 * m.T;
+            pa.tiles = (int32_t*)tiles.p;
+            na.ps = (const double*)m.ne_ps.p;
+            na.counts = (const double*)m.ne_cnt.p;
+            na.NR = NR;
+            na.chunks = fa.chunks;
+            na.max_blocks = kFacBlocks;
+            for (int s = 0; s < 8; ++s) na.e[s] = fa.e[s];
+        }
         return BI_OK;
     }
 
@@ -62,7 +83,7 @@ struct PlannedItems {
     int queue(int64_t n, const double* z, const double* rs, const int64_t* ds, double* out, const char* who, int64_t* launches) {
         SourcewisePlanArgs p = pa;
         p.z = z; p.rs = rs; p.ds = ds; p.n = n; p.out = out;
-        int rc = launch_sourcewise_plan(c, SC, p);
+        int rc = ne ? launch_sourcewise_plan_nonempty(c, SC, p) : launch_sourcewise_plan(c, SC, p);
         if (rc) return fail(c, rc, "%s: no planner variant for %d source slots", who, SC);
         HIP_TRY(c, hipGetLastError());
         int64_t queued = 1;
@@ -81,7 +102,15 @@ struct PlannedItems {
                 b.pflags = (unsigned*)pflags.p;
                 const dim3 grid((unsigned)nbx, (unsigned)ni);
                 c->last_morph_nbx = grid.x; c->last_morph_items = grid.y; c->last_morph_fused = 0;
-                if ((rc = launch_morph_factored(c, SC, EM, false, b, grid, nt)))
+                if (ne) {
+                    SourcewiseNonemptyArgs q = na;
+                    q.rowoff = b.rowoff; q.coef = b.coef; q.rates = b.rates; q.item_cnt = b.item_cnt; q.live = b.live;
+                    q.item_tiles = (const int32_t*)tiles.p + i0;
+                    q.partial = b.partial; q.pflags = b.pflags;
+                    rc = launch_sourcewise_nonempty(c, SC, EM, false, q, grid);
+                } else
+                    rc = launch_morph_factored(c, SC, EM, false, b, grid, nt);
+                if (rc)
                     return fail(c, rc, "%s: no kernel variant for %d source slots with %d own axes", who, SC, EM);
                 launch_finish(c, (const double*)partial.p, (const unsigned*)pflags.p, nbx, 1, ni, (const int64_t*)perm.p + i0,
                               (const double*)slot_lg.p + i0, out, nullptr);

@@ -59,6 +59,16 @@ launches queued on one stream and the step loop waits for nothing.  `blueice_amd
 `datasets=` after `simulate_toys_points` and with `GaussianPrior` constraints on the device.  The bound lf.sample_posterior and
 lf.bestfit_emcee stay refused and name these spellings.
 
+The counts are dense, and by default every evaluation walks every bin.  `likelihood_config['nonempty_bins']` -- False (default),
+True or 'auto' (build when at most a quarter of the bins of all datasets hold events) -- adds the non-empty-bin form of the data
+(bi_sourcewise_build_nonempty; `ctx.build_nonempty()` / `ctx.drop_nonempty()`): per dataset the list of bins with events and a
+compacted copy of the model's rows over it, so that ll = sum over the listed bins of n log mu, less sum_s r_s N_s with N_s the
+interpolated row totals, less the lgamma sum.  `set_data`, `set_binned_data` and `simulate_toys_points` rebuild it after they
+change the counts; `lf(**params)`, eval_points, values_and_gradients, the native fits, scans, intervals, toy fits, `neyman_thresholds`
+and the sampler then read the listed bins only, with no change of their own (results agree with the dense form's to rounding, not
+bit for bit).  Hessians, Fisher information, goodness of fit, the expectation, coarse views and the real-valued store keep reading
+the dense store.
+
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
 full_output calls, eval_toys*, grids (grid_scan), Hessians and sampling on an Asimov view.
@@ -184,6 +194,22 @@ class SourceWiseContext:
         self._counts = None                     # the toys exist on the device only
         self.T = int(n_toys.sum())
         return np.where(n_toys > 0, 0, -1).astype(np.int32)
+
+    # -- the non-empty-bin form of the data (bi_sourcewise_build_nonempty) ------------------
+    def build_nonempty(self):
+        """Build the non-empty-bin form of all T datasets of the store as it stands: their lists of bins with events and, per
+        dataset, a compacted copy of the model's rows over its list.  While it exists (and the parameter `sourcewise_form` is 1)
+        eval, eval_grad, fit_batched, eval_planned and sample_stretch read the listed bins only; every other call keeps reading
+        the dense store.  New counts, toys or a new model release it.  -> list lengths [T].  ValueError (BI_ERR_INVALID) when
+        the copies would exceed the parameter `compact_budget`: nothing is built then."""
+        dev = self._dev
+        nnz = np.zeros(max(int(self.T), 1), dtype=np.int64)
+        dev._check(dev._lib.bi_sourcewise_build_nonempty(dev._h, ptr(nnz)))
+        return nnz[:int(self.T)]
+
+    def drop_nonempty(self):
+        """Release the non-empty-bin form: the calls above read the dense store again."""
+        self._dev._check(self._dev._lib.bi_sourcewise_drop_nonempty(self._dev._h))
 
     # -- evaluation ------------------------------------------------------------------------
     def _point_args(self, z, rate_scale, dataset):
@@ -585,6 +611,34 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         self.is_data_set = False
         self.is_prepared = True
 
+    def _rebuild_nonempty(self):
+        """likelihood_config['nonempty_bins'] after the counts have changed (new counts release the form): False (default) never
+        builds it, True always, 'auto' when at most a quarter of the bins of all datasets hold events (the grid model's rule).
+        -> whether the form is built"""
+        setting = self.config.get('nonempty_bins', False)
+        if setting is None or setting is False:
+            return False
+        ctx = self.ctx
+        if setting is True:
+            ctx.build_nonempty()
+            return True
+        if setting != 'auto':
+            raise ValueError("likelihood_config['nonempty_bins'] is False, True or 'auto', not %r" % (setting,))
+        bins = int(ctx.T) * int(ctx.B)
+        if ctx._counts is not None:                     # uploaded counts: the host copy says
+            if 4 * int(np.count_nonzero(ctx._counts)) > bins:
+                return False
+            ctx.build_nonempty()
+            return True
+        try:                                            # toys on the device: the build counts them
+            nnz = ctx.build_nonempty()
+        except ValueError:                              # (beyond compact_budget: stay dense)
+            return False
+        if 4 * int(np.sum(nnz)) > bins:
+            ctx.drop_nonempty()
+            return False
+        return True
+
     @_needs_preparation
     def set_data(self, d):
         """Bin the events of `d` in the analysis space on the device (numpy.histogramdd semantics) and make the counts
@@ -593,6 +647,7 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         edges = [e for _, e in self.base_model.config['analysis_space']]
         self.ctx.set_counts(self.ctx.histogram_events(edges, self.base_model.to_analysis_dimensions(d)))
         self._binned = None
+        self._rebuild_nonempty()
 
     @_needs_preparation
     def set_binned_data(self, counts):
@@ -605,6 +660,7 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         self.ctx.set_counts(counts)
         self._binned = None
         self.is_data_set = True
+        self._rebuild_nonempty()
 
     @property
     def data_events_per_bin(self):
@@ -637,6 +693,7 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         self._binned = None
         self.is_data_set = True
         self.toy_truth = np.repeat(np.arange(H), n_toys)
+        self._rebuild_nonempty()
         return methods
 
     # -- evaluation ------------------------------------------------------------------------

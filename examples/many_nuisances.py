@@ -61,6 +61,10 @@ blueice_amd.coarse.expected_coarse_points call over draws of the chain.
 --measure-sampler times, at the same source-wise shape, bi_sample_stretch_sourcewise against the host engine (the same move in
 NumPy, one bi_eval_factored call per half-step) at 40 and 1024 walkers for 50 steps, and bi_eval_sourcewise_planned against
 bi_eval_factored values-only at 1, 64 and 4096 points per call; the lines go to profiles/sourcewise_sampler_measure.txt too.
+
+--measure-nonempty times, at the same shape, the non-empty-bin form of the data (bi_sourcewise_build_nonempty) against the dense
+store on the same context at 10^3 ... 2.5 10^5 events in the 10^6 bins: bi_eval_factored, its kernels alone, the build, the
+sampler and a lock-step iteration over 256 toys; the lines go to profiles/sourcewise_nonempty_measure.txt too.
 """
 import argparse
 import time
@@ -79,6 +83,8 @@ ap.add_argument('--measure-coarse-jacobian', action='store_true',
 ap.add_argument('--posterior', action='store_true', help='a posterior chain over all twelve parameters: credible limit and projection band')
 ap.add_argument('--measure-sampler', action='store_true',
                 help='time bi_sample_stretch_sourcewise against the host engine, and bi_eval_sourcewise_planned against bi_eval_factored')
+ap.add_argument('--measure-nonempty', action='store_true',
+                help='time the non-empty-bin form of the data against the dense store on the same context (sourcewise_form)')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -683,6 +689,125 @@ def measure_sampler():
     fac.close()
 
 
+def measure_nonempty():
+    """The non-empty-bin form of the data (bi_sourcewise_build_nonempty) against the dense store on the same context, toggled with
+    the parameter sourcewise_form, at the measured source-wise shape and Poisson data of about 10^3, 10^4, 10^5 and 2.5 10^5 events
+    in its 10^6 bins (the last at the quarter rule of nonempty_bins='auto'): bi_eval_factored values-only and with the gradient
+    at 1, 64 and 4096 points per call, the kernels alone by device events, the build for one dataset and for 256 toys, and
+    bi_sample_stretch_sourcewise at 40 and 1024 walkers.  Alternated calls, medians with quartiles.  Written to
+    profiles/sourcewise_nonempty_measure.txt as well."""
+    import os
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B, steps = 5, args.measure_bins ** 3, 50
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])                   # relative rates; the scale is per dataset
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    mid = n_a // 2
+    shape = sum(mus[s, mid] * rows[s, mid] for s in range(S))
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    def form(v):
+        fac.set_param('sourcewise_form', v)
+
+    def alternated(pairs, rounds):
+        """pairs: (name, form, call); the form is set outside the timed region -> {name: times}"""
+        times = {name: [] for name, _, _ in pairs}
+        for rnd in range(3 + rounds):
+            for name, v, call in pairs:
+                form(v)
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 3:
+                    times[name].append(time.perf_counter() - t0)
+        form(1)
+        return times
+
+    say('# examples/many_nuisances.py --measure-nonempty --measure-bins %d --rounds %d on %s' % (args.measure_bins, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>), %d anchors, %d bins; every other class: not measured' % (d, S, n_a, B))
+    for events in (1e3, 1e4, 1e5, 2.5e5):
+        scale = events / shape.sum()
+        counts = rng.poisson(scale * shape).astype(float)
+        rs_scale = scale                                      # the rate scales carry the dataset's normalisation
+        fac.set_counts(counts)
+        t_build = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            nnz = fac.build_nonempty()
+            t_build.append(time.perf_counter() - t0)
+        say('%.1e events: %d listed bins of %d (%.1f %%), compacted copies %.2f MB, bi_sourcewise_build_nonempty (T = 1) %s'
+            % (events, int(nnz[0]), B, 100.0 * nnz[0] / B, fac.get_param('sourcewise_nonempty_bytes') / 1e6, quartiles(t_build)))
+        for P in (1, 64, 4096):
+            z, r = rng.uniform(-1.9, 1.9, (P, d)), rs_scale * rng.uniform(0.8, 1.2, (P, S))
+            form(1)
+            a = fac.eval_grad(z, r)
+            form(0)
+            b = fac.eval_grad(z, r)
+            rel = np.max(np.abs(a[0] - b[0]) / np.abs(b[0]))
+            rounds = args.rounds if P < 4096 else max(5, args.rounds // 4)
+            t = alternated([('listed, values', 1, lambda: fac.eval(z, r)), ('dense, values', 0, lambda: fac.eval(z, r)),
+                            ('listed, gradient', 1, lambda: fac.eval_grad(z, r)), ('dense, gradient', 0, lambda: fac.eval_grad(z, r))], rounds)
+            for what in ('values', 'gradient'):
+                lt, dt = t['listed, ' + what], t['dense, ' + what]
+                say('%.1e events, %4d points per call, bi_eval_factored %-8s non-empty %s   dense %s   ratio %.2f   (max |ll difference| / |ll| %.1e)'
+                    % (events, P, what, quartiles(lt), quartiles(dt), np.median(dt) / np.median(lt), rel))
+        # the kernels alone at 64 points, from device events around the launches
+        z, r = rng.uniform(-1.9, 1.9, (64, d)), rs_scale * rng.uniform(0.8, 1.2, (64, S))
+        for name, v in (('k_sourcewise_nonempty', 1), ('k_morph_factored', 0)):
+            form(v)
+            fac._dev.profile(True)
+            ks = []
+            for _ in range(args.rounds):
+                fac.eval_grad(z, r)
+                ks.append(fac._dev.profile_read()[1] * 1e-3)
+            fac._dev.profile(False)
+            say('%.1e events, 64 points, with gradient, kernels alone (%s + k_finish): %s' % (events, name, quartiles(ks)))
+        form(1)
+        if events == 1e4:
+            kind = np.array([1] * S + [0] * d, dtype=np.int32)
+            index = np.array(list(range(S)) + list(range(d)), dtype=np.int32)
+            lo, hi = np.array([0.] * S + [-2.] * d), np.array([np.inf] * S + [2.] * d)
+            z0, one = np.zeros(d), np.ones(S)
+            for W in (40, 1024):
+                x0 = np.concatenate([rs_scale * rng.uniform(0.98, 1.02, (W, S)), rng.uniform(-0.1, 0.1, (W, d))], axis=1)[None]
+                call = lambda: fac.sample_stretch(W, kind, index, z0, one, one, None, x0, lo, hi, steps, seed=7)
+                t = alternated([('listed', 1, call), ('dense', 0, call)], max(3, args.rounds // 4))
+                say('%.1e events, bi_sample_stretch_sourcewise W = %4d, %d steps: non-empty %s   dense %s   ratio %.2f'
+                    % (events, W, steps, quartiles(t['listed']), quartiles(t['dense']), np.median(t['dense']) / np.median(t['listed'])))
+            # 256 toys of this size: the build for all of them
+            fac.generate_toys_points(np.zeros((1, d)), np.full((1, S), rs_scale), 256, seed=3)
+            t_build = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                nnz = fac.build_nonempty()
+                t_build.append(time.perf_counter() - t0)
+            say('%.1e events, 256 toys: %d listed bins in all, compacted copies %.1f MB, bi_sourcewise_build_nonempty (T = 256) %s'
+                % (events, int(nnz.sum()), fac.get_param('sourcewise_nonempty_bytes') / 1e6, quartiles(t_build)))
+            P = 256
+            z, r = rng.uniform(-0.5, 0.5, (P, d)), rs_scale * rng.uniform(0.9, 1.1, (P, S))
+            ds = np.arange(P)
+            t = alternated([('listed', 1, lambda: fac.eval_grad(z, r, ds)), ('dense', 0, lambda: fac.eval_grad(z, r, ds))], max(5, args.rounds // 4))
+            say('%.1e events, 256 toys, one point per toy with gradient (an iteration of a lock-step fit): non-empty %s   dense %s   ratio %.2f'
+                % (events, quartiles(t['listed']), quartiles(t['dense']), np.median(t['dense']) / np.median(t['listed'])))
+    say('# not measured: inference.toy_mc_fits through the likelihood class, every class but <4, 1>, other shapes')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_nonempty_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+
+
 def posterior():
     """A chain over all twelve parameters with their constraints on the device; the credible upper limit on the signal's
     multiplier beside one_parameter_interval's; the posterior band of the projection on the first analysis axis."""
@@ -724,6 +849,9 @@ def posterior():
 
 if args.measure_sampler:
     measure_sampler()
+    raise SystemExit(0)
+if args.measure_nonempty:
+    measure_nonempty()
     raise SystemExit(0)
 if args.posterior:
     posterior()

@@ -807,6 +807,36 @@ int bi_sample_stretch_sourcewise(bi_ctx* ctx, int64_t E, int W, int F, const int
                                  int64_t first_ensemble, const double* prior_mean, const double* prior_sigma,
                                  const double* prior_const, double* chain, double* ll, int64_t* n_accepted, int64_t* counters);
 
+/* ... and the non-empty-bin form of its data.  The store's counts are dense, and every evaluation of every point walks all B
+ * bins; data and toys of a large binned analysis hold events in a small fraction of them.  Templates of a source-wise model are
+ * finite and >= 0 and rates outside [0, inf) are BI_ST_UNPHYSICAL, so mu_b >= 0 in every bin, and for dataset t with the list
+ * Z_t = {b : n_b != 0} (ascending bins)
+ *     ll = sum_{b in Z_t} n_b log mu_b  -  sum_s lambda_s  -  sum_b lgamma(n_b + 1),     lambda_s = r_s sum_c w_c R_{s,c}
+ * holds without any condition: corners c ascending, one fma per corner from 0.0; sources ascending; R_{s,c} the total of anchor
+ * row (s, c) over ALL bins, summed once in long double by bi_factored_set_anchor and rounded to double; the sum of lambda_s and
+ * of lgamma is one number per point, subtracted once.  mu_b and the gradient's columns are the dense route's fma chains; the
+ * gradient uses g_b = n_b (1 / mu_b) at the listed bins:
+ *     d ll / d rs_s = M_s (sum_Z g tau_s - N_s),   N_s = sum_c w_c R_{s,c}
+ *     d ll / d z_i  = sum_{s: i in O_s} rs_s [M_s (sum_Z g ups_s,i - d_i N_s) + d_i M_s (sum_Z g tau_s - N_s)]
+ * A listed bin with mu_b = 0 or a listed count that is no integer gives -inf, and the gradient is nan wherever ll is not finite;
+ * status words and early exits are unchanged.  The results agree with the dense route's to rounding, not bit for bit.
+ *   bi_sourcewise_build_nonempty   builds the form for all T datasets of the store as it stands (BI_ERR_STATE without counts): the
+ *                                  lists, and per dataset a compacted copy of all the model's rows over its list, padded with
+ *                                  zeros to whole tiles of tile_bins (at least one), the compacted counts beside it.  nnz [T] (or
+ *                                  NULL) receives the list lengths.  BI_ERR_INVALID, naming the bytes, when the copies would take
+ *                                  more than compact_budget: nothing is built then and the context goes on evaluating densely.
+ *   bi_sourcewise_drop_nonempty    releases the form.  So does everything that replaces the counts or the model:
+ *                                  bi_factored_begin, bi_factored_set_counts, bi_sourcewise_generate_toys.
+ * Where the form is built and the parameter sourcewise_form is 1 (the default), bi_eval_factored (value and gradient; with it
+ * bi_fit_batched_factored, whose objective it is), bi_eval_sourcewise_planned and bi_sample_stretch_sourcewise run on it, their
+ * signatures and contracts unchanged: a point's bits do not depend on the batch or on the other datasets of the call (an item's
+ * blocks follow from its own list's length), a values-only call gives the bits of the call with the gradient, the planned route
+ * and the sampler equal the host route bit for bit.  Every other source-wise call keeps reading the dense store, which stays
+ * resident and valid.  Nothing builds the form unless asked: a context that never calls bi_sourcewise_build_nonempty runs the
+ * code it ran without it. */
+int bi_sourcewise_build_nonempty(bi_ctx* ctx, int64_t* nnz /*[T] or NULL*/);
+int bi_sourcewise_drop_nonempty(bi_ctx* ctx);
+
 /* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
  * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
  * lists one after the other; any order, finite).  The first n_keep variables are kept, the others reduced:
@@ -1048,6 +1078,11 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *   scan_split        scans with sparse = 0 over mostly empty data: non-empty-bin pass + validity pass of every bin on the
  *                     matrix cores (k_scan_valid) instead of the per-bin terms in every bin (1)
  *   compact_budget    bytes of device memory the compacted templates of the non-empty-bin form may take
+ *                     (also the bound of bi_sourcewise_build_nonempty's copies)
+ *   sourcewise_form   source-wise models: 1 (default) = bi_eval_factored, bi_fit_batched_factored, bi_eval_sourcewise_planned and
+ *                     bi_sample_stretch_sourcewise run on the non-empty-bin form where bi_sourcewise_build_nonempty has built
+ *                     it; 0 = they read the dense store although it is built.  Read-only sourcewise_nonempty_ready (1 while the
+ *                     form is built) and sourcewise_nonempty_bytes (the bytes of its compacted copies, 0 when it is not)
  *   toy_offset        bi_generate_toys: toy t of a call is dataset toy_offset + t of the seed's random stream, so ranks
  *                     that each generate a range of one toy-MC ensemble draw the same toys as one process would (0)
  *   scan_pow          scans over dense data on the matrix cores run on a copy of the template rows whose bins are ordered by
