@@ -111,6 +111,8 @@ SIGNATURES = {
     'bi_sourcewise_build_nonempty': (C.c_int, [_p, _p]),
     'bi_sourcewise_drop_nonempty': (C.c_int, [_p]),
     'bi_grid_reduce': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
+    'bi_eval_sourcewise_scan': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
+    'bi_grid_reduce_sourcewise': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, _p, _p, _p]),
     'bi_eval_datasets': (C.c_int, [_p, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),
     'bi_eval_datasets_points_device': (C.c_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p]),

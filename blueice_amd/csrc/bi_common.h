@@ -22,6 +22,8 @@
 //                         descriptors, on the device)                                        bi_k_sourcewise_plan.h
 //     tu_sourcewise_nonempty.hip   k_sourcewise_nonempty (value + gradient sums of one point of a source-wise model over the
 //                         non-empty bins of its dataset), k_sourcewise_gather (the compacted copies)   bi_k_sourcewise_nonempty.h
+//     tu_sourcewise_scan.hip   k_sourcewise_scan_key, _cut, _groups, _fill (the planner's per-point descriptors -> the 16-point work
+//                         items of k_scan_mfma, on the device)                               bi_k_sourcewise_scan.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
 //     tu_grid.hip         k_grid_points, k_grid_reduce, k_grid_finish (gridded likelihoods)      bi_k_grid.h
 //     tu_coarse.hip       k_morph_coarse, k_morph_coarse_jac, k_coarse_finish, k_coarse_list (coarse views: projections, rebinning, their derivatives)   bi_k_coarse.h
@@ -145,6 +147,13 @@ int launch_sourcewise_plan_nonempty(bi_ctx* c, int SC, const SourcewisePlanArgs&
 int launch_sourcewise_nonempty(bi_ctx* c, int SC, int EM, bool grad, const SourcewiseNonemptyArgs& a, dim3 grid);
 // k_sourcewise_gather: the compacted copies of grid.z datasets from a.t0 on
 void launch_sourcewise_gather(bi_ctx* c, const SourcewiseGatherArgs& a, dim3 grid);
+// the scan planner of source-wise points (bi_k_sourcewise_scan.h; no launcher times its kernel, the host half bi_sourcewise_scan.h
+// opens the EventScope): sort keys of a.n points; groups of equal keys cut every `cut` points; group tables and counts; the
+// descriptors of the a.n_valid sorted positions in front of the rejected points
+void launch_sourcewise_scan_key(bi_ctx* c, const SourcewiseScanArgs& a);
+void launch_sourcewise_scan_cut(bi_ctx* c, int64_t* gstart, int64_t n, int64_t cut);
+void launch_sourcewise_scan_groups(bi_ctx* c, const SourcewiseScanArgs& a);
+void launch_sourcewise_scan_fill(bi_ctx* c, const SourcewiseScanArgs& a);
 // k_scan_mfma<CB, KG, MASK, PROD>: rows in bin order; prod = the compacted rows' product form (CB = 2 only)
 void launch_scan_mfma(bi_ctx* c, int cb, bool prod, int NS, dim3 grid, const ScanArgs& a);
 // k_scan_valid<4, KG, MASK>: the validity pass of split scans

@@ -182,6 +182,7 @@ struct bi_ctx {
         DevBuf ne_ps, ne_cnt, ne_tab;
     } fac;
     int64_t sourcewise_form = 1;                 // 0: source-wise evaluations read the dense store although the non-empty-bin form is built
+    int64_t sourcewise_scan_timed = 3;           // profiling: bit 0 = the scan route's planner, bit 1 = its matrix-core launches are timed
 
     // the coarse binning of bi_set_coarse_binning (bi_coarse.h): tensor-product groups of fine bins, b = r L + x with L the
     // fine bins of the last analysis axis.  Released by a new model.

@@ -231,6 +231,47 @@ struct SourcewiseNonemptyArgs {
     const unsigned* live;      // [items] planned items (GRAD = false): 0 = rejected; NULL on the host paths
 };
 
+// The scan planner of source-wise points (bi_k_sourcewise_scan.h): from what k_sourcewise_plan<SC, NE = true> wrote per point to
+// ScanArgs' descriptors per 16-point item.  One block of arguments for its four kernels; every pointer is device memory.
+struct SourcewiseScanArgs {
+    // per point, the planner's output (and the staged datasets)
+    const int32_t* status;     // [n]
+    const int64_t* rowoff_pt;  // [n][NR]
+    const double* coef_pt;     // [n][NR][W], column 0 = w_c
+    const double* rates_pt;    // [n][SC]
+    const int64_t* cnt_off_pt; // [n]
+    const int32_t* tiles_pt;   // [n]
+    const double* slot_lg_pt;  // [n]
+    const int64_t* ds;         // [n]
+    const int64_t* ne_off;     // [T] where a dataset's compacted rows start
+    const int64_t* ne_np;      // [T] their length
+    int64_t n, T;
+    int NR, W, SC, S;
+    int first[8];              // first row of source s among a point's NR rows
+    int64_t row_first[8];      // first row of source s in the model
+    int64_t mult[8];           // mixed radix: the product of the row counts of the sources behind s
+    uint64_t bad_key;          // (all cell tuples) * T: the key of rejected points, one above every other
+    // k_sourcewise_scan_key
+    uint64_t* keys;            // [n]
+    int64_t* idx;              // [n]
+    // sorted order: k_sourcewise_scan_cut, k_sourcewise_scan_groups, k_sourcewise_scan_fill
+    const int64_t* idx_s;      // [n] the point at every sorted position
+    int64_t* gstart;           // [n] first sorted position of the position's group
+    const int64_t* item_incl;  // [n] its item + 1
+    const int64_t* gid_incl;   // [n] its group + 1
+    int64_t cut;               // points (a multiple of 16) after which a group of equal keys is cut into a group of its own
+    int64_t* scal;             // [0] valid points (in), [1] items, [3] most items of a group, [6] groups (out)
+    int64_t* grp_first;        // [groups]
+    int32_t* grp_items;        // [groups]
+    int64_t n_valid;           // k_sourcewise_scan_fill: the sorted positions in front of the rejected points
+    int64_t* rowoff;           // [items][NR]
+    double* coef;              // [items][NR][16]
+    int64_t* item_cnt;         // [items]
+    int32_t* item_tiles;       // [items]
+    double* slot_lg;           // [items][16]
+    int64_t* perm;             // [items][16] the point of the slot, -1: padding
+};
+
 // k_sourcewise_gather (bi_k_sourcewise_nonempty.h): the compacted copies of the datasets t0 + blockIdx.z
 struct SourcewiseGatherArgs {
     const double* ps;          // [rows][Bp] the dense rows

@@ -6,7 +6,13 @@
 // variables' map, the chunk's rows and their evaluation are ResidentPoints' (bi_varmap.h), shared with bi_sampler.h, whose
 // header says what a chunk costs on the host: the planner's counts, the status OR, making and destroying the plan.
 // (The reference's counterpart is the Python double loop of blueice/inference.py:424-432, one scalar call per grid point.)
+// bi_grid_reduce_sourcewise is the same loop over a source-wise model (bi_factored.h): grid_reduce takes the evaluation step as a
+// parameter -- the resident planner for the grid model, PlannedItems::queue (route 0, bi_sourcewise_plan.h) or ScanItems::queue
+// (route 1, the matrix-core scan route of bi_sourcewise_scan.h) for the source-wise one, which keep their buffers across the
+// chunks and leave the planner's status words where the reduction reads them.
 #pragma once
+
+#include <functional>
 
 namespace {
 
@@ -56,9 +62,17 @@ int grid_state_end(bi_ctx* c, GridArgs& a, double* log_marginal, double* profile
     return BI_OK;
 }
 
-int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_t n_total, const int32_t* var_kind, const int32_t* var_index,
-                const double* z0, const double* scale0, const double* unit, const double* nodes, const double* term, const double* logw,
-                int64_t chunk, double* log_marginal, double* profile, int64_t* argmax, int64_t* counters) {
+// The loop of bi_grid_reduce and bi_grid_reduce_sourcewise: chunks of the grid written by k_grid_points, evaluated by `step`, folded
+// by k_grid_reduce.  step(pts, n, counters, reduce) evaluates the first n staged points into pts.llp, calls reduce(status words)
+// once -- that launches the reduction and returns the launch's error -- and releases what it made.  model_d, model_S: the
+// model's axes and sources as ResidentPoints::bind takes them (< 0: the grid model's).
+using GridFold = std::function<hipError_t(const int32_t*)>;
+
+template <class Step>
+int grid_reduce(bi_ctx* c, const char* who, int model_d, int model_S, int64_t E, const int64_t* dataset, GridArgs a, int64_t n_total,
+                const int32_t* var_kind, const int32_t* var_index, const double* z0, const double* scale0, const double* unit, const double* nodes,
+                const double* term, const double* logw, int64_t chunk, double* log_marginal, double* profile, int64_t* argmax, int64_t* counters,
+                Step&& step) {
     const size_t nn = (size_t)n_total;
     const int64_t G = E * a.GK;
     if (chunk == 0) chunk = kGridDefaultChunk;
@@ -69,7 +83,7 @@ int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_
     int rc;
     // (host copies that live until the uploads have been waited for)
     const std::vector<double> h_nodes(nodes, nodes + nn), h_term = host_copy(term, term ? nn : 0, 0.0), h_logw = host_copy(logw, logw ? nn : 0, 0.0);
-    if ((rc = pts.bind(c, a, E, chunk, a.F, var_kind, var_index, z0, scale0, unit, dataset)) || (rc = dev_upload(c, b_nodes, h_nodes)) ||
+    if ((rc = pts.bind(c, a, E, chunk, a.F, var_kind, var_index, z0, scale0, unit, dataset, model_d, model_S)) || (rc = dev_upload(c, b_nodes, h_nodes)) ||
         (term && (rc = dev_upload(c, b_term, h_term))) || (logw && (rc = dev_upload(c, b_logw, h_logw))))
         return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -89,23 +103,107 @@ int grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, GridArgs a, int64_
         grid_chunk_cells(a);
         launch_grid_points(c, a);
         HIP_TRY(c, hipGetLastError());                          // (nothing is launched after a failed launch)
-        bi_plan* plan = nullptr;
-        if ((rc = pts.evaluate(c, a.n, "bi_grid_reduce", &plan, counters))) return rc;
-        if (counters) ++counters[0];
-        a.st = (const int32_t*)plan->status.p;
-        launch_grid_reduce(c, a);
-        const hipError_t e = hipGetLastError();
-        bi_plan_destroy(c, plan);                               // (waits for the stream: the reduction reads the plan's status words)
-        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "bi_grid_reduce (reduce): %s", hipGetErrorString(e));
+        hipError_t e = hipSuccess;
+        const GridFold fold = [&](const int32_t* status) {
+            if (counters) ++counters[0];
+            a.st = status;
+            launch_grid_reduce(c, a);
+            return e = hipGetLastError();
+        };
+        if ((rc = step(pts, a.n, counters, fold))) return rc;
+        if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s (reduce): %s", who, hipGetErrorString(e));
     }
     return grid_state_end(c, a, log_marginal, profile, argmax, counters ? &counters[2] : nullptr);
 }
+
+// the grid model's step: the resident planner and bi_run_plan; the plan goes once the reduction has been queued
+int grid_step_plan(bi_ctx* c, ResidentPoints& pts, int64_t n, int64_t* counters, const GridFold& fold) {
+    bi_plan* plan = nullptr;
+    int rc = pts.evaluate(c, n, "bi_grid_reduce", &plan, counters);
+    if (rc) return rc;
+    (void)fold((const int32_t*)plan->status.p);
+    bi_plan_destroy(c, plan);                                   // (waits for the stream: the reduction reads the plan's status words)
+    return BI_OK;
+}
+
+// The source-wise model's step: route 0 PlannedItems::queue (one work item per point, bi_sourcewise_plan.h), route 1
+// ScanItems::queue (the matrix-core scan route, bi_sourcewise_scan.h); both leave the planner's status words where they were
+// written, and nothing is made per chunk.  The buffers are sized by the first chunk, the largest.
+struct GridStepSourcewise {
+    bi_ctx* c;
+    int route;
+    PlannedItems points;
+    ScanItems scan;
+    bool ready = false;
+    GridStepSourcewise(bi_ctx* ctx, int r) : c(ctx), route(r), points(ctx), scan(ctx) {}
+
+    int operator()(ResidentPoints& pts, int64_t n, int64_t* counters, const GridFold& fold) {
+        const char* who = "bi_grid_reduce_sourcewise";
+        int rc;
+        if (!ready && (rc = route == 1 ? scan.init(n) : points.init(n))) return rc;
+        ready = true;
+        const double* zp = c->fac.d > 0 ? (const double*)pts.zp.p : nullptr;
+        int64_t launches = 0;
+        if (route == 1) {
+            int64_t ctr[5] = {0, 0, 0, 0, 0};
+            if ((rc = scan.queue(n, zp, (const double*)pts.rsp.p, (const int64_t*)pts.dsp.p, (double*)pts.llp.p, who, ctr))) return rc;
+            launches = ctr[3];
+        } else if ((rc = points.queue(n, zp, (const double*)pts.rsp.p, (const int64_t*)pts.dsp.p, (double*)pts.llp.p, who, &launches)))
+            return rc;
+        if (counters) { counters[1] += n; counters[3] += launches; }
+        (void)fold((const int32_t*)(route == 1 ? scan.pt.status.p : points.status.p));
+        return BI_OK;
+    }
+};
 
 // true: a * b fits below `limit` (a, b >= 1), and *out = a * b
 bool grid_mul(int64_t a, int64_t b, int64_t limit, int64_t* out) {
     if (a > limit / b) return false;
     *out = a * b;
     return *out <= limit;
+}
+
+// The argument checks the two entry points share, reported under `who`, and the grid's shape into a / n_total; d, S: the model's
+int grid_check_args(bi_ctx* c, const char* who, int d, int S, int64_t E, int F, int n_keep, const int32_t* var_kind, const int32_t* var_index,
+                    const double* z0, const double* scale0, const double* unit, const int32_t* n_nodes, const double* nodes, const double* term,
+                    const double* logw, int64_t chunk, const double* log_marginal, const double* profile, const int64_t* argmax, GridArgs& a,
+                    int64_t& n_total) {
+    int rc;
+    if (F < 1 || F > kGridMaxVars) return fail(c, BI_ERR_INVALID, "%s: need 1 <= F <= %d variables (got %d)", who, kGridMaxVars, F);
+    if (n_keep < 0 || n_keep > F) return fail(c, BI_ERR_INVALID, "%s: n_keep must lie in [0, F = %d] (got %d)", who, F, n_keep);
+    if (E < 1) return fail(c, BI_ERR_INVALID, "%s: need E >= 1 (got %lld)", who, (long long)E);
+    if (chunk < 0 || chunk > kGridMaxChunk) return fail(c, BI_ERR_INVALID, "%s: chunk must lie in [0, 2^26] (got %lld)", who, (long long)chunk);
+    if (!var_kind || !var_index || !scale0 || !unit || (d > 0 && !z0) || !n_nodes || !nodes || !log_marginal || !profile || !argmax)
+        return fail(c, BI_ERR_INVALID, "%s: NULL argument", who);
+    a.F = F; a.n_keep = n_keep;
+    for (int j = 0; j < F; ++j) {
+        if ((rc = check_variable(c, who, j, var_kind, var_index, true, d, S))) return rc;
+        if (n_nodes[j] < 1) return fail(c, BI_ERR_INVALID, "%s: variable %d has %d nodes: need at least 1", who, j, (int)n_nodes[j]);
+        a.n_nodes[j] = n_nodes[j];
+    }
+    int64_t K = 1, R = 1, cells = 0, G = 0;
+    for (int j = 0; j < F; ++j) {
+        a.node_off[j] = n_total;
+        n_total += n_nodes[j];
+        if (!grid_mul(j < n_keep ? K : R, n_nodes[j], kGridMaxPoints, j < n_keep ? &K : &R))
+            return fail(c, BI_ERR_INVALID, "%s: the grid has more than 2^48 points", who);
+    }
+    if (!grid_mul(E, K, kGridMaxCells, &cells))
+        return fail(c, BI_ERR_INVALID, "%s: E * K (%lld dataset entries x %lld kept points) is more than 2^24 cells", who, (long long)E, (long long)K);
+    if (!grid_mul(cells, R, kGridMaxPoints, &G)) return fail(c, BI_ERR_INVALID, "%s: the grid has more than 2^48 points", who);
+    for (int64_t stride = 1, j = F - 1; j >= 0; --j) {
+        a.stride[j] = stride;
+        stride *= n_nodes[j];
+    }
+    a.R = R; a.GK = K * R;
+    for (int64_t i = 0; i < n_total; ++i) {
+        if (!std::isfinite(nodes[i])) return fail(c, BI_ERR_INVALID, "%s: node %lld is not finite (%g)", who, (long long)i, nodes[i]);
+        if (term && !(term[i] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "%s: term %lld is %g: a term is finite or -inf", who, (long long)i, term[i]);
+        if (logw && !(logw[i] < std::numeric_limits<double>::infinity()))
+            return fail(c, BI_ERR_INVALID, "%s: logw %lld is %g: a log weight is finite or -inf", who, (long long)i, logw[i]);
+    }
+    return BI_OK;
 }
 
 }  // namespace
@@ -119,50 +217,50 @@ int bi_grid_reduce(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_ke
     int rc = check_ready(c, true);
     if (rc) return rc;
     c->plan_refused = 0;
-    if (F < 1 || F > kGridMaxVars) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: need 1 <= F <= %d variables (got %d)", kGridMaxVars, F);
-    if (n_keep < 0 || n_keep > F) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: n_keep must lie in [0, F = %d] (got %d)", F, n_keep);
-    if (E < 1) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: need E >= 1 (got %lld)", (long long)E);
-    if (chunk < 0 || chunk > kGridMaxChunk) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: chunk must lie in [0, 2^26] (got %lld)", (long long)chunk);
-    if (!var_kind || !var_index || !scale0 || !unit || (c->d > 0 && !z0) || !n_nodes || !nodes || !log_marginal || !profile || !argmax)
-        return fail(c, BI_ERR_INVALID, "bi_grid_reduce: NULL argument");
     GridArgs a{};
-    a.F = F; a.n_keep = n_keep;
-    for (int j = 0; j < F; ++j) {
-        if ((rc = check_variable(c, "bi_grid_reduce", j, var_kind, var_index, true))) return rc;
-        if (n_nodes[j] < 1) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: variable %d has %d nodes: need at least 1", j, (int)n_nodes[j]);
-        a.n_nodes[j] = n_nodes[j];
-    }
-    int64_t n_total = 0, K = 1, R = 1, cells = 0, G = 0;
-    for (int j = 0; j < F; ++j) {
-        a.node_off[j] = n_total;
-        n_total += n_nodes[j];
-        if (!grid_mul(j < n_keep ? K : R, n_nodes[j], kGridMaxPoints, j < n_keep ? &K : &R))
-            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: the grid has more than 2^48 points");
-    }
-    if (!grid_mul(E, K, kGridMaxCells, &cells))
-        return fail(c, BI_ERR_INVALID, "bi_grid_reduce: E * K (%lld dataset entries x %lld kept points) is more than 2^24 cells", (long long)E, (long long)K);
-    if (!grid_mul(cells, R, kGridMaxPoints, &G)) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: the grid has more than 2^48 points");
-    for (int64_t stride = 1, j = F - 1; j >= 0; --j) {
-        a.stride[j] = stride;
-        stride *= n_nodes[j];
-    }
-    a.R = R; a.GK = K * R;
-    for (int64_t i = 0; i < n_total; ++i) {
-        if (!std::isfinite(nodes[i])) return fail(c, BI_ERR_INVALID, "bi_grid_reduce: node %lld is not finite (%g)", (long long)i, nodes[i]);
-        if (term && !(term[i] < std::numeric_limits<double>::infinity()))
-            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: term %lld is %g: a term is finite or -inf", (long long)i, term[i]);
-        if (logw && !(logw[i] < std::numeric_limits<double>::infinity()))
-            return fail(c, BI_ERR_INVALID, "bi_grid_reduce: logw %lld is %g: a log weight is finite or -inf", (long long)i, logw[i]);
-    }
+    int64_t n_total = 0;
+    if ((rc = grid_check_args(c, "bi_grid_reduce", c->d, c->S, E, F, n_keep, var_kind, var_index, z0, scale0, unit, n_nodes, nodes, term, logw, chunk,
+                              log_marginal, profile, argmax, a, n_total)))
+        return rc;
     if ((rc = check_single_set(c, "bi_grid_reduce", "dataset entry", E, dataset)) ||
         (rc = check_entry_datasets(c, "bi_grid_reduce", "entry", E, dataset, c->T)))
         return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     try {
-        return grid_reduce(c, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk, log_marginal, profile, argmax,
-                           counters);
+        return grid_reduce(c, "bi_grid_reduce", -1, -1, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk,
+                           log_marginal, profile, argmax, counters,
+                           [&](ResidentPoints& pts, int64_t n, int64_t* ctr, const GridFold& fold) { return grid_step_plan(c, pts, n, ctr, fold); });
     } catch (const std::bad_alloc&) {
         return fail(c, BI_ERR_NOMEM, "bi_grid_reduce: out of host memory");
+    }
+}
+
+int bi_grid_reduce_sourcewise(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_keep, const int32_t* var_kind, const int32_t* var_index,
+                              const double* z0, const double* scale0, const double* unit, const int32_t* n_nodes, const double* nodes,
+                              const double* term, const double* logw, int64_t chunk, int route, double* log_marginal, double* profile,
+                              int64_t* argmax, int64_t* counters) {
+    const char* who = "bi_grid_reduce_sourcewise";
+    int rc = fac_check(c, who, true);
+    if (rc) return rc;
+    GridArgs a{};
+    int64_t n_total = 0;
+    if ((rc = grid_check_args(c, who, c->fac.d, c->fac.S, E, F, n_keep, var_kind, var_index, z0, scale0, unit, n_nodes, nodes, term, logw, chunk,
+                              log_marginal, profile, argmax, a, n_total)) ||
+        (rc = check_entry_datasets(c, who, "entry", E, dataset, c->fac.T)))
+        return rc;
+    if (route < -1 || route > 1) return fail(c, BI_ERR_INVALID, "%s: route is -1 (the scan route where the model is eligible), 0 (points) or 1 (scan), not %d", who, route);
+    if (route < 0) route = sourcewise_scan_refusal(c) == 0 ? 1 : 0;
+    if (route == 1 && (rc = sourcewise_scan_check(c, who))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    try {
+        GridStepSourcewise step(c, route);
+        rc = grid_reduce(c, who, c->fac.d, c->fac.S, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk,
+                         log_marginal, profile, argmax, counters, step);
+        if (rc) (void)hipStreamSynchronize(c->stream);          // (the step's buffers go with the scope)
+        if (counters) counters[4] = route;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "%s: out of host memory", who);
     }
 }
 

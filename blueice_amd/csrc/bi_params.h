@@ -89,6 +89,7 @@ const ParamDef kParams[] = {
     {"dot_lanes", kParamRW, BI_P_GET(c->dot_lanes), BI_P_SET(c->dot_lanes = (v == 16 || v == 8 || v == 4) ? v : 0)},
     {"compact_budget", kParamRW, BI_P_GET(c->compact_budget), BI_P_SET(c->compact_budget = v)},
     {"sourcewise_form", kParamRW, BI_P_GET(c->sourcewise_form), BI_P_RANGE(0, 1, sourcewise_form, "sourcewise_form: 0 dense, 1 the non-empty-bin form where it is built")},
+    {"sourcewise_scan_timed", kParamRW, BI_P_GET(c->sourcewise_scan_timed), BI_P_RANGE(0, 3, sourcewise_scan_timed, "sourcewise_scan_timed: bit 0 the planner, bit 1 the matrix-core launches")},
     {"toy_offset", kParamRW, BI_P_GET(c->toy_offset), BI_P_RANGE(0, INT64_MAX, toy_offset, "toy_offset >= 0")},
     {"narrow_counts", kParamRW, BI_P_GET(c->narrow_counts), BI_P_FLAG(narrow_counts)},
     {"packed_rows", kParamRW, BI_P_GET(c->packed_rows), BI_P_FLAG(packed_rows)},

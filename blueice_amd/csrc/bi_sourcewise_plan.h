@@ -34,8 +34,8 @@ struct PlannedItems {
         : c(ctx), m(ctx->fac), SC(m.S <= 2 ? 2 : m.S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM), NR(m.n_rows_point),
           ne(fac_nonempty_on(ctx)), nbx(ne ? m.ne_max_nbx : std::min((int)(m.Bp / kTile), kFacBlocks)) {}
 
-    // room for n_max items, both argument blocks
-    int init(int64_t n) {
+    // room for n_max items, both argument blocks; evaluate = false: the planner's buffers alone (queue() must not be called)
+    int init(int64_t n, bool evaluate = true) {
         n_max = n;
         per_call = std::max<int64_t>(1, kFacPartialDoubles / (int64_t)nbx);
         const size_t un = (size_t)n, part = (size_t)std::min<int64_t>(std::min<int64_t>(65535, per_call), n) * (size_t)nbx;
@@ -44,7 +44,7 @@ struct PlannedItems {
             (rc = dev_alloc(c, rowoff, un * NR * sizeof(int64_t))) || (rc = dev_alloc(c, coef, un * NR * W * sizeof(double))) ||
             (rc = dev_alloc(c, rates, un * SC * sizeof(double))) || (rc = dev_alloc(c, cnt_off, un * sizeof(int64_t))) ||
             (rc = dev_alloc(c, slot_lg, un * sizeof(double))) || (rc = dev_alloc(c, perm, un * sizeof(int64_t))) ||
-            (rc = dev_alloc(c, partial, part * sizeof(double))) || (rc = dev_alloc(c, pflags, part * sizeof(unsigned))))
+            (evaluate && ((rc = dev_alloc(c, partial, part * sizeof(double))) || (rc = dev_alloc(c, pflags, part * sizeof(unsigned))))))
             return rc;
         if (ne && (rc = dev_alloc(c, tiles, un * sizeof(int32_t)))) return rc;
         fa = FacBatch(c, 0).args();

@@ -1619,6 +1619,7 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_sampler.h"
 #include "bi_sourcewise_plan.h"
 #include "bi_sourcewise_nonempty.h"
+#include "bi_sourcewise_scan.h"
 #include "bi_grid.h"
 #include "bi_coarse.h"
 #include "bi_sourcewise_coarse.h"

@@ -653,37 +653,10 @@ class DeviceContext:
         index as `fit_batched`), reduced over the variables from n_keep on.  z0 [E, d], scale0 / unit [E, S] (rows broadcast),
         dataset [E] or None (one entry, dataset 0); term / logw: None or one array per variable, shaped as its nodes.
         -> (log_marginal [E, K], profile [E, K], argmax [E, K], counters [4]: chunks, evaluations, excluded points, launches)."""
-        kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
-        nodes = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in nodes]
-        F, n_keep = len(nodes), int(n_keep)
-        if len(kind) != F or len(index) != F or any(v.ndim != 1 for v in nodes):
-            raise ValueError("kind, index and nodes must have one entry per variable, every entry of nodes one-dimensional")
-        n_nodes = np.array([len(v) for v in nodes], dtype=np.int32)
-
-        def flat(arrays, what):
-            if arrays is None:
-                return None
-            arrays = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in arrays]
-            if len(arrays) != F or any(v.shape != w.shape for v, w in zip(arrays, nodes)):
-                raise ValueError("%s must hold one array per variable, shaped as its nodes" % what)
-            return np.ascontiguousarray(np.concatenate(arrays)) if F else np.zeros(0)
-        term, logw = flat(term, 'term'), flat(logw, 'logw')
-        nodes_flat = np.ascontiguousarray(np.concatenate(nodes)) if F else np.zeros(0)
-        if dataset is not None:
-            dataset = np.ascontiguousarray(np.atleast_1d(np.asarray(dataset, dtype=np.int64)))
-        E = 1 if dataset is None else len(dataset)
-        z0, scale0, unit = self._map_entries(E, z0, scale0, unit)
-        K = int(np.prod(n_nodes[:max(0, min(n_keep, F))], dtype=np.int64)) if F and np.all(n_nodes >= 1) else 1
-        if E * K > 2 ** 24:                                   # (refused by the library too; here before the outputs are made)
-            raise ValueError("bi_grid_reduce: E * K (%d dataset entries x %d kept points) is more than 2^24 cells" % (E, K))
-        log_marginal, profile = np.empty((E, K)), np.empty((E, K))
-        argmax = np.empty((E, K), dtype=np.int64)
-        counters = np.zeros(4, dtype=np.int64)
-        rc = self._lib.bi_grid_reduce(self._h, E, ptr(dataset), F, n_keep, ptr(kind), ptr(index), ptr(z0) if self.d else None, ptr(scale0),
-                                      ptr(unit), ptr(n_nodes), ptr(nodes_flat), ptr(term), ptr(logw), int(chunk), ptr(log_marginal),
-                                      ptr(profile), ptr(argmax), ptr(counters))
+        rc, out = grid_reduce_call(self._lib.bi_grid_reduce, 'bi_grid_reduce', self._h, self.d, self.S, kind, index, z0, scale0, unit, dataset,
+                                   n_keep, nodes, term, logw, chunk, 4)
         self._check_resident(rc)
-        return log_marginal, profile, argmax, counters
+        return out
 
     def selftest_grid_reduce(self, t, q=None, chunk=0):
         """bi_selftest_grid_reduce: t [cells, R] (and q, or None) through the reduction kernels of `grid_reduce`, in chunks of
@@ -852,6 +825,46 @@ class DeviceContext:
         ms = C.c_double()
         self._check(self._lib.bi_profile_read(self._h, C.byref(n), C.byref(ms)))
         return n.value, ms.value
+
+
+def grid_reduce_call(symbol, who, handle, d, S, kind, index, z0, scale0, unit, dataset, n_keep, nodes, term, logw, chunk, n_counters, extra=()):
+    """The arguments and outputs of bi_grid_reduce and bi_grid_reduce_sourcewise (`symbol`; `who` names it in messages) for a model of
+    d axes and S sources: the per-variable arrays laid out one after the other, the entries' rows broadcast, the outputs made.
+    `extra`: the arguments between `chunk` and the outputs.  -> (return code, (log_marginal [E, K], profile [E, K], argmax [E, K],
+    counters [n_counters]))."""
+    kind, index = np.ascontiguousarray(kind, dtype=np.int32), np.ascontiguousarray(index, dtype=np.int32)
+    nodes = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in nodes]
+    F, n_keep = len(nodes), int(n_keep)
+    if len(kind) != F or len(index) != F or any(v.ndim != 1 for v in nodes):
+        raise ValueError("kind, index and nodes must have one entry per variable, every entry of nodes one-dimensional")
+    n_nodes = np.array([len(v) for v in nodes], dtype=np.int32)
+
+    def flat(arrays, what):
+        if arrays is None:
+            return None
+        arrays = [np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in arrays]
+        if len(arrays) != F or any(v.shape != w.shape for v, w in zip(arrays, nodes)):
+            raise ValueError("%s must hold one array per variable, shaped as its nodes" % what)
+        return np.ascontiguousarray(np.concatenate(arrays)) if F else np.zeros(0)
+    term, logw = flat(term, 'term'), flat(logw, 'logw')
+    nodes_flat = np.ascontiguousarray(np.concatenate(nodes)) if F else np.zeros(0)
+    if dataset is not None:
+        dataset = np.ascontiguousarray(np.atleast_1d(np.asarray(dataset, dtype=np.int64)))
+    E = 1 if dataset is None else len(dataset)
+
+    def rows(a, n):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float64).reshape(-1, n), (E, n)))
+    z0 = rows(z0, d) if d else None
+    scale0, unit = rows(scale0, S), rows(unit, S)
+    K = int(np.prod(n_nodes[:max(0, min(n_keep, F))], dtype=np.int64)) if F and np.all(n_nodes >= 1) else 1
+    if E * K > 2 ** 24:                                       # (refused by the library too; here before the outputs are made)
+        raise ValueError("%s: E * K (%d dataset entries x %d kept points) is more than 2^24 cells" % (who, E, K))
+    log_marginal, profile = np.empty((E, K)), np.empty((E, K))
+    argmax = np.empty((E, K), dtype=np.int64)
+    counters = np.zeros(int(n_counters), dtype=np.int64)
+    rc = symbol(handle, E, ptr(dataset), F, n_keep, ptr(kind), ptr(index), ptr(z0), ptr(scale0), ptr(unit), ptr(n_nodes), ptr(nodes_flat),
+                ptr(term), ptr(logw), int(chunk), *extra, ptr(log_marginal), ptr(profile), ptr(argmax), ptr(counters))
+    return rc, (log_marginal, profile, argmax, counters)
 
 
 class DeviceBuffer:

@@ -25,6 +25,12 @@ Two engines compute the same thing:
     'host'     the executable specification: `lf.eval_points` over the same grid in chunks, reduced in NumPy -- for anything
                that has `eval_points` (sums, re-parametrisations), and for models whose batches the device planner
                refuses.
+
+A prepared source-wise model (`SourceWiseBinnedLogLikelihood`) runs natively as a function, `blueice_amd.grid.grid_scan(lf, ...)`
+(bi_grid_reduce_sourcewise; the bound lf.grid_scan stays refused and names this spelling).  Its chunks are evaluated by the
+route `likelihood_config['sourcewise_grid_route']` names: 'points' (one work item per point, the kernels of `eval_points`),
+'scan' (the matrix-core scan route of `eval_points_scan`: needs the non-empty-bin form and at most 32 rows per point) or 'auto'
+(the default: see SOURCEWISE_AUTO_ROUTE).
 """
 import numpy as np
 
@@ -33,6 +39,22 @@ from .exceptions import PlannerRefused
 __all__ = ['grid_scan', 'GridResult', 'trapezoid_weights', 'reduce_cells']
 
 HOST_CHUNK = 1 << 16
+# what likelihood_config['sourcewise_grid_route'] = 'auto' asks the library for: -1 = the scan route where the model is eligible
+# (the non-empty-bin form built, at most 32 rows per point), else one work item per point
+SOURCEWISE_AUTO_ROUTE = -1
+_SOURCEWISE_ROUTES = {'auto': None, 'points': 0, 'scan': 1}
+
+
+def _sourcewise_route(lf):
+    """-> the `route` of ctx.grid_reduce for a source-wise model (likelihood_config['sourcewise_grid_route']), None for any other"""
+    from .source_wise import SourceWiseBinnedLogLikelihood
+    if not isinstance(lf, SourceWiseBinnedLogLikelihood):
+        return None
+    setting = lf.config.get('sourcewise_grid_route', 'auto')
+    if not isinstance(setting, str) or setting not in _SOURCEWISE_ROUTES:
+        raise ValueError("likelihood_config['sourcewise_grid_route'] is 'auto', 'points' or 'scan', not %r" % (setting,))
+    route = _SOURCEWISE_ROUTES[setting]
+    return SOURCEWISE_AUTO_ROUTE if route is None else route
 
 
 def trapezoid_weights(x):
@@ -79,7 +101,8 @@ def reduce_cells(t, q=None):
 class GridResult:
     """keep / reduce: [(name, nodes), ...]; log_marginal, profile, argmax: [(E,) n_0, ..., n_keep-1]; best: reduce name ->
     the node at the argmax (nan where a cell has no point); excluded: points of likelihood zero; engine 'native' or 'host';
-    counters: chunks, evaluations, excluded points, evaluation launches."""
+    counters: chunks, evaluations, excluded points, evaluation launches (and, for a source-wise model, the route taken: 0 points,
+    1 scan)."""
 
     def __init__(self, keep, reduce, log_marginal, profile, argmax, excluded, engine, counters, has_datasets):
         self.keep, self.reduce = keep, reduce
@@ -271,8 +294,10 @@ def grid_scan(lf, keep=(), reduce=(), weights='trapezoid', datasets=None, liveti
     if plan is not None:
         try:
             full_logw = None if logw is None else [np.zeros(len(v)) for _, v in keep] + logw
+            route = _sourcewise_route(lf)
+            more = {} if route is None else {'route': route}
             lm, prof, arg, counters = lf.ctx.grid_reduce(plan['kind'], plan['index'], plan['z0'], plan['scale0'], plan['unit'], datasets, n_keep,
-                                                         [v for _, v in axes], term=plan['term'], logw=full_logw, chunk=chunk or 0)
+                                                         [v for _, v in axes], term=plan['term'], logw=full_logw, chunk=chunk or 0, **more)
             result = (lm.ravel() + plan['const'], prof.ravel() + plan['const'], arg.ravel(), counters)
             used = 'native'
         except PlannerRefused:

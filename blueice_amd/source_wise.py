@@ -59,6 +59,17 @@ launches queued on one stream and the step loop waits for nothing.  `blueice_amd
 `datasets=` after `simulate_toys_points` and with `GaussianPrior` constraints on the device.  The bound lf.sample_posterior and
 lf.bestfit_emcee stay refused and name these spellings.
 
+Gridded likelihoods -- the marginal likelihood by quadrature, the grid profile, a credible limit without a chain -- run on the
+device as well (bi_grid_reduce_sourcewise): `blueice_amd.grid.grid_scan(lf, keep=..., reduce=...)` takes a prepared source-wise
+model, with `datasets=` after `simulate_toys_points` and with priors; the bound lf.grid_scan stays refused.
+`likelihood_config['sourcewise_grid_route']` -- 'auto' (default), 'points' or 'scan' -- names how a chunk of the grid is
+evaluated: one work item per point (the kernels of eval_points), or the matrix-core scan route (bi_eval_sourcewise_scan,
+`lf.eval_points_scan(points)`): the points sorted by (cell tuple, dataset) on the device and evaluated 16 at a time on the fp64
+matrix cores over the compacted rows of the non-empty-bin form, a group's rows read once per strip of bins.  That route needs
+`nonempty_bins` and at most 32 rows per point (sum_s 2^e_s); its values agree with eval_points' to rounding, and -- unlike every
+other entry point -- a point's bits may depend on the batch it is evaluated in (a repeated call repeats its bits).  No existing
+entry point changes its route: eval_points, the fits and the sampler keep their kernels and their bits.
+
 The counts are dense, and by default every evaluation walks every bin.  `likelihood_config['nonempty_bins']` -- False (default),
 True or 'auto' (build when at most a quarter of the bins of all datasets hold events) -- adds the non-empty-bin form of the data
 (bi_sourcewise_build_nonempty; `ctx.build_nonempty()` / `ctx.drop_nonempty()`): per dataset the list of bins with events and a
@@ -71,15 +82,17 @@ the dense store.
 
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
 full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
-full_output calls, eval_toys*, grids (grid_scan), Hessians and sampling on an Asimov view.
+full_output calls, eval_toys*, Hessians, sampling and gridded likelihoods on an Asimov view, and the bound lf.grid_scan (the
+function is the spelling that works, above).
 """
 import ctypes as C
 from collections import OrderedDict
 
 import numpy as np
 
+from . import _capi
 from ._capi import as_f64, ptr
-from .device import DeviceContext
+from .device import DeviceContext, grid_reduce_call
 from .histdd import Histdd, device_histograms
 from .likelihood import DeviceLogLikelihood, LogLikelihoodBase, _needs_data, _needs_preparation
 
@@ -243,6 +256,34 @@ class SourceWiseContext:
         status = np.zeros(P, dtype=np.int32)
         dev._check(dev._lib.bi_eval_sourcewise_planned(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(status)))
         return ll, status
+
+    def eval_scan(self, z, rate_scale=None, dataset=None):
+        """`eval_planned` on the matrix-core scan route (bi_eval_sourcewise_scan): the points are sorted by (cell tuple, dataset)
+        on the device and evaluated 16 at a time over the compacted rows of the non-empty-bin form, each group's rows read once
+        per strip of bins -> (ll [P], status [P]).  Status words and the -inf of rejected points are `eval_planned`'s bit for
+        bit; a live point's ll agrees to rounding, and its bits may depend on the batch (the same call repeats its bits).
+        `last_scan_counters` [5]: groups, work items, live points, launches, host reads of the call.  ValueError
+        (BI_ERR_INVALID) unless the form is built (`build_nonempty`) and a point reads at most 32 rows."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        ll = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        counters = np.zeros(5, dtype=np.int64)
+        dev._check(dev._lib.bi_eval_sourcewise_scan(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(status), ptr(counters)))
+        self.last_scan_counters = counters
+        return ll, status
+
+    def grid_reduce(self, kind, index, z0, scale0, unit, dataset, n_keep, nodes, term=None, logw=None, chunk=0, route=-1):
+        """bi_grid_reduce_sourcewise: DeviceContext.grid_reduce with the source-wise likelihood -- the same arguments and
+        return value, and `route`: 0 = one work item per point (the kernels of `eval_planned`), 1 = the matrix-core scan route
+        (`eval_scan`), -1 = 1 where the model is eligible (the non-empty-bin form built, at most 32 rows per point), else 0.
+        -> (log_marginal [E, K], profile [E, K], argmax [E, K], counters [5]: chunks, evaluations, excluded points, launches,
+        the route taken)."""
+        dev = self._dev
+        rc, out = grid_reduce_call(dev._lib.bi_grid_reduce_sourcewise, 'bi_grid_reduce_sourcewise', dev._h, self.d, self.S, kind, index, z0, scale0,
+                                   unit, dataset, n_keep, nodes, term, logw, chunk, 5, extra=(int(route),))
+        dev._check(rc)
+        return out
 
     def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0, priors=None):
         """bi_sample_stretch_sourcewise: DeviceContext.sample_stretch with the source-wise likelihood as the target -- the same
@@ -528,7 +569,8 @@ def _refused(name):
                                       % (name, _REFUSED_SPELLINGS[name]))
         raise NotImplementedError("%s is not available for a source-wise model (SourceWiseBinnedLogLikelihood): value, gradient, "
                                   "Hessian, expected information, the fit, scan and interval layers, toys at truth points, "
-                                  "goodness of fit, coarse views, Asimov data and the ensemble sampler are" % name)
+                                  "goodness of fit, coarse views, Asimov data and the ensemble sampler are, and gridded likelihoods "
+                                  "as blueice_amd.grid.grid_scan(lf, ...)" % name)
     method.__name__ = name
     return method
 
@@ -697,6 +739,21 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         return methods
 
     # -- evaluation ------------------------------------------------------------------------
+    @_needs_data
+    def eval_points_scan(self, points, livetime_days=None, dataset=None):
+        """`eval_points` on the matrix-core scan route (bi_eval_sourcewise_scan; see the module's docstring): for batches whose
+        points pile up in few cell tuples.  The same arguments, return value and treatment of rejected points; the values agree
+        with `eval_points` to rounding, and a point's bits may depend on the batch.  ValueError unless the non-empty-bin form
+        is built (likelihood_config['nonempty_bins']) and a point reads at most 32 rows."""
+        z, scale, prior = self._batch_terms(points, livetime_days)
+        ll, st = self.ctx.eval_scan(z if z.shape[1] else None, scale, dataset)
+        bad = st & _capi.ST_UNPHYSICAL
+        if np.any(bad) and self.config.get('unphysical_behaviour') == 'error':
+            raise ValueError("Unphysical rates at %d of %d points" % (int(np.count_nonzero(bad)), len(st)))
+        out = ll + prior
+        out[(st & (_capi.ST_OUT_OF_BOUNDS | _capi.ST_UNPHYSICAL)) != 0] = -np.inf
+        return out
+
     @_needs_data
     def __call__(self, livetime_days=None, compute_pdf=False, full_output=False, **kwargs):
         if compute_pdf or full_output:

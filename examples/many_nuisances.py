@@ -1,6 +1,6 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
-    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band] [--posterior]
+    PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band] [--posterior] [--grid]
         [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian | --measure-sampler [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
@@ -65,6 +65,15 @@ bi_eval_factored values-only at 1, 64 and 4096 points per call; the lines go to 
 --measure-nonempty times, at the same shape, the non-empty-bin form of the data (bi_sourcewise_build_nonempty) against the dense
 store on the same context at 10^3 ... 2.5 10^5 events in the 10^6 bins: bi_eval_factored, its kernels alone, the build, the
 sampler and a lock-step iteration over 256 toys; the lines go to profiles/sourcewise_nonempty_measure.txt too.
+
+--grid computes, instead of (2) - (6), the 90 % credible upper limit on the signal's multiplier from a gridded likelihood
+(blueice_amd.grid.grid_scan on the source-wise model: bi_grid_reduce_sourcewise, on the matrix-core scan route and on the per-point
+route), marginalised over one nuisance parameter and two background multipliers with the others fixed, and prints it beside the
+same quantile of a chain over the same four parameters (blueice_amd.sampler.sample_posterior).
+
+--measure-grid times, at the measured source-wise shape with Poisson data of 10^4 events, bi_grid_reduce_sourcewise on its two routes
+against the host engine on a grid of about 10^6 points, bi_eval_sourcewise_scan against bi_eval_factored values-only at 4096 and 10^6
+points of one cell tuple, and the planner's share of a call by device events; the lines go to profiles/sourcewise_scan_measure.txt too.
 """
 import argparse
 import time
@@ -85,6 +94,10 @@ ap.add_argument('--measure-sampler', action='store_true',
                 help='time bi_sample_stretch_sourcewise against the host engine, and bi_eval_sourcewise_planned against bi_eval_factored')
 ap.add_argument('--measure-nonempty', action='store_true',
                 help='time the non-empty-bin form of the data against the dense store on the same context (sourcewise_form)')
+ap.add_argument('--grid', action='store_true',
+                help='a credible upper limit on the signal multiplier from a gridded likelihood, marginalised over three nuisances, beside the chain\'s')
+ap.add_argument('--measure-grid', action='store_true',
+                help='time bi_grid_reduce_sourcewise on its two routes against the host engine, and bi_eval_sourcewise_scan against bi_eval_factored')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -847,6 +860,179 @@ def posterior():
         print('      %2d  %10.2f  %+8.2f  %+8.2f' % (c, q50[c], q16[c] - q50[c], q84[c] - q50[c]))
 
 
+def measure_grid():
+    """The gridded likelihood of a source-wise model at the measured shape with Poisson data of 10^4 events, on the context:
+    bi_grid_reduce_sourcewise on route 1 (the matrix-core scan route) and route 0 (one work item per point) against the host engine
+    (blueice_amd.grid._host_engine over a likelihood whose eval_points is bi_eval_factored, reduced by reduce_cells) on the same
+    grid; bi_eval_sourcewise_scan against bi_eval_factored values-only at 4096 and 10^6 points of one cell tuple; the planner's
+    share of a call from device events.  Alternated calls, medians with quartiles.  Written to
+    profiles/sourcewise_scan_measure.txt as well."""
+    import os
+    from blueice_amd import grid
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, B = 5, args.measure_bins ** 3
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05
+    rows /= rows.sum(axis=-1, keepdims=True)
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    mid = n_a // 2
+    shape = sum(mus[s, mid] * rows[s, mid] for s in range(S))
+    scale = 1e4 / shape.sum()
+    fac.set_counts(rng.poisson(scale * shape).astype(float))
+    nnz = fac.build_nonempty()
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    def alternated(calls, rounds):
+        times = {name: [] for name, _ in calls}
+        for rnd in range(2 + rounds):
+            for name, call in calls:
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 2:
+                    times[name].append(time.perf_counter() - t0)
+        return times
+
+    say('# examples/many_nuisances.py --measure-grid --measure-bins %d --rounds %d on %s' % (args.measure_bins, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>: 8 rows per point), %d anchors, %d bins, %d listed bins (10^4 events); '
+        'every other class: not measured' % (d, S, n_a, B, int(nnz[0])))
+    # the grid: the multiplier of source 0 kept, two shape parameters and the multiplier of source 1 reduced
+    names = ['r0', 'z0', 'z1', 'r1']
+    kind, index = np.array([1, 0, 0, 1], dtype=np.int32), np.array([0, 0, 1, 1], dtype=np.int32)
+    nodes = [np.linspace(0.5, 1.5, 33), np.linspace(-1.9, 1.9, 65), np.linspace(-1.9, 1.9, 65), np.linspace(0.8, 1.2, 7)]
+    z0, scale0, unit = np.zeros((1, d)), np.full((1, S), scale), np.full((1, S), scale)
+    G = int(np.prod([len(v) for v in nodes]))
+    logw = [np.zeros(len(nodes[0]))] + [np.log(grid.trapezoid_weights(v)) for v in nodes[1:]]
+
+    class HostLikelihood:
+        """what _host_engine asks of a likelihood: eval_points over the axes' columns, through bi_eval_factored"""
+        def eval_points(self, call, livetime_days=None):
+            P = len(call['r0'])
+            z, r = np.zeros((P, d)), np.full((P, S), scale)
+            z[:, 0], z[:, 1], r[:, 0], r[:, 1] = call['z0'], call['z1'], scale * call['r0'], scale * call['r1']
+            return fac.eval(z, r)[0]
+
+    axes = list(zip(names, nodes))
+    run = {route: (lambda route=route: fac.grid_reduce(kind, index, z0, scale0, unit, None, 1, nodes, logw=logw, route=route)) for route in (1, 0)}
+    host = lambda: grid._host_engine(HostLikelihood(), axes, 1, logw[1:], None, None, None, {})
+    a, b, h = run[1](), run[0](), host()
+    say('grid of 33 x 65 x 65 x 7 = %d points, 16 cell tuples: route scan %d chunk(s), %d launches; route points %d launches'
+        % (G, a[3][0], a[3][3], b[3][3]))
+    say('    max |log_marginal difference|: scan - points %.2e, scan - host %.2e; argmax equal: %s, %s'
+        % (np.max(np.abs(a[0] - b[0])), np.max(np.abs(a[0].ravel() - h[0])), np.array_equal(a[2], b[2]), np.array_equal(a[2].ravel(), h[2])))
+    rounds = max(5, args.rounds // 4)
+    t = alternated([('scan', run[1]), ('points', run[0])], rounds)
+    th = alternated([('host', host)], 3)
+    for name, tt in (('route scan  ', t['scan']), ('route points', t['points']), ('engine host ', th['host'])):
+        say('    bi_grid_reduce_sourcewise %s %s   %.2f M points/s' % (name, quartiles(tt), G / np.median(tt) / 1e6))
+    say('    ratio points / scan %.2f, host / scan %.2f' % (np.median(t['points']) / np.median(t['scan']), np.median(th['host']) / np.median(t['scan'])))
+    # one cell tuple: bi_eval_sourcewise_scan against bi_eval_factored values-only
+    for P in (4096, 10 ** 6):
+        z, r = rng.uniform(0.05, 0.95, (P, d)), scale * rng.uniform(0.8, 1.2, (P, S))
+        ll_s, ll_e = fac.eval_scan(z, r)[0], fac.eval(z, r)[0]
+        c = fac.last_scan_counters
+        rounds = args.rounds if P == 4096 else 5
+        t = alternated([('scan', lambda: fac.eval_scan(z, r)), ('factored', lambda: fac.eval(z, r))], rounds)
+        say('%7d points of one cell tuple (%d groups, %d items, nslots %d): bi_eval_sourcewise_scan %s   bi_eval_factored values-only %s   '
+            'ratio %.2f   (max |ll difference| / |ll| %.1e)' % (P, c[0], c[1], fac.get_param('last_scan_nslots'), quartiles(t['scan']),
+                                                              quartiles(t['factored']), np.median(t['factored']) / np.median(t['scan']),
+                                                              np.max(np.abs(ll_s - ll_e) / np.abs(ll_e))))
+        # the planner's share, from device events: everything in front of the matrix-core launch (the host read included), and the launch
+        parts = {}
+        for what, bits_ in (('planner', 1), ('k_scan_mfma', 2)):
+            fac.set_param('sourcewise_scan_timed', bits_)
+            fac._dev.profile(True)
+            ks = []
+            for _ in range(rounds):
+                fac.eval_scan(z, r)
+                ks.append(fac._dev.profile_read()[1] * 1e-3)
+            fac._dev.profile(False)
+            parts[what] = ks
+        fac.set_param('sourcewise_scan_timed', 3)
+        say('%7d points, device events: planner (screen, key, sort, structure, host read, fill) %s   k_scan_mfma %s   planner share %.0f %%'
+            % (P, quartiles(parts['planner']), quartiles(parts['k_scan_mfma']),
+               100 * np.median(parts['planner']) / (np.median(parts['planner']) + np.median(parts['k_scan_mfma']))))
+    say('# not measured: blueice_amd.grid.grid_scan through the likelihood class, every class but <4, 1>, several datasets, other list lengths')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_scan_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+
+
+def grid_limit():
+    """The 90 % credible upper limit on the signal's multiplier from a gridded likelihood (blueice_amd.grid.grid_scan on the
+    source-wise model: bi_grid_reduce_sourcewise), marginalised by the trapezoid rule over the signal's own nuisance parameter and
+    two background multipliers with every other parameter at its default, beside the same quantile of a chain over the same four
+    parameters (blueice_amd.sampler.sample_posterior with the others fixed)."""
+    from blueice_amd import GaussianPrior, SourceWiseBinnedLogLikelihood, grid, sampler
+    from blueice_amd.synthetic import many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins))
+    lf = SourceWiseBinnedLogLikelihood(conf, likelihood_config=dict(nonempty_bins=True))
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    lf.prepare()
+    np.random.seed(3)
+    d = lf.base_model.simulate()
+    lf.set_data(d[:max(len(d) // 8, 1)])                          # mostly empty bins: the non-empty-bin form's case
+    nuisance = own[0][0]                                          # the signal's first own parameter
+    keep = [('s0_rate_multiplier', np.linspace(0.0, 1.0, 65))]
+    reduce = [(nuisance, np.linspace(-2.0, 2.0, 33)), ('s1_rate_multiplier', np.linspace(0.02, 0.4, 25)),
+              ('s2_rate_multiplier', np.linspace(0.02, 0.4, 25))]
+    fixed = {n: 0.0 for n in names if n != nuisance}
+    fixed['s3_rate_multiplier'] = 0.125
+    results = {}
+    for route in ('scan', 'points'):
+        lf.config['sourcewise_grid_route'] = route
+        grid.grid_scan(lf, keep=keep, reduce=reduce, **fixed)    # (warm: allocations)
+        t0 = time.perf_counter()
+        results[route] = grid.grid_scan(lf, keep=keep, reduce=reduce, **fixed)
+        res = results[route]
+        print('grid of %d x %d x %d x %d = %d points, route %s on the %s engine: %.3f s (%d chunks, %d launches, %d excluded points)'
+              % (len(keep[0][1]), 33, 25, 25, res.counters[1], route, res.engine, time.perf_counter() - t0, res.counters[0], res.counters[3],
+                 res.excluded))
+    limits = {r: v.credible_upper_limit(0.9) for r, v in results.items()}
+    rng = np.random.default_rng(1)
+    W, steps, burn = 32, 2000, 500
+    best = results['scan']
+    k = int(np.argmax(best.profile))
+    at = dict([('s0_rate_multiplier', keep[0][1][k])] + [(n, float(best.best[n][k])) for n, _ in reduce])
+    order = ['s0_rate_multiplier', 's1_rate_multiplier', 's2_rate_multiplier', nuisance]      # rate multipliers first, then shape parameters
+    p0 = np.array([at[n] for n in order])[None, :] + 0.01 * rng.standard_normal((W, 4))
+    p0[:, :3] = np.abs(p0[:, :3])
+    t0 = time.perf_counter()
+    run = sampler.sample_posterior(lf, n_walkers=W, n_steps=steps, seed=4, p0=p0, **fixed)
+    assert run.names == order, run.names
+    kept = run.flat(discard=burn)
+    s0 = kept[:, run.names.index('s0_rate_multiplier')]
+    inside = np.mean(s0 <= keep[0][1][-1])
+    print('chain over the same %d parameters: %d walkers x %d steps on the %s engine in %.3f s, acceptance %.3f'
+          % (len(run.names), W, steps, run.engine, time.perf_counter() - t0, run.acceptance_fraction.mean()))
+    print('90 % credible upper limit on s0_rate_multiplier (flat priors on the multipliers, the nuisance parameter\'s Gaussian constraint):')
+    print('    gridded likelihood, route scan    %.4f' % limits['scan'])
+    print('    gridded likelihood, route points  %.4f' % limits['points'])
+    print('    chain (posterior quantile)        %.4f   (%.1f %% of the chain inside the grid\'s range of the multiplier)'
+          % (np.quantile(s0, 0.9), 100 * inside))
+
+
+if args.grid:
+    grid_limit()
+    raise SystemExit(0)
+if args.measure_grid:
+    measure_grid()
+    raise SystemExit(0)
 if args.measure_sampler:
     measure_sampler()
     raise SystemExit(0)

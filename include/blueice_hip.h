@@ -867,6 +867,44 @@ int bi_grid_reduce(bi_ctx* ctx, int64_t E, const int64_t* dataset /*[E] or NULL*
                    const double* logw, int64_t chunk, double* log_marginal /*[E][K]*/, double* profile /*[E][K]*/,
                    int64_t* argmax /*[E][K]*/, int64_t* counters /*[4] or NULL*/);
 
+/* Source-wise models on the matrix-core scan route, and their gridded likelihood.  The per-point kernels of a source-wise model
+ * stream a point's NR = sum_s 2^e_s rows once per point; a batch whose points pile up in a handful of cell tuples (one cell per
+ * source over the axes it owns) -- a gridded likelihood -- reads the same rows over and over.  The scan route sorts the staged
+ * points by (cell tuple, dataset) on the device, chops every group into 16-point work items and hands them to the matrix-core scan
+ * kernel of the grid model over the compacted rows of the non-empty-bin form: mu[bin][point] = sum_k row_k[bin] w_k r_s(k), the
+ * rows of a group read once per strip of bins; sum_s lambda_s and the lgamma sum are subtracted once per point, as above.
+ * Conditions, else BI_ERR_INVALID naming the cause: the non-empty-bin form is built (bi_sourcewise_build_nonempty) and chosen
+ * (sourcewise_form = 1); NR <= 32, the scan kernel's row limit; the cell tuples times T fit a 63-bit sort key.
+ *   bi_eval_sourcewise_scan       bi_eval_sourcewise_planned's arguments and conventions on that route.  The screen is the same
+ *                                 planner kernel: status [P] (or NULL) and the -inf of a rejected point are bit for bit
+ *                                 bi_eval_sourcewise_planned's.  A live point's ll agrees with it to rounding, NOT bit for bit,
+ *                                 and -- unlike every per-point entry point -- its bits may depend on the batch: which points
+ *                                 share a work item, the number of partial sums per item and whether a block of bins takes the
+ *                                 product form (counts of 1 and 2: one logarithm of the product of mu^n) follow from the batch.
+ *                                 The same call gives the same bits every time (no floating-point atomics outside partial
+ *                                 slots that one wave owns, every sum in a fixed order).  A listed bin with mu = 0 or a count
+ *                                 that is no integer gives -inf (a nan count cannot reach the store: bi_factored_set_counts refuses it).  One host read per call (the planner's
+ *                                 counts).  counters [5] or NULL: [0] groups (cell tuple, dataset; very long groups are cut into
+ *                                 several), [1] work items, [2] live points, [3] launches, [4] host reads inside the call.
+ *                                 P = 0: BI_OK without device work.  n_scan_launches advances, last_scan_* report the launch.
+ *   bi_grid_reduce_sourcewise     bi_grid_reduce's contract, checks, limits and errors (reported under this name) with this
+ *                                 model's likelihood: var_index refers to its d axes and S sources, `dataset` to the sets of
+ *                                 bi_factored_set_counts or of the toy generator.  Per chunk the staged points are evaluated by
+ *                                 route 0: the planner and per-point kernels of bi_eval_sourcewise_planned (on the dense store or
+ *                                 the non-empty-bin form, whichever the context evaluates on); route 1: the scan route above;
+ *                                 route -1: 1 where the conditions hold, else 0.  The reduction reads the planner's status words;
+ *                                 nothing is read by the host per chunk on route 0, the planner's counts on route 1.  With route
+ *                                 0 and one chunk the outputs are bit for bit the reduction of bi_eval_sourcewise_planned's
+ *                                 values.  counters [5] or NULL: chunks, evaluations, excluded points, launches, the route taken. */
+int bi_eval_sourcewise_scan(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                            int32_t* status, int64_t* counters /*[5] or NULL*/);
+int bi_grid_reduce_sourcewise(bi_ctx* ctx, int64_t E, const int64_t* dataset /*[E] or NULL*/, int F, int n_keep,
+                              const int32_t* var_kind, const int32_t* var_index, const double* z0 /*[E][d]*/,
+                              const double* scale0 /*[E][S]*/, const double* unit /*[E][S]*/, const int32_t* n_nodes /*[F]*/,
+                              const double* nodes, const double* term, const double* logw, int64_t chunk, int route,
+                              double* log_marginal /*[E][K]*/, double* profile /*[E][K]*/, int64_t* argmax /*[E][K]*/,
+                              int64_t* counters /*[5] or NULL*/);
+
 /* One parameter point against datasets [t0, t1): the toy-MC form.  mu_b / log mu_b are computed
  * once and every dataset reduces sum_b xlogy(n, mu) against them.  Not available with
  * Beeston-Barlow (mu then depends on the data).  out [t1 - t0]. */
@@ -1083,6 +1121,9 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     bi_sample_stretch_sourcewise run on the non-empty-bin form where bi_sourcewise_build_nonempty has built
  *                     it; 0 = they read the dense store although it is built.  Read-only sourcewise_nonempty_ready (1 while the
  *                     form is built) and sourcewise_nonempty_bytes (the bytes of its compacted copies, 0 when it is not)
+ *   sourcewise_scan_timed   while profiling (bi_profile_enable), which parts of the source-wise scan route are between events:
+ *                     bit 0 = the planner (screen, key, sort, structure, the host read of the counts, fill), bit 1 = the
+ *                     matrix-core launches (3: both); bi_profile_read sums what was timed
  *   toy_offset        bi_generate_toys: toy t of a call is dataset toy_offset + t of the seed's random stream, so ranks
  *                     that each generate a range of one toy-MC ensemble draw the same toys as one process would (0)
  *   scan_pow          scans over dense data on the matrix cores run on a copy of the template rows whose bins are ordered by
