@@ -11,5 +11,6 @@ from .likelihood import (LogLikelihoodBase, BinnedLogLikelihood, UnbinnedLogLike
 from .grid import grid_scan, GridResult  # noqa: F401
 from .coarse import CoarseBinning  # noqa: F401
 from .source_wise import SourceWiseBinnedLogLikelihood  # noqa: F401
+from .source_wise_unbinned import SourceWiseUnbinnedLogLikelihood  # noqa: F401
 
 __version__ = '0.1.0'

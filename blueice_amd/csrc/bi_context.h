@@ -180,6 +180,16 @@ struct bi_ctx {
         int ne_max_nbx = 1;
         std::vector<int64_t> ne_off, ne_np, ne_cnt_off;
         DevBuf ne_ps, ne_cnt, ne_tab;
+        // the event store (bi_sourcewise_events.h): the pdf value of every event at every anchor row, ev_ps [rows][ev_cols]; set t
+        // of ev_T at the columns [ev_first[t], ev_first[t] + ev_n[t]), every set padded to whole tiles (at least one; zeros in
+        // the padding).  While it exists (ev_ready, or ev_open between _events_begin and _events_end) the context is an
+        // unbinned source-wise likelihood: bi_eval_factored and the native fit read it, every other source-wise call refuses.
+        bool ev_ready = false, ev_open = false;
+        int64_t ev_T = 0, ev_cols = 0, ev_bytes = 0;
+        double ev_outlier = 0.0;
+        std::vector<int64_t> ev_first, ev_n;
+        std::vector<char> ev_row_set;                // [rows] the row has been uploaded (bi_sourcewise_events_set_row)
+        DevBuf ev_ps;
     } fac;
     int64_t sourcewise_form = 1;                 // 0: source-wise evaluations read the dense store although the non-empty-bin form is built
     int64_t sourcewise_scan_timed = 3;           // profiling: bit 0 = the scan route's planner, bit 1 = its matrix-core launches are timed

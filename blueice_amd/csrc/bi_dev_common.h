@@ -231,6 +231,25 @@ struct SourcewiseNonemptyArgs {
     const unsigned* live;      // [items] planned items (GRAD = false): 0 = rejected; NULL on the host paths
 };
 
+// k_sourcewise_events (bi_k_sourcewise_events.h): FactoredArgs' descriptors over the event store of a source-wise model.  The rows
+// of an item are the store's rows at ITS event set's columns (rowoff holds the set's first column), and the number of tiles and
+// of events is the set's: per item.
+struct SourcewiseEventsArgs {
+    const double* ps;          // [rows][columns] the pdf values of every event at every anchor row
+    const int64_t* rowoff;     // [items][NR] element offsets of the item's corner rows at its set's first column
+    const double* coef;        // [items][NR][1 + EM] as FactoredArgs::coef
+    const double* rates;       // [items][SC]
+    const int64_t* item_n;     // [items] events of the item's set: later columns are padding, masked by index
+    const int32_t* item_tiles; // [items] tiles of the item's set (>= 1)
+    double* partial;           // [items][gridDim.x][NSL]
+    unsigned* pflags;          // [items][gridDim.x][NSL]
+    double outlier;            // likelihood of events whose density is not > 0 (0 = none)
+    int NR;                    // rows per item
+    int chunks;                // ItemTiles' chunks
+    int max_blocks;            // an item's tiles are walked by min(tiles, max_blocks) blocks, whatever gridDim.x is
+    int e[8];                  // own axes of every source
+};
+
 // The scan planner of source-wise points (bi_k_sourcewise_scan.h): from what k_sourcewise_plan<SC, NE = true> wrote per point to
 // ScanArgs' descriptors per 16-point item.  One block of arguments for its four kernels; every pointer is device memory.
 struct SourcewiseScanArgs {

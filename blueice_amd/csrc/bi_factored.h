@@ -13,7 +13,9 @@
 // Limits: d <= 32 axes, S <= 8 sources, e_s <= 3 own axes (a source that responds to more belongs on the full grid).  The
 // geometry arrays here are sized by those, not by kMaxDim (PointGeom).  Out of scope, refused where they can be asked for:
 // sources that may go negative (template entries must be finite and >= 0; rates outside [0, inf) are BI_ST_UNPHYSICAL),
-// Beeston-Barlow, unbinned data.  The counts are dense doubles [T][Bp]: the caller's (bi_factored_set_counts) or toys drawn
+// Beeston-Barlow.  Unbinned data are a second form of the data, the event store of bi_sourcewise_events.h: while it exists
+// factored_eval, and through it the native fit, run on it (FacBatch with events = true) and every other source-wise entry point
+// refuses (fac_check).  The counts are dense doubles [T][Bp]: the caller's (bi_factored_set_counts) or toys drawn
 // on the device (bi_sourcewise_generate_toys, bi_sourcewise.h, which also holds the expectation and goodness-of-fit layers).
 // Beside them, when asked for, the non-empty-bin form of the same counts (bi_sourcewise_build_nonempty, bi_sourcewise_nonempty.h:
 // per dataset its list of bins with events and a compacted copy of the rows over it), on which factored_eval, and through it the
@@ -119,7 +121,7 @@ struct FacSource {
 
 // the early exits of one point, in screen_point's order: dataset (where the call reads data), anchor box (every axis), rates
 int32_t fac_screen(const bi_ctx::Factored& m, const double* z, const double* rs, int64_t ds, bool dataset_test, FacGeom& g) {
-    if (dataset_test && (ds < 0 || ds >= m.T)) return BI_ST_BAD_DATASET;
+    if (dataset_test && (ds < 0 || ds >= (m.ev_ready ? m.ev_T : m.T))) return BI_ST_BAD_DATASET;
     if (!fac_geometry(m, z, g)) return BI_ST_OUT_OF_BOUNDS;
     const double inf = std::numeric_limits<double>::infinity();
     FacSource fs;
@@ -131,10 +133,20 @@ int32_t fac_screen(const bi_ctx::Factored& m, const double* z, const double* rs,
     return 0;
 }
 
-int fac_check(bi_ctx* c, const char* who, bool need_counts) {
+// events_ok: the call serves the event store (bi_sourcewise_events.h) -- bi_eval_factored, the native fit and the store's own
+// entry points; while a store exists every other source-wise call is refused, and those read it instead of the counts
+int fac_check(bi_ctx* c, const char* who, bool need_counts, bool events_ok = false) {
     if (!c) return BI_ERR_INVALID;
     if (c->pending) return fail(c, BI_ERR_STATE, "a bi_eval_begin is outstanding on this context: call bi_eval_end first");
     if (!c->fac.ready) return fail(c, BI_ERR_STATE, "%s: no source-wise model uploaded (bi_factored_begin ... bi_factored_end first)", who);
+    if (c->fac.ev_ready || c->fac.ev_open) {
+        if (!events_ok)
+            return fail(c, BI_ERR_STATE, "%s: the context holds an event store (it is an unbinned source-wise likelihood): "
+                        "bi_sourcewise_drop_events first", who);
+        if (need_counts && !c->fac.ev_ready)
+            return fail(c, BI_ERR_STATE, "%s: the event store is still being filled (bi_sourcewise_events_end first)", who);
+        return BI_OK;
+    }
     if (need_counts && (c->fac.T < 1 || !c->fac.counts.p))
         return fail(c, BI_ERR_STATE, "%s: no counts uploaded (bi_factored_set_counts first)", who);
     return BI_OK;
@@ -148,6 +160,14 @@ void fac_drop_nonempty(bi_ctx::Factored& m) {
     m.ne_max_nbx = 1;
     m.ne_off.clear(); m.ne_np.clear(); m.ne_cnt_off.clear();
     dev_free(m.ne_ps); dev_free(m.ne_cnt); dev_free(m.ne_tab);
+}
+// The event store (bi_sourcewise_events.h) belongs to the model: bi_factored_begin and bi_sourcewise_drop_events release it.
+void fac_drop_events(bi_ctx::Factored& m) {
+    m.ev_ready = m.ev_open = false;
+    m.ev_T = m.ev_cols = m.ev_bytes = 0;
+    m.ev_outlier = 0.0;
+    m.ev_first.clear(); m.ev_n.clear(); m.ev_row_set.clear();
+    dev_free(m.ev_ps);
 }
 // do bi_eval_factored (and with it the native fit), bi_eval_sourcewise_planned and bi_sample_stretch_sourcewise run on it
 bool fac_nonempty_on(const bi_ctx* c) { return c->fac.ne_ready && c->sourcewise_form == 1; }
@@ -238,11 +258,15 @@ struct FacBatch {
     std::vector<int32_t> tiles;                 // [n] tiles of the item's dataset's list
     std::vector<double> lam_sum;                // [n] sum_s lambda_s, sources ascending from 0.0
     std::vector<double> hN, hdN;                // [n][S] N_s = sum_c w_c R_{s,c}; [n][S][kFacMaxOwn] d_j N_s (order 1)
+    // the event store (order 0 / 1, bi_sourcewise_events.h): the descriptors point at the item's event set's columns; `tiles` are
+    // the set's, lam_sum is sum_s r_s (sources ascending from 0.0), cnt_off holds the set's number of events
+    bool events;
 
     FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true, bool nonempty_ = false)
         : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
           NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts),
-          nonempty(nonempty_ && order_ <= 1 && reads_counts) {
+          nonempty(nonempty_ && order_ <= 1 && reads_counts && !ctx->fac.ev_ready),
+          events(ctx->fac.ev_ready && order_ <= 1 && reads_counts) {
         c->last_point_pieces = 0;               // (a call with no live item launches nothing)
     }
 
@@ -277,6 +301,10 @@ struct FacBatch {
         if (order == 3) chain.assign(n * SC * W, 0.0);
         if (order >= 1) { hM.resize(n * S); hdM.resize(n * S * kFacMaxOwn); }
         if (order == 2) hd2M.resize(n * S * kFacMaxOwn);
+        if (events) {
+            tiles.assign(n, 1);
+            lam_sum.assign(n, 0.0);
+        }
         if (nonempty) {
             tiles.assign(n, 1);
             lam_sum.assign(n, 0.0);
@@ -291,7 +319,8 @@ struct FacBatch {
                 const int64_t ds = dataset ? dataset[p] : 0;
                 fac_geometry(m, z ? z + p * d : nullptr, g);
                 // the rows of the item: the dense tensor's, or those of its dataset's compacted copy
-                const int64_t row_base = nonempty ? m.ne_off[(size_t)ds] : 0, row_stride = nonempty ? m.ne_np[(size_t)ds] : m.Bp;
+                const int64_t row_base = events ? m.ev_first[(size_t)ds] : nonempty ? m.ne_off[(size_t)ds] : 0;
+                const int64_t row_stride = events ? m.ev_cols : nonempty ? m.ne_np[(size_t)ds] : m.Bp;
                 double lam = 0.0;
                 int k = 0;
                 for (int s = 0; s < S; ++s) {
@@ -319,6 +348,7 @@ struct FacBatch {
                         for (int x = 0; order == 2 && x < fs.e * (fs.e - 1) / 2; ++x) q[W + x] = fs.d2w[cnr][x];
                     }
                     rates[(size_t)i * SC + s] = rate_scale ? fs.M * rate_scale[p * S + s] : fs.M;
+                    if (events) lam = lam + rates[(size_t)i * SC + s];
                     if (order >= 1) {
                         hM[(size_t)i * S + s] = fs.M;
                         for (int j = 0; j < fs.e; ++j) hdM[((size_t)i * S + s) * kFacMaxOwn + j] = fs.dM[j];
@@ -330,7 +360,12 @@ struct FacBatch {
                         for (int j = 0; j < fs.e; ++j) q[1 + j] = rs * fs.dM[j];
                     }
                 }
-                cnt_off[(size_t)i] = nonempty ? m.ne_cnt_off[(size_t)ds] : dataset_test ? ds * m.Bp : 0;
+                cnt_off[(size_t)i] = events ? m.ev_n[(size_t)ds] : nonempty ? m.ne_cnt_off[(size_t)ds] : dataset_test ? ds * m.Bp : 0;
+                if (events) {
+                    const int64_t n_ev = m.ev_n[(size_t)ds];
+                    tiles[(size_t)i] = (int32_t)std::max<int64_t>(1, (n_ev + kTile - 1) / kTile);
+                    lam_sum[(size_t)i] = lam;
+                }
                 if (nonempty) {
                     tiles[(size_t)i] = (int32_t)(m.ne_np[(size_t)ds] / kTile);
                     lam_sum[(size_t)i] = lam;
@@ -412,14 +447,13 @@ struct FacBatch {
         return BI_OK;
     }
 
-    // run() on the non-empty-bin form: k_sourcewise_nonempty over the items' compacted copies.  An item's blocks are
-    // min(its tiles, kFacBlocks) -- its dataset's list alone decides; the grid's x is the largest of them over the batch (the
-    // other blocks post +0.0), which sizes the partial buffers and the sub-batches and changes no bit of any item.
-    template <class L>
-    int run_nonempty(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
-        SourcewiseNonemptyArgs a{};
-        a.ps = (const double*)m.ne_ps.p;
-        a.counts = (const double*)m.ne_cnt.p;
+    // run() over per-item lists: Args is SourcewiseNonemptyArgs (k_sourcewise_nonempty over the items' compacted copies) or
+    // SourcewiseEventsArgs (k_sourcewise_events over the items' event sets), `a` holds what is the same for every item and
+    // item_at(b, at) points b at what part 3 of the upload means to the kernel (the item's counts, or its number of events).  An
+    // item's blocks are min(its tiles, kFacBlocks) -- its own list alone decides; the grid's x is the largest of them over the
+    // batch (the other blocks post +0.0), which sizes the partial buffers and the sub-batches and changes no bit of any item.
+    template <class Args, class At, class L>
+    int run_lists(Args a, At item_at, int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
         a.NR = NR;
         a.chunks = (int)c->tile_chunks;
         a.max_blocks = kFacBlocks;
@@ -431,12 +465,12 @@ struct FacBatch {
             const int64_t nj = std::min(per_call, n_items - j0);
             const int rc = run_item_chunks(c, nj, nbx, nsl, perm + j0 * nsl, slot_lg + j0 * nsl, (double*)pu.host_out(), nullptr, what,
                                            [&](int64_t i0, dim3 grid, double* partial, unsigned* pflags) {
-                                               SourcewiseNonemptyArgs b = a;
+                                               Args b = a;
                                                const int64_t at = j0 + i0;
                                                b.rowoff = pu.dev<int64_t>(0) + at * NR;
                                                b.coef = pu.dev<double>(1) + at * NR * WC;
                                                b.rates = pu.dev<double>(2) + at * SC;
-                                               b.item_cnt = pu.dev<int64_t>(3) + at;
+                                               item_at(b, at);
                                                b.item_tiles = pu.dev<int32_t>(5) + at;
                                                b.partial = partial;
                                                b.pflags = pflags;
@@ -449,6 +483,22 @@ struct FacBatch {
             c->last_point_pieces = pieces;
         }
         return BI_OK;
+    }
+    // ... on the non-empty-bin form
+    template <class L>
+    int run_nonempty(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+        SourcewiseNonemptyArgs a{};
+        a.ps = (const double*)m.ne_ps.p;
+        a.counts = (const double*)m.ne_cnt.p;
+        return run_lists(a, [&](SourcewiseNonemptyArgs& b, int64_t at) { b.item_cnt = pu.dev<int64_t>(3) + at; }, nsl, perm, slot_lg, what, launch);
+    }
+    // ... on the event store
+    template <class L>
+    int run_events(int nsl, const int64_t* perm, const double* slot_lg, const char* what, L launch) const {
+        SourcewiseEventsArgs a{};
+        a.ps = (const double*)m.ev_ps.p;
+        a.outlier = m.ev_outlier;
+        return run_lists(a, [&](SourcewiseEventsArgs& b, int64_t at) { b.item_n = pu.dev<int64_t>(3) + at; }, nsl, perm, slot_lg, what, launch);
     }
 
     // the chain rule of item i's gradient sums h (the slots of k_morph_factored<.., GRAD>) to gp [d + S]: sources ascending, own
@@ -474,6 +524,7 @@ int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scal
                   int32_t* status) {
     const bool want_grad = grad != nullptr;
     const bool ne = fac_nonempty_on(c);         // the non-empty-bin form (bi_sourcewise_nonempty.h), where it is built and chosen
+    const bool evs = c->fac.ev_ready;           // the event store (bi_sourcewise_events.h): the unbinned likelihood
     FacBatch b(c, want_grad ? 1 : 0, true, ne);
     const int d = b.d, S = b.S, NSL = factored_slots(b.SC, b.EM, want_grad);
     const double inf = std::numeric_limits<double>::infinity();
@@ -492,13 +543,20 @@ int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scal
     std::vector<double> slot_lg(n * NSL, 0.0);
     for (size_t q = 0; q < perm.size(); ++q) perm[q] = (int64_t)q;
     for (size_t i = 0; i < n; ++i) {
+        if (evs) { slot_lg[i * NSL] = b.lam_sum[i]; continue; }     // (sum_s r_s: there is no lgamma over events)
         const double lg = b.m.h_lgsum[(size_t)(dataset ? dataset[b.live[i]] : 0)];
         slot_lg[i * NSL] = ne ? b.lam_sum[i] + lg : lg;         // (k_finish subtracts sum_s lambda_s + lgsum: one number per item)
     }
     int rc = b.upload({{perm.data(), perm.size() * sizeof(int64_t)}, {slot_lg.data(), slot_lg.size() * sizeof(double)}}, n * NSL);
     if (rc) return rc;
     const bool nt = c->nt_loads == 1 || (c->nt_loads == 2 && n_items == 1);
-    if (ne)
+    if (evs)
+        rc = b.run_events(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
+                          [&](const SourcewiseEventsArgs& a, dim3 grid) {
+                              const int e = launch_sourcewise_events(c, b.SC, b.EM, want_grad, a, grid);
+                              return e ? fail(c, e, "bi_eval_factored: no kernel variant for %d source slots with %d own axes", b.SC, b.EM) : BI_OK;
+                          });
+    else if (ne)
         rc = b.run_nonempty(NSL, b.pu.dev<int64_t>(b.first_extra), b.pu.dev<double>(b.first_extra + 1), "bi_eval_factored",
                             [&](const SourcewiseNonemptyArgs& a, dim3 grid) {
                                 const int e = launch_sourcewise_nonempty(c, b.SC, b.EM, want_grad, a, grid);
@@ -519,7 +577,12 @@ int factored_eval(bi_ctx* c, int64_t P, const double* z, const double* rate_scal
         const double* h = out + (size_t)i * NSL;
         ll[p] = h[0];
         if (!want_grad || !std::isfinite(h[0])) continue;
-        if (ne) {
+        if (evs) {
+            // sum_e g tau_s - 1: a pdf integrates to 1 exactly, and its integral has no slope, so the ups slots stand as they are
+            std::copy(h, h + NSL, h_ne.begin());
+            for (int s = 0; s < S; ++s) h_ne[(size_t)(1 + s)] = h[1 + s] - 1.0;
+            h = h_ne.data();
+        } else if (ne) {
             // the sums over the listed bins less the rows' totals: sum_Z g tau_s - N_s and sum_Z g ups_s,j - d_j N_s are what the
             // dense kernel's slots hold (sum_b f tau_s, sum_b f ups_s,j); then the same chain rule
             std::copy(h, h + NSL, h_ne.begin());
@@ -561,6 +624,7 @@ int bi_factored_begin(bi_ctx* c, int d, const int32_t* n_anchor, const double* a
     m.real_T = 0;
     release_coarse(c->sw_coarse);   // (groups of the previous model's bins)
     fac_drop_nonempty(m);           // (compacted copies of the previous model's rows)
+    fac_drop_events(m);             // (events scored at the previous model's anchors)
     m.d = d; m.S = S; m.B = B;
     m.Bp = std::max<int64_t>(kTile, (B + kTile - 1) / kTile * kTile);
     m.grid.assign((size_t)d, {});
@@ -697,7 +761,7 @@ int bi_factored_set_counts(bi_ctx* c, int64_t T, const double* counts) {
 
 int bi_eval_factored(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll, double* grad,
                      int32_t* status) {
-    int rc = fac_check(c, "bi_eval_factored", true);
+    int rc = fac_check(c, "bi_eval_factored", true, true);
     if (rc) return rc;
     if (P < 0 || (P > 0 && !ll)) return fail(c, BI_ERR_INVALID, "bi_eval_factored: bad P / output pointer");
     if (c->fac.d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "bi_eval_factored: z is NULL");
@@ -710,7 +774,7 @@ int bi_fit_batched_factored(bi_ctx* c, int64_t P, int F, const int32_t* var_kind
                             const double* hi, const int32_t* n_kinks, const double* kinks, double gtol, int max_iter,
                             const double* prior_mean, const double* prior_sigma, const double* prior_const, double* x_out,
                             double* f_out, int32_t* flags_out, int64_t* counters) {
-    int rc = fac_check(c, "bi_fit_batched_factored", true);
+    int rc = fac_check(c, "bi_fit_batched_factored", true, true);
     if (rc) return rc;
     return fit_batched(c, "bi_fit_batched_factored", kFitFactored, P, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_kinks, kinks,
                        gtol, max_iter, prior_mean, prior_sigma, prior_const, x_out, f_out, flags_out, counters);

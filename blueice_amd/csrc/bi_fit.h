@@ -508,7 +508,7 @@ int fit_batched(bi_ctx* c, const char* who, FitEval eval, int64_t P, int F, cons
     }
     if (real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->real_T))) return rc;
     if (sw_real && (rc = check_entry_datasets(c, who, nullptr, P, dataset, c->fac.real_T))) return rc;
-    if (factored && !sw_real && (rc = check_entry_datasets(c, who, "problem", P, dataset, c->fac.T))) return rc;
+    if (factored && !sw_real && (rc = check_entry_datasets(c, who, "problem", P, dataset, c->fac.ev_ready ? c->fac.ev_T : c->fac.T))) return rc;
     if (P == 0) { if (counters) counters[0] = counters[1] = counters[2] = counters[3] = 0; return BI_OK; }
     DeviceObjective o{};
     o.c = c; o.eval = eval; o.d = d; o.S = S;

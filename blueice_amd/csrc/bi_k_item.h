@@ -3,6 +3,7 @@
 // block posts one partial per result slot and k_finish adds the blocks.  What a kernel adds is its prologue pointers and its
 // per-bin mathematics.  The host half of the same paths is bi_items.h.
 //     ItemTiles            the XCD-aware tile walk of one work item
+//     ListTiles            ... with the item's own number of blocks as its stride (k_sourcewise_nonempty, k_sourcewise_events)
 //     item_columns         the G coefficient columns of one bin (HessArgs kernels, one bin in flight per thread)
 //     item_reduce_store    the block reduction in its fixed order and the store of the block's partials
 //     item_chain           the single-column expectation sum_k a_k row_k[b]
@@ -27,6 +28,14 @@ struct ItemTiles {
         const int t = chunks > 1 ? (lt % chunks) * per_chunk + lt / chunks : lt;
         return t < n_tiles ? t : -1;
     }
+};
+
+// ItemTiles with the item's own stride: block x of nbx takes the steps x, x + nbx, ...
+struct ListTiles : ItemTiles {
+    int nbx;
+    template <class Args>
+    __device__ __forceinline__ ListTiles(const Args& a, int n_tiles, int nbx_) : ItemTiles(a, n_tiles), nbx(nbx_) {}
+    __device__ __forceinline__ void step() { lt += nbx; }
 };
 
 // acc[g] = sum_k coef[k][g] row_k[bin], k ascending from 0.0 with one fma per row: column 0 is item_chain's mu_b bit for bit

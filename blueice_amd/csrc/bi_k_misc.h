@@ -956,7 +956,10 @@ __global__ __launch_bounds__(kThreads) void k_score_locate(const double* __restr
 constexpr int score_events_per_thread(int K) { return K <= 3 ? 4 : 1; }
 
 // K: analysis dimensions of the 'linear' method (0 = 'piecewise': one value per event and row)
-template <int K>
+// RGI2D (K = 2 only; bi_sourcewise_score_events): value = value + (V * w_0) * w_1, the association of scipy's routine for
+// two-dimensional fields, which RegularGridInterpolator takes for k = 2 -- the bits of HistogramPdfSource.pdf there too.  An
+// instantiation of its own: k_score_rows<K> of bi_score_events and the simulators is the code it was.
+template <int K, bool RGI2D = false>
 __global__ __launch_bounds__(kThreads) void k_score_rows(const int64_t* __restrict__ base_in, const double* __restrict__ t_in, int64_t N,
                                                          ScoreArgs a, const double* __restrict__ rows, int64_t row_stride, int n_rows,
                                                          double* __restrict__ out, int64_t out_stride,
@@ -985,6 +988,13 @@ __global__ __launch_bounds__(kThreads) void k_score_rows(const int64_t* __restri
                 const double* __restrict__ src = row + base[j];
                 double v = 0.0;
                 auto add_corner = [&](int corner) {
+                    if constexpr (RGI2D) {
+                        static_assert(K == 2, "scipy's own routine is the two-dimensional one");
+                        const bool up0 = (corner >> 1) & 1, up1 = corner & 1;
+                        const int64_t off = (up0 ? a.stride[0] : 0) + (up1 ? a.stride[1] : 0);
+                        v = v + (src[off] * (up0 ? t[j][0] : 1.0 - t[j][0])) * (up1 ? t[j][1] : 1.0 - t[j][1]);
+                        return;
+                    }
                     double weight = 1.0;
                     int64_t off = 0;
 #pragma unroll

@@ -33,14 +33,6 @@
 
 namespace {
 
-// ItemTiles with the item's own stride: block x of nbx takes the steps x, x + nbx, ...
-struct ListTiles : ItemTiles {
-    int nbx;
-    template <class Args>
-    __device__ __forceinline__ ListTiles(const Args& a, int n_tiles, int nbx_) : ItemTiles(a, n_tiles), nbx(nbx_) {}
-    __device__ __forceinline__ void step() { lt += nbx; }
-};
-
 // n log mu of a listed bin under poisson_term's rules: mu not >= 0 or n nan -> nan; n negative or no integer -> -inf; n = 0
 // (padding) -> +0.0 whatever mu is; mu = 0 under n > 0 -> -inf
 __device__ __forceinline__ double listed_term(double n, double mu) {

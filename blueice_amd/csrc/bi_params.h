@@ -141,6 +141,9 @@ const ParamDef kParams[] = {
     BI_P_RO("coarse_cells", c->coarse.set ? c->coarse.C : 0),
     BI_P_RO("sourcewise_nonempty_ready", c->fac.ne_ready ? 1 : 0),
     BI_P_RO("sourcewise_nonempty_bytes", c->fac.ne_ready ? c->fac.ne_bytes : 0),
+    BI_P_RO("sourcewise_events_ready", c->fac.ev_ready ? 1 : 0),
+    BI_P_RO("sourcewise_events_bytes", c->fac.ev_ready ? c->fac.ev_bytes : 0),
+    BI_P_RO("sourcewise_event_sets", c->fac.ev_ready ? c->fac.ev_T : 0),
     BI_P_RO("compact_sorted", (c->compact_ready && c->compact_sorted) ? 1 : 0),
     BI_P_RO("nnz_total", c->csr_ready ? c->h_nz_off.back() : -1),
     BI_P_RO("last_scan_nslots", c->last_scan_nslots),

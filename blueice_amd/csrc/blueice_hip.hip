@@ -107,6 +107,7 @@ void bi_destroy(bi_ctx* c) {
     dev_free(c->real_counts);
     dev_free(c->fac.ps); dev_free(c->fac.counts); dev_free(c->fac.real_counts); dev_free(c->fac.geom); dev_free(c->fac.lgsum_dev);
     dev_free(c->fac.ne_ps); dev_free(c->fac.ne_cnt); dev_free(c->fac.ne_tab);
+    dev_free(c->fac.ev_ps);
     release_coarse(c);
     release_coarse(c->sw_coarse);
     if (c->slot_host) (void)hipHostFree(c->slot_host);
@@ -1619,6 +1620,7 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_sampler.h"
 #include "bi_sourcewise_plan.h"
 #include "bi_sourcewise_nonempty.h"
+#include "bi_sourcewise_events.h"
 #include "bi_sourcewise_scan.h"
 #include "bi_grid.h"
 #include "bi_coarse.h"

@@ -1027,6 +1027,28 @@ class BinnedLogLikelihood(DeviceLogLikelihood):
         return out
 
 
+def histogram_lookup_method(sources, edges):
+    """-> 'piecewise' or 'linear' when every one of `sources` takes its pdf from a histogram over the analysis space with the
+    bin edges `edges` through HistogramPdfSource.pdf itself, all with that one interpolation method: the device can then look
+    the events up in the density histograms.  None otherwise (analytic pdfs, overridden pdf(), mixed methods)."""
+    from .source import HistogramPdfSource
+    methods = set()
+    for s in sources:
+        if not isinstance(s, HistogramPdfSource) or type(s).pdf is not HistogramPdfSource.pdf \
+                or not s.pdf_has_been_computed or s._pdf_histogram is None:
+            return None
+        he = s._pdf_histogram.bin_edges
+        if len(he) != len(edges) or any(len(a) != len(b) or np.any(a != b) for a, b in zip(he, edges)):
+            return None
+        methods.add(s.config['pdf_interpolation_method'])
+    if len(methods) != 1 or methods - {'linear', 'piecewise'}:
+        return None
+    method = methods.pop()
+    if method == 'linear' and any(len(e) < 3 for e in edges):
+        return None                      # one bin on an axis: scipy refuses such a grid, let the host say so
+    return method
+
+
 class UnbinnedLogLikelihood(DeviceLogLikelihood):
     """Extended unbinned likelihood, -sum_s mu_s + sum_events log(sum_s mu_s p_s(x_e)), on the same device
     path (reference: blueice/likelihood.py:528-573, extended_loglikelihood :678-690).  `set_data` scores the
@@ -1054,9 +1076,9 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
     # -- set_data on the device, when every source's pdf is a histogram -------------------------------------------
     def _histogram_templates(self):
         """-> (templates context, method, grid) when every source of every anchor model takes its pdf from a histogram
-        over the model's analysis space through HistogramPdfSource.pdf itself, all with the same interpolation method;
-        None otherwise (analytic pdfs, overridden pdf(), mixed methods): then the events are scored on the host."""
-        from .source import HistogramPdfSource
+        over the model's analysis space through HistogramPdfSource.pdf itself, all with the same interpolation method
+        (`histogram_lookup_method`); None otherwise (analytic pdfs, overridden pdf(), mixed methods): then the events are
+        scored on the host."""
         if self._templates is False or not self.config.get('device_scoring', True) or not hasattr(DeviceContext, 'score_events'):
             return None
         if self._templates is None:
@@ -1064,20 +1086,9 @@ class UnbinnedLogLikelihood(DeviceLogLikelihood):
             models = list(self.anchor_models.values()) if len(self.shape_parameters) else [self.base_model]
             sources = {id(s): s for m in models for s in m.sources}.values()
             edges = [np.asarray(e, dtype=float) for _, e in self.base_model.config['analysis_space']]
-            methods = set()
-            for s in sources:
-                if not isinstance(s, HistogramPdfSource) or type(s).pdf is not HistogramPdfSource.pdf \
-                        or not s.pdf_has_been_computed or s._pdf_histogram is None:
-                    return None
-                he = s._pdf_histogram.bin_edges
-                if len(he) != len(edges) or any(len(a) != len(b) or np.any(a != b) for a, b in zip(he, edges)):
-                    return None
-                methods.add(s.config['pdf_interpolation_method'])
-            if len(methods) != 1 or methods - {'linear', 'piecewise'}:
+            method = histogram_lookup_method(sources, edges)
+            if method is None:
                 return None
-            method = methods.pop()
-            if method == 'linear' and any(len(e) < 3 for e in edges):
-                return None                      # one bin on an axis: scipy refuses such a grid, let the host say so
             tp = DeviceContext(self.config.get('device'))
             S = len(self.source_name_list)
             n_bins = int(np.prod([len(e) - 1 for e in edges], dtype=np.int64))

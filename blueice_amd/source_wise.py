@@ -1,4 +1,6 @@
-"""Source-wise binned likelihoods on the device: one anchor grid per source.
+"""Source-wise likelihoods on the device: one anchor grid per source.  This module: binned data, the context both kinds share
+(`SourceWiseContext`) and their common base; unbinned data -- the event store of the same model -- is
+`source_wise_unbinned.SourceWiseUnbinnedLogLikelihood`.
 
     lf = SourceWiseBinnedLogLikelihood(pdf_base_config, likelihood_config=None, **overrides)
     lf.add_rate_parameter(...); lf.add_shape_parameter(...); lf.prepare(); lf.set_data(d)
@@ -81,7 +83,10 @@ bit for bit).  Hessians, Fisher information, goodness of fit, the expectation, c
 the dense store.
 
 Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a source that responds to more belongs on the
-full grid).  Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
+full grid).  Unbinned data: `SourceWiseContext.score_events` / `set_event_rows` put an event store beside the counts
+(bi_sourcewise_score_events, bi_sourcewise_events_begin ...); while it exists `eval`, `eval_grad` and `fit_batched` are the extended
+unbinned likelihood over its event sets and every other call of the context is refused by the library; `drop_events` releases it.
+Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
 full_output calls, eval_toys*, Hessians, sampling and gridded likelihoods on an Asimov view, and the bound lf.grid_scan (the
 function is the spelling that works, above).
 """
@@ -129,6 +134,7 @@ class SourceWiseContext:
         self.T = 0
         self._counts = None
         self._coarse_key = None
+        self._binned = None                     # (T, host copy) of the counts while an event store stands in front of them
 
     def set_param(self, name, value):
         """a parameter of the underlying context (`toy_offset`: the number of a generator call's first toy in the seed's ensemble)"""
@@ -162,6 +168,7 @@ class SourceWiseContext:
         self.mus = [np.zeros(tuple(len(anchor_z[i]) for i in own)) for own in own_axes]      # host copy of the rates
         self.T = 0
         self._counts = None
+        self._binned = None
 
     def set_anchor(self, s, local_index, ps_row, mu):
         dev = self._dev
@@ -223,6 +230,71 @@ class SourceWiseContext:
     def drop_nonempty(self):
         """Release the non-empty-bin form: the calls above read the dense store again."""
         self._dev._check(self._dev._lib.bi_sourcewise_drop_nonempty(self._dev._h))
+
+    # -- the event store: unbinned data (bi_sourcewise_score_events, bi_sourcewise_events_begin ...) ------
+    def score_events(self, method, grid, coords, outlier_likelihood=0.0):
+        """Make T event sets the context's data, scored ON THE DEVICE: the model's rows are density histograms over the analysis
+        space, looked up with `method` -- 'piecewise' (grid = the bin edges) or 'linear' (grid = the bin centres; the
+        coordinates arrive clipped).  coords: a list of T sets, each a list of k coordinate arrays.  While the store exists
+        eval, eval_grad and fit_batched are the extended unbinned likelihood (`dataset` indexes the sets) and every other call
+        of this class is refused by the library."""
+        dev = self._dev
+        grid, n_grid, flat = dev._grid_args(grid)
+        k = len(grid)
+        sets = [[as_f64(c).ravel() for c in cs] for cs in coords]
+        if not sets or any(len(cs) != k or any(len(c) != len(cs[0]) for c in cs) for cs in sets):
+            raise ValueError("coords must be a list of event sets, each with one coordinate array per analysis dimension")
+        offsets = np.concatenate([[0], np.cumsum([len(cs[0]) for cs in sets])]).astype(np.int64)
+        block = np.ascontiguousarray(np.stack([np.concatenate([cs[i] for cs in sets]) for i in range(k)]))
+        dev._check(dev._lib.bi_sourcewise_score_events(dev._h, {'piecewise': 0, 'linear': 1}[method], k, ptr(n_grid), ptr(flat), len(sets),
+                                                       ptr(offsets), ptr(block), float(outlier_likelihood)))
+        self._enter_events(len(sets))
+
+    def set_event_rows(self, n_events, rows, outlier_likelihood=0.0):
+        """Make T event sets of n_events [T] events the context's data from pdf values scored on the host: rows(s, local_index)
+        -> values [sum(n_events)], set after set, finite or nan, called once per anchor row of every source (C order over
+        the source's own axes).  The model's own rows are not read."""
+        dev = self._dev
+        n_events = np.ascontiguousarray(np.atleast_1d(n_events), dtype=np.int64)
+        total = int(n_events.sum())
+        dev._check(dev._lib.bi_sourcewise_events_begin(dev._h, len(n_events), ptr(n_events), float(outlier_likelihood)))
+        try:
+            for s, mus in enumerate(self.mus):
+                for local in range(mus.size):
+                    v = np.ascontiguousarray(as_f64(rows(s, local)).reshape(total))
+                    dev._check(dev._lib.bi_sourcewise_events_set_row(dev._h, s, local, ptr(v) if total else None))
+            dev._check(dev._lib.bi_sourcewise_events_end(dev._h))
+        except Exception:
+            self.drop_events()
+            raise
+        self._enter_events(len(n_events))
+
+    def _enter_events(self, T):
+        if self._binned is None:                # (the counts stay resident beside the store, unread)
+            self._binned = (self.T, self._counts)
+        self._counts = None
+        self.T = T
+
+    def drop_events(self):
+        """Release the event store: the context is a binned source-wise model again, with the counts it held before (if any)."""
+        self._dev._check(self._dev._lib.bi_sourcewise_drop_events(self._dev._h))
+        if self._binned is not None:
+            self.T, self._counts = self._binned
+            self._binned = None
+
+    def event_set_counts(self):
+        """events of every set of the store: [T]"""
+        T = int(self.get_param('sourcewise_event_sets'))
+        out = np.zeros(max(T, 1), dtype=np.int64)
+        self._dev._check(self._dev._lib.bi_sourcewise_event_set_counts(self._dev._h, ptr(out)))
+        return out[:T]
+
+    def download_event_set(self, t=0):
+        """the stored pdf values of set t: [rows, N_t] (for tests)"""
+        n = int(self.event_set_counts()[int(t)])
+        out = np.empty((sum(m.size for m in self.mus), n), dtype=np.float64)
+        self._dev._check(self._dev._lib.bi_sourcewise_download_event_set(self._dev._h, int(t), ptr(out) if n else None))
+        return out
 
     # -- evaluation ------------------------------------------------------------------------
     def _point_args(self, z, rate_scale, dataset):
@@ -575,31 +647,17 @@ def _refused(name):
     return method
 
 
-class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
-    """Binned Poisson likelihood whose sources each morph over their own shape parameters (see the module's docstring)."""
-
-    _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'expected_counts',
-                'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
-                'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
-                'expected_upper_limit',
-                'fisher_information', 'hesse', 'sample_posterior', 'bestfit_emcee',
-                'grid_scan', 'asimov', 'real_data', 'simulate_toys', 'eval_toys', 'eval_toys_points',
-                'ps_interpolator', 'n_model_events_interpolator')
+class _SourceWiseLikelihood(DeviceLogLikelihood):
+    """What the binned and the unbinned source-wise likelihood share: the context, the models at the projected anchors and the
+    upload of one row per own anchor of every source, and the single-point call."""
 
     supports_gradient = True
-    toys_through_points = True      # inference draws its toys with simulate_toys_points (the bound simulate_toys stays refused)
-
-    @property
-    def supports_hessian(self):
-        """True once data are set: the analytic Hessian of bi_eval_sourcewise_hess (`hessian_method` is 'analytic')"""
-        return self.ctx is not None and bool(self.is_data_set)
 
     def __init__(self, pdf_base_config, likelihood_config=None, **kwargs):
         super().__init__(pdf_base_config, likelihood_config, **kwargs)
         self.source_wise_interpolation = True
         if self.config.get('model_statistical_uncertainty_handling') is not None:
             raise NotImplementedError("Beeston-Barlow (model_statistical_uncertainty_handling) is not available for a source-wise model")
-        self._binned = None
 
     def _context(self):
         if self.ctx is None:
@@ -612,10 +670,9 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
             return nullcontext()
         return device_histograms(self._context(), self.config.get('device_histograms_min_events', 32768))
 
-    # -- lifecycle -------------------------------------------------------------------------
-    def prepare(self, n_cores=1, ipp_client=None):
-        """Models at the anchors some source needs only (one per distinct projection of a source's own anchors), then every
-        source's rows streamed to the device from there.  The product grid of all shape parameters is never enumerated."""
+    def _build_projected_anchors(self, n_cores):
+        """The limits, then models at the anchors some source needs only (one per distinct projection of a source's own anchors:
+        `_build_source_anchors`).  The product grid of all shape parameters is never enumerated."""
         names = list(self.shape_parameters)
         own_params = self.source_shape_parameters
         if any(self.source_allowed_negative):
@@ -626,29 +683,85 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         for name, own in own_params.items():
             if len(own) > MAX_OWN_PARAMETERS:
                 raise ValueError("source %s responds to %d shape parameters (%s); a source-wise model takes at most %d per source: a source "
-                                 "that responds to more belongs on the full grid (BinnedLogLikelihood)"
-                                 % (name, len(own), ', '.join(own), MAX_OWN_PARAMETERS))
+                                 "that responds to more belongs on the full grid (%s)"
+                                 % (name, len(own), ', '.join(own), MAX_OWN_PARAMETERS, self._full_grid_class))
         self.anchor_models = OrderedDict()
         self.morpher = None
         self.anchor_sources = OrderedDict()
         if own_params:
             self._build_source_anchors(self._anchor_model_builder(n_cores))
-        self.ps, self.n_model_events = self.base_model.pmf_grids()
-        self.bin_shape = self.ps.shape[1:]
-        n_bins = int(np.prod(self.bin_shape, dtype=np.int64))
+
+    def _own_sources(self, s):
+        """the Source objects of source s at its own anchors, in the order of its rows on the device (the source's own morpher
+        lists its anchors in C order over its own parameters, each ascending)"""
+        name = self.source_name_list[s]
+        if name in self.anchor_sources:
+            return list(self.anchor_sources[name].values())
+        return [self.base_model.sources[s]]
+
+    def _upload_source_rows(self, n_bins, row_of):
+        """begin_model ... end_model: row_of(source) -> the [n_bins] row of a Source at one of its own anchors"""
+        names = list(self.shape_parameters)
+        own_params = self.source_shape_parameters
         anchor_z = [np.array(sorted(anchors.keys()), dtype=float) for anchors, _, _ in self.shape_parameters.values()]
         own_axes = [tuple(names.index(k) for k in own_params.get(name, ())) for name in self.source_name_list]
         ctx = self._context()
         ctx.begin_model(anchor_z, len(self.source_name_list), n_bins, own_axes)
-        for s, name in enumerate(self.source_name_list):
-            if name in own_params:
-                # (the source's own morpher lists its anchors in C order over its own parameters, each ascending)
-                for local, source in enumerate(self.anchor_sources[name].values()):
-                    ctx.set_anchor(s, local, source.get_pmf_grid()[0], source.expected_events)
-            else:
-                source = self.base_model.sources[s]
-                ctx.set_anchor(s, 0, source.get_pmf_grid()[0], source.expected_events)
+        for s in range(len(self.source_name_list)):
+            for local, source in enumerate(self._own_sources(s)):
+                ctx.set_anchor(s, local, row_of(source), source.expected_events)
         ctx.end_model()
+
+    @_needs_data
+    def __call__(self, livetime_days=None, compute_pdf=False, full_output=False, **kwargs):
+        if compute_pdf or full_output:
+            raise NotImplementedError("a source-wise model (%s) evaluates the morphed model only: no "
+                                      "compute_pdf=True / full_output=True" % type(self).__name__)
+        prior, zs, scale = self._host_terms(livetime_days, kwargs)
+        if prior is None:
+            return -float('inf')
+        ll, st = self.ctx.eval(zs if len(zs) else None, scale[None, :])
+        return self._finish_call(prior, zs, scale, float(ll[0]), int(st[0]))
+
+    def _call_begin(self, livetime_days=None, **kwargs):
+        return self(livetime_days=livetime_days, **kwargs)
+
+    def _call_end(self, token):
+        return token
+
+
+class SourceWiseBinnedLogLikelihood(_SourceWiseLikelihood):
+    """Binned Poisson likelihood whose sources each morph over their own shape parameters (see the module's docstring)."""
+
+    _full_grid_class = 'BinnedLogLikelihood'
+
+    _REFUSED = ('best_anchor', 'bestfit_toys', 'toy_mc_fits', 'expected_counts',
+                'expected_counts_points', 'gof_statistics', 'goodness_of_fit', 'expected_coarse', 'expected_coarse_points', 'coarse_counts',
+                'expected_coarse_jacobian', 'expected_coarse_jacobian_points', 'expected_coarse_band', 'coarse_information',
+                'expected_upper_limit',
+                'fisher_information', 'hesse', 'sample_posterior', 'bestfit_emcee',
+                'grid_scan', 'asimov', 'real_data', 'simulate_toys', 'eval_toys', 'eval_toys_points',
+                'ps_interpolator', 'n_model_events_interpolator')
+
+    toys_through_points = True      # inference draws its toys with simulate_toys_points (the bound simulate_toys stays refused)
+
+    @property
+    def supports_hessian(self):
+        """True once data are set: the analytic Hessian of bi_eval_sourcewise_hess (`hessian_method` is 'analytic')"""
+        return self.ctx is not None and bool(self.is_data_set)
+
+    def __init__(self, pdf_base_config, likelihood_config=None, **kwargs):
+        super().__init__(pdf_base_config, likelihood_config, **kwargs)
+        self._binned = None
+
+    # -- lifecycle -------------------------------------------------------------------------
+    def prepare(self, n_cores=1, ipp_client=None):
+        """Models at the anchors some source needs only (one per distinct projection of a source's own anchors), then every
+        source's rows streamed to the device from there.  The product grid of all shape parameters is never enumerated."""
+        self._build_projected_anchors(n_cores)
+        self.ps, self.n_model_events = self.base_model.pmf_grids()
+        self.bin_shape = self.ps.shape[1:]
+        self._upload_source_rows(int(np.prod(self.bin_shape, dtype=np.int64)), lambda source: source.get_pmf_grid()[0])
         self._binned = None
         self.is_data_set = False
         self.is_prepared = True
@@ -753,23 +866,6 @@ class SourceWiseBinnedLogLikelihood(DeviceLogLikelihood):
         out = ll + prior
         out[(st & (_capi.ST_OUT_OF_BOUNDS | _capi.ST_UNPHYSICAL)) != 0] = -np.inf
         return out
-
-    @_needs_data
-    def __call__(self, livetime_days=None, compute_pdf=False, full_output=False, **kwargs):
-        if compute_pdf or full_output:
-            raise NotImplementedError("a source-wise model (SourceWiseBinnedLogLikelihood) evaluates the morphed model only: no "
-                                      "compute_pdf=True / full_output=True")
-        prior, zs, scale = self._host_terms(livetime_days, kwargs)
-        if prior is None:
-            return -float('inf')
-        ll, st = self.ctx.eval(zs if len(zs) else None, scale[None, :])
-        return self._finish_call(prior, zs, scale, float(ll[0]), int(st[0]))
-
-    def _call_begin(self, livetime_days=None, **kwargs):
-        return self(livetime_days=livetime_days, **kwargs)
-
-    def _call_end(self, token):
-        return token
 
 
 for _name in SourceWiseBinnedLogLikelihood._REFUSED:

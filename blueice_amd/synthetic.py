@@ -13,9 +13,10 @@ import itertools
 
 import numpy as np
 
-from .source import Source
+from .histdd import Histdd
+from .source import HistogramPdfSource, Source
 
-__all__ = ['SyntheticModel', 'CONFIGS', 'TemplateSource', 'NuisanceBlobSource', 'many_nuisances_config']
+__all__ = ['SyntheticModel', 'CONFIGS', 'TemplateSource', 'NuisanceBlobSource', 'NuisanceHistogramSource', 'many_nuisances_config']
 
 _MU_SLOPES = (0.02, -0.01, 0.005, 0.0025, -0.00125, 0.0006, 0.0003, 0.0001)
 
@@ -273,33 +274,49 @@ SyntheticModel.likelihood = _likelihood
 
 # -- a model with many nuisance parameters, each moving one source (source_wise.SourceWiseBinnedLogLikelihood) ---------
 
+def _blob_own(config):
+    """the values of the blob's own settings (one or two of them), padded with zeros"""
+    return [float(config[name]) for name in config['own_settings']] + [0.0, 0.0]
+
+
+def blob_moments(config):
+    """-> ((mean x, mean y), (sigma x, sigma y)) of the Gaussian blob a source's config describes"""
+    z = _blob_own(config)
+    cx, cy = config['centre']
+    return (cx + 0.04 * z[0], cy + 0.03 * z[1]), (config['width'] * (1 + 0.08 * z[1]), config['width'] * (1 - 0.05 * z[0]))
+
+
+def blob_rate(config):
+    """events per day of the blob at its own settings (from the config's value: not cumulative)"""
+    z = _blob_own(config)
+    return config['events_per_day'] * (1 + 0.03 * z[0] - 0.02 * z[1])
+
+
+def blob_pmf(config):
+    """the blob integrated over every bin of the config's two-dimensional analysis space"""
+    from scipy.stats import norm
+    (mx, my), (sx, sy) = blob_moments(config)
+    (_, ex), (_, ey) = config['analysis_space']
+    px = np.diff(norm(mx, sx).cdf(np.asarray(ex, dtype=float)))
+    py = np.diff(norm(my, sy).cdf(np.asarray(ey, dtype=float)))
+    return np.outer(px, py)
+
+
 class NuisanceBlobSource(Source):
     """A Gaussian blob in a two-dimensional analysis space (x, y) whose position, width and rate respond to the settings
     named in config['own_settings'] (one or two of them) and to nothing else: the closed-form stand-in for a source with
     its own nuisance parameters.  The PMF is the blob integrated over every bin."""
 
-    def _moments(self):
-        c = self.config
-        z = [float(c[name]) for name in c['own_settings']] + [0.0, 0.0]
-        cx, cy = c['centre']
-        return (cx + 0.04 * z[0], cy + 0.03 * z[1]), (c['width'] * (1 + 0.08 * z[1]), c['width'] * (1 - 0.05 * z[0]))
-
     def compute_pdf(self):
-        z = [float(self.config[name]) for name in self.config['own_settings']] + [0.0, 0.0]
-        self.events_per_day = self.config['events_per_day'] * (1 + 0.03 * z[0] - 0.02 * z[1])      # (from the config's value: not cumulative)
+        self.events_per_day = blob_rate(self.config)
         super().compute_pdf()
 
     def get_pmf_grid(self):
-        from scipy.stats import norm
-        (mx, my), (sx, sy) = self._moments()
-        (_, ex), (_, ey) = self.config['analysis_space']
-        px = np.diff(norm(mx, sx).cdf(np.asarray(ex, dtype=float)))
-        py = np.diff(norm(my, sy).cdf(np.asarray(ey, dtype=float)))
-        pmf = np.outer(px, py)
+        pmf = blob_pmf(self.config)
         return pmf, np.full(pmf.shape, np.inf)
 
     def simulate(self, n_events):
-        (mx, my), (sx, sy) = self._moments()
+        (mx, my), (sx, sy) = blob_moments(self.config)
         (nx, _), (ny, _) = self.config['analysis_space']
         d = np.zeros(int(n_events), dtype=[('source', int), (nx, float), (ny, float)])
         d[nx] = np.random.normal(mx, sx, int(n_events))
@@ -307,14 +324,36 @@ class NuisanceBlobSource(Source):
         return d
 
 
-def many_nuisances_config(n_bins=(20, 20), n_params=8, n_sources=4, own_per_source=2, events_per_day=400.):
-    """-> (model config, shape-parameter names, per source the names it responds to): `n_sources` NuisanceBlobSources in the
+class NuisanceHistogramSource(HistogramPdfSource):
+    """NuisanceBlobSource's blob as a HistogramPdfSource: its density histogram is the blob integrated over every bin, divided by
+    the bin's volume -- no Monte Carlo, so two builds at one anchor agree bit for bit.  pdf() is HistogramPdfSource's lookup
+    (config['pdf_interpolation_method']: 'linear' or 'piecewise'), simulate() draws from the histogram."""
+
+    def compute_pdf(self):
+        self.events_per_day = blob_rate(self.config)
+        super().compute_pdf()
+
+    def build_histogram(self):
+        names, edges = zip(*self.config['analysis_space'])
+        pmf = blob_pmf(self.config)
+        blank = Histdd(bins=edges, axis_names=names)
+        self._bin_volumes = blank.bin_volumes()
+        self._pdf_histogram = blank.similar_blank_hist()
+        self._pdf_histogram.histogram = pmf / self._bin_volumes
+        self._n_events_histogram = blank.similar_blank_hist()
+        self._n_events_histogram.histogram = np.full(pmf.shape, np.inf)
+        self.fraction_in_range = float(pmf.sum())
+
+
+def many_nuisances_config(n_bins=(20, 20), n_params=8, n_sources=4, own_per_source=2, events_per_day=400., source_class=None):
+    """-> (model config, shape-parameter names, per source the names it responds to): `n_sources` NuisanceBlobSources (or
+    `source_class`) in the
     unit square, source s responding to the `own_per_source` settings np(s * own_per_source) ... only (every other one is
     listed in its dont_hash_settings).  Every setting's base value is 0."""
     names = ['np%d' % i for i in range(n_params)]
     own = [tuple(names[(s * own_per_source + j) % n_params] for j in range(own_per_source)) for s in range(n_sources)]
     conf = dict(analysis_space=[('x', np.linspace(0., 1., n_bins[0] + 1)), ('y', np.linspace(0., 1., n_bins[1] + 1))],
-                default_source_class=NuisanceBlobSource, livetime_days=1., sources=[], **{n: 0. for n in names})
+                default_source_class=source_class or NuisanceBlobSource, livetime_days=1., sources=[], **{n: 0. for n in names})
     for s in range(n_sources):
         conf['sources'].append(dict(name='s%d' % s, events_per_day=events_per_day * (1 + 0.5 * s), own_settings=list(own[s]),
                                     centre=(0.3 + 0.4 * (s % 2), 0.3 + 0.4 * ((s // 2) % 2)), width=0.12 + 0.02 * s,

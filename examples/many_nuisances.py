@@ -74,6 +74,14 @@ same quantile of a chain over the same four parameters (blueice_amd.sampler.samp
 --measure-grid times, at the measured source-wise shape with Poisson data of 10^4 events, bi_grid_reduce_sourcewise on its two routes
 against the host engine on a grid of about 10^6 points, bi_eval_sourcewise_scan against bi_eval_factored values-only at 4096 and 10^6
 points of one cell tuple, and the planner's share of a call by device events; the lines go to profiles/sourcewise_scan_measure.txt too.
+
+--unbinned fits, instead of (2) - (6), the same twelve parameters over the EVENTS (SourceWiseUnbinnedLogLikelihood: the event store of
+bi_sourcewise_score_events, k_sourcewise_events) with the sources' pdfs taken from histograms, and runs one profile scan of the
+signal's multiplier.  The full-grid unbinned route would hold 5^8 anchors x 4 sources x N values.
+
+--measure-unbinned times, at the measured source-wise shape with 10^4 and 10^6 events, bi_eval_factored on the event store against
+bi_eval_grad / bi_eval on the same model expanded to the 5^4 unbinned grid model, and bi_sourcewise_score_events against
+bi_score_events on the expanded templates; the lines go to profiles/sourcewise_events_measure.txt too.
 """
 import argparse
 import time
@@ -98,6 +106,9 @@ ap.add_argument('--grid', action='store_true',
                 help='a credible upper limit on the signal multiplier from a gridded likelihood, marginalised over three nuisances, beside the chain\'s')
 ap.add_argument('--measure-grid', action='store_true',
                 help='time bi_grid_reduce_sourcewise on its two routes against the host engine, and bi_eval_sourcewise_scan against bi_eval_factored')
+ap.add_argument('--unbinned', action='store_true', help='fit the twelve parameters over events (unbinned source-wise likelihood) and scan the signal multiplier')
+ap.add_argument('--measure-unbinned', action='store_true',
+                help='time bi_eval_factored on the event store against the expanded unbinned grid model, and the two scoring calls')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -1027,6 +1038,150 @@ def grid_limit():
           % (np.quantile(s0, 0.9), 100 * inside))
 
 
+def unbinned():
+    """Eight nuisances of five anchors and four rate multipliers fitted over events, and one profile scan of the signal's multiplier"""
+    from blueice_amd import GaussianPrior, SourceWiseUnbinnedLogLikelihood
+    from blueice_amd.synthetic import NuisanceHistogramSource, many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins), source_class=NuisanceHistogramSource)
+    lf = SourceWiseUnbinnedLogLikelihood(conf)
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    t0 = time.perf_counter()
+    lf.prepare()
+    rows = sum(5 ** len(o) for o in own)
+    print('(1) prepare(): %d shape parameters x 5 anchors, 4 histogram sources responding to %s: %d density histograms on the device, %.2f s'
+          % (len(names), ', '.join('/'.join(o) for o in own), rows, time.perf_counter() - t0))
+    np.random.seed(3)
+    data = lf.base_model.simulate()
+    t0 = time.perf_counter()
+    lf.set_data(data)
+    print('    set_data(): %d events scored on the %s at %d rows: an event store of %.2f MB (the full grid would hold 5^%d x 4 rows: %.1e MB)'
+          % (len(data), lf.last_scoring_route, rows, lf.ctx.get_param('sourcewise_events_bytes') / 1e6, len(names),
+             5.0 ** len(names) * 4 * len(data) * 8 / 1e6))
+    t0 = time.perf_counter()
+    best, ll, info = lf.bestfit_batched(return_info=True)
+    print('(2) bestfit_batched over events, %d parameters floating: max ll %.4f, converged %s, %d evaluations in %d device calls, %.3f s'
+          % (len(best), ll[0], bool(info['converged'][0]), info['evaluations'], info['calls'], time.perf_counter() - t0))
+    print('    ' + ', '.join('%s %.3f' % (k.replace('_rate_multiplier', ''), v[0]) for k, v in best.items()))
+    grid = np.linspace(0.7, 1.3, args.scan)
+    t0 = time.perf_counter()
+    scan = lf.likelihood_ratio_scan(('s0_rate_multiplier', grid))
+    dt = time.perf_counter() - t0
+    inside = grid[2 * scan <= 1.0]
+    print('(3) likelihood_ratio_scan over s0_rate_multiplier: %d hypotheses, 11 nuisances profiled at each, %.3f s; minimum at %.3f, '
+          '2 dlnL <= 1 on [%.3f, %.3f]' % (args.scan, dt, grid[np.argmin(scan)], inside.min(), inside.max()))
+    lf.ctx.close()
+
+
+def measure_unbinned():
+    """bi_eval_factored on the event store against the parent's route -- the same model expanded to the 5^4 unbinned grid model in a
+    second context, which reads 64 rows per point where this one reads 8 -- at 10^4 and 10^6 events, 64 points and one point per
+    call, with and without the gradient; and bi_sourcewise_score_events against bi_score_events on the expanded templates.
+    Alternated calls, medians with quartiles, device events for the kernels alone.  Written to
+    profiles/sourcewise_events_measure.txt as well."""
+    import os
+    from blueice_amd.device import DeviceContext
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, nb = 5, args.measure_bins
+    B = nb ** 3
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05                                         # densities over the unit cube
+    rows *= B / rows.sum(axis=-1, keepdims=True)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    fac = SourceWiseContext(0)
+    say('# examples/many_nuisances.py --measure-unbinned --measure-bins %d --rounds %d on %s' % (nb, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>), %d anchors, density histograms of %d^3 bins, \'linear\' lookup' % (d, S, n_a, nb))
+    edges = [np.linspace(0., 1., nb + 1)] * 3
+    centres = [0.5 * (e[:-1] + e[1:]) for e in edges]
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])                   # relative rates (10 in all); the scale is per dataset
+    tp = DeviceContext(0)
+    t0 = time.perf_counter()
+    tp.begin_model([g] * d, S, B)
+    for lin, idx in enumerate(np.ndindex(*(n_a,) * d)):          # the same likelihood on the product grid: source s from ITS anchor
+        tp.set_anchor(lin, np.stack([rows[s, idx[s]] for s in range(S)]), np.array([mus[s, idx[s]] for s in range(S)]))
+    tp.end_model()
+    say('expanded templates resident: %d anchor models, %.1f GB, %.1f s to stream; source-wise: %d rows, %.2f GB'
+        % (n_a ** d, n_a ** d * S * B * 8 / 1e9, time.perf_counter() - t0, S * n_a, S * n_a * B * 8 / 1e9))
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    for events in (1e4, 1e6):
+        N = int(events)
+        coords = [np.clip(rng.random(N), c[0], c[-1]) for c in centres]
+        full = DeviceContext(0)
+        t_sw, t_full = [], []
+        for rnd in range(1 + args.rounds):                        # one warm-up round; the two calls alternate
+            t0 = time.perf_counter()
+            fac.score_events('linear', centres, [coords], 1e-12)
+            t1 = time.perf_counter()
+            tp.score_events(full, 'linear', centres, coords, 1e-12)
+            t2 = time.perf_counter()
+            if rnd:
+                t_sw.append(t1 - t0)
+                t_full.append(t2 - t1)
+        say('%.0e events: bi_sourcewise_score_events (%d rows, store %.1f MB) %s   bi_score_events on the expanded templates (%d rows, %.1f MB) %s   ratio %.1f'
+            % (events, S * n_a, fac.get_param('sourcewise_events_bytes') / 1e6, quartiles(t_sw), n_a ** d * S, n_a ** d * S * N * 8 / 1e6,
+               quartiles(t_full), np.median(t_full) / np.median(t_sw)))
+        for P in (64, 1):
+            z, r = rng.uniform(-1.9, 1.9, (P, d)), events / 10.0 * rng.uniform(0.8, 1.2, (P, S))
+            a, b = fac.eval_grad(z, r), full.eval_grad(z, r)
+            rel = np.max(np.abs(a[0] - b[0]) / np.abs(b[0]))
+            calls = [('store, gradient', lambda: fac.eval_grad(z, r)), ('grid, gradient', lambda: full.eval_grad(z, r)),
+                     ('store, values', lambda: fac.eval(z, r)), ('grid, values', lambda: full.eval(z, r))]
+            times = {name: [] for name, _ in calls}
+            for rnd in range(3 + args.rounds):          # three warm-up rounds; the calls alternate inside every round
+                for name, call in calls:
+                    t0 = time.perf_counter()
+                    call()
+                    if rnd >= 3:
+                        times[name].append(time.perf_counter() - t0)
+            for what, base in (('gradient', 'bi_eval_grad'), ('values', 'bi_eval')):
+                st, gt = times['store, ' + what], times['grid, ' + what]
+                say('%.0e events, %2d points per call, %-8s bi_eval_factored on the event store %s   %s on the 5^%d unbinned grid model %s   ratio %.2f   '
+                    '(max |ll difference| / |ll| %.1e)' % (events, P, what, quartiles(st), base, d, quartiles(gt), np.median(gt) / np.median(st), rel))
+            if P == 64:
+                cols = max(512, (N + 511) // 512 * 512)
+                for name, ctx, call, n_rows in (('k_sourcewise_events + k_finish', fac._dev, calls[0][1], 2 * S),
+                                                ('the grid route\'s kernels', full, calls[1][1], S * 2 ** d)):
+                    ctx.profile(True)
+                    ks = []
+                    for _ in range(args.rounds):
+                        call()
+                        ks.append(ctx.profile_read()[1] * 1e-3)
+                    ctx.profile(False)
+                    med = np.median(ks)
+                    say('%.0e events, 64 points, with gradient, kernels alone (%s): %s; %d rows x %d columns x 8 bytes x 64 points = %.3f GB -> %.2f TB/s'
+                        % (events, name, quartiles(ks), n_rows, cols, n_rows * cols * 8 * 64 / 1e9, n_rows * cols * 8 * 64 / med / 1e12))
+        full.close()
+    say('# cache-assisted: every figure at 1e4 events (the event store is %.1f MB, inside an L2; the grid model\'s tensor is %.0f MB, inside the '
+        '256 MiB Infinity Cache; the 64 points of a call read the same rows again).  At 1e6 events the store is %.0f MB -- still inside the '
+        'Infinity Cache -- and the grid model\'s tensor %.0f GB, which is not' % (S * n_a * 10240 * 8 / 1e6, n_a ** d * S * 1e4 * 8 / 1e6,
+                                                                                 S * n_a * 1e6 * 8 / 1e6, n_a ** d * S * 1e6 * 8 / 1e9))
+    say('# not measured: every class but <4, 1>, T > 1 event sets, the fit loop\'s wall time, \'piecewise\' scoring, other shapes')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_events_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+    tp.close()
+
+
+if args.unbinned:
+    unbinned()
+    raise SystemExit(0)
+if args.measure_unbinned:
+    measure_unbinned()
+    raise SystemExit(0)
 if args.grid:
     grid_limit()
     raise SystemExit(0)

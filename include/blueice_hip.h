@@ -537,7 +537,9 @@ int bi_fit_batched_real(bi_ctx* ctx, int64_t P, int F, const int32_t* var_kind, 
  *
  * Limits: d <= 32, S <= 8, e_s <= 3 (a source that responds to more axes belongs on the grid model).  Out of scope, and
  * refused where they can be asked for: sources that may go negative (template entries must be finite and >= 0),
- * Beeston-Barlow, unbinned data.  The store's counts are dense doubles, [T][B]: the caller's (bi_factored_set_counts) or toys
+ * Beeston-Barlow.  Unbinned data: the event store of bi_sourcewise_score_events / bi_sourcewise_events_begin below, a second form
+ * of the data with which bi_eval_factored and bi_fit_batched_factored are the extended unbinned likelihood.  The store's counts
+ * are dense doubles, [T][B]: the caller's (bi_factored_set_counts) or toys
  * drawn on the device at truth points of this model (bi_sourcewise_generate_toys below, with the expectation per bin and the
  * goodness-of-fit sums).
  *
@@ -836,6 +838,54 @@ int bi_sample_stretch_sourcewise(bi_ctx* ctx, int64_t E, int W, int F, const int
  * code it ran without it. */
 int bi_sourcewise_build_nonempty(bi_ctx* ctx, int64_t* nnz /*[T] or NULL*/);
 int bi_sourcewise_drop_nonempty(bi_ctx* ctx);
+
+/* ... and UNBINNED data: the event store of a source-wise model (the reference's source_wise_interpolation for unbinned
+ * likelihoods).  Per anchor row of the model the store holds the pdf value of every event, [rows][columns] with
+ * rows = sum_s prod_{i in O_s} n_i, and T event sets side by side in the layout of bi_score_event_sets: set t at the columns
+ * [first_t, first_t + N_t), every first_t even, every set padded to whole tiles of tile_bins behind its events and to at least
+ * one tile; N_t = 0 is allowed.  Events keep the caller's order.  With it
+ *     tau_s,e = sum_c w_c p_s,c,e, ups_s,j,e = sum_c d_j w_c p_s,c,e      the fma chains of the binned route, per event
+ *     lam_e   = sum_s r_s tau_s,e      one fma per source from 0.0; a source whose tau_s,e is nan is left out of lam_e and of its
+ *                                      own sums for that event (numpy.nansum)
+ *     clamped = outlier != 0 and not (lam_e > 0):  lam_e := outlier, g_e := 0;   otherwise g_e = 1 / lam_e
+ *     ll      = sum_e log lam_e - sum_s r_s
+ *     d ll / d rs_s = M_s (sum_e g tau_s - 1)
+ *     d ll / d z_i  = sum_{s: i in O_s} rs_s [M_s sum_e g ups_s,i + d_i M_s (sum_e g tau_s - 1)]
+ * With outlier = 0 an event with lam_e = 0 gives ll = -inf; the gradient is nan wherever ll is not finite.  Columns behind N_t
+ * are masked by index.  A point's bits do not depend on its batch or on the other sets of the call (an item's blocks follow from
+ * its own set's length), a values-only call gives the bits of the call with the gradient, repeated calls agree bit for bit, and
+ * a store scored on the device and the same values uploaded row by row give the same bits.
+ *   bi_sourcewise_events_begin     T sets of n_events [T] events, pdf values scored on the host.  Needs a finished source-wise
+ *   bi_sourcewise_events_set_row   model for its geometry and rates; the model's own rows are not read.  Row `local_index` of
+ *   bi_sourcewise_events_end       source s: values [sum_t N_t], set after set; finite or nan (+-inf: BI_ERR_INVALID); each row
+ *                                  exactly once (a second upload: BI_ERR_INVALID; _end names the first missing row, BI_ERR_STATE)
+ *   bi_sourcewise_score_events     the model's rows are density histograms over the analysis space (B = histogram bins) and the
+ *                                  store is filled on the device with bi_score_events' two methods and contract: 0 'piecewise'
+ *                                  takes edges, 1 'linear' bin centres, coords [k][N] (N = offsets[T]) arrive clipped and
+ *                                  finite.  Every stored value has the bits bi_score_events gives for that row, and those of
+ *                                  HistogramPdfSource.pdf on the host -- except that for 'linear' with k = 2, where scipy's
+ *                                  RegularGridInterpolator associates the products in a routine of its own, the store follows
+ *                                  scipy (bi_score_events differs from it by a rounding there).  BI_ERR_INVALID when the grid
+ *                                  does not describe B bins
+ *   bi_sourcewise_drop_events      releases the store; so does bi_factored_begin
+ *   bi_sourcewise_event_set_counts counts [T] = N_t
+ *   bi_sourcewise_download_event_set   (for tests) out [rows][N_t]: the stored values of set t
+ * The store's bytes are bounded by compact_budget: beyond it the call fails with BI_ERR_INVALID naming the bytes and nothing is
+ * built.  Read-only parameters sourcewise_events_ready, sourcewise_events_bytes, sourcewise_event_sets.
+ * While a store exists (from _events_begin on) the context is an unbinned source-wise likelihood: bi_eval_factored and
+ * bi_fit_batched_factored evaluate it, signatures unchanged, `dataset` indexing the event sets (an index >= T:
+ * BI_ST_BAD_DATASET); every other source-wise entry point (bi_factored_set_counts, bi_sourcewise_generate_toys, the Hessian, the
+ * Fisher information, goodness of fit, expectations, coarse views, the real-valued store, bi_sourcewise_build_nonempty,
+ * bi_eval_sourcewise_planned, bi_eval_sourcewise_scan, bi_sample_stretch_sourcewise, bi_grid_reduce_sourcewise) refuses with
+ * BI_ERR_STATE naming the event store.  A context that never creates one runs the code it ran before. */
+int bi_sourcewise_events_begin(bi_ctx* ctx, int64_t T, const int64_t* n_events, double outlier_likelihood);
+int bi_sourcewise_events_set_row(bi_ctx* ctx, int s, int64_t local_index, const double* values);
+int bi_sourcewise_events_end(bi_ctx* ctx);
+int bi_sourcewise_score_events(bi_ctx* ctx, int method, int k, const int32_t* n_grid, const double* grid, int64_t T,
+                               const int64_t* offsets, const double* coords, double outlier_likelihood);
+int bi_sourcewise_drop_events(bi_ctx* ctx);
+int bi_sourcewise_event_set_counts(bi_ctx* ctx, int64_t* counts);
+int bi_sourcewise_download_event_set(bi_ctx* ctx, int64_t t, double* out);
 
 /* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
  * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
