@@ -117,6 +117,7 @@ SIGNATURES = {
     'bi_sourcewise_drop_events': (C.c_int, [_p]),
     'bi_sourcewise_event_set_counts': (C.c_int, [_p, _p]),
     'bi_sourcewise_download_event_set': (C.c_int, [_p, _i64, _p]),
+    'bi_eval_sourcewise_events_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     'bi_grid_reduce': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     'bi_eval_sourcewise_scan': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_grid_reduce_sourcewise': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, _p, _p, _p]),

@@ -24,6 +24,8 @@
 //                         non-empty bins of its dataset), k_sourcewise_gather (the compacted copies)   bi_k_sourcewise_nonempty.h
 //     tu_sourcewise_events.hip   k_sourcewise_events (value + gradient sums of one point of a source-wise model over the events of
 //                         its event set: the unbinned likelihood)                           bi_k_sourcewise_events.h
+//     tu_sourcewise_events_curv.hip   k_sourcewise_events_curv (the Hessian's sums of one point of a source-wise model over the events
+//                         of its event set, in k_factored_curv's Gram panels)                bi_k_sourcewise_events_curv.h
 //     tu_sourcewise_scan.hip   k_sourcewise_scan_key, _cut, _groups, _fill (the planner's per-point descriptors -> the 16-point work
 //                         items of k_scan_mfma, on the device)                               bi_k_sourcewise_scan.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
@@ -152,6 +154,10 @@ void launch_sourcewise_gather(bi_ctx* c, const SourcewiseGatherArgs& a, dim3 gri
 // k_sourcewise_events<SC, EM, GRAD>: the sums of one point of a source-wise model over the events of its event set per item; classes
 // and result slots (factored_slots) as launch_morph_factored.  grid.x: the largest block count of the launch's items
 int launch_sourcewise_events(bi_ctx* c, int SC, int EM, bool grad, const SourcewiseEventsArgs& a, dim3 grid);
+// k_sourcewise_events_curv<SC, EM, PS, PANEL>: the Hessian's sums of one point of a source-wise model over the events of its event
+// set per item, Gram panel `panel` of factored_curv_panels(SC, EM); a.coef holds launch_factored_curv's observed-form columns.
+// BI_ERR_INVALID for another (SC, EM, panel).  grid.x: the largest block count of the launch's items
+int launch_sourcewise_events_curv(bi_ctx* c, int SC, int EM, int panel, const SourcewiseEventsArgs& a, dim3 grid);
 // the scan planner of source-wise points (bi_k_sourcewise_scan.h; no launcher times its kernel, the host half bi_sourcewise_scan.h
 // opens the EventScope): sort keys of a.n points; groups of equal keys cut every `cut` points; group tables and counts; the
 // descriptors of the a.n_valid sorted positions in front of the rejected points

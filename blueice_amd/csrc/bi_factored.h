@@ -258,15 +258,16 @@ struct FacBatch {
     std::vector<int32_t> tiles;                 // [n] tiles of the item's dataset's list
     std::vector<double> lam_sum;                // [n] sum_s lambda_s, sources ascending from 0.0
     std::vector<double> hN, hdN;                // [n][S] N_s = sum_c w_c R_{s,c}; [n][S][kFacMaxOwn] d_j N_s (order 1)
-    // the event store (order 0 / 1, bi_sourcewise_events.h): the descriptors point at the item's event set's columns; `tiles` are
-    // the set's, lam_sum is sum_s r_s (sources ascending from 0.0), cnt_off holds the set's number of events
+    // the event store (order 0 / 1 / 2, bi_sourcewise_events.h): the descriptors point at the item's event set's columns; `tiles`
+    // are the set's, lam_sum is sum_s r_s (sources ascending from 0.0), cnt_off holds the set's number of events; at order 2 the
+    // d2w columns and hd2M as for the counts (bi_eval_sourcewise_events_hess)
     bool events;
 
     FacBatch(bi_ctx* ctx, int order_, bool reads_counts = true, bool nonempty_ = false)
         : c(ctx), m(ctx->fac), order(order_), d(m.d), S(m.S), SC(S <= 2 ? 2 : S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM),
           NX(order_ == 2 ? EM * (EM - 1) / 2 : 0), WC(W + NX), NR(m.n_rows_point), dataset_test(order_ != 3 && reads_counts),
           nonempty(nonempty_ && order_ <= 1 && reads_counts && !ctx->fac.ev_ready),
-          events(ctx->fac.ev_ready && order_ <= 1 && reads_counts) {
+          events(ctx->fac.ev_ready && order_ <= 2 && reads_counts) {
         c->last_point_pieces = 0;               // (a call with no live item launches nothing)
     }
 

@@ -49,6 +49,16 @@ struct FacCurvPlan {
         int rc = b.upload(extra, (size_t)b.n_items * NTOT);
         if (rc) return rc;
         for (int p = 0; p < panels; ++p) {
+            if (b.events) {     // the event store (bi_eval_sourcewise_events_hess): the same panels over the items' event sets
+                rc = b.run_events(nsl[(size_t)p], b.pu.dev<int64_t>(b.first_extra + 2 + p), b.pu.dev<double>(b.first_extra + (p == 0 ? 0 : 1)), what,
+                                  [&](const SourcewiseEventsArgs& a, dim3 grid) {
+                                      const int e = launch_sourcewise_events_curv(c, b.SC, b.EM, p, a, grid);
+                                      return e ? fail(c, e, "%s: no kernel variant for %d source slots with %d own axes, panel %d", what, b.SC, b.EM, p)
+                                               : BI_OK;
+                                  });
+                if (rc) return rc;
+                continue;
+            }
             rc = b.run(nsl[(size_t)p], b.pu.dev<int64_t>(b.first_extra + 2 + p), b.pu.dev<double>(b.first_extra + (p == 0 ? 0 : 1)), what,
                        [&](const FactoredArgs& a, dim3 grid) {
                            const int e = launch_factored_curv(c, b.SC, b.EM, fisher, p, a, grid);
@@ -99,6 +109,41 @@ void fac_curv_contract(int F, int K, const std::vector<long double>& C, const do
         }
 }
 
+// The observed Hessian of item i into hp [F][F]: H = -C Q C^T plus the (rs_s, z_i), (z_i, z_i) and (z_i, z_k) terms of the header,
+// from the linear sums L (k_factored_curv's observed layout: L[1 + s] = L_tau_s, L[1 + SC + s EM + j] = L_ups_s,j,
+// L[1 + K + s NX + x] = L_chi_s,x) and the Gram triangle tri.  What bi_eval_sourcewise_hess (L over f = n / mu - 1) and
+// bi_eval_sourcewise_events_hess (L over g = 1 / lam, L_tau less 1) share; C, T [F][K] and H [F][F] are the caller's scratch.
+void fac_curv_hessian(const FacBatch& b, int64_t i, const double* L, const double* tri, const double* rate_scale, std::vector<long double>& C,
+                      std::vector<long double>& T, std::vector<long double>& H, double* hp) {
+    const int d = b.d, S = b.S, F = d + S, K = b.SC * b.W, NXK = b.EM * (b.EM - 1) / 2;
+    const int64_t p = b.live[(size_t)i];
+    fac_curv_matrix(b, i, rate_scale, C);
+    fac_curv_contract(F, K, C, tri, -1.0L, T, H);
+    for (int s = 0; s < S; ++s) {
+        const long double M = b.hM[(size_t)i * S + s], rs = rate_scale ? rate_scale[p * S + s] : 1.0, Lt = L[1 + s];
+        const double* dM = &b.hdM[((size_t)i * S + s) * kFacMaxOwn];
+        const double* d2M = &b.hd2M[((size_t)i * S + s) * kFacMaxOwn];
+        const double* Lu = L + 1 + b.SC + s * b.EM;
+        const double* Lx = L + 1 + K + s * NXK;
+        const int* ax = &b.m.own[(size_t)s * kFacMaxOwn];
+        for (int j = 0; j < b.m.n_own[(size_t)s]; ++j) {
+            const long double v = (long double)dM[j] * Lt + M * (long double)Lu[j];
+            H[(size_t)(d + s) * F + ax[j]] += v;
+            H[(size_t)ax[j] * F + (d + s)] += v;
+            H[(size_t)ax[j] * F + ax[j]] += 2.0L * rs * (long double)dM[j] * (long double)Lu[j];
+            for (int k = j + 1; k < b.m.n_own[(size_t)s]; ++k) {
+                const int x = k * (k - 1) / 2 + j;
+                const long double w = rs * ((long double)d2M[x] * Lt + (long double)dM[j] * (long double)Lu[k] +
+                                            (long double)dM[k] * (long double)Lu[j] + M * (long double)Lx[x]);
+                H[(size_t)ax[j] * F + ax[k]] += w;
+                H[(size_t)ax[k] * F + ax[j]] += w;
+            }
+        }
+    }
+    for (int q = 0; q < F; ++q)
+        for (int r = 0; r <= q; ++r) hp[q * F + r] = hp[r * F + q] = (double)H[(size_t)q * F + r] + 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -111,7 +156,7 @@ int bi_eval_sourcewise_hess(bi_ctx* c, int64_t P, const double* z, const double*
     if (c->fac.d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "bi_eval_sourcewise_hess: z is NULL");
     if (P == 0) return BI_OK;
     FacBatch b(c, 2);
-    const int d = b.d, S = b.S, F = d + S, K = b.SC * b.W, NXK = b.EM * (b.EM - 1) / 2;
+    const int d = b.d, S = b.S, F = d + S, K = b.SC * b.W;
     const double inf = std::numeric_limits<double>::infinity();
     const double qnan = std::numeric_limits<double>::quiet_NaN();
     HIP_TRY(c, hipSetDevice(c->device));
@@ -136,32 +181,7 @@ int bi_eval_sourcewise_hess(bi_ctx* c, int64_t P, const double* z, const double*
             ll[p] = h[0];
             if (!std::isfinite(h[0])) continue;             // gradient and Hessian stay nan
             b.gradient(i, h, rate_scale, grad + p * F, gz);
-            fac_curv_matrix(b, i, rate_scale, C);
-            fac_curv_contract(F, K, C, h + plan.NL, -1.0L, T, H);
-            for (int s = 0; s < S; ++s) {
-                const long double M = b.hM[(size_t)i * S + s], rs = rate_scale ? rate_scale[p * S + s] : 1.0, Lt = h[1 + s];
-                const double* dM = &b.hdM[((size_t)i * S + s) * kFacMaxOwn];
-                const double* d2M = &b.hd2M[((size_t)i * S + s) * kFacMaxOwn];
-                const double* Lu = h + 1 + b.SC + s * b.EM;
-                const double* Lx = h + 1 + K + s * NXK;
-                const int* ax = &b.m.own[(size_t)s * kFacMaxOwn];
-                for (int j = 0; j < b.m.n_own[(size_t)s]; ++j) {
-                    const long double v = (long double)dM[j] * Lt + M * (long double)Lu[j];
-                    H[(size_t)(d + s) * F + ax[j]] += v;
-                    H[(size_t)ax[j] * F + (d + s)] += v;
-                    H[(size_t)ax[j] * F + ax[j]] += 2.0L * rs * (long double)dM[j] * (long double)Lu[j];
-                    for (int k = j + 1; k < b.m.n_own[(size_t)s]; ++k) {
-                        const int x = k * (k - 1) / 2 + j;
-                        const long double w = rs * ((long double)d2M[x] * Lt + (long double)dM[j] * (long double)Lu[k] +
-                                                    (long double)dM[k] * (long double)Lu[j] + M * (long double)Lx[x]);
-                        H[(size_t)ax[j] * F + ax[k]] += w;
-                        H[(size_t)ax[k] * F + ax[j]] += w;
-                    }
-                }
-            }
-            double* hp = hess + p * F * F;
-            for (int q = 0; q < F; ++q)
-                for (int r = 0; r <= q; ++r) hp[q * F + r] = hp[r * F + q] = (double)H[(size_t)q * F + r] + 0.0;
+            fac_curv_hessian(b, i, h, h + plan.NL, rate_scale, C, T, H, hess + p * F * F);
         }
     });
     return BI_OK;

@@ -1,6 +1,8 @@
 // bi_sourcewise_events.h -- source-wise models: the event store, with which the context is an UNBINNED source-wise likelihood
 // (host half; the kernel is k_sourcewise_events, bi_k_sourcewise_events.h).  bi_sourcewise_events_begin / _set_row / _end,
-// bi_sourcewise_score_events, bi_sourcewise_drop_events, bi_sourcewise_event_set_counts, bi_sourcewise_download_event_set.
+// bi_sourcewise_score_events, bi_sourcewise_drop_events, bi_sourcewise_event_set_counts, bi_sourcewise_download_event_set, and
+// bi_eval_sourcewise_events_hess (value, gradient and analytic Hessian over the store; kernel k_sourcewise_events_curv,
+// bi_k_sourcewise_events_curv.h).
 //
 // The reference's source_wise_interpolation keeps, per source, the pdf values of the events at the anchors of the parameters
 // that source responds to only.  The store is that: a second form of the data beside the dense counts, [rows][columns] with
@@ -264,6 +266,54 @@ int bi_sourcewise_download_event_set(bi_ctx* c, int64_t t, double* out) {
     HIP_TRY(c, hipMemcpy2DAsync(out, (size_t)n * sizeof(double), (const double*)m.ev_ps.p + m.ev_first[(size_t)t], (size_t)m.ev_cols * sizeof(double),
                                 (size_t)n * sizeof(double), (size_t)m.row_first[(size_t)m.S], hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BI_OK;
+}
+
+// bi_eval_sourcewise_hess (bi_factored_curv.h) on the event store: the same batch, panels and second-order host loop
+// (fac_curv_hessian), k_sourcewise_events_curv for k_factored_curv.  The linear sums of the event likelihood are L_tau_s =
+// sum_e g tau_s - 1 (a pdf integrates to one: sum_s r_s has the second derivatives d_j M_s, rs_s d_jk M_s and nothing else),
+// L_ups and L_chi as the kernel gives them; slot 0 less sum_s r_s through k_finish, as factored_eval does for events.
+int bi_eval_sourcewise_events_hess(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                                   double* grad, double* hess, int32_t* status) {
+    int rc = fac_check(c, "bi_eval_sourcewise_events_hess", true, true);
+    if (rc) return rc;
+    if (!c->fac.ev_ready)
+        return fail(c, BI_ERR_STATE, "bi_eval_sourcewise_events_hess: the context holds no event store (bi_sourcewise_events_begin ... _end or "
+                    "bi_sourcewise_score_events first; the Hessian against counts is bi_eval_sourcewise_hess)");
+    if (P < 0 || (P > 0 && (!ll || !grad || !hess))) return fail(c, BI_ERR_INVALID, "bi_eval_sourcewise_events_hess: bad P / output pointer");
+    if (c->fac.d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "bi_eval_sourcewise_events_hess: z is NULL");
+    if (P == 0) return BI_OK;
+    FacBatch b(c, 2);
+    const int d = b.d, S = b.S, F = d + S, K = b.SC * b.W;
+    const double inf = std::numeric_limits<double>::infinity();
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    HIP_TRY(c, hipSetDevice(c->device));
+    b.screen(P, z, rate_scale, dataset, status, [&](int64_t p) {
+        ll[p] = -inf;
+        for (int j = 0; j < F; ++j) grad[p * F + j] = qnan;
+        for (int j = 0; j < F * F; ++j) hess[p * F * F + j] = qnan;
+    });
+    if (b.n_items == 0) return BI_OK;
+    b.fill(z, rate_scale, dataset);
+    FacCurvPlan plan(b, false);
+    for (int64_t i = 0; i < b.n_items; ++i) plan.lg0[(size_t)(i * plan.nsl[0])] = b.lam_sum[(size_t)i];     // (sum_s r_s: no lgamma over events)
+    if ((rc = plan.run(c, b, false, "bi_eval_sourcewise_events_hess"))) return rc;
+
+    const double* out = b.out();
+    parallel_for(b.n_items, 256, [&](int64_t lo, int64_t hi) {
+        std::vector<double> gz((size_t)std::max(d, 1)), L((size_t)plan.NL);
+        std::vector<long double> C((size_t)F * K), T((size_t)F * K), H((size_t)F * F);
+        for (int64_t i = lo; i < hi; ++i) {
+            const int64_t p = b.live[(size_t)i];
+            const double* h = out + (size_t)i * plan.NTOT;
+            ll[p] = h[0];
+            if (!std::isfinite(h[0])) continue;             // gradient and Hessian stay nan
+            std::copy(h, h + plan.NL, L.begin());
+            for (int s = 0; s < S; ++s) L[(size_t)(1 + s)] = h[1 + s] - 1.0;
+            b.gradient(i, L.data(), rate_scale, grad + p * F, gz);
+            fac_curv_hessian(b, i, L.data(), h + plan.NL, rate_scale, C, T, H, hess + p * F * F);
+        }
+    });
     return BI_OK;
 }
 

@@ -784,7 +784,7 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         self._hessian_route = 'analytic'
         z, scale, prior = self._batch_terms(points, livetime_days)
         P = len(z)
-        ll, gz, gs, Hth, st = self.ctx.eval_hess(z if z.shape[1] else None, scale, dataset)
+        ll, gz, gs, Hth, st = self._device_hessian(z if z.shape[1] else None, scale, dataset)
         if np.any(st & _capi.ST_INTERNAL):
             raise DeviceError("the device gave up waiting for a partial sum (in-launch reduction): GPU fault")
         bad = (st & (_capi.ST_OUT_OF_BOUNDS | _capi.ST_UNPHYSICAL)) != 0
@@ -807,6 +807,11 @@ class DeviceLogLikelihood(LogLikelihoodBase):
         H[bad | ~np.isfinite(out)] = np.nan
         names = self._parameter_names()
         return out, OrderedDict((n, g[:, j]) for j, n in enumerate(names)), names, H
+
+    def _device_hessian(self, z, scale, dataset):
+        """the context's analytic route over (z, rate_scale): eval_hess' shapes (a subclass whose context has another entry
+        point for its form of the data names it here)"""
+        return self.ctx.eval_hess(z, scale, dataset)
 
     def _hessian_by_gradient_differences(self, points, livetime_days, dataset):
         names = self._parameter_names()

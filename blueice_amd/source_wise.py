@@ -119,7 +119,7 @@ def _find_cell(g, z):
 class SourceWiseContext:
     """What the evaluation code of DeviceLogLikelihood and the native fit loop (profile.BatchObjective.native) see as `ctx`:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
-    eval_grad, eval_hess, eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, expected_coarse_jacobian,
+    eval_grad, eval_hess (eval_events_hess on the event store), eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, expected_coarse_jacobian,
     coarse_counts,
     generate_toys_points, download_counts, set_param / get_param,
     fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
@@ -415,6 +415,21 @@ class SourceWiseContext:
         status = np.zeros(P, dtype=np.int32)
         dev._check(dev._lib.bi_eval_sourcewise_hess(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(hess),
                                                     ptr(status)))
+        return ll, grad[:, :self.d], grad[:, self.d:], hess, status
+
+    def eval_events_hess(self, z, rate_scale=None, dataset=None):
+        """eval_hess on the event store (bi_eval_sourcewise_events_hess): value, gradient and analytic Hessian of the unbinned
+        likelihood, `dataset` indexing the event sets -> eval_hess's shapes.  ll, the gradient and the status are eval_grad's
+        bits on the store; H is nan wherever ll is not finite.  Without a store the library refuses."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        F = self.d + self.S
+        ll = np.empty(P, dtype=np.float64)
+        grad = np.empty((P, F), dtype=np.float64)
+        hess = np.empty((P, F, F), dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_events_hess(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(grad), ptr(hess),
+                                                           ptr(status)))
         return ll, grad[:, :self.d], grad[:, self.d:], hess, status
 
     def eval_gof(self, z, rate_scale=None, dataset=None):

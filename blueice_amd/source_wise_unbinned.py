@@ -3,6 +3,7 @@
     lf = SourceWiseUnbinnedLogLikelihood(pdf_base_config, likelihood_config=None, **overrides)
     lf.add_rate_parameter(...); lf.add_shape_parameter(...); lf.prepare(); lf.set_data(d)   (or lf.set_datasets([d0, d1, ...]))
     lf(**params), lf.eval_points, lf.value_and_gradient, lf.values_and_gradients,
+    lf.value_gradient_hessian, lf.values_gradients_hessians, lf.bestfit_minuit, blueice_amd.inference.hesse(lf, values, datasets=),
     lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval,
     blueice_amd.inference.bestfit_toys(lf) over the sets of set_datasets, lf.n_events_per_dataset, and as a term of a LogLikelihoodSum
 
@@ -21,8 +22,16 @@ method (the test of UnbinnedLogLikelihood's device scoring) the density histogra
 `set_datasets` send the event coordinates only; otherwise the model is a one-bin carrier of the geometry and the rates and the
 events are scored on the host, one `source.pdf(*coords)` per own anchor row.  Both give the same bits.
 
-Limits as SourceWiseBinnedLogLikelihood's: 32 shape parameters, 8 sources, 3 own parameters per source.  `supports_hessian` is
-False: `values_gradients_hessians`, `bestfit_minuit` and `blueice_amd.inference.hesse` take differences of the analytic gradient.
+Limits as SourceWiseBinnedLogLikelihood's: 32 shape parameters, 8 sources, 3 own parameters per source.
+
+Second derivatives: with `likelihood_config['analytic_hessian'] = True`, `supports_hessian` is true once data are set and
+`value_gradient_hessian`, `values_gradients_hessians`, `bestfit_minuit` and `blueice_amd.inference.hesse` run on the analytic
+Hessian over the event store (bi_eval_sourcewise_events_hess, kernel k_sourcewise_events_curv: one pass over the events and a
+host contraction per point) through the usual chain rule (priors, GaussianPrior, live time); `hessian_method` is 'analytic'.  By
+default (`analytic_hessian` False) `supports_hessian` is False and the same calls take central differences of the analytic
+gradient, 2 F + 1 displaced gradient evaluations per point, `hessian_method` 'gradient-differences': the behaviour the class had
+before the analytic route existed, which stays the default so that results do not change under existing users.  Events carry no
+expected information: `fisher_information*` and `expected_*` stay refused either way.
 Refused with NotImplementedError: compute_pdf / full_output, allow_negative sources, Beeston-Barlow, event toys drawn on the
 device (simulate_toy*), sampling and grid_scan, and everything that reads the dense store of a binned source-wise model.
 """
@@ -34,8 +43,9 @@ from .source_wise import _SourceWiseLikelihood
 __all__ = ['SourceWiseUnbinnedLogLikelihood']
 
 _SCOPE = ("an unbinned source-wise model (SourceWiseUnbinnedLogLikelihood) has value, gradient, the fit, scan and interval layers and "
-          "fits of the event sets of set_datasets; not event toys drawn on the device, sampling, gridded likelihoods, an analytic "
-          "Hessian, or anything that reads binned counts")
+          "fits of the event sets of set_datasets, and (likelihood_config['analytic_hessian'] = True) the analytic Hessian behind "
+          "values_gradients_hessians, bestfit_minuit and inference.hesse; not event toys drawn on the device, sampling, gridded "
+          "likelihoods, the expected (Fisher) information, or anything that reads binned counts")
 
 
 def _refused(name):
@@ -57,7 +67,17 @@ class SourceWiseUnbinnedLogLikelihood(_SourceWiseLikelihood):
                 'real_data', 'expected_upper_limit', 'expected_discovery_significance')
 
     _full_grid_class = 'UnbinnedLogLikelihood'
-    supports_hessian = False        # (values_gradients_hessians takes differences of the analytic gradient)
+
+    @property
+    def supports_hessian(self):
+        """True once data are set when likelihood_config['analytic_hessian'] is true: the analytic Hessian over the event store
+        (bi_eval_sourcewise_events_hess; `hessian_method` is then 'analytic').  The default is False -- `values_gradients_hessians`
+        takes differences of the analytic gradient, as it did before the analytic route existed -- so that nothing changes for
+        a likelihood that does not ask for it."""
+        return bool(self.config.get('analytic_hessian', False)) and self.ctx is not None and bool(self.is_data_set)
+
+    def _device_hessian(self, z, scale, dataset):
+        return self.ctx.eval_events_hess(z, scale, dataset)
 
     def __init__(self, pdf_base_config, likelihood_config=None, **kwargs):
         super().__init__(pdf_base_config, likelihood_config, **kwargs)

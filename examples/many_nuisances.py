@@ -1,6 +1,7 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
     PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band] [--posterior] [--grid]
+        [--unbinned | --measure-unbinned | --measure-unbinned-hessian]
         [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian | --measure-sampler [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
@@ -77,11 +78,17 @@ points of one cell tuple, and the planner's share of a call by device events; th
 
 --unbinned fits, instead of (2) - (6), the same twelve parameters over the EVENTS (SourceWiseUnbinnedLogLikelihood: the event store of
 bi_sourcewise_score_events, k_sourcewise_events) with the sources' pdfs taken from histograms, and runs one profile scan of the
-signal's multiplier.  The full-grid unbinned route would hold 5^8 anchors x 4 sources x N values.
+signal's multiplier, then bestfit_minuit with the errors of all twelve parameters from both routes: the analytic Hessian over the event
+store (likelihood_config['analytic_hessian'] = True: bi_eval_sourcewise_events_hess) and differences of the analytic gradient (the
+default).  The full-grid unbinned route would hold 5^8 anchors x 4 sources x N values.
 
 --measure-unbinned times, at the measured source-wise shape with 10^4 and 10^6 events, bi_eval_factored on the event store against
 bi_eval_grad / bi_eval on the same model expanded to the 5^4 unbinned grid model, and bi_sourcewise_score_events against
 bi_score_events on the expanded templates; the lines go to profiles/sourcewise_events_measure.txt too.
+
+--measure-unbinned-hessian times, at the same shape and numbers of events, bi_eval_sourcewise_events_hess against the one bi_eval_factored
+gradient call over the (2 F + 1) P points it replaces and against bi_eval_hess on the expanded unbinned grid model, and the kernels alone by
+device events; the lines go to profiles/sourcewise_events_curv_measure.txt too.
 """
 import argparse
 import time
@@ -109,6 +116,8 @@ ap.add_argument('--measure-grid', action='store_true',
 ap.add_argument('--unbinned', action='store_true', help='fit the twelve parameters over events (unbinned source-wise likelihood) and scan the signal multiplier')
 ap.add_argument('--measure-unbinned', action='store_true',
                 help='time bi_eval_factored on the event store against the expanded unbinned grid model, and the two scoring calls')
+ap.add_argument('--measure-unbinned-hessian', action='store_true',
+                help='time bi_eval_sourcewise_events_hess against the gradient differences it replaces and bi_eval_hess on the expanded unbinned grid model')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -1072,7 +1081,124 @@ def unbinned():
     inside = grid[2 * scan <= 1.0]
     print('(3) likelihood_ratio_scan over s0_rate_multiplier: %d hypotheses, 11 nuisances profiled at each, %.3f s; minimum at %.3f, '
           '2 dlnL <= 1 on [%.3f, %.3f]' % (args.scan, dt, grid[np.argmin(scan)], inside.min(), inside.max()))
+    # the errors of all twelve parameters from both routes: the analytic Hessian over the event store, and differences of the gradient
+    errors, seconds = {}, {}
+    for route, analytic in (('analytic', True), ('gradient-differences', False)):
+        lf.config['analytic_hessian'] = analytic
+        t0 = time.perf_counter()
+        fit, ll_fit = lf.bestfit_minuit()
+        seconds[route] = time.perf_counter() - t0
+        assert lf.hessian_method == route
+        errors[route] = fit
+    print('(4) bestfit_minuit: max ll %.4f; parabolic errors from the analytic Hessian (bi_eval_sourcewise_events_hess, %.3f s with the fit) and '
+          'from differences of the gradient (%d displaced points, %.3f s with the fit)' % (ll_fit, seconds['analytic'], 2 * len(best) + 1,
+                                                                                           seconds['gradient-differences']))
+    print('    %-10s %10s %12s %12s' % ('parameter', 'value', 'analytic', 'differences'))
+    for k in best:
+        print('    %-10s %10.4f %12.5f %12.5f' % (k.replace('_rate_multiplier', ''), errors['analytic'][k], errors['analytic'][k + '_error'],
+                                                  errors['gradient-differences'][k + '_error']))
     lf.ctx.close()
+
+
+def measure_unbinned_hessian():
+    """bi_eval_sourcewise_events_hess against what it replaces -- ONE bi_eval_factored gradient call over the (2 F + 1) P points of
+    central differences, as the class takes them -- and against bi_eval_hess on the same model expanded to the 5^4 unbinned grid
+    model, at 10^6 and 10^4 events, 64 points and one point per call.  Alternated calls, medians with quartiles, device events for
+    the kernels alone.  Written to profiles/sourcewise_events_curv_measure.txt as well."""
+    import os
+    from blueice_amd.device import DeviceContext
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    F = d + S
+    n_a, nb = 5, args.measure_bins
+    B = nb ** 3
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05                                         # densities over the unit cube
+    rows *= B / rows.sum(axis=-1, keepdims=True)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    fac = SourceWiseContext(0)
+    say('# examples/many_nuisances.py --measure-unbinned-hessian --measure-bins %d --rounds %d on %s' % (nb, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>: 8 basis columns, one launch), %d anchors, density histograms of %d^3 bins, '
+        '\'linear\' lookup, F = %d' % (d, S, n_a, nb, F))
+    edges = [np.linspace(0., 1., nb + 1)] * 3
+    centres = [0.5 * (e[:-1] + e[1:]) for e in edges]
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])                   # relative rates (10 in all); the scale is per dataset
+    tp = DeviceContext(0)
+    tp.begin_model([g] * d, S, B)
+    for lin, idx in enumerate(np.ndindex(*(n_a,) * d)):          # the same likelihood on the product grid: source s from ITS anchor
+        tp.set_anchor(lin, np.stack([rows[s, idx[s]] for s in range(S)]), np.array([mus[s, idx[s]] for s in range(S)]))
+    tp.end_model()
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    for events in (1e6, 1e4):
+        N = int(events)
+        coords = [np.clip(rng.random(N), c[0], c[-1]) for c in centres]
+        full = DeviceContext(0)
+        fac.score_events('linear', centres, [coords], 1e-12)
+        tp.score_events(full, 'linear', centres, coords, 1e-12)
+        for P in (64, 1):
+            z = rng.uniform(0.1, 0.9, (P, d)) + rng.integers(-2, 2, (P, d))      # strictly inside cells: the differences stay in them
+            r = events / 10.0 * rng.uniform(0.8, 1.2, (P, S))
+            zz, rr = np.tile(z, (2 * F + 1, 1)), np.tile(r, (2 * F + 1, 1))
+            for j in range(F):
+                for k, sign in enumerate((1.0, -1.0)):
+                    at = slice((1 + 2 * j + k) * P, (2 + 2 * j + k) * P)
+                    if j < d:
+                        zz[at, j] += sign * 1e-4
+                    else:
+                        rr[at, j - d] *= 1.0 + sign * 1e-5
+            a, b = fac.eval_events_hess(z, r), full.eval_hess(z, r)
+            g1 = fac.eval_grad(z, r)
+            same = np.array_equal(a[0], g1[0]) and np.array_equal(a[1], g1[1]) and np.array_equal(a[2], g1[2])
+            rel = np.max(np.abs(a[3] - b[3])) / np.max(np.abs(b[3]))
+            calls = [('hess', lambda: fac.eval_events_hess(z, r)), ('diff', lambda: fac.eval_grad(zz, rr)), ('grid', lambda: full.eval_hess(z, r)),
+                     ('grad', lambda: fac.eval_grad(z, r))]
+            times = {name: [] for name, _ in calls}
+            for rnd in range(3 + args.rounds):          # three warm-up rounds; the calls alternate inside every round
+                for name, call in calls:
+                    t0 = time.perf_counter()
+                    call()
+                    if rnd >= 3:
+                        times[name].append(time.perf_counter() - t0)
+            say('%.0e events, %2d points per call: bi_eval_sourcewise_events_hess %s   bi_eval_factored + gradient at (2 F + 1) P = %d points %s   '
+                'bi_eval_hess on the 5^%d unbinned grid model %s   bi_eval_factored + gradient at the P points %s'
+                % (events, P, quartiles(times['hess']), len(zz), quartiles(times['diff']), d, quartiles(times['grid']), quartiles(times['grad'])))
+            say('%.0e events, %2d points per call: differences / analytic %.2f, grid model / analytic %.2f, analytic / one gradient call %.2f; ll and '
+                'gradient bit for bit bi_eval_factored\'s: %s; max |H - H of the grid model| %.1e of the largest entry'
+                % (events, P, np.median(times['diff']) / np.median(times['hess']), np.median(times['grid']) / np.median(times['hess']),
+                   np.median(times['hess']) / np.median(times['grad']), same, rel))
+            cols = max(512, (N + 511) // 512 * 512)
+            for name, ctx, call, n_rows, n_pts in (('k_sourcewise_events_curv + k_finish', fac._dev, calls[0][1], 2 * S, P),
+                                                   ('k_sourcewise_events + k_finish, (2 F + 1) P points', fac._dev, calls[1][1], 2 * S, len(zz)),
+                                                   ('the grid route\'s kernels', full, calls[2][1], S * 2 ** d, P)):
+                ctx.profile(True)
+                ks = []
+                for _ in range(args.rounds):
+                    call()
+                    ks.append(ctx.profile_read()[1] * 1e-3)
+                ctx.profile(False)
+                gb = n_rows * cols * 8 * n_pts / 1e9
+                say('%.0e events, %2d points, kernels alone (%s): %s; %d rows x %d columns x 8 bytes x %d points = %.3f GB -> %.2f TB/s'
+                    % (events, P, name, quartiles(ks), n_rows, cols, n_pts, gb, gb / np.median(ks) / 1e3))
+        full.close()
+    say('# cache-assisted: the event store is %.1f MB at 1e4 events (inside an L2) and %.0f MB at 1e6 (inside the 256 MiB Infinity Cache), and the '
+        'points of a call read the same rows again; the grid model\'s tensor is %.0f MB and %.0f GB' % (S * n_a * 10240 * 8 / 1e6, S * n_a * 1e6 * 8 / 1e6,
+                                                                                                       n_a ** d * S * 1e4 * 8 / 1e6, n_a ** d * S * 1e6 * 8 / 1e9))
+    say('# not measured: every class but <4, 1> (more sources, more own axes), the panelled classes <8, 2> and <8, 3>, T > 1 event sets, other shapes')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_events_curv_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+    tp.close()
 
 
 def measure_unbinned():
@@ -1181,6 +1307,9 @@ if args.unbinned:
     raise SystemExit(0)
 if args.measure_unbinned:
     measure_unbinned()
+    raise SystemExit(0)
+if args.measure_unbinned_hessian:
+    measure_unbinned_hessian()
     raise SystemExit(0)
 if args.grid:
     grid_limit()

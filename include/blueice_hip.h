@@ -887,6 +887,21 @@ int bi_sourcewise_drop_events(bi_ctx* ctx);
 int bi_sourcewise_event_set_counts(bi_ctx* ctx, int64_t* counts);
 int bi_sourcewise_download_event_set(bi_ctx* ctx, int64_t t, double* out);
 
+/* ... and its analytic Hessian: bi_eval_sourcewise_hess' contract on the event store.  theta = (z, rs), F = d + S.  The event
+ * likelihood is the binned observed form with n = 1 per event, no lgamma and N_s = 1; beside the sums above the kernel
+ * (k_sourcewise_events_curv, in the Gram panels of the binned curvature kernel) forms per event chi_s,jk = sum_c d_j d_k w_c p_s,c,e
+ * and sums g chi_s,jk and the Gram Q_ab = sum_e ((g u_a) g) u_b over u = (tau_s, ups_s,j) -- no g^2 is formed; nan sources and
+ * clamped events (g = 0) as above.  With L_tau_s = sum_e g tau_s - 1, L_ups = sum_e g ups, L_chi = sum_e g chi the host forms
+ * H = -C Q C^T plus the (rs_s, z_i), (z_i, z_i) and (z_i, z_k) terms of bi_eval_sourcewise_hess, in long double.
+ *   ll [P], grad [P][F], status [P]   bit for bit what bi_eval_factored returns on the store with a gradient
+ *   hess [P][F][F]                    full and exactly symmetric (one triangle computed, mirrored); rows and columns of axes nobody
+ *                                     owns are 0; nan wherever ll is not finite (outlier = 0 with some lam_e = 0 among them)
+ * `dataset` indexes the event sets (an index outside [0, T): BI_ST_BAD_DATASET, ll = -inf, grad and hess nan).  A point's bits do
+ * not depend on its batch or on the other sets of the call; repeated calls agree bit for bit.  Needs a finished event store:
+ * without one BI_ERR_STATE (the Hessian against counts is bi_eval_sourcewise_hess, which in turn refuses while a store exists). */
+int bi_eval_sourcewise_events_hess(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                                   double* grad, double* hess, int32_t* status);
+
 /* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
  * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
  * lists one after the other; any order, finite).  The first n_keep variables are kept, the others reduced:
