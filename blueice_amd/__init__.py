@@ -11,6 +11,7 @@ from .likelihood import (LogLikelihoodBase, BinnedLogLikelihood, UnbinnedLogLike
 from .grid import grid_scan, GridResult  # noqa: F401
 from .coarse import CoarseBinning  # noqa: F401
 from .source_wise import SourceWiseBinnedLogLikelihood  # noqa: F401
-from .source_wise_unbinned import SourceWiseUnbinnedLogLikelihood  # noqa: F401
+from .source_wise_unbinned import (SourceWiseUnbinnedLogLikelihood, sourcewise_event_toys, sourcewise_event_toys_points,  # noqa: F401
+                                   sourcewise_simulated_events)
 
 __version__ = '0.1.0'

@@ -117,6 +117,9 @@ SIGNATURES = {
     'bi_sourcewise_drop_events': (C.c_int, [_p]),
     'bi_sourcewise_event_set_counts': (C.c_int, [_p, _p]),
     'bi_sourcewise_download_event_set': (C.c_int, [_p, _i64, _p]),
+    'bi_sourcewise_simulate_event_toys': (C.c_int, [_p, C.c_int, C.c_int, _p, _p, _i64, _p, _p, _p, C.c_uint64, C.c_double, _p]),
+    'bi_sourcewise_simulated_event_count': (_i64, [_p]),
+    'bi_sourcewise_download_events': (C.c_int, [_p, _p, _p]),
     'bi_eval_sourcewise_events_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     'bi_grid_reduce': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     'bi_eval_sourcewise_scan': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),

@@ -1,4 +1,4 @@
-"""Build libblueice_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU): twenty-eight translation units compiled
+"""Build libblueice_hip.so in-tree with hipcc for gfx950 (cross-compiles without a GPU): twenty-nine translation units compiled
 side by side, rebuilt when the sha256 of the sources' content changes (lib/libblueice_hip.sha256).
 
     python -m blueice_amd.build [--force]
@@ -17,7 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, 'csrc')
 # one translation unit per heavy kernel family (csrc/bi_common.h says which), compiled side by side
-UNITS = ('blueice_hip', 'tu_morph', 'tu_scan', 'tu_scan_sorted', 'tu_grad', 'tu_scan_bb', 'tu_prim', 'tu_hess', 'tu_sampler', 'tu_gof', 'tu_real', 'tu_factored', 'tu_factored_curv', 'tu_factored_fisher', 'tu_sourcewise_expect', 'tu_sourcewise_gof', 'tu_sourcewise_real', 'tu_grid', 'tu_coarse', 'tu_sourcewise_coarse', 'tu_sourcewise_coarse_jac', 'tu_fisher', 'tu_toys', 'tu_sourcewise_plan', 'tu_sourcewise_nonempty', 'tu_sourcewise_scan', 'tu_sourcewise_events', 'tu_sourcewise_events_curv')
+UNITS = ('blueice_hip', 'tu_morph', 'tu_scan', 'tu_scan_sorted', 'tu_grad', 'tu_scan_bb', 'tu_prim', 'tu_hess', 'tu_sampler', 'tu_gof', 'tu_real', 'tu_factored', 'tu_factored_curv', 'tu_factored_fisher', 'tu_sourcewise_expect', 'tu_sourcewise_gof', 'tu_sourcewise_real', 'tu_grid', 'tu_coarse', 'tu_sourcewise_coarse', 'tu_sourcewise_coarse_jac', 'tu_fisher', 'tu_toys', 'tu_sourcewise_plan', 'tu_sourcewise_nonempty', 'tu_sourcewise_scan', 'tu_sourcewise_events', 'tu_sourcewise_events_curv', 'tu_sourcewise_sim')
 HDR = os.path.join(os.path.dirname(_HERE), 'include', 'blueice_hip.h')
 OUT_DIR = os.path.join(_HERE, 'lib')
 OBJ_DIR = os.path.join(_HERE, 'lib', 'obj')

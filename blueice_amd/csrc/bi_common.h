@@ -26,6 +26,8 @@
 //                         its event set: the unbinned likelihood)                           bi_k_sourcewise_events.h
 //     tu_sourcewise_events_curv.hip   k_sourcewise_events_curv (the Hessian's sums of one point of a source-wise model over the events
 //                         of its event set, in k_factored_curv's Gram panels)                bi_k_sourcewise_events_curv.h
+//     tu_sourcewise_sim.hip   k_sourcewise_pmf, k_sourcewise_sim_counts, _room, _first, _events (event-level toys of a source-wise
+//                         model: per-source pmf rows, counts, layout and the events themselves)   bi_k_sourcewise_sim.h
 //     tu_sourcewise_scan.hip   k_sourcewise_scan_key, _cut, _groups, _fill (the planner's per-point descriptors -> the 16-point work
 //                         items of k_scan_mfma, on the device)                               bi_k_sourcewise_scan.h
 //     tu_sampler.hip      k_stretch_propose, k_stretch_accept (ensemble sampler half-steps)      bi_k_sampler.h
@@ -158,6 +160,14 @@ int launch_sourcewise_events(bi_ctx* c, int SC, int EM, bool grad, const Sourcew
 // set per item, Gram panel `panel` of factored_curv_panels(SC, EM); a.coef holds launch_factored_curv's observed-form columns.
 // BI_ERR_INVALID for another (SC, EM, panel).  grid.x: the largest block count of the launch's items
 int launch_sourcewise_events_curv(bi_ctx* c, int SC, int EM, int panel, const SourcewiseEventsArgs& a, dim3 grid);
+// event toys of a source-wise model (bi_k_sourcewise_sim.h; no launcher times its kernel, the host half bi_sourcewise_sim.h opens
+// the EventScopes).  k_sourcewise_pmf<SC, EM>: the pmf rows of n_items (<= 65 535) truths, BI_ERR_INVALID for an (SC, EM) without
+// a variant; then the counts and rooms of all (toy, source), the per-(toy, source) starts, and the events of a range of columns
+int launch_sourcewise_pmf(bi_ctx* c, int SC, int EM, const SourcewisePmfArgs& a, int64_t n_items);
+void launch_sourcewise_sim_counts(bi_ctx* c, const SourcewiseSimArgs& a);
+void launch_sourcewise_sim_room(bi_ctx* c, const SourcewiseSimArgs& a);
+void launch_sourcewise_sim_first(bi_ctx* c, const SourcewiseSimArgs& a);
+void launch_sourcewise_sim_events(bi_ctx* c, const SourcewiseSimArgs& a);
 // the scan planner of source-wise points (bi_k_sourcewise_scan.h; no launcher times its kernel, the host half bi_sourcewise_scan.h
 // opens the EventScope): sort keys of a.n points; groups of equal keys cut every `cut` points; group tables and counts; the
 // descriptors of the a.n_valid sorted positions in front of the rejected points

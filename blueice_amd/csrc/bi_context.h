@@ -190,7 +190,15 @@ struct bi_ctx {
         std::vector<int64_t> ev_first, ev_n;
         std::vector<char> ev_row_set;                // [rows] the row has been uploaded (bi_sourcewise_events_set_row)
         DevBuf ev_ps;
+        // the events of a store drawn on the device (bi_sourcewise_simulate_event_toys; bi_sourcewise_sim.h): coordinates
+        // [sim_k][ev_cols] and the source of every column (-1: padding) in the store's padded layout, sim_n events in all.  They
+        // belong to that store: whatever releases or replaces it releases them (fac_drop_events).  sim_n < 0: none
+        DevBuf sim_coords, sim_source;
+        int sim_k = 0;
+        int64_t sim_n = -1;
     } fac;
+    int64_t sim_truth_chunk = 0;                 // bi_sourcewise_simulate_event_toys: truths per sub-batch (0: by the scratch bound)
+    int64_t sim_part_ns[4] = {};                 // ... while profiling, the device time of its last call: layout, pmf + scans, events, scoring
     int64_t sourcewise_form = 1;                 // 0: source-wise evaluations read the dense store although the non-empty-bin form is built
     int64_t sourcewise_scan_timed = 3;           // profiling: bit 0 = the scan route's planner, bit 1 = its matrix-core launches are timed
 

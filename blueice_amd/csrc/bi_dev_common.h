@@ -314,6 +314,46 @@ struct SourcewiseExpectArgs {
     int R;
 };
 
+// the analysis space of the event simulators (k_sim_*, bi_k_misc.h; sim_one_event, bi_k_draw.h; bi_k_sourcewise_sim.h)
+struct SimArgs {
+    int k;                       // analysis dimensions
+    int S;
+    int n_edges[kMaxDim];
+    int edge_off[kMaxDim];
+    int64_t stride[kMaxDim];     // bins (C order) per step along the axis
+};
+
+// k_sourcewise_pmf (bi_k_sourcewise_sim.h): FactoredArgs' order-0 descriptors of a sub-batch of truths and where their pmf rows go
+struct SourcewisePmfArgs {
+    FactoredArgs f;
+    SimArgs sim;
+    const double* edges;       // the bin edges of every axis back to back
+    double* out;               // [items][S][B] max(tau_s,b, 0) vol_b
+    int64_t B;
+};
+
+// the other kernels of bi_sourcewise_simulate_event_toys (bi_k_sourcewise_sim.h): T toys, toy t at truth[t], its number in the
+// seed's ensemble toy0 + t
+struct SourcewiseSimArgs {
+    SimArgs sim;
+    const double* edges;
+    const double* rates;       // [H][rate_stride] r_s of every truth
+    const int32_t* truth;      // [T]
+    int64_t* n;                // [T][S] events per (toy, source)
+    int64_t* room;             // [T + 1] columns a toy takes (whole tiles, at least one); the last entry 0
+    const int64_t* set_first;  // [T + 1] the exclusive prefix sums of room
+    int64_t* first;            // [T][S + 1] first column of (toy, source); the last entry the end of the toy's events
+    int64_t T, toy0;
+    uint64_t seed;
+    int rate_stride;
+    // k_sourcewise_sim_events: the columns [col0, col0 + ncols) of the toys [t0, t0 + nt), whose truths start at h0
+    const double* cdf;         // [truths of the sub-batch][S][B] running sums of the pmf rows
+    int64_t B, col0, ncols, t0, nt, h0;
+    int64_t cols;              // columns of the whole call: the row length of coords
+    double* coords;            // [k][cols]
+    int32_t* source;           // [cols]
+};
+
 // k_morph_expect (bi_k_gof.h)
 struct ExpectArgs {
     const double* ps;          // [rows][Bp] the dense template tensor

@@ -168,6 +168,9 @@ void fac_drop_events(bi_ctx::Factored& m) {
     m.ev_outlier = 0.0;
     m.ev_first.clear(); m.ev_n.clear(); m.ev_row_set.clear();
     dev_free(m.ev_ps);
+    dev_free(m.sim_coords); dev_free(m.sim_source);      // (the events a simulated store was scored from)
+    m.sim_k = 0;
+    m.sim_n = -1;
 }
 // do bi_eval_factored (and with it the native fit), bi_eval_sourcewise_planned and bi_sample_stretch_sourcewise run on it
 bool fac_nonempty_on(const bi_ctx* c) { return c->fac.ne_ready && c->sourcewise_form == 1; }

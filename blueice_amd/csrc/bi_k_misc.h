@@ -4,6 +4,7 @@
 #pragma once
 
 #include "bi_philox.h"
+#include "bi_k_draw.h"
 
 namespace {
 
@@ -537,36 +538,7 @@ __global__ void k_pad_copy(const double* __restrict__ src, int64_t n, int64_t np
 // Counter-based Philox4x32-10 keyed by the seed, counter = (bin, dataset, attempt): every (dataset, bin) draw
 // is independent of launch geometry and can be regenerated, which is what lets the two-pass CSR build
 // (count, then scatter) see the same numbers twice.
-// lam < 10: inversion by sequential search with one 53-bit uniform; p0 = exp(-lam) comes from a per-bin table (it is
-// the same for every toy)
-__device__ __forceinline__ double poisson_small(double lam, double p0, double u) {
-    double p = p0, F = p, n = 0.0;
-    while (u > F && n < 1000.0) {
-        n += 1.0;
-        p *= lam / n;
-        F += p;
-    }
-    return n;
-}
-
-// lam >= 10: PTRS, Hoermann (1993): transformed rejection with squeeze, as in numpy's random_poisson_ptrs
-__device__ double poisson_ptrs(double lam, uint64_t seed, int64_t t, int64_t b) {
-    uint32_t r[4];
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const double slam = sqrt(lam), loglam = log(lam);
-    const double bb = 0.931 + 2.53 * slam, aa = -0.059 + 0.02483 * bb;
-    const double invalpha = 1.1239 + 1.1328 / (bb - 3.4), vr = 0.9277 - 3.6224 / (bb - 2.0);
-    for (uint32_t attempt = 0; attempt < 4096u; ++attempt) {
-        philox4x32_10((uint32_t)b, (uint32_t)(b >> 32), (uint32_t)t, ((uint32_t)(t >> 32) & 0xFFFFu) | ((attempt + 1u) << 16), k0, k1, r);
-        const double U = u53(r[0], r[1]) - 0.5, V = u53(r[2], r[3]);
-        const double us = 0.5 - fabs(U);
-        const double k = floor((2.0 * aa / us + bb) * U + lam + 0.43);
-        if (us >= 0.07 && V <= vr) return k;
-        if (k < 0.0 || (us < 0.013 && V > us)) continue;
-        if (log(V) + log(invalpha) - log(aa / (us * us) + bb) <= -lam + k * loglam - lgamma(k + 1.0)) return k;
-    }
-    return floor(lam);  // unreachable in practice (acceptance > 0.9 per attempt)
-}
+// (poisson_small for lam < 10 and poisson_ptrs from there on: bi_k_draw.h)
 
 // The draws of bins b (even) and b + 1 of toy t: one Philox block gives both their uniforms.
 __device__ __forceinline__ void poisson_draw_pair(const double* __restrict__ mu, const double* __restrict__ p0, int64_t B,
@@ -692,14 +664,7 @@ __global__ void k_toy_lgsum(const double* __restrict__ lg_partial, int nchunks, 
 // with the same counters (Philox4x32-10 keyed by the seed; counter = (event, toy)): the first only counts the non-empty
 // bins of every toy, the second writes them behind the offsets a scan made of the counts.
 constexpr int kEvThreads = 512;
-constexpr uint32_t kEvTag = 0x45564E54u;        // separates the event counters from the per-bin ones
-
-__device__ __forceinline__ int toy_event_count(double M, uint64_t seed, int64_t t) {
-    if (M >= 10.0) return (int)poisson_ptrs(M, seed, t, ((int64_t)1 << 40) + 7);          // a "bin" no model has
-    uint32_t r[4];
-    philox4x32_10(0xFFFFFFFFu, kEvTag, (uint32_t)t, (uint32_t)(t >> 32) & 0xFFFFu, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-    return (int)poisson_small(M, exp(-M), u53(r[0], r[1]));
-}
+// (toy_event_count and its counter tag kEvTag: bi_k_draw.h)
 
 // events per toy (an upper bound of its non-empty bins: the room it gets in the provisional lists)
 // (overflow: one word per truth -- a toy beyond its truth's sort buffer sends that truth to the bin-by-bin group)
@@ -1030,15 +995,7 @@ __global__ __launch_bounds__(kThreads) void k_score_rows(const int64_t* __restri
 // their running sums are prepared per source (k_sim_pmf + a scan), then one thread per event finds its source from the
 // per-source counts, its bin by bisection in that source's cumulative sums and its position in the bin -- Philox4x32-10
 // counters (event within its source, source) keyed by the seed, so a toy does not depend on the launch geometry.
-struct SimArgs {
-    int k;                       // analysis dimensions
-    int S;
-    int n_edges[kMaxDim];
-    int edge_off[kMaxDim];
-    int64_t stride[kMaxDim];     // bins (C order) per step along the axis
-};
-constexpr uint32_t kSimTag = 0x53494D45u;
-constexpr double kSimMaxRate = 1073741824.0;   // 2^30 expected events per source: toy_event_count returns an int, bi_simulate_events refuses more
+// (SimArgs: bi_dev_common.h; kSimTag, kSimMaxRate and sim_one_event, the draw of one event: bi_k_draw.h)
 
 // dens [S][B] (morphed densities) -> pmf [S][B] = density x bin volume (negative / nan densities count as 0)
 __global__ __launch_bounds__(kThreads) void k_sim_pmf(const double* __restrict__ dens, SimArgs a, const double* __restrict__ edges,
@@ -1065,35 +1022,6 @@ __global__ void k_sim_counts(const double* __restrict__ rates, int S, uint64_t s
     n_out[s] = (M > 0.0 && M < kSimMaxRate) ? (int64_t)toy_event_count(M, seed ^ 0x9E3779B97F4A7C15ull, (int64_t)s) : 0;
 }
 
-// event j of source s of the toy keyed by `seed`, stored at column e of coords [k][N]
-__device__ __forceinline__ void sim_one_event(const double* __restrict__ cdf /*[S][B]*/, int64_t B, const SimArgs& a,
-                                              const double* __restrict__ edges, uint64_t seed, int s, int64_t j, int64_t N, int64_t e,
-                                              double* __restrict__ coords /*[k][N]*/, int32_t* __restrict__ source /*[N]*/) {
-    const double* __restrict__ F = cdf + (int64_t)s * B;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    uint32_t r[4];
-    philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), (uint32_t)s, kSimTag, k0, k1, r);
-    const double target = u53(r[0], r[1]) * F[B - 1];
-    int64_t lo = 0, hi = B;                                              // first bin whose cumulative sum exceeds the target
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (F[mid] <= target) lo = mid + 1; else hi = mid;
-    }
-    int64_t rem = min(lo, B - 1);
-    for (int ax = 0; ax < a.k; ++ax) {
-        // the position inside the bin: one uniform per axis, counter (event, source, axis)
-        philox4x32_10((uint32_t)j, (uint32_t)(j >> 32), (uint32_t)s | ((uint32_t)ax << 24), kSimTag + 1u, k0, k1, r);
-        const double u = u53(r[0], r[1]);
-        const int64_t i = rem / a.stride[ax];
-        rem -= i * a.stride[ax];
-        const double* __restrict__ ed = edges + a.edge_off[ax];
-        // (uniform inside the bin, as Histdd.get_random draws it, source.py:248-264; a 'linear' pdf clips to the outer bin
-        //  centres only when it is EVALUATED, source.py:231-239: k_score_locate does that, the stored events stay as drawn)
-        coords[(int64_t)ax * N + e] = ed[i] + u * (ed[i + 1] - ed[i]);
-    }
-    source[e] = s;
-}
-
 __global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restrict__ cdf /*[S][B]*/, int64_t B, SimArgs a,
                                                          const double* __restrict__ edges, const int64_t* __restrict__ first /*[S+1]*/,
                                                          uint64_t seed, int64_t N, double* __restrict__ coords /*[k][N]*/,
@@ -1106,14 +1034,7 @@ __global__ __launch_bounds__(kThreads) void k_sim_events(const double* __restric
 }
 
 // ---- an ensemble of T event-level toys (bi_simulate_event_toys) ------------------------------------------------
-// Toy D of the seed's ensemble is bi_simulate_events' toy with the seed toy_seed(seed, D) (include/blueice_hip.h): D ->
-// seed + (D + 1) c is one-to-one modulo 2^64 (c odd), the rest is the bijective finaliser of splitmix64.
-__host__ __device__ inline uint64_t toy_seed(uint64_t seed, uint64_t D) {
-    uint64_t x = seed + (D + 1ull) * 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// Toy D of the seed's ensemble is bi_simulate_events' toy with the seed toy_seed(seed, D) (bi_k_draw.h).
 
 // one launch for the T x S counts: N_{t,s} ~ Poisson(rate_s) of toy toy0 + t (k_sim_counts with that toy's seed)
 __global__ void k_sim_toy_counts(const double* __restrict__ rates, int S, int64_t T, uint64_t seed, int64_t toy0, int64_t* __restrict__ n_out /*[T][S]*/) {

@@ -91,6 +91,7 @@ const ParamDef kParams[] = {
     {"sourcewise_form", kParamRW, BI_P_GET(c->sourcewise_form), BI_P_RANGE(0, 1, sourcewise_form, "sourcewise_form: 0 dense, 1 the non-empty-bin form where it is built")},
     {"sourcewise_scan_timed", kParamRW, BI_P_GET(c->sourcewise_scan_timed), BI_P_RANGE(0, 3, sourcewise_scan_timed, "sourcewise_scan_timed: bit 0 the planner, bit 1 the matrix-core launches")},
     {"toy_offset", kParamRW, BI_P_GET(c->toy_offset), BI_P_RANGE(0, INT64_MAX, toy_offset, "toy_offset >= 0")},
+    {"sim_truth_chunk", kParamRW, BI_P_GET(c->sim_truth_chunk), BI_P_RANGE(0, 32768, sim_truth_chunk, "sim_truth_chunk in [0, 32768] (0 = automatic)")},
     {"narrow_counts", kParamRW, BI_P_GET(c->narrow_counts), BI_P_FLAG(narrow_counts)},
     {"packed_rows", kParamRW, BI_P_GET(c->packed_rows), BI_P_FLAG(packed_rows)},
     {"mail_timeout_ms", kParamRW, BI_P_GET(c->mail_timeout_ms),
@@ -106,6 +107,10 @@ const ParamDef kParams[] = {
     {"debug_late_post", kParamWrite, nullptr, BI_P_SET(c->debug_late_post = v < 0 ? -1 : v)},
     // ---- counters and state (read-only) ------------------------------------------------------------------------
     BI_P_RO("tile_bins", kTile),
+    BI_P_RO("sim_ns_layout", c->sim_part_ns[0]),
+    BI_P_RO("sim_ns_pmf", c->sim_part_ns[1]),
+    BI_P_RO("sim_ns_events", c->sim_part_ns[2]),
+    BI_P_RO("sim_ns_score", c->sim_part_ns[3]),
     BI_P_RO("padded_bins", c->Bp),
     BI_P_RO("n_scan_launches", c->n_scan_launches),
     BI_P_RO("n_toy_polled", c->n_toy_polled),

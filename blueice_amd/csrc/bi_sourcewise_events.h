@@ -22,7 +22,8 @@
 // (k_score_locate, k_score_rows: every stored value has the bits bi_score_events gives for that row -- but for 'linear' lookups
 // in TWO analysis dimensions, where scipy's RegularGridInterpolator takes a routine of its own that associates the products
 // differently: there the store follows scipy, k_score_rows<2, true>, so that device- and host-scored stores agree bit for bit, and
-// differs from bi_score_events' tensor by a rounding).  Both need a finished
+// differs from bi_score_events' tensor by a rounding; events_score_columns, which takes the coordinates where they lie in HBM, so that
+// bi_sourcewise_simulate_event_toys, bi_sourcewise_sim.h, scores the events it drew through the same launches).  Both need a finished
 // source-wise model for the geometry and the rates; the first does not read the model's rows.
 // While a store exists bi_eval_factored and bi_fit_batched_factored evaluate it (`dataset` indexes the event sets) and every
 // other source-wise entry point refuses with BI_ERR_STATE (fac_check).  compact_budget bounds its bytes.
@@ -80,6 +81,71 @@ int events_create(bi_ctx* c, const char* who, int64_t T, const int64_t* n_events
     return BI_OK;
 }
 
+// The lookup of the store's columns: coords_dev [k][cols] in HBM in the store's padded layout (whatever the padding columns hold:
+// the lookup stays inside every row, and they are set to zero behind it) -> every row of the fresh store of events_create.
+// clip: 'linear' lookups clip the coordinates here (events drawn on the device arrive unclipped; a caller's are clipped already).
+// Waits for the stream; after a device error the context holds no store.
+int events_score_columns(bi_ctx* c, const char* who, int method, int k, const AxisWalk& ax, const double* grid, const double* coords_dev, int clip) {
+    bi_ctx::Factored& m = c->fac;
+    const int64_t cols = m.ev_cols, rows = m.row_first[(size_t)m.S], T = m.ev_T;
+    std::vector<int64_t> pads;
+    for (int64_t t = 0; t < T; ++t) {
+        const int64_t end = t + 1 < T ? m.ev_first[(size_t)t + 1] : cols;
+        for (int64_t col = m.ev_first[(size_t)t] + m.ev_n[(size_t)t]; col < end; ++col) pads.push_back(col);
+    }
+    ScoreArgs a{};
+    a.k = k;
+    a.method = method;
+    a.clip = clip;
+    ax.put(a.n_grid, a.grid_off, a.stride);
+    ScratchBuf d_grid, d_base, d_t, d_pad;
+    int rc;
+    if ((rc = dev_alloc(c, d_grid, (size_t)ax.flat * sizeof(double))) || (rc = dev_alloc(c, d_base, (size_t)cols * sizeof(int64_t))) ||
+        (method == 1 && (rc = dev_alloc(c, d_t, (size_t)cols * k * sizeof(double)))) || (!pads.empty() && (rc = dev_upload(c, d_pad, pads)))) {
+        (void)hipStreamSynchronize(c->stream);
+        fac_drop_events(m);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(d_grid.p, grid, (size_t)ax.flat * sizeof(double), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_score_locate, dim3((unsigned)((cols + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream, coords_dev, cols, a,
+                           (const double*)d_grid.p, (int64_t*)d_base.p, (double*)d_t.p);
+        const int per_block = kThreads * score_events_per_thread(method == 0 ? 0 : k);
+        const unsigned bx = (unsigned)((cols + per_block - 1) / per_block);
+#define BI_ROWS(...)                                                                                                            \
+    hipLaunchKernelGGL((k_score_rows<__VA_ARGS__>), dim3(bx, (unsigned)std::min<int64_t>(rows, 65535)), dim3(kThreads), 0, c->stream,       \
+                       (const int64_t*)d_base.p, (const double*)d_t.p, cols, a, (const double*)m.ps.p, m.Bp, (int)rows, (double*)m.ev_ps.p, \
+                       cols, (const int32_t*)nullptr)
+        switch (method == 0 ? 0 : k) {
+            case 0: BI_ROWS(0); break; case 1: BI_ROWS(1); break; case 3: BI_ROWS(3); break;
+            case 2: BI_ROWS(2, true); break;    // scipy's own routine for two-dimensional fields: see k_score_rows
+            case 4: BI_ROWS(4); break; case 5: BI_ROWS(5); break; case 6: BI_ROWS(6); break; case 7: BI_ROWS(7); break;
+            default: BI_ROWS(8); break;
+        }
+#undef BI_ROWS
+        if (!pads.empty()) {
+            const int64_t n_fill = rows * (int64_t)pads.size();
+            hipLaunchKernelGGL(k_fill_columns, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, c->stream, (double*)m.ev_ps.p, cols, rows,
+                               (const int64_t*)d_pad.p, (int64_t)pads.size(), 0.0);
+        }
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // the grid and the host blocks are borrowed for the call only
+    else (void)hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        fac_drop_events(m);
+        return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return BI_OK;
+}
+
+// the fresh store of events_create is complete
+void events_close(bi_ctx::Factored& m) {
+    std::fill(m.ev_row_set.begin(), m.ev_row_set.end(), 1);
+    m.ev_open = false;
+    m.ev_ready = true;
+}
+
 int sourcewise_score_events(bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t T, const int64_t* offsets,
                             const double* coords, double outlier) {
     const char* who = "bi_sourcewise_score_events";
@@ -100,70 +166,33 @@ int sourcewise_score_events(bi_ctx* c, int method, int k, const int32_t* n_grid,
     const int64_t N = offsets[T];
     if (N > 0 && !coords) return fail(c, BI_ERR_INVALID, "%s: coords is NULL", who);
     if ((rc = events_create(c, who, T, n.data(), outlier))) return rc;
-    const int64_t cols = m.ev_cols, rows = m.row_first[(size_t)m.S];
+    const int64_t cols = m.ev_cols;
     if (N > 0) {
         // the caller's events at their columns; a padding column is looked up at the first grid value of every axis (inside every
         // row) and set to zero behind the lookup
         std::vector<double> padded((size_t)cols * k);
-        std::vector<int64_t> pads;
         for (int i = 0; i < k; ++i) {
             double* row = padded.data() + (size_t)i * cols;
             std::fill(row, row + cols, grid[ax.off[i]]);
             for (int64_t t = 0; t < T; ++t)
                 std::copy(coords + (size_t)i * N + offsets[t], coords + (size_t)i * N + offsets[t + 1], row + m.ev_first[(size_t)t]);
         }
-        for (int64_t t = 0; t < T; ++t) {
-            const int64_t end = t + 1 < T ? m.ev_first[(size_t)t + 1] : cols;
-            for (int64_t col = m.ev_first[(size_t)t] + n[(size_t)t]; col < end; ++col) pads.push_back(col);
-        }
-        ScoreArgs a{};
-        a.k = k;
-        a.method = method;
-        a.clip = 0;                         // the caller's events are clipped already (bi_score_events' contract)
-        ax.put(a.n_grid, a.grid_off, a.stride);
-        ScratchBuf d_ev, d_grid, d_base, d_t, d_pad;
-        if ((rc = dev_alloc(c, d_ev, (size_t)cols * k * sizeof(double))) || (rc = dev_alloc(c, d_grid, (size_t)ax.flat * sizeof(double))) ||
-            (rc = dev_alloc(c, d_base, (size_t)cols * sizeof(int64_t))) || (method == 1 && (rc = dev_alloc(c, d_t, (size_t)cols * k * sizeof(double)))) ||
-            (!pads.empty() && (rc = dev_upload(c, d_pad, pads)))) {
+        ScratchBuf d_ev;
+        if ((rc = dev_alloc(c, d_ev, (size_t)cols * k * sizeof(double)))) {
             (void)hipStreamSynchronize(c->stream);
             fac_drop_events(m);
             return rc;
         }
-        hipError_t e = hipMemcpyAsync(d_ev.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_grid.p, grid, (size_t)ax.flat * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_score_locate, dim3((unsigned)((cols + kThreads - 1) / kThreads)), dim3(kThreads), 0, c->stream,
-                               (const double*)d_ev.p, cols, a, (const double*)d_grid.p, (int64_t*)d_base.p, (double*)d_t.p);
-            const int per_block = kThreads * score_events_per_thread(method == 0 ? 0 : k);
-            const unsigned bx = (unsigned)((cols + per_block - 1) / per_block);
-#define BI_ROWS(...)                                                                                                            \
-    hipLaunchKernelGGL((k_score_rows<__VA_ARGS__>), dim3(bx, (unsigned)std::min<int64_t>(rows, 65535)), dim3(kThreads), 0, c->stream,       \
-                       (const int64_t*)d_base.p, (const double*)d_t.p, cols, a, (const double*)m.ps.p, m.Bp, (int)rows, (double*)m.ev_ps.p, \
-                       cols, (const int32_t*)nullptr)
-            switch (method == 0 ? 0 : k) {
-                case 0: BI_ROWS(0); break; case 1: BI_ROWS(1); break; case 3: BI_ROWS(3); break;
-                case 2: BI_ROWS(2, true); break;    // scipy's own routine for two-dimensional fields: see k_score_rows
-                case 4: BI_ROWS(4); break; case 5: BI_ROWS(5); break; case 6: BI_ROWS(6); break; case 7: BI_ROWS(7); break;
-                default: BI_ROWS(8); break;
-            }
-#undef BI_ROWS
-            if (!pads.empty()) {
-                const int64_t n_fill = rows * (int64_t)pads.size();
-                hipLaunchKernelGGL(k_fill_columns, dim3((unsigned)((n_fill + 255) / 256)), dim3(256), 0, c->stream, (double*)m.ev_ps.p, cols, rows,
-                                   (const int64_t*)d_pad.p, (int64_t)pads.size(), 0.0);
-            }
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);      // coords and the host blocks are borrowed for the call only
-        else (void)hipStreamSynchronize(c->stream);
+        const hipError_t e = hipMemcpyAsync(d_ev.p, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream);
             fac_drop_events(m);
             return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
         }
+        // (the caller's events are clipped already: bi_score_events' contract)
+        if ((rc = events_score_columns(c, who, method, k, ax, grid, (const double*)d_ev.p, 0))) return rc;
     }
-    std::fill(m.ev_row_set.begin(), m.ev_row_set.end(), 1);
-    m.ev_open = false;
-    m.ev_ready = true;
+    events_close(m);
     return BI_OK;
 }
 

@@ -1621,6 +1621,7 @@ int bi_profile_read(bi_ctx* c, int64_t* n_launches, double* total_ms) {
 #include "bi_sourcewise_plan.h"
 #include "bi_sourcewise_nonempty.h"
 #include "bi_sourcewise_events.h"
+#include "bi_sourcewise_sim.h"
 #include "bi_sourcewise_scan.h"
 #include "bi_grid.h"
 #include "bi_coarse.h"

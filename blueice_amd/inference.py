@@ -208,13 +208,23 @@ def bestfit_device(lf, guess=None, **kwargs):
 
 
 def _simulate_toys_at(lf, n_toys, seed, livetime_days, truth):
-    """`lf.simulate_toys(n_toys, seed=, livetime_days=, **truth)` -- spelled as `simulate_toys_points` with a one-row `points`
-    dict for a class that says so (`toys_through_points`: a source-wise model, whose bound `simulate_toys` stays refused).  The
-    toys are the same either way: toy t of the call is toy toy_offset + t of the seed's ensemble."""
-    if getattr(type(lf), 'toys_through_points', False):
-        lf.simulate_toys_points({k: np.array([float(v)]) for k, v in truth.items()}, [int(n_toys)], seed=seed, livetime_days=livetime_days)
-    else:
+    """The one place where the toy layers call a generator.  n_toys an int and truth a dict of scalars: `lf.simulate_toys(n_toys,
+    seed=, livetime_days=, **truth)` -- spelled as `simulate_toys_points` with a one-row `points` dict for a class that says so
+    (`toys_through_points`: a source-wise model, whose bound `simulate_toys` stays refused).  n_toys an array [H] and truth a
+    dict of arrays [H]: `lf.simulate_toys_points(truth, n_toys, ...)`, toys of several truths from one generator call.  An
+    unbinned source-wise model takes both through its private `_simulate_toys_points` (source_wise_unbinned.py: its bound
+    generator names stay refused).  The toys are the same either way: toy t of the call is toy toy_offset + t of the seed's
+    ensemble."""
+    points = np.ndim(n_toys) > 0
+    draw = getattr(lf, '_simulate_toys_points', None)
+    if draw is None and (points or getattr(type(lf), 'toys_through_points', False)):
+        draw = lf.simulate_toys_points
+    if draw is None:
         lf.simulate_toys(n_toys, seed=seed, livetime_days=livetime_days, **truth)
+    elif points:
+        draw(truth, n_toys, seed=seed, livetime_days=livetime_days)
+    else:
+        draw({k: np.array([float(v)]) for k, v in truth.items()}, [int(n_toys)], seed=seed, livetime_days=livetime_days)
 
 
 def _binned_or_source_wise(lf, what, binning=None):
@@ -260,7 +270,7 @@ def toy_mc_fits(lf, n_toys, chunk=256, seed=0, truth=None, livetime_days=None, f
     (seed, toy number, bin)), so the ensemble does not depend on `chunk`: that only bounds the HBM taken by the toys'
     compacted templates (see `bestfit_toys`).  first_toy: the number of this call's first toy -- ranks that each take a range
     of one ensemble (one process per GPU) draw the toys one process would.  fit_kwargs: parameters held fixed, `guess`, ...
-    as `bestfit_batched`.
+    as `bestfit_batched`.  A SourceWiseUnbinnedLogLikelihood is taken too (its event toys: sourcewise_event_toys_points).
     -> (OrderedDict name -> fitted values [n_toys], max log likelihood [n_toys]).  Afterwards the likelihood's data are
     the toys of the last chunk."""
     ctx = getattr(lf, 'ctx', None)
@@ -304,7 +314,8 @@ def _resident_data(lf, ctx):
     """-> a callable that gives `lf` the data back that it holds now, or None where that is not possible"""
     if not getattr(lf, 'is_data_set', False):
         return None
-    if hasattr(lf, 'set_binned_data') and ctx is not None and hasattr(ctx, 'download_counts'):
+    events_only = hasattr(lf, '_simulate_toys_points')     # (an unbinned source-wise model: its bound set_binned_data is a refusal)
+    if not events_only and hasattr(lf, 'set_binned_data') and ctx is not None and hasattr(ctx, 'download_counts'):
         counts = np.stack([ctx.download_counts(t) for t in range(int(ctx.T))])
         counts = counts.reshape(((len(counts),) if len(counts) > 1 else ()) + tuple(lf.bin_shape))
         events = getattr(lf, '_data', None)
@@ -329,7 +340,8 @@ def toy_test_statistics(lf, target, hypotheses, n_toys, seed=0, kind='central', 
     Toy j of hypothesis i is drawn at {target: hypotheses[i], **truth_i} (truth: dict of nuisance values, scalars or
     arrays [H]; other parameters at their defaults) and is toy D = first_toy + i n_toys + j of the seed's ensemble: the
     result does not depend on `chunk`, and ranks can each take toy_range = (j0, j1), the toys j0 <= j < j1 of every
-    hypothesis.  Toys are drawn and fitted `chunk` at a time.  A likelihood with `simulate_toys_points` (binned) gets chunks
+    hypothesis.  Toys are drawn and fitted `chunk` at a time.  A likelihood with `simulate_toys_points` (binned; an unbinned
+    source-wise model through sourcewise_event_toys_points) gets chunks
     that run across hypothesis boundaries -- toys of several hypotheses from one generator call, fitted in one engine
     call per fit; any other likelihood with `simulate_toys` (unbinned; a duck-typed one) gets chunks of one hypothesis, with
     its context's toy_offset set as `toy_mc_fits` does -- as does a toy_range that leaves toys out (the numbers of a
@@ -346,7 +358,7 @@ def toy_test_statistics(lf, target, hypotheses, n_toys, seed=0, kind='central', 
 
     Afterwards the likelihood has its own data back where that is possible: a binned likelihood's resident datasets are read
     (`download_counts`) before and handed to `set_binned_data` after -- the same counts, as a dense stack; an unbinned
-    one gets `set_data` of the events it still holds.  It is not possible for datasets that exist on the device only
+    one (an unbinned source-wise model too) gets `set_data` of the events it still holds.  It is not possible for datasets that exist on the device only
     (`set_datasets`, simulated events): then the toys of the last chunk stay, as after `toy_mc_fits`."""
     if kind not in ('upper', 'lower', 'central'):
         raise ValueError("kind must be 'upper', 'lower' or 'central'")
@@ -380,7 +392,7 @@ def toy_test_statistics(lf, target, hypotheses, n_toys, seed=0, kind='central', 
             if mixed:
                 pts = {k: v[i_a:i_b] for k, v in truth.items()}
                 pts[target] = hyp[i_a:i_b]
-                lf.simulate_toys_points(pts, np.bincount(i_of - i_a, minlength=i_b - i_a), seed=seed, livetime_days=livetime_days)
+                _simulate_toys_at(lf, np.bincount(i_of - i_a, minlength=i_b - i_a), seed, livetime_days, pts)
             else:
                 _simulate_toys_at(lf, f1 - f0, seed, livetime_days,
                                   dict({k: float(v[i_a]) for k, v in truth.items()}, **{target: float(hyp[i_a])}))

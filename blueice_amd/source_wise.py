@@ -86,6 +86,8 @@ Limits: 32 shape parameters, 8 sources, at most 3 own parameters per source (a s
 full grid).  Unbinned data: `SourceWiseContext.score_events` / `set_event_rows` put an event store beside the counts
 (bi_sourcewise_score_events, bi_sourcewise_events_begin ...); while it exists `eval`, `eval_grad` and `fit_batched` are the extended
 unbinned likelihood over its event sets and every other call of the context is refused by the library; `drop_events` releases it.
+`SourceWiseContext.simulate_event_toys` draws event-level toys on the device into that store (bi_sourcewise_simulate_event_toys)
+and `download_events` fetches them; the class layer is blueice_amd.source_wise_unbinned.
 Not available, and refused with NotImplementedError: sources that may go negative, Beeston-Barlow, compute_pdf /
 full_output calls, eval_toys*, Hessians, sampling and gridded likelihoods on an Asimov view, and the bound lf.grid_scan (the
 function is the spelling that works, above).
@@ -121,7 +123,7 @@ class SourceWiseContext:
     a thin adapter over a DeviceContext whose model is the source-wise store.  It exposes what they duck-type on -- eval,
     eval_grad, eval_hess (eval_events_hess on the event store), eval_fisher, eval_gof, expected_counts, set_coarse_binning, expected_coarse, expected_coarse_jacobian,
     coarse_counts,
-    generate_toys_points, download_counts, set_param / get_param,
+    generate_toys_points, download_counts, simulate_event_toys / download_events (event-level toys into the event store), set_param / get_param,
     fit_batched, interpolate('mus', z), T, the real-valued store under DeviceContext's names (set_real_counts, set_asimov_counts,
     real_count_sets, download_real_counts, eval_real, fit_batched_real), sample_stretch (with eval_planned, the same device planner
     for points given by the host) -- and the uploads; nothing else of the DeviceContext (plans, grids ...) has a meaning here and is
@@ -135,6 +137,7 @@ class SourceWiseContext:
         self._counts = None
         self._coarse_key = None
         self._binned = None                     # (T, host copy) of the counts while an event store stands in front of them
+        self._sim_k = 0                         # analysis dimensions of the events simulate_event_toys drew
 
     def set_param(self, name, value):
         """a parameter of the underlying context (`toy_offset`: the number of a generator call's first toy in the seed's ensemble)"""
@@ -295,6 +298,45 @@ class SourceWiseContext:
         out = np.empty((sum(m.size for m in self.mus), n), dtype=np.float64)
         self._dev._check(self._dev._lib.bi_sourcewise_download_event_set(self._dev._h, int(t), ptr(out) if n else None))
         return out
+
+    def simulate_event_toys(self, method, edges, z, rate_scale=None, n_toys=1, seed=0, outlier_likelihood=0.0):
+        """Draw sum(n_toys) event-level toys ON THE DEVICE, n_toys[h] of them at truth (z[h], rate_scale[h]), truth-major, and make
+        them the context's event sets (bi_sourcewise_simulate_event_toys): the model's rows are density histograms over `edges`
+        (k ascending arrays), the events are scored with `method` ('piecewise' or 'linear') as `score_events` scores them.  Toy t
+        of the call is toy toy_offset + t (the context parameter) of the seed's ensemble.  -> events per (toy, source) [T, S].
+        Everything is validated before the previous store is touched (ValueError)."""
+        dev = self._dev
+        edges, n_edges, flat = dev._grid_args(edges)
+        n_toys = np.ascontiguousarray(np.atleast_1d(n_toys), dtype=np.int64)
+        H = len(n_toys)
+        z = np.ascontiguousarray(as_f64(z).reshape(H, self.d)) if self.d else None
+        if rate_scale is not None:
+            rate_scale = np.ascontiguousarray(np.broadcast_to(as_f64(np.atleast_2d(rate_scale)), (H, self.S)))
+        T = int(n_toys.sum()) if H and (n_toys >= 0).all() else 0
+        counts = np.zeros((max(T, 1), self.S), dtype=np.int64)
+        dev._check(dev._lib.bi_sourcewise_simulate_event_toys(dev._h, {'piecewise': 0, 'linear': 1}[method], len(edges), ptr(n_edges), ptr(flat),
+                                                              H, ptr(z), ptr(rate_scale), ptr(n_toys), int(seed) & (2**64 - 1),
+                                                              float(outlier_likelihood), ptr(counts)))
+        self._enter_events(T)
+        self._sim_k = len(edges)
+        return counts[:T]
+
+    def simulated_event_count(self):
+        """events of the resident simulated toys in all; -1 when the store (if any) was not drawn on the device"""
+        return int(self._dev._lib.bi_sourcewise_simulated_event_count(self._dev._h))
+
+    def download_events(self):
+        """The events `simulate_event_toys` drew, without the padding, set by set -> (coords [k, N], source [N]); their split
+        into sets is `event_set_counts()`.  NotPreparedException once another store has replaced the toys."""
+        dev = self._dev
+        N = self.simulated_event_count()
+        if N < 0:
+            dev._check(dev._lib.bi_sourcewise_download_events(dev._h, None, None))
+        k = self._sim_k
+        coords = np.empty((k, max(N, 0)), dtype=np.float64)
+        source = np.empty(max(N, 0), dtype=np.int32)
+        dev._check(dev._lib.bi_sourcewise_download_events(dev._h, ptr(coords) if N else None, ptr(source) if N else None))
+        return coords, source
 
     # -- evaluation ------------------------------------------------------------------------
     def _point_args(self, z, rate_scale, dataset):

@@ -6,6 +6,8 @@
     lf.value_gradient_hessian, lf.values_gradients_hessians, lf.bestfit_minuit, blueice_amd.inference.hesse(lf, values, datasets=),
     lf.bestfit_scipy, lf.bestfit_batched, lf.bestfit_device, lf.likelihood_ratio_scan, lf.one_parameter_interval,
     blueice_amd.inference.bestfit_toys(lf) over the sets of set_datasets, lf.n_events_per_dataset, and as a term of a LogLikelihoodSum
+    sourcewise_event_toys(lf, n_toys, seed, **truth), sourcewise_event_toys_points(lf, points, n_toys, seed), sourcewise_simulated_events(lf),
+    blueice_amd.inference.toy_mc_fits(lf, ...), .toy_test_statistics(lf, ...), .neyman_thresholds(lf, ...)
 
 This is the reference's `source_wise_interpolation` for the likelihood it exists for (blueice/likelihood.py:152-171, 210-240,
 534-563): every source keeps the pdf values of the events at the anchors of the shape parameters IT responds to only.
@@ -32,20 +34,34 @@ default (`analytic_hessian` False) `supports_hessian` is False and the same call
 gradient, 2 F + 1 displaced gradient evaluations per point, `hessian_method` 'gradient-differences': the behaviour the class had
 before the analytic route existed, which stays the default so that results do not change under existing users.  Events carry no
 expected information: `fisher_information*` and `expected_*` stay refused either way.
-Refused with NotImplementedError: compute_pdf / full_output, allow_negative sources, Beeston-Barlow, event toys drawn on the
-device (simulate_toy*), sampling and grid_scan, and everything that reads the dense store of a binned source-wise model.
+
+Event-level toys are drawn on the device (bi_sourcewise_simulate_event_toys; kernels k_sourcewise_pmf and k_sourcewise_sim_*):
+`sourcewise_event_toys_points(lf, points, n_toys, seed)` draws n_toys[h] toys at the H truths of `points` in one call and makes
+them the likelihood's datasets, `sourcewise_event_toys` is its one-truth spelling and `sourcewise_simulated_events(lf, t)` fetches
+the events.  The stream is `UnbinnedLogLikelihood.simulate_toys`': toy t of a call is toy toy_offset + t of the seed's ensemble,
+whatever the number of toys, the grouping of truths into calls or the sub-batches the device works in, and where no comparison
+is a near-tie it is event for event the toy the expanded grid model draws.  They need `scoring_route == 'device'`.  On top of
+them `blueice_amd.inference.toy_mc_fits(lf, ...)`, `toy_test_statistics(lf, ...)` and `neyman_thresholds(lf, ...)` take the
+class, with chunks that run across hypothesis boundaries as for binned models.  The bound lf.simulate_toy* / lf.toy_* /
+lf.neyman_thresholds stay refused and name these spellings.
+Refused with NotImplementedError: compute_pdf / full_output, allow_negative sources, Beeston-Barlow, sampling and grid_scan, and
+everything that reads the dense store of a binned source-wise model.
 """
 import numpy as np
 
+from .exceptions import NotPreparedException
 from .likelihood import LogLikelihoodBase, _needs_preparation, histogram_lookup_method
 from .source_wise import _SourceWiseLikelihood
 
-__all__ = ['SourceWiseUnbinnedLogLikelihood']
+__all__ = ['SourceWiseUnbinnedLogLikelihood', 'sourcewise_event_toys', 'sourcewise_event_toys_points', 'sourcewise_simulated_events']
 
 _SCOPE = ("an unbinned source-wise model (SourceWiseUnbinnedLogLikelihood) has value, gradient, the fit, scan and interval layers and "
           "fits of the event sets of set_datasets, and (likelihood_config['analytic_hessian'] = True) the analytic Hessian behind "
-          "values_gradients_hessians, bestfit_minuit and inference.hesse; not event toys drawn on the device, sampling, gridded "
-          "likelihoods, the expected (Fisher) information, or anything that reads binned counts")
+          "values_gradients_hessians, bestfit_minuit and inference.hesse; event toys drawn on the device are the functions "
+          "sourcewise_event_toys(lf, n_toys, seed, **truth), sourcewise_event_toys_points(lf, points, n_toys, seed) and "
+          "sourcewise_simulated_events(lf, t) of blueice_amd, and toy-calibrated inference is blueice_amd.inference.toy_mc_fits(lf, ...), "
+          "toy_test_statistics(lf, ...) and neyman_thresholds(lf, ...), not the bound methods; not sampling, gridded likelihoods, the "
+          "expected (Fisher) information, or anything that reads binned counts")
 
 
 def _refused(name):
@@ -152,6 +168,10 @@ class SourceWiseUnbinnedLogLikelihood(_SourceWiseLikelihood):
         self.ctx.set_event_rows([len(d) for d in datasets], rows, self.outlier_likelihood)
         self.last_scoring_route = 'host'
 
+    def _simulate_toys_points(self, points, n_toys, seed=0, livetime_days=None):
+        """what blueice_amd.inference's toy layers call for this class (the bound simulate_toys_points stays refused)"""
+        return sourcewise_event_toys_points(self, points, n_toys, seed=seed, livetime_days=livetime_days)
+
     @property
     def n_events_per_dataset(self):
         """events of every dataset the likelihood holds: [T]"""
@@ -164,3 +184,74 @@ class SourceWiseUnbinnedLogLikelihood(_SourceWiseLikelihood):
 
 for _name in SourceWiseUnbinnedLogLikelihood._REFUSED:
     setattr(SourceWiseUnbinnedLogLikelihood, _name, _refused(_name))
+
+
+# ---- event-level toys drawn on the device -------------------------------------------------------------------------------------
+
+def sourcewise_event_toys_points(lf, points, n_toys, seed=0, livetime_days=None):
+    """Draw event-level toys ON THE DEVICE at H truth points in one call (bi_sourcewise_simulate_event_toys) and make them the
+    likelihood's datasets: n_toys[h] toys (an int: the same number everywhere) at truth h, truth-major.  points: dict parameter
+    name -> array [H] (scalars broadcast; absent parameters take their defaults), as `eval_points`.  Per source N_s ~ Poisson(r_s),
+    every event a bin of the source's morphed histogram drawn with probability density x volume and a uniform position inside it
+    -- `UnbinnedLogLikelihood.simulate_toys`' stream: toy t of the call is toy `toy_offset + t` (the context parameter) of the
+    seed's ensemble, so an ensemble over many hypotheses does not depend on how they are grouped into calls.  Dataset 0 is what
+    plain `lf(**params)` sees; `eval_points(..., dataset=)`, `inference.bestfit_toys(lf)` and `inference.hesse(..., datasets=)`
+    take them all.  Afterwards `toy_truth` [T] holds the truth index of every dataset.  Needs histogram-pdf sources with one
+    lookup method (`scoring_route == 'device'`), NotImplementedError otherwise.  -> events per toy and source [T, S]."""
+    if not isinstance(lf, SourceWiseUnbinnedLogLikelihood):
+        raise TypeError("sourcewise_event_toys_points takes a SourceWiseUnbinnedLogLikelihood, not a %s" % type(lf).__name__)
+    if not lf.is_prepared:
+        raise NotPreparedException("sourcewise_event_toys_points requires you to first prepare the likelihood function using prepare()")
+    if lf.scoring_route != 'device':
+        raise NotImplementedError("event toys of an unbinned source-wise model are drawn on the device from the sources' density "
+                                  "histograms: they need scoring_route == 'device' (every source a HistogramPdfSource with one "
+                                  "interpolation method, likelihood_config['device_scoring'] not False); this likelihood scores on the host")
+    z, scale, _ = lf._batch_terms(points, livetime_days)
+    H = max(len(z), np.size(n_toys))
+    n_toys = np.ascontiguousarray(np.broadcast_to(np.asarray(n_toys, dtype=np.int64), (H,)))
+    z, scale = np.broadcast_to(z, (H, z.shape[1])), np.broadcast_to(scale, (H, scale.shape[1]))
+    for i, name in enumerate(lf.shape_parameters):
+        lo, hi = lf.get_bounds(name)
+        outside = np.flatnonzero(~((z[:, i] >= lo) & (z[:, i] <= hi)))
+        if len(outside):
+            raise ValueError("cannot simulate outside the anchor box (truth %d: %s = %r)" % (outside[0], name, z[outside[0], i]))
+    edges = [np.asarray(e, dtype=float) for _, e in lf.base_model.config['analysis_space']]
+    counts = lf.ctx.simulate_event_toys(lf._lookup[0], edges, z if z.shape[1] else None, scale, n_toys, seed, lf.outlier_likelihood)
+    lf._data = None
+    lf.is_data_set = True
+    lf.bin_shape = (int(counts[0].sum()),)
+    lf.toy_truth = np.repeat(np.arange(H), n_toys)
+    lf.last_scoring_route = 'device'
+    return counts
+
+
+def sourcewise_event_toys(lf, n_toys, seed=0, livetime_days=None, **truth):
+    """`sourcewise_event_toys_points` at one truth: `n_toys` toys at the given parameter values (defaults elsewhere), the
+    counterpart of `UnbinnedLogLikelihood.simulate_toys`.  -> events per toy and source [T, S]."""
+    if int(n_toys) < 1:
+        raise ValueError("n_toys must be at least 1")
+    return sourcewise_event_toys_points(lf, {k: np.array([float(v)]) for k, v in truth.items()}, [int(n_toys)], seed=seed,
+                                        livetime_days=livetime_days)
+
+
+def sourcewise_simulated_events(lf, t=None):
+    """The events of the toys `sourcewise_event_toys*` drew, as a record array with the analysis dimensions and a 'source' field,
+    as `Model.simulate` returns them: of toy t, or (t = None) of all toys, set by set in drawn order, with a 'toy' field when
+    the likelihood holds more than one -- what `UnbinnedLogLikelihood.simulated_events` returns."""
+    coords, source = lf.ctx.download_events()
+    names = [n for n, _ in lf.base_model.config['analysis_space']]
+    many = lf.ctx.T > 1
+    d = np.zeros(coords.shape[1], dtype=[(n, float) for n in names] + [('source', int)] + ([('toy', int)] if many else []))
+    for n, c in zip(names, coords):
+        d[n] = c
+    d['source'] = source
+    if many:
+        d['toy'] = np.repeat(np.arange(lf.ctx.T), lf.ctx.event_set_counts())
+    if t is None:
+        return d
+    if not many:
+        if t != 0:
+            raise ValueError("the likelihood holds one toy")
+        return d
+    keep = d[d['toy'] == int(t)]
+    return keep[[n for n in keep.dtype.names if n != 'toy']].copy()

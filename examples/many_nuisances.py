@@ -1,7 +1,7 @@
 """A binned likelihood with many nuisance shape parameters, each moving one source -- run as
 
     PYTHONPATH=. python examples/many_nuisances.py [--bins 20] [--scan 33] [--toys 200] [--asimov] [--band] [--posterior] [--grid]
-        [--unbinned | --measure-unbinned | --measure-unbinned-hessian]
+        [--unbinned | --unbinned-toys | --measure-unbinned | --measure-unbinned-hessian | --measure-unbinned-toys]
         [--measure | --measure-toys | --measure-asimov | --measure-coarse | --measure-coarse-jacobian | --measure-sampler [--rounds 31]]
 
 Eight shape parameters with five anchors each and four sources that respond to two of them each.  On one tensor-product
@@ -89,6 +89,14 @@ bi_score_events on the expanded templates; the lines go to profiles/sourcewise_e
 --measure-unbinned-hessian times, at the same shape and numbers of events, bi_eval_sourcewise_events_hess against the one bi_eval_factored
 gradient call over the (2 F + 1) P points it replaces and against bi_eval_hess on the expanded unbinned grid model, and the kernels alone by
 device events; the lines go to profiles/sourcewise_events_curv_measure.txt too.
+
+--unbinned-toys draws a small ensemble of event-level toys of the twelve-nuisance model (twelve shape parameters of five anchors, six
+histogram sources: no grid model exists) on the device, fits all of them, and prints the toy-calibrated critical value of an upper
+limit on one rate multiplier beside Wilks' (sourcewise_event_toys, inference.bestfit_toys, inference.neyman_thresholds).
+
+--measure-unbinned-toys times, at the measured source-wise shape, bi_sourcewise_simulate_event_toys (256 toys of 10^4 expected events,
+one toy of 10^6) against bi_simulate_event_toys on the expanded 5^4 grid model and against the host route, and the device time of
+the call's four parts; the lines go to profiles/sourcewise_event_toys_measure.txt too.
 """
 import argparse
 import time
@@ -118,6 +126,10 @@ ap.add_argument('--measure-unbinned', action='store_true',
                 help='time bi_eval_factored on the event store against the expanded unbinned grid model, and the two scoring calls')
 ap.add_argument('--measure-unbinned-hessian', action='store_true',
                 help='time bi_eval_sourcewise_events_hess against the gradient differences it replaces and bi_eval_hess on the expanded unbinned grid model')
+ap.add_argument('--unbinned-toys', action='store_true',
+                help='draw and fit a small ensemble of event-level toys of the twelve-nuisance model: a toy-calibrated threshold beside Wilks\'')
+ap.add_argument('--measure-unbinned-toys', action='store_true',
+                help='time bi_sourcewise_simulate_event_toys against the expanded grid model\'s generator and the host route')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -1302,6 +1314,152 @@ def measure_unbinned():
     tp.close()
 
 
+def unbinned_toys():
+    """Twelve nuisances of five anchors (5^12 grid anchors: no grid model) and six rate multipliers over events: a small ensemble of
+    event-level toys drawn on the device and fitted, and the toy-calibrated critical value of the signal's upper limit beside Wilks'"""
+    from scipy import stats
+    from blueice_amd import GaussianPrior, SourceWiseUnbinnedLogLikelihood, inference, sourcewise_event_toys, sourcewise_simulated_events
+    from blueice_amd.synthetic import NuisanceHistogramSource, many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins), n_params=12, n_sources=6, own_per_source=2, events_per_day=40.,
+                                             source_class=NuisanceHistogramSource)
+    lf = SourceWiseUnbinnedLogLikelihood(conf)
+    for s in range(6):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    t0 = time.perf_counter()
+    lf.prepare()
+    print('(1) prepare(): %d shape parameters x 5 anchors, 6 histogram sources of two own parameters: %d density histograms, %.2f s'
+          % (len(names), sum(5 ** len(o) for o in own), time.perf_counter() - t0))
+    n_toys = max(8, args.toys // 5)
+    t0 = time.perf_counter()
+    counts = sourcewise_event_toys(lf, n_toys, seed=5, np3=0.5)
+    dt = time.perf_counter() - t0
+    d0 = sourcewise_simulated_events(lf, 0)
+    print('(2) sourcewise_event_toys: %d toys of %.0f events on average drawn and scored on the device in %.4f s (store %.2f MB); toy 0 has %d events, '
+          '%s per source' % (n_toys, counts.sum(axis=1).mean(), dt, lf.ctx.get_param('sourcewise_events_bytes') / 1e6, len(d0), counts[0].tolist()))
+    t0 = time.perf_counter()
+    best, ll = inference.bestfit_toys(lf)
+    # (s3 is the one source alone at its centre: s0 and s4, s1 and s5 share theirs and are all but degenerate pairs)
+    print('    bestfit_toys: %d parameters floating in each of %d fits, %.3f s; s3_rate_multiplier %.3f +- %.3f over the ensemble (truth 1)'
+          % (len(best), n_toys, time.perf_counter() - t0, best['s3_rate_multiplier'].mean(), best['s3_rate_multiplier'].std()))
+    hyp = np.array([0.8, 1.0, 1.2])
+    t0 = time.perf_counter()
+    table = inference.neyman_thresholds(lf, 's3_rate_multiplier', hyp, n_toys, kind='upper', seed=6, chunk=2 * n_toys)
+    level = 1 - 1.0 / n_toys if n_toys < 10 else 0.9
+    crit = table.critical_values(level)
+    print('(3) neyman_thresholds: %d hypotheses x %d toys, two fits per toy, %.3f s' % (len(hyp), n_toys, time.perf_counter() - t0))
+    print('    critical value of t at the %.0f %% level (kind upper):  ' % (100 * level)
+          + ', '.join('s3 = %.1f: %.3f' % (h, c) for h, c in zip(hyp, crit)) + ';   Wilks: %.3f' % stats.norm.ppf(level) ** 2)
+    lf.ctx.close()
+
+
+def measure_unbinned_toys():
+    """bi_sourcewise_simulate_event_toys against the two routes that existed: bi_simulate_event_toys on the same model expanded to the
+    5^4 unbinned grid model (2500 rows per event where the source-wise store holds 20), and the host route (draw every toy with NumPy
+    from the morphed histograms as HistogramPdfSource.simulate does, then score all sets with bi_sourcewise_score_events, as
+    base_model.simulate() + set_datasets do).  256 toys of 10^4 expected events and one toy of 10^6, one truth; alternated calls,
+    medians with quartiles, and the device time of the call's four parts from the library's own events.  Written to
+    profiles/sourcewise_event_toys_measure.txt as well."""
+    import os
+    from blueice_amd.device import DeviceContext
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a, nb = 5, args.measure_bins
+    B = nb ** 3
+    rng = np.random.default_rng(11)
+    g = np.linspace(-2., 2., n_a)
+    rows = rng.random((S, n_a, B)) + 0.05                                         # densities over the unit cube
+    rows *= B / rows.sum(axis=-1, keepdims=True)
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    fac = SourceWiseContext(0)
+    say('# examples/many_nuisances.py --measure-unbinned-toys --measure-bins %d --rounds %d on %s' % (nb, args.rounds, fac.info()['arch']))
+    say('# d = %d, S = %d, one own axis per source (class <4, 1>), %d anchors, density histograms of %d^3 bins, \'linear\' lookup, one truth' % (d, S, n_a, nb))
+    edges = [np.linspace(0., 1., nb + 1)] * 3
+    centres = [0.5 * (e[:-1] + e[1:]) for e in edges]
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])                   # relative rates (10 in all); the scale is per call
+    tp = DeviceContext(0)
+    tp.begin_model([g] * d, S, B)
+    for lin, idx in enumerate(np.ndindex(*(n_a,) * d)):          # the same likelihood on the product grid: source s from ITS anchor
+        tp.set_anchor(lin, np.stack([rows[s, idx[s]] for s in range(S)]), np.array([mus[s, idx[s]] for s in range(S)]))
+    tp.end_model()
+    fac.begin_model([g] * d, S, B, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, rows[s, a], mus[s, a])
+    fac.end_model()
+    z = np.array([0.3, -1.2, 0.7, 1.6])
+
+    def host_route(T, scale, seed):
+        """what base_model.simulate() + set_datasets do, T times: Poisson numbers, bins by the running sums of the morphed pmf,
+        uniform positions (NumPy), then one device scoring of all sets"""
+        gen = np.random.default_rng(seed)
+        k = np.clip(np.searchsorted(g, z, side='right') - 1, 0, n_a - 2)
+        t = (z - g[k]) / (g[k + 1] - g[k])
+        cdf = [np.cumsum((1 - t[s]) * rows[s, k[s]] + t[s] * rows[s, k[s] + 1]) for s in range(S)]
+        rate = [((1 - t[s]) * mus[s, k[s]] + t[s] * mus[s, k[s] + 1]) * scale[s] for s in range(S)]
+        sets = []
+        for _ in range(T):
+            bins = np.concatenate([np.searchsorted(cdf[s], gen.random(gen.poisson(rate[s])) * cdf[s][-1], side='right') for s in range(S)])
+            idx = np.unravel_index(np.minimum(bins, B - 1), (nb,) * 3)
+            sets.append([np.clip(e[i] + gen.random(len(bins)) * (e[i + 1] - e[i]), c[0], c[-1]) for e, i, c in zip(edges, idx, centres)])
+        fac.score_events('linear', centres, sets, 1e-12)
+
+    for T, events in ((256, 1e4), (1, 1e6)):
+        scale = np.full(S, events / 10.0)
+        full = DeviceContext(0)
+        calls = [('device', lambda: fac.simulate_event_toys('linear', edges, z[None], scale[None], [T], 7, 1e-12)),
+                 ('grid', lambda: tp.simulate_event_toys(full, 'linear', edges, z, scale, T, 7, 1e-12)),
+                 ('host', lambda: host_route(T, scale, 7))]
+        n_sw, n_grid = calls[0][1](), calls[1][1]()
+        same = np.array_equal(n_sw, n_grid) and np.array_equal(fac.download_events()[0], full.download_events()[0])
+        times = {name: [] for name, _ in calls}
+        for rnd in range(2 + args.rounds):              # two warm-up rounds; the calls alternate inside every round
+            for name, call in calls:
+                t0 = time.perf_counter()
+                call()
+                if rnd >= 2:
+                    times[name].append(time.perf_counter() - t0)
+        say('%3d toys of %.0e expected events (%d drawn): bi_sourcewise_simulate_event_toys (store: 20 rows, %.1f MB) %s   bi_simulate_event_toys on the '
+            '5^%d grid model (2500 rows, %.1f MB) %s   host route (NumPy draws + bi_sourcewise_score_events) %s'
+            % (T, events, n_sw.sum(), S * n_a * 8 * np.maximum(512, (n_sw.sum(axis=1) + 511) // 512 * 512).sum() / 1e6, quartiles(times['device']), d,
+               n_a ** d * S * 8 * n_sw.sum() / 1e6, quartiles(times['grid']), quartiles(times['host'])))
+        say('%3d toys of %.0e: grid model / source-wise %.2f, host route / source-wise %.2f; the events of the two device routes are equal bit for bit: %s'
+            % (T, events, np.median(times['grid']) / np.median(times['device']), np.median(times['host']) / np.median(times['device']), same))
+        fac._dev.profile(True)
+        parts = {k: [] for k in ('layout', 'pmf', 'events', 'score')}
+        for _ in range(args.rounds):
+            calls[0][1]()
+            for k in parts:
+                parts[k].append(fac.get_param('sim_ns_' + k) * 1e-9)
+            fac._dev.profile_read()
+        fac._dev.profile(False)
+        say('%3d toys of %.0e, device time of the call\'s parts: counts + layout %s   pmf rows + running sums (k_sourcewise_pmf, %d scans) %s   '
+            'event kernel %s   scoring (k_score_locate, k_score_rows, k_fill_columns; with the host\'s gaps between them) %s'
+            % (T, events, quartiles(parts['layout']), S, quartiles(parts['pmf']), quartiles(parts['events']), quartiles(parts['score'])))
+        full.close()
+    say('# cache-assisted: the pmf and cdf rows of the truth (2 x %d x %.0f MB) and the %d rows the scoring gathers from (%.0f MB) stay in the 256 MiB '
+        'Infinity Cache between the rounds, as does the store of the 256 toys; the grid model gathers from %.0f GB of templates, which do not'
+        % (S, B * 8 / 1e6, S * n_a, S * n_a * B * 8 / 1e6, n_a ** d * S * B * 8 / 1e9))
+    say('# not measured: every class but <4, 1>, H > 1 truths (sub-batches), \'piecewise\' scoring, the fits on the toys, other shapes')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_event_toys_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+    fac.close()
+    tp.close()
+
+
+if args.unbinned_toys:
+    unbinned_toys()
+    raise SystemExit(0)
+if args.measure_unbinned_toys:
+    measure_unbinned_toys()
+    raise SystemExit(0)
 if args.unbinned:
     unbinned()
     raise SystemExit(0)

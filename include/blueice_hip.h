@@ -887,6 +887,34 @@ int bi_sourcewise_drop_events(bi_ctx* ctx);
 int bi_sourcewise_event_set_counts(bi_ctx* ctx, int64_t* counts);
 int bi_sourcewise_download_event_set(bi_ctx* ctx, int64_t t, double* out);
 
+/* ... and event-level toys drawn on the device: T = sum_h n_toys[h] toys at H truths (z [H][d], rate_scale [H][S] or NULL),
+ * truth-major, scored into the event store above.  The toys become the context's T event sets in that store's layout (every set
+ * padded to whole tiles and to at least one, the padding zero and masked by index), so bi_eval_factored,
+ * bi_fit_batched_factored and bi_eval_sourcewise_events_hess run on them as on any store.  The model must be a finished
+ * source-wise model whose rows are density histograms over `edges` (bi_sourcewise_score_events' condition); method 0
+ * 'piecewise' / 1 'linear' is the lookup that scores the events (1 needs three edges per axis).
+ * The stream is bi_simulate_event_toys': toy t of the call is toy D = toy_offset + t of the seed's ensemble, keyed by
+ * toy_seed(seed, D) -- for T = 1 too; per source N_s ~ Poisson(r_s) with r_s = M_s(z_h) rs_s interpolated over the source's own
+ * axes; each event's bin by bisection in the running sums of pmf_s,b = max(tau_s,b(z_h), 0) vol_b (tau_s the source-wise fma
+ * chain over the source's own corner rows), its position inside the bin from one uniform per axis; events in drawn order, source
+ * by source, positions unclipped (a 'linear' lookup clips only when it scores).  A toy therefore does not depend on T, on the
+ * launch geometry, on how truths are grouped into calls (with toy_offset advanced) or on the sub-batches of truths the call works
+ * in (parameter sim_truth_chunk), and where no comparison is a near-tie it is event for event the toy bi_simulate_event_toys
+ * draws from the expanded grid model.
+ *   n_per_toy_source [T][S] (nullable)        the events of every (toy, source); written on success only
+ *   bi_sourcewise_simulated_event_count       the events of the resident toys in all, -1 without any
+ *   bi_sourcewise_download_events             coords [k][N], source [N] (either nullable): the events without the padding, set by
+ *                                             set.  They belong to the simulated store: bi_sourcewise_drop_events and any later
+ *                                             store release them, after which the call is BI_ERR_STATE
+ * Everything is validated before the previous store is touched (BI_ERR_INVALID: the method, the axes, edges that do not
+ * describe B bins, H < 1, a negative n_toys, T < 1 or T >= 2^31, toy numbers beyond 2^48, a truth outside the anchor box, a rate
+ * outside [0, 2^30), a store beyond compact_budget); after a device error the context holds no store. */
+int bi_sourcewise_simulate_event_toys(bi_ctx* ctx, int method, int k, const int32_t* n_edges, const double* edges, int64_t H,
+                                      const double* z, const double* rate_scale, const int64_t* n_toys, uint64_t seed,
+                                      double outlier_likelihood, int64_t* n_per_toy_source);
+int64_t bi_sourcewise_simulated_event_count(const bi_ctx* ctx);
+int bi_sourcewise_download_events(bi_ctx* ctx, double* coords, int32_t* source);
+
 /* ... and its analytic Hessian: bi_eval_sourcewise_hess' contract on the event store.  theta = (z, rs), F = d + S.  The event
  * likelihood is the binned observed form with n = 1 per event, no lgamma and N_s = 1; beside the sums above the kernel
  * (k_sourcewise_events_curv, in the Gram panels of the binned curvature kernel) forms per event chi_s,jk = sum_c d_j d_k w_c p_s,c,e
@@ -1191,6 +1219,11 @@ int bi_profile_read(bi_ctx* ctx, int64_t* n_launches, double* total_ms);
  *                     matrix-core launches (3: both); bi_profile_read sums what was timed
  *   toy_offset        bi_generate_toys: toy t of a call is dataset toy_offset + t of the seed's random stream, so ranks
  *                     that each generate a range of one toy-MC ensemble draw the same toys as one process would (0)
+ *   sim_truth_chunk   bi_sourcewise_simulate_event_toys: truths per sub-batch of the pmf rows, their running sums and the event
+ *                     kernel; 0 (default) = as many as 256 MiB of scratch hold at 16 S B bytes per truth.  The toys do not
+ *                     depend on it: it places the seam between sub-batches (tests).  Read-only sim_ns_layout, sim_ns_pmf,
+ *                     sim_ns_events, sim_ns_score: while profiling (bi_profile_enable), the device time in ns of the last call's
+ *                     counts + layout, pmf rows + running sums, event kernel and scoring; 0 otherwise
  *   scan_pow          scans over dense data on the matrix cores run on a copy of the template rows whose bins are ordered by
  *                     their count (one dataset, within compact_budget; built on first use per data upload): a lane's bins then
  *                     carry one count n, and sum n log mu over them is n log of their product -- one logarithm per lane, work
