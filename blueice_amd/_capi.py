@@ -121,6 +121,11 @@ SIGNATURES = {
     'bi_sourcewise_simulated_event_count': (_i64, [_p]),
     'bi_sourcewise_download_events': (C.c_int, [_p, _p, _p]),
     'bi_eval_sourcewise_events_hess': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'bi_eval_sourcewise_events_planned': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p]),
+    'bi_sample_stretch_sourcewise_events': (C.c_int, [_p, _i64, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_double, C.c_uint64,
+                                                      _i64, _p, _p, _p, _p, _p, _p, _p]),
+    'bi_grid_reduce_sourcewise_events': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, _p, _p,
+                                                   _p]),
     'bi_grid_reduce': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p]),
     'bi_eval_sourcewise_scan': (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _p]),
     'bi_grid_reduce_sourcewise': (C.c_int, [_p, _i64, _p, C.c_int, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, C.c_int, _p, _p, _p, _p]),

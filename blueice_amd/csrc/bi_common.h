@@ -148,6 +148,9 @@ int launch_sourcewise_plan(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
 // ... k_sourcewise_plan<SC, NE = true>: the same for k_sourcewise_nonempty (rows, counts and tiles of the dataset's compacted copy,
 // slot_lg = sum_s lambda_s + lgsum; a.g.rowsum and a.g.ne_* set)
 int launch_sourcewise_plan_nonempty(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
+// ... k_sourcewise_plan<SC, false, EV = true>: the same for k_sourcewise_events (rows at the event set's columns, the set's number
+// of events and tiles, slot_lg = sum_s r_s; a.ev_first, a.ev_n, a.ev_cols set, a.g.T the number of sets; a rejected point: tiles 0)
+int launch_sourcewise_plan_events(bi_ctx* c, int SC, const SourcewisePlanArgs& a);
 // k_sourcewise_nonempty<SC, EM, GRAD>: the sums of one point of a source-wise model over the non-empty bins of its dataset per item;
 // classes and result slots (factored_slots) as launch_morph_factored.  grid.x: the largest block count of the launch's items
 int launch_sourcewise_nonempty(bi_ctx* c, int SC, int EM, bool grad, const SourcewiseNonemptyArgs& a, dim3 grid);

@@ -190,6 +190,10 @@ struct bi_ctx {
         std::vector<int64_t> ev_first, ev_n;
         std::vector<char> ev_row_set;                // [rows] the row has been uploaded (bi_sourcewise_events_set_row)
         DevBuf ev_ps;
+        // ev_tab: ev_first and ev_n back to back [2][ev_T] for the device planner's event variant (bi_sourcewise_plan.h), uploaded
+        // when the store is finished (events_finish) and released with it.  ev_max_nbx: the most blocks an item of any set takes.
+        DevBuf ev_tab;
+        int ev_max_nbx = 1;
         // the events of a store drawn on the device (bi_sourcewise_simulate_event_toys; bi_sourcewise_sim.h): coordinates
         // [sim_k][ev_cols] and the source of every column (-1: padding) in the store's padded layout, sim_n events in all.  They
         // belong to that store: whatever releases or replaces it releases them (fac_drop_events).  sim_n < 0: none

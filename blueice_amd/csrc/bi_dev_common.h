@@ -209,7 +209,11 @@ struct SourcewisePlanArgs {
     double* slot_lg;           // [n]
     int64_t* perm;             // [n] k_finish's: i, or -1 for a rejected point (neither summed nor written)
     double* out;               // [n] where k_finish writes the results: the planner writes a rejected point's -inf
-    int32_t* tiles;            // [n] (NE alone) the 512-bin tiles of the item's dataset's list
+    int32_t* tiles;            // [n] (NE, EV) the 512-bin tiles of the item's dataset's list / of its event set
+    // k_sourcewise_plan<SC, false, EV = true> alone (the event store, bi_sourcewise_events.h); g.T is the number of event sets there
+    const int64_t* ev_first;   // [T] the set's first column
+    const int64_t* ev_n;       // [T] its number of events
+    int64_t ev_cols;           // columns of every row of the store
 };
 
 // k_sourcewise_nonempty (bi_k_sourcewise_nonempty.h): FactoredArgs' descriptors over the compacted copies of the non-empty bins.

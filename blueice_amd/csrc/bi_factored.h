@@ -168,6 +168,8 @@ void fac_drop_events(bi_ctx::Factored& m) {
     m.ev_outlier = 0.0;
     m.ev_first.clear(); m.ev_n.clear(); m.ev_row_set.clear();
     dev_free(m.ev_ps);
+    dev_free(m.ev_tab);
+    m.ev_max_nbx = 1;
     dev_free(m.sim_coords); dev_free(m.sim_source);      // (the events a simulated store was scored from)
     m.sim_k = 0;
     m.sim_n = -1;

@@ -135,10 +135,10 @@ struct GridStepSourcewise {
     PlannedItems points;
     ScanItems scan;
     bool ready = false;
-    GridStepSourcewise(bi_ctx* ctx, int r) : c(ctx), route(r), points(ctx), scan(ctx) {}
+    const char* who;
+    GridStepSourcewise(bi_ctx* ctx, int r, const char* w = "bi_grid_reduce_sourcewise") : c(ctx), route(r), points(ctx), scan(ctx), who(w) {}
 
     int operator()(ResidentPoints& pts, int64_t n, int64_t* counters, const GridFold& fold) {
-        const char* who = "bi_grid_reduce_sourcewise";
         int rc;
         if (!ready && (rc = route == 1 ? scan.init(n) : points.init(n))) return rc;
         ready = true;
@@ -254,6 +254,37 @@ int bi_grid_reduce_sourcewise(bi_ctx* c, int64_t E, const int64_t* dataset, int 
     HIP_TRY(c, hipSetDevice(c->device));
     try {
         GridStepSourcewise step(c, route);
+        rc = grid_reduce(c, who, c->fac.d, c->fac.S, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk,
+                         log_marginal, profile, argmax, counters, step);
+        if (rc) (void)hipStreamSynchronize(c->stream);          // (the step's buffers go with the scope)
+        if (counters) counters[4] = route;
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "%s: out of host memory", who);
+    }
+}
+
+// ... on the event store (bi_sourcewise_events.h): the same loop, PlannedItems in its event mode
+int bi_grid_reduce_sourcewise_events(bi_ctx* c, int64_t E, const int64_t* dataset, int F, int n_keep, const int32_t* var_kind,
+                                     const int32_t* var_index, const double* z0, const double* scale0, const double* unit, const int32_t* n_nodes,
+                                     const double* nodes, const double* term, const double* logw, int64_t chunk, int route, double* log_marginal,
+                                     double* profile, int64_t* argmax, int64_t* counters) {
+    const char* who = "bi_grid_reduce_sourcewise_events";
+    int rc = events_routes_check(c, who, "bi_grid_reduce_sourcewise");
+    if (rc) return rc;
+    GridArgs a{};
+    int64_t n_total = 0;
+    if ((rc = grid_check_args(c, who, c->fac.d, c->fac.S, E, F, n_keep, var_kind, var_index, z0, scale0, unit, n_nodes, nodes, term, logw, chunk,
+                              log_marginal, profile, argmax, a, n_total)) ||
+        (rc = check_entry_datasets(c, who, "entry", E, dataset, c->fac.ev_T)))
+        return rc;
+    if (route < -1 || route > 1) return fail(c, BI_ERR_INVALID, "%s: route is -1 (the route this store is evaluated on: 0), 0 (points) or 1 (scan), not %d", who, route);
+    if (route == 1)
+        return fail(c, BI_ERR_INVALID, "%s: route 1 is not available: the matrix-core scan route does not read the event store (route 0 or -1)", who);
+    route = 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    try {
+        GridStepSourcewise step(c, route, who);
         rc = grid_reduce(c, who, c->fac.d, c->fac.S, E, dataset, a, n_total, var_kind, var_index, z0, scale0, unit, nodes, term, logw, chunk,
                          log_marginal, profile, argmax, counters, step);
         if (rc) (void)hipStreamSynchronize(c->stream);          // (the step's buffers go with the scope)

@@ -45,9 +45,17 @@ __device__ __forceinline__ void plan_find_cell(const double* __restrict__ g, int
 //     N_s      = sum_c w_c R_{s,c}, one fma per corner from 0.0;   lambda_s = r_s N_s
 //     slot_lg  = (sum_s lambda_s, sources ascending from 0.0) + lgsum[ds]
 // (the lane of source slot s computes lambda_s, lane 0 collects them in order).  NE = false is the code it was.
-template <int SC, bool NE = false>
+//
+// EV = true (with NE = false): the descriptors of k_sourcewise_events instead (the event store, bi_sourcewise_events.h), bit for
+// bit FacBatch::fill's with events = true; a.g.T is the number of event sets:
+//     rowoff   = ev_first[ds] + row ev_cols,   cnt_off = ev_n[ds] (the kernel's item_n),   tiles = max(1, ceil(ev_n[ds] / 512))
+//     slot_lg  = sum_s r_s, sources ascending from 0.0, one rounded addition each (the slot lanes hand r_s to lane 0)
+// No lgamma, no rowsum.  The event kernel reads no live word: a rejected point gets tiles = 0, with which every block of its item
+// posts +0.0 and returns at entry.  EV = false is the code it was.
+template <int SC, bool NE = false, bool EV = false>
 __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePlanArgs a) {
     static_assert(SC == 2 || SC == 4 || SC == 8, "the source slots of a point share a wave");
+    static_assert(!(NE && EV), "the non-empty-bin form and the event store are two forms of the data");
     const int64_t gid = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     const int64_t i = gid / SC;
     const int s = (int)(gid % SC);
@@ -77,6 +85,13 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
         const int64_t t = (ds < 0 || ds >= m.T) ? 0 : ds;      // (a rejected point: in-range descriptors that never run)
         ne_off = m.ne_off[t];
         ne_np = m.ne_np[t];
+    }
+    [[maybe_unused]] int64_t ev_first = 0, ev_n = 0;
+    if constexpr (EV) {
+        const int64_t ds = a.ds[i];
+        const int64_t t = (ds < 0 || ds >= m.T) ? 0 : ds;      // (a rejected point: in-range descriptors that never run)
+        ev_first = a.ev_first[t];
+        ev_n = a.ev_n[t];
     }
     if (real) {
         int64_t base = m.row_first[s];
@@ -114,6 +129,8 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
                 if constexpr (NE) {
                     a.rowoff[row] = ne_off + r * ne_np;
                     N = __fma_rn(wc, m.rowsum[r], N);
+                } else if constexpr (EV) {
+                    a.rowoff[row] = ev_first + r * a.ev_cols;
                 } else {
                     a.rowoff[row] = r * m.Bp;
                 }
@@ -135,6 +152,10 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
 #pragma unroll
         for (int q = 0; q < SC; ++q) lam_sum = __dadd_rn(lam_sum, __shfl(lambda, q, SC));      // (a padded slot adds +0.0)
     }
+    if constexpr (EV) {
+#pragma unroll
+        for (int q = 0; q < SC; ++q) lam_sum = __dadd_rn(lam_sum, __shfl(rate, q, SC));        // (a padded slot adds +0.0)
+    }
     if (s == 0) {
         const int64_t ds = a.ds[i];
         const int32_t status = (ds < 0 || ds >= m.T) ? BI_ST_BAD_DATASET
@@ -147,6 +168,10 @@ __global__ __launch_bounds__(kThreads) void k_sourcewise_plan(const SourcewisePl
             a.cnt_off[i] = status == 0 ? m.ne_cnt_off[ds] : 0;
             a.slot_lg[i] = status == 0 ? __dadd_rn(lam_sum, m.lgsum[ds]) : 0.0;
             a.tiles[i] = (int32_t)(ne_np / kTile);
+        } else if constexpr (EV) {
+            a.cnt_off[i] = status == 0 ? ev_n : 0;
+            a.slot_lg[i] = status == 0 ? lam_sum : 0.0;
+            a.tiles[i] = status != 0 ? 0 : ev_n > kTile ? (int32_t)((ev_n + kTile - 1) / kTile) : 1;
         } else {
             a.cnt_off[i] = status == 0 ? ds * m.Bp : 0;
             a.slot_lg[i] = status == 0 ? m.lgsum[ds] : 0.0;

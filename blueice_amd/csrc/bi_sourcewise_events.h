@@ -139,11 +139,31 @@ int events_score_columns(bi_ctx* c, const char* who, int method, int k, const Ax
     return BI_OK;
 }
 
-// the fresh store of events_create is complete
-void events_close(bi_ctx::Factored& m) {
-    std::fill(m.ev_row_set.begin(), m.ev_row_set.end(), 1);
+// The store is complete: the device planner's table of the sets (ev_first, ev_n: k_sourcewise_plan's event variant,
+// bi_sourcewise_plan.h) and the most blocks an item of any set takes, then ev_ready.  Waits for the copy; on an error the store
+// stays as it was (open).
+int events_finish(bi_ctx* c, const char* who) {
+    bi_ctx::Factored& m = c->fac;
+    std::vector<int64_t> tab(m.ev_first);
+    tab.insert(tab.end(), m.ev_n.begin(), m.ev_n.end());
+    int64_t max_tiles = 1;
+    for (int64_t n : m.ev_n) max_tiles = std::max(max_tiles, (n + kTile - 1) / kTile);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = dev_upload(c, m.ev_tab, tab);
+    if (rc) return rc;
+    const hipError_t e = hipStreamSynchronize(c->stream);      // (tab is pageable and leaves with the scope)
+    if (e != hipSuccess) return fail(c, BI_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    m.ev_max_nbx = (int)std::min<int64_t>(max_tiles, kFacBlocks);
     m.ev_open = false;
     m.ev_ready = true;
+    return BI_OK;
+}
+// ... of the fresh store of events_create, every row filled by the scoring kernels; after an error the context holds no store
+int events_close(bi_ctx* c, const char* who) {
+    std::fill(c->fac.ev_row_set.begin(), c->fac.ev_row_set.end(), 1);
+    const int rc = events_finish(c, who);
+    if (rc) fac_drop_events(c->fac);
+    return rc;
 }
 
 int sourcewise_score_events(bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t T, const int64_t* offsets,
@@ -192,8 +212,7 @@ int sourcewise_score_events(bi_ctx* c, int method, int k, const int32_t* n_grid,
         // (the caller's events are clipped already: bi_score_events' contract)
         if ((rc = events_score_columns(c, who, method, k, ax, grid, (const double*)d_ev.p, 0))) return rc;
     }
-    events_close(m);
-    return BI_OK;
+    return events_close(c, who);
 }
 
 }  // namespace
@@ -250,9 +269,7 @@ int bi_sourcewise_events_end(bi_ctx* c) {
         for (int64_t r = m.row_first[(size_t)s]; r < m.row_first[(size_t)s + 1]; ++r)
             if (!m.ev_row_set[(size_t)r])
                 return fail(c, BI_ERR_STATE, "%s: anchor %lld of source %d was never set", who, (long long)(r - m.row_first[(size_t)s]), s);
-    m.ev_open = false;
-    m.ev_ready = true;
-    return BI_OK;
+    return events_finish(c, who);
 }
 
 int bi_sourcewise_score_events(bi_ctx* c, int method, int k, const int32_t* n_grid, const double* grid, int64_t T, const int64_t* offsets,

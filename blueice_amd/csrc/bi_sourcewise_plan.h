@@ -14,6 +14,11 @@
 // variant -> k_sourcewise_nonempty -> k_finish: the descriptors point into the datasets' compacted copies, the tile count is per
 // item, and the grid's x is the most blocks an item of any dataset of the store takes -- known when the form is built, so still
 // nothing is read and nothing waited for.
+// On a finished event store (bi_sourcewise_events.h; bi_eval_sourcewise_events_planned, bi_sample_stretch_sourcewise_events, and
+// through bi_grid.h bi_grid_reduce_sourcewise_events) the queue runs the planner's EV variant -> k_sourcewise_events (values only)
+// -> k_finish: rows at the point's set's columns, the set's number of events and tiles per item, sum_s r_s for the finish, from the
+// device table of the sets (ev_tab, uploaded when the store is finished).  The event kernel reads no live word: a rejected point
+// gets zero tiles, so its blocks post +0.0 and return at entry.  The grid's x is the most blocks any set takes (ev_max_nbx).
 #pragma once
 
 namespace {
@@ -22,17 +27,21 @@ struct PlannedItems {
     bi_ctx* c;
     const bi_ctx::Factored& m;
     int SC, EM, W, NR;
+    bool ev;                    // the event store (bi_sourcewise_events.h): the planner's EV variant and k_sourcewise_events
     bool ne;                    // the non-empty-bin form (bi_sourcewise_nonempty.h): the planner's NE variant and k_sourcewise_nonempty
-    int nbx;                    // (ne: the most blocks an item of ANY dataset of the store takes -- known without a host read)
+    int nbx;                    // (ne, ev: the most blocks an item of ANY dataset of the store takes -- known without a host read)
     int64_t n_max = 0, per_call = 1;
     ScratchBuf status, live, rowoff, coef, rates, cnt_off, slot_lg, perm, partial, pflags, tiles;
     FactoredArgs fa{};
     SourcewiseNonemptyArgs na{};
+    SourcewiseEventsArgs ea{};
     SourcewisePlanArgs pa{};
 
+    // (a finished event store is what the context evaluates, as in FacBatch; only the entry points for it get here while one exists)
     explicit PlannedItems(bi_ctx* ctx)
         : c(ctx), m(ctx->fac), SC(m.S <= 2 ? 2 : m.S <= 4 ? 4 : 8), EM(std::max(1, m.max_own)), W(1 + EM), NR(m.n_rows_point),
-          ne(fac_nonempty_on(ctx)), nbx(ne ? m.ne_max_nbx : std::min((int)(m.Bp / kTile), kFacBlocks)) {}
+          ev(m.ev_ready), ne(!ev && fac_nonempty_on(ctx)),
+          nbx(ev ? m.ev_max_nbx : ne ? m.ne_max_nbx : std::min((int)(m.Bp / kTile), kFacBlocks)) {}
 
     // room for n_max items, both argument blocks; evaluate = false: the planner's buffers alone (queue() must not be called)
     int init(int64_t n, bool evaluate = true) {
@@ -46,7 +55,7 @@ struct PlannedItems {
             (rc = dev_alloc(c, slot_lg, un * sizeof(double))) || (rc = dev_alloc(c, perm, un * sizeof(int64_t))) ||
             (evaluate && ((rc = dev_alloc(c, partial, part * sizeof(double))) || (rc = dev_alloc(c, pflags, part * sizeof(unsigned))))))
             return rc;
-        if (ne && (rc = dev_alloc(c, tiles, un * sizeof(int32_t)))) return rc;
+        if ((ne || ev) && (rc = dev_alloc(c, tiles, un * sizeof(int32_t)))) return rc;
         fa = FacBatch(c, 0).args();
         const char* g = (const char*)m.geom.p;
         pa.g.anchors = (const double*)(g + m.geom_off[0]);
@@ -75,6 +84,19 @@ struct PlannedItems {
             na.max_blocks = kFacBlocks;
             for (int s = 0; s < 8; ++s) na.e[s] = fa.e[s];
         }
+        if (ev) {
+            pa.g.T = m.ev_T;
+            pa.ev_first = (const int64_t*)m.ev_tab.p;
+            pa.ev_n = pa.ev_first + m.ev_T;
+            pa.ev_cols = m.ev_cols;
+            pa.tiles = (int32_t*)tiles.p;
+            ea.ps = (const double*)m.ev_ps.p;
+            ea.outlier = m.ev_outlier;
+            ea.NR = NR;
+            ea.chunks = fa.chunks;
+            ea.max_blocks = kFacBlocks;
+            for (int s = 0; s < 8; ++s) ea.e[s] = fa.e[s];
+        }
         return BI_OK;
     }
 
@@ -83,7 +105,7 @@ struct PlannedItems {
     int queue(int64_t n, const double* z, const double* rs, const int64_t* ds, double* out, const char* who, int64_t* launches) {
         SourcewisePlanArgs p = pa;
         p.z = z; p.rs = rs; p.ds = ds; p.n = n; p.out = out;
-        int rc = ne ? launch_sourcewise_plan_nonempty(c, SC, p) : launch_sourcewise_plan(c, SC, p);
+        int rc = ev ? launch_sourcewise_plan_events(c, SC, p) : ne ? launch_sourcewise_plan_nonempty(c, SC, p) : launch_sourcewise_plan(c, SC, p);
         if (rc) return fail(c, rc, "%s: no planner variant for %d source slots", who, SC);
         HIP_TRY(c, hipGetLastError());
         int64_t queued = 1;
@@ -102,7 +124,13 @@ struct PlannedItems {
                 b.pflags = (unsigned*)pflags.p;
                 const dim3 grid((unsigned)nbx, (unsigned)ni);
                 c->last_morph_nbx = grid.x; c->last_morph_items = grid.y; c->last_morph_fused = 0;
-                if (ne) {
+                if (ev) {
+                    SourcewiseEventsArgs q = ea;
+                    q.rowoff = b.rowoff; q.coef = b.coef; q.rates = b.rates; q.item_n = b.item_cnt;
+                    q.item_tiles = (const int32_t*)tiles.p + i0;
+                    q.partial = b.partial; q.pflags = b.pflags;
+                    rc = launch_sourcewise_events(c, SC, EM, false, q, grid);
+                } else if (ne) {
                     SourcewiseNonemptyArgs q = na;
                     q.rowoff = b.rowoff; q.coef = b.coef; q.rates = b.rates; q.item_cnt = b.item_cnt; q.live = b.live;
                     q.item_tiles = (const int32_t*)tiles.p + i0;
@@ -123,12 +151,11 @@ struct PlannedItems {
     }
 };
 
-int sample_stretch_sourcewise(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+int sample_stretch_sourcewise(bi_ctx* c, const char* who, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                               const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                               const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, const double* prior_mean,
                               const double* prior_sigma, const double* prior_const, double* chain, double* ll, int64_t* n_accepted,
                               int64_t* counters) {
-    const char* who = "bi_sample_stretch_sourcewise";
     const size_t nE = (size_t)E, nW = (size_t)E * W;
     SamplerBuffers b;
     ResidentPoints pts;
@@ -228,15 +255,21 @@ int sample_stretch_sourcewise(bi_ctx* c, int64_t E, int W, int F, const int32_t*
     return BI_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bi_eval_sourcewise_planned(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
-                               int32_t* status) {
-    const char* who = "bi_eval_sourcewise_planned";
-    int rc = fac_check(c, who, true);
+// the event store's entry points: a finished store, else BI_ERR_STATE naming the binned spelling
+int events_routes_check(bi_ctx* c, const char* who, const char* binned) {
+    int rc = fac_check(c, who, false, true);
     if (rc) return rc;
+    if (c->fac.ev_open) return fail(c, BI_ERR_STATE, "%s: the event store is still being filled (bi_sourcewise_events_end first)", who);
+    if (!c->fac.ev_ready)
+        return fail(c, BI_ERR_STATE, "%s: the context holds no event store (bi_sourcewise_events_begin ... _end or bi_sourcewise_score_events "
+                    "first; against counts the call is %s)", who, binned);
+    return BI_OK;
+}
+
+// bi_eval_sourcewise_planned and bi_eval_sourcewise_events_planned behind their state checks
+int eval_sourcewise_planned(bi_ctx* c, const char* who, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                            int32_t* status) {
+    int rc;
     if (P < 0 || (P > 0 && !ll)) return fail(c, BI_ERR_INVALID, "%s: bad P / output pointer", who);
     const int d = c->fac.d, S = c->fac.S;
     if (d > 0 && P > 0 && !z) return fail(c, BI_ERR_INVALID, "%s: z is NULL", who);
@@ -268,6 +301,46 @@ int bi_eval_sourcewise_planned(bi_ctx* c, int64_t P, const double* z, const doub
     }
 }
 
+// bi_sample_stretch_sourcewise and bi_sample_stretch_sourcewise_events behind their state checks; T: the sets `dataset` indexes
+int sample_stretch_sourcewise_checked(bi_ctx* c, const char* who, int64_t T, int64_t E, int W, int F, const int32_t* var_kind,
+                                      const int32_t* var_index, const double* z0, const double* scale0, const double* unit, const int64_t* dataset,
+                                      const double* x0, const double* lo, const double* hi, int64_t n_steps, double a, uint64_t seed,
+                                      int64_t first_ensemble, const double* prior_mean, const double* prior_sigma, const double* prior_const,
+                                      double* chain, double* ll, int64_t* n_accepted, int64_t* counters) {
+    int rc;
+    if ((rc = stretch_check_args(c, who, who, c->fac.d, c->fac.S, T, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi,
+                                 n_steps, a, first_ensemble, prior_mean, prior_sigma, prior_const, chain, ll, n_accepted)))
+        return rc;
+    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = counters[4] = 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    try {
+        return sample_stretch_sourcewise(c, who, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble,
+                                         prior_mean, prior_sigma, prior_const, chain, ll, n_accepted, counters);
+    } catch (const std::bad_alloc&) {
+        return fail(c, BI_ERR_NOMEM, "%s: out of host memory", who);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bi_eval_sourcewise_planned(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                               int32_t* status) {
+    const char* who = "bi_eval_sourcewise_planned";
+    int rc = fac_check(c, who, true);
+    if (rc) return rc;
+    return eval_sourcewise_planned(c, who, P, z, rate_scale, dataset, ll, status);
+}
+
+int bi_eval_sourcewise_events_planned(bi_ctx* c, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
+                                      int32_t* status) {
+    const char* who = "bi_eval_sourcewise_events_planned";
+    int rc = events_routes_check(c, who, "bi_eval_sourcewise_planned");
+    if (rc) return rc;
+    return eval_sourcewise_planned(c, who, P, z, rate_scale, dataset, ll, status);
+}
+
 int bi_sample_stretch_sourcewise(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
                                  const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
                                  const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble, const double* prior_mean,
@@ -276,17 +349,20 @@ int bi_sample_stretch_sourcewise(bi_ctx* c, int64_t E, int W, int F, const int32
     const char* who = "bi_sample_stretch_sourcewise";
     int rc = fac_check(c, who, true);
     if (rc) return rc;
-    if ((rc = stretch_check_args(c, who, who, c->fac.d, c->fac.S, c->fac.T, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi,
-                                 n_steps, a, first_ensemble, prior_mean, prior_sigma, prior_const, chain, ll, n_accepted)))
-        return rc;
-    if (counters) counters[0] = counters[1] = counters[2] = counters[3] = counters[4] = 0;
-    HIP_TRY(c, hipSetDevice(c->device));
-    try {
-        return sample_stretch_sourcewise(c, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble,
-                                         prior_mean, prior_sigma, prior_const, chain, ll, n_accepted, counters);
-    } catch (const std::bad_alloc&) {
-        return fail(c, BI_ERR_NOMEM, "%s: out of host memory", who);
-    }
+    return sample_stretch_sourcewise_checked(c, who, c->fac.T, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed,
+                                             first_ensemble, prior_mean, prior_sigma, prior_const, chain, ll, n_accepted, counters);
+}
+
+int bi_sample_stretch_sourcewise_events(bi_ctx* c, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index, const double* z0,
+                                        const double* scale0, const double* unit, const int64_t* dataset, const double* x0, const double* lo,
+                                        const double* hi, int64_t n_steps, double a, uint64_t seed, int64_t first_ensemble,
+                                        const double* prior_mean, const double* prior_sigma, const double* prior_const, double* chain, double* ll,
+                                        int64_t* n_accepted, int64_t* counters) {
+    const char* who = "bi_sample_stretch_sourcewise_events";
+    int rc = events_routes_check(c, who, "bi_sample_stretch_sourcewise");
+    if (rc) return rc;
+    return sample_stretch_sourcewise_checked(c, who, c->fac.ev_T, E, W, F, var_kind, var_index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a,
+                                             seed, first_ensemble, prior_mean, prior_sigma, prior_const, chain, ll, n_accepted, counters);
 }
 
 }  // extern "C"

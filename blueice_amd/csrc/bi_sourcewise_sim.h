@@ -215,7 +215,7 @@ int sourcewise_simulate_event_toys(bi_ctx* c, int method, int k, const int32_t* 
         if ((rc = events_score_columns(c, who, method, k, gax, grid.data(), (const double*)coords.p, 1))) return give_up(rc);
     }
     sim_part_times(c, scope0, part);
-    events_close(m);
+    if ((rc = events_close(c, who))) return give_up(rc);
     m.sim_coords = coords;
     m.sim_source = source;
     m.sim_k = k;

@@ -107,7 +107,7 @@ void bi_destroy(bi_ctx* c) {
     dev_free(c->real_counts);
     dev_free(c->fac.ps); dev_free(c->fac.counts); dev_free(c->fac.real_counts); dev_free(c->fac.geom); dev_free(c->fac.lgsum_dev);
     dev_free(c->fac.ne_ps); dev_free(c->fac.ne_cnt); dev_free(c->fac.ne_tab);
-    dev_free(c->fac.ev_ps);
+    dev_free(c->fac.ev_ps); dev_free(c->fac.ev_tab);
     release_coarse(c);
     release_coarse(c->sw_coarse);
     if (c->slot_host) (void)hipHostFree(c->slot_host);

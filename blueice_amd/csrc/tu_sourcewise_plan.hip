@@ -15,6 +15,17 @@ int launch_sourcewise_plan(bi_ctx* c, int SC, const SourcewisePlanArgs& a) {
     return BI_ERR_INVALID;
 }
 
+int launch_sourcewise_plan_events(bi_ctx* c, int SC, const SourcewisePlanArgs& a) {
+    EventScope ev(c);
+    const dim3 grid((unsigned)((a.n * SC + kThreads - 1) / kThreads));
+    switch (SC) {
+        case 2: hipLaunchKernelGGL((k_sourcewise_plan<2, false, true>), grid, dim3(kThreads), 0, c->stream, a); return BI_OK;
+        case 4: hipLaunchKernelGGL((k_sourcewise_plan<4, false, true>), grid, dim3(kThreads), 0, c->stream, a); return BI_OK;
+        case 8: hipLaunchKernelGGL((k_sourcewise_plan<8, false, true>), grid, dim3(kThreads), 0, c->stream, a); return BI_OK;
+    }
+    return BI_ERR_INVALID;
+}
+
 int launch_sourcewise_plan_nonempty(bi_ctx* c, int SC, const SourcewisePlanArgs& a) {
     EventScope ev(c);
     const dim3 grid((unsigned)((a.n * SC + kThreads - 1) / kThreads));

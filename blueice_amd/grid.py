@@ -31,6 +31,14 @@ A prepared source-wise model (`SourceWiseBinnedLogLikelihood`) runs natively as 
 route `likelihood_config['sourcewise_grid_route']` names: 'points' (one work item per point, the kernels of `eval_points`),
 'scan' (the matrix-core scan route of `eval_points_scan`: needs the non-empty-bin form and at most 32 rows per point) or 'auto'
 (the default: see SOURCEWISE_AUTO_ROUTE).
+
+So does a prepared unbinned source-wise model with data set (`SourceWiseUnbinnedLogLikelihood`; bi_grid_reduce_sourcewise_events
+through the class's `_native_grid_reduce`, `ctx.grid_reduce_events`; `datasets=` indexes the event sets of `set_datasets` or of
+`sourcewise_event_toys*`).  The matrix-core scan route does not read the event store: 'auto' means 'points' there
+(SOURCEWISE_EVENTS_AUTO_ROUTE) and 'scan' raises ValueError.  No scan route over events exists.  The per-point route against the host
+engine (examples/many_nuisances.py --measure-unbinned-grid, profiles/sourcewise_events_scan_measure.txt, one MI355X, d = 4, S = 4, 5
+anchors, cache-assisted): 10^4 events, 975 975 grid points 58.0 ms against 183.3 ms (3.2 x); 10^6 events, 66 759 points 547.7 ms against
+557.7 ms (1.02 x: the event kernel is all of the time there).
 """
 import numpy as np
 
@@ -42,19 +50,23 @@ HOST_CHUNK = 1 << 16
 # what likelihood_config['sourcewise_grid_route'] = 'auto' asks the library for: -1 = the scan route where the model is eligible
 # (the non-empty-bin form built, at most 32 rows per point), else one work item per point
 SOURCEWISE_AUTO_ROUTE = -1
+SOURCEWISE_EVENTS_AUTO_ROUTE = 0        # ... on an event store: one work item per point, the only route that reads it
 _SOURCEWISE_ROUTES = {'auto': None, 'points': 0, 'scan': 1}
 
 
 def _sourcewise_route(lf):
     """-> the `route` of ctx.grid_reduce for a source-wise model (likelihood_config['sourcewise_grid_route']), None for any other"""
     from .source_wise import SourceWiseBinnedLogLikelihood
-    if not isinstance(lf, SourceWiseBinnedLogLikelihood):
+    from .source_wise_unbinned import SourceWiseUnbinnedLogLikelihood
+    if not isinstance(lf, (SourceWiseBinnedLogLikelihood, SourceWiseUnbinnedLogLikelihood)):
         return None
     setting = lf.config.get('sourcewise_grid_route', 'auto')
     if not isinstance(setting, str) or setting not in _SOURCEWISE_ROUTES:
         raise ValueError("likelihood_config['sourcewise_grid_route'] is 'auto', 'points' or 'scan', not %r" % (setting,))
     route = _SOURCEWISE_ROUTES[setting]
-    return SOURCEWISE_AUTO_ROUTE if route is None else route
+    if route is None:
+        return SOURCEWISE_EVENTS_AUTO_ROUTE if isinstance(lf, SourceWiseUnbinnedLogLikelihood) else SOURCEWISE_AUTO_ROUTE
+    return route
 
 
 def trapezoid_weights(x):
@@ -189,7 +201,8 @@ def _native_plan(lf, axes, fixed, livetime_days):
     between the parameters and the device call (the conditions of BatchObjective.native(), without its restriction on priors)."""
     from .likelihood import DeviceLogLikelihood, _prior_of
     from .profile import variable_map
-    ok = isinstance(lf, DeviceLogLikelihood) and getattr(lf, 'ctx', None) is not None and hasattr(lf.ctx, 'grid_reduce') and \
+    ok = isinstance(lf, DeviceLogLikelihood) and getattr(lf, 'ctx', None) is not None and \
+        (hasattr(lf, '_native_grid_reduce') or hasattr(lf.ctx, 'grid_reduce')) and \
         not any(getattr(lf, 'source_apply_efficiency', [])) and lf.config.get('unphysical_behaviour') != 'error'
     if not ok:
         return None
@@ -296,8 +309,9 @@ def grid_scan(lf, keep=(), reduce=(), weights='trapezoid', datasets=None, liveti
             full_logw = None if logw is None else [np.zeros(len(v)) for _, v in keep] + logw
             route = _sourcewise_route(lf)
             more = {} if route is None else {'route': route}
-            lm, prof, arg, counters = lf.ctx.grid_reduce(plan['kind'], plan['index'], plan['z0'], plan['scale0'], plan['unit'], datasets, n_keep,
-                                                         [v for _, v in axes], term=plan['term'], logw=full_logw, chunk=chunk or 0, **more)
+            reduce_call = getattr(lf, '_native_grid_reduce', None) or lf.ctx.grid_reduce
+            lm, prof, arg, counters = reduce_call(plan['kind'], plan['index'], plan['z0'], plan['scale0'], plan['unit'], datasets, n_keep,
+                                                  [v for _, v in axes], term=plan['term'], logw=full_logw, chunk=chunk or 0, **more)
             result = (lm.ravel() + plan['const'], prof.ravel() + plan['const'], arg.ravel(), counters)
             used = 'native'
         except PlannerRefused:

@@ -9,7 +9,9 @@ documented with `bi_sample_stretch` in include/blueice_hip.h):
     'native'   bi_sample_stretch: propose, evaluate, accept and the chain stay on the device; taken whenever nothing but
                the device call sits between the parameters and the likelihood (`BatchObjective.native()`); Gaussian
                constraints (`priors.GaussianPrior`) are added on the device (bi_sample_stretch_gauss); a source-wise model
-               (`SourceWiseBinnedLogLikelihood`) has bi_sample_stretch_sourcewise behind the same `ctx.sample_stretch`
+               (`SourceWiseBinnedLogLikelihood`) has bi_sample_stretch_sourcewise behind the same `ctx.sample_stretch`; an
+               unbinned one (`SourceWiseUnbinnedLogLikelihood`, taken by this function, not as a bound method) has
+               bi_sample_stretch_sourcewise_events, `ctx.sample_stretch_events`, through the class's `_native_sample_stretch`
     'host'     the restatement below in NumPy, one `lf.eval_points` call per half-step -- for likelihoods with other
                Python callables as priors, sums, re-parametrisations, efficiencies, unphysical_behaviour='error', and
                models whose batches the device planner refuses
@@ -165,8 +167,9 @@ def sample_posterior(lf, n_walkers=40, n_steps=200, a=2.0, seed=0, guess=None, p
             priors = None
             if np.any(np.isfinite(native['prior_sigma'])) or np.any(native['prior_const'] != 0):
                 priors = (native['prior_mean'], native['prior_sigma'], native['prior_const'])
-            result = lf.ctx.sample_stretch(W, native['kind'], native['index'], native['z0'], native['scale0'], native['unit'], datasets, x, lo, hi,
-                                           n_steps, a=a, seed=seed, first_ensemble=first_ensemble, priors=priors)
+            stretch = getattr(lf, '_native_sample_stretch', None) or lf.ctx.sample_stretch
+            result = stretch(W, native['kind'], native['index'], native['z0'], native['scale0'], native['unit'], datasets, x, lo, hi, n_steps,
+                             a=a, seed=seed, first_ensemble=first_ensemble, priors=priors)
             used = 'native'
         except PlannerRefused:
             if engine == 'native':

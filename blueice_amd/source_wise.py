@@ -371,6 +371,17 @@ class SourceWiseContext:
         dev._check(dev._lib.bi_eval_sourcewise_planned(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(status)))
         return ll, status
 
+    def eval_events_planned(self, z, rate_scale=None, dataset=None):
+        """`eval_planned` on the event store (bi_eval_sourcewise_events_planned: the planner's event variant, then the event kernel
+        of `eval`), `dataset` indexing the event sets -> (ll [P], status [P]), bit for bit `eval`'s on the store.  Without a
+        finished store the library refuses."""
+        dev = self._dev
+        P, z, rate_scale, dataset = self._point_args(z, rate_scale, dataset)
+        ll = np.empty(P, dtype=np.float64)
+        status = np.zeros(P, dtype=np.int32)
+        dev._check(dev._lib.bi_eval_sourcewise_events_planned(dev._h, P, ptr(z), ptr(rate_scale), ptr(dataset), ptr(ll), ptr(status)))
+        return ll, status
+
     def eval_scan(self, z, rate_scale=None, dataset=None):
         """`eval_planned` on the matrix-core scan route (bi_eval_sourcewise_scan): the points are sorted by (cell tuple, dataset)
         on the device and evaluated 16 at a time over the compacted rows of the non-empty-bin form, each group's rows read once
@@ -399,11 +410,33 @@ class SourceWiseContext:
         dev._check(rc)
         return out
 
+    def grid_reduce_events(self, kind, index, z0, scale0, unit, dataset, n_keep, nodes, term=None, logw=None, chunk=0, route=-1):
+        """bi_grid_reduce_sourcewise_events: `grid_reduce` on the event store, `dataset` indexing the event sets -- the same
+        arguments and return value.  The chunks are evaluated by the kernels of `eval_events_planned` (route 0; -1 takes it);
+        route 1 raises ValueError: the matrix-core scan route does not read the event store."""
+        dev = self._dev
+        rc, out = grid_reduce_call(dev._lib.bi_grid_reduce_sourcewise_events, 'bi_grid_reduce_sourcewise_events', dev._h, self.d, self.S, kind,
+                                   index, z0, scale0, unit, dataset, n_keep, nodes, term, logw, chunk, 5, extra=(int(route),))
+        dev._check(rc)
+        return out
+
     def sample_stretch(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0, priors=None):
         """bi_sample_stretch_sourcewise: DeviceContext.sample_stretch with the source-wise likelihood as the target -- the same
         arguments, random stream and return value (chain [n_steps, E, W, F], ll [n_steps, E, W], n_accepted [E, W], counters),
         `priors` included.  counters has five entries here: half-steps, evaluations, accepted moves, launches, and the stream
         synchronisations inside the step loop (0: the loop is queued without a host wait)."""
+        return self._sample_stretch(self._dev._lib.bi_sample_stretch_sourcewise, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a,
+                                    seed, first_ensemble, priors)
+
+    def sample_stretch_events(self, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a=2.0, seed=0, first_ensemble=0,
+                              priors=None):
+        """bi_sample_stretch_sourcewise_events: `sample_stretch` with the event store's likelihood as the target, `dataset`
+        indexing the event sets -- the same arguments, random stream and return value; the chain is bit for bit the host engine's
+        on the same store.  Without a finished store the library refuses."""
+        return self._sample_stretch(self._dev._lib.bi_sample_stretch_sourcewise_events, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi,
+                                    n_steps, a, seed, first_ensemble, priors)
+
+    def _sample_stretch(self, call, W, kind, index, z0, scale0, unit, dataset, x0, lo, hi, n_steps, a, seed, first_ensemble, priors):
         dev = self._dev
         x0 = np.ascontiguousarray(x0, dtype=np.float64)
         E, W2, F = x0.shape
@@ -428,10 +461,9 @@ class SourceWiseContext:
         mean = sigma = const = None
         if priors is not None:
             mean, sigma, const = dev._gauss_terms(priors, F, E)
-        dev._check(dev._lib.bi_sample_stretch_sourcewise(dev._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0), ptr(scale0), ptr(unit), ptr(dataset),
-                                                         ptr(x0), ptr(lo), ptr(hi), n_steps, float(a), int(seed) & (2 ** 64 - 1),
-                                                         int(first_ensemble), ptr(mean), ptr(sigma), ptr(const), ptr(chain), ptr(ll),
-                                                         ptr(n_acc), ptr(counters)))
+        dev._check(call(dev._h, E, int(W), F, ptr(kind), ptr(index), ptr(z0), ptr(scale0), ptr(unit), ptr(dataset), ptr(x0), ptr(lo), ptr(hi),
+                        n_steps, float(a), int(seed) & (2 ** 64 - 1), int(first_ensemble), ptr(mean), ptr(sigma), ptr(const), ptr(chain), ptr(ll),
+                        ptr(n_acc), ptr(counters)))
         return chain, ll, n_acc, counters
 
     def eval_grad(self, z, rate_scale=None, dataset=None):

@@ -8,6 +8,7 @@
     blueice_amd.inference.bestfit_toys(lf) over the sets of set_datasets, lf.n_events_per_dataset, and as a term of a LogLikelihoodSum
     sourcewise_event_toys(lf, n_toys, seed, **truth), sourcewise_event_toys_points(lf, points, n_toys, seed), sourcewise_simulated_events(lf),
     blueice_amd.inference.toy_mc_fits(lf, ...), .toy_test_statistics(lf, ...), .neyman_thresholds(lf, ...)
+    blueice_amd.sampler.sample_posterior(lf, ...), blueice_amd.inference.bestfit_emcee(lf, ...), blueice_amd.grid.grid_scan(lf, ...)
 
 This is the reference's `source_wise_interpolation` for the likelihood it exists for (blueice/likelihood.py:152-171, 210-240,
 534-563): every source keeps the pdf values of the events at the anchors of the shape parameters IT responds to only.
@@ -44,8 +45,16 @@ is a near-tie it is event for event the toy the expanded grid model draws.  They
 them `blueice_amd.inference.toy_mc_fits(lf, ...)`, `toy_test_statistics(lf, ...)` and `neyman_thresholds(lf, ...)` take the
 class, with chunks that run across hypothesis boundaries as for binned models.  The bound lf.simulate_toy* / lf.toy_* /
 lf.neyman_thresholds stay refused and name these spellings.
-Refused with NotImplementedError: compute_pdf / full_output, allow_negative sources, Beeston-Barlow, sampling and grid_scan, and
-everything that reads the dense store of a binned source-wise model.
+Posteriors and marginal likelihoods run on the event store as well, as functions that take the class:
+`blueice_amd.sampler.sample_posterior(lf, ...)` and `blueice_amd.inference.bestfit_emcee(lf, ...)` (bi_sample_stretch_sourcewise_events:
+the proposals planned on the device by the event variant of k_sourcewise_plan, the chain bit for bit the host engine's, no host wait
+inside the step loop, GaussianPrior constraints on the device) and `blueice_amd.grid.grid_scan(lf, ...)`
+(bi_grid_reduce_sourcewise_events, one work item per grid point); `datasets=` indexes the event sets of `set_datasets` or of
+`sourcewise_event_toys*`.  `likelihood_config['sourcewise_grid_route']` applies: 'auto' and 'points' are the per-point route, 'scan'
+raises -- the matrix-core scan route does not read the event store, and there is no `eval_points_scan` here.  The bound
+lf.sample_posterior / lf.bestfit_emcee / lf.grid_scan stay refused and name these spellings.
+Refused with NotImplementedError: compute_pdf / full_output, allow_negative sources, Beeston-Barlow, the bound sampling and grid_scan
+methods, and everything that reads the dense store of a binned source-wise model.
 """
 import numpy as np
 
@@ -60,8 +69,10 @@ _SCOPE = ("an unbinned source-wise model (SourceWiseUnbinnedLogLikelihood) has v
           "values_gradients_hessians, bestfit_minuit and inference.hesse; event toys drawn on the device are the functions "
           "sourcewise_event_toys(lf, n_toys, seed, **truth), sourcewise_event_toys_points(lf, points, n_toys, seed) and "
           "sourcewise_simulated_events(lf, t) of blueice_amd, and toy-calibrated inference is blueice_amd.inference.toy_mc_fits(lf, ...), "
-          "toy_test_statistics(lf, ...) and neyman_thresholds(lf, ...), not the bound methods; not sampling, gridded likelihoods, the "
-          "expected (Fisher) information, or anything that reads binned counts")
+          "toy_test_statistics(lf, ...) and neyman_thresholds(lf, ...), not the bound methods; posterior sampling and gridded "
+          "likelihoods are the functions blueice_amd.sampler.sample_posterior(lf, ...), blueice_amd.inference.bestfit_emcee(lf, ...) and "
+          "blueice_amd.grid.grid_scan(lf, ...), not the bound methods either; not the expected (Fisher) information, or anything that "
+          "reads binned counts")
 
 
 def _refused(name):
@@ -167,6 +178,15 @@ class SourceWiseUnbinnedLogLikelihood(_SourceWiseLikelihood):
             return np.concatenate(parts) if parts else np.zeros(0)
         self.ctx.set_event_rows([len(d) for d in datasets], rows, self.outlier_likelihood)
         self.last_scoring_route = 'host'
+
+    def _native_sample_stretch(self, *args, **kwargs):
+        """what blueice_amd.sampler.sample_posterior (and through it inference.bestfit_emcee) calls for this class in the place of
+        ctx.sample_stretch: the sampler on the event store (the bound sample_posterior / bestfit_emcee stay refused)"""
+        return self.ctx.sample_stretch_events(*args, **kwargs)
+
+    def _native_grid_reduce(self, *args, **kwargs):
+        """what blueice_amd.grid.grid_scan calls for this class in the place of ctx.grid_reduce (the bound grid_scan stays refused)"""
+        return self.ctx.grid_reduce_events(*args, **kwargs)
 
     def _simulate_toys_points(self, points, n_toys, seed=0, livetime_days=None):
         """what blueice_amd.inference's toy layers call for this class (the bound simulate_toys_points stays refused)"""

@@ -97,6 +97,14 @@ limit on one rate multiplier beside Wilks' (sourcewise_event_toys, inference.bes
 --measure-unbinned-toys times, at the measured source-wise shape, bi_sourcewise_simulate_event_toys (256 toys of 10^4 expected events,
 one toy of 10^6) against bi_simulate_event_toys on the expanded 5^4 grid model and against the host route, and the device time of
 the call's four parts; the lines go to profiles/sourcewise_event_toys_measure.txt too.
+
+--unbinned-posterior computes, instead of (2) - (6), the 90 % credible upper limit on the signal's multiplier of the EVENT model from a
+gridded likelihood (blueice_amd.grid.grid_scan on SourceWiseUnbinnedLogLikelihood: bi_grid_reduce_sourcewise_events), on the native and
+on the host engine, beside the same quantile of a chain (blueice_amd.sampler.sample_posterior: bi_sample_stretch_sourcewise_events).
+
+--measure-unbinned-grid and --measure-unbinned-sampler time, at the measured source-wise shape with 10^4 and 10^6 events,
+bi_grid_reduce_sourcewise_events and bi_sample_stretch_sourcewise_events (40 and 1024 walkers) against the host engines on the same
+event store; the lines go to profiles/sourcewise_events_scan_measure.txt and profiles/sourcewise_events_sampler_measure.txt too.
 """
 import argparse
 import time
@@ -130,6 +138,12 @@ ap.add_argument('--unbinned-toys', action='store_true',
                 help='draw and fit a small ensemble of event-level toys of the twelve-nuisance model: a toy-calibrated threshold beside Wilks\'')
 ap.add_argument('--measure-unbinned-toys', action='store_true',
                 help='time bi_sourcewise_simulate_event_toys against the expanded grid model\'s generator and the host route')
+ap.add_argument('--unbinned-posterior', action='store_true',
+                help='a credible upper limit on the signal multiplier of the event model from grid_scan, beside one from sample_posterior')
+ap.add_argument('--measure-unbinned-grid', action='store_true',
+                help='time bi_grid_reduce_sourcewise_events against the host engine on the same event store')
+ap.add_argument('--measure-unbinned-sampler', action='store_true',
+                help='time bi_sample_stretch_sourcewise_events against the host engine on the same event store')
 ap.add_argument('--band', action='store_true', help='the post-fit band of a projection and the impact table of a signal box')
 ap.add_argument('--asimov', action='store_true', help='the expected upper-limit band from the Asimov dataset, and from toys')
 ap.add_argument('--toys', type=int, default=200, help='toys of the goodness-of-fit p-value; a fifth as many per Neyman hypothesis')
@@ -1454,6 +1468,219 @@ def measure_unbinned_toys():
     tp.close()
 
 
+def unbinned_posterior():
+    """The 90 % credible upper limit on the signal's multiplier of the EVENT model from a gridded likelihood
+    (blueice_amd.grid.grid_scan on SourceWiseUnbinnedLogLikelihood: bi_grid_reduce_sourcewise_events, one work item per grid point),
+    marginalised over the signal's own nuisance parameter and two background multipliers with every other parameter fixed, beside
+    the same quantile of a chain over the same four parameters (blueice_amd.sampler.sample_posterior:
+    bi_sample_stretch_sourcewise_events, the proposals planned on the device)."""
+    from blueice_amd import GaussianPrior, SourceWiseUnbinnedLogLikelihood, grid, sampler
+    from blueice_amd.synthetic import NuisanceHistogramSource, many_nuisances_config
+    conf, names, own = many_nuisances_config(n_bins=(args.bins, args.bins), source_class=NuisanceHistogramSource)
+    lf = SourceWiseUnbinnedLogLikelihood(conf)
+    for s in range(4):
+        lf.add_rate_parameter('s%d' % s)
+    for n in names:
+        lf.add_shape_parameter(n, (-2., -1., 0., 1., 2.), log_prior=GaussianPrior(0., 1.))
+    lf.prepare()
+    np.random.seed(3)
+    d = lf.base_model.simulate()
+    lf.set_data(d[:max(len(d) // 8, 1)])
+    print('%d events scored on the %s: an event store of %.2f MB' % (lf.n_events_per_dataset[0], lf.last_scoring_route,
+                                                                    lf.ctx.get_param('sourcewise_events_bytes') / 1e6))
+    nuisance = own[0][0]                                          # the signal's first own parameter
+    keep = [('s0_rate_multiplier', np.linspace(0.0, 1.0, 65))]
+    reduce = [(nuisance, np.linspace(-2.0, 2.0, 33)), ('s1_rate_multiplier', np.linspace(0.02, 0.4, 25)),
+              ('s2_rate_multiplier', np.linspace(0.02, 0.4, 25))]
+    fixed = {n: 0.0 for n in names if n != nuisance}
+    fixed['s3_rate_multiplier'] = 0.125
+    results = {}
+    for engine in ('native', 'host'):
+        if engine == 'native':
+            grid.grid_scan(lf, keep=keep, reduce=reduce, engine=engine, **fixed)     # (warm: allocations)
+        t0 = time.perf_counter()
+        res = results[engine] = grid.grid_scan(lf, keep=keep, reduce=reduce, engine=engine, **fixed)
+        print('grid of %d x %d x %d x %d = %d points on the %s engine: %.3f s (%d chunks, %d launches, %d excluded points)'
+              % (len(keep[0][1]), 33, 25, 25, res.counters[1], res.engine, time.perf_counter() - t0, res.counters[0], res.counters[3], res.excluded))
+    rng = np.random.default_rng(1)
+    W, steps, burn = 32, 2000, 500
+    best = results['native']
+    k = int(np.argmax(best.profile))
+    at = dict([('s0_rate_multiplier', keep[0][1][k])] + [(n, float(best.best[n][k])) for n, _ in reduce])
+    order = ['s0_rate_multiplier', 's1_rate_multiplier', 's2_rate_multiplier', nuisance]      # rate multipliers first, then shape parameters
+    p0 = np.array([at[n] for n in order])[None, :] + 0.01 * rng.standard_normal((W, 4))
+    p0[:, :3] = np.abs(p0[:, :3])
+    t0 = time.perf_counter()
+    run = sampler.sample_posterior(lf, n_walkers=W, n_steps=steps, seed=4, p0=p0, **fixed)
+    assert run.names == order, run.names
+    s0 = run.flat(discard=burn)[:, 0]
+    print('chain over the same %d parameters: %d walkers x %d steps on the %s engine in %.3f s, acceptance %.3f, %d stream waits in the step loop'
+          % (len(run.names), W, steps, run.engine, time.perf_counter() - t0, run.acceptance_fraction.mean(), run.counters[4]))
+    print('90 % credible upper limit on s0_rate_multiplier (flat priors on the multipliers, the nuisance parameter\'s Gaussian constraint):')
+    print('    gridded likelihood, native engine  %.4f' % results['native'].credible_upper_limit(0.9))
+    print('    gridded likelihood, host engine    %.4f' % results['host'].credible_upper_limit(0.9))
+    print('    chain (posterior quantile)         %.4f   (%.1f %% of the chain inside the grid\'s range of the multiplier)'
+          % (np.quantile(s0, 0.9), 100 * np.mean(s0 <= keep[0][1][-1])))
+    lf.ctx.close()
+
+
+def measured_event_store(rng, N):
+    """the measured source-wise shape over N events -- d = 4, S = 4, one own axis per source (class <4, 1>: 8 rows per point), 5
+    anchors -- as a one-bin carrier of the geometry and the rates with random pdf values of order one uploaded row by row"""
+    from blueice_amd.source_wise import SourceWiseContext
+    d = S = 4
+    n_a = 5
+    g = np.linspace(-2., 2., n_a)
+    mus = (1 + np.arange(S))[:, None] * (1 + 0.02 * g[None, :])                   # relative rates (10 in all); the scale is per call
+    fac = SourceWiseContext(0)
+    fac.begin_model([g] * d, S, 1, [(s,) for s in range(S)])
+    for s in range(S):
+        for a in range(n_a):
+            fac.set_anchor(s, a, np.ones(1), mus[s, a])
+    fac.end_model()
+    values = rng.random((S, n_a, N)) + 0.05
+    fac.set_event_rows([N], lambda s, local: values[s, local], 1e-12)
+    return fac, d, S, n_a
+
+
+def alternated(calls, rounds, warm=2):
+    times = {name: [] for name, _ in calls}
+    for rnd in range(warm + rounds):
+        for name, call in calls:
+            t0 = time.perf_counter()
+            call()
+            if rnd >= warm:
+                times[name].append(time.perf_counter() - t0)
+    return times
+
+
+def measure_unbinned_grid():
+    """The gridded likelihood on the event store at the measured shape: bi_grid_reduce_sourcewise_events (one work item per grid
+    point, nothing read by the host per chunk) against the host engine (blueice_amd.grid._host_engine over a likelihood whose
+    eval_points is bi_eval_factored on the same store, reduced by reduce_cells) on the same grid, at 10^4 and 10^6 events.
+    Alternated calls, medians with quartiles, host clock around calls that end in a stream synchronisation.  There is no scan
+    route over events.  Written to profiles/sourcewise_events_scan_measure.txt as well."""
+    import os
+    from blueice_amd import grid
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    rng = np.random.default_rng(11)
+    first = True
+    for events, nodes in ((1e4, [np.linspace(0.5, 1.5, 33), np.linspace(-1.9, 1.9, 65), np.linspace(-1.9, 1.9, 65), np.linspace(0.8, 1.2, 7)]),
+                          (1e6, [np.linspace(0.5, 1.5, 33), np.linspace(-1.9, 1.9, 17), np.linspace(-1.9, 1.9, 17), np.linspace(0.8, 1.2, 7)])):
+        N = int(events)
+        fac, d, S, n_a = measured_event_store(rng, N)
+        if first:
+            say('# examples/many_nuisances.py --measure-unbinned-grid --rounds %d on %s' % (args.rounds, fac.info()['arch']))
+            say('# d = %d, S = %d, one own axis per source (class <4, 1>: 8 rows per point), %d anchors, one event set; every other class: '
+                'not measured.  The store (20 rows x N doubles) fits the Infinity Cache at both sizes: every number below is cache-assisted'
+                % (d, S, n_a))
+            first = False
+        scale = events / 10.0
+        names = ['r0', 'z0', 'z1', 'r1']
+        kind, index = np.array([1, 0, 0, 1], dtype=np.int32), np.array([0, 0, 1, 1], dtype=np.int32)
+        z0, scale0, unit = np.zeros((1, d)), np.full((1, S), scale), np.full((1, S), scale)
+        G = int(np.prod([len(v) for v in nodes]))
+        logw = [np.zeros(len(nodes[0]))] + [np.log(grid.trapezoid_weights(v)) for v in nodes[1:]]
+
+        class HostLikelihood:
+            """what _host_engine asks of a likelihood: eval_points over the axes' columns, through bi_eval_factored"""
+            def eval_points(self, call, livetime_days=None):
+                P = len(call['r0'])
+                z, r = np.zeros((P, d)), np.full((P, S), scale)
+                z[:, 0], z[:, 1], r[:, 0], r[:, 1] = call['z0'], call['z1'], scale * call['r0'], scale * call['r1']
+                return fac.eval(z, r)[0]
+
+        axes = list(zip(names, nodes))
+        native = lambda: fac.grid_reduce_events(kind, index, z0, scale0, unit, None, 1, nodes, logw=logw, route=0)
+        host = lambda: grid._host_engine(HostLikelihood(), axes, 1, logw[1:], None, None, None, {})
+        a, h = native(), host()
+        say('%.0e events, grid of %s = %d points, 16 cell tuples: route points %d chunk(s), %d launches; max |log_marginal difference| native - host '
+            '%.2e, argmax equal: %s' % (events, ' x '.join(str(len(v)) for v in nodes), G, a[3][0], a[3][3], np.max(np.abs(a[0].ravel() - h[0])),
+                                        np.array_equal(a[2].ravel(), h[2])))
+        rounds = max(3, args.rounds // 8)
+        t = alternated([('native', native), ('host', host)], rounds, warm=1)
+        for name, what in (('native', 'bi_grid_reduce_sourcewise_events route points'), ('host', 'host engine, bi_eval_factored per 65 536 points')):
+            say('    %-48s %s   %.3f M points/s' % (what, quartiles(t[name]), G / np.median(t[name]) / 1e6))
+        say('    ratio host / native %.2f' % (np.median(t['host']) / np.median(t['native'])))
+        fac.close()
+    say('# not measured: a scan route over events (none exists: route 1 is refused), the 10^6-point grid at 10^6 events (the grid there is '
+        '33 x 17 x 17 x 7), blueice_amd.grid.grid_scan through the likelihood class, every class but <4, 1>, several event sets')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_events_scan_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+
+
+def measure_unbinned_sampler():
+    """The ensemble sampler on the event store at the measured shape: bi_sample_stretch_sourcewise_events (propose, the planner's
+    event variant, k_sourcewise_events, finish and accept queued on one stream) against the host engine of blueice_amd.sampler -- the
+    same move in NumPy, one bi_eval_factored call per half-step -- at 40 and 1024 walkers for 50 steps, 10^4 and 10^6 events.
+    Alternated calls, medians with quartiles.  Written to profiles/sourcewise_events_sampler_measure.txt as well."""
+    import os
+    from blueice_amd import sampler
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    rng = np.random.default_rng(11)
+    steps = 50
+    first = True
+    for events in (1e4, 1e6):
+        fac, d, S, n_a = measured_event_store(rng, int(events))
+        if first:
+            say('# examples/many_nuisances.py --measure-unbinned-sampler --rounds %d on %s' % (args.rounds, fac.info()['arch']))
+            say('# d = %d, S = %d, one own axis per source (class <4, 1>), %d anchors, one event set; every other class: not measured.  The store '
+                '(20 rows x N doubles) fits the Infinity Cache at both sizes: every number below is cache-assisted' % (d, S, n_a))
+            first = False
+        scale = events / 10.0
+        kind = np.array([1] * S + [0] * d, dtype=np.int32)
+        index = np.array(list(range(S)) + list(range(d)), dtype=np.int32)
+        names = ['r%d' % s for s in range(S)] + ['z%d' % i for i in range(d)]
+        lo, hi = np.array([0.] * S + [-2.] * d), np.array([np.inf] * S + [2.] * d)
+        z0, one, unit = np.zeros(d), np.full(S, scale), np.full(S, scale)
+
+        class HostLikelihood:
+            """what _host_engine asks of a likelihood: eval_points over the variables' columns, through bi_eval_factored"""
+            def eval_points(self, call, livetime_days=None):
+                return fac.eval(np.stack([call[n] for n in names[S:]], axis=1), scale * np.stack([call[n] for n in names[:S]], axis=1))[0]
+
+        for W in (40, 1024):
+            x0 = np.concatenate([rng.uniform(0.99, 1.01, (W, S)), rng.uniform(-0.1, 0.1, (W, d))], axis=1)[None]
+            native = lambda: fac.sample_stretch_events(W, kind, index, z0, one, unit, None, x0, lo, hi, steps, seed=7)
+            host = lambda: sampler._host_engine(HostLikelihood(), names, {}, None, None, x0.copy(), lo, hi, steps, 2.0, 7, 0)
+            a, b = native(), host()
+            say('%.0e events, W = %4d, %d steps: counters of the device loop %s (half-steps, evaluations, accepted, launches, stream waits in the '
+                'loop); accepted on the host %d; %.1f %% of the chain entries equal bit for bit'
+                % (events, W, steps, [int(v) for v in a[3]], b[3][2], 100 * np.mean(a[0] == b[0])))
+            rounds = args.rounds if events * W < 1e8 else max(3, args.rounds // 8)
+            t = alternated([('native', native), ('host', host)], rounds, warm=1)
+            for name, what in (('native', 'bi_sample_stretch_sourcewise_events'), ('host', 'host engine, bi_eval_factored per half-step')):
+                say('%.0e events, W = %4d, %d steps, %-46s %s per call, %.1f us per half-step'
+                    % (events, W, steps, what, quartiles(t[name]), np.median(t[name]) * 1e6 / (2 * steps)))
+            say('%.0e events, W = %4d: ratio host / native %.2f' % (events, W, np.median(t['host']) / np.median(t['native'])))
+        fac.close()
+    say('# not measured: blueice_amd.sampler.sample_posterior through the likelihood class, constraint terms, several ensembles, every class '
+        'but <4, 1>')
+    out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'sourcewise_events_sampler_measure.txt')
+    with open(out, 'w') as fh:
+        fh.write('\n'.join(lines) + '\n')
+
+
+if args.unbinned_posterior:
+    unbinned_posterior()
+    raise SystemExit(0)
+if args.measure_unbinned_grid:
+    measure_unbinned_grid()
+    raise SystemExit(0)
+if args.measure_unbinned_sampler:
+    measure_unbinned_sampler()
+    raise SystemExit(0)
 if args.unbinned_toys:
     unbinned_toys()
     raise SystemExit(0)

@@ -930,6 +930,39 @@ int bi_sourcewise_download_events(bi_ctx* ctx, double* coords, int32_t* source);
 int bi_eval_sourcewise_events_hess(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset, double* ll,
                                    double* grad, double* hess, int32_t* status);
 
+/* ... and the loops over staged points on the event store: the device planner, the ensemble sampler and the gridded likelihood
+ * of the binned model (bi_eval_sourcewise_planned, bi_sample_stretch_sourcewise, bi_grid_reduce_sourcewise, which keep refusing
+ * while a store exists) under names of their own, signatures equal to theirs.  The planner's event variant writes per point the
+ * descriptors bi_eval_factored fills on the host for the store, bit for bit -- rows at the point's set's columns, the set's
+ * number of events and tiles, sum_s r_s (sources ascending from 0.0, one rounded addition each) for the finish -- from a device
+ * table of the sets uploaded when the store is finished; a rejected point gets zero tiles, so every block of its item returns at
+ * entry and the event kernel (k_sourcewise_events, values only) runs the code it ran.  The grid's x is the most blocks any set of
+ * the store takes, known on the host: nothing is read and nothing waited for.
+ *   bi_eval_sourcewise_events_planned     ll [P] and status [P] (or NULL) bit for bit bi_eval_factored's on the store, values only
+ *   bi_sample_stretch_sourcewise_events   bi_sample_stretch_sourcewise's contract and counters [5] with the store's likelihood as the
+ *                                         log density: chain, ll and n_accepted are bit for bit those of the same move with one
+ *                                         bi_eval_factored call per half-step; counters[4] (synchronisations in the step loop) = 0
+ *   bi_grid_reduce_sourcewise_events      bi_grid_reduce_sourcewise's contract and counters [5] on route 0; with one chunk the outputs
+ *                                         are bit for bit the reduction of bi_eval_sourcewise_events_planned's values.  route -1
+ *                                         takes route 0; route 1 is refused with BI_ERR_INVALID: the matrix-core scan route
+ *                                         does not read the event store
+ * `dataset` indexes the event sets: an index outside [0, T) is BI_ST_BAD_DATASET in the planned call and BI_ERR_INVALID in the
+ * other two, as for the binned calls.  All three need a finished event store: without one (or with an open one) BI_ERR_STATE,
+ * naming the binned spelling. */
+int bi_eval_sourcewise_events_planned(bi_ctx* ctx, int64_t P, const double* z, const double* rate_scale, const int64_t* dataset,
+                                      double* ll, int32_t* status);
+int bi_sample_stretch_sourcewise_events(bi_ctx* ctx, int64_t E, int W, int F, const int32_t* var_kind, const int32_t* var_index,
+                                        const double* z0, const double* scale0, const double* unit, const int64_t* dataset,
+                                        const double* x0, const double* lo, const double* hi, int64_t n_steps, double a, uint64_t seed,
+                                        int64_t first_ensemble, const double* prior_mean, const double* prior_sigma,
+                                        const double* prior_const, double* chain, double* ll, int64_t* n_accepted, int64_t* counters);
+int bi_grid_reduce_sourcewise_events(bi_ctx* ctx, int64_t E, const int64_t* dataset /*[E] or NULL*/, int F, int n_keep,
+                                     const int32_t* var_kind, const int32_t* var_index, const double* z0 /*[E][d]*/,
+                                     const double* scale0 /*[E][S]*/, const double* unit /*[E][S]*/, const int32_t* n_nodes /*[F]*/,
+                                     const double* nodes, const double* term, const double* logw, int64_t chunk, int route,
+                                     double* log_marginal /*[E][K]*/, double* profile /*[E][K]*/, int64_t* argmax /*[E][K]*/,
+                                     int64_t* counters /*[5] or NULL*/);
+
 /* The likelihood on a tensor-product grid, reduced over some of its axes on the device: F variables (described as for
  * bi_fit_batched: var_kind / var_index, each parameter at most once), variable j with n_nodes[j] values nodes_j (`nodes`: the F
  * lists one after the other; any order, finite).  The first n_keep variables are kept, the others reduced:
